@@ -8,7 +8,9 @@ loop does) and re-encoded (AC3_encode_frame) in ONE ac3mi_transcode_batch call, 
 (decoder overlap 0 / dither seed 1, encoder history 0 / csnroffst 40: BASELINE's definition of configs[2] / [4]); frames
 in and frames out resident in HBM.  One "step" = state reset + one such call; `value` = frames of all ranks / wall time.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  --dump-outputs: what the last timed step handed back (re-encoded frames, status, the updated stream state) for a fixed
+  seeded sample of 2048 streams, as float32 / float64 DIR/<name>.npy (~30 MB), to compare two builds output for output.
   N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
   (RANK / LOCAL_RANK / WORLD_SIZE in the environment), or started plainly, in which case this process only
   spawns N child ranks of itself (before touching the GPU), one per device, and relays rank 0's line.
@@ -296,6 +298,25 @@ class Content:
     def transcode(self):
         self.eng.transcode_batch(self.dec, self.enc, self.frames, self.delay2, self.lfsr2, self.chmap, self.last2, self.csnr2,
                                  out=self.frames2, status=self.status_tc, wait_torch=False)
+
+    def transcode_outputs(self, n=2048, seed=2024):
+        """What the last transcode call handed its caller, for a fixed seeded sample of n streams (all of them when the batch
+        is smaller), as host float arrays: the re-encoded frames, the per-frame status and the stream state the call updated
+        in place.  Call after the engine's stream has drained."""
+        import numpy as np
+        import torch
+        idx = np.sort(np.random.default_rng(seed).choice(self.S, size=min(n, self.S), replace=False))
+        t = torch.from_numpy(idx).to(self.frames2.device)
+
+        def pick(a, dtype):
+            return a.index_select(0, t).cpu().numpy().astype(dtype)
+        return {"stream_index": idx.astype(np.float64),
+                "frames": pick(self.frames2, np.float32)[:, :, :self.fb],      # AC-3 bytes (the output rows are padded to 4)
+                "status": pick(self.status_tc, np.float64),
+                "delay": pick(self.delay2, np.float32),
+                "lfsr": pick(self.lfsr2, np.float32),
+                "last_samples": pick(self.last2, np.float32),
+                "csnroffst": pick(self.csnr2, np.float64)}
 
 
 def secondary_timings(pkg, eng, dev, C, rank, dist, barrier, steps=20, checks=True, warm=True):
@@ -644,7 +665,9 @@ def launch_check(job_streams=0):
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(backend="gloo")
-        dist.barrier()
+        # gloo's own CPU barrier: dist.barrier() looks for an accelerator first, which starts the HIP runtime and opens
+        # the GPU in every rank
+        dist.monitored_barrier()
     lo, hi = sh.shard(job_streams or FRAMES_PER_GPU * world, world, rank)
     plan = sh.plan_transcode_bytes(hi - lo)
     tmax, pmax = sh.reduce_max([0.001 * (rank + 1), float(plan["total"])], dist if world > 1 else None)
@@ -680,7 +703,12 @@ def main():
     ap.add_argument("--no-warm", action="store_true", help="skip the warm (state carried on) passes of the encode / transcode legs (PMC runs)")
     ap.add_argument("--launch-check", action="store_true", help="N-rank rendezvous and reductions only (gloo, no GPU)")
     ap.add_argument("--job-streams", type=int, default=0, help="--launch-check: streams of the whole job (default 65536 per rank)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0, a seeded sample of 2048 streams) "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -742,6 +770,7 @@ def main():
         step()
     barrier()
     dt_own = time.perf_counter() - t0
+    dumped = C.transcode_outputs() if args.dump_outputs and rank == 0 else None     # untimed; before anything reruns the call
     dt = dt_own
     per_rank = [S * args.steps / dt_own]
     if dist is not None:
@@ -923,6 +952,13 @@ def main():
                 extra["transform_imdct512"]["cpu_baseline"] = cpu_baseline()
         else:
             line["cpu_baseline"] = None
+        if dumped is not None:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+            line["dump_outputs"] = {"dir": args.dump_outputs, "streams": int(dumped["stream_index"].size),
+                                    "arrays": sorted(dumped)}
         print(json.dumps(line), flush=True)
 
     eng.close()

@@ -1,11 +1,14 @@
 """Shared test plumbing: package import, oracle (liborc.so) and reference-build
-(oracle/_ref/liba52_ref.so) bindings, seeded synthetic inputs.
+(oracle/_ref/liba52_ref.so) bindings, liba52's stored sweep results, seeded synthetic inputs.
 
 The oracle is TEST INFRASTRUCTURE: only tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg import this module.
 """
+import atexit
 import ctypes
+import hashlib
 import importlib
+import json
 import os
 import subprocess
 
@@ -234,6 +237,69 @@ def orc_decode(frames, flags=7 | 16, level=1.0, bias=0.0, dynrng_off=False):
 
 def ref_decode(frames, flags=7 | 16, level=1.0, bias=0.0, dynrng_off=False):
     return _decode_stream(ref(), "a52_", frames, flags, level, bias, dynrng_off)
+
+
+# ---------------------------------------------------------------------------
+# the real liba52's results on the seeded sweeps, stored for machines without oracle/_ref
+
+LIBA52_RECORDS = os.path.join(GOLDEN, "liba52_records.json")
+_records = None
+
+
+def fingerprint(*parts):
+    """Bit-exact fingerprint (sha256, 128 bits kept) of arrays (dtype, shape and bytes) and plain values."""
+    h = hashlib.sha256()
+    for p in parts:
+        if isinstance(p, np.ndarray):
+            a = np.ascontiguousarray(p)
+            h.update(("%s%r" % (a.dtype.str, a.shape)).encode())
+            h.update(a.tobytes())
+        else:
+            h.update(repr(p).encode())
+        h.update(b"|")
+    return h.hexdigest()[:32]
+
+
+def _save_records():
+    with open(LIBA52_RECORDS, "w") as f:
+        json.dump(_records, f, indent=0, sort_keys=True)
+        f.write("\n")
+
+
+def liba52_record(key, live):
+    """The real liba52's result for one sweep case, as a JSON value.  Where oracle/_ref exists it is computed by live()
+    and must equal the one stored in tests/golden/liba52_records.json; elsewhere the stored one stands in for it.
+    With oracle/_ref and AC3MI_RECORD_LIBA52=1 the computed results are written to that file instead (at exit)."""
+    global _records
+    recording = os.environ.get("AC3MI_RECORD_LIBA52") == "1"
+    if _records is None:
+        _records = {}
+        if os.path.exists(LIBA52_RECORDS):
+            with open(LIBA52_RECORDS) as f:
+                _records = json.load(f)
+        if recording:
+            atexit.register(_save_records)
+    if have_ref():
+        rec = json.loads(json.dumps(live()))
+        if recording:
+            _records[key] = rec
+        else:
+            assert _records.get(key) == rec, "liba52 gives %r for case %s, %s holds %r" % (
+                rec, key, os.path.basename(LIBA52_RECORDS), _records.get(key))
+        return rec
+    assert key in _records, "case %s has no stored liba52 result in %s" % (key, os.path.basename(LIBA52_RECORDS))
+    return _records[key]
+
+
+def decode_record(pcm, errs, flags):
+    """[fingerprint of the PCM's bits, summed return codes, output flags] of a decoded stream."""
+    return [fingerprint(np.ascontiguousarray(pcm, np.float32).view(np.uint32)), int(errs), int(flags)]
+
+
+def ref_decode_record(frames, flags=7 | 16, level=1.0, bias=0.0, dynrng_off=False):
+    """decode_record of the real liba52's decode of one stream (computed, or stored: liba52_record)."""
+    key = "decode:" + fingerprint(np.ascontiguousarray(frames, np.uint8), int(flags), float(level), float(bias), bool(dynrng_off))
+    return liba52_record(key, lambda: decode_record(*ref_decode(frames, flags, level, bias, dynrng_off)))
 
 
 def orc_xform(coef, blksw, acmod, lfeon, output, bias=0.0, clev=0.0, slev=0.0, state=None):

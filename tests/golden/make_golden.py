@@ -9,14 +9,21 @@ What is pinned and by what:
   downmix.npz    REAL a52_downmix_init / a52_downmix_coeff / a52_downmix / a52_upmix results
   encoder.npz    our encoder oracle's own output and stage dumps (regression pin only: PARITY UNPINNED
                  against ac3enc, see oracle/ac3enc_oracle.c)
+  a52dec_drivers.npz   tests/test_tools_gpu.py's streams through the reference's own liba52 + libao file drivers
+                 (oracle/_ref/a52dec_ref): WAV and float output   (`--only a52dec_drivers` regenerates just this file)
   ac3tab.npz     the REAL encoder's constant tables (src/ac3enc/ac3tab.h:3-171 compiled unmodified behind
                  oracle/ref_ac3tab_glue.cpp): ac3_window, latab, hth, baptab, sdecaytab ... fgaintab, bndsz,
                  ac3_freqs, ac3_bitratetab   (`make_golden.py --only ac3tab` regenerates just this file)
+  liba52_records.json   not written here: fingerprints of what the REAL liba52 gives on the seeded sweeps of
+                 tests/test_oracle_vs_ref.py, test_oracle_encoder.py, test_mixlevel_switch.py, test_packer_streams.py
+                 (tests/_harness.liba52_record); the tests write it themselves with oracle/_ref present:
+                 AC3MI_RECORD_LIBA52=1 python -m pytest tests -m "not gpu"
 Fixtures are data (inputs + expected outputs); no reference source text is stored.
 """
 import ctypes
 import os
 import sys
+import tempfile
 
 import numpy as np
 
@@ -77,6 +84,23 @@ def make_ac3tab():
     print("ac3tab.npz", os.path.getsize(os.path.join(OUT, "ac3tab.npz")), {k: v.shape for k, v in d.items()})
 
 
+def make_a52dec_drivers():
+    from tests import test_tools_gpu as T
+    assert os.path.exists(T.REF_TOOL), "oracle/_ref/a52dec_ref missing: run `make -C oracle` in the build container"
+    d, paths = {}, {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for key, data in T.make_streams().items():
+            d["stream_" + key] = np.frombuffer(data, np.uint8)
+            paths[key] = os.path.join(tmp, key + ".ac3")
+            with open(paths[key], "wb") as f:
+                f.write(data)
+        runs = [(mode, key, {}) for mode, key in T.WAV_CASES] + [("float", "51", opts) for _, opts in T.FLOAT_CASES]
+        for mode, key, opts in runs:
+            d[T.ref_driver_name(mode, key, **opts)] = np.frombuffer(T.run_ref_tool(mode, paths[key], **opts), np.uint8)
+    np.savez_compressed(os.path.join(OUT, "a52dec_drivers.npz"), **d)
+    print("a52dec_drivers.npz", os.path.getsize(os.path.join(OUT, "a52dec_drivers.npz")), sorted(d))
+
+
 MIXFLIP = (("a7_st", 7, 2, (1, 1, 2, 2, 0, 0, 2, 1), 0.0), ("a7_mono", 7, 1, (0, 2, 2, 1, 2, 0), 0.0), ("a7_dolby", 7, 10, (3, 2, 0, 2, 2, 1), 0.0),
            ("a6_st", 6, 2, (1, 2, 2, 0, 2, 1), 0.0), ("a5_st", 5, 2, (0, 2, 1, 2, 2, 3), 0.0), ("a4_mono", 4, 1, (1, 2, 0, 2, 2, 1), 0.0),
            # at bias 384 (what the ACM driver decodes at): 2/x -> stereo and 3/x -> 3F lose the bias in blocks of mixed block sizes
@@ -107,6 +131,9 @@ def main():
         return
     if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "ac3tab":
         make_ac3tab()
+        return
+    if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "a52dec_drivers":
+        make_a52dec_drivers()
         return
     make_ac3tab()
     assert H.have_ref(), "oracle/_ref/liba52_ref.so missing: run `make -C oracle` in the build container"
@@ -225,6 +252,7 @@ def main():
         d["args_" + tag] = np.array([flags, oflags], np.int32)
     np.savez_compressed(os.path.join(OUT, "packer.npz"), **d)
     make_mixflip()
+    make_a52dec_drivers()
 
     for fn in sorted(os.listdir(OUT)):
         if fn.endswith(".npz"):

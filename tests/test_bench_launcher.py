@@ -62,3 +62,32 @@ def test_two_rank_line_carries_every_ranks_rate_and_the_cpu_baseline():
     assert abs(d["value"] - 2 * 2048 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
     assert d["all_frames_ok"] and d["cpu_baseline"] and d["cpu_baseline"]["value"] > 0
     assert d["roofline"]["hbm"]["frac"] > 0
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_the_last_steps_results(tmp_path):
+    """--dump-outputs DIR: what the timed transcode handed back in its last step, for a seeded sample of the streams, as
+    float32 / float64 .npy files of 64 MB at most.  Every step starts from fresh stream state, so two runs with different
+    step counts must dump the same arrays; the frames must be valid AC-3 (both CRCs) and the decode status clean."""
+    import numpy as np
+    import bench
+    dumps = []
+    for steps in (2, 3):
+        out = tmp_path / ("s%d" % steps)
+        d = _run(["--gpus", "1", "--steps", str(steps), "--warmup", "1", "--frames", "4096", "--no-extra", "--no-cpu-baseline",
+                  "--dump-outputs", str(out)], env_extra={"AC3MI_BENCH_MILLION": "0"})
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["all_frames_ok"]
+        assert d["dump_outputs"]["streams"] == 2048
+        dumps.append({n: np.load(str(out / (n + ".npy"))) for n in d["dump_outputs"]["arrays"]})
+    a, b = dumps
+    assert sorted(a) == ["csnroffst", "delay", "frames", "last_samples", "lfsr", "status", "stream_index"]
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+    idx = a["stream_index"]
+    assert idx.size == 2048 and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 4096
+    frames = a["frames"].reshape(2048, -1)
+    assert np.array_equal(frames, np.round(frames)) and frames.min() >= 0 and frames.max() <= 255
+    assert bench.ac3_crc_ok(frames.astype(np.uint8)) == 0
+    assert (a["status"].astype(np.int64) & 0x1ff).max() == 0

@@ -1,6 +1,7 @@
-"""CPU, build container only: the oracle against the REAL liba52 (oracle/_ref/liba52_ref.so) on
-fresh seeded inputs - broader than the committed fixtures.  Skipped where /root/reference was not
-available to build _ref (the prebuilt binary does travel to the GPU box)."""
+"""CPU: the oracle against the REAL liba52 (oracle/_ref/liba52_ref.so) on fresh seeded inputs - broader than the
+committed fixtures.  Where oracle/_ref was not built, the decode and transform sweeps compare against liba52's results
+stored in tests/golden/liba52_records.json (H.liba52_record); the two corrupt-frame tests follow liba52's parse step by
+step and need the library itself."""
 import ctypes
 
 import numpy as np
@@ -8,7 +9,7 @@ import pytest
 
 from tests import _harness as H
 
-pytestmark = pytest.mark.skipif(not H.have_ref(), reason="oracle/_ref/liba52_ref.so not built")
+needs_ref = pytest.mark.skipif(not H.have_ref(), reason="oracle/_ref/liba52_ref.so not built")
 
 
 def _bits(a):
@@ -24,19 +25,19 @@ def test_decode_matches_liba52_bit_for_bit(kind, nch, bitrate):
     frames = H.orc_encode(pcm, nch=nch, bitrate=bitrate, chmap=chmap)
     for flags, level, bias in ((7 | 16, 1.0, 0.0), (2, 1.0, 0.0), (2 | 32, 0.7, 384.0), (10 | 32, 1.0, 0.0),
                                (1, 1.0, 0.0), (6 | 16 | 32, 1.0, 0.0), (3 | 32, 1.0, 0.0)):
-        a, ea, fa = H.ref_decode(frames, flags, level, bias)
-        b, eb, fb = H.orc_decode(frames, flags, level, bias)
-        assert ea == 0 and eb == 0 and fa == fb
-        assert np.array_equal(_bits(a), _bits(b)), (kind, nch, flags)
+        want = H.ref_decode_record(frames, flags, level, bias)
+        got = H.decode_record(*H.orc_decode(frames, flags, level, bias))
+        assert want[1] == 0 and got[1] == 0 and got[2] == want[2]
+        assert got == want, (kind, nch, flags)
 
 
 def test_dynrng_off_matches():
     frames = H.orc_encode(H.gen_pcm(4, 6, seed=3, kind="tones"))
-    a, _, _ = H.ref_decode(frames, 2, 1.0, 0.0, dynrng_off=True)
-    b, _, _ = H.orc_decode(frames, 2, 1.0, 0.0, dynrng_off=True)
-    assert np.array_equal(_bits(a), _bits(b))
+    want = H.ref_decode_record(frames, 2, 1.0, 0.0, dynrng_off=True)
+    assert H.decode_record(*H.orc_decode(frames, 2, 1.0, 0.0, dynrng_off=True))[0] == want[0]
 
 
+@needs_ref
 def test_corrupt_frames_same_return_codes():
     """Flip bits: a52_syncinfo / a52_frame / a52_block must agree on every return code and, where both
     succeed, on the output."""
@@ -80,19 +81,31 @@ def test_corrupt_frames_same_return_codes():
 
 def test_imdct_random_bit_exact():
     rng = np.random.default_rng(11)
-    R, L = H.ref(), H.orc()
-    d1 = (rng.standard_normal(256) * 0.2).astype(np.float32)
-    d2 = d1.copy()
+    d0 = (rng.standard_normal(256) * 0.2).astype(np.float32)
+    steps = []
     for i in range(200):
         x = (rng.standard_normal(256) * 0.2).astype(np.float32)
-        a, b = x.copy(), x.copy()
         short = rng.random() < 0.4
-        bias = float(rng.choice([0.0, 384.0, 0.5]))
-        (R.a52_imdct_256 if short else R.a52_imdct_512)(H.P(a, H.fp), H.P(d1, H.fp), bias)
-        (L.orc_imdct_256 if short else L.orc_imdct_512)(H.P(b, H.fp), H.P(d2, H.fp), bias)
-        assert np.array_equal(_bits(a), _bits(b)) and np.array_equal(_bits(d1), _bits(d2))
+        steps.append((x, short, float(rng.choice([0.0, 384.0, 0.5]))))
+
+    def run(imdct_512, imdct_256):
+        """one fingerprint of (output, delay) per step, the delay carried from step to step"""
+        d, out = d0.copy(), []
+        for x, short, bias in steps:
+            a = x.copy()
+            (imdct_256 if short else imdct_512)(H.P(a, H.fp), H.P(d, H.fp), bias)
+            out.append(H.fingerprint(_bits(a), _bits(d)))
+        return out
+    L = H.orc()
+    want = H.liba52_record("imdct:" + H.fingerprint(d0, *[v for s in steps for v in s]),
+                           lambda: run(H.ref().a52_imdct_512, H.ref().a52_imdct_256))
+    got = run(L.orc_imdct_512, L.orc_imdct_256)
+    assert len(got) == len(want) == 200
+    bad = [i for i in range(200) if got[i] != want[i]]
+    assert not bad, "first differing step %d" % bad[0]
 
 
+@needs_ref
 @pytest.mark.parametrize("acmod,lfe,seed", [(7, 1, 31), (2, 0, 39597), (3, 1, 33), (0, 0, 34)])
 def test_damaged_packer_frames_same_samples(acmod, lfe, seed):
     """The damaged frames of tests/fuzz_corrupt.py (packer frames with coupling, rematrixing, block switching, delta bit

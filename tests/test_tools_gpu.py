@@ -1,7 +1,8 @@
 """GPU: tools/ac3mi_dec (a52dec-like file decoder on libac3mi.so) against the reference's own
-liba52 + libao file drivers (oracle/_ref/a52dec_ref, built by oracle/Makefile from the reference sources; the
-binary travels to the GPU box, the sources do not).  WAV headers must be identical byte for byte; s16 samples may
-differ by one step (the float PCM may differ by one float32 ulp at bias 384); float output within 1e-6 RMS."""
+liba52 + libao file drivers (oracle/_ref/a52dec_ref, built by oracle/Makefile from the reference sources), or, where
+that was not built, against their output stored in tests/golden/a52dec_drivers.npz (generator: make_golden.py).  WAV
+headers must be identical byte for byte; s16 samples may differ by one step (the float PCM may differ by one float32
+ulp at bias 384); float output within 1e-6 RMS."""
 import os
 import subprocess
 
@@ -13,6 +14,9 @@ from tests import _harness as H
 pytestmark = pytest.mark.gpu
 
 REF_TOOL = os.path.join(H.ORACLE_DIR, "_ref", "a52dec_ref")
+DRIVERS = os.path.join(H.GOLDEN, "a52dec_drivers.npz")
+WAV_CASES = [("wav", "51"), ("wavdolby", "51"), ("wav6", "51"), ("wav6", "20"), ("wav6", "30"), ("wav", "20")]
+FLOAT_CASES = [([], {}), (["-r"], {"no_dynrng": 1}), (["-a"], {"no_adjust": 1}), (["-g", "-6"], {"gain_db": -6.0})]
 
 
 @pytest.fixture(scope="module")
@@ -21,19 +25,25 @@ def tool():
     return os.path.join(H.ROOT, "tools", "ac3mi_dec")
 
 
+def make_streams():
+    """the test streams' bytes: 5.1, 2/0 and 3/0"""
+    out = {}
+    fr = H.orc_encode(H.gen_pcm(4, 6, seed=3, kind="tones"))
+    out["51"] = b"\x12\x34\x0b\x76" * 5 + fr.tobytes()          # junk first: resync
+    fr = H.orc_encode(H.gen_pcm(3, 2, seed=4, kind="music"), nch=2, bitrate=192000, chmap=(0, 1))
+    out["20"] = fr.tobytes()
+    fr = H.orc_encode(H.gen_pcm(3, 3, seed=5, kind="tones"), nch=3, bitrate=256000, chmap=(0, 2, 1))
+    out["30"] = fr.tobytes()
+    return out
+
+
 @pytest.fixture(scope="module")
 def streams(tmp_path_factory):
     d = tmp_path_factory.mktemp("tools")
     out = {}
-    fr = H.orc_encode(H.gen_pcm(4, 6, seed=3, kind="tones"))
-    (d / "51.ac3").write_bytes(b"\x12\x34\x0b\x76" * 5 + fr.tobytes())          # junk first: resync
-    out["51"] = str(d / "51.ac3")
-    fr = H.orc_encode(H.gen_pcm(3, 2, seed=4, kind="music"), nch=2, bitrate=192000, chmap=(0, 1))
-    (d / "20.ac3").write_bytes(fr.tobytes())
-    out["20"] = str(d / "20.ac3")
-    fr = H.orc_encode(H.gen_pcm(3, 3, seed=5, kind="tones"), nch=3, bitrate=256000, chmap=(0, 2, 1))
-    (d / "30.ac3").write_bytes(fr.tobytes())
-    out["30"] = str(d / "30.ac3")
+    for key, data in make_streams().items():
+        (d / (key + ".ac3")).write_bytes(data)
+        out[key] = str(d / (key + ".ac3"))
     return out
 
 
@@ -44,16 +54,30 @@ def _run(tool, args, path):
     return r.stdout
 
 
-def _ref(mode, path, no_dynrng=0, no_adjust=0, gain_db=0.0):
-    if not os.path.exists(REF_TOOL):
-        pytest.skip("oracle/_ref/a52dec_ref not built (needs /root/reference at build time)")
+def ref_driver_name(mode, key, no_dynrng=0, no_adjust=0, gain_db=0.0):
+    return "%s_%s_r%d_a%d_g%g" % (mode, key, no_dynrng, no_adjust, gain_db)
+
+
+def run_ref_tool(mode, path, no_dynrng=0, no_adjust=0, gain_db=0.0):
     r = subprocess.run([REF_TOOL, mode, str(no_dynrng), str(no_adjust), str(gain_db), path], capture_output=True)
     assert r.returncode == 0 and b"errors 0" in r.stderr, r.stderr.decode()
     return r.stdout
 
 
-@pytest.mark.parametrize("mode,key", [("wav", "51"), ("wavdolby", "51"), ("wav6", "51"), ("wav6", "20"), ("wav6", "30"),
-                                      ("wav", "20")])
+def _ref(mode, path, **opts):
+    """The reference drivers' output for one of make_streams()' streams: computed where oracle/_ref/a52dec_ref was built
+    (and then equal to the stored one), else the one stored in tests/golden/a52dec_drivers.npz."""
+    key = os.path.basename(path)[:-len(".ac3")]
+    d = np.load(DRIVERS, allow_pickle=False)
+    with open(path, "rb") as f:
+        assert f.read() == d["stream_" + key].tobytes(), "stream %s differs from the one the fixture was made from" % key
+    want = d[ref_driver_name(mode, key, **opts)].tobytes()
+    if os.path.exists(REF_TOOL):
+        assert run_ref_tool(mode, path, **opts) == want, "oracle/_ref/a52dec_ref differs from %s" % os.path.basename(DRIVERS)
+    return want
+
+
+@pytest.mark.parametrize("mode,key", WAV_CASES)
 def test_wav_output_matches_reference_drivers(tool, streams, mode, key):
     got = _run(tool, ["-o", mode], streams[key])
     want = _ref(mode, streams[key])
@@ -77,8 +101,7 @@ def test_wav_sizes_patched_when_seekable(tool, streams, tmp_path):
     assert b[20:22] == b"\xfe\xff" and int.from_bytes(b[40:44], "little") == 0x3F
 
 
-@pytest.mark.parametrize("args,ref_args", [([], {}), (["-r"], {"no_dynrng": 1}), (["-a"], {"no_adjust": 1}),
-                                           (["-g", "-6"], {"gain_db": -6.0})])
+@pytest.mark.parametrize("args,ref_args", FLOAT_CASES)
 def test_float_output_and_options(tool, streams, args, ref_args):
     got = np.frombuffer(_run(tool, ["-o", "float"] + args, streams["51"]), np.float32)
     want = np.frombuffer(_ref("float", streams["51"], **ref_args), np.float32)
