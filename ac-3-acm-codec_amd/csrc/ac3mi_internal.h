@@ -34,6 +34,7 @@ struct EncTables {
     uint8_t band_start[51];     // bndtab (entry 50 = 0 as in ac3_common_init)
     uint8_t band_size[50];      // bndsz
     uint16_t crc_tab[256];
+    int16_t xcos2[64], xsin2[64];   // the short transform pair's pre/post-rotation (256-point MDCT: xcos1/xsin1 at N = 256)
 };
 
 // what AC3_encode_init derives from (freq, bitrate, channels): ENC/ac3enc.cpp:1019-1110
@@ -155,6 +156,7 @@ struct EncodeLaunch {
     int pack_mode = 0;          // ac3mi_set_encode_mode
     const uint32_t *search_hint = nullptr;     // transcode: per frame, an offset 16 csnroffst + fsnroffst near which to start costing (stride in dwords)
     int search_hint_stride = 0;
+    uint8_t *ws_bsw = nullptr;  // [S][F][6][nch] block-switch decisions (ac3mi_set_encode_block_switch 1; null: long blocks only)
 };
 hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStream_t stream);
 hipError_t launch_enc_history(const EncodeLaunch &E, hipStream_t stream);
@@ -175,6 +177,9 @@ struct ac3mi_ctx {
     // second stream: the byte-stream layer's PCIe copies beside the kernels (stream.hip)
     hipStream_t stream2;
     int encode_mode;        // ac3mi_set_encode_mode
+    int block_switch;       // ac3mi_set_encode_block_switch
+    uint8_t *ws_bsw;        // its decisions between the MDCT kernel and the packers, one byte per channel-block
+    size_t ws_bsw_bytes;
     ac3mi::DeviceTables tab;
     // decode workspace (coefficient planes + block-switch flags between the two kernels)
     float *ws_coef;

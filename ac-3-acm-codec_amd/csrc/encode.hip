@@ -69,6 +69,7 @@ struct PackParams {
     int marker;                 // the reference's "member already merged" value, 128 (:1375-1413); AC3MI_ENC_MARKER: test aid
     const uint32_t *hint;       // optional, [frame * hint_stride]: 16 csnroffst + fsnroffst the frame's SOURCE was coded with (transcode)
     int hint_stride;
+    const uint8_t *bsw;         // optional, [S][F][6][nch]: blksw of each channel-block (block switching); null: all 0
 };
 
 
@@ -434,6 +435,7 @@ struct MdctParams {
     const int32_t *slot;        // optional: stream s keeps its history in slot[s] (stride 6*256 samples)
     int store_history;          // one frame per stream: this kernel also leaves the new history (else enc_history_kernel)
     int full_rows;              // store all 256 coefficients of a row (stage tap); else only the bins the packer codes
+    uint8_t *bsw;               // enc_mdct_kernel<true>: [S][F][6][nch] block-switch decisions for the packers
     ExpParams x;                // the exponent stage that follows the transform
 };
 
@@ -450,7 +452,21 @@ __device__ __forceinline__ void bfly(c16 &p, c16 &q, int bx, int by, int ax, int
 #ifndef ENC_MDCT_LB
 #define ENC_MDCT_LB 7        // 71 VGPRs, no scratch: 1.97 ms against 2.00 at 5 or 6 (75 VGPRs) and 2.07 at 8 (64 VGPRs, 24 bytes of scratch)
 #endif
-__global__ __launch_bounds__(64, ENC_MDCT_LB) void enc_mdct_kernel(const MdctParams P)
+#ifndef ENC_MDCT_BSW_LB
+#define ENC_MDCT_BSW_LB 5    // block switching: 95 VGPRs, no scratch (at 6: 80 VGPRs and 64 bytes of scratch, at 7: 100 bytes)
+#endif
+// Block switching (BSW, ac3mi_set_encode_block_switch 1).  Per block, before the window: the transient detector of
+// include/ac3mi.h on the raw samples (z = the 256 old || the 256 new ones, through LDS: lane L takes the second differences
+// of z[8L .. 8L+7], groups of eight lanes the 64-sample segments), a wave-uniform verdict.  A switched block keeps the window
+// and the block-floating-point shift of its 512 samples and takes A/52's pair of 256-point transforms instead of the
+// 512-point one, restated like the long one at N = 256 (ac3enc.cpp:574-603 with MDCT_N = 256): transform 1 is that MDCT of
+// the samples rotated by N/4 (phase term 0: alpha = -1), transform 2 of the samples rotated by 3N/4 (alpha = +1).  Each is
+// a 64-point complex FFT: lanes 0-31 hold transform 1, lanes 32-63 transform 2, lane l of a half points bitrev5(l) and
+// bitrev5(l) + 32 - the long layout one level down, so passes 0..5 are the long passes 0..5 with the same twiddles (the
+// 64-point table is every other entry of the 128-point one) and trades at distances 1..16 that never cross the halves.
+// coef[2k] = X1[k], coef[2k+1] = X2[k], the layout liba52's a52_imdct_256 reads: same scale as the long path.
+template <bool BSW>
+__global__ __launch_bounds__(64, BSW ? ENC_MDCT_BSW_LB : ENC_MDCT_LB) void enc_mdct_kernel(const MdctParams P)
 {
     __shared__ int32_t out[256];
     __shared__ ExpLDS XL;
@@ -502,6 +518,10 @@ __global__ __launch_bounds__(64, ENC_MDCT_LB) void enc_mdct_kernel(const MdctPar
         twc[k] = P.tab->cos[m * nblocks];
         tws[k] = -P.tab->sin[m * nblocks];
     }
+    // the short pair: lane = 32 tsh + ls holds points Ls = bitrev5(ls) and Ls + 32 of transform tsh before the passes, ls and
+    // ls + 32 after them (rotation factors read per switched block, from L1: held across the loop they spill)
+    const int ls = lane & 31, Ls = (int)(__builtin_bitreverse32((unsigned)ls) >> 27), tsh = lane >> 5;
+    const bool lfe_ch = P.x.lfe && ch == P.nch - 1;
 
     const int16_t *frame_pcm = P.pcm + ((size_t)s * P.frames + f) * 1536 * P.nch + P.chmap[ch];
     // the lane's four samples of: the block before (history), this block, and - in flight while this block is
@@ -517,7 +537,36 @@ __global__ __launch_bounds__(64, ENC_MDCT_LB) void enc_mdct_kernel(const MdctPar
         else oldv[k] = P.slot ? P.last[((size_t)P.slot[s] * 6 + ch) * 256 + j] : P.last[((size_t)s * P.nch + ch) * 256 + j];
         newv[k] = frame_pcm[joff[k]];
     }
+    int16_t *const zs = reinterpret_cast<int16_t *>(out);        // BSW: 512 16-bit samples staged in the coefficient row's LDS
     for (int blk = 0; blk < 6; blk++) {
+        // ---- BSW: the transient detector (include/ac3mi.h) on the raw samples: z = old || new ----
+        bool sw = false;
+        if constexpr (BSW) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) { zs[jpos[k]] = oldv[k]; zs[256 + jpos[k]] = newv[k]; }
+            WAVE_SYNC();
+            const int n0 = 8 * lane;
+            int zm2 = lane ? zs[n0 - 2] : 0, zm1 = lane ? zs[n0 - 1] : 0, m = 0;
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const int z = zs[n0 + j];
+                const int y = z - 2 * zm1 + zm2;
+                if (lane || j >= 2) m = max(m, y < 0 ? -y : y);
+                zm2 = zm1; zm1 = z;
+            }
+            m = max(m, __shfl_xor(m, 1));
+            m = max(m, __shfl_xor(m, 2));
+            m = max(m, __shfl_xor(m, 4));
+            int g[8];                                               // maxima of the 64-sample segments of [0, 512)
+#pragma unroll
+            for (int k = 0; k < 8; k++) g[k] = __builtin_amdgcn_readlane(m, 8 * k);
+            const int p10 = max(max(g[0], g[1]), max(g[2], g[3])), p11 = max(max(g[4], g[5]), max(g[6], g[7]));
+            const int p20 = max(g[2], g[3]), p21 = max(g[4], g[5]), p22 = max(g[6], g[7]);
+            sw = !lfe_ch && p11 > 400 &&
+                 (p11 > 10 * p10 || 3 * p21 > 40 * p20 || 3 * p22 > 40 * p21 ||
+                  g[4] > 20 * g[3] || g[5] > 20 * g[4] || g[6] > 20 * g[5] || g[7] > 20 * g[6]);
+            WAVE_SYNC();                                            // (every lane has read z before the row reuses the LDS)
+        }
         // ---- 512 input samples: 256 old + 256 new (:1673-1683), windowed (:1686-1693) - in registers ----
         int win_[8];
 #pragma unroll
@@ -548,7 +597,28 @@ __global__ __launch_bounds__(64, ENC_MDCT_LB) void enc_mdct_kernel(const MdctPar
         for (int k = 0; k < 4; k++) { O[k] = win_[k] << v; N[k] = win_[4 + k] << v; }
         // ---- rotation + pre-rotation (:578-591) of the points L (-> p) and L + 64 (-> q) ----
         int pr, pi, qr, qi;
-        {
+        if (BSW && sw) {
+            // the short pair: point i of the lane's transform takes rot[2i], rot[255 - 2i], rot[128 + 2i], rot[127 - 2i] of its
+            // 256 rotated samples - transform 1: rot = in[0..255]; transform 2: rot = -in[384..511] || in[256..383]
+#pragma unroll
+            for (int k = 0; k < 4; k++) { zs[jpos[k]] = (int16_t)O[k]; zs[256 + jpos[k]] = (int16_t)N[k]; }
+            WAVE_SYNC();
+            int rr[2], ri[2], spc[2], sps[2];
+#pragma unroll
+            for (int k = 0; k < 2; k++) { spc[k] = -P.tab->xcos2[Ls + 32 * k]; sps[k] = P.tab->xsin2[Ls + 32 * k]; }
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const int i2 = 2 * (Ls + 32 * k), base = 256 * tsh;
+                const int a = zs[base + (tsh ? 128 + i2 : i2)], b = zs[base + (tsh ? 127 - i2 : 255 - i2)];
+                const int c = zs[base + (tsh ? i2 : 128 + i2)], d = zs[base + (tsh ? 255 - i2 : 127 - i2)];
+                const int a2 = tsh ? (int)(int16_t)(-a) : a, d2 = tsh ? (int)(int16_t)(-d) : d;
+                const int re = (a2 - b) >> 1, im = (-(c - d2)) >> 1;
+                rr[k] = (int16_t)((__mul24(re, spc[k]) - __mul24(im, sps[k])) >> 15);
+                ri[k] = (int16_t)((__mul24(re, sps[k]) + __mul24(spc[k], im)) >> 15);
+            }
+            pr = rr[0]; pi = ri[0]; qr = rr[1]; qi = ri[1];
+            WAVE_SYNC();                                            // (z is read everywhere before the post-rotation writes the row)
+        } else {
             const int re0 = ((int)(int16_t)(-N[2]) - N[1]) >> 1, im0 = (-(O[2] - O[1])) >> 1;
             const int re1 = (O[0] - O[3]) >> 1, im1 = (-(N[0] - (int)(int16_t)(-N[3]))) >> 1;
             // (every product of this kernel has operands of 17 bits at most: the 24-bit multiplier, not the quarter-rate 32-bit one)
@@ -622,15 +692,30 @@ __global__ __launch_bounds__(64, ENC_MDCT_LB) void enc_mdct_kernel(const MdctPar
         pass(0); trade(std::integral_constant<int, 4>{});
         pass(1); trade(std::integral_constant<int, 8>{});
         pass(2); trade(std::integral_constant<int, 16>{});
-        pass(3); trade(std::integral_constant<int, 32>{});
-        pass(4);
-        // ---- post-rotation (:596-602): the lane now holds points lane and lane + 64 ----
-        {
-            const int sx0 = xsv[0], c0 = xcv[0], sx1 = xsv[1], c1 = xcv[1];
-            out[2 * lane] = (__mul24(pr, c0) + __mul24(sx0, pi)) >> 15;
-            out[255 - 2 * lane] = (__mul24(pr, sx0) - __mul24(pi, c0)) >> 15;
-            out[2 * (lane + 64)] = (__mul24(qr, c1) + __mul24(sx1, qi)) >> 15;
-            out[255 - 2 * (lane + 64)] = (__mul24(qr, sx1) - __mul24(qi, c1)) >> 15;
+        pass(3);
+        if (BSW && sw) {
+            // the short pair's post-rotation: the lane holds points ls and ls + 32 of its transform; X[2i] = im, X[127 - 2i] = re,
+            // interleaved into the row as coef[2k + transform]
+            int sxc[2], sxs[2];
+#pragma unroll
+            for (int k = 0; k < 2; k++) { sxc[k] = P.tab->xcos2[ls + 32 * k]; sxs[k] = P.tab->xsin2[ls + 32 * k]; }
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const int i = ls + 32 * k, zr = k ? qr : pr, zi = k ? qi : pi;
+                out[4 * i + tsh] = (__mul24(zr, sxc[k]) + __mul24(sxs[k], zi)) >> 15;
+                out[254 - 4 * i + tsh] = (__mul24(zr, sxs[k]) - __mul24(zi, sxc[k])) >> 15;
+            }
+        } else {
+            trade(std::integral_constant<int, 32>{});
+            pass(4);
+            // ---- post-rotation (:596-602): the lane now holds points lane and lane + 64 ----
+            {
+                const int sx0 = xsv[0], c0 = xcv[0], sx1 = xsv[1], c1 = xcv[1];
+                out[2 * lane] = (__mul24(pr, c0) + __mul24(sx0, pi)) >> 15;
+                out[255 - 2 * lane] = (__mul24(pr, sx0) - __mul24(pi, c0)) >> 15;
+                out[2 * (lane + 64)] = (__mul24(qr, c1) + __mul24(sx1, qi)) >> 15;
+                out[255 - 2 * (lane + 64)] = (__mul24(qr, sx1) - __mul24(qi, c1)) >> 15;
+            }
         }
         WAVE_SYNC();
         // ---- exponents (:1707-1722) ----
@@ -655,6 +740,7 @@ __global__ __launch_bounds__(64, ENC_MDCT_LB) void enc_mdct_kernel(const MdctPar
         if (P.expo) *reinterpret_cast<uint32_t *>(P.expo + row * 256 + 4 * lane) = epack;       // tap only
         *reinterpret_cast<uint32_t *>(&XL.E[blk][4 * lane]) = epack;
         if (lane == 0) P.shift[row] = (int8_t)shift;
+        if constexpr (BSW) if (lane == 0) P.bsw[row] = sw ? 1 : 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) newv[k] = nxtv[k];
         WAVE_SYNC();
@@ -1327,7 +1413,10 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         }
         auto strat_of = [&](int ch) { return (uint32_t)__builtin_amdgcn_readlane(strat_l, 6 * b + ch); };
         flush();
-        for (int ch = 0; ch < nfbw; ch++) put(1, 0);
+        if (const uint8_t *bs = P.bsw ? P.bsw + (fidx * 6 + b) * nch : nullptr)
+            for (int ch = 0; ch < nfbw; ch++) put(1, bs[ch]);
+        else
+            for (int ch = 0; ch < nfbw; ch++) put(1, 0);
         for (int ch = 0; ch < nfbw; ch++) put(1, 1);
         put(1, 0);
         if (b == 0) { put(1, 1); put(1, 0); } else put(1, 0);
@@ -1582,7 +1671,10 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
             flush();
             pos = mine;
         }
-        for (int ch = 0; ch < nfbw; ch++) put(1, 0);
+        if (const uint8_t *bs = P.bsw ? P.bsw + (fidx * 6 + b) * nch : nullptr)
+            for (int ch = 0; ch < nfbw; ch++) put(1, bs[ch]);
+        else
+            for (int ch = 0; ch < nfbw; ch++) put(1, 0);
         for (int ch = 0; ch < nfbw; ch++) put(1, 1);
         put(1, 0);
         if (b == 0) { put(1, 1); put(1, 0); } else put(1, 0);
@@ -1740,7 +1832,9 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     M.x.fscod = c.fscod;
     M.x.halfrate = c.halfrate;
     M.x.nbc = 223;      // the only reader of last[] is this same wavefront's block 0
-    hipLaunchKernelGGL(enc_mdct_kernel, dim3(E.n_streams * E.frames_per_stream * c.nch), dim3(64), 0, stream, M);
+    M.bsw = E.ws_bsw;
+    if (M.bsw) hipLaunchKernelGGL(enc_mdct_kernel<true>, dim3(E.n_streams * E.frames_per_stream * c.nch), dim3(64), 0, stream, M);
+    else hipLaunchKernelGGL(enc_mdct_kernel<false>, dim3(E.n_streams * E.frames_per_stream * c.nch), dim3(64), 0, stream, M);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 
@@ -1789,6 +1883,7 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.memo = nullptr;
     P.hint = E.search_hint;
     P.hint_stride = E.search_hint_stride;
+    P.bsw = E.ws_bsw;
 #ifndef ENC_FR_HEADROOM
 #define ENC_FR_HEADROOM 256
 #endif

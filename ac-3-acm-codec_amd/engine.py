@@ -261,6 +261,11 @@ class Engine:
         (ac3mi_set_encode_mode)."""
         self._check(self.lib.ac3mi_set_encode_mode(ctypes.c_void_p(self.ctx), int(mode)))
 
+    def set_encode_block_switch(self, mode):
+        """0 = long blocks only (the reference), 1 = a transient detector switches channel-blocks to the short transform
+        pair (ac3mi_set_encode_block_switch).  Applies to encode_batch and transcode_batch."""
+        self._check(self.lib.ac3mi_set_encode_block_switch(ctypes.c_void_p(self.ctx), int(mode)))
+
     def set_mix_state(self, pending=None, flags=None):
         """liba52's overlap bookkeeping around frames with surround level 0 (ac3mi_set_mix_state): `pending` float32 shaped
         like the delay array, `flags` int32 [S][6], both zero for new streams and updated in place by the decode calls that

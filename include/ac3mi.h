@@ -172,6 +172,20 @@ int ac3mi_set_decode_mode(ac3mi_ctx *ctx, int mode);
  *   0  (default) 2 for up to 1 024 frames per call, else 1. */
 int ac3mi_set_encode_mode(ac3mi_ctx *ctx, int mode);
 
+/* Block switching in the encoder (new; applies to every following ac3mi_encode_batch / ac3mi_transcode_batch on `ctx`,
+ * in either packer variant, with or without state slots, tiled or not):
+ *   0  (default) the reference's behaviour: every channel-block is one 512-point MDCT, blksw = 0;
+ *   1  a transient detector per full-bandwidth channel and audio block (never the LFE) switches the block to A/52's pair
+ *      of 256-point transforms, blksw = 1 in the bitstream.  Integer and stateless beyond d_last: the block's 256 new s16
+ *      samples x and the 256 before them h, z = h || x, the second difference y[n] = z[n] - 2 z[n-1] + z[n-2] (n >= 2),
+ *      a = |y|; maxima of a over [2,256) and [256,512) (P1), over [128,256) and the halves of [256,512) (P2), over
+ *      [192,256) and the quarters of [256,512) (P3).  blksw = 0 if P1[1] <= 400, else 1 if P1[1] > 10 P1[0], or
+ *      3 P2[k] > 40 P2[k-1] for k = 1, 2, or P3[k] > 20 P3[k-1] for k = 1..4 (A/52's thresholds 0.1, 0.075, 0.05).
+ * The same input gives the same decisions and bytes in one call or split over several.  Content without a transient
+ * codes to the same bytes in either mode.  The drop-in AC3_encode_* and the byte-stream layer (ac3mi_stream.h) always
+ * code long blocks.  Any other mode: AC3MI_ERR_ARG. */
+int ac3mi_set_encode_block_switch(ac3mi_ctx *ctx, int mode);
+
 /* Workspace bound (new; results do not depend on it, except for frames flagged AC3MI_STATUS_REUSE0 at a tile boundary).  ac3mi_decode_batch, ac3mi_encode_batch and ac3mi_transcode_batch keep
  * their intermediates (coefficient planes, MDCT coefficients, exponents, PCM between decoder and encoder: 37 / 60 /
  * 102 - 139 KB per 5.1 frame) in workspaces owned by the context.  A batch of more than `frames` frames goes through in tiles
