@@ -157,6 +157,7 @@ struct EncodeLaunch {
     const uint32_t *search_hint = nullptr;     // transcode: per frame, an offset 16 csnroffst + fsnroffst near which to start costing (stride in dwords)
     int search_hint_stride = 0;
     uint8_t *ws_bsw = nullptr;  // [S][F][6][nch] block-switch decisions (ac3mi_set_encode_block_switch 1; null: long blocks only)
+    uint8_t *ws_remat = nullptr;    // [S][F][6] rematrixing decisions (ac3mi_set_encode_rematrix 1; null, or not 2/0: none)
 };
 hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStream_t stream);
 hipError_t launch_enc_history(const EncodeLaunch &E, hipStream_t stream);
@@ -180,6 +181,9 @@ struct ac3mi_ctx {
     int block_switch;       // ac3mi_set_encode_block_switch
     uint8_t *ws_bsw;        // its decisions between the MDCT kernel and the packers, one byte per channel-block
     size_t ws_bsw_bytes;
+    int rematrix;           // ac3mi_set_encode_rematrix
+    uint8_t *ws_remat;      // its decisions between the MDCT kernel, the search and the packers, one byte per frame-block
+    size_t ws_remat_bytes;
     ac3mi::DeviceTables tab;
     // decode workspace (coefficient planes + block-switch flags between the two kernels)
     float *ws_coef;

@@ -488,6 +488,9 @@ ac3mi_ctx *ac3mi_create(int device)
     ctx->block_switch = 0;
     ctx->ws_bsw = nullptr;
     ctx->ws_bsw_bytes = 0;
+    ctx->rematrix = 0;
+    ctx->ws_remat = nullptr;
+    ctx->ws_remat_bytes = 0;
     ctx->ws_draws = nullptr;
     ctx->ws_draws_bytes = 0;
     ctx->ws_split = nullptr;
@@ -523,6 +526,7 @@ void ac3mi_destroy(ac3mi_ctx *ctx)
     (void)hipFree(ctx->ws_draws);
     (void)hipFree(ctx->ws_split);
     (void)hipFree(ctx->ws_bsw);
+    (void)hipFree(ctx->ws_remat);
     (void)hipFree(ctx->tab.enc);
     (void)hipEventDestroy(ctx->ev0);
     (void)hipEventDestroy(ctx->ev1);
@@ -740,6 +744,13 @@ int ac3mi_set_encode_block_switch(ac3mi_ctx *ctx, int mode)
     return AC3MI_OK;
 }
 
+int ac3mi_set_encode_rematrix(ac3mi_ctx *ctx, int mode)
+{
+    if (!ctx || mode < 0 || mode > 1) return AC3MI_ERR_ARG;
+    ctx->rematrix = mode;
+    return AC3MI_OK;
+}
+
 int ac3mi_set_tile_frames(ac3mi_ctx *ctx, long long frames)
 {
     if (!ctx || frames < 0) return AC3MI_ERR_ARG;
@@ -814,6 +825,19 @@ static int ensure_bsw(ac3mi_ctx *ctx, size_t rows)
     return AC3MI_OK;
 }
 
+// the rematrixing decisions of `nfr` frames, one byte per audio block (mode 1 only: mode 0 allocates nothing)
+static int ensure_remat(ac3mi_ctx *ctx, size_t nfr)
+{
+    if (6 * nfr <= ctx->ws_remat_bytes) return AC3MI_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(ctx->ws_remat);
+    ctx->ws_remat = nullptr;
+    ctx->ws_remat_bytes = 0;
+    HIPCHK(ctx, hipMalloc((void **)&ctx->ws_remat, 6 * nfr));
+    ctx->ws_remat_bytes = 6 * nfr;
+    return AC3MI_OK;
+}
+
 // workspace of the split front end for nfr frames: descriptors, generator positions, coupling coordinates, row sets
 struct SplitWs { void *desc; uint32_t *fpos; float *cplco; uint8_t *rows; };
 static size_t split_bytes(size_t nfr) { return nfr * (6 * 80 + 16 + 6 * 90 * 4 + 6 * 7 * 512) + 256; }
@@ -871,7 +895,7 @@ static int ensure_draws(ac3mi_ctx *ctx, size_t nfr)
 size_t ac3mi_workspace_bytes(const ac3mi_ctx *ctx)
 {
     if (!ctx) return 0;
-    return ctx->ws_coef_bytes + ctx->ws_blksw_bytes + ctx->ws_bsw_bytes + ctx->ws_enc_bytes + ctx->ws_tc_bytes + ctx->ws_draws_bytes + ctx->ws_split_bytes;
+    return ctx->ws_coef_bytes + ctx->ws_blksw_bytes + ctx->ws_bsw_bytes + ctx->ws_remat_bytes + ctx->ws_enc_bytes + ctx->ws_tc_bytes + ctx->ws_draws_bytes + ctx->ws_split_bytes;
 }
 
 size_t ac3mi_transcode_workspace_plan(size_t frames, int frames_per_stream, int n_in, int nfchans, int n_out)
@@ -1297,6 +1321,11 @@ int ac3mi_encode_batch(ac3mi_ctx *ctx, const ac3mi_encode_desc *desc, const int1
         if (r != AC3MI_OK) return r;
         E.ws_bsw = ctx->ws_bsw;
     }
+    if (ctx->rematrix) {
+        const int r = ensure_remat(ctx, (size_t)n_streams * frames_per_stream);
+        if (r != AC3MI_OK) return r;
+        E.ws_remat = ctx->ws_remat;
+    }
     E.ws_mdct = (int32_t *)ctx->ws_enc;
     E.ws_expo = nullptr;                                                   // raw exponents leave the MDCT kernel only as a tap
     E.ws_eexp = (uint8_t *)ctx->ws_enc + off_eexp;
@@ -1425,6 +1454,7 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     const bool fp = !fused && use_frame_parallel(ctx, n_streams, frames_per_stream);
     if (fp) { const int r = ensure_draws(ctx, nfr); if (r != AC3MI_OK) return r; }
     if (ctx->block_switch) { const int r = ensure_bsw(ctx, rows); if (r != AC3MI_OK) return r; }
+    if (ctx->rematrix) { const int r = ensure_remat(ctx, nfr); if (r != AC3MI_OK) return r; }
     if (split) { const int r = ensure_split(ctx, nfr); if (r != AC3MI_OK) return r; }
     // Decoder front end, transform to s16, encoder: back to back on the context's stream.  (Until round 2 two chunks were
     // pipelined over two streams; profiles/transcode_overlap.py measured 12.20 ms with and 12.23 - 12.27 ms without it per
@@ -1521,6 +1551,7 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         G.ws_snr = (int32_t *)((uint8_t *)ctx->ws_enc + off_snr) + f0 * 2;
         G.ws_memo = (uint32_t *)((uint8_t *)ctx->ws_enc + off_memo) + f0 * 8;
         G.ws_bsw = ctx->block_switch ? ctx->ws_bsw + r0 : nullptr;
+        G.ws_remat = ctx->rematrix ? ctx->ws_remat + f0 * 6 : nullptr;
         G.pcm = ws_s16 + f0 * 1536 * n_out;
         G.last = ctx->slots ? d_last : d_last + (size_t)s0 * E.cfg.nch * 256;
         G.csnr = ctx->slots ? d_csnroffst : d_csnroffst + s0;

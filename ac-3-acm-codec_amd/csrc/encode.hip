@@ -70,6 +70,7 @@ struct PackParams {
     const uint32_t *hint;       // optional, [frame * hint_stride]: 16 csnroffst + fsnroffst the frame's SOURCE was coded with (transcode)
     int hint_stride;
     const uint8_t *bsw;         // optional, [S][F][6][nch]: blksw of each channel-block (block switching); null: all 0
+    const uint8_t *remat;       // optional, [S][F][6]: 2/0 rematrixing, flags in bits 0-3, rematstr in bit 4; null: none
 };
 
 
@@ -435,8 +436,9 @@ struct MdctParams {
     const int32_t *slot;        // optional: stream s keeps its history in slot[s] (stride 6*256 samples)
     int store_history;          // one frame per stream: this kernel also leaves the new history (else enc_history_kernel)
     int full_rows;              // store all 256 coefficients of a row (stage tap); else only the bins the packer codes
-    uint8_t *bsw;               // enc_mdct_kernel<true>: [S][F][6][nch] block-switch decisions for the packers
+    uint8_t *bsw;               // enc_mdct_kernel<true, *>: [S][F][6][nch] block-switch decisions for the packers
     ExpParams x;                // the exponent stage that follows the transform
+    uint8_t *remat;             // enc_mdct_kernel<*, true>: [S][F][6] rematrixing decisions for the search and the packers
 };
 
 struct c16 { int16_t re, im; };
@@ -465,25 +467,47 @@ __device__ __forceinline__ void bfly(c16 &p, c16 &q, int bx, int by, int ax, int
 // bitrev5(l) + 32 - the long layout one level down, so passes 0..5 are the long passes 0..5 with the same twiddles (the
 // 64-point table is every other entry of the 128-point one) and trades at distances 1..16 that never cross the halves.
 // coef[2k] = X1[k], coef[2k+1] = X2[k], the layout liba52's a52_imdct_256 reads: same scale as the long path.
-template <bool BSW>
-__global__ __launch_bounds__(64, BSW ? ENC_MDCT_BSW_LB : ENC_MDCT_LB) void enc_mdct_kernel(const MdctParams P)
+//
+// Rematrixing (REMAT, ac3mi_set_encode_rematrix 1, 2/0 only).  A stereo frame is one workgroup of two wavefronts, wave w
+// = channel w, each with its own row and exponent LDS.  Per block, after the post-rotation, each wave publishes its v (and
+// its blksw) and one workgroup barrier later reads the other's.  Rows and v are double-buffered by block parity, so that
+// one barrier per block suffices: a wave writes parity p again only after the next block's barrier, which the other wave
+// passes only after it has read parity p.  The band energies of include/ac3mi.h: lane l < 53 takes the bins 13 + 4l ..
+// 16 + 4l below 223 of both rows (the band edges 13, 25, 37, 61 are 13 + 4 x {0, 3, 6, 12}: no lane straddles one), four
+// sums of squares as u64, split into 20-bit low and high parts that a 32-bit prefix scan sums exactly; the band totals
+// are the scan at lanes 2, 5, 11 and 63.  Both waves compute the same flags.  A block with a flag rewrites each wave's
+// own four bins (aligned, M or S) in registers before the exponents; the barrier is a bare s_barrier behind an LDS-only
+// fence, so the next block's PCM loads (nxtv) stay in flight across it.
+#ifndef ENC_MDCT_REMAT_LB
+#define ENC_MDCT_REMAT_LB 5          // 90 VGPRs, no scratch (at 6: 80 VGPRs and 20 bytes of scratch, at 7: 72 and 52)
+#endif
+#ifndef ENC_MDCT_BSW_REMAT_LB
+#define ENC_MDCT_BSW_REMAT_LB 4      // with block switching: 118 VGPRs, no scratch (at 5: 96 VGPRs and 48 bytes of scratch)
+#endif
+template <bool BSW, bool REMAT>
+__global__ __launch_bounds__(REMAT ? 128 : 64, REMAT ? (BSW ? ENC_MDCT_BSW_REMAT_LB : ENC_MDCT_REMAT_LB) : BSW ? ENC_MDCT_BSW_LB : ENC_MDCT_LB)
+void enc_mdct_kernel(const MdctParams P)
 {
-    __shared__ int32_t out[256];
-    __shared__ ExpLDS XL;
+    __shared__ int32_t out_[REMAT ? 4 : 1][256];        // REMAT: [2 * block parity + wave]
+    __shared__ ExpLDS XL_[REMAT ? 2 : 1];
+    __shared__ int rv_[REMAT ? 2 : 1][2];              // REMAT: [block parity][wave] = v | blksw << 8
 
-    const int lane = threadIdx.x;
+    const int wave = REMAT ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+    const int lane = REMAT ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
+    ExpLDS &XL = XL_[wave];
     // The nch wavefronts of a frame de-interleave the same PCM lines, one channel each.  Workgroups are dealt round-robin over the
     // 8 XCDs (private L2s), so with unit = blockIdx the channels of a frame sat on different XCDs and each fetched the frame's
     // samples for itself (PMC: 114 KB fetched per frame against 18 KB of PCM).  The bijective remap of cdna_hip_programming.md
-    // (T1) makes consecutive units share an XCD: blocks with equal blockIdx % 8 take one contiguous range of units.
-    int unit;                                       // (s*F + f)*nch + ch
+    // (T1) makes consecutive units share an XCD: blocks with equal blockIdx % 8 take one contiguous range of units.  With
+    // REMAT a unit is a workgroup = a stereo frame (the same bijection over gridDim.x = frames), its waves the channels.
+    int unit;                                       // (s*F + f)*nch + ch; REMAT: s*F + f
     {
         const unsigned n = gridDim.x, q = n >> 3, r = n & 7u, x = blockIdx.x & 7u, i = blockIdx.x >> 3;
         unit = (int)((x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i);
         unit = __builtin_amdgcn_readfirstlane(unit);        // (wave-uniform by construction: row and state addresses on the scalar unit)
     }
-    const int ch = unit % P.nch;
-    const int sf = unit / P.nch;
+    const int ch = REMAT ? wave : unit % P.nch;
+    const int sf = REMAT ? unit : unit / P.nch;
     const int f = sf % P.frames;
     const int s = sf / P.frames;
 
@@ -537,8 +561,10 @@ __global__ __launch_bounds__(64, BSW ? ENC_MDCT_BSW_LB : ENC_MDCT_LB) void enc_m
         else oldv[k] = P.slot ? P.last[((size_t)P.slot[s] * 6 + ch) * 256 + j] : P.last[((size_t)s * P.nch + ch) * 256 + j];
         newv[k] = frame_pcm[joff[k]];
     }
-    int16_t *const zs = reinterpret_cast<int16_t *>(out);        // BSW: 512 16-bit samples staged in the coefficient row's LDS
+    int rprev = 0;                                  // REMAT: the flags of the block before
     for (int blk = 0; blk < 6; blk++) {
+        int32_t *const out = out_[REMAT ? 2 * (blk & 1) + wave : 0];
+        int16_t *const zs = reinterpret_cast<int16_t *>(out);    // BSW: 512 16-bit samples staged in the coefficient row's LDS
         // ---- BSW: the transient detector (include/ac3mi.h) on the raw samples: z = old || new ----
         bool sw = false;
         if constexpr (BSW) {
@@ -590,7 +616,7 @@ __global__ __launch_bounds__(64, BSW ? ENC_MDCT_BSW_LB : ENC_MDCT_LB) void enc_m
         acc = wave_max_nonneg(acc);
         int v = 14 - ilog2u((unsigned)acc);
         if (v < 0) v = 0;
-        const int shift = v - 9;
+        int shift = v - 9;
         int O[4], N[4];                                                     // in[jpos[k]], in[256 + jpos[k]] as 16-bit values
         // (|x| << v < 2^15 by the choice of v, or v = 0: the shifted values are 16-bit values already)
 #pragma unroll
@@ -722,6 +748,73 @@ __global__ __launch_bounds__(64, BSW ? ENC_MDCT_BSW_LB : ENC_MDCT_LB) void enc_m
         const size_t row = (((size_t)s * P.frames + f) * 6 + blk) * P.nch + ch;
         int4 cv = *reinterpret_cast<const int4 *>(&out[4 * lane]);
         int cc[4] = {cv.x, cv.y, cv.z, cv.w};
+        if constexpr (REMAT) {
+            // ---- rematrixing (include/ac3mi.h): both rows, one barrier ----
+            const int par = blk & 1;
+            if (lane == 0) rv_[par][wave] = v | (sw ? 1 << 8 : 0);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+            const int r0 = rv_[par][0], r1 = rv_[par][1];
+            const int vl = r0 & 0xff, vr = r1 & 0xff, vm = min(vl, vr), dl = vl - vm, dr = vr - vm;
+            const int32_t *rl = out_[2 * par], *rr = out_[2 * par + 1];
+            uint64_t el = 0, er = 0, em = 0, es = 0;
+            if (lane < 53) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int j = 13 + 4 * lane + k;
+                    if (j < 223) {
+                        const int a = rl[j] >> dl, b = rr[j] >> dr, m = (a + b) >> 1, d = (a - b) >> 1;
+                        el += (uint64_t)(uint32_t)abs(a) * (uint32_t)abs(a);
+                        er += (uint64_t)(uint32_t)abs(b) * (uint32_t)abs(b);
+                        em += (uint64_t)(uint32_t)abs(m) * (uint32_t)abs(m);
+                        es += (uint64_t)(uint32_t)abs(d) * (uint32_t)abs(d);
+                    }
+                }
+            }
+            // (a lane's sums are below 2^36: 20-bit low parts and the high parts scan to below 2^26 and 2^22)
+            const uint64_t e4[4] = {el, er, em, es};
+            uint64_t eb[4][4];                                      // [quantity][band]
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const uint32_t lo = wave_incl_scan_u32((uint32_t)e4[q] & 0xfffffu), hi = wave_incl_scan_u32((uint32_t)(e4[q] >> 20));
+                const int at[4] = {2, 5, 11, 63};
+                uint64_t prev = 0;
+#pragma unroll
+                for (int bd = 0; bd < 4; bd++) {
+                    const uint64_t t = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hi, at[bd]) << 20) +
+                                       (uint32_t)__builtin_amdgcn_readlane((int)lo, at[bd]);
+                    eb[q][bd] = t - prev;
+                    prev = t;
+                }
+            }
+            int flags = 0;
+            if (!BSW || ((r0 ^ r1) & 0x100) == 0) {
+#pragma unroll
+                for (int bd = 0; bd < 4; bd++) {
+                    const uint64_t ems = eb[2][bd] < eb[3][bd] ? eb[2][bd] : eb[3][bd];
+                    const uint64_t elr = eb[0][bd] < eb[1][bd] ? eb[0][bd] : eb[1][bd];
+                    if (2 * ems < elr) flags |= 1 << bd;
+                }
+            }
+            if (flags) {
+                // rows L' = cL >> dl, R' = cR >> dr at shift vm - 9; M / S in the flagged bands
+                const int32_t *ro = wave ? rl : rr;
+                const int dmine = wave ? dr : dl, doth = wave ? dl : dr;
+                const int4 ov = *reinterpret_cast<const int4 *>(&ro[4 * lane]);
+                const int oc[4] = {ov.x, ov.y, ov.z, ov.w};
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int j = 4 * lane + k;
+                    const int bd = j < 13 ? -1 : j < 25 ? 0 : j < 37 ? 1 : j < 61 ? 2 : j < 223 ? 3 : -1;
+                    const int a = cc[k] >> dmine, b = oc[k] >> doth;
+                    cc[k] = bd >= 0 && ((flags >> bd) & 1) ? (wave ? (b - a) >> 1 : (a + b) >> 1) : a;
+                }
+                shift = vm - 9;
+            }
+            if (lane == 0 && wave == 0) P.remat[(size_t)sf * 6 + blk] = (uint8_t)(flags | (blk == 0 || flags != rprev ? 0x10 : 0));
+            rprev = flags;
+        }
         uint32_t epack = 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -741,6 +834,7 @@ __global__ __launch_bounds__(64, BSW ? ENC_MDCT_BSW_LB : ENC_MDCT_LB) void enc_m
         *reinterpret_cast<uint32_t *>(&XL.E[blk][4 * lane]) = epack;
         if (lane == 0) P.shift[row] = (int8_t)shift;
         if constexpr (BSW) if (lane == 0) P.bsw[row] = sw ? 1 : 0;
+        (void)rprev;
 #pragma unroll
         for (int k = 0; k < 4; k++) newv[k] = nxtv[k];
         WAVE_SYNC();
@@ -945,6 +1039,9 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                 frame_bits += 2 * 4 + 3 + 6 + nch * (4 + 3);
                 frame_bits += 2;
                 frame_bits += 16;
+                // rematrixing: the four flags of every block 1..5 that sends them (block 0's stay uncounted, as above)
+                if (P.remat)
+                    for (int b = 1; b < 6; b++) frame_bits += (P.remat[fidx * 6 + b] & 0x10) ? 4 : 0;
             }
         };
         // PART 1 replays the search from tabulated verdicts and needs the frame's data only for a verdict that is missing
@@ -1420,7 +1517,13 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         for (int ch = 0; ch < nfbw; ch++) put(1, 1);
         put(1, 0);
         if (b == 0) { put(1, 1); put(1, 0); } else put(1, 0);
-        if (acmod == 2) { if (b == 0) { put(1, 1); put(4, 0); } else put(1, 0); }
+        if (acmod == 2) {
+            if (P.remat) {
+                const uint32_t r = P.remat[fidx * 6 + b];
+                put(1, r >> 4);
+                if (r & 0x10) { put(1, r & 1); put(1, (r >> 1) & 1); put(1, (r >> 2) & 1); put(1, (r >> 3) & 1); }
+            } else if (b == 0) { put(1, 1); put(4, 0); } else put(1, 0);
+        }
         for (int ch = 0; ch < nfbw; ch++) put(2, strat_of(ch));
         if (lfe) put(1, strat_of(nch - 1));
         for (int ch = 0; ch < nfbw; ch++) if (strat_of(ch) != 0) put(6, P.chbwcod);
@@ -1601,6 +1704,8 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
                          (P.acmod == 2 ? 2 : 0) + 1 + 5 + 3 + 1 + 1 + 3;
     int side_bits = 2 * nfbw + 1 + (b == 0 ? 2 : 1) + (P.acmod == 2 ? (b == 0 ? 5 : 1) : 0) + 2 * nfbw + (P.lfe ? 1 : 0) +
                     1 + (b == 0 ? 11 : 0) + 1 + (b == 0 ? 6 + 7 * nch : 0) + 2;
+    const int rem = P.remat ? (int)P.remat[fidx * 6 + b] : -1;     // rematrixing: block b > 0 sends its four flags when rematstr
+    if (b > 0 && rem >= 0 && (rem & 0x10)) side_bits += 4;
     for (int ch = 0; ch < nch; ch++) {
         const int stg = strat_of(ch);
         if (stg == 0) continue;
@@ -1678,7 +1783,12 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
         for (int ch = 0; ch < nfbw; ch++) put(1, 1);
         put(1, 0);
         if (b == 0) { put(1, 1); put(1, 0); } else put(1, 0);
-        if (P.acmod == 2) { if (b == 0) { put(1, 1); put(4, 0); } else put(1, 0); }
+        if (P.acmod == 2) {
+            if (rem >= 0) {
+                put(1, (uint32_t)rem >> 4);
+                if (rem & 0x10) { put(1, rem & 1); put(1, (rem >> 1) & 1); put(1, (rem >> 2) & 1); put(1, (rem >> 3) & 1); }
+            } else if (b == 0) { put(1, 1); put(4, 0); } else put(1, 0);
+        }
         for (int ch = 0; ch < nfbw; ch++) put(2, (uint32_t)strat_of(ch));
         if (P.lfe) put(1, (uint32_t)strat_of(nch - 1));
         for (int ch = 0; ch < nfbw; ch++) if ((strat_set >> ch) & 1u) put(6, P.chbwcod);
@@ -1833,8 +1943,12 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     M.x.halfrate = c.halfrate;
     M.x.nbc = 223;      // the only reader of last[] is this same wavefront's block 0
     M.bsw = E.ws_bsw;
-    if (M.bsw) hipLaunchKernelGGL(enc_mdct_kernel<true>, dim3(E.n_streams * E.frames_per_stream * c.nch), dim3(64), 0, stream, M);
-    else hipLaunchKernelGGL(enc_mdct_kernel<false>, dim3(E.n_streams * E.frames_per_stream * c.nch), dim3(64), 0, stream, M);
+    M.remat = c.acmod == 2 && c.nch == 2 ? E.ws_remat : nullptr;      // (rematrixing is a 2/0 tool: other layouts ignore it)
+    const dim3 units(E.n_streams * E.frames_per_stream * c.nch), frames(E.n_streams * E.frames_per_stream);
+    if (M.remat && M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, true>), frames, dim3(128), 0, stream, M);
+    else if (M.remat) hipLaunchKernelGGL((enc_mdct_kernel<false, true>), frames, dim3(128), 0, stream, M);
+    else if (M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, false>), units, dim3(64), 0, stream, M);
+    else hipLaunchKernelGGL((enc_mdct_kernel<false, false>), units, dim3(64), 0, stream, M);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 
@@ -1884,6 +1998,7 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.hint = E.search_hint;
     P.hint_stride = E.search_hint_stride;
     P.bsw = E.ws_bsw;
+    P.remat = M.remat;
 #ifndef ENC_FR_HEADROOM
 #define ENC_FR_HEADROOM 256
 #endif

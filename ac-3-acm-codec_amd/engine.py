@@ -266,6 +266,11 @@ class Engine:
         pair (ac3mi_set_encode_block_switch).  Applies to encode_batch and transcode_batch."""
         self._check(self.lib.ac3mi_set_encode_block_switch(ctypes.c_void_p(self.ctx), int(mode)))
 
+    def set_encode_rematrix(self, mode):
+        """0 = no rematrixing (the reference), 1 = 2/0 frames code (L+R)/2 and (L-R)/2 in the bands where that pays
+        (ac3mi_set_encode_rematrix).  Applies to encode_batch and transcode_batch."""
+        self._check(self.lib.ac3mi_set_encode_rematrix(ctypes.c_void_p(self.ctx), int(mode)))
+
     def set_mix_state(self, pending=None, flags=None):
         """liba52's overlap bookkeeping around frames with surround level 0 (ac3mi_set_mix_state): `pending` float32 shaped
         like the delay array, `flags` int32 [S][6], both zero for new streams and updated in place by the decode calls that

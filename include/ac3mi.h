@@ -186,6 +186,23 @@ int ac3mi_set_encode_mode(ac3mi_ctx *ctx, int mode);
  * code long blocks.  Any other mode: AC3MI_ERR_ARG. */
 int ac3mi_set_encode_block_switch(ac3mi_ctx *ctx, int mode);
 
+/* Stereo rematrixing in the encoder (new; applies to every following ac3mi_encode_batch / ac3mi_transcode_batch on `ctx`,
+ * in either packer variant, with or without state slots, tiled or not, with block switching on or off):
+ *   0  (default) the reference's behaviour: every 2/0 block sends rematrixing flags of 0 (block 0) or none (rematstr 0);
+ *   1  2/0 frames code (L+R)/2 and (L-R)/2 in the rematrixing bands where that pays.  Per audio block, from the two
+ *      channels' 256-bin MDCT rows cL, cR before exponents and their block-floating-point exponents vL, vR (a row's true
+ *      scale is c / 2^v): vm = min(vL, vR), L' = cL >> (vL - vm), R' = cR >> (vR - vm), M = (L' + R') >> 1,
+ *      S = (L' - R') >> 1 (arithmetic shifts).  Bands [13,25), [25,37), [37,61), [61,223); in each the exact sums of
+ *      squares EL, ER, EM, ES; band flagged iff 2 min(EM, ES) < min(EL, ER).  With block switching 1, a block whose two
+ *      channels differ in blksw gets no flags.  A block with a flag codes the rows L', R' at shift vm - 9 with M, S in
+ *      the flagged bands, and takes its exponents (and exponent strategies) from them; a block without one is coded as in
+ *      mode 0.  Block 0 sends rematstr 1 and its flags, block b > 0 sends rematstr 1 and its flags only when they differ
+ *      from block b-1's.  The encode taps' d_mdct / d_exponent then show the coded rows.
+ * Other channel layouts are accepted and unchanged.  The same input gives the same bytes in one call or split over
+ * several.  The drop-in AC3_encode_* and the byte-stream layer (ac3mi_stream.h) never rematrix.  Any other mode:
+ * AC3MI_ERR_ARG. */
+int ac3mi_set_encode_rematrix(ac3mi_ctx *ctx, int mode);
+
 /* Workspace bound (new; results do not depend on it, except for frames flagged AC3MI_STATUS_REUSE0 at a tile boundary).  ac3mi_decode_batch, ac3mi_encode_batch and ac3mi_transcode_batch keep
  * their intermediates (coefficient planes, MDCT coefficients, exponents, PCM between decoder and encoder: 37 / 60 /
  * 102 - 139 KB per 5.1 frame) in workspaces owned by the context.  A batch of more than `frames` frames goes through in tiles
