@@ -132,6 +132,28 @@ hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStre
 hipError_t launch_decode_wg(const DeviceTables &tab, const DecodeLaunch &L, const XformLaunch *X, int grid_cap, hipStream_t stream);
 void build_dec_tables(DecTables *t, uint16_t *lfsr_seq /*[65535]*/, uint16_t *lfsr_idx /*[65536]*/);
 
+// ac3mi_set_encode_coupling 1: what the coupling kernel leaves per frame for the search and the packer
+struct CplWs {
+    uint32_t *word;             // [F] bit 0 cplinu, bits 8 + 2 ch .. 9 + 2 ch: mstrcplco of channel ch
+    uint8_t *co;                // [F][5][16] cplcoexp << 4 | cplcomant per channel and band
+    int32_t *mdct;              // [F][6][256] the coupling rows (bins outside [cplstrtmant, cplendmant): 0)
+    int8_t *shift;              // [F][8] their exp_samples
+    uint8_t *eexp;              // [F][6][256] encoded exponents; bin cplstrtmant - 1 holds 2 cplabsexp
+    int16_t *emask;             // [F][6][50] masking curves minus the floor
+    uint8_t *strat;             // [F][8] cplexpstr
+    int32_t *ebits;             // [F] bits of cplabsexp and the exponent groups
+    // 2/0 with rematrixing on (else null): the rows and exponent stage of enc_mdct_kernel without rematrixing, from which a
+    // coupled frame's rematrixing is decided again over liba52's cplinu-1 band set
+    int32_t *prow;              // [F][6][2][256]
+    int8_t *pshift;             // [F][6][2]
+    uint8_t *peexp;             // [F][6][2][256]
+    int16_t *pemask;            // [F][6][2][50]
+    uint8_t *pstrat;            // [F][6][2]
+    int32_t *pebits;            // [F][2]
+};
+constexpr int CPL_FRAME_BYTES = 16 + 80 + 6 * 256 * 4 + 8 + 6 * 256 + 6 * 50 * 2 + 8 + 8;
+constexpr int CPL_REMAT_FRAME_BYTES = 6 * 2 * 256 * 4 + 16 + 6 * 2 * 256 + 6 * 2 * 50 * 2 + 16 + 16;
+
 struct EncodeLaunch {
     EncConfig cfg;
     const int16_t *pcm;         // [S][F][1536][nch]
@@ -158,7 +180,13 @@ struct EncodeLaunch {
     int search_hint_stride = 0;
     uint8_t *ws_bsw = nullptr;  // [S][F][6][nch] block-switch decisions (ac3mi_set_encode_block_switch 1; null: long blocks only)
     uint8_t *ws_remat = nullptr;    // [S][F][6] rematrixing decisions (ac3mi_set_encode_rematrix 1; null, or not 2/0: none)
+    int cpl_begf = -1;          // ac3mi_set_encode_coupling 1: cplbegf (0..12); -1: no coupling
+    CplWs ws_cpl = {};          // its per-frame results (cpl_begf >= 0)
 };
+// carves CPL_FRAME_BYTES * nfr bytes at `base` into the arrays of CplWs (base 16-byte aligned)
+CplWs cpl_slices(void *base, size_t nfr);
+// carves CPL_REMAT_FRAME_BYTES * nfr bytes at `base` into the p* arrays of `w`
+void cpl_remat_slices(CplWs &w, void *base, size_t nfr);
 hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStream_t stream);
 hipError_t launch_enc_history(const EncodeLaunch &E, hipStream_t stream);
 void build_enc_tables(EncTables *t);
@@ -184,6 +212,11 @@ struct ac3mi_ctx {
     int rematrix;           // ac3mi_set_encode_rematrix
     uint8_t *ws_remat;      // its decisions between the MDCT kernel, the search and the packers, one byte per frame-block
     size_t ws_remat_bytes;
+    int coupling, cpl_begf; // ac3mi_set_encode_coupling
+    void *ws_cpl;           // its per-frame workspace (ac3mi::CplWs, CPL_FRAME_BYTES a frame)
+    size_t ws_cpl_bytes;
+    void *ws_cplr;          // with rematrixing on as well: CPL_REMAT_FRAME_BYTES a frame
+    size_t ws_cplr_bytes;
     ac3mi::DeviceTables tab;
     // decode workspace (coefficient planes + block-switch flags between the two kernels)
     float *ws_coef;

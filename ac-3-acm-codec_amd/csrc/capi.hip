@@ -491,6 +491,12 @@ ac3mi_ctx *ac3mi_create(int device)
     ctx->rematrix = 0;
     ctx->ws_remat = nullptr;
     ctx->ws_remat_bytes = 0;
+    ctx->coupling = 0;
+    ctx->cpl_begf = 0;
+    ctx->ws_cpl = nullptr;
+    ctx->ws_cpl_bytes = 0;
+    ctx->ws_cplr = nullptr;
+    ctx->ws_cplr_bytes = 0;
     ctx->ws_draws = nullptr;
     ctx->ws_draws_bytes = 0;
     ctx->ws_split = nullptr;
@@ -527,6 +533,8 @@ void ac3mi_destroy(ac3mi_ctx *ctx)
     (void)hipFree(ctx->ws_split);
     (void)hipFree(ctx->ws_bsw);
     (void)hipFree(ctx->ws_remat);
+    (void)hipFree(ctx->ws_cpl);
+    (void)hipFree(ctx->ws_cplr);
     (void)hipFree(ctx->tab.enc);
     (void)hipEventDestroy(ctx->ev0);
     (void)hipEventDestroy(ctx->ev1);
@@ -751,6 +759,14 @@ int ac3mi_set_encode_rematrix(ac3mi_ctx *ctx, int mode)
     return AC3MI_OK;
 }
 
+int ac3mi_set_encode_coupling(ac3mi_ctx *ctx, int mode, int begf)
+{
+    if (!ctx || mode < 0 || mode > 1 || begf < 0 || begf > 12) return AC3MI_ERR_ARG;
+    ctx->coupling = mode;
+    ctx->cpl_begf = begf;
+    return AC3MI_OK;
+}
+
 int ac3mi_set_tile_frames(ac3mi_ctx *ctx, long long frames)
 {
     if (!ctx || frames < 0) return AC3MI_ERR_ARG;
@@ -838,6 +854,47 @@ static int ensure_remat(ac3mi_ctx *ctx, size_t nfr)
     return AC3MI_OK;
 }
 
+// the coupling workspace of `nfr` frames (mode 1 only: mode 0 allocates nothing)
+static int ensure_cpl(ac3mi_ctx *ctx, size_t nfr)
+{
+    const size_t need = nfr * ac3mi::CPL_FRAME_BYTES + 256;
+    if (need <= ctx->ws_cpl_bytes) return AC3MI_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(ctx->ws_cpl);
+    ctx->ws_cpl = nullptr;
+    ctx->ws_cpl_bytes = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->ws_cpl, need));
+    ctx->ws_cpl_bytes = need;
+    return AC3MI_OK;
+}
+
+// with rematrixing on as well (2/0): the rows before rematrixing of `nfr` frames
+static int ensure_cplr(ac3mi_ctx *ctx, size_t nfr)
+{
+    const size_t need = nfr * ac3mi::CPL_REMAT_FRAME_BYTES + 256;
+    if (need <= ctx->ws_cplr_bytes) return AC3MI_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(ctx->ws_cplr);
+    ctx->ws_cplr = nullptr;
+    ctx->ws_cplr_bytes = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->ws_cplr, need));
+    ctx->ws_cplr_bytes = need;
+    return AC3MI_OK;
+}
+
+// the coupling arrays of frames f0.. of a workspace carved for nfr frames
+static ac3mi::CplWs cpl_at(const ac3mi::CplWs &w, size_t f0)
+{
+    ac3mi::CplWs r = w;
+    r.word += f0; r.co += 80 * f0; r.mdct += 6 * 256 * f0; r.shift += 8 * f0;
+    r.eexp += 6 * 256 * f0; r.emask += 6 * 50 * f0; r.strat += 8 * f0; r.ebits += f0;
+    if (r.prow) {
+        r.prow += 6 * 2 * 256 * f0; r.pshift += 12 * f0; r.peexp += 6 * 2 * 256 * f0; r.pemask += 6 * 2 * 50 * f0;
+        r.pstrat += 12 * f0; r.pebits += 2 * f0;
+    }
+    return r;
+}
+
 // workspace of the split front end for nfr frames: descriptors, generator positions, coupling coordinates, row sets
 struct SplitWs { void *desc; uint32_t *fpos; float *cplco; uint8_t *rows; };
 static size_t split_bytes(size_t nfr) { return nfr * (6 * 80 + 16 + 6 * 90 * 4 + 6 * 7 * 512) + 256; }
@@ -895,7 +952,7 @@ static int ensure_draws(ac3mi_ctx *ctx, size_t nfr)
 size_t ac3mi_workspace_bytes(const ac3mi_ctx *ctx)
 {
     if (!ctx) return 0;
-    return ctx->ws_coef_bytes + ctx->ws_blksw_bytes + ctx->ws_bsw_bytes + ctx->ws_remat_bytes + ctx->ws_enc_bytes + ctx->ws_tc_bytes + ctx->ws_draws_bytes + ctx->ws_split_bytes;
+    return ctx->ws_coef_bytes + ctx->ws_blksw_bytes + ctx->ws_bsw_bytes + ctx->ws_remat_bytes + ctx->ws_cpl_bytes + ctx->ws_cplr_bytes + ctx->ws_enc_bytes + ctx->ws_tc_bytes + ctx->ws_draws_bytes + ctx->ws_split_bytes;
 }
 
 size_t ac3mi_transcode_workspace_plan(size_t frames, int frames_per_stream, int n_in, int nfchans, int n_out)
@@ -1326,6 +1383,17 @@ int ac3mi_encode_batch(ac3mi_ctx *ctx, const ac3mi_encode_desc *desc, const int1
         if (r != AC3MI_OK) return r;
         E.ws_remat = ctx->ws_remat;
     }
+    if (ctx->coupling) {
+        const int r = ensure_cpl(ctx, (size_t)n_streams * frames_per_stream);
+        if (r != AC3MI_OK) return r;
+        E.cpl_begf = ctx->cpl_begf;
+        E.ws_cpl = ac3mi::cpl_slices(ctx->ws_cpl, (size_t)n_streams * frames_per_stream);
+        if (ctx->rematrix && E.cfg.acmod == 2 && E.cfg.nch == 2) {
+            const int r2 = ensure_cplr(ctx, (size_t)n_streams * frames_per_stream);
+            if (r2 != AC3MI_OK) return r2;
+            ac3mi::cpl_remat_slices(E.ws_cpl, ctx->ws_cplr, (size_t)n_streams * frames_per_stream);
+        }
+    }
     E.ws_mdct = (int32_t *)ctx->ws_enc;
     E.ws_expo = nullptr;                                                   // raw exponents leave the MDCT kernel only as a tap
     E.ws_eexp = (uint8_t *)ctx->ws_enc + off_eexp;
@@ -1455,6 +1523,13 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     if (fp) { const int r = ensure_draws(ctx, nfr); if (r != AC3MI_OK) return r; }
     if (ctx->block_switch) { const int r = ensure_bsw(ctx, rows); if (r != AC3MI_OK) return r; }
     if (ctx->rematrix) { const int r = ensure_remat(ctx, nfr); if (r != AC3MI_OK) return r; }
+    if (ctx->coupling) { const int r = ensure_cpl(ctx, nfr); if (r != AC3MI_OK) return r; }
+    ac3mi::CplWs cplw = ctx->coupling ? ac3mi::cpl_slices(ctx->ws_cpl, nfr) : ac3mi::CplWs{};
+    if (ctx->coupling && ctx->rematrix && E.cfg.acmod == 2 && E.cfg.nch == 2) {
+        const int r = ensure_cplr(ctx, nfr);
+        if (r != AC3MI_OK) return r;
+        ac3mi::cpl_remat_slices(cplw, ctx->ws_cplr, nfr);
+    }
     if (split) { const int r = ensure_split(ctx, nfr); if (r != AC3MI_OK) return r; }
     // Decoder front end, transform to s16, encoder: back to back on the context's stream.  (Until round 2 two chunks were
     // pipelined over two streams; profiles/transcode_overlap.py measured 12.20 ms with and 12.23 - 12.27 ms without it per
@@ -1552,6 +1627,8 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         G.ws_memo = (uint32_t *)((uint8_t *)ctx->ws_enc + off_memo) + f0 * 8;
         G.ws_bsw = ctx->block_switch ? ctx->ws_bsw + r0 : nullptr;
         G.ws_remat = ctx->rematrix ? ctx->ws_remat + f0 * 6 : nullptr;
+        G.cpl_begf = ctx->coupling ? ctx->cpl_begf : -1;
+        G.ws_cpl = ctx->coupling ? cpl_at(cplw, f0) : ac3mi::CplWs{};
         G.pcm = ws_s16 + f0 * 1536 * n_out;
         G.last = ctx->slots ? d_last : d_last + (size_t)s0 * E.cfg.nch * 256;
         G.csnr = ctx->slots ? d_csnroffst : d_csnroffst + s0;

@@ -173,21 +173,27 @@ struct MantBlock {
     int nch, nbc;
     bool lfe;
     uint32_t marker;            // the reference's "member already merged" value, 128 (:1375-1413)
+    const int32_t *cplrow;      // mant_pack_block<true>: the block's coupling row [256]
 };
 
 // Packs the block's mantissas from bit `pos` on; returns the first bit after them.  ew: the encoded exponents (`em`), ad: the
 // bap table addresses (mant_block_addresses), shv: exp_samples per channel (wave-uniform), garbage: a coded coefficient
 // of the block has a negative shift (wave-uniform).
-__device__ __forceinline__ uint32_t mant_pack_block(const MantBlock &B, const uint32_t (&ew)[6], const uint32_t (&ad)[6], const int (&shv)[6],
-                                                    bool garbage, uint32_t pos, int lane)
+// CPL (a coupled frame, every full-bandwidth channel in coupling): the arrays are per PASS - channel 0, the coupling row (from
+// B.cplrow), channels 1 .. nfbw-1 - with the LFE's entries at index 6: the order A/52 reads the mantissas in.
+template <bool CPL = false>
+__device__ __forceinline__ uint32_t mant_pack_block(const MantBlock &B, const uint32_t (&ew)[CPL ? 7 : 6], const uint32_t (&ad)[CPL ? 7 : 6],
+                                                    const int (&shv)[CPL ? 7 : 6], bool garbage, uint32_t pos, int lane)
 {
+    constexpr int NA = CPL ? 7 : 6;
     const int nch = B.nch, nbc = B.nbc;
     // The LFE's seven coefficients ride in the LAST full-bandwidth channel's pass: that channel's 223 bins fill lanes 0..55,
     // lane 56 + k takes LFE bin k in its first slot - lane order is bitstream order (the LFE follows the last channel,
     // :1341-1501), so ranks, offsets and grouped codes come out as from a pass of its own, which would cost as much as a
     // full channel's.
     const bool lfe_rides = B.lfe && nch >= 2 && nbc <= 224;
-    const int npass = lfe_rides ? nch - 1 : nch;
+    const int npass = (lfe_rides ? nch - 1 : nch) + (CPL ? 1 : 0);
+    const int lfe_ix = CPL ? 6 : nch - 1;
     const int lk = lane - 56;                                   // the LFE bin of this lane in the merged pass
     int lfe_c = 0;
     uint32_t lfe_e = 0, lfe_a = 0;
@@ -196,15 +202,15 @@ __device__ __forceinline__ uint32_t mant_pack_block(const MantBlock &B, const ui
         if (lk >= 0 && lk < 7) lfe_c = B.mdb[(nch - 1) * 256 + lk];
         uint32_t le = 0, la = 0;
 #pragma unroll
-        for (int c2 = 0; c2 < 6; c2++) { le = c2 == nch - 1 ? ew[c2] : le; la = c2 == nch - 1 ? ad[c2] : la; lfe_sh = c2 == nch - 1 ? shv[c2] : lfe_sh; }
+        for (int c2 = 0; c2 < NA; c2++) { le = c2 == lfe_ix ? ew[c2] : le; la = c2 == lfe_ix ? ad[c2] : la; lfe_sh = c2 == lfe_ix ? shv[c2] : lfe_sh; }
         const int srcl = lk >= 0 ? lk >> 2 : 0;
         // (slots 1..3 of an LFE lane: exponent 24, address 0 = bap 0, no bits)
         lfe_e = (((uint32_t)__shfl((int)le, srcl, 64) >> (8 * (lk & 3))) & 0xffu) | 0x18181800u;
         lfe_a = lk < 7 ? ((uint32_t)__shfl((int)la, srcl, 64) >> (8 * (lk & 3))) & 63u : 0u;
     }
 
-    uint32_t st[6][4];          // per coefficient: value (0-15) | list position relative to the pass (16-23) | bits (24-28) | kind (29-30) | opens a code (31)
-    uint32_t bw[6];             // per pass: groups of each kind complete before it (10-bit fields, wave-uniform)
+    uint32_t st[NA][4];         // per coefficient: value (0-15) | list position relative to the pass (16-23) | bits (24-28) | kind (29-30) | opens a code (31)
+    uint32_t bw[NA];            // per pass: groups of each kind complete before it (10-bit fields, wave-uniform)
     int P0 = 0, P1 = 0, P2 = 0; // 3- / 5- / 11-level mantissas of the block so far
 
     int4 nx_c = *reinterpret_cast<const int4 *>(B.mdb + 4 * lane);
@@ -212,7 +218,7 @@ __device__ __forceinline__ uint32_t mant_pack_block(const MantBlock &B, const ui
     // ---- stage 1 ----
     MANT_T0();
 #pragma unroll
-    for (int p = 0; p < 6; p++) {
+    for (int p = 0; p < NA; p++) {
         if (p >= npass) continue;
         int4 c4 = nx_c;
         {
@@ -220,7 +226,8 @@ __device__ __forceinline__ uint32_t mant_pack_block(const MantBlock &B, const ui
             // information was measured too: 123 VGPRs and 1.88 ms per 65 536 frames against 1.78 - the rows wait in registers the
             // passes would rather use, and the loads were never what the wavefronts waited for: a build without them runs 1.74)
             const int nc = p + 1 < npass ? p + 1 : p;
-            nx_c = *reinterpret_cast<const int4 *>(B.mdb + nc * 256 + 4 * lane);
+            if constexpr (CPL) nx_c = *reinterpret_cast<const int4 *>((nc == 0 ? B.mdb : nc == 1 ? B.cplrow : B.mdb + (nc - 1) * 256) + 4 * lane);
+            else nx_c = *reinterpret_cast<const int4 *>(B.mdb + nc * 256 + 4 * lane);
         }
         const bool merged = lfe_rides && p == npass - 1;        // wave-uniform
         const bool lfe_lane = merged && lk >= 0;
@@ -276,8 +283,8 @@ __device__ __forceinline__ uint32_t mant_pack_block(const MantBlock &B, const ui
             B.glist[u ? lpos : (uint32_t)(GL_SINK + lane)] = (uint16_t)q;
             st[p][j] = q | (arel << 16) | (((pw[j] & 0x7fu) | t) << 24);    // (0x80 of t: bit 31; its code bits replace the - zero - plain bits)
         }
-        if (B.tap_bap) {
-            uint8_t *tb = B.tap_bap + p * 256;
+        if (B.tap_bap && !(CPL && p == 1)) {
+            uint8_t *tb = B.tap_bap + (CPL && p > 1 ? p - 1 : p) * 256;
             const uint32_t four = ((pw[0] >> 7) & 15u) | (((pw[1] >> 7) & 15u) << 8) | (((pw[2] >> 7) & 15u) << 16) | (((pw[3] >> 7) & 15u) << 24);
             *reinterpret_cast<uint32_t *>(tb + 4 * lane) = lfe_lane ? 0u : four;
             if (merged) {                                       // the LFE's row: bins 0..6 from lanes 56..62, zeros beyond
@@ -308,7 +315,7 @@ __device__ __forceinline__ uint32_t mant_pack_block(const MantBlock &B, const ui
     // (fields beyond the buffer - a failed search's overflow - land in its last three dwords: the headroom behind the frame's bytes)
     uint32_t *const sink = B.fr + B.frw - 3;
 #pragma unroll
-    for (int p = 0; p < 6; p++) {
+    for (int p = 0; p < NA; p++) {
         if (p >= npass) continue;
         uint32_t mm[4];                                         // the openers' 2nd | 3rd member << 16
 #pragma unroll

@@ -71,6 +71,8 @@ struct PackParams {
     int hint_stride;
     const uint8_t *bsw;         // optional, [S][F][6][nch]: blksw of each channel-block (block switching); null: all 0
     const uint8_t *remat;       // optional, [S][F][6]: 2/0 rematrixing, flags in bits 0-3, rematstr in bit 4; null: none
+    CplWs cpl;                  // channel coupling (enc_cpl_kernel); cpl.word null: none
+    int cpl_begf;
 };
 
 
@@ -83,15 +85,17 @@ struct MaskTabs {
     uint8_t band_start[52];
 };
 
-// The search kernel's LDS: the frame's 36 masking curves, the cost table and the list of run-start rows.
+// The search kernel's LDS: the frame's 36 masking curves (+ 6 of a coupling row), the cost table and the list of run-start rows.
+template <bool CPL>
 struct alignas(16) SearchLDS {
-    int16_t mask[36][50];       // masking curve minus the floor, row blk * nch + ch as exp_stage leaves them (a straight copy)
+    int16_t mask[CPL ? 42 : 36][50];       // masking curve minus the floor, row blk * nch + ch as exp_stage leaves them (a straight copy); 36 + blk: coupling
     uint32_t bitlut[64];        // see "bap of one coefficient" below
     uint8_t strat[6][6];
     uint8_t band_of_bin[256];
     // the frame's run-start rows in (block, channel) order, for the search's sweeps: byte offset of the row's encoded
-    // exponents (bits 0-13) | LFE row (7 coefficients, bit 14) | blocks the run covers (bits 16-21) | mask row (24-29)
-    uint32_t rowdesc[36];
+    // exponents (bits 0-13) | LFE row (7 coefficients, bit 14) | coupling row (bit 15: bins [cplstrtmant, 217) of the
+    // coupling exponents) | blocks the run covers (bits 16-21) | coupled channel (bit 22: bins below cplstrtmant) | mask row (24-29)
+    uint32_t rowdesc[CPL ? 42 : 36];
     // per band of the row being costed (two buffers: the next row's are worked out a row ahead), for each candidate offset:
     // 320 - max(0, ((mask - snroffset) >> 3) & ~3) as int16, so that a coefficient's table address x 4 is
     // clamp(term - 16 exponent, 0, 252)
@@ -259,6 +263,9 @@ struct ExpLDS {
 };
 
 // Runs at the end of enc_mdct_kernel: L.t holds the tables, L.E the six blocks' raw exponents of this channel.
+// KEEP (enc_cpl_kernel, a coupled channel): the strategies are the ones P.strat already holds (mode 0's, from all 256 bins),
+// the rest is recomputed for the P.nbc = cplstrtmant bins the channel codes.
+template <bool KEEP = false>
 __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, int lane)
 {
     const int nch = P.nch;
@@ -272,7 +279,10 @@ __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, in
     //      reduction: each stays below 2^16) ----
     int st[6];
     st[0] = 1;
-    {
+    if constexpr (KEEP) {
+#pragma unroll
+        for (int b = 0; b < 6; b++) st[b] = (int)P.strat[(fidx * 6 + b) * nch + ch];
+    } else {
         const uint32_t d1 = __builtin_amdgcn_sad_u8(raw[1], raw[0], 0u), d2 = __builtin_amdgcn_sad_u8(raw[2], raw[1], 0u);
         const uint32_t d3 = __builtin_amdgcn_sad_u8(raw[3], raw[2], 0u), d4 = __builtin_amdgcn_sad_u8(raw[4], raw[3], 0u);
         const uint32_t d5 = __builtin_amdgcn_sad_u8(raw[5], raw[4], 0u);
@@ -284,7 +294,7 @@ __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, in
     uint32_t starts = 0;                                        // bit b: block b sends exponents (wave-uniform)
 #pragma unroll
     for (int b = 0; b < 6; b++) starts |= (st[b] != 0 ? 1u : 0u) << b;
-    if (!is_lfe) {
+    if (!KEEP && !is_lfe) {
 #pragma unroll
         for (int b = 0; b < 6; b++) {
             if (st[b] == 0) continue;
@@ -843,6 +853,427 @@ void enc_mdct_kernel(const MdctParams P)
 }
 
 
+// ---------------------------------------------------------------------------------------------
+// enc_cpl_kernel: channel coupling (ac3mi_set_encode_coupling 1; the rule is include/ac3mi.h's).  One wavefront per frame,
+// after enc_mdct_kernel, on the rows and exp_samples it left: per block the coupling row (the full-bandwidth rows aligned to
+// the block's smallest exp_samples, summed over [cplstrtmant, 217), >> cpl_g(nfbw)), the exact band energies of the frame
+// (u64 LDS atomics), the frame decision, the coordinates; then, for a coupled frame only, the coupling row's exponent stage
+// (strategies as exp_stage's, exponents from cplstrtmant with 2 cplabsexp in front, masks from cplstrtbnd seeded with the
+// coupling leaks) and the coupled channels' exponent stage again over [0, cplstrtmant) with their mode-0 strategies.  An
+// uncoupled frame keeps everything enc_mdct_kernel wrote: its bytes are mode 0's.
+struct CplParams {
+    const int32_t *mdct;        // [S][F][6][nch][256]
+    const int8_t *shift;        // [S][F][6][nch]
+    const uint8_t *bsw;         // optional [S][F][6][nch]: a frame with a switched full-bandwidth block is not coupled
+    uint8_t *remat;             // optional [S][F][6] (2/0, rematrixing on): rewritten for coupled frames; rows from w.prow
+    int32_t *mdct_out;          // with remat: the coded rows of a coupled frame ([S][F][6][2][256])
+    int8_t *shift_out;
+    CplWs w;
+    ExpParams x;                // the channels' exponent stage, x.nbc = cplstrtmant
+    int nfbw, begf, nfr;
+};
+
+struct CplLDS {
+    ExpLDS X;
+    uint8_t E1[6][256];                 // rematrixing: channel 1's raw exponents while X.E holds channel 0's
+    unsigned long long rq[4][4];        // rematrixing: [L, R, M, S][band] sums of squares of one block
+    unsigned long long en[6][16];       // [coupled channel, 5 = coupling row][band]: sums of squares over the frame
+    unsigned long long score[5][4];     // [channel][mstrcplco]: sum over the bands of the coded coordinate squared
+    int sh[6][8];                       // [block][channel]: exp_samples
+};
+
+constexpr int CPL_FLEAK = 0, CPL_SLEAK = 0;     // cplfleak / cplsleak, sent with cplleake 1 in block 0
+
+__host__ __device__ constexpr int cpl_g(int nfbw) { return nfbw <= 2 ? 1 : nfbw <= 4 ? 2 : 3; }
+
+// The coordinate of one channel and band under mstrcplco M (liba52 parse.c:642-656): the largest value mant 2^-s,
+// E < 15: mant = 16 + m, s = E + 3M + 2;  E = 15: mant = m, s = 16 + 3M, with mant^2 Ecpl <= Ech (exact, 128-bit).
+// Returns E << 4 | m, and mant, s.
+__device__ __forceinline__ int cpl_quant(unsigned long long ech, unsigned long long ecpl, int M, int &mant, int &sv)
+{
+    auto fits = [&](int mt, int s_) {
+        return (unsigned __int128)(unsigned)(mt * mt) * ecpl <= ((unsigned __int128)ech << (2 * s_));
+    };
+    for (int E = 0; E < 15; E++) {
+        const int s_ = E + 3 * M + 2;
+        if (!fits(16, s_)) continue;
+        int m = 15;
+        while (!fits(16 + m, s_)) m--;
+        mant = 16 + m; sv = s_;
+        return E << 4 | m;
+    }
+    const int s_ = 16 + 3 * M;
+    int m = 15;
+    while (m > 0 && !fits(m, s_)) m--;
+    mant = m; sv = s_;
+    return 15 << 4 | m;
+}
+
+// The coupling row's exponents (encode_exp with the coupling start, cf. A/52 7.1.3): entry i of the ne = (ce - cs) / gs
+// entries is the minimum of bins cs + i gs .. + gs - 1; the +-2 constraint as a prefix then a suffix minimum (three entries
+// per lane, one scan over the lane totals per direction); the reference exponent in front, 2 cplabsexp = entry 0 & ~1, goes
+// to bin cs - 1.  Returns the bits of cplabsexp and the groups.
+__device__ int cpl_encode_exp(uint8_t *row, int cs, int ce, int strategy, int lane)
+{
+    constexpr int INF = 0x3fffffff;
+    const int gs = strategy == 1 ? 1 : strategy == 2 ? 2 : 4, ne = (ce - cs) / gs;
+    int g[3], t[3], ix[3];
+    bool valid[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const int i = 3 * lane + c;
+        ix[c] = 2 * i;
+        valid[c] = i < ne;
+        int m = INF;
+        if (valid[c])
+            for (int k = 0; k < gs; k++) { const int e = row[cs + i * gs + k]; m = e < m ? e : m; }
+        g[c] = m;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const int a = valid[c] ? g[c] - ix[c] : INF;
+        t[c] = c == 0 ? a : (a < t[c > 0 ? c - 1 : 0] ? a : t[c > 0 ? c - 1 : 0]);
+    }
+    {
+        const int ex = __builtin_amdgcn_update_dpp(INF, wave_incl_scan_min(t[2]), 0x138, 0xf, 0xf, false);     // wave_shr:1
+#pragma unroll
+        for (int c = 0; c < 3; c++) g[c] = (t[c] < ex ? t[c] : ex) + ix[c];
+    }
+#pragma unroll
+    for (int c = 2; c >= 0; c--) {
+        const int a = valid[c] ? g[c] + ix[c] : INF;
+        t[c] = c == 2 ? a : (a < t[c < 2 ? c + 1 : c] ? a : t[c < 2 ? c + 1 : c]);
+    }
+    {
+        const int suf = wave_suffix_scan_min(t[0], lane);
+        const int ex = __builtin_amdgcn_update_dpp(INF, suf, 0x130, 0xf, 0xf, false);                         // wave_shl:1
+#pragma unroll
+        for (int c = 0; c < 3; c++) g[c] = (t[c] < ex ? t[c] : ex) - ix[c];
+    }
+    const int ref = __builtin_amdgcn_readfirstlane(g[0]) & ~1;
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+        if (valid[c])
+            for (int k = 0; k < gs; k++) row[cs + (3 * lane + c) * gs + k] = (uint8_t)g[c];
+    if (lane == 0) row[cs - 1] = (uint8_t)ref;
+    return 4 + 7 * (ne / 3);
+}
+
+// The coupling row's masking curve (A/52 7.2.2: the coupling channel's loop, no lowcomp), one lane per band: band PSDs of
+// bins [cs, ce) (a band that starts below cs integrates from cs), the leaks seeded with (cplfleak << 8) + 768 and
+// (cplsleak << 8) + 768 before band cplstrtbnd.  Bands outside the coupling range get 0.
+__device__ void cpl_mask_wave(const MaskTabs &T, const uint8_t *row, int16_t *mask, int cs, int ce, int sdecay, int fdecay,
+                              int sgain, int dbknee, int fgain, int halfrate, int lane)
+{
+    constexpr int NEG = -0x3fffffff;
+    const int b = lane, bs = T.band_of_bin[cs], bend = T.band_of_bin[ce - 1] + 1;
+    const bool live = b >= bs && b < bend;
+    int psd = 0;
+    if (live) {
+        const int lo = T.band_start[b] > cs ? T.band_start[b] : cs;
+        const int hi = T.band_start[b + 1] < ce ? T.band_start[b + 1] : ce;
+        psd = 3072 - ((int)row[lo] << 7);
+        for (int j = lo + 1; j < hi; j++) {
+            const int pj = 3072 - ((int)row[j] << 7);
+            int t = (psd > pj ? psd - pj : pj - psd) >> 1;
+            t = t > 255 ? 255 : t;
+            psd = (psd > pj ? psd : pj) + (int)T.latab[t];
+        }
+    }
+    int fast = live ? psd - fgain + b * fdecay : NEG, slow = live ? psd - sgain + b * sdecay : NEG;
+    wave_incl_scan_max2(fast, slow);
+    fast -= b * fdecay;
+    slow -= b * sdecay;
+    const int f0 = (CPL_FLEAK << 8) + 768 - (b - bs + 1) * fdecay, s0 = (CPL_SLEAK << 8) + 768 - (b - bs + 1) * sdecay;
+    fast = fast > f0 ? fast : f0;
+    slow = slow > s0 ? slow : s0;
+    int excite = (int16_t)(fast > slow ? fast : slow);
+    const int t = dbknee - psd;
+    if (t > 0) excite += t >> 2;
+    const int h = T.hth[(b < 50 ? b : 49) >> halfrate];
+    if (b < 50) mask[b] = live ? (int16_t)(excite > h ? excite : h) : (int16_t)0;
+}
+
+__global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
+{
+    __shared__ CplLDS L;
+    const int lane = threadIdx.x;
+    const size_t fidx = blockIdx.x;
+    const int nch = P.x.nch, nfbw = P.nfbw, g = cpl_g(nfbw);
+    const int cs = 37 + 12 * P.begf, ce = 217, nb = 15 - P.begf;
+    const EncTables *tab = P.x.tab;
+    ExpLDS &X = L.X;
+    reinterpret_cast<uint32_t *>(X.t.latab)[lane] = reinterpret_cast<const uint32_t *>(tab->latab)[lane];
+    reinterpret_cast<uint32_t *>(X.t.band_of_bin)[lane] = reinterpret_cast<const uint32_t *>(tab->band_of_bin)[lane];
+    if (lane < 50) X.t.hth[lane] = tab->hth[lane][P.x.fscod];
+    if (lane < 52) X.t.band_start[lane] = lane < 51 ? tab->band_start[lane] : 0;
+    for (int i = lane; i < 6 * 16; i += 64) (&L.en[0][0])[i] = 0;
+    if (lane < 20) (&L.score[0][0])[lane] = 0;
+    const bool rm = P.remat != nullptr;                 // 2/0 with rematrixing: the rows before it (w.prow)
+    if (lane < 6 * nch) L.sh[lane / nch][lane % nch] = rm ? P.w.pshift[fidx * 12 + lane] : P.shift[fidx * 6 * nch + lane];
+    bool decline = false;
+    if (P.bsw) decline = __ballot(lane < 6 * nch && lane % nch < nfbw && P.bsw[fidx * 6 * nch + lane] != 0) != 0;
+    WAVE_SYNC();
+    int fmin = 127;
+    for (int b = 0; b < 6; b++)
+        for (int ch = 0; ch < nfbw; ch++) fmin = L.sh[b][ch] < fmin ? L.sh[b][ch] : fmin;
+
+    // ---- per block: the coupling row, its raw exponents, the energies ----
+    const int32_t *md = rm ? P.w.prow + fidx * 6 * 2 * 256 : P.mdct + fidx * 6 * nch * 256;
+    for (int b = 0; b < 6; b++) {
+        int shb = 127;
+        for (int ch = 0; ch < nfbw; ch++) shb = L.sh[b][ch] < shb ? L.sh[b][ch] : shb;
+        int S[4] = {0, 0, 0, 0};
+#pragma unroll 1
+        for (int ch = 0; ch < nfbw; ch++) {
+            const int sc = L.sh[b][ch];
+            const int4 cv = *reinterpret_cast<const int4 *>(md + (b * nch + ch) * 256 + 4 * lane);
+            const int c4[4] = {cv.x, cv.y, cv.z, cv.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int j = 4 * lane + k;
+                if (j >= cs && j < ce) {
+                    S[k] += c4[k] >> (sc - shb);
+                    const int a = c4[k] >> (sc - fmin);
+                    atomicAdd(&L.en[ch][(j - cs) / 12], (unsigned long long)((long long)a * a));
+                }
+            }
+        }
+        int cr[4];
+        uint32_t epack = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int j = 4 * lane + k;
+            int v = j >= cs && j < ce ? S[k] >> g : 0;
+            const int a = v < 0 ? -v : v;
+            int e = 24;
+            if (a) {
+                e = 23 - ilog2u((unsigned)a) + shb;
+                if (e >= 24) { e = 24; v = 0; }
+            }
+            cr[k] = v;
+            epack |= (uint32_t)e << (8 * k);
+            if (v) { const int q = v >> (shb - fmin); atomicAdd(&L.en[5][(j - cs) / 12], (unsigned long long)((long long)q * q)); }
+        }
+        *reinterpret_cast<int4 *>(P.w.mdct + (fidx * 6 + b) * 256 + 4 * lane) = make_int4(cr[0], cr[1], cr[2], cr[3]);
+        *reinterpret_cast<uint32_t *>(&X.E[b][4 * lane]) = epack;
+        if (lane == 0) P.w.shift[fidx * 8 + b] = (int8_t)shb;
+    }
+    WAVE_SYNC();
+
+    // ---- the frame decision: no band where 4 E(sum) < sum of the channels' E, E(sum) = 2^(2 g) E(coupling row) ----
+    {
+        unsigned long long tot = 0;
+        if (lane < nb)
+            for (int ch = 0; ch < nfbw; ch++) tot += L.en[ch][lane];
+        decline = decline || __ballot(lane < nb && (L.en[5][lane < nb ? lane : 0] << (2 * g + 2)) < tot) != 0;
+    }
+    if (decline) {
+        if (lane == 0) P.w.word[fidx] = 0;
+        return;
+    }
+
+    // ---- coordinates: per channel and band, for every mstrcplco; the channel's mstrcplco maximises the sum over its bands of
+    //      the coded coordinate squared (ties: the smaller) ----
+    int code[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const int i = lane + 64 * r;
+        if (i < nfbw * nb) {
+            const int ch = i / nb, bd = i - ch * nb;
+#pragma unroll
+            for (int M = 0; M < 4; M++) {
+                int mant, sv;
+                code[r][M] = cpl_quant(L.en[ch][bd], L.en[5][bd], M, mant, sv);
+                atomicAdd(&L.score[ch][M], (unsigned long long)(mant * mant) << (50 - 2 * sv));
+            }
+        }
+    }
+    WAVE_SYNC();
+    uint32_t word = 1;
+    for (int ch = 0; ch < nfbw; ch++) {
+        int best = 0;
+        for (int M = 1; M < 4; M++) best = L.score[ch][M] > L.score[ch][best] ? M : best;
+        word |= (uint32_t)best << (8 + 2 * ch);
+    }
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const int i = lane + 64 * r;
+        if (i < nfbw * nb) {
+            const int ch = i / nb, bd = i - ch * nb, M = (word >> (8 + 2 * ch)) & 3;
+            const int cd = M == 0 ? code[r][0] : M == 1 ? code[r][1] : M == 2 ? code[r][2] : code[r][3];
+            P.w.co[fidx * 80 + ch * 16 + bd] = (uint8_t)cd;
+        }
+    }
+    if (lane == 0) P.w.word[fidx] = word;
+
+    // ---- the coupling row's exponent stage ----
+    {
+        uint32_t raw[6];
+#pragma unroll
+        for (int b = 0; b < 6; b++) raw[b] = *reinterpret_cast<const uint32_t *>(&X.E[b][4 * lane]);
+        int st[6];
+        st[0] = 1;
+        {
+            const uint32_t d1 = __builtin_amdgcn_sad_u8(raw[1], raw[0], 0u), d2 = __builtin_amdgcn_sad_u8(raw[2], raw[1], 0u);
+            const uint32_t d3 = __builtin_amdgcn_sad_u8(raw[3], raw[2], 0u), d4 = __builtin_amdgcn_sad_u8(raw[4], raw[3], 0u);
+            const uint32_t d5 = __builtin_amdgcn_sad_u8(raw[5], raw[4], 0u);
+            const uint32_t t12 = wave_sum_u32(d1 | d2 << 16), t34 = wave_sum_u32(d3 | d4 << 16), t5 = wave_sum_u32(d5);
+            st[1] = (t12 & 0xffffu) > 1000u; st[2] = (t12 >> 16) > 1000u;
+            st[3] = (t34 & 0xffffu) > 1000u; st[4] = (t34 >> 16) > 1000u;
+            st[5] = t5 > 1000u;
+        }
+        uint32_t starts = 0;
+#pragma unroll
+        for (int b = 0; b < 6; b++) starts |= (st[b] != 0 ? 1u : 0u) << b;
+#pragma unroll
+        for (int b = 0; b < 6; b++) {
+            if (st[b] == 0) continue;
+            int run = 1;
+#pragma unroll
+            for (int e = 1; e < 6; e++) if (b + e < 6 && run == e && st[b + e] == 0) run = e + 1;
+            st[b] = run == 1 ? 3 : run <= 3 ? 2 : 1;
+        }
+        uint32_t inside = 0;
+#pragma unroll
+        for (int c = 0; c < 4; c++) inside |= (4 * lane + c >= cs && 4 * lane + c < ce ? 0xffu : 0u) << (8 * c);
+#pragma unroll
+        for (int b = 0; b < 5; b++) {
+            if (!((starts >> b) & 1u)) continue;
+            bool open = true, touched = false;
+#pragma unroll
+            for (int e = b + 1; e < 6; e++) {
+                open = open && !((starts >> e) & 1u);
+                if (open) { raw[b] = bytes_min_where(raw[b], raw[e], inside); touched = true; }
+            }
+            if (touched) *reinterpret_cast<uint32_t *>(&X.E[b][4 * lane]) = raw[b];
+        }
+        WAVE_SYNC();
+        int bits = 0;
+        for (uint32_t m = starts; m; m &= m - 1) {
+            const int b = __builtin_ctz(m);
+            bits += cpl_encode_exp(X.E[b], cs, ce, st[b], lane);
+        }
+        WAVE_SYNC();
+        constexpr int sdecaycod = 2, fdecaycod = 1, fgaincod = 4, sgaincod = 1, dbkneecod = 2;
+        const int sdecay = enc_sdecay(sdecaycod) >> P.x.halfrate, fdecay = enc_fdecay(fdecaycod) >> P.x.halfrate;
+        for (uint32_t m = starts; m; m &= m - 1) {
+            const int b = __builtin_ctz(m);
+            cpl_mask_wave(X.t, X.E[b], X.mask[b], cs, ce, sdecay, fdecay, enc_sgain(sgaincod), enc_dbknee(dbkneecod),
+                          enc_fgain(fgaincod), P.x.halfrate, lane);
+        }
+        WAVE_SYNC();
+        int src = 0;
+        for (int b = 0; b < 6; b++) {
+            src = ((starts >> b) & 1u) ? b : src;
+            *reinterpret_cast<uint32_t *>(P.w.eexp + (fidx * 6 + b) * 256 + 4 * lane) = *reinterpret_cast<const uint32_t *>(&X.E[src][4 * lane]);
+            if (lane < 50) P.w.emask[(fidx * 6 + b) * 50 + lane] = (int16_t)(X.mask[src][lane] - enc_floor(4));
+        }
+        if (lane < 6) P.w.strat[fidx * 8 + lane] = (uint8_t)(lane == 0 ? st[0] : lane == 1 ? st[1] : lane == 2 ? st[2] : lane == 3 ? st[3] : lane == 4 ? st[4] : st[5]);
+        if (lane == 0) P.w.ebits[fidx] = bits;
+        WAVE_SYNC();
+    }
+
+    if (rm) {
+        // ---- 2/0 with rematrixing: the mode-1 rule again, over liba52's cplinu-1 bands (the last ends at cplstrtmant); the
+        //      coded rows, their exp_samples and exponents (strategies from them, as enc_mdct_kernel<*, true> does) ----
+        const int nrem = P.begf == 0 ? 2 : P.begf <= 2 ? 3 : 4;
+        auto band_of = [&](int j) { return j < 13 || j >= cs ? -1 : j < 25 ? 0 : j < 37 ? 1 : j < 61 ? 2 : 3; };
+        int prev = 0;
+        for (int b = 0; b < 6; b++) {
+            if (lane < 16) (&L.rq[0][0])[lane] = 0;
+            WAVE_SYNC();
+            const int vl = L.sh[b][0], vr = L.sh[b][1], vm = vl < vr ? vl : vr;
+            const int4 lv = *reinterpret_cast<const int4 *>(md + (b * 2) * 256 + 4 * lane);
+            const int4 rv = *reinterpret_cast<const int4 *>(md + (b * 2 + 1) * 256 + 4 * lane);
+            const int lc[4] = {lv.x, lv.y, lv.z, lv.w}, rc[4] = {rv.x, rv.y, rv.z, rv.w};
+            int a[4], c[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                a[k] = lc[k] >> (vl - vm);
+                c[k] = rc[k] >> (vr - vm);
+                const int bd = band_of(4 * lane + k);
+                if (bd >= 0) {
+                    const long long m = (a[k] + c[k]) >> 1, d = (a[k] - c[k]) >> 1;
+                    atomicAdd(&L.rq[0][bd], (unsigned long long)((long long)a[k] * a[k]));
+                    atomicAdd(&L.rq[1][bd], (unsigned long long)((long long)c[k] * c[k]));
+                    atomicAdd(&L.rq[2][bd], (unsigned long long)(m * m));
+                    atomicAdd(&L.rq[3][bd], (unsigned long long)(d * d));
+                }
+            }
+            WAVE_SYNC();
+            int flags = 0;
+            if (!P.bsw || P.bsw[(fidx * 6 + b) * 2] == P.bsw[(fidx * 6 + b) * 2 + 1])
+                for (int bd = 0; bd < nrem; bd++) {
+                    const unsigned long long ems = L.rq[2][bd] < L.rq[3][bd] ? L.rq[2][bd] : L.rq[3][bd];
+                    const unsigned long long elr = L.rq[0][bd] < L.rq[1][bd] ? L.rq[0][bd] : L.rq[1][bd];
+                    if (2 * ems < elr) flags |= 1 << bd;
+                }
+            uint32_t ep[2] = {0, 0};
+            int out[2][4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int bd = band_of(4 * lane + k);
+                int x0 = flags ? a[k] : lc[k], x1 = flags ? c[k] : rc[k];
+                if (bd >= 0 && ((flags >> bd) & 1)) { x0 = (a[k] + c[k]) >> 1; x1 = (a[k] - c[k]) >> 1; }
+                const int xs[2] = {x0, x1};
+#pragma unroll
+                for (int ch = 0; ch < 2; ch++) {
+                    const int sh = flags ? vm : L.sh[b][ch];
+                    int x = xs[ch];
+                    const int ax = x < 0 ? -x : x;
+                    int e = 24;
+                    if (ax) {
+                        e = 23 - ilog2u((unsigned)ax) + sh;
+                        if (e >= 24) { e = 24; x = 0; }
+                    }
+                    out[ch][k] = x;
+                    ep[ch] |= (uint32_t)(e & 0xff) << (8 * k);
+                }
+            }
+#pragma unroll
+            for (int ch = 0; ch < 2; ch++) {
+                const size_t row = (fidx * 6 + b) * 2 + ch;
+                *reinterpret_cast<int4 *>(P.mdct_out + row * 256 + 4 * lane) = make_int4(out[ch][0], out[ch][1], out[ch][2], out[ch][3]);
+                if (lane == 0) P.shift_out[row] = (int8_t)(flags ? vm : L.sh[b][ch]);
+            }
+            *reinterpret_cast<uint32_t *>(&X.E[b][4 * lane]) = ep[0];
+            *reinterpret_cast<uint32_t *>(&L.E1[b][4 * lane]) = ep[1];
+            if (lane == 0) P.remat[fidx * 6 + b] = (uint8_t)(flags | (b == 0 || flags != prev ? 0x10 : 0));
+            prev = flags;
+        }
+        WAVE_SYNC();
+        exp_stage(P.x, X, fidx, 0, lane);
+        WAVE_SYNC();
+#pragma unroll
+        for (int b = 0; b < 6; b++) *reinterpret_cast<uint32_t *>(&X.E[b][4 * lane]) = *reinterpret_cast<const uint32_t *>(&L.E1[b][4 * lane]);
+        WAVE_SYNC();
+        exp_stage(P.x, X, fidx, 1, lane);
+        return;
+    }
+
+    // ---- the coupled channels' exponent stage over [0, cplstrtmant), with their mode-0 strategies ----
+    for (int ch = 0; ch < nfbw; ch++) {
+        for (int b = 0; b < 6; b++) {
+            const int shc = L.sh[b][ch];
+            const int4 cv = *reinterpret_cast<const int4 *>(md + (b * nch + ch) * 256 + 4 * lane);
+            const int c4[4] = {cv.x, cv.y, cv.z, cv.w};
+            uint32_t epack = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int a = c4[k] < 0 ? -c4[k] : c4[k];
+                const int e = 4 * lane + k >= 223 || a == 0 ? 24 : 23 - ilog2u((unsigned)a) + shc;
+                epack |= (uint32_t)(e & 0xff) << (8 * k);
+            }
+            *reinterpret_cast<uint32_t *>(&X.E[b][4 * lane]) = epack;
+        }
+        WAVE_SYNC();
+        exp_stage<true>(P.x, X, fidx, ch, lane);
+        WAVE_SYNC();
+    }
+}
+
+
 // bap of one coefficient for SNR offset `snroffset` (:393-420):
 //   v = ((max(mask - snroffset - floor, 0)) & 0x1fe0) + floor,  address = (psd - v) >> 5,  psd = 3072 - 128 exp
 //   =>  address = clamp(80 - 4 exp - max(0, (mask - floor - snroffset) >> 5), 0, 63)       (floor = 0x1f0)
@@ -952,11 +1383,12 @@ __device__ unsigned long long g_pack_cycles[16];
 #define ENC_SEARCH_LB 4          // 128 VGPRs; a fifth wavefront per SIMD (96 VGPRs, 28 bytes of scratch) measured the same 1.02 ms
 #endif
 // enc_search_kernel<1>: one wavefront per stream, frames in order; <3>: one wavefront per frame tabulates (see above).
-template <int PART>
+// CPL (enc_search_cpl_kernel: channel coupling on, P.cpl): the coupling rows join the costed rows of a coupled frame.
+template <int PART, bool CPL = false>
 __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const PackParams P)
 {
     static_assert(PART == 1 || PART == 3, "the packers are enc_packf_kernel / enc_packb_kernel");
-    __shared__ SearchLDS L;
+    __shared__ SearchLDS<CPL> L;
     const int lane = threadIdx.x;
     constexpr bool PER_FRAME = PART == 3;
     const int s = PER_FRAME ? (int)(blockIdx.x / (unsigned)P.frames_per_stream) : (int)blockIdx.x;
@@ -974,6 +1406,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
     const int fs = P.frame_words;
 
     const int sslot = P.slot ? P.slot[s] : s;
+    const int cpl_cs = 37 + 12 * P.cpl_begf;        // (coupling only)
     // the stream's search state: csnroffst in bits 0-7, the fsnroffst of its last coded frame in bits 8-11 (what the
     // reference's s->csnroffst / s->fsnroffst[] hold between frames, ENC/ac3enc.cpp:969-972)
     const int state_in = P.csnr_state[sslot];
@@ -987,6 +1420,9 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
         const uint8_t *ex = P.eexp + fidx * 6 * nch * 256;
         int frame_bits = 0;
         uint64_t run_starts = 0, row_set = 0;
+        int ncplrows = 0;                                           // coupling run-start rows behind the channels' in rowdesc
+        const bool cplf = CPL && (__builtin_amdgcn_readfirstlane((int)P.cpl.word[fidx]) & 1);
+        const uint8_t *cex = cplf ? P.cpl.eexp + fidx * 6 * 256 : ex;
         bool loaded = false;
         auto load_frame = [&]() {
             loaded = true;
@@ -1022,7 +1458,8 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                     const uint32_t later = (uint32_t)((run_starts >> (8 * c6)) & 0x3f) | 0x40u;       // bit b: block b of this channel sends exponents
                     const int b1 = __builtin_ctz(later >> (b6 + 1)) + b6 + 1;
                     const uint32_t cover = ((1u << b1) - 1u) & ~((1u << b6) - 1u);
-                    const uint32_t d = (uint32_t)((b6 * nch + c6) * 256) | ((P.lfe && c6 == nch - 1) ? 1u << 14 : 0u) | (cover << 16) | ((uint32_t)(b6 * nch + c6) << 24);
+                    uint32_t d = (uint32_t)((b6 * nch + c6) * 256) | ((P.lfe && c6 == nch - 1) ? 1u << 14 : 0u) | (cover << 16) | ((uint32_t)(b6 * nch + c6) << 24);
+                    if constexpr (CPL) d |= cplf && c6 < nfbw ? 1u << 22 : 0u;
                     L.rowdesc[__builtin_popcountll(row_set & ((1ull << lane) - 1ull))] = d;
                 }
             }
@@ -1042,6 +1479,33 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                 // rematrixing: the four flags of every block 1..5 that sends them (block 0's stay uncounted, as above)
                 if (P.remat)
                     for (int b = 1; b < 6; b++) frame_bits += (P.remat[fidx * 6 + b] & 0x10) ? 4 : 0;
+                if (CPL && cplf) {
+                    // coupling: chincpl, phsflginu (2/0), cplbegf / cplendf, cplbndstrc; cplcoe, mstrcplco and the coordinates
+                    // in block 0, cplcoe 0 in blocks 1..5; cplexpstr; cplfsnroffst / cplfgaincod; cplleake (+ the two leaks in
+                    // block 0); the coupling exponents; no chbwcod for the coupled channels
+                    const int nb = 15 - P.cpl_begf;
+                    frame_bits += nfbw + (P.acmod == 2 ? 1 : 0) + 8 + (nb - 1) + nfbw * (3 + 8 * nb) + 5 * nfbw + 6 * 2 + 7 + 7 + 5;
+                    frame_bits += __builtin_amdgcn_readfirstlane(P.cpl.ebits[fidx]) - 6 * __builtin_popcountll(row_set & fbw_rows);
+                    if (P.remat) {                  // a coupled frame's blocks 1..5 send liba52's cplinu-1 flag count, not 4
+                        const int nrem = P.cpl_begf == 0 ? 2 : P.cpl_begf <= 2 ? 3 : 4;
+                        for (int b = 1; b < 6; b++) frame_bits -= (P.remat[fidx * 6 + b] & 0x10) ? 4 - nrem : 0;
+                    }
+                }
+            }
+            if constexpr (CPL) if (cplf) {
+                // the coupling rows: masks to rows 36.., run starts behind the channels' in rowdesc
+                const uint32_t *gm = reinterpret_cast<const uint32_t *>(P.cpl.emask + fidx * 6 * 50);
+                for (int i = lane; i < 150; i += 64) reinterpret_cast<uint32_t *>(&L.mask[36][0])[i] = gm[i];
+                const int st = lane < 6 ? (int)P.cpl.strat[fidx * 8 + lane] : 0;
+                const uint32_t cst = (uint32_t)__ballot(lane < 6 && st != 0) | 0x40u;
+                const int n0 = __builtin_popcountll(row_set);
+                if (lane < 6 && st != 0) {
+                    const int b1 = __builtin_ctz(cst >> (lane + 1)) + lane + 1;
+                    const uint32_t cover = ((1u << b1) - 1u) & ~((1u << lane) - 1u);
+                    L.rowdesc[n0 + __builtin_popcount(cst & ((1u << lane) - 1u))] = (uint32_t)(lane * 256) | (1u << 15) | (cover << 16) | ((uint32_t)(36 + lane) << 24);
+                }
+                ncplrows = __builtin_popcount(cst & 0x3fu);
+                WAVE_SYNC();
             }
         };
         // PART 1 replays the search from tabulated verdicts and needs the frame's data only for a verdict that is missing
@@ -1114,9 +1578,12 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
             {
                 // one run-start row per step: four bins per lane from one dword (HBM/L2); the exponent dwords of the next
                 // three rows are in flight while one is costed
-                const int nrows = __builtin_popcountll(row_set);
+                const int nrows = __builtin_popcountll(row_set) + (CPL ? ncplrows : 0);
                 auto desc_of = [&](int i) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)L.rowdesc[i < nrows ? i : nrows - 1]); };
-                auto fetch = [&](uint32_t d) { return *reinterpret_cast<const uint32_t *>(ex + (d & 0x3fffu) + 4 * lane); };
+                auto fetch = [&](uint32_t d) {
+                    if constexpr (CPL) return *reinterpret_cast<const uint32_t *>(((d & (1u << 15)) ? cex : ex) + (d & 0x3fffu) + 4 * lane);
+                    else return *reinterpret_cast<const uint32_t *>(ex + (d & 0x3fffu) + 4 * lane);
+                };
                 uint32_t d0 = desc_of(0), d1 = desc_of(1), d2 = desc_of(2);
                 uint32_t ev = fetch(d0), ev1 = fetch(d1), ev2 = fetch(d2);
                 static_assert(ENC_NC == 3, "two packed candidates + one");
@@ -1145,7 +1612,13 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                     const uint32_t ev3 = fetch(d3);
                     if (i + 1 < nrows) terms(d1, (i + 1) & 1);
                     const char *Tr = reinterpret_cast<const char *>(&L.terms[i & 1][0]);
-                    const uint32_t em = ev | ((d0 & (1u << 14)) ? um_lfe : um_fbw);
+                    uint32_t em;
+                    if constexpr (CPL) {
+                        const uint32_t um_cch = beyond(cpl_cs), um_cpl = ~beyond(cpl_cs) | beyond(217);
+                        em = ev | ((d0 & (1u << 14)) ? um_lfe : (d0 & (1u << 15)) ? um_cpl : (d0 & (1u << 22)) ? um_cch : um_fbw);
+                    } else {
+                        em = ev | ((d0 & (1u << 14)) ? um_lfe : um_fbw);
+                    }
                     uint32_t sum[ENC_NC];
 #pragma unroll
                     for (int c = 0; c < ENC_NC; c++) sum[c] = 0;
@@ -1395,12 +1868,14 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
 }
 
 
+
 // ---------------------------------------------------------------------------------------------
 // enc_packf_kernel: a frame whose SNR offsets are known (P.snr, from enc_search_kernel<1>) is packed by ONE wavefront -
 // the packer of large batches.  Header, side information and exponent groups as wave-uniform fields through a 64-bit
 // scalar accumulator, the mantissas block by block on enc_mant.h, both CRCs, the frame out.
+template <bool CPL>
 struct alignas(16) PackfLDS {
-    int16_t mask[6][50];                // this block's masking curves as band terms (mant_band_terms), one row per channel
+    int16_t mask[CPL ? 7 : 6][50];  // this block's masking curves as band terms (mant_band_terms), one row per channel (+ coupling)
     uint32_t packlut[64];               // mant_pack_word per bap table address
     alignas(16) uint16_t glist[GL_ENTRIES];
     alignas(4) uint8_t erow[256];       // encoded exponents of the channel whose exponent groups are being packed
@@ -1413,10 +1888,12 @@ struct alignas(16) PackfLDS {
 #endif
 // FIXED51: the 5.1 configuration (five full-bandwidth channels + LFE, acmod 7) as compile-time constants - the shape large batches
 // have; its five mantissa passes, the merged LFE lanes and the side information's field list then need no tests
-template <bool FIXED51>
+// CPL: coupled frames (channel coupling on, never with FIXED51): the coupling fields, exponents and mantissa pass
+template <bool FIXED51, bool CPL = false>
 __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackParams P)
 {
-    __shared__ PackfLDS L;
+    static_assert(!(FIXED51 && CPL), "coupled frames take the generic packer");
+    __shared__ PackfLDS<CPL> L;
     extern __shared__ uint4 pk_dyn[];
     uint32_t *fr = reinterpret_cast<uint32_t *>(pk_dyn);
     const int lane = threadIdx.x;
@@ -1441,6 +1918,10 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
     // 1.84.  Wavefronts that start together stay in step - all in their scalar side information, then all in their mantissa
     // passes - and the units they share are used in turns instead of side by side; the dispatcher's staggered starts mix the phases.)
     const size_t fidx = blockIdx.x;
+    // channel coupling (enc_cpl_kernel): every full-bandwidth channel in coupling, one set of coordinates in block 0
+    const uint32_t cplw = CPL ? (uint32_t)__builtin_amdgcn_readfirstlane((int)P.cpl.word[fidx]) : 0u;
+    const bool cplf = (cplw & 1u) != 0;
+    const int cs = 37 + 12 * P.cpl_begf, ncb = 15 - P.cpl_begf;
     PK_T0();
     PK_COUNT(7);
     for (int i = lane; i < P.frw / 4; i += 64) reinterpret_cast<uint4 *>(fr)[i] = make_uint4(0, 0, 0, 0);
@@ -1499,6 +1980,15 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         uint32_t ew[6];
 #pragma unroll
         for (int ch = 0; ch < 6; ch++) ew[ch] = ch < nch ? *reinterpret_cast<const uint32_t *>(ex + ((size_t)b * nch + ch) * 256 + 4 * lane) : 0u;
+        uint32_t cew = 0;
+        int cstg = 0;
+        if (cplf) {
+            cew = *reinterpret_cast<const uint32_t *>(P.cpl.eexp + (fidx * 6 + b) * 256 + 4 * lane);
+            cstg = __builtin_amdgcn_readfirstlane((int)P.cpl.strat[fidx * 8 + b]);
+            if (lane < 25)
+                reinterpret_cast<uint32_t *>(&L.mask[CPL ? 6 : 0][0])[lane] =
+                    mant_band_terms(reinterpret_cast<const uint32_t *>(P.cpl.emask + (fidx * 6 + b) * 50)[lane], snroffset);
+        }
         {                                           // this block's mask rows (25 dwords per channel), in flight during the side information
             const uint32_t *gm = reinterpret_cast<const uint32_t *>(P.emask + (fidx * 6 + b) * nch * 50);
             uint32_t mv[3];
@@ -1516,24 +2006,68 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
             for (int ch = 0; ch < nfbw; ch++) put(1, 0);
         for (int ch = 0; ch < nfbw; ch++) put(1, 1);
         put(1, 0);
-        if (b == 0) { put(1, 1); put(1, 0); } else put(1, 0);
+        if (cplf) {
+            // cplstre, cplinu, chincpl, phsflginu, cplbegf, cplendf, cplbndstrc (all 0); cplcoe, mstrcplco, the coordinates
+            if (b == 0) {
+                put(1, 1); put(1, 1);
+                for (int ch = 0; ch < nfbw; ch++) put(1, 1);
+                if (acmod == 2) put(1, 0);
+                put(4, (uint32_t)P.cpl_begf); put(4, 12); put(ncb - 1, 0);
+                flush();
+                const uint8_t *co = P.cpl.co + fidx * 80;
+                for (int ch = 0; ch < nfbw; ch++) {
+                    put(1, 1); put(2, (cplw >> (8 + 2 * ch)) & 3u);
+                    for (int bd = 0; bd < ncb; bd++) { put(8, co[ch * 16 + bd]); if ((bd & 3) == 3) flush(); }
+                    flush();
+                }
+            } else {
+                put(1, 0);
+                for (int ch = 0; ch < nfbw; ch++) put(1, 0);
+            }
+        } else if (b == 0) { put(1, 1); put(1, 0); } else put(1, 0);
         if (acmod == 2) {
-            if (P.remat) {
+            if (cplf) {                     // liba52's band set for cplinu 1: 2, 3 or 4 flags
+                const int nrem = P.cpl_begf == 0 ? 2 : P.cpl_begf <= 2 ? 3 : 4;
+                if (P.remat) {
+                    const uint32_t r = P.remat[fidx * 6 + b];
+                    put(1, r >> 4);
+                    if (r & 0x10) for (int i = 0; i < nrem; i++) put(1, (r >> i) & 1);
+                } else if (b == 0) { put(1, 1); put(nrem, 0); } else put(1, 0);
+            } else if (P.remat) {
                 const uint32_t r = P.remat[fidx * 6 + b];
                 put(1, r >> 4);
                 if (r & 0x10) { put(1, r & 1); put(1, (r >> 1) & 1); put(1, (r >> 2) & 1); put(1, (r >> 3) & 1); }
             } else if (b == 0) { put(1, 1); put(4, 0); } else put(1, 0);
         }
+        if (cplf) put(2, (uint32_t)cstg);
         for (int ch = 0; ch < nfbw; ch++) put(2, strat_of(ch));
         if (lfe) put(1, strat_of(nch - 1));
-        for (int ch = 0; ch < nfbw; ch++) if (strat_of(ch) != 0) put(6, P.chbwcod);
+        for (int ch = 0; ch < nfbw; ch++) if (strat_of(ch) != 0 && !cplf) put(6, P.chbwcod);
+        if (cplf && cstg != 0) {
+            // the coupling exponents: cplabsexp (bin cs - 1 holds 2 cplabsexp), groups from cplstrtmant
+            const int gs = cstg == 1 ? 1 : cstg == 2 ? 2 : 4;
+            const int ng = (217 - cs) / (3 * gs);
+            const uint8_t *e = &L.erow[0];
+            WAVE_SYNC();
+            *reinterpret_cast<uint32_t *>(&L.erow[4 * lane]) = cew;
+            WAVE_SYNC();
+            put(4, (uint32_t)__builtin_amdgcn_readfirstlane((int)e[cs - 1]) >> 1);
+            flush();
+            for (int g = lane; g < ng; g += 64) {
+                const int k0 = cs + 3 * g * gs;
+                const int prev = g ? e[k0 - gs] : e[cs - 1];
+                const int d0 = e[k0] - prev + 2, d1 = e[k0 + gs] - e[k0] + 2, d2 = e[k0 + 2 * gs] - e[k0 + gs] + 2;
+                put_bits(fr, P.frw, pos + 7 * g, 7, (uint32_t)((d0 * 5 + d1) * 5 + d2));
+            }
+            pos += 7 * ng;
+        }
         // exponents: lanes over groups
         for (int ch = 0; ch < nch; ch++) {
             const int stg = (int)strat_of(ch);
             if (stg == 0) continue;
             const bool is_lfe = lfe && ch == nch - 1;
             const int gs = stg == 1 ? 1 : stg == 2 ? 2 : 4;
-            const int ng = ((is_lfe ? 7 : nbc) + gs * 3 - 4) / (3 * gs);
+            const int ng = ((is_lfe ? 7 : cplf ? cs : nbc) + gs * 3 - 4) / (3 * gs);
             const uint8_t *e = &L.erow[0];
             {
                 uint32_t row = 0;
@@ -1560,7 +2094,12 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         put(1, b == 0);
         if (b == 0) {
             put(6, csnr);
+            if (cplf) { put(4, fsnr); put(3, fgaincod); flush(); }
             for (int ch = 0; ch < nch; ch++) { put(4, fsnr); put(3, fgaincod); }
+        }
+        if (cplf) {                         // cplleake (+ cplfleak, cplsleak in block 0)
+            put(1, b == 0);
+            if (b == 0) { put(3, CPL_FLEAK); put(3, CPL_SLEAK); }
         }
         put(1, 0);
         put(1, 0);
@@ -1572,17 +2111,57 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
             int shv[6];
 #pragma unroll
             for (int ch = 0; ch < 6; ch++) shv[ch] = __builtin_amdgcn_readlane(shift_l, 6 * b + ch);
-            uint32_t ad[6];
-            int neg;
-            uint32_t em[6];
-            mant_block_addresses(ad, em, neg, ew, shv, L.mask, bandoff, nch, nbc, lfe, lane);
-            PK_LAP(8);
-            MantBlock B;
-            B.fr = fr; B.frw = P.frw; B.glist = L.glist; B.packlut = L.packlut;
-            B.mdb = md + (size_t)b * nch * 256;
-            B.tap_bap = P.tap_bap ? P.tap_bap + (fidx * 6 + b) * nch * 256 : nullptr;
-            B.nch = nch; B.nbc = nbc; B.lfe = lfe; B.marker = (uint32_t)P.marker;
-            pos = mant_pack_block(B, em, ad, shv, __ballot(neg < 0) != 0, pos, lane);
+            if (CPL && cplf) {
+                MantBlock B;
+                B.fr = fr; B.frw = P.frw; B.glist = L.glist; B.packlut = L.packlut;
+                B.mdb = md + (size_t)b * nch * 256;
+                B.tap_bap = P.tap_bap ? P.tap_bap + (fidx * 6 + b) * nch * 256 : nullptr;
+                B.nch = nch; B.nbc = nbc; B.lfe = lfe; B.marker = (uint32_t)P.marker;
+                // per pass: channel 0, the coupling row, channels 1.. (bins below cplstrtmant / in [cplstrtmant, 217)), LFE at 6
+                const int csh = __builtin_amdgcn_readfirstlane((int)P.cpl.shift[fidx * 8 + b]);
+                auto beyond = [&](int n) { const int k = n - 4 * lane; return k >= 4 ? 0u : k <= 0 ? 0xffffffffu : 0xffffffffu << (8 * k); };
+                const uint32_t um_cch = beyond(cs), um_cpl = ~beyond(cs) | beyond(217), um_lfe = beyond(7);
+                uint32_t ad7[7], em7[7];
+                int sh7[7], neg = 0;
+#pragma unroll
+                for (int p = 0; p < 7; p++) {
+                    const int c = p == 0 ? 0 : p == 6 ? nch - 1 : p - 1;
+                    const bool on = p == 1 || (p == 6 ? lfe : p == 0 || p - 1 < nfbw);
+                    uint32_t e = 0;
+                    int sv = 0, trow = 0;
+#pragma unroll
+                    for (int c2 = 0; c2 < 6; c2++) { e = c2 == c ? ew[c2] : e; sv = c2 == c ? shv[c2] : sv; }
+                    trow = c;
+                    if (p == 1) { e = cew; sv = csh; trow = 6; }
+                    ad7[p] = 0; em7[p] = 0; sh7[p] = sv;
+                    if (on) {
+                        em7[p] = e | (p == 1 ? um_cpl : p == 6 ? um_lfe : um_cch);
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            const int xe = (int)((em7[p] >> (8 * j)) & 0xff);
+                            int a = (int)L.mask[trow][(bandoff >> (8 * j)) & 0xff] - 4 * xe;
+                            a = a < 0 ? 0 : a > 63 ? 63 : a;
+                            ad7[p] |= (uint32_t)a << (8 * j);
+                            neg |= xe - sv;
+                        }
+                    }
+                }
+                PK_LAP(8);
+                B.cplrow = P.cpl.mdct + (fidx * 6 + b) * 256;
+                pos = mant_pack_block<true>(B, em7, ad7, sh7, __ballot(neg < 0) != 0, pos, lane);
+            } else {
+                uint32_t ad[6];
+                int neg;
+                uint32_t em[6];
+                mant_block_addresses(ad, em, neg, ew, shv, L.mask, bandoff, nch, nbc, lfe, lane);
+                PK_LAP(8);
+                MantBlock B;
+                B.fr = fr; B.frw = P.frw; B.glist = L.glist; B.packlut = L.packlut;
+                B.mdb = md + (size_t)b * nch * 256;
+                B.tap_bap = P.tap_bap ? P.tap_bap + (fidx * 6 + b) * nch * 256 : nullptr;
+                B.nch = nch; B.nbc = nbc; B.lfe = lfe; B.marker = (uint32_t)P.marker;
+                pos = mant_pack_block(B, em, ad, shv, __ballot(neg < 0) != 0, pos, lane);
+            }
         }
         PK_LAP(2);
     }
@@ -1918,6 +2497,8 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
 {
     if (E.n_streams <= 0 || E.frames_per_stream <= 0) return hipSuccess;
     const EncConfig &c = E.cfg;
+    // the packers' member lists (enc_mant.h) hold the grouped mantissas of at most 5 x 223 + 7 coefficients a block
+    if (c.nfbw * 223 + 7 > 1122) return hipErrorInvalidValue;
     MdctParams M;
     M.pcm = E.pcm;
     M.last = E.last;
@@ -1945,12 +2526,50 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     M.bsw = E.ws_bsw;
     M.remat = c.acmod == 2 && c.nch == 2 ? E.ws_remat : nullptr;      // (rematrixing is a 2/0 tool: other layouts ignore it)
     const dim3 units(E.n_streams * E.frames_per_stream * c.nch), frames(E.n_streams * E.frames_per_stream);
+    const bool cpl = E.cpl_begf >= 0 && c.nfbw >= 2;
+    if (cpl && M.remat) {
+        // coupling with rematrixing: the rows without rematrixing first (before the history is rewritten), for enc_cpl_kernel
+        MdctParams M0 = M;
+        M0.mdct = E.ws_cpl.prow;
+        M0.shift = E.ws_cpl.pshift;
+        M0.expo = nullptr;
+        M0.full_rows = 1;
+        M0.store_history = 0;
+        M0.remat = nullptr;
+        M0.x.eexp = E.ws_cpl.peexp;
+        M0.x.emask = E.ws_cpl.pemask;
+        M0.x.strat = E.ws_cpl.pstrat;
+        M0.x.ebits = E.ws_cpl.pebits;
+        if (M0.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, false>), units, dim3(64), 0, stream, M0);
+        else hipLaunchKernelGGL((enc_mdct_kernel<false, false>), units, dim3(64), 0, stream, M0);
+        const hipError_t e0 = hipGetLastError();
+        if (e0 != hipSuccess) return e0;
+    }
     if (M.remat && M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, true>), frames, dim3(128), 0, stream, M);
     else if (M.remat) hipLaunchKernelGGL((enc_mdct_kernel<false, true>), frames, dim3(128), 0, stream, M);
     else if (M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, false>), units, dim3(64), 0, stream, M);
     else hipLaunchKernelGGL((enc_mdct_kernel<false, false>), units, dim3(64), 0, stream, M);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    // channel coupling: layouts with two or more full-bandwidth channels
+    if (cpl) {
+        CplParams C;
+        C.mdct = E.ws_mdct;
+        C.shift = E.ws_shift;
+        C.bsw = E.ws_bsw;
+        C.remat = M.remat;
+        C.mdct_out = E.ws_mdct;
+        C.shift_out = E.ws_shift;
+        C.w = E.ws_cpl;
+        C.x = M.x;
+        C.x.nbc = 37 + 12 * E.cpl_begf;
+        C.nfbw = c.nfbw;
+        C.begf = E.cpl_begf;
+        C.nfr = E.n_streams * E.frames_per_stream;
+        hipLaunchKernelGGL(enc_cpl_kernel, dim3(C.nfr), dim3(64), 0, stream, C);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
 
     PackParams P;
     P.mdct = E.ws_mdct;
@@ -1999,6 +2618,8 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.hint_stride = E.search_hint_stride;
     P.bsw = E.ws_bsw;
     P.remat = M.remat;
+    P.cpl = cpl ? E.ws_cpl : CplWs{};
+    P.cpl_begf = cpl ? E.cpl_begf : 0;
 #ifndef ENC_FR_HEADROOM
 #define ENC_FR_HEADROOM 256
 #endif
@@ -2016,13 +2637,19 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     // E.pack_mode (ac3mi_set_encode_mode): 0 = that rule, 1 = never, 2 = always the block packer.
     const unsigned nfr = (unsigned)E.n_streams * (unsigned)E.frames_per_stream;
     const bool long_streams = E.frames_per_stream > 1 && E.n_streams < 5120;
-    const bool packb = E.pack_mode == 2 || (E.pack_mode == 0 && nfr <= 1024);
+    // (coupled frames are packed by enc_packf_kernel<false> only)
+    const bool packb = !cpl && (E.pack_mode == 2 || (E.pack_mode == 0 && nfr <= 1024));
     // Always two steps: the searches (enc_search_kernel), then the packers - one wavefront per frame (enc_packf_kernel) beyond
     // 1 024 frames.  (Rounds 1-3 also had a one-kernel packer per stream; it held neither half's registers comfortably.)
     P.memo = long_streams && E.n_streams < 2048 ? E.ws_memo : nullptr;      // worth its cost only when the per-stream replay is the long pole
-    if (P.memo) hipLaunchKernelGGL(enc_search_kernel<3>, dim3(nfr), dim3(64), 0, stream, P);
-    hipLaunchKernelGGL(enc_search_kernel<1>, dim3(E.n_streams), dim3(64), 0, stream, P);
+    if (P.memo) {
+        if (cpl) hipLaunchKernelGGL((enc_search_kernel<3, true>), dim3(nfr), dim3(64), 0, stream, P);
+        else hipLaunchKernelGGL(enc_search_kernel<3>, dim3(nfr), dim3(64), 0, stream, P);
+    }
+    if (cpl) hipLaunchKernelGGL((enc_search_kernel<1, true>), dim3(E.n_streams), dim3(64), 0, stream, P);
+    else hipLaunchKernelGGL(enc_search_kernel<1>, dim3(E.n_streams), dim3(64), 0, stream, P);
     if (packb) hipLaunchKernelGGL(enc_packb_kernel, dim3(nfr), dim3(384), fr_lds, stream, P);
+    else if (cpl) hipLaunchKernelGGL((enc_packf_kernel<false, true>), dim3(nfr), dim3(64), fr_lds, stream, P);
     else if (c.nch == 6 && c.nfbw == 5 && c.lfe && c.acmod == 7 && P.nbc == 223) hipLaunchKernelGGL(enc_packf_kernel<true>, dim3(nfr), dim3(64), fr_lds, stream, P);
     else hipLaunchKernelGGL(enc_packf_kernel<false>, dim3(nfr), dim3(64), fr_lds, stream, P);
     e = hipGetLastError();
@@ -2044,6 +2671,34 @@ __global__ void enc_history_kernel(const int16_t *pcm, int16_t *last, int n_stre
     const int16_t v = fp[(size_t)(5 * 256 + j) * nch + chmap[ch]];
     if (slot) last[((size_t)slot[s] * 6 + ch) * 256 + j] = v;
     else last[idx] = v;
+}
+
+CplWs cpl_slices(void *base, size_t nfr)
+{
+    uint8_t *p = (uint8_t *)base;
+    CplWs w;
+    auto take = [&](size_t n) { uint8_t *q = p; p += (n + 15) & ~(size_t)15; return q; };
+    w.word = (uint32_t *)take(4 * nfr);
+    w.co = take(80 * nfr);
+    w.mdct = (int32_t *)take(6 * 256 * 4 * nfr);
+    w.shift = (int8_t *)take(8 * nfr);
+    w.eexp = take(6 * 256 * nfr);
+    w.emask = (int16_t *)take(6 * 50 * 2 * nfr);
+    w.strat = take(8 * nfr);
+    w.ebits = (int32_t *)take(4 * nfr);
+    return w;
+}
+
+void cpl_remat_slices(CplWs &w, void *base, size_t nfr)
+{
+    uint8_t *p = (uint8_t *)base;
+    auto take = [&](size_t n) { uint8_t *q = p; p += (n + 15) & ~(size_t)15; return q; };
+    w.prow = (int32_t *)take(6 * 2 * 256 * 4 * nfr);
+    w.pshift = (int8_t *)take(16 * nfr);
+    w.peexp = take(6 * 2 * 256 * nfr);
+    w.pemask = (int16_t *)take(6 * 2 * 50 * 2 * nfr);
+    w.pstrat = take(16 * nfr);
+    w.pebits = (int32_t *)take(16 * nfr);
 }
 
 hipError_t launch_enc_history(const EncodeLaunch &E, hipStream_t stream)

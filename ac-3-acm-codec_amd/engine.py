@@ -271,6 +271,12 @@ class Engine:
         (ac3mi_set_encode_rematrix).  Applies to encode_batch and transcode_batch."""
         self._check(self.lib.ac3mi_set_encode_rematrix(ctypes.c_void_p(self.ctx), int(mode)))
 
+    def set_encode_coupling(self, mode, begf=0):
+        """0 = every channel coded on its own (the reference), 1 = frames with two or more full-bandwidth channels couple them
+        above sub-band `begf` (0..12; cplstrtmant = 37 + 12 begf) where the rule of ac3mi_set_encode_coupling allows.
+        Applies to encode_batch and transcode_batch."""
+        self._check(self.lib.ac3mi_set_encode_coupling(ctypes.c_void_p(self.ctx), int(mode), int(begf)))
+
     def set_mix_state(self, pending=None, flags=None):
         """liba52's overlap bookkeeping around frames with surround level 0 (ac3mi_set_mix_state): `pending` float32 shaped
         like the delay array, `flags` int32 [S][6], both zero for new streams and updated in place by the decode calls that

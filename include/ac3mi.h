@@ -203,6 +203,42 @@ int ac3mi_set_encode_block_switch(ac3mi_ctx *ctx, int mode);
  * AC3MI_ERR_ARG. */
 int ac3mi_set_encode_rematrix(ac3mi_ctx *ctx, int mode);
 
+/* Channel coupling in the encoder (new; applies to every following ac3mi_encode_batch / ac3mi_transcode_batch on `ctx`,
+ * in either packer variant, with or without state slots, tiled or not, with block switching and rematrixing on or off):
+ *   0  (default) the reference's behaviour: every channel is coded on its own up to bin 223, block 0 sends cplstre 1,
+ *      cplinu 0.  `begf` is ignored.
+ *   1  layouts with two or more full-bandwidth channels couple every full-bandwidth channel (never the LFE) above
+ *      cplbegf = begf (0..12), cplendf = 12: cplstrtmant = 37 + 12 begf, cplendmant = 217; a coupled frame codes no bin in
+ *      217..222.  The rule, per frame (integer arithmetic throughout; c = a channel's 256-bin MDCT row before exponents,
+ *      x = its exp_samples, the encode taps' d_mdct / d_exp_samples in mode 0):
+ *      - coupling row, per block: xb = the smallest x of the nfbw channels, cpl[k] = (sum over channels of
+ *        c[k] >> (x - xb)) >> g for k in [cplstrtmant, 217), 0 elsewhere, g = 1 (2 channels), 2 (3, 4), 3 (5); coded at
+ *        exp_samples xb like a channel's row (exponent 23 - ilog2|cpl| + xb, 24 and coefficient 0 from 24 on);
+ *      - energies, per coupling band (12 bins, cplbndstrc all 0: 15 - begf bands) over the frame's six blocks, every row
+ *        aligned to the frame's smallest x, xf: Ech = sum (c >> (x - xf))^2, Ecpl = sum (cpl >> (xb - xf))^2 (exact u64);
+ *      - the frame is NOT coupled (cplstre 1, cplinu 0 in block 0; then coded exactly as in mode 0, same bytes) if block
+ *        switching is on and a full-bandwidth channel switches a block, or if in some band 2^(2g+2) Ecpl < the sum of the
+ *        channels' Ech (channels that cancel); with rematrixing on, c and x are the rows before rematrixing;
+ *      - coordinates, one set per frame in block 0 (cplcoe 1; cplcoe 0 in blocks 1..5; phsflginu 0): under mstrcplco M
+ *        the value of (cplcoexp E, cplcomant m) is liba52's (parse.c:642-656, the x8 included): (16 + m) 2^-(E + 3M + 2)
+ *        for E < 15, m 2^-(16 + 3M) for E = 15; the code is the largest value v with v^2 Ecpl <= Ech (exact; Ech = 0
+ *        gives E 15, m 0); a channel's mstrcplco is the M whose codes give the largest sum over its bands of v^2, ties to
+ *        the smaller M;
+ *      - the coupling channel: exponent strategies by the reference's rule on its raw exponents (24 outside the coupling
+ *        range), min-merged over reuse runs, groups from cplstrtmant under the +-2 constraint, 2 cplabsexp = the first
+ *        exponent & ~1; masking curve from cplstrtbnd without lowcomp, cplleake 1 in block 0 with cplfleak = cplsleak
+ *        = 0; cplfsnroffst / cplfgaincod equal to the channels';
+ *      - the coupled channels keep their mode-0 exponent strategies and code [0, cplstrtmant) (no chbwcod); in 2/0 block
+ *        frame with rematrixing on applies its mode-1 rule to the rows before rematrixing over liba52's cplinu-1 bands
+ *        ([13,25), [25,37), [37,61), [61,223) cut at cplstrtmant: 2, 3 or 4 bands for begf 0, 1-2, 3 and up), with its
+ *        exponents and strategies from the rows so coded; with rematrixing off block 0 sends that many zero flags;
+ *      - mantissas in A/52 order: channel 0, the coupling channel, the other channels, the LFE.
+ *      Coupled frames are packed by the one-wavefront packer whatever ac3mi_set_encode_mode says (same bytes).
+ * One full-bandwidth channel: accepted and unchanged.  The same input gives the same bytes in one call or split over
+ * several.  The drop-in AC3_encode_* and the byte-stream layer (ac3mi_stream.h) never couple.  Any other mode, or begf
+ * outside 0..12: AC3MI_ERR_ARG. */
+int ac3mi_set_encode_coupling(ac3mi_ctx *ctx, int mode, int begf);
+
 /* Workspace bound (new; results do not depend on it, except for frames flagged AC3MI_STATUS_REUSE0 at a tile boundary).  ac3mi_decode_batch, ac3mi_encode_batch and ac3mi_transcode_batch keep
  * their intermediates (coefficient planes, MDCT coefficients, exponents, PCM between decoder and encoder: 37 / 60 /
  * 102 - 139 KB per 5.1 frame) in workspaces owned by the context.  A batch of more than `frames` frames goes through in tiles

@@ -136,7 +136,7 @@ legs = {
     "decode": pick("decode_kernel<4>", "mant_kernel", "xform_kernel<false, 4, false>"),
     "decode_s16": pick("decode_kernel<4>", "mantx_kernel<true>"),
     "decode_s16_two_kernels": pick("decode_kernel<4>", "mant_kernel", "xform_kernel<false, 3, true>"),
-    "encode": pick("enc_mdct_kernel", "enc_search_kernel<1>", "enc_packf_kernel"),
+    "encode": pick("enc_mdct_kernel", "enc_search_kernel<1", "enc_packf_kernel"),
     "transform_downmix_mixed_blocks": pick("xform_kernel<true, 2, false>", "xform_kernel<true, 3, false>"),
 }
 legs["transcode"] = sorted(set(legs["decode_s16"]) | set(legs["encode"]))
