@@ -182,6 +182,8 @@ struct EncodeLaunch {
     uint8_t *ws_remat = nullptr;    // [S][F][6] rematrixing decisions (ac3mi_set_encode_rematrix 1; null, or not 2/0: none)
     int cpl_begf = -1;          // ac3mi_set_encode_coupling 1: cplbegf (0..12); -1: no coupling
     CplWs ws_cpl = {};          // its per-frame results (cpl_begf >= 0)
+    int chbwcod = 50;           // ac3mi_set_encode_bandwidth: the call's chbwcod (0..50), nbc = 73 + 3 chbwcod
+    bool bw = false;            // ... and whether it is on (mode 1 or 2): the runtime-bandwidth kernel variants run
 };
 // carves CPL_FRAME_BYTES * nfr bytes at `base` into the arrays of CplWs (base 16-byte aligned)
 CplWs cpl_slices(void *base, size_t nfr);
@@ -213,6 +215,7 @@ struct ac3mi_ctx {
     uint8_t *ws_remat;      // its decisions between the MDCT kernel, the search and the packers, one byte per frame-block
     size_t ws_remat_bytes;
     int coupling, cpl_begf; // ac3mi_set_encode_coupling
+    int bw_mode, bw_chbwcod;    // ac3mi_set_encode_bandwidth
     void *ws_cpl;           // its per-frame workspace (ac3mi::CplWs, CPL_FRAME_BYTES a frame)
     size_t ws_cpl_bytes;
     void *ws_cplr;          // with rematrixing on as well: CPL_REMAT_FRAME_BYTES a frame

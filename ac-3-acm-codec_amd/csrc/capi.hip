@@ -493,6 +493,8 @@ ac3mi_ctx *ac3mi_create(int device)
     ctx->ws_remat_bytes = 0;
     ctx->coupling = 0;
     ctx->cpl_begf = 0;
+    ctx->bw_mode = 0;
+    ctx->bw_chbwcod = 50;
     ctx->ws_cpl = nullptr;
     ctx->ws_cpl_bytes = 0;
     ctx->ws_cplr = nullptr;
@@ -765,6 +767,30 @@ int ac3mi_set_encode_coupling(ac3mi_ctx *ctx, int mode, int begf)
     ctx->coupling = mode;
     ctx->cpl_begf = begf;
     return AC3MI_OK;
+}
+
+int ac3mi_set_encode_bandwidth(ac3mi_ctx *ctx, int mode, int chbwcod)
+{
+    if (!ctx || mode < 0 || mode > 2 || (mode == 1 && (chbwcod < 0 || chbwcod > 50))) return AC3MI_ERR_ARG;
+    ctx->bw_mode = mode;
+    ctx->bw_chbwcod = mode == 1 ? chbwcod : 50;
+    return AC3MI_OK;
+}
+
+// the chbwcod a call codes with (ac3mi_set_encode_bandwidth's rule, include/ac3mi.h); callers pass a descriptor enc_config
+// accepted (a channel count outside 1..6 gets 50 here rather than a division by zero)
+static int call_chbwcod(const ac3mi_ctx *ctx, const ac3mi_encode_desc *d)
+{
+    if (ctx->bw_mode == 1) return ctx->bw_chbwcod;
+    if (ctx->bw_mode != 2 || d->channels < 1 || d->channels > 6) return 50;
+    const int nfbw = d->channels > 5 ? 5 : d->channels;
+    const long long r = d->bit_rate / nfbw;
+    if (r >= 96000) return 50;
+    const long long fc = r >= 80000 ? 18000 : r >= 64000 ? 16000 : r >= 48000 ? 14000 : r >= 32000 ? 11000 : 8000;
+    int c = 0;
+    for (int k = 0; k <= 50; k++)
+        if ((73LL + 3 * k) * d->sample_rate <= 512 * fc) c = k;
+    return c;
 }
 
 int ac3mi_set_tile_frames(ac3mi_ctx *ctx, long long frames)
@@ -1407,6 +1433,8 @@ int ac3mi_encode_batch(ac3mi_ctx *ctx, const ac3mi_encode_desc *desc, const int1
     if (taps && taps->d_exponent) E.ws_expo = taps->d_exponent;
     if (taps && taps->d_exp_samples) E.ws_shift = taps->d_exp_samples;
     if (taps && taps->d_encoded_exp) E.ws_eexp = taps->d_encoded_exp;      // the exponent stage writes the tap directly
+    E.chbwcod = call_chbwcod(ctx, desc);
+    E.bw = ctx->bw_mode != 0;
     E.pcm = d_pcm;
     E.last = d_last;
     E.csnr = d_csnroffst;
@@ -1456,6 +1484,8 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         ctx->err = "ac3mi_transcode_batch: encoder configuration rejected, or its channel count differs from the decoder's output";
         return AC3MI_ERR_ARG;
     }
+    E.chbwcod = call_chbwcod(ctx, enc);                 // (after enc_config: the descriptor is a valid one)
+    E.bw = ctx->bw_mode != 0;
     if (out_stride < ((fb + 3) & ~3) || (out_stride & 3) || ((uintptr_t)d_frames_out & 3)) {
         ctx->err = "ac3mi_transcode_batch: out_stride must be a multiple of 4 and >= the frame size";
         return AC3MI_ERR_ARG;

@@ -37,8 +37,14 @@ extern __device__ unsigned long long g_pack_cycles[16];
 // the group's opener fetches both with ONE aligned 32-bit read.  Kinds 0 / 1 (3- / 5-level codes, three members) at 0 / 752:
 // at most 748 members + the two entries cleared behind the last one; kind 2 (11-level, two members: entry 2 g + 1 is never
 // written and stays zero from mant_lists_init) at 1504: entries up to 2 x 561 + 1; then one sink entry per lane.
+// The most coefficients a block codes: five full-bandwidth channels of MAX_NBC bins (chbwcod 50) and the LFE's 7.  The
+// encoder's bandwidth (ac3mi_set_encode_bandwidth) only ever lowers nbc below it.
+constexpr int MAX_NBC = 223;
+constexpr int MANT_MAX_COEFS = 5 * MAX_NBC + 7;
 constexpr int GL_STRIDE = 752;
 constexpr int GL_KIND2 = 1128;
+static_assert(GL_STRIDE >= 2 * ((MANT_MAX_COEFS + 2) / 3) + 2 && GL_STRIDE % 8 == 0, "3- / 5-level lists: 2 entries a group + 2 cleared");
+static_assert(GL_KIND2 >= 2 * ((MANT_MAX_COEFS + 1) / 2) + 1 && GL_KIND2 % 8 == 0, "11-level list: entries up to 2 g + 1");
 constexpr int GL_SINK = 2 * GL_STRIDE + GL_KIND2;
 constexpr int GL_ENTRIES = GL_SINK + 64;
 

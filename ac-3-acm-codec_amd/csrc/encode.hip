@@ -73,6 +73,7 @@ struct PackParams {
     const uint8_t *remat;       // optional, [S][F][6]: 2/0 rematrixing, flags in bits 0-3, rematstr in bit 4; null: none
     CplWs cpl;                  // channel coupling (enc_cpl_kernel); cpl.word null: none
     int cpl_begf;
+    int cpl_endf;               // cplendf of a coupled frame: 12, min(12, chbwcod >> 2) in the BW variants (cplendmant 73 + 12 cplendf)
 };
 
 
@@ -494,7 +495,9 @@ __device__ __forceinline__ void bfly(c16 &p, c16 &q, int bx, int by, int ax, int
 #ifndef ENC_MDCT_BSW_REMAT_LB
 #define ENC_MDCT_BSW_REMAT_LB 4      // with block switching: 118 VGPRs, no scratch (at 5: 96 VGPRs and 48 bytes of scratch)
 #endif
-template <bool BSW, bool REMAT>
+// BW (ac3mi_set_encode_bandwidth 1 or 2, with REMAT only - the other variants take P.x.nbc at run time already): the fourth
+// rematrixing band ends at nbc = 73 + 3 chbwcod instead of 223.  nbc can split a lane's four bins only inside that band.
+template <bool BSW, bool REMAT, bool BW = false>
 __global__ __launch_bounds__(REMAT ? 128 : 64, REMAT ? (BSW ? ENC_MDCT_BSW_REMAT_LB : ENC_MDCT_REMAT_LB) : BSW ? ENC_MDCT_BSW_LB : ENC_MDCT_LB)
 void enc_mdct_kernel(const MdctParams P)
 {
@@ -768,12 +771,13 @@ void enc_mdct_kernel(const MdctParams P)
             const int r0 = rv_[par][0], r1 = rv_[par][1];
             const int vl = r0 & 0xff, vr = r1 & 0xff, vm = min(vl, vr), dl = vl - vm, dr = vr - vm;
             const int32_t *rl = out_[2 * par], *rr = out_[2 * par + 1];
+            const int jend = BW ? P.x.nbc : 223;                    // the fourth band's end
             uint64_t el = 0, er = 0, em = 0, es = 0;
             if (lane < 53) {
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const int j = 13 + 4 * lane + k;
-                    if (j < 223) {
+                    if (j < jend) {
                         const int a = rl[j] >> dl, b = rr[j] >> dr, m = (a + b) >> 1, d = (a - b) >> 1;
                         el += (uint64_t)(uint32_t)abs(a) * (uint32_t)abs(a);
                         er += (uint64_t)(uint32_t)abs(b) * (uint32_t)abs(b);
@@ -816,7 +820,7 @@ void enc_mdct_kernel(const MdctParams P)
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const int j = 4 * lane + k;
-                    const int bd = j < 13 ? -1 : j < 25 ? 0 : j < 37 ? 1 : j < 61 ? 2 : j < 223 ? 3 : -1;
+                    const int bd = j < 13 ? -1 : j < 25 ? 0 : j < 37 ? 1 : j < 61 ? 2 : j < jend ? 3 : -1;
                     const int a = cc[k] >> dmine, b = oc[k] >> doth;
                     cc[k] = bd >= 0 && ((flags >> bd) & 1) ? (wave ? (b - a) >> 1 : (a + b) >> 1) : a;
                 }
@@ -837,7 +841,9 @@ void enc_mdct_kernel(const MdctParams P)
             }
             epack |= (uint32_t)(e & 0xff) << (8 * k);
         }
-        // (the packers read a row's coded bins only: 223 of a full-bandwidth channel, 7 of the LFE - a quarter of the store traffic)
+        // (the packers read a row's coded bins only: nbc of a full-bandwidth channel, 7 of the LFE - a quarter of the store traffic.
+        //  Every reader of a row masks what lies beyond: the search and the packers give bins >= nbc exponent 255 (bap 0, no bits),
+        //  enc_cpl_kernel reads [cplstrtmant, cplendmant) and, for a coupled channel's exponents, bins below cplstrtmant only)
         if (P.full_rows || 4 * lane < ((P.x.lfe && ch == P.nch - 1) ? 7 : P.x.nbc))
             *reinterpret_cast<int4 *>(P.mdct + row * 256 + 4 * lane) = make_int4(cc[0], cc[1], cc[2], cc[3]);
         if (P.expo) *reinterpret_cast<uint32_t *>(P.expo + row * 256 + 4 * lane) = epack;       // tap only
@@ -871,6 +877,8 @@ struct CplParams {
     CplWs w;
     ExpParams x;                // the channels' exponent stage, x.nbc = cplstrtmant
     int nfbw, begf, nfr;
+    int endf;                   // enc_cpl_kernel<true>: cplendf (begf <= endf + 2); <false>: 12
+    int nbc;                    // enc_cpl_kernel<true>: the channels' nbc (rows are stored below it only); <false>: 223
 };
 
 struct CplLDS {
@@ -994,13 +1002,15 @@ __device__ void cpl_mask_wave(const MaskTabs &T, const uint8_t *row, int16_t *ma
     if (b < 50) mask[b] = live ? (int16_t)(excite > h ? excite : h) : (int16_t)0;
 }
 
+// BW (ac3mi_set_encode_bandwidth 1 or 2): the coupling range ends at cplendmant = 73 + 12 P.endf, 3 + endf - begf bands
+template <bool BW = false>
 __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
 {
     __shared__ CplLDS L;
     const int lane = threadIdx.x;
     const size_t fidx = blockIdx.x;
     const int nch = P.x.nch, nfbw = P.nfbw, g = cpl_g(nfbw);
-    const int cs = 37 + 12 * P.begf, ce = 217, nb = 15 - P.begf;
+    const int cs = 37 + 12 * P.begf, ce = BW ? 73 + 12 * P.endf : 217, nb = BW ? 3 + P.endf - P.begf : 15 - P.begf;
     const EncTables *tab = P.x.tab;
     ExpLDS &X = L.X;
     reinterpret_cast<uint32_t *>(X.t.latab)[lane] = reinterpret_cast<const uint32_t *>(tab->latab)[lane];
@@ -1262,7 +1272,8 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int a = c4[k] < 0 ? -c4[k] : c4[k];
-                const int e = 4 * lane + k >= 223 || a == 0 ? 24 : 23 - ilog2u((unsigned)a) + shc;
+                // (bins from nbc on: exponent 24 - the row store leaves them unwritten, so the exponent tap stays reproducible)
+                const int e = 4 * lane + k >= (BW ? P.nbc : 223) || a == 0 ? 24 : 23 - ilog2u((unsigned)a) + shc;
                 epack |= (uint32_t)(e & 0xff) << (8 * k);
             }
             *reinterpret_cast<uint32_t *>(&X.E[b][4 * lane]) = epack;
@@ -1384,7 +1395,8 @@ __device__ unsigned long long g_pack_cycles[16];
 #endif
 // enc_search_kernel<1>: one wavefront per stream, frames in order; <3>: one wavefront per frame tabulates (see above).
 // CPL (enc_search_cpl_kernel: channel coupling on, P.cpl): the coupling rows join the costed rows of a coupled frame.
-template <int PART, bool CPL = false>
+// BW (with CPL; ac3mi_set_encode_bandwidth 1 or 2): a coupled frame ends at cplendmant = 73 + 12 P.cpl_endf, not 217.
+template <int PART, bool CPL = false, bool BW = false>
 __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const PackParams P)
 {
     static_assert(PART == 1 || PART == 3, "the packers are enc_packf_kernel / enc_packb_kernel");
@@ -1407,6 +1419,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
 
     const int sslot = P.slot ? P.slot[s] : s;
     const int cpl_cs = 37 + 12 * P.cpl_begf;        // (coupling only)
+    const int cpl_ce = BW ? 73 + 12 * P.cpl_endf : 217, cpl_nb = BW ? 3 + P.cpl_endf - P.cpl_begf : 15 - P.cpl_begf;
     // the stream's search state: csnroffst in bits 0-7, the fsnroffst of its last coded frame in bits 8-11 (what the
     // reference's s->csnroffst / s->fsnroffst[] hold between frames, ENC/ac3enc.cpp:969-972)
     const int state_in = P.csnr_state[sslot];
@@ -1483,7 +1496,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                     // coupling: chincpl, phsflginu (2/0), cplbegf / cplendf, cplbndstrc; cplcoe, mstrcplco and the coordinates
                     // in block 0, cplcoe 0 in blocks 1..5; cplexpstr; cplfsnroffst / cplfgaincod; cplleake (+ the two leaks in
                     // block 0); the coupling exponents; no chbwcod for the coupled channels
-                    const int nb = 15 - P.cpl_begf;
+                    const int nb = cpl_nb;
                     frame_bits += nfbw + (P.acmod == 2 ? 1 : 0) + 8 + (nb - 1) + nfbw * (3 + 8 * nb) + 5 * nfbw + 6 * 2 + 7 + 7 + 5;
                     frame_bits += __builtin_amdgcn_readfirstlane(P.cpl.ebits[fidx]) - 6 * __builtin_popcountll(row_set & fbw_rows);
                     if (P.remat) {                  // a coupled frame's blocks 1..5 send liba52's cplinu-1 flag count, not 4
@@ -1614,7 +1627,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                     const char *Tr = reinterpret_cast<const char *>(&L.terms[i & 1][0]);
                     uint32_t em;
                     if constexpr (CPL) {
-                        const uint32_t um_cch = beyond(cpl_cs), um_cpl = ~beyond(cpl_cs) | beyond(217);
+                        const uint32_t um_cch = beyond(cpl_cs), um_cpl = ~beyond(cpl_cs) | beyond(cpl_ce);
                         em = ev | ((d0 & (1u << 14)) ? um_lfe : (d0 & (1u << 15)) ? um_cpl : (d0 & (1u << 22)) ? um_cch : um_fbw);
                     } else {
                         em = ev | ((d0 & (1u << 14)) ? um_lfe : um_fbw);
@@ -1889,7 +1902,9 @@ struct alignas(16) PackfLDS {
 // FIXED51: the 5.1 configuration (five full-bandwidth channels + LFE, acmod 7) as compile-time constants - the shape large batches
 // have; its five mantissa passes, the merged LFE lanes and the side information's field list then need no tests
 // CPL: coupled frames (channel coupling on, never with FIXED51): the coupling fields, exponents and mantissa pass
-template <bool FIXED51, bool CPL = false>
+// BW (ac3mi_set_encode_bandwidth 1 or 2): FIXED51 with the run-time nbc; CPL with the coupling range ending at cplendmant =
+// 73 + 12 P.cpl_endf (3 + cpl_endf - cpl_begf bands, cplendf = P.cpl_endf)
+template <bool FIXED51, bool CPL = false, bool BW = false>
 __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackParams P)
 {
     static_assert(!(FIXED51 && CPL), "coupled frames take the generic packer");
@@ -1909,7 +1924,7 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
     const uint32_t bandoff = *reinterpret_cast<const uint32_t *>(&P.tab->band_of_bin[4 * lane]);     // bands of bins 4*lane..+3
     // fixed allocation codes (:861-879)
     constexpr int sdecaycod = 2, fdecaycod = 1, sgaincod = 1, dbkneecod = 2, floorcod = 4, fgaincod = 4;
-    const int nch = FIXED51 ? 6 : P.nch, nfbw = FIXED51 ? 5 : P.nfbw, nbc = FIXED51 ? 223 : P.nbc;
+    const int nch = FIXED51 ? 6 : P.nch, nfbw = FIXED51 ? 5 : P.nfbw, nbc = FIXED51 && !BW ? 223 : P.nbc;
     const int acmod = FIXED51 ? 7 : P.acmod;
     const bool lfe = FIXED51 ? true : P.lfe != 0;
     const int fs = P.frame_words;
@@ -1921,7 +1936,8 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
     // channel coupling (enc_cpl_kernel): every full-bandwidth channel in coupling, one set of coordinates in block 0
     const uint32_t cplw = CPL ? (uint32_t)__builtin_amdgcn_readfirstlane((int)P.cpl.word[fidx]) : 0u;
     const bool cplf = (cplw & 1u) != 0;
-    const int cs = 37 + 12 * P.cpl_begf, ncb = 15 - P.cpl_begf;
+    const int cs = 37 + 12 * P.cpl_begf, ncb = BW ? 3 + P.cpl_endf - P.cpl_begf : 15 - P.cpl_begf;
+    const int cendf = BW ? P.cpl_endf : 12, ce = 73 + 12 * cendf;
     PK_T0();
     PK_COUNT(7);
     for (int i = lane; i < P.frw / 4; i += 64) reinterpret_cast<uint4 *>(fr)[i] = make_uint4(0, 0, 0, 0);
@@ -2012,7 +2028,7 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
                 put(1, 1); put(1, 1);
                 for (int ch = 0; ch < nfbw; ch++) put(1, 1);
                 if (acmod == 2) put(1, 0);
-                put(4, (uint32_t)P.cpl_begf); put(4, 12); put(ncb - 1, 0);
+                put(4, (uint32_t)P.cpl_begf); put(4, (uint32_t)cendf); put(ncb - 1, 0);
                 flush();
                 const uint8_t *co = P.cpl.co + fidx * 80;
                 for (int ch = 0; ch < nfbw; ch++) {
@@ -2046,7 +2062,7 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         if (cplf && cstg != 0) {
             // the coupling exponents: cplabsexp (bin cs - 1 holds 2 cplabsexp), groups from cplstrtmant
             const int gs = cstg == 1 ? 1 : cstg == 2 ? 2 : 4;
-            const int ng = (217 - cs) / (3 * gs);
+            const int ng = (ce - cs) / (3 * gs);
             const uint8_t *e = &L.erow[0];
             WAVE_SYNC();
             *reinterpret_cast<uint32_t *>(&L.erow[4 * lane]) = cew;
@@ -2117,10 +2133,10 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
                 B.mdb = md + (size_t)b * nch * 256;
                 B.tap_bap = P.tap_bap ? P.tap_bap + (fidx * 6 + b) * nch * 256 : nullptr;
                 B.nch = nch; B.nbc = nbc; B.lfe = lfe; B.marker = (uint32_t)P.marker;
-                // per pass: channel 0, the coupling row, channels 1.. (bins below cplstrtmant / in [cplstrtmant, 217)), LFE at 6
+                // per pass: channel 0, the coupling row, channels 1.. (bins below cplstrtmant / in [cplstrtmant, cplendmant)), LFE at 6
                 const int csh = __builtin_amdgcn_readfirstlane((int)P.cpl.shift[fidx * 8 + b]);
                 auto beyond = [&](int n) { const int k = n - 4 * lane; return k >= 4 ? 0u : k <= 0 ? 0xffffffffu : 0xffffffffu << (8 * k); };
-                const uint32_t um_cch = beyond(cs), um_cpl = ~beyond(cs) | beyond(217), um_lfe = beyond(7);
+                const uint32_t um_cch = beyond(cs), um_cpl = ~beyond(cs) | beyond(ce), um_lfe = beyond(7);
                 uint32_t ad7[7], em7[7];
                 int sh7[7], neg = 0;
 #pragma unroll
@@ -2497,8 +2513,13 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
 {
     if (E.n_streams <= 0 || E.frames_per_stream <= 0) return hipSuccess;
     const EncConfig &c = E.cfg;
-    // the packers' member lists (enc_mant.h) hold the grouped mantissas of at most 5 x 223 + 7 coefficients a block
-    if (c.nfbw * 223 + 7 > 1122) return hipErrorInvalidValue;
+    // the call's bandwidth (ac3mi_set_encode_bandwidth): nbc coefficients per full-bandwidth channel, a coupled frame ends at
+    // cplendf.  E.bw, or any chbwcod below 50: the runtime-bandwidth variants run (mode 0 launches exactly the kernels it always did)
+    if (E.chbwcod < 0 || E.chbwcod > 50) return hipErrorInvalidValue;
+    const int nbc = 73 + 3 * E.chbwcod, cpl_endf = E.chbwcod >> 2 < 12 ? E.chbwcod >> 2 : 12;
+    const bool bw = E.bw || E.chbwcod != 50;
+    // the packers' member lists (enc_mant.h) hold the grouped mantissas of at most 5 x MAX_NBC + 7 coefficients a block
+    if (c.nfbw * nbc + 7 > MANT_MAX_COEFS) return hipErrorInvalidValue;
     MdctParams M;
     M.pcm = E.pcm;
     M.last = E.last;
@@ -2522,11 +2543,12 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     M.x.lfe = c.lfe;
     M.x.fscod = c.fscod;
     M.x.halfrate = c.halfrate;
-    M.x.nbc = 223;      // the only reader of last[] is this same wavefront's block 0
+    M.x.nbc = nbc;      // the only reader of last[] is this same wavefront's block 0
     M.bsw = E.ws_bsw;
     M.remat = c.acmod == 2 && c.nch == 2 ? E.ws_remat : nullptr;      // (rematrixing is a 2/0 tool: other layouts ignore it)
     const dim3 units(E.n_streams * E.frames_per_stream * c.nch), frames(E.n_streams * E.frames_per_stream);
-    const bool cpl = E.cpl_begf >= 0 && c.nfbw >= 2;
+    // (begf > cplendf + 2: no coupling band - no frame couples, the bytes are coupling off's)
+    const bool cpl = E.cpl_begf >= 0 && c.nfbw >= 2 && E.cpl_begf <= cpl_endf + 2;
     if (cpl && M.remat) {
         // coupling with rematrixing: the rows without rematrixing first (before the history is rewritten), for enc_cpl_kernel
         MdctParams M0 = M;
@@ -2545,7 +2567,9 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
         const hipError_t e0 = hipGetLastError();
         if (e0 != hipSuccess) return e0;
     }
-    if (M.remat && M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, true>), frames, dim3(128), 0, stream, M);
+    if (M.remat && M.bsw && bw) hipLaunchKernelGGL((enc_mdct_kernel<true, true, true>), frames, dim3(128), 0, stream, M);
+    else if (M.remat && bw) hipLaunchKernelGGL((enc_mdct_kernel<false, true, true>), frames, dim3(128), 0, stream, M);
+    else if (M.remat && M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, true>), frames, dim3(128), 0, stream, M);
     else if (M.remat) hipLaunchKernelGGL((enc_mdct_kernel<false, true>), frames, dim3(128), 0, stream, M);
     else if (M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, false>), units, dim3(64), 0, stream, M);
     else hipLaunchKernelGGL((enc_mdct_kernel<false, false>), units, dim3(64), 0, stream, M);
@@ -2566,7 +2590,10 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
         C.nfbw = c.nfbw;
         C.begf = E.cpl_begf;
         C.nfr = E.n_streams * E.frames_per_stream;
-        hipLaunchKernelGGL(enc_cpl_kernel, dim3(C.nfr), dim3(64), 0, stream, C);
+        C.endf = bw ? cpl_endf : 12;
+        C.nbc = nbc;
+        if (bw) hipLaunchKernelGGL(enc_cpl_kernel<true>, dim3(C.nfr), dim3(64), 0, stream, C);
+        else hipLaunchKernelGGL(enc_cpl_kernel<false>, dim3(C.nfr), dim3(64), 0, stream, C);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -2598,8 +2625,8 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.bsid = c.bsid;
     P.frmsizecod = c.frmsizecod;
     P.frame_words = c.frame_words;
-    P.nbc = 223;
-    P.chbwcod = 50;
+    P.nbc = nbc;
+    P.chbwcod = E.chbwcod;
     const int fs = c.frame_words, fs58 = (fs >> 1) + (fs >> 3);
     auto times_x = [](uint16_t *t, uint32_t v) {                    // t[i] = v * x^i mod poly
         for (int i = 0; i < 16; i++) { t[i] = (uint16_t)v; v = h_gf_mul(v, 2); }
@@ -2620,6 +2647,7 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.remat = M.remat;
     P.cpl = cpl ? E.ws_cpl : CplWs{};
     P.cpl_begf = cpl ? E.cpl_begf : 0;
+    P.cpl_endf = bw ? cpl_endf : 12;
 #ifndef ENC_FR_HEADROOM
 #define ENC_FR_HEADROOM 256
 #endif
@@ -2642,15 +2670,22 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     // Always two steps: the searches (enc_search_kernel), then the packers - one wavefront per frame (enc_packf_kernel) beyond
     // 1 024 frames.  (Rounds 1-3 also had a one-kernel packer per stream; it held neither half's registers comfortably.)
     P.memo = long_streams && E.n_streams < 2048 ? E.ws_memo : nullptr;      // worth its cost only when the per-stream replay is the long pole
+    // (the uncoupled search and enc_packb_kernel take nbc / chbwcod at run time in every mode; bw picks the variants whose coupling
+    // end or 5.1 band edge is a run-time value)
     if (P.memo) {
-        if (cpl) hipLaunchKernelGGL((enc_search_kernel<3, true>), dim3(nfr), dim3(64), 0, stream, P);
+        if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<3, true, true>), dim3(nfr), dim3(64), 0, stream, P);
+        else if (cpl) hipLaunchKernelGGL((enc_search_kernel<3, true>), dim3(nfr), dim3(64), 0, stream, P);
         else hipLaunchKernelGGL(enc_search_kernel<3>, dim3(nfr), dim3(64), 0, stream, P);
     }
-    if (cpl) hipLaunchKernelGGL((enc_search_kernel<1, true>), dim3(E.n_streams), dim3(64), 0, stream, P);
+    if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<1, true, true>), dim3(E.n_streams), dim3(64), 0, stream, P);
+    else if (cpl) hipLaunchKernelGGL((enc_search_kernel<1, true>), dim3(E.n_streams), dim3(64), 0, stream, P);
     else hipLaunchKernelGGL(enc_search_kernel<1>, dim3(E.n_streams), dim3(64), 0, stream, P);
+    const bool fixed51 = c.nch == 6 && c.nfbw == 5 && c.lfe && c.acmod == 7;
     if (packb) hipLaunchKernelGGL(enc_packb_kernel, dim3(nfr), dim3(384), fr_lds, stream, P);
+    else if (cpl && bw) hipLaunchKernelGGL((enc_packf_kernel<false, true, true>), dim3(nfr), dim3(64), fr_lds, stream, P);
     else if (cpl) hipLaunchKernelGGL((enc_packf_kernel<false, true>), dim3(nfr), dim3(64), fr_lds, stream, P);
-    else if (c.nch == 6 && c.nfbw == 5 && c.lfe && c.acmod == 7 && P.nbc == 223) hipLaunchKernelGGL(enc_packf_kernel<true>, dim3(nfr), dim3(64), fr_lds, stream, P);
+    else if (fixed51 && bw) hipLaunchKernelGGL((enc_packf_kernel<true, false, true>), dim3(nfr), dim3(64), fr_lds, stream, P);
+    else if (fixed51 && P.nbc == 223) hipLaunchKernelGGL(enc_packf_kernel<true>, dim3(nfr), dim3(64), fr_lds, stream, P);
     else hipLaunchKernelGGL(enc_packf_kernel<false>, dim3(nfr), dim3(64), fr_lds, stream, P);
     e = hipGetLastError();
     if (e != hipSuccess) return e;

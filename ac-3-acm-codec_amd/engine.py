@@ -277,6 +277,12 @@ class Engine:
         Applies to encode_batch and transcode_batch."""
         self._check(self.lib.ac3mi_set_encode_coupling(ctypes.c_void_p(self.ctx), int(mode), int(begf)))
 
+    def set_encode_bandwidth(self, mode, chbwcod=50):
+        """0 = chbwcod 50, bins [0, 223) (the reference), 1 = every full-bandwidth channel codes [0, 73 + 3 chbwcod) with `chbwcod`
+        (0..50), 2 = chbwcod follows each call's bit rate per full-bandwidth channel and sample rate (ac3mi_set_encode_bandwidth).
+        Applies to encode_batch and transcode_batch."""
+        self._check(self.lib.ac3mi_set_encode_bandwidth(ctypes.c_void_p(self.ctx), int(mode), int(chbwcod)))
+
     def set_mix_state(self, pending=None, flags=None):
         """liba52's overlap bookkeeping around frames with surround level 0 (ac3mi_set_mix_state): `pending` float32 shaped
         like the delay array, `flags` int32 [S][6], both zero for new streams and updated in place by the decode calls that

@@ -239,6 +239,33 @@ int ac3mi_set_encode_rematrix(ac3mi_ctx *ctx, int mode);
  * outside 0..12: AC3MI_ERR_ARG. */
 int ac3mi_set_encode_coupling(ac3mi_ctx *ctx, int mode, int begf);
 
+/* Audio bandwidth in the encoder (new; applies to every following ac3mi_encode_batch / ac3mi_transcode_batch on `ctx`, in
+ * either packer variant, with or without state slots, tiled or not, with block switching, rematrixing and coupling on or off):
+ *   0  (default) the reference's behaviour: chbwcod 50, every full-bandwidth channel codes bins [0, 223), a coupled frame
+ *      ends at cplendf 12.  `chbwcod` is ignored.
+ *   1  every full-bandwidth channel of every uncoupled frame sends `chbwcod` (0..50) and codes bins [0, nbc),
+ *      nbc = 73 + 3 chbwcod (liba52 parse.c:699); the LFE keeps its 7 bins.
+ *   2  chbwcod follows the call's descriptor (`chbwcod` is ignored): nfbw = min(channels, 5), r = bit_rate / nfbw (integer
+ *      b/s, the descriptor's bit_rate); chbwcod 50 if r >= 96 000, else the cutoff Fc = 18 000 Hz (r >= 80 000), 16 000
+ *      (r >= 64 000), 14 000 (r >= 48 000), 11 000 (r >= 32 000) or 8 000 (below), and chbwcod the largest c in 0..50 with
+ *      (73 + 3c) sample_rate <= 512 Fc (exact integers), 0 if none.  E.g. 2/0 at 96 kb/s, 48 kHz: 25 (nbc 148); 5.1 at
+ *      384 kb/s: 32.
+ * The rule, for the chbwcod so chosen (integer arithmetic throughout):
+ *      - exponent strategies are decided exactly as in mode 0, from all 256 raw exponents: d_exponent, d_exp_strategy and
+ *        d_mdct on [0, nbc) are mode 0's.  encode_exp (min-merge over reuse runs, grouping, the +-2 constraint) runs over
+ *        nb_exps = nbc as the reference's encode_exp does over its nb_coefs, the masking curve ends at nbc's band, and bit
+ *        allocation, the SNR-offset search and the bytes follow; mode 1 with chbwcod 50 is mode 0 byte for byte;
+ *      - rematrixing (uncoupled 2/0 frames): the fourth band is [61, nbc) (liba52 parse.c:840-864 clips it to the smaller
+ *        endmant); four flags are still sent;
+ *      - coupling: a coupled frame has cplendf = min(12, chbwcod >> 2), cplendmant = 73 + 12 cplendf, and 3 + cplendf - begf
+ *        coupling bands, over which the coupling row, the energies, the decision and the coordinates run; it ends at
+ *        cplendmant, which can be up to 9 bins below nbc (the coupled channels send no chbwcod).  If begf > cplendf + 2 no
+ *        frame couples: the bytes are those of coupling off at the same bandwidth.
+ * chbwcod 51..60 (legal A/52) are not offered: the packers' member lists are sized for 5 x 223 + 7 coefficients a block.
+ * The drop-in AC3_encode_* and the byte-stream layer (ac3mi_stream.h) never band-limit.  Any other mode, or a mode-1
+ * chbwcod outside 0..50: AC3MI_ERR_ARG. */
+int ac3mi_set_encode_bandwidth(ac3mi_ctx *ctx, int mode, int chbwcod);
+
 /* Workspace bound (new; results do not depend on it, except for frames flagged AC3MI_STATUS_REUSE0 at a tile boundary).  ac3mi_decode_batch, ac3mi_encode_batch and ac3mi_transcode_batch keep
  * their intermediates (coefficient planes, MDCT coefficients, exponents, PCM between decoder and encoder: 37 / 60 /
  * 102 - 139 KB per 5.1 frame) in workspaces owned by the context.  A batch of more than `frames` frames goes through in tiles
