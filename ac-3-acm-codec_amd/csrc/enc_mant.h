@@ -13,6 +13,7 @@
 //            to the reference's "merged" marker (:1466-1480, never written) is simply a field of no bits, decided before
 //            the offsets are summed: no second attempt - one scan over the lanes' bits gives the offsets, the lane's
 //            four fields are concatenated in a 64-bit register and reach the frame with three LDS ORs.
+// Quantiser: mant_quant_lut, one expression for both kinds from the 16-byte packlut entry.
 // Out-of-contract values (sym_quant with a negative shift, :1150-1166) are wider than their fields and
 // the release build's put_bits does not mask them: the excess bits are OR-ed in a second sweep that only blocks with a
 // negative shift run (wave-uniform flag), exactly where put_bits would have put them.
@@ -56,19 +57,22 @@ __device__ __forceinline__ void mant_lists_init(uint16_t *glist, int lane)
     for (int i = lane; i < GL_KIND2 / 8; i += 64) q[i] = make_uint4(0, 0, 0, 0);
 }
 
-// What the packing passes need to know about a bap code, as fields of one word (packlut[address]):
-//   0-4 plain bits (0 for the grouped codes and bap 0)   5-6 kind (0/1/2 = member of a 3-/5-/11-level code, 3 = not grouped)
-//   7-10 bap   11-14 levels of the symmetric quantiser   15 symmetric
+// What the packing passes need to know about a bap code, as fields of one word (packlut[address].x):
+//   0-4 SH, the quantiser's final shift (mant_quant_lut)   5-9 plain bits (0 for the grouped codes and bap 0)
+//   10-11 kind (0/1/2 = member of a 3-/5-/11-level code, 3 = not grouped)   12-15 bap
 //   16-23 0x80 | bits of the grouped code (0 when not grouped)   24-28 10 * kind (position of the kind's counter in the packed rank words)
 __device__ __forceinline__ uint32_t mant_pack_word(int bp, int plain_bits)
 {
     const uint32_t kind = bp == 1 ? 0u : bp == 2 ? 1u : bp == 4 ? 2u : 3u;
     const uint32_t gbits = kind == 0 ? 5u : kind < 3 ? 7u : 0u;
-    const uint32_t levels = bp == 1 ? 3u : bp == 2 ? 5u : bp == 4 ? 11u : bp == 3 ? 7u : 15u;
-    const uint32_t sym = (kind < 3 || bp == 3 || bp == 5) ? 1u : 0u;
-    return (uint32_t)plain_bits | (kind << 5) | ((uint32_t)bp << 7) | (levels << 11) | (sym << 15) | ((kind < 3 ? 0x80u | gbits : 0u) << 16) |
+    const uint32_t sym = bp >= 1 && bp <= 5;
+    const uint32_t sh = bp == 0 ? 0u : sym ? 27u : 32u - (uint32_t)plain_bits;
+    return sh | ((uint32_t)plain_bits << 5) | (kind << 10) | ((uint32_t)bp << 12) | ((kind < 3 ? 0x80u | gbits : 0u) << 16) |
            ((10u * kind) << 24);
 }
+__device__ __forceinline__ uint32_t mant_pw_plain(uint32_t pw) { return (pw >> 5) & 31u; }
+__device__ __forceinline__ uint32_t mant_pw_kind(uint32_t pw) { return (pw >> 10) & 3u; }
+__device__ __forceinline__ uint32_t mant_pw_bap(uint32_t pw) { return (pw >> 12) & 15u; }
 
 __device__ __forceinline__ int mant_quant_sym(int c, int e, int levels)       // :1150-1166
 {
@@ -90,25 +94,46 @@ __device__ __forceinline__ int mant_quant_asym(int c, int e, int qbits)       //
     return v & ((1 << qbits) - 1);
 }
 
-// Both quantisers for a coefficient in contract - shift e >= 0 and |c| << e < 2^24, which the exponent the encoder sends
-// guarantees unless a reuse run pulled it below the block's exp_samples - with fewer instructions and no 32-bit multiply:
-//   Y = c << e;   symmetric: ((levels |Y|) >> 24 + 1) >> 1 = (levels |Y| + 2^24) >> 25, sign of c;
-//   asymmetric, w bits: c << (e + w - 24) or c >> (24 - w - e) is Y >> (24 - w) either way; ((Y >> s) + 1) >> 1 = (Y + 2^s) >> (s + 1).
-// Identical results there (tests/test_encode_gpu.py compares every frame with the oracle); blocks with a negative shift
-// anywhere take mant_quant_sym / mant_quant_asym, which restate what the x86 build does out of contract.
-__device__ __forceinline__ uint32_t mant_quant_fast(int c, int e, uint32_t pw)
+// Both quantisers as ONE expression for a coefficient in contract - shift e >= 0 and |Y| < 2^24, Y = c << e, which the exponent
+// the encoder sends guarantees unless a reuse run pulled it below the block's exp_samples:
+//   x = F Y + R  (32-bit, exact),  v = bits [30 - mw, 30) of min(x, 2^29 - 1) = (min(x, 2^29 - 1) << 2) >> SH,  SH = 32 - mw
+//   symmetric, L levels:  F = L,  R = 2^24 + (L >> 1) 2^25,  mw = 5:  (L >> 1) + floor((L Y + 2^24) / 2^25), which for Y < 0 is
+//                         (L >> 1) - ((L |Y| + 2^24) >> 25) because L |Y| = 2^24 (mod 2^25) has no solution for odd L and |Y| < 2^24;
+//                         x < 30 2^24: never clamped, a field of 5 bits whose top bit is 0
+//   asymmetric, w bits:   F = 32,  R = 2^(29 - w) = 32 2^s (s = 24 - w),  mw = w:  x = 32 (Y + 2^s), so bits [30 - w, 30) are
+//                         ((Y >> s) + 1) >> 1 = (Y + 2^s) >> (s + 1) modulo 2^w; the clamp at 2^29 - 1 is the reference's v >= m
+//   bap 0:                F = R = 0 (SH 0): v = 0
+// v_mad_u32_u24 reads the low 24 bits of Y: for Y < 0 that is Y + 2^24, so the table keeps R - F 2^24 for negative Y (.w) beside
+// R (.z), F in .y.  tests/test_quantiser_cpu.py checks the form against both quantisers for every e, level count and width.
+__device__ __forceinline__ uint4 mant_pack_entry(int bp, int plain_bits)
 {
-    const int w = (int)(pw & 31u), levels = (int)((pw >> 11) & 15u);
-    const int Y = (int)((uint32_t)c << (e & 31));
-    const int aY = Y < 0 ? -Y : Y;
-    const int vs0 = (int)((__umul24((uint32_t)levels, (uint32_t)aY) + (1u << 24)) >> 25);
-    const int vs = (levels >> 1) + (Y < 0 ? -vs0 : vs0);
-    const int s = 24 - w;
-    int va = (Y + (1 << (s & 31))) >> ((s + 1) & 31);
-    const int cm = (int)((1u << ((w - 1) & 31)) - 1u);
-    va = va < cm ? va : cm;
-    va = (int)__builtin_amdgcn_ubfe((uint32_t)va, 0u, (uint32_t)w);
-    return (uint32_t)(((pw >> 15) & 1u) ? vs : va);
+    const bool sym = bp >= 1 && bp <= 5;
+    const uint32_t levels = bp == 1 ? 3u : bp == 2 ? 5u : bp == 4 ? 11u : bp == 3 ? 7u : 15u;
+    const uint32_t F = bp == 0 ? 0u : sym ? levels : 32u;
+    const uint32_t R = bp == 0 ? 0u : sym ? (1u << 24) + ((levels >> 1) << 25) : 1u << ((29 - plain_bits) & 31);
+    return make_uint4(mant_pack_word(bp, plain_bits), F, R, R - (F << 24));
+}
+__device__ __forceinline__ uint32_t mad24_asm(uint32_t a, uint32_t b, uint32_t c)
+{
+    uint32_t r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+// e: the shift in its low 5 bits (higher bits are ignored)
+__device__ __forceinline__ uint32_t mant_quant_lut(int c, uint32_t e, const uint4 &q)
+{
+    const int Y = (int)((uint32_t)c << (e & 31u));
+    int x = (int)mad24_asm(q.y, (uint32_t)Y, Y < 0 ? q.w : q.z);
+    x = x < (1 << 29) - 1 ? x : (1 << 29) - 1;
+    return ((uint32_t)x << 2) >> (q.x & 31u);
+}
+
+// The exact quantisers of a block with a negative shift somewhere (mant_pack_block<.., true>): as the release build computes them
+__device__ __forceinline__ uint32_t mant_quant_exact(int c, int e, uint32_t pw, uint32_t levels)
+{
+    const uint32_t bp = mant_pw_bap(pw), w = mant_pw_plain(pw);
+    const int vs = mant_quant_sym(c, e, (int)levels), va = mant_quant_asym(c, e, w ? (int)w : 1);
+    return (uint32_t)(bp >= 1 && bp <= 5 ? vs : va) & 0xffffu;
 }
 
 // put_bits (:148-176) for every lane at once, no branch: a field of no bits (or outside the frame) goes to the lane's own
@@ -173,7 +198,7 @@ struct MantBlock {
     uint32_t *fr;               // the frame, MSB-first dwords (LDS)
     int frw;                    // its dwords
     uint16_t *glist;            // GL_ENTRIES member-list entries of this wavefront (LDS)
-    const uint32_t *packlut;    // mant_pack_word per bap table address (LDS)
+    const uint4 *packlut;       // mant_pack_entry per bap table address (LDS)
     const int32_t *mdb;         // the block's coefficient rows [nch][256]
     uint8_t *tap_bap;           // optional: the block's bap rows [nch][256]
     int nch, nbc;
@@ -184,7 +209,9 @@ struct MantBlock {
 
 // Packs the block's mantissas from bit `pos` on; returns the first bit after them.  ew: the encoded exponents (`em`), ad: the
 // bap table addresses (mant_block_addresses), shv: exp_samples per channel (wave-uniform), garbage: a coded coefficient
-// of the block has a negative shift (wave-uniform).
+// of the block has a negative shift (wave-uniform) - the exact quantisers and the sweep of excess bits.  (A second, inlined
+// instantiation for such blocks was measured: two copies of the passes in one kernel made the allocator spill 16 registers in
+// enc_packf_kernel<true>; a noinline one 208 bytes of scratch for its call frame.  One copy with wave-uniform branches spills none.)
 // CPL (a coupled frame, every full-bandwidth channel in coupling): the arrays are per PASS - channel 0, the coupling row (from
 // B.cplrow), channels 1 .. nfbw-1 - with the LFE's entries at index 6: the order A/52 reads the mantissas in.
 template <bool CPL = false>
@@ -246,11 +273,22 @@ __device__ __forceinline__ uint32_t mant_pack_block(const MantBlock &B, const ui
             sv = lfe_lane ? lfe_sh : sv;
         }
         const int cj[4] = {c4.x, c4.y, c4.z, c4.w};
-        uint32_t pw[4], cnt_lane = 0;
+        uint32_t pw[4], qv[4], cnt_lane = 0;
+        // quantise (:1150-1190): 16-bit values (qmant[] is unsigned short, :1347), each as soon as its table entry is in.
+        // The four shifts exponent - sv in one subtraction: sv (exp_samples, an int8: -9..5 from the MDCT) may be negative, so
+        // the subtraction may be an addition.  Bit 7 of every byte is cleared first: a coded exponent is <= 24 and keeps its
+        // value, and when the block is not `garbage` its shift lies in 0..24 - sv; a bin the pass does not code (exponent 255,
+        // below cplstrtmant in the coupling pass, above nbc elsewhere) becomes 127 - sv, in 0..255 for every int8 sv, and
+        // an LFE lane's bap-0 slot (24) 24 - sv.  So no byte borrows from or carries into its neighbour; the uncoded ones have
+        // table address 0 (bap 0: value 0 whatever their shift).
+        const uint32_t e4s = (e4 & 0x7f7f7f7fu) - (uint32_t)sv * 0x01010101u;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            pw[j] = B.packlut[(a4 >> (8 * j)) & 63u];
+            const uint4 qw = B.packlut[(a4 >> (8 * j)) & 63u];
+            pw[j] = qw.x;
             cnt_lane += 1u << (pw[j] >> 24);                    // (a bin that is not grouped counts in bits 30-31: ignored)
+            if (garbage) qv[j] = mant_quant_exact(cj[j], (int)((e4 >> (8 * j)) & 0xff) - sv, qw.x, qw.y);
+            else qv[j] = mant_quant_lut(cj[j], e4s >> (8 * j), qw);
         }
         // ranks: the kind's count in the block modulo its group size (0..2 / 0..1) + the lanes before + the lane's own bins
         const int G0 = (int)(((uint32_t)P0 * 0xaaabu) >> 17), G1 = (int)(((uint32_t)P1 * 0xaaabu) >> 17), G2 = P2 >> 1;
@@ -258,23 +296,9 @@ __device__ __forceinline__ uint32_t mant_pack_block(const MantBlock &B, const ui
         bw[p] = (uint32_t)G0 | ((uint32_t)G1 << 10) | ((uint32_t)G2 << 20);
         const uint32_t gin = wave_incl_scan_u32(cnt_lane);
         uint32_t run = gin - cnt_lane + phase;
-        // quantise (:1150-1190): 16-bit values (qmant[] is unsigned short, :1347)
-        uint32_t qv[4];
-        if (garbage) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int levels = (int)((pw[j] >> 11) & 15u), w = (int)(pw[j] & 31u);
-                const int e = (int)((e4 >> (8 * j)) & 0xff) - sv;
-                const int vs = mant_quant_sym(cj[j], e, levels), va = mant_quant_asym(cj[j], e, w ? w : 1);
-                qv[j] = (uint32_t)(((pw[j] >> 15) & 1u) ? vs : va) & 0xffffu;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; j++) qv[j] = mant_quant_fast(cj[j], (int)((e4 >> (8 * j)) & 0xff) - sv, pw[j]) & 0xffffu;
-        }
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const uint32_t sh = pw[j] >> 24, kind = (pw[j] >> 5) & 3u;
+            const uint32_t sh = pw[j] >> 24, kind = mant_pw_kind(pw[j]);
             const uint32_t r = __builtin_amdgcn_ubfe(run, sh, 10u);         // rank counted from the opener of the group open at the pass's start
             run += 1u << sh;
             const uint32_t k1 = kind >> 1;                                   // members per group: 3 - k1
@@ -287,16 +311,16 @@ __device__ __forceinline__ uint32_t mant_pack_block(const MantBlock &B, const ui
             const uint32_t q = qv[j];
             const uint32_t lpos = kind * (uint32_t)GL_STRIDE + 2u * __builtin_amdgcn_ubfe(bw[p], sh, 10u) + arel - 1u;
             B.glist[u ? lpos : (uint32_t)(GL_SINK + lane)] = (uint16_t)q;
-            st[p][j] = q | (arel << 16) | (((pw[j] & 0x7fu) | t) << 24);    // (0x80 of t: bit 31; its code bits replace the - zero - plain bits)
+            st[p][j] = q | (arel << 16) | ((((pw[j] >> 5) & 0x7fu) | t) << 24);    // (0x80 of t: bit 31; its code bits replace the - zero - plain bits)
         }
         if (B.tap_bap && !(CPL && p == 1)) {
             uint8_t *tb = B.tap_bap + (CPL && p > 1 ? p - 1 : p) * 256;
-            const uint32_t four = ((pw[0] >> 7) & 15u) | (((pw[1] >> 7) & 15u) << 8) | (((pw[2] >> 7) & 15u) << 16) | (((pw[3] >> 7) & 15u) << 24);
+            const uint32_t four = mant_pw_bap(pw[0]) | (mant_pw_bap(pw[1]) << 8) | (mant_pw_bap(pw[2]) << 16) | (mant_pw_bap(pw[3]) << 24);
             *reinterpret_cast<uint32_t *>(tb + 4 * lane) = lfe_lane ? 0u : four;
             if (merged) {                                       // the LFE's row: bins 0..6 from lanes 56..62, zeros beyond
                 uint8_t *tl = B.tap_bap + (nch - 1) * 256;
                 if (lane >= 2) *reinterpret_cast<uint32_t *>(tl + 4 * lane) = 0u;
-                if (lfe_lane) tl[lk] = (uint8_t)(lk < 7 ? (pw[0] >> 7) & 15u : 0u);
+                if (lfe_lane) tl[lk] = (uint8_t)(lk < 7 ? mant_pw_bap(pw[0]) : 0u);
             }
         }
         {

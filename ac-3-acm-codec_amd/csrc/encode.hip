@@ -1889,7 +1889,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
 template <bool CPL>
 struct alignas(16) PackfLDS {
     int16_t mask[CPL ? 7 : 6][50];  // this block's masking curves as band terms (mant_band_terms), one row per channel (+ coupling)
-    uint32_t packlut[64];               // mant_pack_word per bap table address
+    uint4 packlut[64];                  // mant_pack_entry per bap table address
     alignas(16) uint16_t glist[GL_ENTRIES];
     alignas(4) uint8_t erow[256];       // encoded exponents of the channel whose exponent groups are being packed
     alignas(4) uint16_t crc_tab[256];
@@ -1897,7 +1897,9 @@ struct alignas(16) PackfLDS {
 };
 
 #ifndef ENC_PACK2_LB
-#define ENC_PACK2_LB 4           // 115 VGPRs, no scratch: 1.78 ms per 65 536 frames against 1.84 at 5 per SIMD (96 VGPRs, 72 bytes of scratch)
+#define ENC_PACK2_LB 4           // <true>: 125 VGPRs, no scratch (<true, false, true>: 11 VGPRs spilled, the coupled ones none).  5 per SIMD cannot
+                                 // be reached any more: with the 1-KiB quantiser table a 384 kbps frame's workgroup takes ~9.6 KB of LDS, 16 per CU
+                                 // (round 4, before the table: 1.78 ms per 65 536 frames at 4 against 1.84 at 5)
 #endif
 // FIXED51: the 5.1 configuration (five full-bandwidth channels + LFE, acmod 7) as compile-time constants - the shape large batches
 // have; its five mantissa passes, the merged LFE lanes and the side information's field list then need no tests
@@ -1918,7 +1920,7 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
     for (int i = lane; i < 256; i += 64) L.crc_tab[i] = P.tab->crc_tab[i];
     {
         const int bp = P.tab->baptab[lane];
-        L.packlut[lane] = mant_pack_word(bp, plain_bits(bp));
+        L.packlut[lane] = mant_pack_entry(bp, plain_bits(bp));
     }
     mant_lists_init(L.glist, lane);
     const uint32_t bandoff = *reinterpret_cast<const uint32_t *>(&P.tab->band_of_bin[4 * lane]);     // bands of bins 4*lane..+3
@@ -2225,7 +2227,7 @@ struct PackbWave {                  // per wavefront = audio block
 };
 struct alignas(16) PackbLDS {
     PackbWave w[6];
-    uint32_t packlut[64];
+    uint4 packlut[64];
     uint16_t crc_tab[256];
     uint8_t band_of_bin[256];
     uint32_t blk_bits[6];           // bits of each block: nominal (from the bap codes) ...
@@ -2235,7 +2237,7 @@ struct alignas(16) PackbLDS {
 };
 
 #ifndef ENC_PACKB_LB
-#define ENC_PACKB_LB 4        // 128 VGPRs, 12 bytes of scratch (6: 80 VGPRs, 204 bytes).  Its batches fit the chip several times over, so a frame's latency
+#define ENC_PACKB_LB 4        // 128 VGPRs, 5 spilled, 24 bytes of scratch (6: 80 VGPRs, 204 bytes).  Its batches fit the chip several times over, so a frame's latency
                               // counts, not occupancy: cold encode 0.107 / 0.113 / 0.189 / 0.286 ms per 64 / 256 / 1 024 / 2 048 frames against 0.110 /
                               // 0.121 / 0.186 / 0.291 at 6
 #endif
@@ -2260,7 +2262,7 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
         L.band_of_bin[i] = P.tab->band_of_bin[i];
         L.crc_tab[i] = P.tab->crc_tab[i];
     }
-    if (tid < 64) { const int bp = P.tab->baptab[tid]; L.packlut[tid] = mant_pack_word(bp, plain_bits(bp)); }
+    if (tid < 64) { const int bp = P.tab->baptab[tid]; L.packlut[tid] = mant_pack_entry(bp, plain_bits(bp)); }
     for (int i = tid; i < P.frw / 4; i += 384) reinterpret_cast<uint4 *>(fr)[i] = make_uint4(0, 0, 0, 0);
     const size_t rowb = (fidx * 6 + b) * nch;
     uint32_t mrows[3] = {0u, 0u, 0u};                   // the block's masking curves, two bands per dword (to LDS as band terms once the offsets are known)
@@ -2328,9 +2330,9 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
                 if (ch >= nch) continue;
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    const uint32_t w = L.packlut[(ad[ch] >> (8 * j)) & 63u];
+                    const uint32_t w = L.packlut[(ad[ch] >> (8 * j)) & 63u].x;
                     cnt += 1u << (w >> 24);
-                    plain += w & 31u;
+                    plain += mant_pw_plain(w);
                 }
             }
             const uint32_t s1 = wave_sum_u32((cnt & 1023u) | (((cnt >> 10) & 1023u) << 16));
