@@ -154,6 +154,15 @@ struct CplWs {
 constexpr int CPL_FRAME_BYTES = 16 + 80 + 6 * 256 * 4 + 8 + 6 * 256 + 6 * 50 * 2 + 8 + 8;
 constexpr int CPL_REMAT_FRAME_BYTES = 6 * 2 * 256 * 4 + 16 + 6 * 2 * 256 + 6 * 2 * 50 * 2 + 16 + 16;
 
+// the encoder's BSI fields (ac3mi_set_encode_metadata) in one word: dialnorm bits 0-4, bsmod 5-7, cmixlev 8-9, surmixlev
+// 10-11, dsurmod 12-13, copyrightb 14, origbs 15
+constexpr uint32_t bsi_word(int dialnorm, int bsmod, int cmixlev, int surmixlev, int dsurmod, int copyrightb, int origbs)
+{
+    return (uint32_t)dialnorm | (uint32_t)bsmod << 5 | (uint32_t)cmixlev << 8 | (uint32_t)surmixlev << 10 |
+           (uint32_t)dsurmod << 12 | (uint32_t)copyrightb << 14 | (uint32_t)origbs << 15;
+}
+constexpr uint32_t BSI_DEFAULT = bsi_word(31, 0, 1, 1, 0, 0, 1);      // the reference's fixed BSI
+
 struct EncodeLaunch {
     EncConfig cfg;
     const int16_t *pcm;         // [S][F][1536][nch]
@@ -184,6 +193,11 @@ struct EncodeLaunch {
     CplWs ws_cpl = {};          // its per-frame results (cpl_begf >= 0)
     int chbwcod = 50;           // ac3mi_set_encode_bandwidth: the call's chbwcod (0..50), nbc = 73 + 3 chbwcod
     bool bw = false;            // ... and whether it is on (mode 1 or 2): the runtime-bandwidth kernel variants run
+    uint32_t bsi = BSI_DEFAULT; // ac3mi_set_encode_metadata, packed (bsi_word); not the default: the packers' MD variants run
+    int drc_profile = 0;        // ac3mi_set_encode_drc: 1..5, 0 = no dynrng words
+    int32_t *drc_state = nullptr;   // its smoothing state, [S] (or by slot)
+    int16_t *ws_drc_gain = nullptr; // [S][F][6] static-curve gains (drc_profile > 0)
+    uint8_t *ws_drc_code = nullptr; // [S][F][6] dynrng codes for the search and the packers
 };
 // carves CPL_FRAME_BYTES * nfr bytes at `base` into the arrays of CplWs (base 16-byte aligned)
 CplWs cpl_slices(void *base, size_t nfr);
@@ -216,6 +230,11 @@ struct ac3mi_ctx {
     size_t ws_remat_bytes;
     int coupling, cpl_begf; // ac3mi_set_encode_coupling
     int bw_mode, bw_chbwcod;    // ac3mi_set_encode_bandwidth
+    uint32_t enc_bsi;       // ac3mi_set_encode_metadata (ac3mi::bsi_word)
+    int drc_profile;        // ac3mi_set_encode_drc
+    int32_t *drc_state;
+    void *ws_drc;           // its gains and codes between the DRC kernels, the search and the packers, 3 bytes a frame-block
+    size_t ws_drc_bytes;
     void *ws_cpl;           // its per-frame workspace (ac3mi::CplWs, CPL_FRAME_BYTES a frame)
     size_t ws_cpl_bytes;
     void *ws_cplr;          // with rematrixing on as well: CPL_REMAT_FRAME_BYTES a frame

@@ -495,6 +495,11 @@ ac3mi_ctx *ac3mi_create(int device)
     ctx->cpl_begf = 0;
     ctx->bw_mode = 0;
     ctx->bw_chbwcod = 50;
+    ctx->enc_bsi = ac3mi::BSI_DEFAULT;
+    ctx->drc_profile = 0;
+    ctx->drc_state = nullptr;
+    ctx->ws_drc = nullptr;
+    ctx->ws_drc_bytes = 0;
     ctx->ws_cpl = nullptr;
     ctx->ws_cpl_bytes = 0;
     ctx->ws_cplr = nullptr;
@@ -537,6 +542,7 @@ void ac3mi_destroy(ac3mi_ctx *ctx)
     (void)hipFree(ctx->ws_remat);
     (void)hipFree(ctx->ws_cpl);
     (void)hipFree(ctx->ws_cplr);
+    (void)hipFree(ctx->ws_drc);
     (void)hipFree(ctx->tab.enc);
     (void)hipEventDestroy(ctx->ev0);
     (void)hipEventDestroy(ctx->ev1);
@@ -793,6 +799,31 @@ static int call_chbwcod(const ac3mi_ctx *ctx, const ac3mi_encode_desc *d)
     return c;
 }
 
+int ac3mi_set_encode_metadata(ac3mi_ctx *ctx, const ac3mi_encode_metadata *md)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (!md) {
+        ctx->enc_bsi = ac3mi::BSI_DEFAULT;
+        return AC3MI_OK;
+    }
+    auto in = [](int v, int lo, int hi) { return v >= lo && v <= hi; };
+    if (!in(md->dialnorm, 1, 31) || !in(md->bsmod, 0, 7) || !in(md->cmixlev, 0, 2) || !in(md->surmixlev, 0, 2) ||
+        !in(md->dsurmod, 0, 2) || !in(md->copyrightb, 0, 1) || !in(md->origbs, 0, 1)) {
+        ctx->err = "ac3mi_set_encode_metadata: field out of range";
+        return AC3MI_ERR_ARG;
+    }
+    ctx->enc_bsi = ac3mi::bsi_word(md->dialnorm, md->bsmod, md->cmixlev, md->surmixlev, md->dsurmod, md->copyrightb, md->origbs);
+    return AC3MI_OK;
+}
+
+int ac3mi_set_encode_drc(ac3mi_ctx *ctx, int profile, int32_t *d_drc_state)
+{
+    if (!ctx || profile < 0 || profile > 5 || (profile != 0 && !d_drc_state)) return AC3MI_ERR_ARG;
+    ctx->drc_profile = profile;
+    ctx->drc_state = profile ? d_drc_state : nullptr;
+    return AC3MI_OK;
+}
+
 int ac3mi_set_tile_frames(ac3mi_ctx *ctx, long long frames)
 {
     if (!ctx || frames < 0) return AC3MI_ERR_ARG;
@@ -878,6 +909,31 @@ static int ensure_remat(ac3mi_ctx *ctx, size_t nfr)
     HIPCHK(ctx, hipMalloc((void **)&ctx->ws_remat, 6 * nfr));
     ctx->ws_remat_bytes = 6 * nfr;
     return AC3MI_OK;
+}
+
+// the DRC workspace of `nfr` frames: [nfr][6] int16 gains, then [nfr][6] codes (profile 0 allocates nothing)
+static int ensure_drc(ac3mi_ctx *ctx, size_t nfr)
+{
+    if (18 * nfr <= ctx->ws_drc_bytes) return AC3MI_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(ctx->ws_drc);
+    ctx->ws_drc = nullptr;
+    ctx->ws_drc_bytes = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->ws_drc, 18 * nfr));
+    ctx->ws_drc_bytes = 18 * nfr;
+    return AC3MI_OK;
+}
+
+// the encoder's metadata and DRC settings into a launch of frames f0.. of a DRC workspace carved for nfr frames (the state
+// pointer as the context holds it: callers offset it to their first stream when there are no slots)
+static void set_drc(const ac3mi_ctx *ctx, EncodeLaunch &E, size_t nfr, size_t f0)
+{
+    E.bsi = ctx->enc_bsi;
+    E.drc_profile = ctx->drc_profile;
+    if (!ctx->drc_profile) return;
+    E.drc_state = ctx->drc_state;
+    E.ws_drc_gain = (int16_t *)ctx->ws_drc + f0 * 6;
+    E.ws_drc_code = (uint8_t *)ctx->ws_drc + nfr * 12 + f0 * 6;
 }
 
 // the coupling workspace of `nfr` frames (mode 1 only: mode 0 allocates nothing)
@@ -1375,16 +1431,19 @@ int ac3mi_encode_batch(ac3mi_ctx *ctx, const ac3mi_encode_desc *desc, const int1
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (const int g = taps ? 0 : tile_streams(ctx, n_streams, frames_per_stream)) {
         const int32_t *slots0 = ctx->slots;
+        int32_t *const ds0 = ctx->drc_state;
         int rc = AC3MI_OK;
         for (int s0 = 0; s0 < n_streams && rc == AC3MI_OK; s0 += g) {
             const int ns = n_streams - s0 < g ? n_streams - s0 : g;
             const size_t f0 = (size_t)s0 * frames_per_stream;
             if (slots0) ctx->slots = slots0 + s0;
+            else if (ds0) ctx->drc_state = ds0 + s0;
             rc = ac3mi_encode_batch(ctx, desc, d_pcm + f0 * 1536 * E.cfg.nch, chmap,
                                     slots0 ? d_last : d_last + (size_t)s0 * E.cfg.nch * 256, slots0 ? d_csnroffst : d_csnroffst + s0,
                                     d_frames + f0 * frame_stride, frame_stride, ns, frames_per_stream, nullptr);
         }
         ctx->slots = slots0;
+        ctx->drc_state = ds0;
         return rc;
     }
     const size_t rows = (size_t)n_streams * frames_per_stream * 6 * E.cfg.nch;
@@ -1420,6 +1479,11 @@ int ac3mi_encode_batch(ac3mi_ctx *ctx, const ac3mi_encode_desc *desc, const int1
             ac3mi::cpl_remat_slices(E.ws_cpl, ctx->ws_cplr, (size_t)n_streams * frames_per_stream);
         }
     }
+    if (ctx->drc_profile) {
+        const int r = ensure_drc(ctx, (size_t)n_streams * frames_per_stream);
+        if (r != AC3MI_OK) return r;
+    }
+    set_drc(ctx, E, (size_t)n_streams * frames_per_stream, 0);
     E.ws_mdct = (int32_t *)ctx->ws_enc;
     E.ws_expo = nullptr;                                                   // raw exponents leave the MDCT kernel only as a tap
     E.ws_eexp = (uint8_t *)ctx->ws_enc + off_eexp;
@@ -1498,12 +1562,14 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         const int32_t *slots0 = ctx->slots;
         float *const mp0 = ctx->mix_pending;
         int32_t *const mf0 = ctx->mix_flags;
+        int32_t *const ds0 = ctx->drc_state;
         int rc = AC3MI_OK;
         for (int s0 = 0; s0 < n_streams && rc == AC3MI_OK; s0 += g) {
             const int ns = n_streams - s0 < g ? n_streams - s0 : g;
             const size_t f0 = (size_t)s0 * frames_per_stream;
             if (slots0) ctx->slots = slots0 + s0;
             else if (mp0) { ctx->mix_pending = mp0 + (size_t)s0 * n_out * 128; ctx->mix_flags = mf0 + (size_t)s0 * 6; }
+            if (!slots0 && ds0) ctx->drc_state = ds0 + s0;
             rc = ac3mi_transcode_batch(ctx, dec, enc, d_frames_in + f0 * in_stride, in_stride, ns, frames_per_stream,
                                        slots0 ? d_delay : d_delay + (size_t)s0 * n_out * 128, slots0 ? d_lfsr : d_lfsr + s0, chmap,
                                        slots0 ? d_last : d_last + (size_t)s0 * E.cfg.nch * 256, slots0 ? d_csnroffst : d_csnroffst + s0,
@@ -1512,6 +1578,7 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         ctx->slots = slots0;
         ctx->mix_pending = mp0;
         ctx->mix_flags = mf0;
+        ctx->drc_state = ds0;
         return rc;
     }
     const size_t F = (size_t)frames_per_stream, nfr = (size_t)n_streams * F;
@@ -1554,6 +1621,7 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     if (ctx->block_switch) { const int r = ensure_bsw(ctx, rows); if (r != AC3MI_OK) return r; }
     if (ctx->rematrix) { const int r = ensure_remat(ctx, nfr); if (r != AC3MI_OK) return r; }
     if (ctx->coupling) { const int r = ensure_cpl(ctx, nfr); if (r != AC3MI_OK) return r; }
+    if (ctx->drc_profile) { const int r = ensure_drc(ctx, nfr); if (r != AC3MI_OK) return r; }
     ac3mi::CplWs cplw = ctx->coupling ? ac3mi::cpl_slices(ctx->ws_cpl, nfr) : ac3mi::CplWs{};
     if (ctx->coupling && ctx->rematrix && E.cfg.acmod == 2 && E.cfg.nch == 2) {
         const int r = ensure_cplr(ctx, nfr);
@@ -1659,6 +1727,8 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         G.ws_remat = ctx->rematrix ? ctx->ws_remat + f0 * 6 : nullptr;
         G.cpl_begf = ctx->coupling ? ctx->cpl_begf : -1;
         G.ws_cpl = ctx->coupling ? cpl_at(cplw, f0) : ac3mi::CplWs{};
+        set_drc(ctx, G, nfr, f0);
+        if (G.drc_state && !ctx->slots) G.drc_state += s0;
         G.pcm = ws_s16 + f0 * 1536 * n_out;
         G.last = ctx->slots ? d_last : d_last + (size_t)s0 * E.cfg.nch * 256;
         G.csnr = ctx->slots ? d_csnroffst : d_csnroffst + s0;

@@ -22,6 +22,8 @@
 #include "spec_tables.h"
 #include "enc_mant.h"
 
+#include <type_traits>
+
 namespace ac3mi {
 
 #define WAVE_SYNC()                                          \
@@ -74,7 +76,12 @@ struct PackParams {
     CplWs cpl;                  // channel coupling (enc_cpl_kernel); cpl.word null: none
     int cpl_begf;
     int cpl_endf;               // cplendf of a coupled frame: 12, min(12, chbwcod >> 2) in the BW variants (cplendmant 73 + 12 cplendf)
+    const uint8_t *drc;         // the DRC variants: [S][F][6] dynrng codes (enc_drc_smooth_kernel); null in the others
+    uint32_t bsi;               // the MD packers: the BSI fields (bsi_word)
 };
+
+// dynrng words of a frame (ac3mi_set_encode_drc): block 0 sends its code, block b > 0 only when it differs from block b - 1's
+__device__ __forceinline__ bool drc_sends(const uint8_t *code, int b) { return b == 0 || code[b] != code[b - 1]; }
 
 
 
@@ -1396,7 +1403,8 @@ __device__ unsigned long long g_pack_cycles[16];
 // enc_search_kernel<1>: one wavefront per stream, frames in order; <3>: one wavefront per frame tabulates (see above).
 // CPL (enc_search_cpl_kernel: channel coupling on, P.cpl): the coupling rows join the costed rows of a coupled frame.
 // BW (with CPL; ac3mi_set_encode_bandwidth 1 or 2): a coupled frame ends at cplendmant = 73 + 12 P.cpl_endf, not 217.
-template <int PART, bool CPL = false, bool BW = false>
+// DRC (ac3mi_set_encode_drc 1..5): every block that sends a dynrng word (P.drc) costs its 8 bits.
+template <int PART, bool CPL = false, bool BW = false, bool DRC = false>
 __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const PackParams P)
 {
     static_assert(PART == 1 || PART == 3, "the packers are enc_packf_kernel / enc_packb_kernel");
@@ -1489,6 +1497,10 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                 frame_bits += 2 * 4 + 3 + 6 + nch * (4 + 3);
                 frame_bits += 2;
                 frame_bits += 16;
+                if constexpr (DRC) {
+                    const uint8_t *code = P.drc + fidx * 6;
+                    for (int b = 0; b < 6; b++) frame_bits += drc_sends(code, b) ? 8 : 0;
+                }
                 // rematrixing: the four flags of every block 1..5 that sends them (block 0's stay uncounted, as above)
                 if (P.remat)
                     for (int b = 1; b < 6; b++) frame_bits += (P.remat[fidx * 6 + b] & 0x10) ? 4 : 0;
@@ -1906,7 +1918,8 @@ struct alignas(16) PackfLDS {
 // CPL: coupled frames (channel coupling on, never with FIXED51): the coupling fields, exponents and mantissa pass
 // BW (ac3mi_set_encode_bandwidth 1 or 2): FIXED51 with the run-time nbc; CPL with the coupling range ending at cplendmant =
 // 73 + 12 P.cpl_endf (3 + cpl_endf - cpl_begf bands, cplendf = P.cpl_endf)
-template <bool FIXED51, bool CPL = false, bool BW = false>
+// MD (ac3mi_set_encode_metadata / ac3mi_set_encode_drc): the BSI fields of P.bsi, and the dynrng words of P.drc if it is set
+template <bool FIXED51, bool CPL = false, bool BW = false, bool MD = false>
 __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackParams P)
 {
     static_assert(!(FIXED51 && CPL), "coupled frames take the generic packer");
@@ -1983,12 +1996,22 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
             nacc = 0;
         }
     };
-    put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, 0); put(3, acmod);
-    flush();
-    if ((acmod & 1) && acmod != 1) put(2, 1);
-    if (acmod & 4) put(2, 1);
-    if (acmod == 2) put(2, 0);
-    put(1, lfe); put(5, 31); put(3, 0); put(1, 0); put(1, 1); put(3, 0);
+    if constexpr (MD) {
+        const uint32_t m = P.bsi;
+        put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, (m >> 5) & 7u); put(3, acmod);
+        flush();
+        if ((acmod & 1) && acmod != 1) put(2, (m >> 8) & 3u);
+        if (acmod & 4) put(2, (m >> 10) & 3u);
+        if (acmod == 2) put(2, (m >> 12) & 3u);
+        put(1, lfe); put(5, m & 31u); put(3, 0); put(1, (m >> 14) & 1u); put(1, (m >> 15) & 1u); put(3, 0);
+    } else {
+        put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, 0); put(3, acmod);
+        flush();
+        if ((acmod & 1) && acmod != 1) put(2, 1);
+        if (acmod & 4) put(2, 1);
+        if (acmod == 2) put(2, 0);
+        put(1, lfe); put(5, 31); put(3, 0); put(1, 0); put(1, 1); put(3, 0);
+    }
 
     // ---- audio blocks (:1194-1502) ----
 #pragma unroll 1
@@ -2023,7 +2046,13 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         else
             for (int ch = 0; ch < nfbw; ch++) put(1, 0);
         for (int ch = 0; ch < nfbw; ch++) put(1, 1);
-        put(1, 0);
+        if constexpr (MD) {
+            // dynrnge + dynrng (flushed: the block's first stretch of fields stays within the accumulator)
+            if (P.drc && drc_sends(P.drc + fidx * 6, b)) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
+            else put(1, 0);
+        } else {
+            put(1, 0);
+        }
         if (cplf) {
             // cplstre, cplinu, chincpl, phsflginu, cplbegf, cplendf, cplbndstrc (all 0); cplcoe, mstrcplco, the coordinates
             if (b == 0) {
@@ -2241,6 +2270,8 @@ struct alignas(16) PackbLDS {
                               // counts, not occupancy: cold encode 0.107 / 0.113 / 0.189 / 0.286 ms per 64 / 256 / 1 024 / 2 048 frames against 0.110 /
                               // 0.121 / 0.186 / 0.291 at 6
 #endif
+// MD (ac3mi_set_encode_metadata / ac3mi_set_encode_drc): the BSI fields of P.bsi, and the dynrng words of P.drc if it is set
+template <bool MD = false>
 __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const PackParams P)
 {
     __shared__ PackbLDS L;
@@ -2303,6 +2334,8 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
                     1 + (b == 0 ? 11 : 0) + 1 + (b == 0 ? 6 + 7 * nch : 0) + 2;
     const int rem = P.remat ? (int)P.remat[fidx * 6 + b] : -1;     // rematrixing: block b > 0 sends its four flags when rematstr
     if (b > 0 && rem >= 0 && (rem & 0x10)) side_bits += 4;
+    const bool drc_word = MD && P.drc && drc_sends(P.drc + fidx * 6, b);
+    if (drc_word) side_bits += 8;
     for (int ch = 0; ch < nch; ch++) {
         const int stg = strat_of(ch);
         if (stg == 0) continue;
@@ -2364,12 +2397,22 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
         if (b == 0) {                               // the frame header is block 0's to write
             const uint32_t mine = pos;
             pos = 0;
-            put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, 0); put(3, P.acmod);
-            flush();
-            if ((P.acmod & 1) && P.acmod != 1) put(2, 1);
-            if (P.acmod & 4) put(2, 1);
-            if (P.acmod == 2) put(2, 0);
-            put(1, P.lfe); put(5, 31); put(3, 0); put(1, 0); put(1, 1); put(3, 0);
+            if constexpr (MD) {
+                const uint32_t m = P.bsi;
+                put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, (m >> 5) & 7u); put(3, P.acmod);
+                flush();
+                if ((P.acmod & 1) && P.acmod != 1) put(2, (m >> 8) & 3u);
+                if (P.acmod & 4) put(2, (m >> 10) & 3u);
+                if (P.acmod == 2) put(2, (m >> 12) & 3u);
+                put(1, P.lfe); put(5, m & 31u); put(3, 0); put(1, (m >> 14) & 1u); put(1, (m >> 15) & 1u); put(3, 0);
+            } else {
+                put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, 0); put(3, P.acmod);
+                flush();
+                if ((P.acmod & 1) && P.acmod != 1) put(2, 1);
+                if (P.acmod & 4) put(2, 1);
+                if (P.acmod == 2) put(2, 0);
+                put(1, P.lfe); put(5, 31); put(3, 0); put(1, 0); put(1, 1); put(3, 0);
+            }
             flush();
             pos = mine;
         }
@@ -2378,7 +2421,13 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
         else
             for (int ch = 0; ch < nfbw; ch++) put(1, 0);
         for (int ch = 0; ch < nfbw; ch++) put(1, 1);
-        put(1, 0);
+        if constexpr (MD) {
+            // dynrnge + dynrng (flushed: the fields up to the first exponent would overflow the accumulator by up to 2 bits)
+            if (drc_word) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
+            else put(1, 0);
+        } else {
+            put(1, 0);
+        }
         if (b == 0) { put(1, 1); put(1, 0); } else put(1, 0);
         if (P.acmod == 2) {
             if (rem >= 0) {
@@ -2511,6 +2560,175 @@ static uint32_t h_gf_pow(uint32_t a, uint32_t n)
     return r;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Dynamic range control (ac3mi_set_encode_drc; the rule is include/ac3mi.h's).  Two kernels before the search:
+//   enc_drc_gain_kernel    one wavefront per frame: the six block energies from the PCM (a read of its own: the DRC-off
+//                          MDCT kernels stay as they are), levels relative to dialnorm and the profile's static gain
+//   enc_drc_smooth_kernel  one lane per stream, its frames in order: the attack / release smoothing and the codes
+// The tables are exact (no entry within 1e-4 of a rounding tie), computed once in double precision and frozen here:
+//   DRC_LG[m] = round(256 log2(1 + m / 256)), DRC_XT[f] = round(32 (2^(f / 256) - 1)); DN[d] is folded in on the host.
+__constant__ uint8_t DRC_LG[256] = {
+    0, 1, 3, 4, 6, 7, 9, 10, 11, 13, 14, 16, 17, 18, 20, 21, 22, 24, 25, 26, 28, 29, 30, 32, 33, 34, 36, 37, 38, 40, 41, 42,
+    44, 45, 46, 47, 49, 50, 51, 52, 54, 55, 56, 57, 59, 60, 61, 62, 63, 65, 66, 67, 68, 69, 71, 72, 73, 74, 75, 77, 78, 79, 80, 81,
+    82, 84, 85, 86, 87, 88, 89, 90, 92, 93, 94, 95, 96, 97, 98, 99, 100, 102, 103, 104, 105, 106, 107, 108, 109, 110, 111, 112, 113, 114, 116, 117,
+    118, 119, 120, 121, 122, 123, 124, 125, 126, 127, 128, 129, 130, 131, 132, 133, 134, 135, 136, 137, 138, 139, 140, 141, 142, 143, 144, 145, 146, 147, 148, 149,
+    150, 151, 152, 153, 154, 155, 155, 156, 157, 158, 159, 160, 161, 162, 163, 164, 165, 166, 167, 168, 169, 169, 170, 171, 172, 173, 174, 175, 176, 177, 178, 178,
+    179, 180, 181, 182, 183, 184, 185, 185, 186, 187, 188, 189, 190, 191, 192, 192, 193, 194, 195, 196, 197, 198, 198, 199, 200, 201, 202, 203, 203, 204, 205, 206,
+    207, 208, 208, 209, 210, 211, 212, 212, 213, 214, 215, 216, 216, 217, 218, 219, 220, 220, 221, 222, 223, 224, 224, 225, 226, 227, 228, 228, 229, 230, 231, 231,
+    232, 233, 234, 234, 235, 236, 237, 238, 238, 239, 240, 241, 241, 242, 243, 244, 244, 245, 246, 247, 247, 248, 249, 249, 250, 251, 252, 252, 253, 254, 255, 255};
+__constant__ uint8_t DRC_XT[256] = {
+    0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 3, 3, 3, 3,
+    3, 3, 3, 3, 3, 3, 3, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 6, 6, 6, 6, 6,
+    6, 6, 6, 6, 6, 7, 7, 7, 7, 7, 7, 7, 7, 7, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 9, 9, 9, 9, 9, 9, 9, 9,
+    9, 10, 10, 10, 10, 10, 10, 10, 10, 11, 11, 11, 11, 11, 11, 11, 11, 11, 12, 12, 12, 12, 12, 12, 12, 12, 13, 13, 13, 13, 13, 13,
+    13, 13, 14, 14, 14, 14, 14, 14, 14, 14, 14, 15, 15, 15, 15, 15, 15, 15, 16, 16, 16, 16, 16, 16, 16, 16, 17, 17, 17, 17, 17, 17,
+    17, 17, 18, 18, 18, 18, 18, 18, 18, 19, 19, 19, 19, 19, 19, 19, 20, 20, 20, 20, 20, 20, 20, 21, 21, 21, 21, 21, 21, 21, 22, 22,
+    22, 22, 22, 22, 22, 23, 23, 23, 23, 23, 23, 23, 24, 24, 24, 24, 24, 24, 25, 25, 25, 25, 25, 25, 25, 26, 26, 26, 26, 26, 26, 27,
+    27, 27, 27, 27, 27, 27, 28, 28, 28, 28, 28, 28, 29, 29, 29, 29, 29, 29, 30, 30, 30, 30, 30, 30, 31, 31, 31, 31, 31, 31, 32, 32};
+// DN[d] = round(256 d / (20 log10 2)), d = dialnorm 0..31
+static const int16_t DRC_DN[32] = {0, 43, 85, 128, 170, 213, 255, 298, 340, 383, 425, 468, 510, 553, 595, 638,
+                                   680, 723, 765, 808, 850, 893, 935, 978, 1020, 1063, 1106, 1148, 1191, 1233, 1276, 1318};
+// the static curves of profiles 1..5: MB, Rb, N0, N1, C0, Re, Rc (lv)
+static const int16_t DRC_CURVE[5][7] = {{255, 2, 0, 213, 638, 2, 20}, {255, 2, -425, 425, 850, 2, 20}, {510, 2, 0, 213, 638, 2, 20},
+                                        {510, 2, -425, 425, 425, 2, 2}, {638, 5, 0, 213, 638, 2, 20}};
+
+struct DrcParams {
+    const int16_t *pcm;         // [S][F][1536][nch] interleaved
+    int16_t *gain;              // [S][F][6] static-curve gains (lv)
+    uint8_t *code;              // [S][F][6] dynrng codes
+    int32_t *state;             // [S] smoothing state (lv), or by slot
+    const int32_t *slot;
+    int n_streams, frames, nch;
+    uint32_t fbw_in;            // bit c: input channel c is a coded full-bandwidth channel (chmap[0 .. nfbw - 1])
+    int dn;                     // DN[dialnorm]
+    int mb, rb, n0, n1, c0, re, rc;
+};
+
+// VEC (the PCM 16-byte aligned, as every frame then is: 3 072 nch bytes apart): eight samples per load, a block's at most
+// three loads per lane, all six blocks' in flight together; else one sample per load
+template <bool VEC>
+__global__ __launch_bounds__(64) void enc_drc_gain_kernel(const DrcParams Q)
+{
+    const int lane = threadIdx.x, nch = Q.nch, n = 256 * nch;
+    const size_t fidx = blockIdx.x;
+    const int16_t *fp = Q.pcm + fidx * 1536 * nch;
+    uint64_t e6[6];
+    if constexpr (VEC) {
+        const uint4 *fv = reinterpret_cast<const uint4 *>(fp);
+        const int nv = n / 8;                                   // 16-byte loads per block: 32 nch
+        uint4 v[6][3];
+#pragma unroll
+        for (int b = 0; b < 6; b++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const int j = lane + 64 * k;
+                v[b][k] = j < nv ? fv[b * nv + j] : make_uint4(0, 0, 0, 0);
+            }
+#pragma unroll
+        for (int b = 0; b < 6; b++) {
+            uint64_t e = 0;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const int j = lane + 64 * k;
+                int c = (8 * j) % nch;                          // the channel of the load's first sample
+                const uint32_t w[4] = {v[b][k].x, v[b][k].y, v[b][k].z, v[b][k].w};
+#pragma unroll
+                for (int t = 0; t < 8; t++) {
+                    const int x = (int16_t)(w[t >> 1] >> (16 * (t & 1)));
+                    if ((Q.fbw_in >> c) & 1u) e += (uint32_t)(x * x);
+                    c = c + 1 == nch ? 0 : c + 1;
+                }
+            }
+            e6[b] = e;
+        }
+    } else {
+        const int c_first = lane % nch, c_step = 64 % nch;       // the channel of sample `lane` of a block, and its step per pass
+#pragma unroll
+        for (int b = 0; b < 6; b++) {
+            const int16_t *bp = fp + (size_t)b * n;
+            uint64_t e = 0;
+            int c = c_first;
+            for (int i = lane; i < n; i += 64) {
+                const int x = bp[i];
+                if ((Q.fbw_in >> c) & 1u) e += (uint32_t)(x * x);
+                c += c_step;
+                if (c >= nch) c -= nch;
+            }
+            e6[b] = e;
+        }
+    }
+    int g_lane = 0;
+#pragma unroll
+    for (int b = 0; b < 6; b++) {
+        uint64_t e = e6[b];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) e += __shfl_xor(e, o);
+        // level (lv) relative to a full-scale sine on one channel, then to the dialogue level
+        int lev = -4096;
+        if (e) {
+            const int k = 63 - __builtin_clzll(e);
+            const int m = (int)(((e << 8) >> k) & 255u);
+            lev = max(-4096, 256 * k + (int)DRC_LG[m] - 37 * 256);
+        }
+        const int r = lev + Q.dn;
+        int g;
+        if (r < Q.n0) g = min(Q.mb, ((Q.n0 - r) * (Q.rb - 1)) / Q.rb);
+        else if (r <= Q.n1) g = 0;
+        else if (r <= Q.c0) g = -(((r - Q.n1) * (Q.re - 1)) / Q.re);
+        else g = -(((Q.c0 - Q.n1) * (Q.re - 1)) / Q.re) - (((r - Q.c0) * (Q.rc - 1)) / Q.rc);
+        g_lane = lane == b ? max(g, -1024) : g_lane;
+    }
+    if (lane < 6) Q.gain[fidx * 6 + lane] = (int16_t)g_lane;
+}
+
+__global__ __launch_bounds__(64) void enc_drc_smooth_kernel(const DrcParams Q)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= Q.n_streams) return;
+    int32_t *sp = Q.state + (Q.slot ? Q.slot[s] : s);
+    int st = *sp;
+    for (int f = 0; f < Q.frames; f++) {
+        const size_t fidx = (size_t)s * Q.frames + f;
+        int16_t g6[6];
+#pragma unroll
+        for (int b = 0; b < 6; b++) g6[b] = Q.gain[fidx * 6 + b];
+#pragma unroll
+        for (int b = 0; b < 6; b++) {
+            const long long d = (long long)g6[b] - st;          // (64 bits: a caller's state may be any int32)
+            if (d < 0) st -= (int)max(1LL, (-d * 6631) >> 16);
+            else if (d > 0) st += (int)max(1LL, (d * 349) >> 16);
+            const int v = 32 * (st >> 8) + (int)DRC_XT[st & 255];
+            Q.code[fidx * 6 + b] = (uint8_t)(v < -128 ? -128 : v > 127 ? 127 : v);
+        }
+    }
+    *sp = st;
+}
+
+static hipError_t launch_drc(const EncodeLaunch &E, hipStream_t stream)
+{
+    const EncConfig &c = E.cfg;
+    if (E.drc_profile < 1 || E.drc_profile > 5 || !E.drc_state || !E.ws_drc_gain || !E.ws_drc_code) return hipErrorInvalidValue;
+    DrcParams Q;
+    Q.pcm = E.pcm;
+    Q.gain = E.ws_drc_gain;
+    Q.code = E.ws_drc_code;
+    Q.state = E.drc_state;
+    Q.slot = E.slot;
+    Q.n_streams = E.n_streams;
+    Q.frames = E.frames_per_stream;
+    Q.nch = c.nch;
+    Q.fbw_in = 0;
+    for (int ch = 0; ch < c.nfbw; ch++) Q.fbw_in |= 1u << E.chmap[ch];
+    Q.dn = DRC_DN[E.bsi & 31u];
+    const int16_t *k = DRC_CURVE[E.drc_profile - 1];
+    Q.mb = k[0]; Q.rb = k[1]; Q.n0 = k[2]; Q.n1 = k[3]; Q.c0 = k[4]; Q.re = k[5]; Q.rc = k[6];
+    const dim3 frames((unsigned)E.n_streams * (unsigned)E.frames_per_stream);
+    if (((uintptr_t)E.pcm & 15) == 0) hipLaunchKernelGGL(enc_drc_gain_kernel<true>, frames, dim3(64), 0, stream, Q);
+    else hipLaunchKernelGGL(enc_drc_gain_kernel<false>, frames, dim3(64), 0, stream, Q);
+    hipLaunchKernelGGL(enc_drc_smooth_kernel, dim3((E.n_streams + 63) / 64), dim3(64), 0, stream, Q);
+    return hipGetLastError();
+}
+
 hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStream_t stream)
 {
     if (E.n_streams <= 0 || E.frames_per_stream <= 0) return hipSuccess;
@@ -2522,6 +2740,13 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     const bool bw = E.bw || E.chbwcod != 50;
     // the packers' member lists (enc_mant.h) hold the grouped mantissas of at most 5 x MAX_NBC + 7 coefficients a block
     if (c.nfbw * nbc + 7 > MANT_MAX_COEFS) return hipErrorInvalidValue;
+    // metadata and dynamic range control: the DRC kernels write the frames' codes first; with DRC on the search costs the words
+    // (DRC variants), with either on the packers write them (MD variants).  Both off: exactly the kernels of before
+    const bool drc = E.drc_profile != 0, md = drc || E.bsi != BSI_DEFAULT;
+    if (drc) {
+        const hipError_t ed = launch_drc(E, stream);
+        if (ed != hipSuccess) return ed;
+    }
     MdctParams M;
     M.pcm = E.pcm;
     M.last = E.last;
@@ -2650,6 +2875,8 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.cpl = cpl ? E.ws_cpl : CplWs{};
     P.cpl_begf = cpl ? E.cpl_begf : 0;
     P.cpl_endf = bw ? cpl_endf : 12;
+    P.drc = drc ? E.ws_drc_code : nullptr;
+    P.bsi = E.bsi;
 #ifndef ENC_FR_HEADROOM
 #define ENC_FR_HEADROOM 256
 #endif
@@ -2674,21 +2901,32 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.memo = long_streams && E.n_streams < 2048 ? E.ws_memo : nullptr;      // worth its cost only when the per-stream replay is the long pole
     // (the uncoupled search and enc_packb_kernel take nbc / chbwcod at run time in every mode; bw picks the variants whose coupling
     // end or 5.1 band edge is a run-time value)
-    if (P.memo) {
-        if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<3, true, true>), dim3(nfr), dim3(64), 0, stream, P);
-        else if (cpl) hipLaunchKernelGGL((enc_search_kernel<3, true>), dim3(nfr), dim3(64), 0, stream, P);
-        else hipLaunchKernelGGL(enc_search_kernel<3>, dim3(nfr), dim3(64), 0, stream, P);
-    }
-    if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<1, true, true>), dim3(E.n_streams), dim3(64), 0, stream, P);
-    else if (cpl) hipLaunchKernelGGL((enc_search_kernel<1, true>), dim3(E.n_streams), dim3(64), 0, stream, P);
-    else hipLaunchKernelGGL(enc_search_kernel<1>, dim3(E.n_streams), dim3(64), 0, stream, P);
+    // (the same chains for DRC on / off and MD on / off: D and X below are std::bool_constant tags)
+    auto searches = [&](auto D) {
+        constexpr bool DRC = decltype(D)::value;
+        if (P.memo) {
+            if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<3, true, true, DRC>), dim3(nfr), dim3(64), 0, stream, P);
+            else if (cpl) hipLaunchKernelGGL((enc_search_kernel<3, true, false, DRC>), dim3(nfr), dim3(64), 0, stream, P);
+            else hipLaunchKernelGGL((enc_search_kernel<3, false, false, DRC>), dim3(nfr), dim3(64), 0, stream, P);
+        }
+        if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<1, true, true, DRC>), dim3(E.n_streams), dim3(64), 0, stream, P);
+        else if (cpl) hipLaunchKernelGGL((enc_search_kernel<1, true, false, DRC>), dim3(E.n_streams), dim3(64), 0, stream, P);
+        else hipLaunchKernelGGL((enc_search_kernel<1, false, false, DRC>), dim3(E.n_streams), dim3(64), 0, stream, P);
+    };
     const bool fixed51 = c.nch == 6 && c.nfbw == 5 && c.lfe && c.acmod == 7;
-    if (packb) hipLaunchKernelGGL(enc_packb_kernel, dim3(nfr), dim3(384), fr_lds, stream, P);
-    else if (cpl && bw) hipLaunchKernelGGL((enc_packf_kernel<false, true, true>), dim3(nfr), dim3(64), fr_lds, stream, P);
-    else if (cpl) hipLaunchKernelGGL((enc_packf_kernel<false, true>), dim3(nfr), dim3(64), fr_lds, stream, P);
-    else if (fixed51 && bw) hipLaunchKernelGGL((enc_packf_kernel<true, false, true>), dim3(nfr), dim3(64), fr_lds, stream, P);
-    else if (fixed51 && P.nbc == 223) hipLaunchKernelGGL(enc_packf_kernel<true>, dim3(nfr), dim3(64), fr_lds, stream, P);
-    else hipLaunchKernelGGL(enc_packf_kernel<false>, dim3(nfr), dim3(64), fr_lds, stream, P);
+    auto packers = [&](auto X) {
+        constexpr bool MD = decltype(X)::value;
+        if (packb) hipLaunchKernelGGL((enc_packb_kernel<MD>), dim3(nfr), dim3(384), fr_lds, stream, P);
+        else if (cpl && bw) hipLaunchKernelGGL((enc_packf_kernel<false, true, true, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
+        else if (cpl) hipLaunchKernelGGL((enc_packf_kernel<false, true, false, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
+        else if (fixed51 && bw) hipLaunchKernelGGL((enc_packf_kernel<true, false, true, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
+        else if (fixed51 && P.nbc == 223) hipLaunchKernelGGL((enc_packf_kernel<true, false, false, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
+        else hipLaunchKernelGGL((enc_packf_kernel<false, false, false, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
+    };
+    if (drc) searches(std::true_type{});
+    else searches(std::false_type{});
+    if (md) packers(std::true_type{});
+    else packers(std::false_type{});
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     // the new history: last 256 samples per channel of each stream's final frame

@@ -283,6 +283,36 @@ class Engine:
         Applies to encode_batch and transcode_batch."""
         self._check(self.lib.ac3mi_set_encode_bandwidth(ctypes.c_void_p(self.ctx), int(mode), int(chbwcod)))
 
+    _METADATA_FIELDS = ("dialnorm", "bsmod", "cmixlev", "surmixlev", "dsurmod", "copyrightb", "origbs")
+    _METADATA_DEFAULTS = (31, 0, 1, 1, 0, 0, 1)
+
+    def set_encode_metadata(self, **fields):
+        """BSI fields of the encoded frames (ac3mi_set_encode_metadata): dialnorm 1..31, bsmod 0..7, cmixlev / surmixlev /
+        dsurmod 0..2, copyrightb / origbs 0/1; fields not given take their defaults (31, 0, 1, 1, 0, 0, 1), no fields
+        restores the defaults.  Applies to encode_batch and transcode_batch."""
+        unknown = set(fields) - set(self._METADATA_FIELDS)
+        if unknown:
+            raise TypeError("unknown metadata field(s): %s" % ", ".join(sorted(unknown)))
+        if not fields:
+            self._check(self.lib.ac3mi_set_encode_metadata(ctypes.c_void_p(self.ctx), None))
+            return
+        vals = [int(fields.get(k, d)) for k, d in zip(self._METADATA_FIELDS, self._METADATA_DEFAULTS)]
+        md = (ctypes.c_int * 7)(*vals)
+        self._check(self.lib.ac3mi_set_encode_metadata(ctypes.c_void_p(self.ctx), ctypes.cast(md, ctypes.c_void_p)))
+
+    def set_encode_drc(self, profile, state=None):
+        """Dynamic range control (ac3mi_set_encode_drc): profile 0 = no dynrng words, 1..5 = film standard / film light /
+        music standard / music light / speech; `state` int32 [S] on the device (the smoothing state, indexed like
+        csnroffst, 0 for new streams, updated in place; kept referenced while set).  Applies to encode_batch and
+        transcode_batch."""
+        if state is not None:
+            import torch
+            if state.dtype != torch.int32 or not state.is_cuda or not state.is_contiguous():
+                raise ValueError("state must be a contiguous int32 tensor on the device")
+        ptr = ctypes.c_void_p(state.data_ptr()) if state is not None else None
+        self._check(self.lib.ac3mi_set_encode_drc(ctypes.c_void_p(self.ctx), int(profile), ptr))
+        self._drc_state = state if int(profile) else None
+
     def set_mix_state(self, pending=None, flags=None):
         """liba52's overlap bookkeeping around frames with surround level 0 (ac3mi_set_mix_state): `pending` float32 shaped
         like the delay array, `flags` int32 [S][6], both zero for new streams and updated in place by the decode calls that

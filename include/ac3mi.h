@@ -266,6 +266,63 @@ int ac3mi_set_encode_coupling(ac3mi_ctx *ctx, int mode, int begf);
  * chbwcod outside 0..50: AC3MI_ERR_ARG. */
 int ac3mi_set_encode_bandwidth(ac3mi_ctx *ctx, int mode, int chbwcod);
 
+/* Bitstream information (BSI) of the encoder's frames (new; applies to every following ac3mi_encode_batch /
+ * ac3mi_transcode_batch on `ctx`, in either packer variant, with or without state slots, tiled or not, with every other
+ * encoder tool on or off).  The fields are written as given; all have fixed widths, so the bit allocation, the SNR offsets
+ * and every bit outside the BSI fields and the two CRC words are those of the defaults.  cmixlev is sent only when acmod
+ * has three front channels (acmod 3, 5, 7), surmixlev only when it has surround channels (acmod 4..7), dsurmod only for
+ * 2/0; the decoders use cmixlev / surmixlev when they downmix.  dialnorm is also the dialogue level of
+ * ac3mi_set_encode_drc.  md NULL restores the defaults (the reference's fixed BSI).  A field out of range (the reserved
+ * value 3 of cmixlev, surmixlev and dsurmod included): AC3MI_ERR_ARG, and the setting is unchanged.  The drop-in
+ * AC3_encode_* and the byte-stream layer (ac3mi_stream.h) always write the defaults. */
+typedef struct {
+    int dialnorm;    /* 1..31  (-dialnorm dBFS), default 31 */
+    int bsmod;       /* 0..7,  default 0 */
+    int cmixlev;     /* 0..2,  default 1; sent only when acmod has three front channels */
+    int surmixlev;   /* 0..2,  default 1; sent only when acmod has surround channels */
+    int dsurmod;     /* 0..2,  default 0; sent only for 2/0 */
+    int copyrightb;  /* 0/1,   default 0 */
+    int origbs;      /* 0/1,   default 1 */
+} ac3mi_encode_metadata;
+int ac3mi_set_encode_metadata(ac3mi_ctx *ctx, const ac3mi_encode_metadata *md);   /* NULL: the defaults */
+
+/* Dynamic range control in the encoder (new; applies to every following ac3mi_encode_batch / ac3mi_transcode_batch on
+ * `ctx`, in either packer variant, with or without state slots, tiled or not, with every other encoder tool on or off):
+ * profile 0 (default) sends no dynrng word (dynrnge 0 in every block, the reference's behaviour); profiles 1..5 send the
+ * words of the rule below.  d_drc_state: int32 per stream, the smoothing state s, indexed like d_csnroffst (by slot under
+ * ac3mi_set_state_slots, by stream otherwise), 0 for a new stream, updated in place by every call; ignored under profile 0.
+ * The rule (integer arithmetic throughout; a gain or level is in lv = 1/256 octave, 2^(1/256), about 0.0235 dB):
+ *   1. block level: E = the exact u64 sum of x^2 over a block's 256 new samples (pcm[256 b .. 256 b + 255] of its frame) of
+ *      every coded full-bandwidth channel (after chmap; not the LFE).  lg(E) = 256 k + LG[m], k = floor(log2 E),
+ *      m = ((E << 8) >> k) & 255, LG[m] = round(256 log2(1 + m / 256)); L = max(-4096, lg(E) - 37 * 256), -4096 for
+ *      E = 0 (a full-scale sine on one channel reads about 0);
+ *   2. r = L + DN[dialnorm], DN[d] = round(256 d / (20 log10 2)) (DN[24] = 1020, DN[31] = 1318);
+ *   3. static curve g(r), breakpoints in lv (dB converted by the same rounding); // below has a non-negative numerator:
+ *        r < N0: g = min(MB, ((N0 - r)(Rb - 1)) // Rb);  N0 <= r <= N1: g = 0;
+ *        N1 < r <= C0: g = -(((r - N1)(Re - 1)) // Re);  r > C0: g = -(((C0 - N1)(Re - 1)) // Re) - (((r - C0)(Rc - 1)) // Rc);
+ *        then g = max(g, -1024).
+ *        profile           MB   Rb   N0    N1   C0   Re  Rc
+ *        1 film standard   255  2    0     213  638  2   20
+ *        2 film light      255  2   -425   425  850  2   20
+ *        3 music standard  510  2    0     213  638  2   20
+ *        4 music light     510  2   -425   425  425  2   2
+ *        5 speech          638  5    0     213  638  2   20
+ *      (after the widely published line-mode profile table: 6 / 12 / 15 dB of boost, null bands of -5..+5 / -10..+10 dB,
+ *      2:1 early and 20:1 late cut; not claimed to be Dolby's curves);
+ *   4. smoothing, per stream, blocks in stream order: d = g - s; d < 0: s -= max(1, (-d * 6631) >> 16) (attack, about
+ *      50 ms at 48 kHz); d > 0: s += max(1, (d * 349) >> 16) (release, about 1 s).  The constants are per 256-sample block,
+ *      whatever the sample rate (at 32 kHz both time constants are 1.5 times as long).  A step never overshoots g.  s
+ *      after the last block of the call's last frame is written back;
+ *   5. code v = clamp(32 (s >> 8) + XT[s & 255], -128, 127), XT[f] = round(32 (2^(f / 256) - 1)) (0..32, 32 carries into
+ *      the next octave); the dynrng byte v & 0xff decodes (liba52) to (32 + X) 2^(Y - 5), X its low 5 bits, Y its signed
+ *      top 3;
+ *   6. block 0 sends dynrnge 1 and the code; block b > 0 only when its code differs from block b - 1's, dynrnge 0 otherwise
+ *      (liba52 keeps the gain within the frame).  compre stays 0; the words cost 8 bits a block that sends one, which the
+ *      SNR-offset search accounts for.
+ * A profile outside 0..5, or a profile other than 0 with d_drc_state NULL: AC3MI_ERR_ARG, and the setting is unchanged.
+ * The drop-in AC3_encode_* and the byte-stream layer (ac3mi_stream.h) never send dynrng. */
+int ac3mi_set_encode_drc(ac3mi_ctx *ctx, int profile, int32_t *d_drc_state);
+
 /* Workspace bound (new; results do not depend on it, except for frames flagged AC3MI_STATUS_REUSE0 at a tile boundary).  ac3mi_decode_batch, ac3mi_encode_batch and ac3mi_transcode_batch keep
  * their intermediates (coefficient planes, MDCT coefficients, exponents, PCM between decoder and encoder: 37 / 60 /
  * 102 - 139 KB per 5.1 frame) in workspaces owned by the context.  A batch of more than `frames` frames goes through in tiles
