@@ -198,6 +198,7 @@ struct EncodeLaunch {
     int32_t *drc_state = nullptr;   // its smoothing state, [S] (or by slot)
     int16_t *ws_drc_gain = nullptr; // [S][F][6] static-curve gains (drc_profile > 0)
     uint8_t *ws_drc_code = nullptr; // [S][F][6] dynrng codes for the search and the packers
+    int exp_strategy = 0;       // ac3mi_set_encode_exp_strategy: 1 = strategies by cost (the XS kernel variants), 0 = the reference's rule
 };
 // carves CPL_FRAME_BYTES * nfr bytes at `base` into the arrays of CplWs (base 16-byte aligned)
 CplWs cpl_slices(void *base, size_t nfr);
@@ -232,6 +233,7 @@ struct ac3mi_ctx {
     int bw_mode, bw_chbwcod;    // ac3mi_set_encode_bandwidth
     uint32_t enc_bsi;       // ac3mi_set_encode_metadata (ac3mi::bsi_word)
     int drc_profile;        // ac3mi_set_encode_drc
+    int exp_strategy;       // ac3mi_set_encode_exp_strategy
     int32_t *drc_state;
     void *ws_drc;           // its gains and codes between the DRC kernels, the search and the packers, 3 bytes a frame-block
     size_t ws_drc_bytes;

@@ -498,6 +498,7 @@ ac3mi_ctx *ac3mi_create(int device)
     ctx->enc_bsi = ac3mi::BSI_DEFAULT;
     ctx->drc_profile = 0;
     ctx->drc_state = nullptr;
+    ctx->exp_strategy = 0;
     ctx->ws_drc = nullptr;
     ctx->ws_drc_bytes = 0;
     ctx->ws_cpl = nullptr;
@@ -821,6 +822,13 @@ int ac3mi_set_encode_drc(ac3mi_ctx *ctx, int profile, int32_t *d_drc_state)
     if (!ctx || profile < 0 || profile > 5 || (profile != 0 && !d_drc_state)) return AC3MI_ERR_ARG;
     ctx->drc_profile = profile;
     ctx->drc_state = profile ? d_drc_state : nullptr;
+    return AC3MI_OK;
+}
+
+int ac3mi_set_encode_exp_strategy(ac3mi_ctx *ctx, int mode)
+{
+    if (!ctx || mode < 0 || mode > 1) return AC3MI_ERR_ARG;
+    ctx->exp_strategy = mode;
     return AC3MI_OK;
 }
 
@@ -1499,6 +1507,7 @@ int ac3mi_encode_batch(ac3mi_ctx *ctx, const ac3mi_encode_desc *desc, const int1
     if (taps && taps->d_encoded_exp) E.ws_eexp = taps->d_encoded_exp;      // the exponent stage writes the tap directly
     E.chbwcod = call_chbwcod(ctx, desc);
     E.bw = ctx->bw_mode != 0;
+    E.exp_strategy = ctx->exp_strategy;
     E.pcm = d_pcm;
     E.last = d_last;
     E.csnr = d_csnroffst;
@@ -1550,6 +1559,7 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     }
     E.chbwcod = call_chbwcod(ctx, enc);                 // (after enc_config: the descriptor is a valid one)
     E.bw = ctx->bw_mode != 0;
+    E.exp_strategy = ctx->exp_strategy;
     if (out_stride < ((fb + 3) & ~3) || (out_stride & 3) || ((uintptr_t)d_frames_out & 3)) {
         ctx->err = "ac3mi_transcode_batch: out_stride must be a multiple of 4 and >= the frame size";
         return AC3MI_ERR_ARG;

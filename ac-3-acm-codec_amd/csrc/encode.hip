@@ -212,6 +212,177 @@ __device__ int encode_exp_wave(uint8_t *row, int n, int strategy, int lane)
     return encode_exp_wave_t<1>(row, n, lane);
 }
 
+// encode_exp_wave_t<PER> in registers, for the cost of a candidate set (ac3mi_set_encode_exp_strategy 1): `own` is this lane's
+// dword of the row (bins 4 lane .. 4 lane + 3); returns this lane's share of the sum of the coded exponents over bins [0, n),
+// bin 0 on lane 0.  The row is not written.
+template <int PER>
+__device__ __forceinline__ int encode_exp_sum_t(uint32_t own, int n, int lane)
+{
+    constexpr int INF = 0x3fffffff;
+    constexpr int gs = PER == 4 ? 1 : PER == 2 ? 2 : 4;
+    const int ng = ((n + gs * 3 - 4) / (3 * gs)) * 3;
+    const uint32_t nxt = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)own, 0x130, 0xf, 0xf, false);      // wave_shl:1
+    const uint32_t S = __builtin_amdgcn_alignbyte(nxt, own, 1u);
+    const int b0 = (int)(S & 0xffu), b1 = (int)((S >> 8) & 0xffu), b2 = (int)((S >> 16) & 0xffu), b3 = (int)(S >> 24);
+    int row0 = (int)(__builtin_amdgcn_readfirstlane((int)own) & 0xff);
+    row0 = row0 > 15 ? 15 : row0;
+    int g[PER], ix[PER];
+    bool valid[PER];
+    if (PER == 4) { g[0] = b0; g[PER > 1 ? 1 : 0] = b1; g[PER > 2 ? 2 : 0] = b2; g[PER > 3 ? 3 : 0] = b3; }
+    else if (PER == 2) { g[0] = b1 < b0 ? b1 : b0; g[PER > 1 ? 1 : 0] = b3 < b2 ? b3 : b2; }
+    else { const int m01 = b1 < b0 ? b1 : b0, m23 = b3 < b2 ? b3 : b2; g[0] = m23 < m01 ? m23 : m01; }
+#pragma unroll
+    for (int c = 0; c < PER; c++) {
+        ix[c] = 2 * (PER * lane + 1 + c);
+        valid[c] = PER * lane + 1 + c <= ng;
+    }
+    int t[PER];
+#pragma unroll
+    for (int c = 0; c < PER; c++) {
+        const int a = valid[c] ? g[c] - ix[c] : INF;
+        t[c] = c == 0 ? a : (a < t[c > 0 ? c - 1 : 0] ? a : t[c > 0 ? c - 1 : 0]);
+    }
+    {
+        int ex = __builtin_amdgcn_update_dpp(INF, wave_incl_scan_min(t[PER - 1]), 0x138, 0xf, 0xf, false);       // wave_shr:1
+        ex = row0 < ex ? row0 : ex;
+#pragma unroll
+        for (int c = 0; c < PER; c++) g[c] = (t[c] < ex ? t[c] : ex) + ix[c];
+    }
+#pragma unroll
+    for (int c = PER - 1; c >= 0; c--) {
+        const int a = valid[c] ? g[c] + ix[c] : INF;
+        t[c] = c == PER - 1 ? a : (a < t[c < PER - 1 ? c + 1 : c] ? a : t[c < PER - 1 ? c + 1 : c]);
+    }
+    const int suf = wave_suffix_scan_min(t[0], lane);
+    {
+        const int ex = __builtin_amdgcn_update_dpp(INF, suf, 0x130, 0xf, 0xf, false);                       // wave_shl:1
+#pragma unroll
+        for (int c = 0; c < PER; c++) g[c] = (t[c] < ex ? t[c] : ex) - ix[c];
+    }
+    const int head = __builtin_amdgcn_readfirstlane(suf);
+    int sum = lane == 0 ? (head < row0 ? head : row0) : 0;
+#pragma unroll
+    for (int c = 0; c < PER; c++) {
+        int cnt = n - (4 * lane + 1 + c * gs);                  // bins of entry c below n
+        cnt = cnt < 0 ? 0 : cnt > gs ? gs : cnt;
+        sum += valid[c] ? g[c] * cnt : 0;
+    }
+    return sum;
+}
+
+// cpl_encode_exp's coded exponents summed over [cs, ce) (this lane's share), the row in LDS left as it is
+__device__ __forceinline__ int cpl_exp_sum(const uint8_t *row, int cs, int ce, int strategy, int lane)
+{
+    constexpr int INF = 0x3fffffff;
+    const int gs = strategy == 1 ? 1 : strategy == 2 ? 2 : 4, ne = (ce - cs) / gs;
+    int g[3], t[3], ix[3];
+    bool valid[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const int i = 3 * lane + c;
+        ix[c] = 2 * i;
+        valid[c] = i < ne;
+        int m = INF;
+        if (valid[c])
+            for (int k = 0; k < gs; k++) { const int e = row[cs + i * gs + k]; m = e < m ? e : m; }
+        g[c] = m;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const int a = valid[c] ? g[c] - ix[c] : INF;
+        t[c] = c == 0 ? a : (a < t[c > 0 ? c - 1 : 0] ? a : t[c > 0 ? c - 1 : 0]);
+    }
+    {
+        const int ex = __builtin_amdgcn_update_dpp(INF, wave_incl_scan_min(t[2]), 0x138, 0xf, 0xf, false);     // wave_shr:1
+#pragma unroll
+        for (int c = 0; c < 3; c++) g[c] = (t[c] < ex ? t[c] : ex) + ix[c];
+    }
+#pragma unroll
+    for (int c = 2; c >= 0; c--) {
+        const int a = valid[c] ? g[c] + ix[c] : INF;
+        t[c] = c == 2 ? a : (a < t[c < 2 ? c + 1 : c] ? a : t[c < 2 ? c + 1 : c]);
+    }
+    const int suf = wave_suffix_scan_min(t[0], lane);
+    const int ex = __builtin_amdgcn_update_dpp(INF, suf, 0x130, 0xf, 0xf, false);                             // wave_shl:1
+    int sum = 0;
+#pragma unroll
+    for (int c = 0; c < 3; c++) sum += valid[c] ? ((t[c] < ex ? t[c] : ex) - ix[c]) * gs : 0;
+    return sum;
+}
+
+// Exponent strategies by cost (ac3mi_set_encode_exp_strategy 1; the rule is include/ac3mi.h's).  E[b]: block b's raw row in
+// LDS; `in`: this lane's byte mask of the coded range - [0, n) of a channel, [cs, ce) of the coupling row (CPLROW: the
+// candidate's merged row goes through `scratch`, a 256-byte LDS row, since the coupling groups straddle lanes); `extra`: the
+// set's bits besides absexp and the groups (gainrng 2 + chbwcod 6, gainrng 2 in a coupled frame, 0 for the LFE and the
+// coupling row); `d15`: D15 only (the LFE).  A candidate (i, L, s) costs bits(s) + sum over its blocks and the range of
+// (raw - coded) = bits(s) + sum_b R_b - L sum c: per lane the raw sum (v_sad_u8) and the three strategies' coded sums, two
+// sums per wave reduction (each is below 2^16).  J(i) = min over L, s of cost(i, L, s) + J(i + L), wave-uniform; the loops stay
+// rolled (one copy of the three encode_exp sums) and J, the choices live in scalars.  Returns block b's strategy in bits
+// 4b .. 4b + 3 (0: reuse).
+template <bool CPLROW>
+__device__ uint32_t xs_choose(const uint8_t (*E)[256], uint8_t *scratch, uint32_t in, int n, int cs, int ce, int extra,
+                              bool d15, int lane)
+{
+    int bits[3];
+#pragma unroll
+    for (int s = 0; s < 3; s++) {
+        const int gs = 1 << s;
+        const int groups = CPLROW ? (ce - cs) / gs / 3 : (n + gs * 3 - 4) / (3 * gs);
+        bits[s] = 4 + 7 * groups + extra;
+    }
+    int J1 = 0, J2 = 0, J3 = 0, J4 = 0, J5 = 0, J6 = 0;         // J(1) .. J(6) (J(6) = 0)
+    uint32_t choice = 0;                                        // per block i: L | s << 3, 5 bits each
+#pragma unroll 1
+    for (int i = 5; i >= 0; i--) {
+        uint32_t acc = *reinterpret_cast<const uint32_t *>(&E[i][4 * lane]);
+        uint32_t racc = 0;
+        int best = 0x7fffffff, bl = 1, bs = 1;
+#pragma unroll 1
+        for (int L = 1; L <= 6 - i; L++) {
+            const uint32_t rb = *reinterpret_cast<const uint32_t *>(&E[i + L - 1][4 * lane]);
+            if (L > 1) acc = bytes_min_where(acc, rb, in);
+            racc = __builtin_amdgcn_sad_u8(rb & in, 0u, racc);
+            int c15, c25 = 0, c45 = 0;
+            if constexpr (CPLROW) {
+                *reinterpret_cast<uint32_t *>(&scratch[4 * lane]) = acc;
+                WAVE_SYNC();
+                c15 = cpl_exp_sum(scratch, cs, ce, 1, lane);
+                c25 = cpl_exp_sum(scratch, cs, ce, 2, lane);
+                c45 = cpl_exp_sum(scratch, cs, ce, 3, lane);
+                WAVE_SYNC();
+            } else {
+                c15 = encode_exp_sum_t<4>(acc, n, lane);
+                if (!d15) {
+                    c25 = encode_exp_sum_t<2>(acc, n, lane);
+                    c45 = encode_exp_sum_t<1>(acc, n, lane);
+                }
+            }
+            const uint32_t a = wave_sum_u32((uint32_t)c15 | (uint32_t)c25 << 16);
+            const uint32_t b = wave_sum_u32((uint32_t)c45 | racc << 16);
+            const int R = (int)(b >> 16);
+            const int k = i + L;
+            const int Jn = k == 1 ? J1 : k == 2 ? J2 : k == 3 ? J3 : k == 4 ? J4 : k == 5 ? J5 : J6;
+            const int C[3] = {(int)(a & 0xffffu), (int)(a >> 16), (int)(b & 0xffffu)};
+#pragma unroll
+            for (int s = 0; s < 3; s++) {
+                if (s > 0 && d15) break;
+                const int cost = bits[s] + R - L * C[s] + Jn;
+                if (cost < best) { best = cost; bl = L; bs = s + 1; }
+            }
+        }
+        J1 = i == 1 ? best : J1; J2 = i == 2 ? best : J2; J3 = i == 3 ? best : J3;
+        J4 = i == 4 ? best : J4; J5 = i == 5 ? best : J5;
+        choice |= (uint32_t)(bl | bs << 3) << (5 * i);
+    }
+    uint32_t st = 0;
+    for (int i = 0; i < 6;) {
+        const int c = (int)((choice >> (5 * i)) & 31u);
+        st |= (uint32_t)(c >> 3) << (4 * i);
+        i += c & 7;
+    }
+    return st;
+}
+
 // Masking curve of one row, one lane per band (:220-367).  bndpsd[] must hold the band PSDs.
 //  * lowcomp is a reset-or-decrement automaton: value = max(0, R(last reset) - 64 * decrements since)
 //  * the fast / slow leaks are prefix maxima of psd - gain + band * decay, seeded at band begin-1
@@ -273,7 +444,9 @@ struct ExpLDS {
 // Runs at the end of enc_mdct_kernel: L.t holds the tables, L.E the six blocks' raw exponents of this channel.
 // KEEP (enc_cpl_kernel, a coupled channel): the strategies are the ones P.strat already holds (mode 0's, from all 256 bins),
 // the rest is recomputed for the P.nbc = cplstrtmant bins the channel codes.
-template <bool KEEP = false>
+// XS (ac3mi_set_encode_exp_strategy 1): the strategies are xs_choose's over the coded bins [0, n); 1: a set also sends
+// gainrng and chbwcod (enc_mdct_kernel), 2: gainrng only (a coupled channel, enc_cpl_kernel).
+template <bool KEEP = false, int XS = 0>
 __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, int lane)
 {
     const int nch = P.nch;
@@ -290,6 +463,13 @@ __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, in
     if constexpr (KEEP) {
 #pragma unroll
         for (int b = 0; b < 6; b++) st[b] = (int)P.strat[(fidx * 6 + b) * nch + ch];
+    } else if constexpr (XS != 0) {
+        uint32_t below = 0;
+#pragma unroll
+        for (int c = 0; c < 4; c++) below |= (4 * lane + c < n ? 0xffu : 0u) << (8 * c);
+        const uint32_t x = xs_choose<false>(L.E, nullptr, below, n, 0, 0, is_lfe ? 0 : XS == 1 ? 8 : 2, is_lfe, lane);
+#pragma unroll
+        for (int b = 0; b < 6; b++) st[b] = (int)((x >> (4 * b)) & 15u);
     } else {
         const uint32_t d1 = __builtin_amdgcn_sad_u8(raw[1], raw[0], 0u), d2 = __builtin_amdgcn_sad_u8(raw[2], raw[1], 0u);
         const uint32_t d3 = __builtin_amdgcn_sad_u8(raw[3], raw[2], 0u), d4 = __builtin_amdgcn_sad_u8(raw[4], raw[3], 0u);
@@ -302,7 +482,7 @@ __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, in
     uint32_t starts = 0;                                        // bit b: block b sends exponents (wave-uniform)
 #pragma unroll
     for (int b = 0; b < 6; b++) starts |= (st[b] != 0 ? 1u : 0u) << b;
-    if (!KEEP && !is_lfe) {
+    if (!KEEP && XS == 0 && !is_lfe) {
 #pragma unroll
         for (int b = 0; b < 6; b++) {
             if (st[b] == 0) continue;
@@ -504,7 +684,8 @@ __device__ __forceinline__ void bfly(c16 &p, c16 &q, int bx, int by, int ax, int
 #endif
 // BW (ac3mi_set_encode_bandwidth 1 or 2, with REMAT only - the other variants take P.x.nbc at run time already): the fourth
 // rematrixing band ends at nbc = 73 + 3 chbwcod instead of 223.  nbc can split a lane's four bins only inside that band.
-template <bool BSW, bool REMAT, bool BW = false>
+// XS (ac3mi_set_encode_exp_strategy 1): the exponent stage chooses the strategies by cost (exp_stage<false, 1>).
+template <bool BSW, bool REMAT, bool BW = false, bool XS = false>
 __global__ __launch_bounds__(REMAT ? 128 : 64, REMAT ? (BSW ? ENC_MDCT_BSW_REMAT_LB : ENC_MDCT_REMAT_LB) : BSW ? ENC_MDCT_BSW_LB : ENC_MDCT_LB)
 void enc_mdct_kernel(const MdctParams P)
 {
@@ -862,7 +1043,7 @@ void enc_mdct_kernel(const MdctParams P)
         for (int k = 0; k < 4; k++) newv[k] = nxtv[k];
         WAVE_SYNC();
     }
-    exp_stage(P.x, XL, (size_t)sf, ch, lane);
+    exp_stage<false, XS ? 1 : 0>(P.x, XL, (size_t)sf, ch, lane);
 }
 
 
@@ -1009,8 +1190,10 @@ __device__ void cpl_mask_wave(const MaskTabs &T, const uint8_t *row, int16_t *ma
     if (b < 50) mask[b] = live ? (int16_t)(excite > h ? excite : h) : (int16_t)0;
 }
 
-// BW (ac3mi_set_encode_bandwidth 1 or 2): the coupling range ends at cplendmant = 73 + 12 P.endf, 3 + endf - begf bands
-template <bool BW = false>
+// BW (ac3mi_set_encode_bandwidth 1 or 2): the coupling range ends at cplendmant = 73 + 12 P.endf, 3 + endf - begf bands.
+// XS (ac3mi_set_encode_exp_strategy 1): xs_choose picks the coupling row's strategies (its candidate rows through L.E1[0],
+// free until the rematrixing part) and the coupled channels' over [0, cplstrtmant) (exp_stage<false, 2>).
+template <bool BW = false, bool XS = false>
 __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
 {
     __shared__ CplLDS L;
@@ -1131,7 +1314,14 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
         for (int b = 0; b < 6; b++) raw[b] = *reinterpret_cast<const uint32_t *>(&X.E[b][4 * lane]);
         int st[6];
         st[0] = 1;
-        {
+        if constexpr (XS) {
+            uint32_t in = 0;
+#pragma unroll
+            for (int c = 0; c < 4; c++) in |= (4 * lane + c >= cs && 4 * lane + c < ce ? 0xffu : 0u) << (8 * c);
+            const uint32_t x = xs_choose<true>(X.E, L.E1[0], in, 0, cs, ce, 0, false, lane);
+#pragma unroll
+            for (int b = 0; b < 6; b++) st[b] = (int)((x >> (4 * b)) & 15u);
+        } else {
             const uint32_t d1 = __builtin_amdgcn_sad_u8(raw[1], raw[0], 0u), d2 = __builtin_amdgcn_sad_u8(raw[2], raw[1], 0u);
             const uint32_t d3 = __builtin_amdgcn_sad_u8(raw[3], raw[2], 0u), d4 = __builtin_amdgcn_sad_u8(raw[4], raw[3], 0u);
             const uint32_t d5 = __builtin_amdgcn_sad_u8(raw[5], raw[4], 0u);
@@ -1145,7 +1335,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
         for (int b = 0; b < 6; b++) starts |= (st[b] != 0 ? 1u : 0u) << b;
 #pragma unroll
         for (int b = 0; b < 6; b++) {
-            if (st[b] == 0) continue;
+            if (XS || st[b] == 0) continue;
             int run = 1;
 #pragma unroll
             for (int e = 1; e < 6; e++) if (b + e < 6 && run == e && st[b + e] == 0) run = e + 1;
@@ -1260,12 +1450,12 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
             prev = flags;
         }
         WAVE_SYNC();
-        exp_stage(P.x, X, fidx, 0, lane);
+        exp_stage<false, XS ? 2 : 0>(P.x, X, fidx, 0, lane);
         WAVE_SYNC();
 #pragma unroll
         for (int b = 0; b < 6; b++) *reinterpret_cast<uint32_t *>(&X.E[b][4 * lane]) = *reinterpret_cast<const uint32_t *>(&L.E1[b][4 * lane]);
         WAVE_SYNC();
-        exp_stage(P.x, X, fidx, 1, lane);
+        exp_stage<false, XS ? 2 : 0>(P.x, X, fidx, 1, lane);
         return;
     }
 
@@ -1286,7 +1476,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
             *reinterpret_cast<uint32_t *>(&X.E[b][4 * lane]) = epack;
         }
         WAVE_SYNC();
-        exp_stage<true>(P.x, X, fidx, ch, lane);
+        exp_stage<!XS, XS ? 2 : 0>(P.x, X, fidx, ch, lane);
         WAVE_SYNC();
     }
 }
@@ -2794,7 +2984,16 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
         const hipError_t e0 = hipGetLastError();
         if (e0 != hipSuccess) return e0;
     }
-    if (M.remat && M.bsw && bw) hipLaunchKernelGGL((enc_mdct_kernel<true, true, true>), frames, dim3(128), 0, stream, M);
+    // (the pre-pass above keeps mode 0's strategy rule: of its exponent stage only the rows and exp_samples are read)
+    if (E.exp_strategy) {
+        if (M.remat && M.bsw && bw) hipLaunchKernelGGL((enc_mdct_kernel<true, true, true, true>), frames, dim3(128), 0, stream, M);
+        else if (M.remat && bw) hipLaunchKernelGGL((enc_mdct_kernel<false, true, true, true>), frames, dim3(128), 0, stream, M);
+        else if (M.remat && M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, true, false, true>), frames, dim3(128), 0, stream, M);
+        else if (M.remat) hipLaunchKernelGGL((enc_mdct_kernel<false, true, false, true>), frames, dim3(128), 0, stream, M);
+        else if (M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, false, false, true>), units, dim3(64), 0, stream, M);
+        else hipLaunchKernelGGL((enc_mdct_kernel<false, false, false, true>), units, dim3(64), 0, stream, M);
+    }
+    else if (M.remat && M.bsw && bw) hipLaunchKernelGGL((enc_mdct_kernel<true, true, true>), frames, dim3(128), 0, stream, M);
     else if (M.remat && bw) hipLaunchKernelGGL((enc_mdct_kernel<false, true, true>), frames, dim3(128), 0, stream, M);
     else if (M.remat && M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, true>), frames, dim3(128), 0, stream, M);
     else if (M.remat) hipLaunchKernelGGL((enc_mdct_kernel<false, true>), frames, dim3(128), 0, stream, M);
@@ -2819,7 +3018,9 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
         C.nfr = E.n_streams * E.frames_per_stream;
         C.endf = bw ? cpl_endf : 12;
         C.nbc = nbc;
-        if (bw) hipLaunchKernelGGL(enc_cpl_kernel<true>, dim3(C.nfr), dim3(64), 0, stream, C);
+        if (E.exp_strategy && bw) hipLaunchKernelGGL((enc_cpl_kernel<true, true>), dim3(C.nfr), dim3(64), 0, stream, C);
+        else if (E.exp_strategy) hipLaunchKernelGGL((enc_cpl_kernel<false, true>), dim3(C.nfr), dim3(64), 0, stream, C);
+        else if (bw) hipLaunchKernelGGL(enc_cpl_kernel<true>, dim3(C.nfr), dim3(64), 0, stream, C);
         else hipLaunchKernelGGL(enc_cpl_kernel<false>, dim3(C.nfr), dim3(64), 0, stream, C);
         e = hipGetLastError();
         if (e != hipSuccess) return e;

@@ -313,6 +313,12 @@ class Engine:
         self._check(self.lib.ac3mi_set_encode_drc(ctypes.c_void_p(self.ctx), int(profile), ptr))
         self._drc_state = state if int(profile) else None
 
+    def set_encode_exp_strategy(self, mode):
+        """Exponent strategies (ac3mi_set_encode_exp_strategy): 0 = the reference's rule, 1 = the partition of each frame's
+        six blocks into exponent sets that costs the fewest bits under the header's model.  Applies to encode_batch and
+        transcode_batch."""
+        self._check(self.lib.ac3mi_set_encode_exp_strategy(ctypes.c_void_p(self.ctx), int(mode)))
+
     def set_mix_state(self, pending=None, flags=None):
         """liba52's overlap bookkeeping around frames with surround level 0 (ac3mi_set_mix_state): `pending` float32 shaped
         like the delay array, `flags` int32 [S][6], both zero for new streams and updated in place by the decode calls that

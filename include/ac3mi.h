@@ -266,6 +266,29 @@ int ac3mi_set_encode_coupling(ac3mi_ctx *ctx, int mode, int begf);
  * chbwcod outside 0..50: AC3MI_ERR_ARG. */
 int ac3mi_set_encode_bandwidth(ac3mi_ctx *ctx, int mode, int chbwcod);
 
+/* Exponent strategies in the encoder (new; applies to every following ac3mi_encode_batch / ac3mi_transcode_batch on `ctx`,
+ * in either packer variant, with or without state slots, tiled or not, with every other encoder tool on or off):
+ *   0  (default) the reference's rule: a block sends new exponents when the sum of |differences| of its 256 raw exponents
+ *      against the previous block's is above 1000; a run of 1 block is D45, 2-3 D25, 4 or more D15.
+ *   1  strategies by cost, per frame and per coded exponent row, independently (integer arithmetic):
+ *      row                                 range [lo, hi)             strategies      bits(s), besides the strategy field
+ *      full-bandwidth channel, uncoupled   [0, nbc)                   D15, D25, D45   4 + 7 groups + 2 gainrng + 6 chbwcod
+ *      full-bandwidth channel, coupled     [0, cplstrtmant)           D15, D25, D45   4 + 7 groups + 2 gainrng
+ *      LFE                                 [0, 7)                     D15             4 + 7 x 2 = 18
+ *      coupling channel                    [cplstrtmant, cplendmant)  D15, D25, D45   4 cplabsexp + 7 groups
+ *      r_b[k]: block b's raw exponents (after rematrixing where it applies; from the short-transform pair in a switched block).
+ *      A candidate set (i, L, s) covers blocks i .. i + L - 1 with strategy s; its coded exponents c[k] are the ones the
+ *      frame would carry: the minimum of r_b[k] over the run on the row's range, then the reference's encode_exp for s over
+ *      that range (the coupling channel's: groups from cplstrtmant, the +-2 constraint), so c[k] <= r_b[k].
+ *      cost(i, L, s) = bits(s) + sum over b = i .. i + L - 1 and k in [lo, hi) of (r_b[k] - c[k])  (one exponent step below
+ *      the raw one is modelled as one bit of the bin's mantissa precision).  J(6) = 0; for i = 5 down to 0, J(i) = the
+ *      minimum of cost(i, L, s) + J(i + L), tried in the order L = 1 .. 6 - i and, within L, D15, D25, D45, the first
+ *      minimum kept.  From block 0 on: block i gets s, blocks i + 1 .. i + L - 1 reuse (0), the walk goes on at i + L.
+ *      Everything after the choice (min-merge, encode_exp, masking, bit allocation, the SNR-offset search) is unchanged.
+ * The drop-in AC3_encode_* and the byte-stream layer (ac3mi_stream.h) always use the reference's rule.  Any other mode:
+ * AC3MI_ERR_ARG, and the setting is unchanged. */
+int ac3mi_set_encode_exp_strategy(ac3mi_ctx *ctx, int mode);
+
 /* Bitstream information (BSI) of the encoder's frames (new; applies to every following ac3mi_encode_batch /
  * ac3mi_transcode_batch on `ctx`, in either packer variant, with or without state slots, tiled or not, with every other
  * encoder tool on or off).  The fields are written as given; all have fixed widths, so the bit allocation, the SNR offsets
