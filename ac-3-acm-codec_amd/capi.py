@@ -97,6 +97,7 @@ def load_library():
     lib.ac3mi_set_encode_metadata.argtypes = [c_void_p, c_void_p]
     lib.ac3mi_set_encode_drc.argtypes = [c_void_p, c_int, c_void_p]
     lib.ac3mi_set_encode_exp_strategy.argtypes = [c_void_p, c_int]
+    lib.ac3mi_set_encode_layout.argtypes = [c_void_p, c_int, c_int, c_int]
     lib.ac3mi_memcpy_d2d.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t]
     lib.ac3mi_sync.argtypes = [c_void_p]
     lib.ac3mi_timer_start.argtypes = [c_void_p]

@@ -150,9 +150,17 @@ struct CplWs {
     int16_t *pemask;            // [F][6][2][50]
     uint8_t *pstrat;            // [F][6][2]
     int32_t *pebits;            // [F][2]
+    // (2/0+LFE: every p* array has three rows per block instead of two, the LFE's last - [F][6][3][256] etc.)
 };
 constexpr int CPL_FRAME_BYTES = 16 + 80 + 6 * 256 * 4 + 8 + 6 * 256 + 6 * 50 * 2 + 8 + 8;
-constexpr int CPL_REMAT_FRAME_BYTES = 6 * 2 * 256 * 4 + 16 + 6 * 2 * 256 + 6 * 2 * 50 * 2 + 16 + 16;
+// the p* arrays of one frame with `nrow` rows a block (2: 2/0, 3: 2/0+LFE), each array's frames rounded up to 16 bytes
+constexpr int cpl_remat_frame_bytes(int nrow)
+{
+    return 6 * nrow * 256 * 4 + ((6 * nrow + 15) & ~15) + 6 * nrow * 256 + 6 * nrow * 50 * 2 + ((6 * nrow + 15) & ~15) +
+           ((4 * nrow + 15) & ~15);
+}
+constexpr int CPL_REMAT_FRAME_BYTES = cpl_remat_frame_bytes(2);
+static_assert(CPL_REMAT_FRAME_BYTES == 6 * 2 * 256 * 4 + 16 + 6 * 2 * 256 + 6 * 2 * 50 * 2 + 16 + 16, "2/0 layout");
 
 // the encoder's BSI fields (ac3mi_set_encode_metadata) in one word: dialnorm bits 0-4, bsmod 5-7, cmixlev 8-9, surmixlev
 // 10-11, dsurmod 12-13, copyrightb 14, origbs 15
@@ -202,12 +210,15 @@ struct EncodeLaunch {
 };
 // carves CPL_FRAME_BYTES * nfr bytes at `base` into the arrays of CplWs (base 16-byte aligned)
 CplWs cpl_slices(void *base, size_t nfr);
-// carves CPL_REMAT_FRAME_BYTES * nfr bytes at `base` into the p* arrays of `w`
-void cpl_remat_slices(CplWs &w, void *base, size_t nfr);
+// carves cpl_remat_frame_bytes(nrow) * nfr bytes at `base` into the p* arrays of `w`
+void cpl_remat_slices(CplWs &w, void *base, size_t nfr, int nrow = 2);
 hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStream_t stream);
 hipError_t launch_enc_history(const EncodeLaunch &E, hipStream_t stream);
 void build_enc_tables(EncTables *t);
-int enc_config(int freq, int bitrate, int channels, EncConfig *c);   // 0 = rejected (AC3_encode_init returns 0)
+// 0 = rejected (AC3_encode_init returns 0).  acmod < 0: the reference's layout for the channel count ({1, 2, 3, 6, 7, 7},
+// LFE with six channels); else acmod 0..7 with lfeon 0/1 (ac3mi_set_encode_layout 1), rejected unless channels is
+// nfchans(acmod) + lfeon
+int enc_config(int freq, int bitrate, int channels, EncConfig *c, int acmod = -1, int lfeon = 0);
 
 hipError_t launch_convert_s16(const float *planes, int16_t *out, int flags, size_t n_blocks, hipStream_t stream);
 int s16_channel_map(int flags, int map[6]);
@@ -234,6 +245,7 @@ struct ac3mi_ctx {
     uint32_t enc_bsi;       // ac3mi_set_encode_metadata (ac3mi::bsi_word)
     int drc_profile;        // ac3mi_set_encode_drc
     int exp_strategy;       // ac3mi_set_encode_exp_strategy
+    int layout_mode, layout_acmod, layout_lfeon;    // ac3mi_set_encode_layout
     int32_t *drc_state;
     void *ws_drc;           // its gains and codes between the DRC kernels, the search and the packers, 3 bytes a frame-block
     size_t ws_drc_bytes;

@@ -198,15 +198,22 @@ void build_enc_tables(EncTables *t)
     }
 }
 
-int enc_config(int freq, int bitrate, int channels, EncConfig *c)
+int enc_config(int freq, int bitrate, int channels, EncConfig *c, int acmod, int lfeon)
 {
     static const uint8_t acmod_of[6] = {1, 2, 3, 6, 7, 7};
     const int *rates = kSampleRates, *kbps = kKbps;
     if (channels < 1 || channels > 6) return 0;
     c->nch = channels;
-    c->acmod = acmod_of[channels - 1];
-    c->lfe = channels == 6;
-    c->nfbw = channels > 5 ? 5 : channels;
+    if (acmod < 0) {
+        c->acmod = acmod_of[channels - 1];
+        c->lfe = channels == 6;
+        c->nfbw = channels > 5 ? 5 : channels;
+    } else {
+        if (acmod > 7 || lfeon < 0 || lfeon > 1 || channels != kNfchans[acmod] + lfeon) return 0;
+        c->acmod = acmod;
+        c->lfe = lfeon;
+        c->nfbw = kNfchans[acmod];
+    }
     bool found = false;
     for (int i = 0; i < 3 && !found; i++)
         for (int j = 0; j < 3; j++)
@@ -499,6 +506,9 @@ ac3mi_ctx *ac3mi_create(int device)
     ctx->drc_profile = 0;
     ctx->drc_state = nullptr;
     ctx->exp_strategy = 0;
+    ctx->layout_mode = 0;
+    ctx->layout_acmod = 0;
+    ctx->layout_lfeon = 0;
     ctx->ws_drc = nullptr;
     ctx->ws_drc_bytes = 0;
     ctx->ws_cpl = nullptr;
@@ -785,12 +795,11 @@ int ac3mi_set_encode_bandwidth(ac3mi_ctx *ctx, int mode, int chbwcod)
 }
 
 // the chbwcod a call codes with (ac3mi_set_encode_bandwidth's rule, include/ac3mi.h); callers pass a descriptor enc_config
-// accepted (a channel count outside 1..6 gets 50 here rather than a division by zero)
-static int call_chbwcod(const ac3mi_ctx *ctx, const ac3mi_encode_desc *d)
+// accepted and the layout's number of full-bandwidth channels (a count outside 1..5 gets 50 here rather than a division by zero)
+static int call_chbwcod(const ac3mi_ctx *ctx, const ac3mi_encode_desc *d, int nfbw)
 {
     if (ctx->bw_mode == 1) return ctx->bw_chbwcod;
-    if (ctx->bw_mode != 2 || d->channels < 1 || d->channels > 6) return 50;
-    const int nfbw = d->channels > 5 ? 5 : d->channels;
+    if (ctx->bw_mode != 2 || nfbw < 1 || nfbw > 5) return 50;
     const long long r = d->bit_rate / nfbw;
     if (r >= 96000) return 50;
     const long long fc = r >= 80000 ? 18000 : r >= 64000 ? 16000 : r >= 48000 ? 14000 : r >= 32000 ? 11000 : 8000;
@@ -830,6 +839,30 @@ int ac3mi_set_encode_exp_strategy(ac3mi_ctx *ctx, int mode)
     if (!ctx || mode < 0 || mode > 1) return AC3MI_ERR_ARG;
     ctx->exp_strategy = mode;
     return AC3MI_OK;
+}
+
+int ac3mi_set_encode_layout(ac3mi_ctx *ctx, int mode, int acmod, int lfeon)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (mode < 0 || mode > 2 || (mode == 1 && (acmod < 0 || acmod > 7 || lfeon < 0 || lfeon > 1))) {
+        ctx->err = "ac3mi_set_encode_layout: mode outside 0..2, or a mode-1 acmod / lfeon out of range";
+        return AC3MI_ERR_ARG;
+    }
+    ctx->layout_mode = mode;
+    ctx->layout_acmod = mode == 1 ? acmod : 0;
+    ctx->layout_lfeon = mode == 1 ? lfeon : 0;
+    return AC3MI_OK;
+}
+
+// the layout an encode call codes (ac3mi_set_encode_layout): mode 1's, or -1 for the reference's table (mode 0; mode 2 on
+// ac3mi_encode_batch, which has no source)
+static int call_acmod(const ac3mi_ctx *ctx) { return ctx->layout_mode == 1 ? ctx->layout_acmod : -1; }
+
+// mode 2 on a transcode: the coded layout of the decoder's granted output flags (CHANNEL1 / CHANNEL2: 1/0, DOLBY: 2/0)
+static int granted_acmod(int out_flags)
+{
+    const int cfg = out_flags & AC3MI_CHANNEL_MASK;
+    return cfg <= 7 ? cfg : cfg == AC3MI_DOLBY ? 2 : 1;
 }
 
 int ac3mi_set_tile_frames(ac3mi_ctx *ctx, long long frames)
@@ -959,9 +992,9 @@ static int ensure_cpl(ac3mi_ctx *ctx, size_t nfr)
 }
 
 // with rematrixing on as well (2/0): the rows before rematrixing of `nfr` frames
-static int ensure_cplr(ac3mi_ctx *ctx, size_t nfr)
+static int ensure_cplr(ac3mi_ctx *ctx, size_t nfr, int nrow)
 {
-    const size_t need = nfr * ac3mi::CPL_REMAT_FRAME_BYTES + 256;
+    const size_t need = nfr * ac3mi::cpl_remat_frame_bytes(nrow) + 256;
     if (need <= ctx->ws_cplr_bytes) return AC3MI_OK;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     (void)hipFree(ctx->ws_cplr);
@@ -973,14 +1006,14 @@ static int ensure_cplr(ac3mi_ctx *ctx, size_t nfr)
 }
 
 // the coupling arrays of frames f0.. of a workspace carved for nfr frames
-static ac3mi::CplWs cpl_at(const ac3mi::CplWs &w, size_t f0)
+static ac3mi::CplWs cpl_at(const ac3mi::CplWs &w, size_t f0, int nrow)
 {
     ac3mi::CplWs r = w;
     r.word += f0; r.co += 80 * f0; r.mdct += 6 * 256 * f0; r.shift += 8 * f0;
     r.eexp += 6 * 256 * f0; r.emask += 6 * 50 * f0; r.strat += 8 * f0; r.ebits += f0;
     if (r.prow) {
-        r.prow += 6 * 2 * 256 * f0; r.pshift += 12 * f0; r.peexp += 6 * 2 * 256 * f0; r.pemask += 6 * 2 * 50 * f0;
-        r.pstrat += 12 * f0; r.pebits += 2 * f0;
+        r.prow += 6 * nrow * 256 * f0; r.pshift += 6 * nrow * f0; r.peexp += 6 * nrow * 256 * f0; r.pemask += 6 * nrow * 50 * f0;
+        r.pstrat += 6 * nrow * f0; r.pebits += nrow * f0;
     }
     return r;
 }
@@ -1421,9 +1454,11 @@ int ac3mi_encode_batch(ac3mi_ctx *ctx, const ac3mi_encode_desc *desc, const int1
         ctx->err = "ac3mi_encode_batch: bad argument";
         return AC3MI_ERR_ARG;
     }
-    const int fb = enc_config(desc->sample_rate, desc->bit_rate, desc->channels, &E.cfg);
+    const int fb = enc_config(desc->sample_rate, desc->bit_rate, desc->channels, &E.cfg, call_acmod(ctx), ctx->layout_lfeon);
     if (fb <= 0) {
-        ctx->err = "ac3mi_encode_batch: AC3_encode_init would return 0 for this rate/bitrate/channels";
+        ctx->err = ctx->layout_mode == 1 && ac3mi_encode_frame_bytes(desc) > 0
+                       ? "ac3mi_encode_batch: channels is not nfchans(acmod) + lfeon of the layout set by ac3mi_set_encode_layout"
+                       : "ac3mi_encode_batch: AC3_encode_init would return 0 for this rate/bitrate/channels";
         return AC3MI_ERR_ARG;
     }
     if (frame_stride < ((fb + 3) & ~3) || (frame_stride & 3) || ((uintptr_t)d_frames & 3) || ((uintptr_t)d_pcm & 1)) {
@@ -1481,10 +1516,10 @@ int ac3mi_encode_batch(ac3mi_ctx *ctx, const ac3mi_encode_desc *desc, const int1
         if (r != AC3MI_OK) return r;
         E.cpl_begf = ctx->cpl_begf;
         E.ws_cpl = ac3mi::cpl_slices(ctx->ws_cpl, (size_t)n_streams * frames_per_stream);
-        if (ctx->rematrix && E.cfg.acmod == 2 && E.cfg.nch == 2) {
-            const int r2 = ensure_cplr(ctx, (size_t)n_streams * frames_per_stream);
+        if (ctx->rematrix && E.cfg.acmod == 2) {
+            const int r2 = ensure_cplr(ctx, (size_t)n_streams * frames_per_stream, E.cfg.nch);
             if (r2 != AC3MI_OK) return r2;
-            ac3mi::cpl_remat_slices(E.ws_cpl, ctx->ws_cplr, (size_t)n_streams * frames_per_stream);
+            ac3mi::cpl_remat_slices(E.ws_cpl, ctx->ws_cplr, (size_t)n_streams * frames_per_stream, E.cfg.nch);
         }
     }
     if (ctx->drc_profile) {
@@ -1505,7 +1540,7 @@ int ac3mi_encode_batch(ac3mi_ctx *ctx, const ac3mi_encode_desc *desc, const int1
     if (taps && taps->d_exponent) E.ws_expo = taps->d_exponent;
     if (taps && taps->d_exp_samples) E.ws_shift = taps->d_exp_samples;
     if (taps && taps->d_encoded_exp) E.ws_eexp = taps->d_encoded_exp;      // the exponent stage writes the tap directly
-    E.chbwcod = call_chbwcod(ctx, desc);
+    E.chbwcod = call_chbwcod(ctx, desc, E.cfg.nfbw);
     E.bw = ctx->bw_mode != 0;
     E.exp_strategy = ctx->exp_strategy;
     E.pcm = d_pcm;
@@ -1535,7 +1570,7 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
                           int32_t *d_csnroffst, uint8_t *d_frames_out, int out_stride, uint32_t *d_status)
 {
     if (!ctx) return AC3MI_ERR_ARG;
-    if (!dec || !enc || !d_frames_in || !d_delay || !d_lfsr || !chmap || !d_last || !d_csnroffst || !d_frames_out || !d_status ||
+    if (!dec || !enc || !d_frames_in || !d_delay || !d_lfsr || (!chmap && ctx->layout_mode != 2) || !d_last || !d_csnroffst || !d_frames_out || !d_status ||
         n_streams < 0 || frames_per_stream < 0 || dec->frame_bytes < 8 || dec->frame_bytes > 3840 ||
         in_stride < ((dec->frame_bytes + 3) & ~3) || (in_stride & 3) || ((uintptr_t)d_frames_in & 3)) {
         ctx->err = "ac3mi_transcode_batch: bad argument";
@@ -1552,17 +1587,34 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     }
     EncodeLaunch E;
     E.pack_mode = ctx->encode_mode;
-    const int fb = enc_config(enc->sample_rate, enc->bit_rate, enc->channels, &E.cfg);
+    // ac3mi_set_encode_layout: 0 the reference's table, 1 the set layout, 2 the layout the decoder granted
+    const int lay_acmod = ctx->layout_mode == 2 ? granted_acmod(out_flags) : call_acmod(ctx);
+    const int lay_lfeon = ctx->layout_mode == 2 ? ((out_flags & AC3MI_LFE) ? 1 : 0) : ctx->layout_lfeon;
+    const int fb = enc_config(enc->sample_rate, enc->bit_rate, enc->channels, &E.cfg, lay_acmod, lay_lfeon);
     if (fb <= 0 || enc->channels != n_out) {
-        ctx->err = "ac3mi_transcode_batch: encoder configuration rejected, or its channel count differs from the decoder's output";
+        ctx->err = "ac3mi_transcode_batch: encoder configuration rejected (channels not those of the layout set by "
+                   "ac3mi_set_encode_layout), or its channel count differs from the decoder's output";
         return AC3MI_ERR_ARG;
     }
-    E.chbwcod = call_chbwcod(ctx, enc);                 // (after enc_config: the descriptor is a valid one)
+    E.chbwcod = call_chbwcod(ctx, enc, E.cfg.nfbw);     // (after enc_config: the descriptor is a valid one)
     E.bw = ctx->bw_mode != 0;
     E.exp_strategy = ctx->exp_strategy;
     if (out_stride < ((fb + 3) & ~3) || (out_stride & 3) || ((uintptr_t)d_frames_out & 3)) {
         ctx->err = "ac3mi_transcode_batch: out_stride must be a multiple of 4 and >= the frame size";
         return AC3MI_ERR_ARG;
+    }
+    uint8_t follow[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (ctx->layout_mode == 2) {
+        // the map that inverts the s16 converter's WAVE interleave: coded full-bandwidth channel k is decoded plane lfe + k,
+        // the LFE (coded last) plane 0; the converter puts plane map[w] into WAVE slot w
+        int map[6];
+        if (s16_channel_map(out_flags, map) != n_out) { ctx->err = "ac3mi_transcode_batch: no channel map for the granted output"; return AC3MI_ERR_ARG; }
+        for (int k = 0; k < n_out; k++) {
+            const int plane = k < E.cfg.nfbw ? E.cfg.lfe + k : 0;
+            for (int w = 0; w < n_out; w++)
+                if (map[w] == plane) follow[k] = (uint8_t)w;
+        }
+        chmap = follow;                                 // (each tile below builds it again)
     }
     for (int i = 0; i < 8; i++) E.chmap[i] = i < enc->channels ? chmap[i] : 0;
     for (int i = 0; i < enc->channels; i++)
@@ -1633,10 +1685,10 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     if (ctx->coupling) { const int r = ensure_cpl(ctx, nfr); if (r != AC3MI_OK) return r; }
     if (ctx->drc_profile) { const int r = ensure_drc(ctx, nfr); if (r != AC3MI_OK) return r; }
     ac3mi::CplWs cplw = ctx->coupling ? ac3mi::cpl_slices(ctx->ws_cpl, nfr) : ac3mi::CplWs{};
-    if (ctx->coupling && ctx->rematrix && E.cfg.acmod == 2 && E.cfg.nch == 2) {
-        const int r = ensure_cplr(ctx, nfr);
+    if (ctx->coupling && ctx->rematrix && E.cfg.acmod == 2) {
+        const int r = ensure_cplr(ctx, nfr, E.cfg.nch);
         if (r != AC3MI_OK) return r;
-        ac3mi::cpl_remat_slices(cplw, ctx->ws_cplr, nfr);
+        ac3mi::cpl_remat_slices(cplw, ctx->ws_cplr, nfr, E.cfg.nch);
     }
     if (split) { const int r = ensure_split(ctx, nfr); if (r != AC3MI_OK) return r; }
     // Decoder front end, transform to s16, encoder: back to back on the context's stream.  (Until round 2 two chunks were
@@ -1736,7 +1788,7 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         G.ws_bsw = ctx->block_switch ? ctx->ws_bsw + r0 : nullptr;
         G.ws_remat = ctx->rematrix ? ctx->ws_remat + f0 * 6 : nullptr;
         G.cpl_begf = ctx->coupling ? ctx->cpl_begf : -1;
-        G.ws_cpl = ctx->coupling ? cpl_at(cplw, f0) : ac3mi::CplWs{};
+        G.ws_cpl = ctx->coupling ? cpl_at(cplw, f0, E.cfg.nch) : ac3mi::CplWs{};
         set_drc(ctx, G, nfr, f0);
         if (G.drc_state && !ctx->slots) G.drc_state += s0;
         G.pcm = ws_s16 + f0 * 1536 * n_out;

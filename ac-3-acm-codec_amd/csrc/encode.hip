@@ -685,7 +685,10 @@ __device__ __forceinline__ void bfly(c16 &p, c16 &q, int bx, int by, int ax, int
 // BW (ac3mi_set_encode_bandwidth 1 or 2, with REMAT only - the other variants take P.x.nbc at run time already): the fourth
 // rematrixing band ends at nbc = 73 + 3 chbwcod instead of 223.  nbc can split a lane's four bins only inside that band.
 // XS (ac3mi_set_encode_exp_strategy 1): the exponent stage chooses the strategies by cost (exp_stage<false, 1>).
-template <bool BSW, bool REMAT, bool BW = false, bool XS = false>
+// LFEROW (2/0+LFE with rematrixing, never with BSW or REMAT): the plain kernel restricted to the LFE row, one wavefront per
+// frame (unit = frame, channel nch - 1), launched beside the two-wavefront REMAT workgroups, which code channels 0 and 1.
+// The LFE never switches: with block switching on it leaves its row's decision 0.
+template <bool BSW, bool REMAT, bool BW = false, bool XS = false, bool LFEROW = false>
 __global__ __launch_bounds__(REMAT ? 128 : 64, REMAT ? (BSW ? ENC_MDCT_BSW_REMAT_LB : ENC_MDCT_REMAT_LB) : BSW ? ENC_MDCT_BSW_LB : ENC_MDCT_LB)
 void enc_mdct_kernel(const MdctParams P)
 {
@@ -707,8 +710,9 @@ void enc_mdct_kernel(const MdctParams P)
         unit = (int)((x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i);
         unit = __builtin_amdgcn_readfirstlane(unit);        // (wave-uniform by construction: row and state addresses on the scalar unit)
     }
-    const int ch = REMAT ? wave : unit % P.nch;
-    const int sf = REMAT ? unit : unit / P.nch;
+    static_assert(!(LFEROW && (BSW || REMAT)), "the LFE row alone takes the plain kernel");
+    const int ch = REMAT ? wave : LFEROW ? P.nch - 1 : unit % P.nch;
+    const int sf = REMAT || LFEROW ? unit : unit / P.nch;
     const int f = sf % P.frames;
     const int s = sf / P.frames;
 
@@ -1038,6 +1042,7 @@ void enc_mdct_kernel(const MdctParams P)
         *reinterpret_cast<uint32_t *>(&XL.E[blk][4 * lane]) = epack;
         if (lane == 0) P.shift[row] = (int8_t)shift;
         if constexpr (BSW) if (lane == 0) P.bsw[row] = sw ? 1 : 0;
+        if constexpr (LFEROW) if (lane == 0 && P.bsw) P.bsw[row] = 0;
         (void)rprev;
 #pragma unroll
         for (int k = 0; k < 4; k++) newv[k] = nxtv[k];
@@ -1193,9 +1198,12 @@ __device__ void cpl_mask_wave(const MaskTabs &T, const uint8_t *row, int16_t *ma
 // BW (ac3mi_set_encode_bandwidth 1 or 2): the coupling range ends at cplendmant = 73 + 12 P.endf, 3 + endf - begf bands.
 // XS (ac3mi_set_encode_exp_strategy 1): xs_choose picks the coupling row's strategies (its candidate rows through L.E1[0],
 // free until the rematrixing part) and the coupled channels' over [0, cplstrtmant) (exp_stage<false, 2>).
-template <bool BW = false, bool XS = false>
+// R3 (2/0+LFE with rematrixing): the rows before rematrixing (w.prow ...) and the coded rows have three rows a block, the
+// LFE's last, which this kernel neither reads nor writes (enc_mdct_kernel<.., LFEROW> codes it); <false>: two (2/0)
+template <bool BW = false, bool XS = false, bool R3 = false>
 __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
 {
+    constexpr int RN = R3 ? 3 : 2;                      // rows a block of the rematrixing arrays (= nch when they are used)
     __shared__ CplLDS L;
     const int lane = threadIdx.x;
     const size_t fidx = blockIdx.x;
@@ -1210,7 +1218,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
     for (int i = lane; i < 6 * 16; i += 64) (&L.en[0][0])[i] = 0;
     if (lane < 20) (&L.score[0][0])[lane] = 0;
     const bool rm = P.remat != nullptr;                 // 2/0 with rematrixing: the rows before it (w.prow)
-    if (lane < 6 * nch) L.sh[lane / nch][lane % nch] = rm ? P.w.pshift[fidx * 12 + lane] : P.shift[fidx * 6 * nch + lane];
+    if (lane < 6 * nch) L.sh[lane / nch][lane % nch] = rm ? P.w.pshift[fidx * (6 * RN) + lane] : P.shift[fidx * 6 * nch + lane];
     bool decline = false;
     if (P.bsw) decline = __ballot(lane < 6 * nch && lane % nch < nfbw && P.bsw[fidx * 6 * nch + lane] != 0) != 0;
     WAVE_SYNC();
@@ -1219,7 +1227,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
         for (int ch = 0; ch < nfbw; ch++) fmin = L.sh[b][ch] < fmin ? L.sh[b][ch] : fmin;
 
     // ---- per block: the coupling row, its raw exponents, the energies ----
-    const int32_t *md = rm ? P.w.prow + fidx * 6 * 2 * 256 : P.mdct + fidx * 6 * nch * 256;
+    const int32_t *md = rm ? P.w.prow + fidx * 6 * RN * 256 : P.mdct + fidx * 6 * nch * 256;
     for (int b = 0; b < 6; b++) {
         int shb = 127;
         for (int ch = 0; ch < nfbw; ch++) shb = L.sh[b][ch] < shb ? L.sh[b][ch] : shb;
@@ -1391,8 +1399,8 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
             if (lane < 16) (&L.rq[0][0])[lane] = 0;
             WAVE_SYNC();
             const int vl = L.sh[b][0], vr = L.sh[b][1], vm = vl < vr ? vl : vr;
-            const int4 lv = *reinterpret_cast<const int4 *>(md + (b * 2) * 256 + 4 * lane);
-            const int4 rv = *reinterpret_cast<const int4 *>(md + (b * 2 + 1) * 256 + 4 * lane);
+            const int4 lv = *reinterpret_cast<const int4 *>(md + (b * RN) * 256 + 4 * lane);
+            const int4 rv = *reinterpret_cast<const int4 *>(md + (b * RN + 1) * 256 + 4 * lane);
             const int lc[4] = {lv.x, lv.y, lv.z, lv.w}, rc[4] = {rv.x, rv.y, rv.z, rv.w};
             int a[4], c[4];
 #pragma unroll
@@ -1410,7 +1418,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
             }
             WAVE_SYNC();
             int flags = 0;
-            if (!P.bsw || P.bsw[(fidx * 6 + b) * 2] == P.bsw[(fidx * 6 + b) * 2 + 1])
+            if (!P.bsw || P.bsw[(fidx * 6 + b) * RN] == P.bsw[(fidx * 6 + b) * RN + 1])
                 for (int bd = 0; bd < nrem; bd++) {
                     const unsigned long long ems = L.rq[2][bd] < L.rq[3][bd] ? L.rq[2][bd] : L.rq[3][bd];
                     const unsigned long long elr = L.rq[0][bd] < L.rq[1][bd] ? L.rq[0][bd] : L.rq[1][bd];
@@ -1440,7 +1448,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
             }
 #pragma unroll
             for (int ch = 0; ch < 2; ch++) {
-                const size_t row = (fidx * 6 + b) * 2 + ch;
+                const size_t row = (fidx * 6 + b) * RN + ch;
                 *reinterpret_cast<int4 *>(P.mdct_out + row * 256 + 4 * lane) = make_int4(out[ch][0], out[ch][1], out[ch][2], out[ch][3]);
                 if (lane == 0) P.shift_out[row] = (int8_t)(flags ? vm : L.sh[b][ch]);
             }
@@ -1676,9 +1684,10 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
             }
             // ---- fixed side information (:880-916) ----
             {
-                const int extra[8] = {0, 0, 2, 2, 2, 4, 2, 4};
+                // (dual mono: dialnorm2, compr2e, langcod2e, audprodi2e in the BSI; dynrng2e in every block)
+                const int extra[8] = {8, 0, 2, 2, 2, 4, 2, 4};
                 frame_bits += 65 + extra[P.acmod & 7];
-                frame_bits += 6 * (nfbw * 2 + 2 + (P.acmod == 2 ? 1 : 0) + 2 * nfbw + (P.lfe ? 1 : 0) + 1 + 1 + 2);
+                frame_bits += 6 * (nfbw * 2 + 2 + (P.acmod == 2 ? 1 : 0) + (P.acmod == 0 ? 1 : 0) + 2 * nfbw + (P.lfe ? 1 : 0) + 1 + 1 + 2);
                 // chbwcod (6 bits) and gainrng (2 bits) of every full-bandwidth channel-block that sends exponents
                 uint64_t fbw_rows = 0;
                 for (int b = 0; b < 6; b++) fbw_rows |= ((1ull << nfbw) - 1) << (6 * b);
@@ -1689,7 +1698,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                 frame_bits += 16;
                 if constexpr (DRC) {
                     const uint8_t *code = P.drc + fidx * 6;
-                    for (int b = 0; b < 6; b++) frame_bits += drc_sends(code, b) ? 8 : 0;
+                    for (int b = 0; b < 6; b++) frame_bits += drc_sends(code, b) ? (P.acmod == 0 ? 16 : 8) : 0;     // (dual mono: dynrng2 too)
                 }
                 // rematrixing: the four flags of every block 1..5 that sends them (block 0's stay uncounted, as above)
                 if (P.remat)
@@ -2109,10 +2118,12 @@ struct alignas(16) PackfLDS {
 // BW (ac3mi_set_encode_bandwidth 1 or 2): FIXED51 with the run-time nbc; CPL with the coupling range ending at cplendmant =
 // 73 + 12 P.cpl_endf (3 + cpl_endf - cpl_begf bands, cplendf = P.cpl_endf)
 // MD (ac3mi_set_encode_metadata / ac3mi_set_encode_drc): the BSI fields of P.bsi, and the dynrng words of P.drc if it is set
-template <bool FIXED51, bool CPL = false, bool BW = false, bool MD = false>
+// DUAL (dual mono, acmod 0; generic and uncoupled only): the second programme's BSI fields and dynrng2e / dynrng2
+template <bool FIXED51, bool CPL = false, bool BW = false, bool MD = false, bool DUAL = false>
 __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackParams P)
 {
     static_assert(!(FIXED51 && CPL), "coupled frames take the generic packer");
+    static_assert(!(DUAL && (FIXED51 || CPL)), "dual mono is neither 5.1 nor coupled");
     __shared__ PackfLDS<CPL> L;
     extern __shared__ uint4 pk_dyn[];
     uint32_t *fr = reinterpret_cast<uint32_t *>(pk_dyn);
@@ -2193,14 +2204,18 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         if ((acmod & 1) && acmod != 1) put(2, (m >> 8) & 3u);
         if (acmod & 4) put(2, (m >> 10) & 3u);
         if (acmod == 2) put(2, (m >> 12) & 3u);
-        put(1, lfe); put(5, m & 31u); put(3, 0); put(1, (m >> 14) & 1u); put(1, (m >> 15) & 1u); put(3, 0);
+        put(1, lfe); put(5, m & 31u); put(3, 0);
+        if constexpr (DUAL) { put(5, m & 31u); put(3, 0); }    // dual mono: dialnorm2 = dialnorm, compr2e langcod2e audprodi2e
+        put(1, (m >> 14) & 1u); put(1, (m >> 15) & 1u); put(3, 0);
     } else {
         put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, 0); put(3, acmod);
         flush();
         if ((acmod & 1) && acmod != 1) put(2, 1);
         if (acmod & 4) put(2, 1);
         if (acmod == 2) put(2, 0);
-        put(1, lfe); put(5, 31); put(3, 0); put(1, 0); put(1, 1); put(3, 0);
+        put(1, lfe); put(5, 31); put(3, 0);
+        if constexpr (DUAL) { put(5, 31); put(3, 0); }
+        put(1, 0); put(1, 1); put(3, 0);
     }
 
     // ---- audio blocks (:1194-1502) ----
@@ -2238,10 +2253,16 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         for (int ch = 0; ch < nfbw; ch++) put(1, 1);
         if constexpr (MD) {
             // dynrnge + dynrng (flushed: the block's first stretch of fields stays within the accumulator)
-            if (P.drc && drc_sends(P.drc + fidx * 6, b)) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
+            const bool word = P.drc && drc_sends(P.drc + fidx * 6, b);
+            if (word) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
             else put(1, 0);
+            if constexpr (DUAL) {                   // dual mono: dynrng2e + dynrng2, the same word in the same blocks
+                if (word) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
+                else put(1, 0);
+            }
         } else {
             put(1, 0);
+            if constexpr (DUAL) put(1, 0);
         }
         if (cplf) {
             // cplstre, cplinu, chincpl, phsflginu, cplbegf, cplendf, cplbndstrc (all 0); cplcoe, mstrcplco, the coordinates
@@ -2519,13 +2540,13 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
     auto strat_of = [&](int ch) { return __builtin_amdgcn_readlane(strat_l, ch); };
     // bits of the frame header (:1113-1147) and of this block's side information with its exponents (:1194-1332)
     const int hdr_bits = 16 + 16 + 2 + 6 + 5 + 3 + 3 + (((P.acmod & 1) && P.acmod != 1) ? 2 : 0) + ((P.acmod & 4) ? 2 : 0) +
-                         (P.acmod == 2 ? 2 : 0) + 1 + 5 + 3 + 1 + 1 + 3;
-    int side_bits = 2 * nfbw + 1 + (b == 0 ? 2 : 1) + (P.acmod == 2 ? (b == 0 ? 5 : 1) : 0) + 2 * nfbw + (P.lfe ? 1 : 0) +
+                         (P.acmod == 2 ? 2 : 0) + 1 + 5 + 3 + (P.acmod == 0 ? 8 : 0) + 1 + 1 + 3;
+    int side_bits = 2 * nfbw + 1 + (P.acmod == 0 ? 1 : 0) + (b == 0 ? 2 : 1) + (P.acmod == 2 ? (b == 0 ? 5 : 1) : 0) + 2 * nfbw + (P.lfe ? 1 : 0) +
                     1 + (b == 0 ? 11 : 0) + 1 + (b == 0 ? 6 + 7 * nch : 0) + 2;
     const int rem = P.remat ? (int)P.remat[fidx * 6 + b] : -1;     // rematrixing: block b > 0 sends its four flags when rematstr
     if (b > 0 && rem >= 0 && (rem & 0x10)) side_bits += 4;
     const bool drc_word = MD && P.drc && drc_sends(P.drc + fidx * 6, b);
-    if (drc_word) side_bits += 8;
+    if (drc_word) side_bits += P.acmod == 0 ? 16 : 8;
     for (int ch = 0; ch < nch; ch++) {
         const int stg = strat_of(ch);
         if (stg == 0) continue;
@@ -2594,14 +2615,18 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
                 if ((P.acmod & 1) && P.acmod != 1) put(2, (m >> 8) & 3u);
                 if (P.acmod & 4) put(2, (m >> 10) & 3u);
                 if (P.acmod == 2) put(2, (m >> 12) & 3u);
-                put(1, P.lfe); put(5, m & 31u); put(3, 0); put(1, (m >> 14) & 1u); put(1, (m >> 15) & 1u); put(3, 0);
+                put(1, P.lfe); put(5, m & 31u); put(3, 0);
+                if (P.acmod == 0) { put(5, m & 31u); put(3, 0); }      // dual mono: dialnorm2 = dialnorm, compr2e langcod2e audprodi2e
+                put(1, (m >> 14) & 1u); put(1, (m >> 15) & 1u); put(3, 0);
             } else {
                 put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, 0); put(3, P.acmod);
                 flush();
                 if ((P.acmod & 1) && P.acmod != 1) put(2, 1);
                 if (P.acmod & 4) put(2, 1);
                 if (P.acmod == 2) put(2, 0);
-                put(1, P.lfe); put(5, 31); put(3, 0); put(1, 0); put(1, 1); put(3, 0);
+                put(1, P.lfe); put(5, 31); put(3, 0);
+                if (P.acmod == 0) { put(5, 31); put(3, 0); }
+                put(1, 0); put(1, 1); put(3, 0);
             }
             flush();
             pos = mine;
@@ -2615,8 +2640,13 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
             // dynrnge + dynrng (flushed: the fields up to the first exponent would overflow the accumulator by up to 2 bits)
             if (drc_word) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
             else put(1, 0);
+            if (P.acmod == 0) {                     // dual mono: dynrng2e + dynrng2, the same word in the same blocks
+                if (drc_word) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
+                else put(1, 0);
+            }
         } else {
             put(1, 0);
+            if (P.acmod == 0) put(1, 0);
         }
         if (b == 0) { put(1, 1); put(1, 0); } else put(1, 0);
         if (P.acmod == 2) {
@@ -2962,10 +2992,11 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     M.x.halfrate = c.halfrate;
     M.x.nbc = nbc;      // the only reader of last[] is this same wavefront's block 0
     M.bsw = E.ws_bsw;
-    M.remat = c.acmod == 2 && c.nch == 2 ? E.ws_remat : nullptr;      // (rematrixing is a 2/0 tool: other layouts ignore it)
+    M.remat = c.acmod == 2 ? E.ws_remat : nullptr;      // (rematrixing is a 2/0 tool, with or without the LFE: other layouts ignore it)
     const dim3 units(E.n_streams * E.frames_per_stream * c.nch), frames(E.n_streams * E.frames_per_stream);
-    // (begf > cplendf + 2: no coupling band - no frame couples, the bytes are coupling off's)
-    const bool cpl = E.cpl_begf >= 0 && c.nfbw >= 2 && E.cpl_begf <= cpl_endf + 2;
+    // (begf > cplendf + 2: no coupling band - no frame couples, the bytes are coupling off's; dual mono's two programmes are
+    // never coupled)
+    const bool cpl = E.cpl_begf >= 0 && c.nfbw >= 2 && c.acmod != 0 && E.cpl_begf <= cpl_endf + 2;
     if (cpl && M.remat) {
         // coupling with rematrixing: the rows without rematrixing first (before the history is rewritten), for enc_cpl_kernel
         MdctParams M0 = M;
@@ -3001,6 +3032,15 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     else hipLaunchKernelGGL((enc_mdct_kernel<false, false>), units, dim3(64), 0, stream, M);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    // 2/0+LFE with rematrixing: the REMAT workgroups code channels 0 and 1, a launch of the plain kernel the LFE row beside them
+    if (M.remat && c.lfe) {
+        MdctParams ML = M;
+        ML.remat = nullptr;
+        if (E.exp_strategy) hipLaunchKernelGGL((enc_mdct_kernel<false, false, false, true, true>), frames, dim3(64), 0, stream, ML);
+        else hipLaunchKernelGGL((enc_mdct_kernel<false, false, false, false, true>), frames, dim3(64), 0, stream, ML);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     // channel coupling: layouts with two or more full-bandwidth channels
     if (cpl) {
         CplParams C;
@@ -3018,7 +3058,13 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
         C.nfr = E.n_streams * E.frames_per_stream;
         C.endf = bw ? cpl_endf : 12;
         C.nbc = nbc;
-        if (E.exp_strategy && bw) hipLaunchKernelGGL((enc_cpl_kernel<true, true>), dim3(C.nfr), dim3(64), 0, stream, C);
+        if (M.remat && c.lfe) {                         // 2/0+LFE with rematrixing: three rows a block in the rematrixing arrays
+            if (E.exp_strategy && bw) hipLaunchKernelGGL((enc_cpl_kernel<true, true, true>), dim3(C.nfr), dim3(64), 0, stream, C);
+            else if (E.exp_strategy) hipLaunchKernelGGL((enc_cpl_kernel<false, true, true>), dim3(C.nfr), dim3(64), 0, stream, C);
+            else if (bw) hipLaunchKernelGGL((enc_cpl_kernel<true, false, true>), dim3(C.nfr), dim3(64), 0, stream, C);
+            else hipLaunchKernelGGL((enc_cpl_kernel<false, false, true>), dim3(C.nfr), dim3(64), 0, stream, C);
+        }
+        else if (E.exp_strategy && bw) hipLaunchKernelGGL((enc_cpl_kernel<true, true>), dim3(C.nfr), dim3(64), 0, stream, C);
         else if (E.exp_strategy) hipLaunchKernelGGL((enc_cpl_kernel<false, true>), dim3(C.nfr), dim3(64), 0, stream, C);
         else if (bw) hipLaunchKernelGGL(enc_cpl_kernel<true>, dim3(C.nfr), dim3(64), 0, stream, C);
         else hipLaunchKernelGGL(enc_cpl_kernel<false>, dim3(C.nfr), dim3(64), 0, stream, C);
@@ -3122,6 +3168,7 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
         else if (cpl) hipLaunchKernelGGL((enc_packf_kernel<false, true, false, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
         else if (fixed51 && bw) hipLaunchKernelGGL((enc_packf_kernel<true, false, true, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
         else if (fixed51 && P.nbc == 223) hipLaunchKernelGGL((enc_packf_kernel<true, false, false, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
+        else if (c.acmod == 0) hipLaunchKernelGGL((enc_packf_kernel<false, false, false, MD, true>), dim3(nfr), dim3(64), fr_lds, stream, P);
         else hipLaunchKernelGGL((enc_packf_kernel<false, false, false, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
     };
     if (drc) searches(std::true_type{});
@@ -3165,16 +3212,17 @@ CplWs cpl_slices(void *base, size_t nfr)
     return w;
 }
 
-void cpl_remat_slices(CplWs &w, void *base, size_t nfr)
+void cpl_remat_slices(CplWs &w, void *base, size_t nfr, int nrow)
 {
     uint8_t *p = (uint8_t *)base;
     auto take = [&](size_t n) { uint8_t *q = p; p += (n + 15) & ~(size_t)15; return q; };
-    w.prow = (int32_t *)take(6 * 2 * 256 * 4 * nfr);
-    w.pshift = (int8_t *)take(16 * nfr);
-    w.peexp = take(6 * 2 * 256 * nfr);
-    w.pemask = (int16_t *)take(6 * 2 * 50 * 2 * nfr);
-    w.pstrat = take(16 * nfr);
-    w.pebits = (int32_t *)take(16 * nfr);
+    const size_t r16 = (size_t)((6 * nrow + 15) & ~15), e16 = (size_t)((4 * nrow + 15) & ~15);   // (cpl_remat_frame_bytes)
+    w.prow = (int32_t *)take(6 * nrow * 256 * 4 * nfr);
+    w.pshift = (int8_t *)take(r16 * nfr);
+    w.peexp = take(6 * nrow * 256 * nfr);
+    w.pemask = (int16_t *)take(6 * nrow * 50 * 2 * nfr);
+    w.pstrat = take(r16 * nfr);
+    w.pebits = (int32_t *)take(e16 * nfr);
 }
 
 hipError_t launch_enc_history(const EncodeLaunch &E, hipStream_t stream)

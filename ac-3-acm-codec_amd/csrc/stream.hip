@@ -555,8 +555,9 @@ int encode_group(ac3mi_pool *p, const std::vector<ac3mi_stream *> &group, int ba
         const int bsw = ctx->block_switch, remat = ctx->rematrix;  // the stream layer codes long blocks only and never
         const int cpl = ctx->coupling, bw = ctx->bw_mode;          // rematrixes, couples, band-limits or sends metadata and
         const int drc = ctx->drc_profile;                          // dynrng of its own, and keeps the reference's exponent
-        const int xs = ctx->exp_strategy;                          // strategies (no knobs of its own)
-        const uint32_t bsi = ctx->enc_bsi;
+        const int xs = ctx->exp_strategy;                          // strategies and layout (no knobs of its own: a WAVE
+        const uint32_t bsi = ctx->enc_bsi;                         // format carries only a channel count)
+        const int lay = ctx->layout_mode;
         ctx->block_switch = 0;
         ctx->rematrix = 0;
         ctx->coupling = 0;
@@ -564,6 +565,7 @@ int encode_group(ac3mi_pool *p, const std::vector<ac3mi_stream *> &group, int ba
         ctx->drc_profile = 0;
         ctx->exp_strategy = 0;
         ctx->enc_bsi = ac3mi::BSI_DEFAULT;
+        ctx->layout_mode = 0;
         const int rc = ac3mi_encode_batch(ctx, &d, (const int16_t *)((const uint8_t *)d_s16 + (size_t)lo * in_bytes), chmap, p->d_last, p->d_csnr,
                                           d_frames + (size_t)lo * stride, stride, kc, 1, NULL);
         ctx->block_switch = bsw;
@@ -573,6 +575,7 @@ int encode_group(ac3mi_pool *p, const std::vector<ac3mi_stream *> &group, int ba
         ctx->drc_profile = drc;
         ctx->exp_strategy = xs;
         ctx->enc_bsi = bsi;
+        ctx->layout_mode = lay;
         ac3mi_set_state_slots(ctx, NULL);
         if (rc != AC3MI_OK) { (void)hipDeviceSynchronize(); return fail(p, AC3MI_MMSYSERR_NOMEM, "encode batch"); }
     }

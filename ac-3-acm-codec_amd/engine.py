@@ -319,6 +319,14 @@ class Engine:
         transcode_batch."""
         self._check(self.lib.ac3mi_set_encode_exp_strategy(ctypes.c_void_p(self.ctx), int(mode)))
 
+    def set_encode_layout(self, mode, acmod=None, lfeon=0):
+        """Channel layout of the encoded frames (ac3mi_set_encode_layout): 0 = the reference's table by channel count, 1 = code
+        `acmod` (0..7) with `lfeon` (0/1) - channels must then be nfchans(acmod) + lfeon, coded in A/52's order with the
+        LFE last -, 2 = transcode_batch codes the layout the decoder granted (chmap not read; encode_batch codes as mode 0).
+        Applies to encode_batch and transcode_batch."""
+        self._check(self.lib.ac3mi_set_encode_layout(ctypes.c_void_p(self.ctx), int(mode), -1 if acmod is None else int(acmod),
+                                                     int(lfeon)))
+
     def set_mix_state(self, pending=None, flags=None):
         """liba52's overlap bookkeeping around frames with surround level 0 (ac3mi_set_mix_state): `pending` float32 shaped
         like the delay array, `flags` int32 [S][6], both zero for new streams and updated in place by the decode calls that
@@ -346,7 +354,7 @@ class Engine:
             out = torch.zeros((S, F, stride), dtype=torch.uint8, device=dev)
         if status is None:
             status = torch.zeros((S, F), dtype=torch.int32, device=dev)
-        cm = (ctypes.c_uint8 * 8)(*(list(chmap) + [0] * 8)[:8])
+        cm = (ctypes.c_uint8 * 8)(*(list(chmap) + [0] * 8)[:8]) if chmap is not None else None
         dc, ec = dec.c(), enc.c()
         self._drain_torch(wait_torch)
         self._check(self.lib.ac3mi_transcode_batch(self.ctx, ctypes.byref(dc), ctypes.byref(ec), frames.data_ptr(), in_stride, S, F,

@@ -289,6 +289,32 @@ int ac3mi_set_encode_bandwidth(ac3mi_ctx *ctx, int mode, int chbwcod);
  * AC3MI_ERR_ARG, and the setting is unchanged. */
 int ac3mi_set_encode_exp_strategy(ac3mi_ctx *ctx, int mode);
 
+/* Channel layout of the encoder's frames (new; applies to every following ac3mi_encode_batch / ac3mi_transcode_batch on
+ * `ctx`, in either packer variant, with or without state slots, tiled or not, with every other encoder tool on or off):
+ *   0  (default) the reference's table: 1, 2, 3, 4, 5, 6 channels code 1/0, 2/0, 3/0, 2/2, 3/2, 3/2+LFE (acmod 1, 2, 3, 6,
+ *      7, 7).  acmod and lfeon are ignored; every byte is the one of before.
+ *   1  acmod 0..7 with lfeon 0/1.  A call whose channels is not nfchans(acmod) + lfeon (nfchans 2, 1, 2, 3, 3, 4, 4, 5)
+ *      returns AC3MI_ERR_ARG (ac3mi_last_error says why).  Coded channel order is A/52's - Ch1 Ch2 / C / L R / L C R /
+ *      L R S / L C R S / L R Ls Rs / L C R Ls Rs, the LFE last - and chmap keeps its meaning: coded channel k is input
+ *      slot chmap[k].
+ *   2  follow the source: ac3mi_transcode_batch codes the layout the decoder granted (out_flags of ac3mi_decode_planes):
+ *      acmod = out_flags & 15 for 0..7, 1/0 for AC3MI_CHANNEL1 / AC3MI_CHANNEL2, 2/0 for AC3MI_DOLBY, lfeon = out_flags
+ *      & AC3MI_LFE != 0.  chmap is not read (it may be NULL): coded channel k of the new frames carries decoded coded
+ *      channel k (the map inverts the s16 interleave of those flags).  ac3mi_encode_batch has no source: it codes as mode 0.
+ * Every tool keeps its rule, with nfbw = nfchans(acmod) and the LFE (coded channel nch - 1) taken from the layout: block
+ * switching never switches the LFE; coupling needs two or more full-bandwidth channels; bandwidth mode 2 divides the bit
+ * rate by nfbw; cmixlev / surmixlev / dsurmod are sent by acmod; DRC measures the full-bandwidth channels.  Rematrixing
+ * applies to acmod 2 with or without the LFE (channels 0 and 1, the same flags, bands and interplay with coupling and
+ * bandwidth; the LFE row is coded as in any LFE layout).  Layouts the reference never produced:
+ *   dual mono (acmod 0): the BSI carries dialnorm2 (5 bits, equal to dialnorm: ac3mi_set_encode_metadata's, or 31) and
+ *      compr2e, langcod2e, audprodi2e 0 after the first programme's fields (8 bits); every audio block carries dynrng2e
+ *      after dynrng, and under a DRC profile dynrng2e / dynrng2 go in exactly the blocks that send dynrng, with the same
+ *      code (computed from both channels with the one state word: per-programme gains and dialnorms are not offered).
+ *      No frame is coupled (the bytes are those of coupling off), and rematrixing and dsurmod do not apply.
+ * The drop-in AC3_encode_* and the byte-stream layer (ac3mi_stream.h) always use mode 0: a WAVE format carries only a
+ * channel count.  A mode outside 0..2, or a mode-1 acmod / lfeon out of range: AC3MI_ERR_ARG, and the setting is unchanged. */
+int ac3mi_set_encode_layout(ac3mi_ctx *ctx, int mode, int acmod, int lfeon);
+
 /* Bitstream information (BSI) of the encoder's frames (new; applies to every following ac3mi_encode_batch /
  * ac3mi_transcode_batch on `ctx`, in either packer variant, with or without state slots, tiled or not, with every other
  * encoder tool on or off).  The fields are written as given; all have fixed widths, so the bit allocation, the SNR offsets
