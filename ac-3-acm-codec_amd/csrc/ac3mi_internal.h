@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <array>
 #include <string>
 #include "../../include/ac3mi.h"
 
@@ -225,55 +226,61 @@ int s16_channel_map(int flags, int map[6]);
 
 void build_host_tables(float *window256, float2 *tw_long /*[8][16]*/, float2 *tw_short /*[8][16]*/);
 
+// a device workspace: grown on demand (ws_grow in capi.hip), freed with the context
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    template <class T> T *at(size_t off = 0) const { return (T *)((uint8_t *)p + off); }
+};
+
+// the encoder's bitstream tools (ac3mi_set_encode_*); the defaults are the reference's fixed behaviour
+struct EncTools {
+    int block_switch = 0;               // ac3mi_set_encode_block_switch
+    int rematrix = 0;                   // ac3mi_set_encode_rematrix
+    int coupling = 0, cpl_begf = 0;     // ac3mi_set_encode_coupling
+    int bw_mode = 0, bw_chbwcod = 50;   // ac3mi_set_encode_bandwidth
+    uint32_t bsi = BSI_DEFAULT;         // ac3mi_set_encode_metadata (bsi_word)
+    int drc_profile = 0;                // ac3mi_set_encode_drc
+    int32_t *drc_state = nullptr;
+    int exp_strategy = 0;               // ac3mi_set_encode_exp_strategy
+    int layout_mode = 0, layout_acmod = 0, layout_lfeon = 0;    // ac3mi_set_encode_layout
+};
+
 }  // namespace ac3mi
 
 struct ac3mi_ctx {
-    int device;
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // second stream: the byte-stream layer's PCIe copies beside the kernels (stream.hip)
-    hipStream_t stream2;
-    int encode_mode;        // ac3mi_set_encode_mode
-    int block_switch;       // ac3mi_set_encode_block_switch
-    uint8_t *ws_bsw;        // its decisions between the MDCT kernel and the packers, one byte per channel-block
-    size_t ws_bsw_bytes;
-    int rematrix;           // ac3mi_set_encode_rematrix
-    uint8_t *ws_remat;      // its decisions between the MDCT kernel, the search and the packers, one byte per frame-block
-    size_t ws_remat_bytes;
-    int coupling, cpl_begf; // ac3mi_set_encode_coupling
-    int bw_mode, bw_chbwcod;    // ac3mi_set_encode_bandwidth
-    uint32_t enc_bsi;       // ac3mi_set_encode_metadata (ac3mi::bsi_word)
-    int drc_profile;        // ac3mi_set_encode_drc
-    int exp_strategy;       // ac3mi_set_encode_exp_strategy
-    int layout_mode, layout_acmod, layout_lfeon;    // ac3mi_set_encode_layout
-    int32_t *drc_state;
-    void *ws_drc;           // its gains and codes between the DRC kernels, the search and the packers, 3 bytes a frame-block
-    size_t ws_drc_bytes;
-    void *ws_cpl;           // its per-frame workspace (ac3mi::CplWs, CPL_FRAME_BYTES a frame)
-    size_t ws_cpl_bytes;
-    void *ws_cplr;          // with rematrixing on as well: CPL_REMAT_FRAME_BYTES a frame
-    size_t ws_cplr_bytes;
-    ac3mi::DeviceTables tab;
-    // decode workspace (coefficient planes + block-switch flags between the two kernels)
-    float *ws_coef;
-    uint8_t *ws_blksw;
-    size_t ws_coef_bytes, ws_blksw_bytes;
-    // encode workspace (MDCT coefficients, exponents, block exponents between the two kernels)
-    void *ws_enc;
-    size_t ws_enc_bytes;
-    // transcode workspace (float PCM and s16 PCM between the decoder and the encoder)
-    void *ws_tc;
-    size_t ws_tc_bytes;
+    hipStream_t stream2 = nullptr;
+    int encode_mode = 0;    // ac3mi_set_encode_mode
+    ac3mi::EncTools tools;
+    ac3mi::DeviceTables tab = {};
+    // device workspaces
+    ac3mi::DevBuf ws_coef;  // decode: coefficient planes between the front end and the transform
+    ac3mi::DevBuf ws_blksw; // ... block-switch flags, then the per-frame surround-level-0 flags
+    ac3mi::DevBuf ws_draws; // [S][F] draw counts + [S][F] u16 frame-start LFSR states (decode, frame-parallel)
+    ac3mi::DevBuf ws_split; // descriptors, rows, coupling coordinates, generator positions between the split front end's kernels
+    ac3mi::DevBuf ws_enc;   // encode: MDCT coefficients, exponents, block exponents between the kernels
+    ac3mi::DevBuf ws_tc;    // transcode: s16 PCM between the decoder and the encoder
+    ac3mi::DevBuf ws_bsw;   // block-switch decisions between the MDCT kernel and the packers, one byte per channel-block
+    ac3mi::DevBuf ws_remat; // rematrixing decisions between the MDCT kernel, the search and the packers, one byte per frame-block
+    ac3mi::DevBuf ws_cpl;   // coupling's per-frame workspace (ac3mi::CplWs, CPL_FRAME_BYTES a frame)
+    ac3mi::DevBuf ws_cplr;  // with rematrixing on as well: cpl_remat_frame_bytes a frame
+    ac3mi::DevBuf ws_drc;   // DRC gains and codes between the DRC kernels, the search and the packers, 3 bytes a frame-block
+    // every workspace above (ac3mi_destroy frees them, ac3mi_workspace_bytes sums them)
+    template <class Ctx> static auto workspaces(Ctx *c)
+    {
+        return std::array{&c->ws_coef, &c->ws_blksw, &c->ws_draws, &c->ws_split, &c->ws_enc, &c->ws_tc,
+                          &c->ws_bsw, &c->ws_remat, &c->ws_cpl, &c->ws_cplr, &c->ws_drc};
+    }
     // optional state-slot indirection for the next batch calls (ac3mi_set_state_slots)
-    const int32_t *slots;
+    const int32_t *slots = nullptr;
     // optional liba52-exact overlap state around frames with surround level 0 (ac3mi_set_mix_state)
-    float *mix_pending;
-    int32_t *mix_flags;
-    long long tile_frames;  // workspace bound: batches above this many frames go through in tiles of whole streams (0 = never)
-    int decode_mode;        // ac3mi_set_decode_mode
-    uint32_t *ws_draws;     // [S][F] draw counts + [S][F] u16 frame-start LFSR states (decode, frame-parallel)
-    size_t ws_draws_bytes;
-    void *ws_split;         // descriptors, rows, coupling coordinates, generator positions between the split front end's kernels
-    size_t ws_split_bytes;
+    float *mix_pending = nullptr;
+    int32_t *mix_flags = nullptr;
+    long long tile_frames = 131072;    // workspace bound: batches above this many frames go through in tiles of whole streams (0 = never)
+    int decode_mode = 0;    // ac3mi_set_decode_mode
     std::string err;
 };

@@ -349,6 +349,13 @@ using namespace ac3mi;
         }                                                                              \
     } while (0)
 
+// an AC3MI_* status other than AC3MI_OK returns from the caller
+#define TRY(call)                                                                      \
+    do {                                                                               \
+        const int r_ = (call);                                                         \
+        if (r_ != AC3MI_OK) return r_;                                                 \
+    } while (0)
+
 // Measurement aid: what one SIMD sustains in plain 32-bit VALU instructions while the whole chip is busy with them
 // (the issue ceiling the instruction-bound kernels are priced against; the clock under such a load is not the
 // data-sheet peak).  Every wavefront executes iters x 32 v_add_u32 / v_xor_b32 on eight independent registers.
@@ -474,56 +481,14 @@ ac3mi_ctx *ac3mi_create(int device)
     }
     ac3mi_ctx *ctx = new ac3mi_ctx();
     ctx->device = device;
-    ctx->stream = nullptr;
-    ctx->tab = DeviceTables{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ctx->ws_enc = nullptr;
-    ctx->ws_enc_bytes = 0;
-    ctx->ws_tc = nullptr;
-    ctx->ws_tc_bytes = 0;
-    ctx->slots = nullptr;
-    ctx->decode_mode = 0;
     if (const char *e = getenv("AC3MI_DECODE_MODE")) {          // test aid: default front-end variant (ac3mi_set_decode_mode)
         const int m = atoi(e);
         if (m >= 0 && m <= 6 && m != 2) ctx->decode_mode = m;
     }
-    ctx->tile_frames = 131072;
-    ctx->encode_mode = 0;
     if (const char *e = getenv("AC3MI_ENCODE_MODE")) {          // test aid: default packer variant (ac3mi_set_encode_mode)
         const int m = atoi(e);
         if (m >= 0 && m <= 2) ctx->encode_mode = m;
     }
-    ctx->block_switch = 0;
-    ctx->ws_bsw = nullptr;
-    ctx->ws_bsw_bytes = 0;
-    ctx->rematrix = 0;
-    ctx->ws_remat = nullptr;
-    ctx->ws_remat_bytes = 0;
-    ctx->coupling = 0;
-    ctx->cpl_begf = 0;
-    ctx->bw_mode = 0;
-    ctx->bw_chbwcod = 50;
-    ctx->enc_bsi = ac3mi::BSI_DEFAULT;
-    ctx->drc_profile = 0;
-    ctx->drc_state = nullptr;
-    ctx->exp_strategy = 0;
-    ctx->layout_mode = 0;
-    ctx->layout_acmod = 0;
-    ctx->layout_lfeon = 0;
-    ctx->ws_drc = nullptr;
-    ctx->ws_drc_bytes = 0;
-    ctx->ws_cpl = nullptr;
-    ctx->ws_cpl_bytes = 0;
-    ctx->ws_cplr = nullptr;
-    ctx->ws_cplr_bytes = 0;
-    ctx->ws_draws = nullptr;
-    ctx->ws_draws_bytes = 0;
-    ctx->ws_split = nullptr;
-    ctx->ws_split_bytes = 0;
-    ctx->ws_coef = nullptr;
-    ctx->ws_blksw = nullptr;
-    ctx->mix_pending = nullptr;
-    ctx->mix_flags = nullptr;
-    ctx->ws_coef_bytes = ctx->ws_blksw_bytes = 0;
     if (ctx_init(ctx) != AC3MI_OK) {
         g_err = ctx->err;
         delete ctx;
@@ -543,17 +508,7 @@ void ac3mi_destroy(ac3mi_ctx *ctx)
     (void)hipFree(ctx->tab.dec);
     (void)hipFree(ctx->tab.lfsr_seq);
     (void)hipFree(ctx->tab.lfsr_idx);
-    (void)hipFree(ctx->ws_coef);
-    (void)hipFree(ctx->ws_blksw);
-    (void)hipFree(ctx->ws_enc);
-    (void)hipFree(ctx->ws_tc);
-    (void)hipFree(ctx->ws_draws);
-    (void)hipFree(ctx->ws_split);
-    (void)hipFree(ctx->ws_bsw);
-    (void)hipFree(ctx->ws_remat);
-    (void)hipFree(ctx->ws_cpl);
-    (void)hipFree(ctx->ws_cplr);
-    (void)hipFree(ctx->ws_drc);
+    for (DevBuf *b : ac3mi_ctx::workspaces(ctx)) (void)hipFree(b->p);
     (void)hipFree(ctx->tab.enc);
     (void)hipEventDestroy(ctx->ev0);
     (void)hipEventDestroy(ctx->ev1);
@@ -767,30 +722,30 @@ int ac3mi_set_encode_mode(ac3mi_ctx *ctx, int mode)
 int ac3mi_set_encode_block_switch(ac3mi_ctx *ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 1) return AC3MI_ERR_ARG;
-    ctx->block_switch = mode;
+    ctx->tools.block_switch = mode;
     return AC3MI_OK;
 }
 
 int ac3mi_set_encode_rematrix(ac3mi_ctx *ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 1) return AC3MI_ERR_ARG;
-    ctx->rematrix = mode;
+    ctx->tools.rematrix = mode;
     return AC3MI_OK;
 }
 
 int ac3mi_set_encode_coupling(ac3mi_ctx *ctx, int mode, int begf)
 {
     if (!ctx || mode < 0 || mode > 1 || begf < 0 || begf > 12) return AC3MI_ERR_ARG;
-    ctx->coupling = mode;
-    ctx->cpl_begf = begf;
+    ctx->tools.coupling = mode;
+    ctx->tools.cpl_begf = begf;
     return AC3MI_OK;
 }
 
 int ac3mi_set_encode_bandwidth(ac3mi_ctx *ctx, int mode, int chbwcod)
 {
     if (!ctx || mode < 0 || mode > 2 || (mode == 1 && (chbwcod < 0 || chbwcod > 50))) return AC3MI_ERR_ARG;
-    ctx->bw_mode = mode;
-    ctx->bw_chbwcod = mode == 1 ? chbwcod : 50;
+    ctx->tools.bw_mode = mode;
+    ctx->tools.bw_chbwcod = mode == 1 ? chbwcod : 50;
     return AC3MI_OK;
 }
 
@@ -798,8 +753,8 @@ int ac3mi_set_encode_bandwidth(ac3mi_ctx *ctx, int mode, int chbwcod)
 // accepted and the layout's number of full-bandwidth channels (a count outside 1..5 gets 50 here rather than a division by zero)
 static int call_chbwcod(const ac3mi_ctx *ctx, const ac3mi_encode_desc *d, int nfbw)
 {
-    if (ctx->bw_mode == 1) return ctx->bw_chbwcod;
-    if (ctx->bw_mode != 2 || nfbw < 1 || nfbw > 5) return 50;
+    if (ctx->tools.bw_mode == 1) return ctx->tools.bw_chbwcod;
+    if (ctx->tools.bw_mode != 2 || nfbw < 1 || nfbw > 5) return 50;
     const long long r = d->bit_rate / nfbw;
     if (r >= 96000) return 50;
     const long long fc = r >= 80000 ? 18000 : r >= 64000 ? 16000 : r >= 48000 ? 14000 : r >= 32000 ? 11000 : 8000;
@@ -813,7 +768,7 @@ int ac3mi_set_encode_metadata(ac3mi_ctx *ctx, const ac3mi_encode_metadata *md)
 {
     if (!ctx) return AC3MI_ERR_ARG;
     if (!md) {
-        ctx->enc_bsi = ac3mi::BSI_DEFAULT;
+        ctx->tools.bsi = ac3mi::BSI_DEFAULT;
         return AC3MI_OK;
     }
     auto in = [](int v, int lo, int hi) { return v >= lo && v <= hi; };
@@ -822,22 +777,22 @@ int ac3mi_set_encode_metadata(ac3mi_ctx *ctx, const ac3mi_encode_metadata *md)
         ctx->err = "ac3mi_set_encode_metadata: field out of range";
         return AC3MI_ERR_ARG;
     }
-    ctx->enc_bsi = ac3mi::bsi_word(md->dialnorm, md->bsmod, md->cmixlev, md->surmixlev, md->dsurmod, md->copyrightb, md->origbs);
+    ctx->tools.bsi = ac3mi::bsi_word(md->dialnorm, md->bsmod, md->cmixlev, md->surmixlev, md->dsurmod, md->copyrightb, md->origbs);
     return AC3MI_OK;
 }
 
 int ac3mi_set_encode_drc(ac3mi_ctx *ctx, int profile, int32_t *d_drc_state)
 {
     if (!ctx || profile < 0 || profile > 5 || (profile != 0 && !d_drc_state)) return AC3MI_ERR_ARG;
-    ctx->drc_profile = profile;
-    ctx->drc_state = profile ? d_drc_state : nullptr;
+    ctx->tools.drc_profile = profile;
+    ctx->tools.drc_state = profile ? d_drc_state : nullptr;
     return AC3MI_OK;
 }
 
 int ac3mi_set_encode_exp_strategy(ac3mi_ctx *ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 1) return AC3MI_ERR_ARG;
-    ctx->exp_strategy = mode;
+    ctx->tools.exp_strategy = mode;
     return AC3MI_OK;
 }
 
@@ -848,15 +803,15 @@ int ac3mi_set_encode_layout(ac3mi_ctx *ctx, int mode, int acmod, int lfeon)
         ctx->err = "ac3mi_set_encode_layout: mode outside 0..2, or a mode-1 acmod / lfeon out of range";
         return AC3MI_ERR_ARG;
     }
-    ctx->layout_mode = mode;
-    ctx->layout_acmod = mode == 1 ? acmod : 0;
-    ctx->layout_lfeon = mode == 1 ? lfeon : 0;
+    ctx->tools.layout_mode = mode;
+    ctx->tools.layout_acmod = mode == 1 ? acmod : 0;
+    ctx->tools.layout_lfeon = mode == 1 ? lfeon : 0;
     return AC3MI_OK;
 }
 
 // the layout an encode call codes (ac3mi_set_encode_layout): mode 1's, or -1 for the reference's table (mode 0; mode 2 on
 // ac3mi_encode_batch, which has no source)
-static int call_acmod(const ac3mi_ctx *ctx) { return ctx->layout_mode == 1 ? ctx->layout_acmod : -1; }
+static int call_acmod(const ac3mi_ctx *ctx) { return ctx->tools.layout_mode == 1 ? ctx->tools.layout_acmod : -1; }
 
 // mode 2 on a transcode: the coded layout of the decoder's granted output flags (CHANNEL1 / CHANNEL2: 1/0, DOLBY: 2/0)
 static int granted_acmod(int out_flags)
@@ -881,6 +836,71 @@ static int tile_streams(const ac3mi_ctx *ctx, int n_streams, int frames_per_stre
     return (int)(g < 1 ? 1 : g);
 }
 
+// The context's per-stream pointers while a batch goes through in tiles: at(s0) points them at the tile's first stream s0
+// (the state slots when set, else the mix state of mix_n_out chains a stream - 0: it stays - and with `drc` the encoder's
+// DRC state); the destructor puts them back.
+struct TileState {
+    ac3mi_ctx *ctx;
+    int mix_n_out;
+    bool drc;
+    const int32_t *slots;
+    float *mix_pending;
+    int32_t *mix_flags, *drc_state;
+    TileState(ac3mi_ctx *c, int mix_n_out, bool drc)
+        : ctx(c), mix_n_out(mix_n_out), drc(drc), slots(c->slots), mix_pending(c->mix_pending), mix_flags(c->mix_flags),
+          drc_state(c->tools.drc_state) {}
+    void at(int s0)
+    {
+        if (slots) { ctx->slots = slots + s0; return; }
+        if (mix_n_out && mix_pending) {
+            ctx->mix_pending = mix_pending + (size_t)s0 * mix_n_out * 128;
+            ctx->mix_flags = mix_flags + (size_t)s0 * 6;
+        }
+        if (drc && drc_state) ctx->tools.drc_state = drc_state + s0;
+    }
+    ~TileState()
+    {
+        ctx->slots = slots;
+        ctx->mix_pending = mix_pending;
+        ctx->mix_flags = mix_flags;
+        ctx->tools.drc_state = drc_state;
+    }
+};
+
+// Grows a workspace to `need` bytes if it holds fewer; its contents are not kept.  The context's stream is synchronised
+// before the old buffer is freed.
+static int ws_grow(ac3mi_ctx *ctx, DevBuf &b, size_t need)
+{
+    if (need <= b.bytes) return AC3MI_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(b.p);
+    b.p = nullptr;
+    b.bytes = 0;
+    HIPCHK(ctx, hipMalloc(&b.p, need));
+    b.bytes = need;
+    return AC3MI_OK;
+}
+
+size_t ac3mi_workspace_bytes(const ac3mi_ctx *ctx)
+{
+    if (!ctx) return 0;
+    size_t n = 0;
+    for (const DevBuf *b : ac3mi_ctx::workspaces(ctx)) n += b->bytes;
+    return n;
+}
+
+// one workgroup per stream (decode_wg.hip)?  Its eight wavefronts cut the latency of a frame to a third and nothing but the
+// frame and the PCM touches HBM, but a workgroup's wavefronts wait for each other at the block's barriers, so the chip holds
+// fewer busy wavefronts than the other front ends.  Measured on one-frame streams to s16 (round 3, profiles/decode_ab.py;
+// fused / split front end + transform / one-kernel front end + transform): 64 streams 0.084 / 0.118 / 0.167 ms, 256: 0.086 /
+// 0.121 / 0.165, 1 024: 0.188 / 0.150 / 0.184, 2 048: 0.362 / 0.186 / 0.206, 4 096: 0.70 / 0.28 / 0.28, 65 536: 10.7 / 3.5 / 4.2.
+// auto: batches of up to 512 streams of at most four frames (round 2: 1 024, against the one-kernel front end); mode 3 forces it.
+static bool use_wg_kernel(const ac3mi_ctx *ctx, int n_streams, int frames_per_stream)
+{
+    if (ctx->decode_mode) return ctx->decode_mode == 3;
+    return n_streams <= 512 && frames_per_stream <= 4;
+}
+
 // frame-parallel front end for few long streams?  (auto: more than one frame per stream and too few streams to fill
 // the chip with one wavefront each: 256 CUs x 20 wavefronts)
 static bool use_frame_parallel(const ac3mi_ctx *ctx, int n_streams, int frames_per_stream)
@@ -903,9 +923,87 @@ static bool use_split(const ac3mi_ctx *ctx)
 // profiles/EXPERIMENTS.md): to s16 2.12 - 2.17 ms fused against 1.31 + 0.77 = 2.08 - 2.15 ms in two kernels (a wash in time,
 // 36.9 KB per frame less HBM traffic and workspace), to float 2.45 against 1.31 + 0.97 = 2.28 ms (the two kernels stay);
 // modes 4 / 5 always keep the two kernels (the bit-identity reference, A/B runs).
-static bool use_mantx(const ac3mi_ctx *ctx, int frames_per_stream, bool identity, bool s16)
+static bool use_mantx(int decode_mode, int frames_per_stream, bool identity, bool s16)
 {
-    return ((ctx->decode_mode == 0 && s16) || ctx->decode_mode == 6) && frames_per_stream == 1 && identity;
+    return ((decode_mode == 0 && s16) || decode_mode == 6) && frames_per_stream == 1 && identity;
+}
+
+// The decoder front end of a call.  `taps`: the call writes stage taps; `wg_planes`: the one-workgroup-per-stream kernel may
+// also write coefficient planes for the transform kernel (decode) - else it is taken only with the transform fused in.
+struct FrontEnd {
+    bool identity;      // every coded plane is an output plane
+    bool mixstate;      // liba52's overlap bookkeeping around frames with surround level 0 (ac3mi_set_mix_state)
+    bool wg, fused;     // decode_wg.hip; with the transform fused in (no workspace at all)
+    bool split, mantx;  // the split front end; its mantissa kernel with the transform fused in
+    bool fp;            // frame-parallel
+};
+static FrontEnd front_end(const ac3mi_ctx *ctx, const MixPlan &plan, int n_streams, int frames_per_stream, bool s16, bool taps,
+                          bool wg_planes)
+{
+    FrontEnd f;
+    f.identity = plan.n_in == plan.n_out;
+    for (int o = 0; o < plan.n_out && f.identity; o++)
+        for (int c = 0; c < plan.n_in; c++)
+            if (plan.mix[o][c] != (o == c ? 1 : 0)) f.identity = false;
+    f.mixstate = ctx->mix_pending && plan.surr_mask && !f.identity;
+    f.wg = use_wg_kernel(ctx, n_streams, frames_per_stream) && (wg_planes || f.identity);
+    f.fused = f.wg && f.identity && !taps;
+    f.split = !f.wg && use_split(ctx);
+    f.mantx = f.split && !taps && use_mantx(ctx->decode_mode, frames_per_stream, f.identity, s16);
+    f.fp = !f.wg && use_frame_parallel(ctx, n_streams, frames_per_stream);
+    return f;
+}
+
+// the decoder's workspaces for nfr frames: coefficient planes (ws_coef), block-switch flags with the per-frame "surround
+// level 0" flags after them at zs_off (ws_blksw), the frame-parallel front end's draw counts and LFSR states (ws_draws), the
+// split front end's descriptors, generator positions, coupling coordinates and row sets (ws_split)
+static size_t coef_bytes(size_t nfr, int n_in) { return nfr * 6 * n_in * 256 * sizeof(float); }
+static size_t zs_off(size_t nfr, int nfchans) { return nfr * 6 * nfchans + 4; }
+static size_t split_bytes(size_t nfr) { return nfr * (6 * 80 + 16 + 6 * 90 * 4 + 6 * 7 * 512) + 256; }
+
+static int grow_front_ws(ac3mi_ctx *ctx, const FrontEnd &fe, size_t nfr)
+{
+    if (fe.fp) TRY(ws_grow(ctx, ctx->ws_draws, nfr * 4 + nfr * 2 + 256));
+    if (fe.split) TRY(ws_grow(ctx, ctx->ws_split, split_bytes(nfr)));
+    return AC3MI_OK;
+}
+
+// The DecodeLaunch of a call: its frames, descriptor and state, and the front end's workspaces (grow_front_ws).  Coefficient
+// planes, flags, taps and a fused transform are the caller's.
+static DecodeLaunch decode_launch(const ac3mi_ctx *ctx, const FrontEnd &fe, const ac3mi_decode_desc *desc, const uint8_t *frames,
+                                  int frame_stride, int n_streams, int frames_per_stream, uint16_t *lfsr, uint32_t *status)
+{
+    const size_t nfr = (size_t)n_streams * frames_per_stream;
+    DecodeLaunch D;
+    D.frames = frames;
+    D.frame_bytes = desc->frame_bytes;
+    D.frame_stride = frame_stride;
+    D.n_streams = n_streams;
+    D.frames_per_stream = frames_per_stream;
+    D.req_flags = desc->flags;
+    D.acmod = desc->acmod;
+    D.lfeon = desc->lfeon ? 1 : 0;
+    D.dynrng_on = desc->dynrng ? 1 : 0;
+    D.level = desc->level;
+    D.coef = nullptr;
+    D.blksw = nullptr;
+    D.status = status;
+    D.lfsr = lfsr;
+    D.slot = ctx->slots;
+    D.tap_exp = nullptr;
+    D.tap_bap = nullptr;
+    D.frame_parallel = fe.fp ? 1 : 0;
+    D.frame_draws = fe.fp ? ctx->ws_draws.at<uint32_t>() : nullptr;
+    D.frame_lfsr = fe.fp ? ctx->ws_draws.at<uint16_t>(nfr * 4) : nullptr;
+    if (fe.split) {
+        uint8_t *p = ctx->ws_split.at<uint8_t>();
+        D.split = 1;
+        D.ws_desc = p;
+        D.ws_fpos = (uint32_t *)(p + nfr * 6 * 80);
+        D.ws_cplco = (float *)(p + nfr * (6 * 80 + 16));
+        D.ws_rows = p + nfr * (6 * 80 + 16 + 6 * 90 * 4);
+    }
+    return D;
 }
 
 // the encoder's workspace for `rows` channel-blocks (6 x channels per frame):
@@ -926,167 +1024,74 @@ static EncWs enc_ws_layout(size_t rows)
     return w;
 }
 
-// the block-switch decisions of `rows` channel-blocks (mode 1 only: mode 0 allocates nothing)
-static int ensure_bsw(ac3mi_ctx *ctx, size_t rows)
-{
-    if (rows <= ctx->ws_bsw_bytes) return AC3MI_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->ws_bsw);
-    ctx->ws_bsw = nullptr;
-    ctx->ws_bsw_bytes = 0;
-    HIPCHK(ctx, hipMalloc((void **)&ctx->ws_bsw, rows));
-    ctx->ws_bsw_bytes = rows;
-    return AC3MI_OK;
-}
+// the transcode's s16 PCM between the transform and the encoder (ws_tc)
+static size_t s16_ws_bytes(size_t nfr, int n_out) { return nfr * 1536 * n_out * 2 + 512; }
 
-// the rematrixing decisions of `nfr` frames, one byte per audio block (mode 1 only: mode 0 allocates nothing)
-static int ensure_remat(ac3mi_ctx *ctx, size_t nfr)
+// The encoder's part of a call of nfr frames (E.cfg set): grows the encoder's and the tools' workspaces, and fills E's
+// workspace arrays (the taps replace theirs), the tool settings and what else comes from the context.
+static int encode_setup(ac3mi_ctx *ctx, EncodeLaunch &E, const ac3mi_encode_desc *desc, size_t nfr, const ac3mi_encode_taps *taps)
 {
-    if (6 * nfr <= ctx->ws_remat_bytes) return AC3MI_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->ws_remat);
-    ctx->ws_remat = nullptr;
-    ctx->ws_remat_bytes = 0;
-    HIPCHK(ctx, hipMalloc((void **)&ctx->ws_remat, 6 * nfr));
-    ctx->ws_remat_bytes = 6 * nfr;
-    return AC3MI_OK;
-}
-
-// the DRC workspace of `nfr` frames: [nfr][6] int16 gains, then [nfr][6] codes (profile 0 allocates nothing)
-static int ensure_drc(ac3mi_ctx *ctx, size_t nfr)
-{
-    if (18 * nfr <= ctx->ws_drc_bytes) return AC3MI_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->ws_drc);
-    ctx->ws_drc = nullptr;
-    ctx->ws_drc_bytes = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->ws_drc, 18 * nfr));
-    ctx->ws_drc_bytes = 18 * nfr;
-    return AC3MI_OK;
-}
-
-// the encoder's metadata and DRC settings into a launch of frames f0.. of a DRC workspace carved for nfr frames (the state
-// pointer as the context holds it: callers offset it to their first stream when there are no slots)
-static void set_drc(const ac3mi_ctx *ctx, EncodeLaunch &E, size_t nfr, size_t f0)
-{
-    E.bsi = ctx->enc_bsi;
-    E.drc_profile = ctx->drc_profile;
-    if (!ctx->drc_profile) return;
-    E.drc_state = ctx->drc_state;
-    E.ws_drc_gain = (int16_t *)ctx->ws_drc + f0 * 6;
-    E.ws_drc_code = (uint8_t *)ctx->ws_drc + nfr * 12 + f0 * 6;
-}
-
-// the coupling workspace of `nfr` frames (mode 1 only: mode 0 allocates nothing)
-static int ensure_cpl(ac3mi_ctx *ctx, size_t nfr)
-{
-    const size_t need = nfr * ac3mi::CPL_FRAME_BYTES + 256;
-    if (need <= ctx->ws_cpl_bytes) return AC3MI_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->ws_cpl);
-    ctx->ws_cpl = nullptr;
-    ctx->ws_cpl_bytes = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->ws_cpl, need));
-    ctx->ws_cpl_bytes = need;
-    return AC3MI_OK;
-}
-
-// with rematrixing on as well (2/0): the rows before rematrixing of `nfr` frames
-static int ensure_cplr(ac3mi_ctx *ctx, size_t nfr, int nrow)
-{
-    const size_t need = nfr * ac3mi::cpl_remat_frame_bytes(nrow) + 256;
-    if (need <= ctx->ws_cplr_bytes) return AC3MI_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->ws_cplr);
-    ctx->ws_cplr = nullptr;
-    ctx->ws_cplr_bytes = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->ws_cplr, need));
-    ctx->ws_cplr_bytes = need;
-    return AC3MI_OK;
-}
-
-// the coupling arrays of frames f0.. of a workspace carved for nfr frames
-static ac3mi::CplWs cpl_at(const ac3mi::CplWs &w, size_t f0, int nrow)
-{
-    ac3mi::CplWs r = w;
-    r.word += f0; r.co += 80 * f0; r.mdct += 6 * 256 * f0; r.shift += 8 * f0;
-    r.eexp += 6 * 256 * f0; r.emask += 6 * 50 * f0; r.strat += 8 * f0; r.ebits += f0;
-    if (r.prow) {
-        r.prow += 6 * nrow * 256 * f0; r.pshift += 6 * nrow * f0; r.peexp += 6 * nrow * 256 * f0; r.pemask += 6 * nrow * 50 * f0;
-        r.pstrat += 6 * nrow * f0; r.pebits += nrow * f0;
+    const EncTools &t = ctx->tools;
+    const size_t rows = nfr * 6 * E.cfg.nch;
+    const EncWs W = enc_ws_layout(rows);
+    TRY(ws_grow(ctx, ctx->ws_enc, W.need));
+    if (t.block_switch) {
+        TRY(ws_grow(ctx, ctx->ws_bsw, rows));
+        E.ws_bsw = ctx->ws_bsw.at<uint8_t>();
     }
-    return r;
-}
-
-// workspace of the split front end for nfr frames: descriptors, generator positions, coupling coordinates, row sets
-struct SplitWs { void *desc; uint32_t *fpos; float *cplco; uint8_t *rows; };
-static size_t split_bytes(size_t nfr) { return nfr * (6 * 80 + 16 + 6 * 90 * 4 + 6 * 7 * 512) + 256; }
-static SplitWs split_ws(const ac3mi_ctx *ctx, size_t nfr, size_t f0)
-{
-    SplitWs w;
-    uint8_t *p = (uint8_t *)ctx->ws_split;
-    w.desc = p + f0 * 6 * 80;
-    p += nfr * 6 * 80;
-    w.fpos = (uint32_t *)p + f0;
-    p += nfr * 16;
-    w.cplco = (float *)p + f0 * 6 * 90;
-    p += nfr * 6 * 90 * 4;
-    w.rows = p + f0 * 6 * 7 * 512;
-    return w;
-}
-static int ensure_split(ac3mi_ctx *ctx, size_t nfr)
-{
-    const size_t need = split_bytes(nfr);
-    if (need <= ctx->ws_split_bytes) return AC3MI_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->ws_split);
-    ctx->ws_split = nullptr;
-    ctx->ws_split_bytes = 0;
-    HIPCHK(ctx, hipMalloc((void **)&ctx->ws_split, need));
-    ctx->ws_split_bytes = need;
+    if (t.rematrix) {
+        TRY(ws_grow(ctx, ctx->ws_remat, 6 * nfr));
+        E.ws_remat = ctx->ws_remat.at<uint8_t>();
+    }
+    if (t.coupling) {
+        TRY(ws_grow(ctx, ctx->ws_cpl, nfr * CPL_FRAME_BYTES + 256));
+        E.cpl_begf = t.cpl_begf;
+        E.ws_cpl = cpl_slices(ctx->ws_cpl.p, nfr);
+        if (t.rematrix && E.cfg.acmod == 2) {       // the rows before rematrixing
+            TRY(ws_grow(ctx, ctx->ws_cplr, nfr * cpl_remat_frame_bytes(E.cfg.nch) + 256));
+            cpl_remat_slices(E.ws_cpl, ctx->ws_cplr.p, nfr, E.cfg.nch);
+        }
+    }
+    E.bsi = t.bsi;
+    E.drc_profile = t.drc_profile;
+    if (t.drc_profile) {                            // [nfr][6] int16 gains, then [nfr][6] codes
+        TRY(ws_grow(ctx, ctx->ws_drc, 18 * nfr));
+        E.drc_state = t.drc_state;
+        E.ws_drc_gain = ctx->ws_drc.at<int16_t>();
+        E.ws_drc_code = ctx->ws_drc.at<uint8_t>(nfr * 12);
+    }
+    E.ws_mdct = ctx->ws_enc.at<int32_t>();
+    E.ws_expo = nullptr;                                                   // raw exponents leave the MDCT kernel only as a tap
+    E.ws_eexp = ctx->ws_enc.at<uint8_t>(W.off_eexp);
+    E.ws_emask = ctx->ws_enc.at<int16_t>(W.off_emask);
+    E.ws_shift = ctx->ws_enc.at<int8_t>(W.off_shift);
+    E.ws_strat = ctx->ws_enc.at<uint8_t>(W.off_strat);
+    E.ws_ebits = ctx->ws_enc.at<int32_t>(W.off_ebits);
+    E.ws_snr = ctx->ws_enc.at<int32_t>(W.off_snr);
+    E.ws_memo = ctx->ws_enc.at<uint32_t>(W.off_memo);
+    if (taps && taps->d_mdct) { E.ws_mdct = taps->d_mdct; E.mdct_full_rows = true; }
+    if (taps && taps->d_exponent) E.ws_expo = taps->d_exponent;
+    if (taps && taps->d_exp_samples) E.ws_shift = taps->d_exp_samples;
+    if (taps && taps->d_encoded_exp) E.ws_eexp = taps->d_encoded_exp;      // the exponent stage writes the tap directly
+    E.tap_eexp = taps ? taps->d_encoded_exp : nullptr;
+    E.tap_bap = taps ? taps->d_bap : nullptr;
+    E.tap_strat = taps ? taps->d_exp_strategy : nullptr;
+    E.tap_snr = taps ? taps->d_snroffst : nullptr;
+    E.chbwcod = call_chbwcod(ctx, desc, E.cfg.nfbw);
+    E.bw = t.bw_mode != 0;
+    E.exp_strategy = t.exp_strategy;
+    E.pack_mode = ctx->encode_mode;
+    E.slot = ctx->slots;
     return AC3MI_OK;
-}
-
-// one workgroup per stream (decode_wg.hip)?  Its eight wavefronts cut the latency of a frame to a third and nothing but the
-// frame and the PCM touches HBM, but a workgroup's wavefronts wait for each other at the block's barriers, so the chip holds
-// fewer busy wavefronts than the other front ends.  Measured on one-frame streams to s16 (round 3, profiles/decode_ab.py;
-// fused / split front end + transform / one-kernel front end + transform): 64 streams 0.084 / 0.118 / 0.167 ms, 256: 0.086 /
-// 0.121 / 0.165, 1 024: 0.188 / 0.150 / 0.184, 2 048: 0.362 / 0.186 / 0.206, 4 096: 0.70 / 0.28 / 0.28, 65 536: 10.7 / 3.5 / 4.2.
-// auto: batches of up to 512 streams of at most four frames (round 2: 1 024, against the one-kernel front end); mode 3 forces it.
-static bool use_wg_kernel(const ac3mi_ctx *ctx, int n_streams, int frames_per_stream)
-{
-    if (ctx->decode_mode) return ctx->decode_mode == 3;
-    return n_streams <= 512 && frames_per_stream <= 4;
-}
-
-static int ensure_draws(ac3mi_ctx *ctx, size_t nfr)
-{
-    const size_t need = nfr * 4 + nfr * 2 + 256;
-    if (need <= ctx->ws_draws_bytes) return AC3MI_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->ws_draws);
-    ctx->ws_draws = nullptr;
-    ctx->ws_draws_bytes = 0;
-    HIPCHK(ctx, hipMalloc((void **)&ctx->ws_draws, need));
-    ctx->ws_draws_bytes = need;
-    return AC3MI_OK;
-}
-
-size_t ac3mi_workspace_bytes(const ac3mi_ctx *ctx)
-{
-    if (!ctx) return 0;
-    return ctx->ws_coef_bytes + ctx->ws_blksw_bytes + ctx->ws_bsw_bytes + ctx->ws_remat_bytes + ctx->ws_cpl_bytes + ctx->ws_cplr_bytes + ctx->ws_enc_bytes + ctx->ws_tc_bytes + ctx->ws_draws_bytes + ctx->ws_split_bytes;
 }
 
 size_t ac3mi_transcode_workspace_plan(size_t frames, int frames_per_stream, int n_in, int nfchans, int n_out)
 {
-    // what ac3mi_transcode_batch holds for a call (or tile) of `frames` frames: coefficient planes + block-switch flags and
-    // per-frame level flags (ensure_ws), the split front end's arrays (split_bytes), the s16 PCM between transform and
-    // encoder, the encoder's arrays (enc_ws_layout) - the same expressions the call allocates with
-    // (one-frame streams without a downmix: no coefficient planes, use_mantx)
-    const size_t planes = (frames_per_stream == 1 && n_in == n_out) ? 0 : frames * 6 * (size_t)n_in * 256 * sizeof(float);
-    return planes + (frames * 6 * (size_t)nfchans + 4 + frames) + split_bytes(frames) +
-           (frames * 1536 * (size_t)n_out * 2 + 512) + enc_ws_layout(frames * 6 * (size_t)n_out).need;
+    // what ac3mi_transcode_batch grows for a call (or tile) of `frames` frames in the default decode mode, with the
+    // per-frame level flags and the split front end: the call's own expressions (n_in == n_out stands for identity routing)
+    const bool mantx = use_mantx(0, frames_per_stream, n_in == n_out, true);
+    return (mantx ? 0 : coef_bytes(frames, n_in)) + (zs_off(frames, nfchans) + frames) + split_bytes(frames) +
+           s16_ws_bytes(frames, n_out) + enc_ws_layout(frames * 6 * (size_t)n_out).need;
 }
 
 int ac3mi_xform_planes(const ac3mi_xform_desc *desc, int *n_in, int *n_out)
@@ -1165,27 +1170,6 @@ int ac3mi_decode_planes(const ac3mi_decode_desc *desc, int *n_out, int *out_flag
     return AC3MI_OK;
 }
 
-static int ensure_ws(ac3mi_ctx *ctx, size_t coef_bytes, size_t blksw_bytes)
-{
-    if (coef_bytes > ctx->ws_coef_bytes) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->ws_coef);
-        ctx->ws_coef = nullptr;
-        ctx->ws_coef_bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->ws_coef, coef_bytes));
-        ctx->ws_coef_bytes = coef_bytes;
-    }
-    if (blksw_bytes > ctx->ws_blksw_bytes) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->ws_blksw);
-        ctx->ws_blksw = nullptr;
-        ctx->ws_blksw_bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->ws_blksw, blksw_bytes));
-        ctx->ws_blksw_bytes = blksw_bytes;
-    }
-    return AC3MI_OK;
-}
-
 // d_pcm (float planes) or d_pcm16 (interleaved s16, written by the transform itself)
 static int decode_impl(ac3mi_ctx *ctx, const ac3mi_decode_desc *desc, const uint8_t *d_frames,
                        int frame_stride, int n_streams, int frames_per_stream, float *d_delay,
@@ -1209,101 +1193,63 @@ static int decode_impl(ac3mi_ctx *ctx, const ac3mi_decode_desc *desc, const uint
         return AC3MI_ERR_ARG;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    bool identity = X.plan.n_in == X.plan.n_out;
-    for (int o = 0; o < X.plan.n_out && identity; o++)
-        for (int c = 0; c < X.plan.n_in; c++)
-            if (X.plan.mix[o][c] != (o == c ? 1 : 0)) identity = false;
-    const bool wgk = use_wg_kernel(ctx, n_streams, frames_per_stream);
-    const bool fused = wgk && identity && !taps;                 // no workspace at all: nothing to tile
-    if (const int g = (taps || fused) ? 0 : tile_streams(ctx, n_streams, frames_per_stream)) {
+    const FrontEnd fe = front_end(ctx, X.plan, n_streams, frames_per_stream, d_pcm16 != nullptr, taps != nullptr, true);
+    if (const int g = (taps || fe.fused) ? 0 : tile_streams(ctx, n_streams, frames_per_stream)) {
         // bounded workspace: whole streams at a time (streams are independent; state arrays move with them)
-        const int32_t *slots0 = ctx->slots;
-        float *const mp0 = ctx->mix_pending;
-        int32_t *const mf0 = ctx->mix_flags;
+        TileState tile(ctx, n_out, false);
         int rc = AC3MI_OK;
         for (int s0 = 0; s0 < n_streams && rc == AC3MI_OK; s0 += g) {
             const int ns = n_streams - s0 < g ? n_streams - s0 : g;
             const size_t f0 = (size_t)s0 * frames_per_stream;
-            if (slots0) ctx->slots = slots0 + s0;
-            else if (mp0) { ctx->mix_pending = mp0 + (size_t)s0 * n_out * 128; ctx->mix_flags = mf0 + (size_t)s0 * 6; }
+            tile.at(s0);
             rc = decode_impl(ctx, desc, d_frames + f0 * frame_stride, frame_stride, ns, frames_per_stream,
-                             slots0 ? d_delay : d_delay + (size_t)s0 * n_out * 128, slots0 ? d_lfsr : d_lfsr + s0,
+                             tile.slots ? d_delay : d_delay + (size_t)s0 * n_out * 128, tile.slots ? d_lfsr : d_lfsr + s0,
                              d_pcm ? d_pcm + f0 * 6 * n_out * 256 : nullptr, d_pcm16 ? d_pcm16 + f0 * 6 * n_out * 256 : nullptr,
                              d_status + f0, nullptr);
         }
-        ctx->slots = slots0;
-        ctx->mix_pending = mp0;
-        ctx->mix_flags = mf0;
         return rc;
     }
     const size_t nfr = (size_t)n_streams * frames_per_stream;
     float *coef = taps && taps->d_coef ? taps->d_coef : nullptr;
     uint8_t *blksw = taps && taps->d_blksw ? taps->d_blksw : nullptr;
-    // liba52's overlap bookkeeping around frames with surround level 0: the front end tells the transform which they are
-    const bool mixstate = ctx->mix_pending && X.plan.surr_mask && !identity;
     uint8_t *zs = nullptr;
-    const bool mantx = !wgk && !taps && use_split(ctx) && use_mantx(ctx, frames_per_stream, identity, d_pcm16 != nullptr);
-    if (!fused) {
-        const size_t zs_off = blksw ? 0 : nfr * 6 * X.plan.nfchans + 4;
-        int r = ensure_ws(ctx, (coef || mantx) ? 0 : nfr * 6 * X.plan.n_in * 256 * sizeof(float), zs_off + (mixstate ? nfr : 0));
-        if (r != AC3MI_OK) return r;
-        if (mixstate) zs = ctx->ws_blksw + zs_off;
-        if (!coef) coef = ctx->ws_coef;
-        if (!blksw) blksw = ctx->ws_blksw;
+    if (!fe.fused) {
+        const size_t zs_at = blksw ? 0 : zs_off(nfr, X.plan.nfchans);
+        TRY(ws_grow(ctx, ctx->ws_coef, (coef || fe.mantx) ? 0 : coef_bytes(nfr, X.plan.n_in)));
+        TRY(ws_grow(ctx, ctx->ws_blksw, zs_at + (fe.mixstate ? nfr : 0)));
+        if (fe.mixstate) zs = ctx->ws_blksw.at<uint8_t>(zs_at);
+        if (!coef) coef = ctx->ws_coef.at<float>();
+        if (!blksw) blksw = ctx->ws_blksw.at<uint8_t>();
     }
-    X.mix_pending = mixstate ? ctx->mix_pending : nullptr;
-    X.mix_flags = mixstate ? ctx->mix_flags : nullptr;
-
-    const bool fp = !wgk && use_frame_parallel(ctx, n_streams, frames_per_stream);
-    if (fp) { const int r = ensure_draws(ctx, nfr); if (r != AC3MI_OK) return r; }
-    const bool split = !wgk && use_split(ctx);
-    if (split) { const int r = ensure_split(ctx, nfr); if (r != AC3MI_OK) return r; }
+    TRY(grow_front_ws(ctx, fe, nfr));
+    DecodeLaunch D = decode_launch(ctx, fe, desc, d_frames, frame_stride, n_streams, frames_per_stream, d_lfsr, d_status);
+    D.coef = fe.mantx ? nullptr : coef;
+    D.blksw = blksw;
+    D.zs = zs;
+    D.tap_exp = taps ? taps->d_exp : nullptr;
+    D.tap_bap = taps ? taps->d_bap : nullptr;
+    D.dyn_out = taps ? taps->d_dynrng_out : nullptr;
+    D.dyn_in = taps ? taps->d_dynrng_in : nullptr;
+    X.coef = D.coef;
+    X.blksw = blksw;
+    X.zs = zs;
+    X.mix_pending = fe.mixstate ? ctx->mix_pending : nullptr;
+    X.mix_flags = fe.mixstate ? ctx->mix_flags : nullptr;
+    X.delay = d_delay;
+    X.slot = ctx->slots;
+    X.delay_stride = 6 * 128;
+    X.pcm = d_pcm;
+    X.pcm16 = d_pcm16;
+    X.s16_flags = out_flags;
+    X.n_streams = n_streams;
+    X.frames = frames_per_stream;
+    X.bias = desc->bias;
     // One workgroup per stream, one wavefront per channel, the transform fused in when every
     // coded plane is an output plane (decode_wg.hip) - no coefficient planes in HBM.  Stage taps and mixing outputs
     // take the same front end with the planes written out, then the transform kernel.
-    if (wgk) {
-        DecodeLaunch D;
-        D.frames = d_frames;
-        D.frame_bytes = desc->frame_bytes;
-        D.frame_stride = frame_stride;
-        D.n_streams = n_streams;
-        D.frames_per_stream = frames_per_stream;
-        D.req_flags = desc->flags;
-        D.acmod = desc->acmod;
-        D.lfeon = desc->lfeon ? 1 : 0;
-        D.dynrng_on = desc->dynrng ? 1 : 0;
-        D.level = desc->level;
-        D.coef = coef;
-        D.blksw = blksw;
-        D.zs = zs;
-        D.status = d_status;
-        D.lfsr = d_lfsr;
-        D.slot = ctx->slots;
-        D.tap_exp = taps && taps->d_exp ? taps->d_exp : nullptr;
-        D.tap_bap = taps && taps->d_bap ? taps->d_bap : nullptr;
-        D.dyn_out = taps ? taps->d_dynrng_out : nullptr;
-        D.dyn_in = taps ? taps->d_dynrng_in : nullptr;
-        D.frame_parallel = 0;
-        D.frame_draws = nullptr;
-        D.frame_lfsr = nullptr;
-        X.coef = coef;
-        X.blksw = blksw;
-        X.zs = zs;
-        X.delay = d_delay;
-        X.slot = ctx->slots;
-        X.delay_stride = 6 * 128;
-        X.pcm = d_pcm;
-        X.pcm16 = d_pcm16;
-        X.s16_flags = out_flags;
-        X.n_streams = n_streams;
-        X.frames = frames_per_stream;
-        X.bias = desc->bias;
-        if (fused) {
-            HIPCHK(ctx, launch_decode_wg(ctx->tab, D, &X, 0, ctx->stream));
-            return AC3MI_OK;
-        }
-        HIPCHK(ctx, launch_decode_wg(ctx->tab, D, nullptr, 0, ctx->stream));
-        HIPCHK(ctx, launch_xform(ctx->tab, X, ctx->stream));
+    if (fe.wg) {
+        HIPCHK(ctx, launch_decode_wg(ctx->tab, D, fe.fused ? &X : nullptr, 0, ctx->stream));
+        if (!fe.fused) HIPCHK(ctx, launch_xform(ctx->tab, X, ctx->stream));
         return AC3MI_OK;
     }
     // One pass over the batch, kernels back to back on the context's stream.  Rounds 1-2 sent large batches through in two
@@ -1313,63 +1259,9 @@ static int decode_impl(ac3mi_ctx *ctx, const ac3mi_decode_desc *desc, const uint
     // (Also tried in round 3: the batch in 2 / 4 / 8 / 16 tiles, front end + transform per tile, so that a tile's coefficient
     // planes would still sit in the 256 MiB Infinity Cache when the transform reads them: 3.49 / 3.63 / 3.89 / 4.47 ms against
     // 3.48 ms in one piece - each kernel's tail costs more than the cache gives.)
-    const int n_chunks = 1;
-    const size_t F = (size_t)frames_per_stream;
-    for (int k = 0; k < n_chunks; k++) {
-        const int s0 = (int)((long long)n_streams * k / n_chunks), s1 = (int)((long long)n_streams * (k + 1) / n_chunks);
-        const int ns = s1 - s0;
-        if (ns <= 0) continue;
-        const size_t f0 = (size_t)s0 * F;
-        DecodeLaunch D;
-        D.frames = d_frames + f0 * frame_stride;
-        D.frame_bytes = desc->frame_bytes;
-        D.frame_stride = frame_stride;
-        D.n_streams = ns;
-        D.frames_per_stream = frames_per_stream;
-        D.req_flags = desc->flags;
-        D.acmod = desc->acmod;
-        D.lfeon = desc->lfeon ? 1 : 0;
-        D.dynrng_on = desc->dynrng ? 1 : 0;
-        D.level = desc->level;
-        D.coef = mantx ? nullptr : coef + f0 * 6 * X.plan.n_in * 256;
-        D.blksw = blksw + f0 * 6 * X.plan.nfchans;
-        D.zs = zs ? zs + f0 : nullptr;
-        D.status = d_status + f0;
-        D.lfsr = ctx->slots ? d_lfsr : d_lfsr + s0;
-        D.slot = ctx->slots ? ctx->slots + s0 : nullptr;
-        D.tap_exp = taps && taps->d_exp ? taps->d_exp + f0 * 6 * 7 * 256 : nullptr;
-        D.tap_bap = taps && taps->d_bap ? taps->d_bap + f0 * 6 * 7 * 256 : nullptr;
-        D.dyn_out = taps && taps->d_dynrng_out ? taps->d_dynrng_out + f0 * 12 : nullptr;
-        D.dyn_in = taps && taps->d_dynrng_in ? taps->d_dynrng_in + f0 * 12 : nullptr;
-        D.frame_parallel = fp ? 1 : 0;
-        D.frame_draws = fp ? ctx->ws_draws + f0 : nullptr;
-        D.frame_lfsr = fp ? (uint16_t *)(ctx->ws_draws + nfr) + f0 : nullptr;
-        if (split) {
-            const SplitWs w = split_ws(ctx, nfr, f0);
-            D.split = 1;
-            D.ws_desc = w.desc; D.ws_fpos = w.fpos; D.ws_cplco = w.cplco; D.ws_rows = w.rows;
-        }
-        hipStream_t xs = ctx->stream;
-        X.coef = D.coef;
-        X.blksw = D.blksw;
-        X.zs = D.zs;
-        if (mixstate && !ctx->slots) {
-            X.mix_pending = ctx->mix_pending + (size_t)s0 * X.plan.n_out * 128;
-            X.mix_flags = ctx->mix_flags + (size_t)s0 * 6;
-        }
-        X.delay = ctx->slots ? d_delay : d_delay + (size_t)s0 * X.plan.n_out * 128;
-        X.slot = D.slot;
-        X.delay_stride = 6 * 128;
-        X.pcm = d_pcm ? d_pcm + f0 * 6 * X.plan.n_out * 256 : nullptr;
-        X.pcm16 = d_pcm16 ? d_pcm16 + f0 * 6 * X.plan.n_out * 256 : nullptr;
-        X.s16_flags = out_flags;
-        X.n_streams = ns;
-        X.frames = frames_per_stream;
-        X.bias = desc->bias;
-        if (mantx) D.fuse = &X;                             // the mantissa kernel transforms too (decode_mx.hip)
-        HIPCHK(ctx, launch_decode(ctx->tab, D, ctx->stream));
-        if (!mantx) HIPCHK(ctx, launch_xform(ctx->tab, X, xs));
-    }
+    if (fe.mantx) D.fuse = &X;                              // the mantissa kernel transforms too (decode_mx.hip)
+    HIPCHK(ctx, launch_decode(ctx->tab, D, ctx->stream));
+    if (!fe.mantx) HIPCHK(ctx, launch_xform(ctx->tab, X, ctx->stream));
     return AC3MI_OK;
 }
 
@@ -1454,9 +1346,9 @@ int ac3mi_encode_batch(ac3mi_ctx *ctx, const ac3mi_encode_desc *desc, const int1
         ctx->err = "ac3mi_encode_batch: bad argument";
         return AC3MI_ERR_ARG;
     }
-    const int fb = enc_config(desc->sample_rate, desc->bit_rate, desc->channels, &E.cfg, call_acmod(ctx), ctx->layout_lfeon);
+    const int fb = enc_config(desc->sample_rate, desc->bit_rate, desc->channels, &E.cfg, call_acmod(ctx), ctx->tools.layout_lfeon);
     if (fb <= 0) {
-        ctx->err = ctx->layout_mode == 1 && ac3mi_encode_frame_bytes(desc) > 0
+        ctx->err = ctx->tools.layout_mode == 1 && ac3mi_encode_frame_bytes(desc) > 0
                        ? "ac3mi_encode_batch: channels is not nfchans(acmod) + lfeon of the layout set by ac3mi_set_encode_layout"
                        : "ac3mi_encode_batch: AC3_encode_init would return 0 for this rate/bitrate/channels";
         return AC3MI_ERR_ARG;
@@ -1473,89 +1365,26 @@ int ac3mi_encode_batch(ac3mi_ctx *ctx, const ac3mi_encode_desc *desc, const int1
         }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (const int g = taps ? 0 : tile_streams(ctx, n_streams, frames_per_stream)) {
-        const int32_t *slots0 = ctx->slots;
-        int32_t *const ds0 = ctx->drc_state;
+        TileState tile(ctx, 0, true);
         int rc = AC3MI_OK;
         for (int s0 = 0; s0 < n_streams && rc == AC3MI_OK; s0 += g) {
             const int ns = n_streams - s0 < g ? n_streams - s0 : g;
             const size_t f0 = (size_t)s0 * frames_per_stream;
-            if (slots0) ctx->slots = slots0 + s0;
-            else if (ds0) ctx->drc_state = ds0 + s0;
+            tile.at(s0);
             rc = ac3mi_encode_batch(ctx, desc, d_pcm + f0 * 1536 * E.cfg.nch, chmap,
-                                    slots0 ? d_last : d_last + (size_t)s0 * E.cfg.nch * 256, slots0 ? d_csnroffst : d_csnroffst + s0,
+                                    tile.slots ? d_last : d_last + (size_t)s0 * E.cfg.nch * 256, tile.slots ? d_csnroffst : d_csnroffst + s0,
                                     d_frames + f0 * frame_stride, frame_stride, ns, frames_per_stream, nullptr);
         }
-        ctx->slots = slots0;
-        ctx->drc_state = ds0;
         return rc;
     }
-    const size_t rows = (size_t)n_streams * frames_per_stream * 6 * E.cfg.nch;
-    const EncWs W = enc_ws_layout(rows);
-    const size_t off_eexp = W.off_eexp, off_emask = W.off_emask, off_shift = W.off_shift, off_strat = W.off_strat;
-    const size_t off_ebits = W.off_ebits, off_snr = W.off_snr, off_memo = W.off_memo, need = W.need;
-    if (need > ctx->ws_enc_bytes) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->ws_enc);
-        ctx->ws_enc = nullptr;
-        ctx->ws_enc_bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->ws_enc, need));
-        ctx->ws_enc_bytes = need;
-    }
-    if (ctx->block_switch) {
-        const int r = ensure_bsw(ctx, rows);
-        if (r != AC3MI_OK) return r;
-        E.ws_bsw = ctx->ws_bsw;
-    }
-    if (ctx->rematrix) {
-        const int r = ensure_remat(ctx, (size_t)n_streams * frames_per_stream);
-        if (r != AC3MI_OK) return r;
-        E.ws_remat = ctx->ws_remat;
-    }
-    if (ctx->coupling) {
-        const int r = ensure_cpl(ctx, (size_t)n_streams * frames_per_stream);
-        if (r != AC3MI_OK) return r;
-        E.cpl_begf = ctx->cpl_begf;
-        E.ws_cpl = ac3mi::cpl_slices(ctx->ws_cpl, (size_t)n_streams * frames_per_stream);
-        if (ctx->rematrix && E.cfg.acmod == 2) {
-            const int r2 = ensure_cplr(ctx, (size_t)n_streams * frames_per_stream, E.cfg.nch);
-            if (r2 != AC3MI_OK) return r2;
-            ac3mi::cpl_remat_slices(E.ws_cpl, ctx->ws_cplr, (size_t)n_streams * frames_per_stream, E.cfg.nch);
-        }
-    }
-    if (ctx->drc_profile) {
-        const int r = ensure_drc(ctx, (size_t)n_streams * frames_per_stream);
-        if (r != AC3MI_OK) return r;
-    }
-    set_drc(ctx, E, (size_t)n_streams * frames_per_stream, 0);
-    E.ws_mdct = (int32_t *)ctx->ws_enc;
-    E.ws_expo = nullptr;                                                   // raw exponents leave the MDCT kernel only as a tap
-    E.ws_eexp = (uint8_t *)ctx->ws_enc + off_eexp;
-    E.ws_emask = (int16_t *)((uint8_t *)ctx->ws_enc + off_emask);
-    E.ws_shift = (int8_t *)ctx->ws_enc + off_shift;
-    E.ws_strat = (uint8_t *)ctx->ws_enc + off_strat;
-    E.ws_ebits = (int32_t *)((uint8_t *)ctx->ws_enc + off_ebits);
-    E.ws_snr = (int32_t *)((uint8_t *)ctx->ws_enc + off_snr);
-    E.ws_memo = (uint32_t *)((uint8_t *)ctx->ws_enc + off_memo);
-    if (taps && taps->d_mdct) { E.ws_mdct = taps->d_mdct; E.mdct_full_rows = true; }
-    if (taps && taps->d_exponent) E.ws_expo = taps->d_exponent;
-    if (taps && taps->d_exp_samples) E.ws_shift = taps->d_exp_samples;
-    if (taps && taps->d_encoded_exp) E.ws_eexp = taps->d_encoded_exp;      // the exponent stage writes the tap directly
-    E.chbwcod = call_chbwcod(ctx, desc, E.cfg.nfbw);
-    E.bw = ctx->bw_mode != 0;
-    E.exp_strategy = ctx->exp_strategy;
+    TRY(encode_setup(ctx, E, desc, (size_t)n_streams * frames_per_stream, taps));
     E.pcm = d_pcm;
     E.last = d_last;
     E.csnr = d_csnroffst;
-    E.slot = ctx->slots;
-    E.pack_mode = ctx->encode_mode;
     E.frames = d_frames;
     E.frame_stride = frame_stride;
     E.n_streams = n_streams;
     E.frames_per_stream = frames_per_stream;
-    E.tap_eexp = taps ? taps->d_encoded_exp : nullptr;
-    E.tap_bap = taps ? taps->d_bap : nullptr;
-    E.tap_strat = taps ? taps->d_exp_strategy : nullptr;
-    E.tap_snr = taps ? taps->d_snroffst : nullptr;
     if ((E.tap_bap == nullptr) != (E.tap_eexp == nullptr)) {
         ctx->err = "ac3mi_encode_batch: d_bap and d_encoded_exp taps must be given together";
         return AC3MI_ERR_ARG;
@@ -1570,7 +1399,8 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
                           int32_t *d_csnroffst, uint8_t *d_frames_out, int out_stride, uint32_t *d_status)
 {
     if (!ctx) return AC3MI_ERR_ARG;
-    if (!dec || !enc || !d_frames_in || !d_delay || !d_lfsr || (!chmap && ctx->layout_mode != 2) || !d_last || !d_csnroffst || !d_frames_out || !d_status ||
+    const EncTools &t = ctx->tools;
+    if (!dec || !enc || !d_frames_in || !d_delay || !d_lfsr || (!chmap && t.layout_mode != 2) || !d_last || !d_csnroffst || !d_frames_out || !d_status ||
         n_streams < 0 || frames_per_stream < 0 || dec->frame_bytes < 8 || dec->frame_bytes > 3840 ||
         in_stride < ((dec->frame_bytes + 3) & ~3) || (in_stride & 3) || ((uintptr_t)d_frames_in & 3)) {
         ctx->err = "ac3mi_transcode_batch: bad argument";
@@ -1586,25 +1416,21 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         return AC3MI_ERR_ARG;
     }
     EncodeLaunch E;
-    E.pack_mode = ctx->encode_mode;
     // ac3mi_set_encode_layout: 0 the reference's table, 1 the set layout, 2 the layout the decoder granted
-    const int lay_acmod = ctx->layout_mode == 2 ? granted_acmod(out_flags) : call_acmod(ctx);
-    const int lay_lfeon = ctx->layout_mode == 2 ? ((out_flags & AC3MI_LFE) ? 1 : 0) : ctx->layout_lfeon;
+    const int lay_acmod = t.layout_mode == 2 ? granted_acmod(out_flags) : call_acmod(ctx);
+    const int lay_lfeon = t.layout_mode == 2 ? ((out_flags & AC3MI_LFE) ? 1 : 0) : t.layout_lfeon;
     const int fb = enc_config(enc->sample_rate, enc->bit_rate, enc->channels, &E.cfg, lay_acmod, lay_lfeon);
     if (fb <= 0 || enc->channels != n_out) {
         ctx->err = "ac3mi_transcode_batch: encoder configuration rejected (channels not those of the layout set by "
                    "ac3mi_set_encode_layout), or its channel count differs from the decoder's output";
         return AC3MI_ERR_ARG;
     }
-    E.chbwcod = call_chbwcod(ctx, enc, E.cfg.nfbw);     // (after enc_config: the descriptor is a valid one)
-    E.bw = ctx->bw_mode != 0;
-    E.exp_strategy = ctx->exp_strategy;
     if (out_stride < ((fb + 3) & ~3) || (out_stride & 3) || ((uintptr_t)d_frames_out & 3)) {
         ctx->err = "ac3mi_transcode_batch: out_stride must be a multiple of 4 and >= the frame size";
         return AC3MI_ERR_ARG;
     }
     uint8_t follow[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (ctx->layout_mode == 2) {
+    if (t.layout_mode == 2) {
         // the map that inverts the s16 converter's WAVE interleave: coded full-bandwidth channel k is decoded plane lfe + k,
         // the LFE (coded last) plane 0; the converter puts plane map[w] into WAVE slot w
         int map[6];
@@ -1621,76 +1447,29 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         if (E.chmap[i] >= enc->channels) { ctx->err = "ac3mi_transcode_batch: chmap entry out of range"; return AC3MI_ERR_ARG; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (const int g = tile_streams(ctx, n_streams, frames_per_stream)) {
-        const int32_t *slots0 = ctx->slots;
-        float *const mp0 = ctx->mix_pending;
-        int32_t *const mf0 = ctx->mix_flags;
-        int32_t *const ds0 = ctx->drc_state;
+        TileState tile(ctx, n_out, true);
         int rc = AC3MI_OK;
         for (int s0 = 0; s0 < n_streams && rc == AC3MI_OK; s0 += g) {
             const int ns = n_streams - s0 < g ? n_streams - s0 : g;
             const size_t f0 = (size_t)s0 * frames_per_stream;
-            if (slots0) ctx->slots = slots0 + s0;
-            else if (mp0) { ctx->mix_pending = mp0 + (size_t)s0 * n_out * 128; ctx->mix_flags = mf0 + (size_t)s0 * 6; }
-            if (!slots0 && ds0) ctx->drc_state = ds0 + s0;
+            tile.at(s0);
             rc = ac3mi_transcode_batch(ctx, dec, enc, d_frames_in + f0 * in_stride, in_stride, ns, frames_per_stream,
-                                       slots0 ? d_delay : d_delay + (size_t)s0 * n_out * 128, slots0 ? d_lfsr : d_lfsr + s0, chmap,
-                                       slots0 ? d_last : d_last + (size_t)s0 * E.cfg.nch * 256, slots0 ? d_csnroffst : d_csnroffst + s0,
+                                       tile.slots ? d_delay : d_delay + (size_t)s0 * n_out * 128, tile.slots ? d_lfsr : d_lfsr + s0, chmap,
+                                       tile.slots ? d_last : d_last + (size_t)s0 * E.cfg.nch * 256, tile.slots ? d_csnroffst : d_csnroffst + s0,
                                        d_frames_out + f0 * out_stride, out_stride, d_status + f0);
         }
-        ctx->slots = slots0;
-        ctx->mix_pending = mp0;
-        ctx->mix_flags = mf0;
-        ctx->drc_state = ds0;
         return rc;
     }
-    const size_t F = (size_t)frames_per_stream, nfr = (size_t)n_streams * F;
-    // workspaces: decoder planes, float PCM + s16 PCM, encoder arrays
-    const bool mixstate = ctx->mix_pending && X.plan.surr_mask;       // as in decode_impl
-    const size_t zs_off = nfr * 6 * X.plan.nfchans + 4;
-    bool identity = X.plan.n_in == X.plan.n_out;
-    for (int o = 0; o < X.plan.n_out && identity; o++)
-        for (int c = 0; c < X.plan.n_in; c++)
-            if (X.plan.mix[o][c] != (o == c ? 1 : 0)) identity = false;
-    const bool fused = identity && use_wg_kernel(ctx, n_streams, frames_per_stream);     // decode_wg.hip writes the s16 PCM itself
-    const bool split = !fused && use_split(ctx);
-    const bool mantx = split && use_mantx(ctx, frames_per_stream, identity, true);             // decode_mx.hip: mantissas + transform
-    { const int r = ensure_ws(ctx, mantx ? 0 : nfr * 6 * X.plan.n_in * 256 * sizeof(float), zs_off + (mixstate ? nfr : 0)); if (r != AC3MI_OK) return r; }
-    uint8_t *const zs = mixstate ? ctx->ws_blksw + zs_off : nullptr;
-    const size_t s16_bytes = nfr * 1536 * n_out * 2;       // the transform writes s16 itself: no float PCM in between
-    if (s16_bytes + 512 > ctx->ws_tc_bytes) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->ws_tc);
-        ctx->ws_tc = nullptr;
-        ctx->ws_tc_bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->ws_tc, s16_bytes + 512));
-        ctx->ws_tc_bytes = s16_bytes + 512;
-    }
-    int16_t *ws_s16 = (int16_t *)ctx->ws_tc;
-    const size_t rows = nfr * 6 * E.cfg.nch;
-    const EncWs W = enc_ws_layout(rows);
-    const size_t off_eexp = W.off_eexp, off_emask = W.off_emask, off_shift = W.off_shift, off_strat = W.off_strat;
-    const size_t off_ebits = W.off_ebits, off_snr = W.off_snr, off_memo = W.off_memo, need = W.need;
-    if (need > ctx->ws_enc_bytes) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->ws_enc);
-        ctx->ws_enc = nullptr;
-        ctx->ws_enc_bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->ws_enc, need));
-        ctx->ws_enc_bytes = need;
-    }
-    const bool fp = !fused && use_frame_parallel(ctx, n_streams, frames_per_stream);
-    if (fp) { const int r = ensure_draws(ctx, nfr); if (r != AC3MI_OK) return r; }
-    if (ctx->block_switch) { const int r = ensure_bsw(ctx, rows); if (r != AC3MI_OK) return r; }
-    if (ctx->rematrix) { const int r = ensure_remat(ctx, nfr); if (r != AC3MI_OK) return r; }
-    if (ctx->coupling) { const int r = ensure_cpl(ctx, nfr); if (r != AC3MI_OK) return r; }
-    if (ctx->drc_profile) { const int r = ensure_drc(ctx, nfr); if (r != AC3MI_OK) return r; }
-    ac3mi::CplWs cplw = ctx->coupling ? ac3mi::cpl_slices(ctx->ws_cpl, nfr) : ac3mi::CplWs{};
-    if (ctx->coupling && ctx->rematrix && E.cfg.acmod == 2) {
-        const int r = ensure_cplr(ctx, nfr, E.cfg.nch);
-        if (r != AC3MI_OK) return r;
-        ac3mi::cpl_remat_slices(cplw, ctx->ws_cplr, nfr, E.cfg.nch);
-    }
-    if (split) { const int r = ensure_split(ctx, nfr); if (r != AC3MI_OK) return r; }
+    const size_t nfr = (size_t)n_streams * frames_per_stream;
+    // workspaces: decoder planes, s16 PCM (the transform writes s16 itself: no float PCM in between), the front end's, the encoder's
+    const FrontEnd fe = front_end(ctx, X.plan, n_streams, frames_per_stream, true, false, false);   // wg: only fused (s16 PCM itself)
+    TRY(ws_grow(ctx, ctx->ws_coef, fe.mantx ? 0 : coef_bytes(nfr, X.plan.n_in)));
+    TRY(ws_grow(ctx, ctx->ws_blksw, zs_off(nfr, X.plan.nfchans) + (fe.mixstate ? nfr : 0)));
+    TRY(ws_grow(ctx, ctx->ws_tc, s16_ws_bytes(nfr, n_out)));
+    TRY(grow_front_ws(ctx, fe, nfr));
+    TRY(encode_setup(ctx, E, enc, nfr, nullptr));
+    uint8_t *const zs = fe.mixstate ? ctx->ws_blksw.at<uint8_t>(zs_off(nfr, X.plan.nfchans)) : nullptr;
+    int16_t *const ws_s16 = ctx->ws_tc.at<int16_t>();
     // Decoder front end, transform to s16, encoder: back to back on the context's stream.  (Until round 2 two chunks were
     // pipelined over two streams; profiles/transcode_overlap.py measured 12.20 ms with and 12.23 - 12.27 ms without it per
     // 65 536 cold frames, and the sum of the separate decode-to-s16 and encode calls at 12.1 - 12.2 ms: no overlap to keep.
@@ -1699,118 +1478,43 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     // decoder - 3 072 / 4 096 / 8 192 / 16 384 streams 0.561 / 0.644 / 1.265 / 2.175 ms against 0.537 / 0.639 / 1.142 / 2.110
     // in one piece: a kernel of 2 048 frames already occupies every CU (the six-wavefront-per-frame kernels) or is dispatched
     // whole before the other stream's (the others), so the chunks' latency floors add up instead of overlapping.)
-    const int n_chunks = 1;
-    auto chunk_lo = [&](int k) { return (int)((long long)n_streams * k / n_chunks); };
-    auto front = [&](int k) -> hipError_t {
-        const int s0 = chunk_lo(k), ns = chunk_lo(k + 1) - s0;
-        const size_t f0 = (size_t)s0 * F;
-        DecodeLaunch D;
-        D.frames = d_frames_in + f0 * in_stride;
-        D.frame_bytes = dd.frame_bytes;
-        D.frame_stride = in_stride;
-        D.n_streams = ns;
-        D.frames_per_stream = frames_per_stream;
-        D.req_flags = dd.flags;
-        D.acmod = dd.acmod;
-        D.lfeon = dd.lfeon ? 1 : 0;
-        D.dynrng_on = dd.dynrng ? 1 : 0;
-        D.level = dd.level;
-        D.coef = mantx ? nullptr : ctx->ws_coef + f0 * 6 * X.plan.n_in * 256;
-        D.blksw = ctx->ws_blksw + f0 * 6 * X.plan.nfchans;
-        D.zs = zs ? zs + f0 : nullptr;
-        D.status = d_status + f0;
-        D.lfsr = ctx->slots ? d_lfsr : d_lfsr + s0;
-        D.slot = ctx->slots ? ctx->slots + s0 : nullptr;
-        D.tap_exp = nullptr;
-        D.tap_bap = nullptr;
-        D.frame_parallel = fp ? 1 : 0;
-        D.frame_draws = fp ? ctx->ws_draws + f0 : nullptr;
-        D.frame_lfsr = fp ? (uint16_t *)(ctx->ws_draws + nfr) + f0 : nullptr;
-        if (split) {
-            const SplitWs w = split_ws(ctx, nfr, f0);
-            D.split = 1;
-            D.ws_desc = w.desc; D.ws_fpos = w.fpos; D.ws_cplco = w.cplco; D.ws_rows = w.rows;
-        }
-        if (fused || mantx) {
-            XformLaunch Y = X;
-            Y.coef = nullptr;
-            Y.blksw = nullptr;
-            Y.delay = ctx->slots ? d_delay : d_delay + (size_t)s0 * n_out * 128;
-            Y.slot = D.slot;
-            Y.delay_stride = 6 * 128;
-            Y.pcm = nullptr;
-            Y.pcm16 = ws_s16 + f0 * 1536 * n_out;
-            Y.s16_flags = out_flags;
-            Y.n_streams = ns;
-            Y.frames = frames_per_stream;
-            Y.bias = 384.0f;
-            if (fused) return launch_decode_wg(ctx->tab, D, &Y, 0, ctx->stream);
-            D.fuse = &Y;
-            return launch_decode(ctx->tab, D, ctx->stream);
-        }
-        return launch_decode(ctx->tab, D, ctx->stream);
-    };
-    auto middle = [&](int k, hipStream_t st) -> hipError_t {
-        const int s0 = chunk_lo(k), ns = chunk_lo(k + 1) - s0;
-        const size_t f0 = (size_t)s0 * F;
-        XformLaunch Y = X;
-        Y.coef = ctx->ws_coef + f0 * 6 * X.plan.n_in * 256;
-        Y.blksw = ctx->ws_blksw + f0 * 6 * X.plan.nfchans;
-        Y.zs = zs ? zs + f0 : nullptr;
-        if (mixstate) {
-            Y.mix_pending = ctx->slots ? ctx->mix_pending : ctx->mix_pending + (size_t)s0 * n_out * 128;
-            Y.mix_flags = ctx->slots ? ctx->mix_flags : ctx->mix_flags + (size_t)s0 * 6;
-        }
-        Y.delay = ctx->slots ? d_delay : d_delay + (size_t)s0 * n_out * 128;
-        Y.slot = ctx->slots ? ctx->slots + s0 : nullptr;
-        Y.delay_stride = 6 * 128;
-        Y.pcm = nullptr;
-        Y.pcm16 = ws_s16 + f0 * 1536 * n_out;
-        Y.s16_flags = out_flags;
-        Y.n_streams = ns;
-        Y.frames = frames_per_stream;
-        Y.bias = 384.0f;
-        return launch_xform(ctx->tab, Y, st);
-    };
-    auto back = [&](int k) -> hipError_t {
-        const int s0 = chunk_lo(k), ns = chunk_lo(k + 1) - s0;
-        const size_t f0 = (size_t)s0 * F, r0 = f0 * 6 * E.cfg.nch;
-        EncodeLaunch G = E;
-        G.ws_mdct = (int32_t *)ctx->ws_enc + r0 * 256;
-        G.ws_expo = nullptr;
-        G.ws_eexp = (uint8_t *)ctx->ws_enc + off_eexp + r0 * 256;
-        G.ws_emask = (int16_t *)((uint8_t *)ctx->ws_enc + off_emask) + r0 * 50;
-        G.ws_shift = (int8_t *)ctx->ws_enc + off_shift + r0;
-        G.ws_strat = (uint8_t *)ctx->ws_enc + off_strat + r0;
-        G.ws_ebits = (int32_t *)((uint8_t *)ctx->ws_enc + off_ebits) + f0 * E.cfg.nch;
-        G.ws_snr = (int32_t *)((uint8_t *)ctx->ws_enc + off_snr) + f0 * 2;
-        G.ws_memo = (uint32_t *)((uint8_t *)ctx->ws_enc + off_memo) + f0 * 8;
-        G.ws_bsw = ctx->block_switch ? ctx->ws_bsw + r0 : nullptr;
-        G.ws_remat = ctx->rematrix ? ctx->ws_remat + f0 * 6 : nullptr;
-        G.cpl_begf = ctx->coupling ? ctx->cpl_begf : -1;
-        G.ws_cpl = ctx->coupling ? cpl_at(cplw, f0, E.cfg.nch) : ac3mi::CplWs{};
-        set_drc(ctx, G, nfr, f0);
-        if (G.drc_state && !ctx->slots) G.drc_state += s0;
-        G.pcm = ws_s16 + f0 * 1536 * n_out;
-        G.last = ctx->slots ? d_last : d_last + (size_t)s0 * E.cfg.nch * 256;
-        G.csnr = ctx->slots ? d_csnroffst : d_csnroffst + s0;
-        G.slot = ctx->slots ? ctx->slots + s0 : nullptr;
-        G.frames = d_frames_out + f0 * out_stride;
-        G.frame_stride = out_stride;
-        G.n_streams = ns;
-        G.frames_per_stream = frames_per_stream;
-        G.tap_eexp = G.tap_bap = G.tap_strat = nullptr;
-        G.tap_snr = nullptr;
-        if (split) {                                        // block 0's descriptor of every frame carries the source's SNR offsets
-            const SplitWs w = split_ws(ctx, nfr, f0);
-            G.search_hint = reinterpret_cast<const uint32_t *>(w.desc) + 72 / 4;         // BlkDesc::src_snr (decode_common.h asserts the offset)
-            G.search_hint_stride = 6 * 80 / 4;                                           // six 80-byte descriptors per frame
-        }
-        return launch_encode(ctx->tab, G, ctx->stream);
-    };
-    HIPCHK(ctx, front(0));
-    if (!fused && !mantx) HIPCHK(ctx, middle(0, ctx->stream));
-    HIPCHK(ctx, back(0));
+    DecodeLaunch D = decode_launch(ctx, fe, &dd, d_frames_in, in_stride, n_streams, frames_per_stream, d_lfsr, d_status);
+    D.coef = fe.mantx ? nullptr : ctx->ws_coef.at<float>();
+    D.blksw = ctx->ws_blksw.at<uint8_t>();
+    D.zs = zs;
+    const bool fused = fe.fused || fe.mantx;            // the front end transforms too: no planes between the kernels
+    X.coef = fused ? nullptr : ctx->ws_coef.at<float>();
+    X.blksw = fused ? nullptr : ctx->ws_blksw.at<uint8_t>();
+    X.zs = zs;
+    X.mix_pending = fe.mixstate ? ctx->mix_pending : nullptr;
+    X.mix_flags = fe.mixstate ? ctx->mix_flags : nullptr;
+    X.delay = d_delay;
+    X.slot = ctx->slots;
+    X.delay_stride = 6 * 128;
+    X.pcm = nullptr;
+    X.pcm16 = ws_s16;
+    X.s16_flags = out_flags;
+    X.n_streams = n_streams;
+    X.frames = frames_per_stream;
+    X.bias = 384.0f;
+    if (fe.fused) HIPCHK(ctx, launch_decode_wg(ctx->tab, D, &X, 0, ctx->stream));
+    else {
+        if (fe.mantx) D.fuse = &X;
+        HIPCHK(ctx, launch_decode(ctx->tab, D, ctx->stream));
+        if (!fe.mantx) HIPCHK(ctx, launch_xform(ctx->tab, X, ctx->stream));
+    }
+    E.pcm = ws_s16;
+    E.last = d_last;
+    E.csnr = d_csnroffst;
+    E.frames = d_frames_out;
+    E.frame_stride = out_stride;
+    E.n_streams = n_streams;
+    E.frames_per_stream = frames_per_stream;
+    if (fe.split) {                                     // block 0's descriptor of every frame carries the source's SNR offsets
+        E.search_hint = reinterpret_cast<const uint32_t *>(D.ws_desc) + 72 / 4;      // BlkDesc::src_snr (decode_common.h asserts the offset)
+        E.search_hint_stride = 6 * 80 / 4;                                           // six 80-byte descriptors per frame
+    }
+    HIPCHK(ctx, launch_encode(ctx->tab, E, ctx->stream));
     return AC3MI_OK;
 }
 

@@ -552,30 +552,13 @@ int encode_group(ac3mi_pool *p, const std::vector<ac3mi_stream *> &group, int ba
             return fail(p, AC3MI_MMSYSERR_NOMEM, "copy");
         }
         ac3mi_set_state_slots(ctx, d_slots + lo);
-        const int bsw = ctx->block_switch, remat = ctx->rematrix;  // the stream layer codes long blocks only and never
-        const int cpl = ctx->coupling, bw = ctx->bw_mode;          // rematrixes, couples, band-limits or sends metadata and
-        const int drc = ctx->drc_profile;                          // dynrng of its own, and keeps the reference's exponent
-        const int xs = ctx->exp_strategy;                          // strategies and layout (no knobs of its own: a WAVE
-        const uint32_t bsi = ctx->enc_bsi;                         // format carries only a channel count)
-        const int lay = ctx->layout_mode;
-        ctx->block_switch = 0;
-        ctx->rematrix = 0;
-        ctx->coupling = 0;
-        ctx->bw_mode = 0;
-        ctx->drc_profile = 0;
-        ctx->exp_strategy = 0;
-        ctx->enc_bsi = ac3mi::BSI_DEFAULT;
-        ctx->layout_mode = 0;
+        // the stream layer codes with the reference's fixed tools: none of the encoder's own settings (a WAVE format carries
+        // only a channel count)
+        const ac3mi::EncTools tools = ctx->tools;
+        ctx->tools = ac3mi::EncTools{};
         const int rc = ac3mi_encode_batch(ctx, &d, (const int16_t *)((const uint8_t *)d_s16 + (size_t)lo * in_bytes), chmap, p->d_last, p->d_csnr,
                                           d_frames + (size_t)lo * stride, stride, kc, 1, NULL);
-        ctx->block_switch = bsw;
-        ctx->rematrix = remat;
-        ctx->coupling = cpl;
-        ctx->bw_mode = bw;
-        ctx->drc_profile = drc;
-        ctx->exp_strategy = xs;
-        ctx->enc_bsi = bsi;
-        ctx->layout_mode = lay;
+        ctx->tools = tools;
         ac3mi_set_state_slots(ctx, NULL);
         if (rc != AC3MI_OK) { (void)hipDeviceSynchronize(); return fail(p, AC3MI_MMSYSERR_NOMEM, "encode batch"); }
     }

@@ -302,6 +302,13 @@ def test_drc_with_every_tool(engine):
 
 
 def test_transcode_equals_decode_then_encode(engine):
+    """Transcode with DRC = decode, s16 conversion, encode with DRC: the same frames and final DRC state, in one piece and
+    with a tile bound of 4 frames (below S x F: tiles of one stream, each carrying its own stream's DRC state)."""
+    for tile in (None, 4):
+        _transcode_equals_decode_then_encode(engine, tile)
+
+
+def _transcode_equals_decode_then_encode(engine, tile):
     import torch
     pkg = H.pkg()
     S, F, nch = 2, 4, 2
@@ -321,8 +328,13 @@ def test_transcode_equals_decode_then_encode(engine):
         lfsr = torch.ones((S,), dtype=torch.int16, device="cuda")
         last = torch.zeros((S, 2, 256), dtype=torch.int16, device="cuda")
         csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-        out, status = engine.transcode_batch(dec, enc, frames_t, delay, lfsr, (0, 1), last, csnr)
-        engine.sync()
+        if tile:
+            engine.set_tile_frames(tile)
+        try:
+            out, status = engine.transcode_batch(dec, enc, frames_t, delay, lfsr, (0, 1), last, csnr)
+            engine.sync()
+        finally:
+            engine.set_tile_frames(131072)
         delay2 = torch.zeros((S, 2, 128), dtype=torch.float32, device="cuda")
         lfsr2 = torch.ones((S,), dtype=torch.int16, device="cuda")
         pcmf, _ = engine.decode_batch(dec, frames_t, delay2, lfsr2)
@@ -347,6 +359,25 @@ def test_transcode_equals_decode_then_encode(engine):
     for s in range(S):
         codes, snt, s_end, _ = _model(x[s], 2, 5, 27, state=100)
         assert int(st.cpu()[s]) == s_end
+
+
+def test_workspace_bytes_counts_the_drc_workspace():
+    """ac3mi_workspace_bytes includes the DRC workspace (18 bytes a frame): two fresh engines run the same encode call,
+    one with DRC profile 1 and one without, and hold exactly that much apart."""
+    import torch
+    pkg = H.pkg()
+    S, F, nch = 3, 4, 2
+    pcm = _content("music", nch, S, F, seed=5)
+    held = []
+    for drc in (0, 1):
+        eng = pkg.Engine(0)
+        try:
+            state = torch.zeros((S,), dtype=torch.int32, device="cuda")
+            _encode(eng, pcm, nch, drc=drc, state=state)
+            held.append(eng.workspace_bytes())
+        finally:
+            eng.close()
+    assert held[1] - held[0] == 18 * S * F, held
 
 
 def test_decoded_gain_follows_the_model(engine):

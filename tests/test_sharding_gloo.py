@@ -89,3 +89,22 @@ def test_rank_plan_fits_hbm():
     one = sh.plan_transcode_bytes(65536, frames_per_stream=1)["workspace"]
     two = sh.plan_transcode_bytes(32768, frames_per_stream=2)["workspace"]
     assert two - one == 65536 * 6 * 6 * 256 * 4
+
+
+@pytest.mark.parametrize("args, want", [
+    ((131072, 1, 6, 5, 6), 13_372_360_452),
+    ((131072, 4, 6, 5, 6), 18_204_198_660),
+    ((4096, 1, 2, 2, 2), 205_281_028),
+    ((6000, 3, 6, 5, 2), 521_998_484),
+    ((100, 1, 6, 5, 2), 8_702_880),
+    ((7, 2, 3, 2, 2), 484_095),
+])
+def test_transcode_workspace_plan_is_pinned(args, want):
+    """ac3mi_transcode_workspace_plan(frames, frames_per_stream, n_in, nfchans, n_out), no GPU: the bytes the transcode's
+    allocation expressions give, pinned - with and without coefficient planes, several frames a stream, a downmix."""
+    import ctypes
+    lib = H.pkg().load_library()
+    f = lib.ac3mi_transcode_workspace_plan
+    f.restype = ctypes.c_size_t
+    f.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    assert f(*args) == want
