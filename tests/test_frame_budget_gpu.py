@@ -1,0 +1,385 @@
+"""GPU: the bit budget of every encoder tool, audited with the independent frame reader (tests/ac3_syntax.py).
+
+With a tool on there is no oracle encoder; what the tool tests pin (side information against the numpy models, CRCs, clean
+decodes, decoder parity, quality floors) does not notice a search that counts bits wrongly on the safe side, nor a bap tap
+that disagrees with a decoder's re-derivation.  `audit` asserts for every frame of the matrix below:
+
+1. syntax: the reader reaches the end of block 5 inside the frame, every bit from there to auxdatae is zero, the parsed
+   csnroffst / fsnroffst equal the `snroffst` tap and are the same in every row (coupling channel and LFE included);
+2. accounting: spent bits + 18 <= 8 frame_bytes + c, c = the rematrixing flag bits of block 0 in a frame with acmod 2 (the
+   reference prices rematstr as one bit per block and never the flags: 4 bits without coupling, 2 / 3 / 4 by the coupling
+   start with it, the same with an LFE) and 0 elsewhere;
+3. search: the reference's loop (ENC/ac3enc.cpp:921-967, profiles/search_sim.Search) replayed on the reader's spare-bit
+   curve from the carried start value does not fail and ends exactly at the coded offsets; before that, separately: the
+   coded offset fits, fsnroffst + 1 does not (unless 15), csnroffst + 1 at fsnroffst 0 does not (unless 63);
+4. allocation: the reader's bap and exponents equal the `bap` and `encoded_exp` taps on every coded bin of every row the
+   taps expose;
+5. packers and call shapes: pack modes 1 and 2, and one call against split calls with carried state, give the same bytes.
+Failures are collected over a whole configuration list and reported together, by kind.  Every comparison is an integer
+equality; nothing here measures time."""
+import itertools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from tests import _harness as H
+from tests import ac3_syntax as A
+from tests import layout_model as M
+from tests.test_coupling_gpu import _content
+from tests.test_drc_gpu import _programme
+from tests.test_layout_gpu import _encode, _transcode, _with_lfe
+
+sys.path.insert(0, os.path.join(H.ROOT, "profiles"))
+import search_sim                                       # noqa: E402
+
+gpu = pytest.mark.gpu
+
+# per channel count: a rate at which the plain encoder's search stays far below csnroffst 63 on the matrix's content, and a
+# generous one; at neither does it fail (tests/test_ac3_syntax_cpu.py::test_matrix_rates_do_not_starve_the_plain_encoder).
+RATES = {1: (64000, 192000), 2: (96000, 256000), 3: (128000, 320000), 4: (160000, 384000), 5: (192000, 448000),
+         6: (224000, 448000)}
+# Exponent-strategy mode 1 has no budget term (test_exponent_strategies_overrun_small_frames states what it
+# does at the rates above): without coupling its partitions can fill a 96 kb/s 2/0 or a 224 kb/s 5.1 frame with exponents, the
+# search fails and the audit does not apply.  Tool sets that hold it therefore take these lower rates of 2 and 6 channels;
+# every set without it, the sixteen layouts, the coupled 2/0 cases and the large batch (all with it) keep the rates above.
+XS_LOW = {2: 160000, 6: 320000}
+
+
+def matrix_rate(nch, hi, names):
+    return XS_LOW[nch] if hi == 0 and "xs" in names and nch in XS_LOW else RATES[nch][hi]
+
+
+META = dict(dialnorm=24, bsmod=2, cmixlev=0, surmixlev=2, dsurmod=1, copyrightb=0, origbs=0)
+TOOLS = {"bsw": dict(bsw=1), "remat": dict(remat=1), "cpl": dict(cpl=2), "bw": dict(bw=(2, 0)), "drc": dict(md=META, drc=1),
+         "xs": dict(xs=1)}
+APPLIES = {"remat": lambda nch: nch == 2, "cpl": lambda nch: nch >= 2}
+F = 3
+
+
+def tool_sets(nch):
+    """every tool alone, every pair, all together - of the tools that apply to the channel count"""
+    names = [t for t in TOOLS if APPLIES.get(t, lambda n: True)(nch)]
+    sets = [(t,) for t in names] + list(itertools.combinations(names, 2)) + [tuple(names)]
+    return sets
+
+
+def settings(names):
+    kw = {}
+    for t in names:
+        kw.update(TOOLS[t])
+    return kw
+
+
+def matrix_content(nch, frames=F):
+    """[6][frames * 1536][nch]: the harness's music, bursts and strobe, the coupling tests' music, attack and identical"""
+    a = [H.gen_pcm(frames, nch, seed=700 + i, kind=k) for i, k in enumerate(("music", "bursts", "strobe"))]
+    b = [_content(k, nch, 1, frames, seed=710 + i)[0] for i, k in enumerate(("music", "attack", "identical"))]
+    return np.stack(a + b)
+
+
+class Report:
+    def __init__(self):
+        self.fails = []
+        self.n = dict(frames=0, coupled=0, remat_bands=0, short_blocks=0, dynrng=0, dynrng2=0, configs=0, offsets_costed=0)
+
+    def fail(self, kind, where, msg):
+        self.fails.append("%s | %s | %s" % (kind, where, msg))
+
+    def finish(self, title):
+        print("%s: %d configurations, %d frames audited, %d coupled frames, %d flagged rematrix bands, %d short blocks, "
+              "%d dynrng and %d dynrng2 words, %d offsets costed by the reader" % (
+                  title, self.n["configs"], self.n["frames"], self.n["coupled"], self.n["remat_bands"], self.n["short_blocks"],
+                  self.n["dynrng"], self.n["dynrng2"], self.n["offsets_costed"]))
+        kinds = {}
+        for f in self.fails:
+            kinds[f.split(" | ")[0]] = kinds.get(f.split(" | ")[0], 0) + 1
+        assert not self.fails, "%d failures %r, the first 25:\n%s" % (len(self.fails), kinds, "\n".join(self.fails[:25]))
+
+
+def audit(rep, frames, taps, start, label):
+    """frames [S][F][fb], taps of the same call (None: a transcode, which has none), start [S] = the csnroffst state that
+    entered the call"""
+    S, nfr, fb = frames.shape
+    for s in range(S):
+        c0 = int(start[s]) & 0xff
+        for f in range(nfr):
+            where = "%s stream %d frame %d" % (label, s, f)
+            rep.n["frames"] += 1
+            try:
+                P = A.parse_frame(frames[s, f])
+            except A.SyntaxError_ as e:
+                rep.fail("syntax", where, str(e))
+                break
+            # 1. syntax
+            if P.frame_bytes != fb or P.blocks[5].end > 8 * fb:
+                rep.fail("syntax", where, "block 5 ends at bit %d of %d" % (P.blocks[5].end, 8 * fb))
+            if not A.tail_is_zero(P):
+                rep.fail("syntax", where, "non-zero bits between block 5's end (%d) and auxdatae" % P.blocks[5].end)
+            cs = {B.csnroffst for B in P.blocks}
+            fs = set().union(*(set(B.fsnroffst.values()) for B in P.blocks))
+            if len(cs) != 1 or len(fs) != 1:
+                rep.fail("syntax", where, "offsets differ between rows or blocks: csnroffst %r fsnroffst %r" % (cs, fs))
+                break
+            coded = (cs.pop(), fs.pop())
+            if taps is not None and coded != tuple(int(v) for v in taps["snroffst"][s, f]):
+                rep.fail("syntax", where, "header offsets %r, snroffst tap %r" % (coded, taps["snroffst"][s, f].tolist()))
+            # 2. accounting
+            c = A.uncounted_bits(P)
+            g = 16 * coded[0] + coded[1]
+            curve = A.SpareCurve(P, c)
+            if A.spent_bits(P, g) != P.blocks[5].end:
+                rep.fail("reader", where, "recount at the coded offset %d, parsed end %d" % (A.spent_bits(P, g), P.blocks[5].end))
+            if curve[g] < 0:
+                rep.fail("accounting", where, "spent %d + 18 > %d + %d" % (A.spent_bits(P, g), 8 * fb, c))
+            # 3. search: the path-independent end conditions, then the replay
+            if coded[1] < 15 and curve[g + 1] >= 0:
+                rep.fail("search", where, "fsnroffst %d + 1 would fit with %d bits to spare (coded: %d to spare)" % (coded[1], curve[g + 1], curve[g]))
+            if coded[0] < 63 and curve[16 * (coded[0] + 1)] >= 0:
+                rep.fail("search", where, "csnroffst %d + 1 would fit with %d bits to spare" % (coded[0], curve[16 * (coded[0] + 1)]))
+            ss = search_sim.Search(c0)
+            while True:
+                q = ss.next()
+                if q is None:
+                    break
+                ss.consume(curve[16 * q[0] + q[1]] >= 0)
+            if ss.failed:
+                rep.fail("failed-search", where, "the reference's search fails from start %d: the audit does not apply" % c0)
+            elif (ss.c, ss.f) != coded:
+                rep.fail("search", where, "replay from %d ends at %r, coded %r (spare there %d, at the replay's %d)" % (
+                    c0, (ss.c, ss.f), coded, curve[g], curve[16 * ss.c + ss.f]))
+            c0 = coded[0]
+            rep.n["offsets_costed"] += len(P._spent)
+            # 4. allocation
+            for b, B in enumerate(P.blocks):
+                if taps is not None:
+                    for k, r in enumerate(P.rows()):
+                        lo, hi = B.rng[r]
+                        if not np.array_equal(taps["bap"][s, f, b, k, lo:hi], B.bap[r, lo:hi]):
+                            bad = np.nonzero(taps["bap"][s, f, b, k, lo:hi] != B.bap[r, lo:hi])[0]
+                            rep.fail("bap", where, "block %d row %d: %d bins of [%d, %d), first %d: tap %d reader %d" % (
+                                b, r, bad.size, lo, hi, lo + bad[0], taps["bap"][s, f, b, k, lo + bad[0]], B.bap[r, lo + bad[0]]))
+                        if not np.array_equal(taps["encoded_exp"][s, f, b, k, lo:hi], B.exp[r, lo:hi]):
+                            bad = np.nonzero(taps["encoded_exp"][s, f, b, k, lo:hi] != B.exp[r, lo:hi])[0]
+                            rep.fail("exp", where, "block %d row %d: %d bins of [%d, %d), first %d" % (b, r, bad.size, lo, hi, lo + bad[0]))
+                rep.n["short_blocks"] += sum(B.fields["blksw%d" % ch] for ch in range(P.nfchans))
+                rep.n["remat_bands"] += sum(v for k, v in B.fields.items() if k.startswith("rematflg"))
+                rep.n["dynrng"] += B.fields["dynrnge"]
+                rep.n["dynrng2"] += B.fields.get("dynrng2e", 0)
+            rep.n["coupled"] += P.blocks[0].cplinu
+
+
+def run_config(engine, rep, pcm, label, layout=None, rate=None, sr=48000, chmap=None, **kw):
+    """One configuration: encode with taps, audit (items 1-4), then item 5."""
+    import torch
+    S, n, nch = pcm.shape
+    nfr = n // 1536
+    drc = bool(kw.get("drc"))
+    if chmap is None and layout is None and nch == 6:
+        chmap = H.CHMAP6
+
+    def fresh():
+        return dict(last=torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda"),
+                    csnr=torch.full((S,), 40, dtype=torch.int32, device="cuda"),
+                    state=torch.zeros((S,), dtype=torch.int32, device="cuda") if drc else None)
+
+    rep.n["configs"] += 1
+    common = dict(layout=layout, rate=rate, sr=sr, chmap=chmap, **kw)
+    frames, taps = _encode(engine, pcm, taps=True, **fresh(), **common)
+    audit(rep, frames, taps, np.full(S, 40), label)
+    for pack in (1, 2):
+        engine.set_encode_mode(pack)
+        try:
+            got = _encode(engine, pcm, **fresh(), **common)
+        finally:
+            engine.set_encode_mode(0)
+        if not np.array_equal(got, frames):
+            rep.fail("packers", label, "pack mode %d differs in %d frames" % (pack, int((got != frames).any(axis=2).sum())))
+    st = fresh()
+    parts = [_encode(engine, pcm[:, :1536], **st, **common), _encode(engine, pcm[:, 1536:], **st, **common)] if nfr > 1 else []
+    if parts and not np.array_equal(np.concatenate(parts, 1), frames):
+        rep.fail("call-shape", label, "1 + %d frames with carried state differ in %d frames" % (
+            nfr - 1, int((np.concatenate(parts, 1) != frames).any(axis=2).sum())))
+    return frames
+
+
+@gpu
+@pytest.mark.parametrize("sr", [48000, 44100])
+@pytest.mark.parametrize("hi", [0, 1])
+@pytest.mark.parametrize("nch", [1, 2, 6])
+def test_tools_alone_in_pairs_and_together(engine, nch, hi, sr):
+    rep = Report()
+    pcm = matrix_content(nch)
+    for names in tool_sets(nch):
+        rate = matrix_rate(nch, hi, names)
+        run_config(engine, rep, pcm, "%dch %d b/s %d Hz %s" % (nch, rate, sr, "+".join(names)), rate=rate, sr=sr, **settings(names))
+    rep.finish("tools, %d channels at %d b/s, %d Hz" % (nch, RATES[nch][hi], sr))
+    assert rep.n["frames"] == len(tool_sets(nch)) * 6 * F
+    assert rep.n["short_blocks"] > 0 and rep.n["dynrng"] > 0
+    assert (rep.n["coupled"] > 0) == (nch >= 2) and (rep.n["remat_bands"] > 0) == (nch == 2), rep.n
+
+
+@gpu
+@pytest.mark.parametrize("hi", [0, 1])
+@pytest.mark.parametrize("acmod,lfeon", M.layouts())
+def test_every_layout_with_all_tools(engine, acmod, lfeon, hi):
+    """layout mode 1 with everything on: dual mono has DRC (dynrng2), 2/0+LFE rematrixing and coupling"""
+    rep = Report()
+    nch = M.channels(acmod, lfeon)
+    pcm = matrix_content(nch)
+    kw = settings(TOOLS)
+    run_config(engine, rep, pcm, "layout %d/%d all tools" % (acmod, lfeon), layout=(1, acmod, lfeon), rate=RATES[nch][hi], **kw)
+    rep.finish("layout acmod %d lfeon %d at %d b/s" % (acmod, lfeon, RATES[nch][hi]))
+    assert rep.n["frames"] == 6 * F and rep.n["dynrng"] > 0 and (rep.n["dynrng2"] > 0) == (acmod == 0)
+    assert (rep.n["remat_bands"] > 0) == (acmod == 2)
+    assert (rep.n["coupled"] > 0) == (acmod >= 2), rep.n
+
+
+@gpu
+@pytest.mark.parametrize("nch", [2, 6])
+@pytest.mark.parametrize("begf", [0, 5])
+def test_exponent_strategies_with_coupling(engine, nch, begf):
+    rep = Report()
+    pcm = matrix_content(nch)
+    for hi in (0, 1):
+        for extra in (dict(), dict(remat=1) if nch == 2 else dict(bsw=1)):
+            run_config(engine, rep, pcm, "%dch xs + cpl begf %d %r" % (nch, begf, extra), rate=matrix_rate(nch, hi, ("xs",) if nch == 6 else ()), xs=1, cpl=begf, **extra)
+    rep.finish("exponent strategies + coupling at begf %d, %d channels" % (begf, nch))
+    assert rep.n["frames"] == 4 * 6 * F and rep.n["coupled"] > 0
+
+
+@gpu
+@pytest.mark.parametrize("nch", [1, 2, 6])
+@pytest.mark.parametrize("profile", [1, 3])
+def test_drc_programme(engine, nch, profile):
+    """twelve frames from -60 dBFS to -5 dBFS and silence: some blocks send a word and some do not"""
+    rep = Report()
+    pcm = _programme(nch, seed=11 + nch)
+    for hi in (0, 1):
+        run_config(engine, rep, pcm, "%dch drc %d" % (nch, profile), rate=RATES[nch][hi], md=META, drc=profile)
+    if nch == 2:
+        run_config(engine, rep, pcm, "dual mono drc %d" % profile, layout=(1, 0, 0), rate=RATES[2][1], drc=profile)
+    rep.finish("DRC profile %d, %d channels" % (profile, nch))
+    assert rep.n["frames"] == (3 if nch == 2 else 2) * 12
+    assert rep.n["frames"] < rep.n["dynrng"] < rep.n["frames"] * 6, rep.n
+    assert (12 < rep.n["dynrng2"] < 72) if nch == 2 else rep.n["dynrng2"] == 0, rep.n
+
+
+@gpu
+def test_transcode_follows_a_20_lfe_source(engine):
+    """layout mode 2: a 2/0+LFE source re-encoded as 2/0+LFE with rematrixing, coupling, block switching, bandwidth and
+    exponent strategies, metadata and DRC on (no taps in a transcode: items 1-3 and the packers)"""
+    import torch
+    rep = Report()
+    p3 = _with_lfe(matrix_content(2), 43)
+    src = _encode(engine, p3, layout=(1, 2, 1), rate=256000)
+    outs = []
+    for pack in (0, 1, 2):
+        state = torch.zeros((src.shape[0],), dtype=torch.int32, device="cuda")
+        engine.set_encode_mode(pack)
+        engine.set_encode_layout(2)
+        engine.set_encode_rematrix(1)
+        engine.set_encode_coupling(1, 1)
+        engine.set_encode_block_switch(1)
+        engine.set_encode_bandwidth(2, 0)
+        engine.set_encode_exp_strategy(1)
+        engine.set_encode_metadata(**META)
+        engine.set_encode_drc(1, state)
+        try:
+            out, oflags = _transcode(engine, src, 2, 1, 2 | 16, None, rate=192000)
+        finally:
+            engine.set_encode_mode(0)
+            engine.set_encode_layout(0)
+            engine.set_encode_rematrix(0)
+            engine.set_encode_coupling(0, 0)
+            engine.set_encode_block_switch(0)
+            engine.set_encode_bandwidth(0)
+            engine.set_encode_exp_strategy(0)
+            engine.set_encode_metadata()
+            engine.set_encode_drc(0)
+        outs.append(out)
+    out = outs[0]
+    for pack in (1, 2):
+        if not np.array_equal(outs[pack], out):
+            rep.fail("packers", "transcode 2/0+LFE", "pack mode %d differs" % pack)
+    assert oflags == 2 | 16 and (out[:, :, 6] >> 5 == 2).all()
+    rep.n["configs"] += 1
+    audit(rep, out, None, np.full(out.shape[0], 40), "transcode 2/0+LFE")
+    rep.finish("transcode, layout mode 2, 2/0+LFE")
+    assert rep.n["frames"] == 6 * F and rep.n["coupled"] > 0 and rep.n["remat_bands"] > 0 and rep.n["dynrng"] > 0
+
+
+@gpu
+def test_large_batch(engine):
+    """4 096 three-frame stereo streams (above the 2 048 streams at which the searches change shape), replicas of the six
+    matrix programmes, all tools on: a seeded sample holding every programme is audited in full, every other stream must
+    be byte-identical to the sample's replica of its programme."""
+    import torch
+    rep = Report()
+    S = 4096
+    pool = matrix_content(2)
+    rng = np.random.default_rng(2048)
+    idx = rng.integers(0, len(pool), S)
+    sample = np.concatenate([np.array([np.nonzero(idx == k)[0][0] for k in range(len(pool))]), rng.integers(0, S, 18)])
+    kw = settings(TOOLS)
+    csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
+    frames, taps = _encode(engine, pool[idx], rate=RATES[2][0], taps=True, csnr=csnr, **kw)
+    rep.n["configs"] += 1
+    audit(rep, frames[sample], {k: v[sample] for k, v in taps.items()}, np.full(len(sample), 40), "large batch")
+    first = {int(idx[s]): s for s in sample[::-1]}
+    for s in range(S):
+        if not np.array_equal(frames[s], frames[first[int(idx[s])]]):
+            rep.fail("replica", "large batch stream %d" % s, "differs from stream %d of the same programme" % first[int(idx[s])])
+    for pack in (1, 2):
+        engine.set_encode_mode(pack)
+        try:
+            got = _encode(engine, pool[idx], rate=RATES[2][0], **kw)
+        finally:
+            engine.set_encode_mode(0)
+        if not np.array_equal(got, frames):
+            rep.fail("packers", "large batch", "pack mode %d differs in %d frames" % (pack, int((got != frames).any(axis=2).sum())))
+    small = _encode(engine, pool, rate=RATES[2][0], **kw)
+    if not np.array_equal(small, frames[[first[k] for k in range(len(pool))]]):
+        rep.fail("call-shape", "large batch", "a six-stream call gives other bytes")
+    rep.finish("large batch, %d streams" % S)
+    assert rep.n["frames"] == len(sample) * F and rep.n["coupled"] > 0 and rep.n["remat_bands"] > 0 and rep.n["short_blocks"] > 0
+
+
+@gpu
+@pytest.mark.parametrize("nch", [2, 6])
+def test_exponent_strategies_overrun_small_frames(engine, nch):
+    """A known defect, stated so that the matrix is not silently shaped by it: exponent-strategy mode 1
+    prices exponent error against exponent bits and never against the frame.  On the first frame of the `identical`
+    programme at 96 kb/s 2/0 (224 kb/s 5.1) its partition's exponent sets alone take more than 95 % of the frame, where mode
+    0's take under 65 %: the search fails from any start (the `snroffst` tap keeps the start value 40, 0, as in the
+    reference's failed-search path), the frame does not parse, and the plain encoder codes the same input without trouble.
+    When the mode gets a cap on its exponent bits this test is to be replaced by that rate in the matrix."""
+    pcm = matrix_content(nch)[5:6]
+    rate = RATES[nch][0]
+    chmap = H.CHMAP6 if nch == 6 else None
+    f0, t0 = _encode(engine, pcm, rate=rate, taps=True, chmap=chmap)
+    f1, t1 = _encode(engine, pcm, rate=rate, taps=True, chmap=chmap, xs=1)
+    nfbw = min(nch, 5)
+
+    def exponent_bits(t):
+        tot = 0
+        for b in range(6):
+            for ch in range(nfbw):
+                k = int(t["exp_strategy"][0, 0, b, ch])
+                if k:
+                    gs = 3 << (k - 1)
+                    tot += 4 + 7 * ((223 + gs - 4) // gs) + 2 + 6
+            if nch == 6 and t["exp_strategy"][0, 0, b, 5]:
+                tot += 4 + 14
+        return tot
+
+    bits = 8 * f0.shape[2]
+    rep = Report()
+    audit(rep, f0, t0, [40], "mode 0")
+    rep.finish("mode 0 on the programme that starves mode 1, %d channels" % nch)
+    print("exponent bits of frame 0: mode 0 %d, mode 1 %d of %d" % (exponent_bits(t0), exponent_bits(t1), bits))
+    assert 100 * exponent_bits(t0) < 65 * bits and 100 * exponent_bits(t1) > 95 * bits
+    assert tuple(t1["snroffst"][0, 0]) == (40, 0) and tuple(t0["snroffst"][0, 0]) != (40, 0)
+    with pytest.raises(A.SyntaxError_):
+        A.parse_frame(f1[0, 0])
