@@ -126,12 +126,27 @@ struct DecodeLaunch {
     // split front end, one-frame streams, identity routing: mantissas + transform in one kernel (decode_mx.hip) - no
     // coefficient planes in HBM (coef unused), the caller does not launch the transform
     const XformLaunch *fuse = nullptr;
+    // ac3mi_set_decode_crc 1 / 2: the CRC kernel's verdict byte per frame, [S][F] (crc.hip); null: the frames are not checked
+    const uint8_t *crc = nullptr;
 };
 hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStream_t stream);
 // decode_wg.hip: one workgroup per stream; X == nullptr: coefficient planes (+ taps) to HBM as launch_decode does;
 // else the transform is fused in (identity routing only: returns hipErrorInvalidValue for a mixing plan)
 hipError_t launch_decode_wg(const DeviceTables &tab, const DecodeLaunch &L, const XformLaunch *X, int grid_cap, hipStream_t stream);
 void build_dec_tables(DecTables *t, uint16_t *lfsr_seq /*[65535]*/, uint16_t *lfsr_idx /*[65536]*/);
+
+// crc.hip: one wavefront per frame sums the frame's two CRC regions; verdict[i]: bit 0 crc1's region fails, bit 1 crc2's,
+// bit 6 (with `conceal`, when either fails) the front end is to refuse the frame, bit 7 not summed - the header test on bytes
+// 0-5 failed, the frame is longer than frame_bytes, or (acmod >= 0) its acmod / lfeon are not these
+struct CrcLaunch {
+    const uint8_t *frames;
+    uint8_t *verdict;
+    size_t n_frames;
+    int frame_stride, frame_bytes;
+    int acmod = -1, lfeon = 0;
+    bool conceal = false;
+};
+hipError_t launch_crc(const CrcLaunch &L, hipStream_t stream);
 
 // ac3mi_set_encode_coupling 1: what the coupling kernel leaves per frame for the search and the packer
 struct CplWs {
@@ -269,11 +284,12 @@ struct ac3mi_ctx {
     ac3mi::DevBuf ws_cpl;   // coupling's per-frame workspace (ac3mi::CplWs, CPL_FRAME_BYTES a frame)
     ac3mi::DevBuf ws_cplr;  // with rematrixing on as well: cpl_remat_frame_bytes a frame
     ac3mi::DevBuf ws_drc;   // DRC gains and codes between the DRC kernels, the search and the packers, 3 bytes a frame-block
+    ac3mi::DevBuf ws_crc;   // decode with ac3mi_set_decode_crc on: the CRC kernel's verdicts for the front end, one byte per frame
     // every workspace above (ac3mi_destroy frees them, ac3mi_workspace_bytes sums them)
     template <class Ctx> static auto workspaces(Ctx *c)
     {
         return std::array{&c->ws_coef, &c->ws_blksw, &c->ws_draws, &c->ws_split, &c->ws_enc, &c->ws_tc,
-                          &c->ws_bsw, &c->ws_remat, &c->ws_cpl, &c->ws_cplr, &c->ws_drc};
+                          &c->ws_bsw, &c->ws_remat, &c->ws_cpl, &c->ws_cplr, &c->ws_drc, &c->ws_crc};
     }
     // optional state-slot indirection for the next batch calls (ac3mi_set_state_slots)
     const int32_t *slots = nullptr;
@@ -282,5 +298,6 @@ struct ac3mi_ctx {
     int32_t *mix_flags = nullptr;
     long long tile_frames = 131072;    // workspace bound: batches above this many frames go through in tiles of whole streams (0 = never)
     int decode_mode = 0;    // ac3mi_set_decode_mode
+    int decode_crc = 0;     // ac3mi_set_decode_crc
     std::string err;
 };

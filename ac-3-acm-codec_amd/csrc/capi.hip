@@ -712,6 +712,13 @@ int ac3mi_set_decode_mode(ac3mi_ctx *ctx, int mode)
     return AC3MI_OK;
 }
 
+int ac3mi_set_decode_crc(ac3mi_ctx *ctx, int mode)
+{
+    if (!ctx || mode < 0 || mode > 2) return AC3MI_ERR_ARG;
+    ctx->decode_crc = mode;
+    return AC3MI_OK;
+}
+
 int ac3mi_set_encode_mode(ac3mi_ctx *ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 2) return AC3MI_ERR_ARG;
@@ -968,6 +975,28 @@ static int grow_front_ws(ac3mi_ctx *ctx, const FrontEnd &fe, size_t nfr)
     return AC3MI_OK;
 }
 
+// ac3mi_set_decode_crc 1 / 2: the CRC kernel over the nfr frames of a call (or tile), ahead of its front end; *verdict is
+// the array the front end reads (null in mode 0: nothing is launched)
+static int crc_pass(ac3mi_ctx *ctx, const ac3mi_decode_desc *desc, const uint8_t *frames, int frame_stride, size_t nfr,
+                    const uint8_t **verdict)
+{
+    *verdict = nullptr;
+    if (!ctx->decode_crc || !nfr) return AC3MI_OK;
+    TRY(ws_grow(ctx, ctx->ws_crc, nfr));
+    CrcLaunch C;
+    C.frames = frames;
+    C.verdict = ctx->ws_crc.at<uint8_t>();
+    C.n_frames = nfr;
+    C.frame_stride = frame_stride;
+    C.frame_bytes = desc->frame_bytes;
+    C.acmod = desc->acmod;
+    C.lfeon = desc->lfeon ? 1 : 0;
+    C.conceal = ctx->decode_crc == 2;
+    HIPCHK(ctx, launch_crc(C, ctx->stream));
+    *verdict = C.verdict;
+    return AC3MI_OK;
+}
+
 // The DecodeLaunch of a call: its frames, descriptor and state, and the front end's workspaces (grow_front_ws).  Coefficient
 // planes, flags, taps and a fused transform are the caller's.
 static DecodeLaunch decode_launch(const ac3mi_ctx *ctx, const FrontEnd &fe, const ac3mi_decode_desc *desc, const uint8_t *frames,
@@ -1159,6 +1188,26 @@ int ac3mi_syncinfo(const uint8_t *buf, int *flags, int *sample_rate, int *bit_ra
     return 0;
 }
 
+int ac3mi_crc_check_batch(ac3mi_ctx *ctx, const uint8_t *d_frames, int frame_stride, int frame_bytes, size_t n_frames,
+                          uint8_t *d_verdict)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (!d_frames || !d_verdict || n_frames > 0x7fffffffu || frame_bytes < 8 || frame_bytes > 3840 ||
+        frame_stride < ((frame_bytes + 3) & ~3) || (frame_stride & 3) || ((uintptr_t)d_frames & 3)) {
+        ctx->err = "ac3mi_crc_check_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CrcLaunch C;
+    C.frames = d_frames;
+    C.verdict = d_verdict;
+    C.n_frames = n_frames;
+    C.frame_stride = frame_stride;
+    C.frame_bytes = frame_bytes;
+    HIPCHK(ctx, launch_crc(C, ctx->stream));
+    return AC3MI_OK;
+}
+
 int ac3mi_decode_planes(const ac3mi_decode_desc *desc, int *n_out, int *out_flags)
 {
     if (!desc || desc->acmod < 0 || desc->acmod > 7) return AC3MI_ERR_ARG;
@@ -1223,6 +1272,7 @@ static int decode_impl(ac3mi_ctx *ctx, const ac3mi_decode_desc *desc, const uint
     }
     TRY(grow_front_ws(ctx, fe, nfr));
     DecodeLaunch D = decode_launch(ctx, fe, desc, d_frames, frame_stride, n_streams, frames_per_stream, d_lfsr, d_status);
+    TRY(crc_pass(ctx, desc, d_frames, frame_stride, nfr, &D.crc));
     D.coef = fe.mantx ? nullptr : coef;
     D.blksw = blksw;
     D.zs = zs;
@@ -1479,6 +1529,7 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     // in one piece: a kernel of 2 048 frames already occupies every CU (the six-wavefront-per-frame kernels) or is dispatched
     // whole before the other stream's (the others), so the chunks' latency floors add up instead of overlapping.)
     DecodeLaunch D = decode_launch(ctx, fe, &dd, d_frames_in, in_stride, n_streams, frames_per_stream, d_lfsr, d_status);
+    TRY(crc_pass(ctx, &dd, d_frames_in, in_stride, nfr, &D.crc));
     D.coef = fe.mantx ? nullptr : ctx->ws_coef.at<float>();
     D.blksw = ctx->ws_blksw.at<uint8_t>();
     D.zs = zs;

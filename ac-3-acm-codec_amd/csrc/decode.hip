@@ -58,6 +58,7 @@ __device__ unsigned long long g_dec_cycles[8];
 #define DK_END() do { } while (0)
 #endif
 
+// (crc_verdicts() reads DecodeParams::crc from the kernel-argument segment: P must stay this kernel's first argument)
 template <int MODE>
 __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kernel(const DecodeParams P)
 {
@@ -161,6 +162,8 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
         Rd rd{FB, 0, 0, 0};
         // ---- a52_syncinfo (parse.c:86-129) + a52_frame (parse.c:131-205) ----
         bool hdr_ok = true;
+        if (const uint8_t *crcp = crc_verdicts())           // ac3mi_set_decode_crc 2: the CRC kernel's verdict (wave-uniform) refuses the frame
+            if (crcp[fidx] & 0x40u) hdr_ok = false;
         {
             const uint32_t w0 = rfl(frw[0]), w1 = rfl(frw[1]);
             const int b4 = (w1 >> 24) & 0xff, b5 = (w1 >> 16) & 0xff, b6 = (w1 >> 8) & 0xff;
@@ -607,6 +610,13 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
             __builtin_amdgcn_wave_barrier();
         }
         DK_LAP(5);
+        // ac3mi_set_decode_crc: bits 10 / 11 - not for a frame the header test itself refused (crc_kernel repeats that test and
+        // does not sum such a frame; the one refusal it cannot see, an output liba52 would not grant, is screened per call by
+        // ac3mi_decode_planes - the mask keeps "bit 8 without the verdict's bit 6 = neither bit" whatever the refusal was)
+        if (const uint8_t *crcp = crc_verdicts()) {
+            const uint32_t cv = crcp[fidx];
+            if (!(status & 0x100u) || (cv & 0x40u)) status |= (cv & 3u) << 10;
+        }
         if (lane == 0) P.status[fidx] = status | (reuse0 ? 0x200u : 0u);
         if (lane == 0 && P.zs) P.zs[fidx] = (uint8_t)((status & 0x100u) ? 0 : surround_level_is_zero(st.acmod, st.output, st.slev));
         if (MODE == 5 && lane == 0) P.frame_draws[fidx] = frame_draws;
@@ -786,6 +796,7 @@ hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStre
     P.frame_pos = nullptr;
     P.dyn_out = L.dyn_out;
     P.dyn_in = L.dyn_in;
+    P.crc = L.crc;
     static const int lds_pad = getenv("AC3MI_DEC_LDS_PAD") ? atoi(getenv("AC3MI_DEC_LDS_PAD")) : 0;      // profiling aid: occupancy sweeps
     const size_t fr_bytes = (size_t)(((L.frame_bytes + 3) >> 2) + 6) * 4 + lds_pad;
     const unsigned units = (unsigned)L.n_streams * (unsigned)L.frames_per_stream;

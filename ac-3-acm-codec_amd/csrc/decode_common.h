@@ -2,6 +2,7 @@
 // per frame; decode_wg.hip: one workgroup per stream, one wavefront per channel, transform fused in): bit reader,
 // exponent decode (L52/parse.c:218-270), parametric bit allocation (L52/bit_allocate.c:124-265), dither access.
 #pragma once
+#include <type_traits>
 #include "ac3mi_internal.h"
 #include "a52_levels.h"
 #include "wave_ops.h"
@@ -183,7 +184,23 @@ struct DecodeParams {
     const uint16_t *frame_lfsr;   // [S][F] LFSR state at the start of each frame (frame-parallel pass)
     float *dyn_out;               // optional [S][F][6][2], see ac3mi_decode_taps
     const float *dyn_in;
+    const uint8_t *crc;           // optional [S][F] verdicts of crc_kernel: bits 0-1 -> status bits 10-11, bit 6: refuse the frame
 };
+
+// DecodeParams::crc, read from the kernel-argument segment where it is used (behind an opaque offset, so the load is not
+// hoisted): the front ends sit on spilled scalar registers, and a pointer held across a frame would cost them two more.
+// Holds ONLY for kernels whose first argument is a DecodeParams or a struct that begins with one - decode_kernel (decode.hip)
+// and decode_wg_kernel (decode_wg.hip, static_assert on WgParams there); an argument or a member put in front of it makes
+// this read a wrong pointer.  The ordinary-argument form cost the parse kernel scratch (8 -> 16 B, profiles/EXPERIMENTS.md).
+__device__ __forceinline__ const uint8_t *crc_verdicts()
+{
+    static_assert(std::is_standard_layout<DecodeParams>::value && offsetof(DecodeParams, crc) + sizeof(void *) == sizeof(DecodeParams),
+                  "crc is DecodeParams' last member: kernel-argument offset = offsetof");
+    uint32_t off = (uint32_t)offsetof(DecodeParams, crc);
+    asm volatile("" : "+s"(off));
+    typedef const uint8_t *__attribute__((address_space(4))) const *slot_t;
+    return *(slot_t)((const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
 
 // the range factor of a dynamic-range word (parse.c:587-595), through the optional per-word taps
 __device__ __forceinline__ float dynrng_range(const DecodeParams &P, int code, size_t word_index, int lane)

@@ -186,6 +186,7 @@ struct ParserState {
     uint32_t pos;               // the bit reader's position
     int cplexpstr, lfeexpstr, chexp, redo;      // from the first to the second half of a block's side information
     uint32_t status, reuse0;
+    uint32_t crcv;              // the frame's CRC verdict byte (ac3mi_set_decode_crc), 0 when the frames are not checked
     int frame_dead;
     uint32_t lfsr_idx;          // position in the dither generator's cycle
     int lfsr_live;
@@ -746,6 +747,9 @@ using namespace wg;
 
 // OUT 0: coefficient planes (and block-switch flags) to HBM, for stage taps and the unfused paths
 // OUT 1: float PCM planes          OUT 2: interleaved s16 PCM
+// crc_verdicts() reads DecodeParams::crc from the kernel-argument segment: W stays this kernel's first argument and the
+// DecodeParams its first member
+static_assert(offsetof(WgParams, d) == 0, "crc_verdicts(): the DecodeParams leads the kernel arguments");
 template <int OUT>
 __global__ __launch_bounds__(512, WG_LB) void decode_wg_kernel(const WgParams W)
 {
@@ -825,7 +829,13 @@ __global__ __launch_bounds__(512, WG_LB) void decode_wg_kernel(const WgParams W)
             if (wave == W_PARSE) {
                 PSET(S.status, 0u);
                 PSET(S.reuse0, 0u);
-                const bool ok = parse_frame_header(FB, frw, S, L.hth, P, lane);
+                // (ac3mi_set_decode_crc 2: a frame whose CRC fails is refused before its header is read)
+                {
+                    const uint8_t *crcp = crc_verdicts();
+                    PSET(S.crcv, crcp ? (uint32_t)crcp[fidx] : 0u);
+                }
+                wave_sync();
+                const bool ok = !(ldsu((const int &)S.crcv) & 0x40) && parse_frame_header(FB, frw, S, L.hth, P, lane);
                 PSET(S.frame_dead, ok ? 0 : 1);
                 if (!ok) PSET(S.status, 0x100u);
                 BlkInfo &B0 = L.bi[0];
@@ -1103,7 +1113,9 @@ __global__ __launch_bounds__(512, WG_LB) void decode_wg_kernel(const WgParams W)
             }
             if (wave == W_PARSE && lane == 0) {
                 const uint32_t st = S.status;
-                P.status[fidx] = st | ((st & 0x100u) ? 0x3fu : 0u) | (S.reuse0 ? 0x200u : 0u);
+                // bits 10 / 11: not for a frame the header test itself refused (see decode.hip)
+                const uint32_t cv = S.crcv, cb = (!(st & 0x100u) || (cv & 0x40u)) ? (cv & 3u) << 10 : 0u;
+                P.status[fidx] = st | ((st & 0x100u) ? 0x3fu : 0u) | (S.reuse0 ? 0x200u : 0u) | cb;
                 if (P.zs) P.zs[fidx] = (uint8_t)((st & 0x100u) ? 0 : surround_level_is_zero(S.acmod, S.output, S.slev));
             }
             STAMP(53);
@@ -1151,6 +1163,7 @@ hipError_t launch_decode_wg(const DeviceTables &tab, const DecodeLaunch &D, cons
     P.frame_lfsr = nullptr;
     P.dyn_out = D.dyn_out;
     P.dyn_in = D.dyn_in;
+    P.crc = D.crc;
     W.tw_long = tab.tw_long;
     W.tw_short = tab.tw_short;
     W.window = tab.window;

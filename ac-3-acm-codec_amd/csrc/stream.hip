@@ -489,8 +489,12 @@ int decode_group(ac3mi_pool *p, const std::vector<ac3mi_stream *> &group, int ba
         }
         ac3mi_set_state_slots(ctx, d_slots + lo);
         ac3mi_set_mix_state(ctx, p->d_mixp, p->d_mixf);
+        // the stream layer decodes as the ACM codec does: no CRC check, whatever ac3mi_set_decode_crc set on the caller's context
+        const int crc_mode = ctx->decode_crc;
+        ctx->decode_crc = 0;
         const int rc = ac3mi_decode_s16_batch(ctx, &d, d_frames + (size_t)lo * fstride, fstride, kc, 1, p->d_delay, p->d_lfsr,
                                               (int16_t *)((uint8_t *)d_s16 + (size_t)lo * 6 * blk), d_status + lo);
+        ctx->decode_crc = crc_mode;
         ac3mi_set_mix_state(ctx, NULL, NULL);
         ac3mi_set_state_slots(ctx, NULL);
         if (rc != AC3MI_OK) { (void)hipDeviceSynchronize(); return fail(p, AC3MI_MMSYSERR_NOMEM, "decode batch"); }

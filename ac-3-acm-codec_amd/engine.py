@@ -256,6 +256,29 @@ class Engine:
         in the mantissa kernel for one-frame streams without a downmix (ac3mi_set_decode_mode)."""
         self._check(self.lib.ac3mi_set_decode_mode(ctypes.c_void_p(self.ctx), int(mode)))
 
+    def set_decode_crc(self, mode):
+        """CRC verification of the frames the decode and transcode calls read (ac3mi_set_decode_crc): 0 = none (liba52),
+        1 = report in status bits 10 / 11 (flags.STATUS_CRC1 / STATUS_CRC2), 2 = also decode a failing frame as a refused
+        one (silence, status 0x13f plus its CRC bits)."""
+        self._check(self.lib.ac3mi_set_decode_crc(ctypes.c_void_p(self.ctx), int(mode)))
+
+    def crc_check_batch(self, frames, frame_bytes=None, out=None, wait_torch=True):
+        """ac3mi_crc_check_batch: frames [...][stride] u8 on the device (stride multiple of 4; frame_bytes = the largest
+        frame's size, default the stride) -> verdict u8 [...]: bit 0 CRC1 fails, bit 1 CRC2 fails, bit 7 not summed."""
+        import torch
+        assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.is_cuda and frames.dim() >= 2
+        stride = frames.shape[-1]
+        n = frames.numel() // stride if stride else 0
+        if out is None:
+            out = torch.zeros(tuple(frames.shape[:-1]), dtype=torch.uint8, device=frames.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_crc_check_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(frames.data_ptr()), int(stride),
+                                                   int(stride if frame_bytes is None else frame_bytes), ctypes.c_size_t(n),
+                                                   ctypes.c_void_p(out.data_ptr())))
+        self._keep.append((frames, out))
+        return out
+
     def set_encode_mode(self, mode):
         """0 = choose by batch size, 1 = one wavefront per frame packs, 2 = one wavefront per audio block packs
         (ac3mi_set_encode_mode)."""

@@ -19,3 +19,13 @@ NFCHANS = (2, 1, 2, 3, 3, 4, 4, 5, 1, 1, 2)
 
 def out_channels(flags):
     return NFCHANS[flags & A52_CHANNEL_MASK] + (1 if flags & A52_LFE else 0)
+
+# d_status bits of the batched decoder (include/ac3mi.h)
+STATUS_REFUSED = 0x100      # a52_syncinfo / a52_frame refused the frame
+STATUS_REUSE0 = 0x200
+STATUS_CRC1 = 0x400         # CRC-16 of bytes [2, 2 fs58) is not 0 (ac3mi_set_decode_crc 1 / 2)
+STATUS_CRC2 = 0x800         # CRC-16 of bytes [2 fs58, 2 fs) is not 0
+# ac3mi_set_decode_crc modes
+CRC_OFF, CRC_REPORT, CRC_CONCEAL = 0, 1, 2
+# ac3mi_crc_check_batch verdict bits
+VERDICT_CRC1, VERDICT_CRC2, VERDICT_NOT_SUMMED = 1, 2, 0x80

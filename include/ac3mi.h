@@ -163,6 +163,39 @@ int ac3mi_set_mix_state(ac3mi_ctx *ctx, float *d_pending, int32_t *d_flags);
 #define AC3MI_STATUS_REUSE0 0x200u
 int ac3mi_set_decode_mode(ac3mi_ctx *ctx, int mode);
 
+/* CRC verification of the frames ac3mi_decode_batch / ac3mi_decode_s16_batch / ac3mi_transcode_batch read (new; applies to
+ * every following such call on `ctx`, under every ac3mi_set_decode_mode, with or without state slots, mix state, taps and
+ * tiling).  liba52 never looks at a frame's two CRC words, so a frame damaged in its mantissas parses without a block error,
+ * decodes to noise, and a transcode re-encodes that noise into a frame whose CRCs are valid.  A/52 defines the check: CRC-16,
+ * polynomial x^16 + x^15 + x^2 + 1, MSB first, start value 0; with fs the frame's size in 16-bit words from its own header
+ * (fscod / frmsizecod as ac3mi_syncinfo computes it: 44.1 kHz streams alternate between two sizes inside one batch, bsid 9 /
+ * 10 keep the table) and fs58 = (fs >> 1) + (fs >> 3), bytes [2, 2 fs58) sum to 0 (crc1 is among them) and bytes
+ * [2 fs58, 2 fs), summed from 0 again, sum to 0 (crc2 ends them).  The two sums are independent, so they say where a frame
+ * is damaged.
+ *   0  (default) liba52's behaviour: nothing is checked, no kernel is launched, bits 10 / 11 of d_status are never set;
+ *   1  report: a kernel of its own (one wavefront per frame, ahead of the front end; one verdict byte per frame in a workspace
+ *      of the context - ac3mi_workspace_bytes counts it, ac3mi_transcode_workspace_plan, which plans the default mode, does
+ *      not) sets AC3MI_STATUS_CRC1 / AC3MI_STATUS_CRC2 in d_status for every frame that passes the header test; a frame that
+ *      gets bit 8 for its own sake (no sync word, reserved codes, other acmod / lfeon, longer than frame_bytes) is not summed
+ *      and gets neither bit.  PCM, s16, taps, d_delay, d_lfsr and transcoded frames are those of mode 0, bit for bit;
+ *   2  conceal: as 1, and a frame with either bit set is treated exactly as a frame the header test refuses: status
+ *      0x100 | 0x3f plus its CRC bits, six silent blocks (the previous frame's overlap tail fades out, the next frame fades
+ *      in), the dither generator not advanced.  The call's outputs and state equal those of mode 0 on the same batch with
+ *      bytes 0-1 of every failing frame zeroed; a transcode codes a frame of silence for it and says so in d_status.
+ * Any other mode: AC3MI_ERR_ARG, the setting stays.  The a52_* drop-in and the byte-stream layer (ac3mi_dropin.h,
+ * ac3mi_stream.h) never check, as liba52 and the ACM codec do not. */
+#define AC3MI_STATUS_CRC1 0x400u   /* CRC-16 of bytes [2, 2*fs58) of the frame is not 0 (first 5/8, holds crc1)      */
+#define AC3MI_STATUS_CRC2 0x800u   /* CRC-16 of bytes [2*fs58, 2*fs) of the frame is not 0 (the rest, ends with crc2) */
+int ac3mi_set_decode_crc(ac3mi_ctx *ctx, int mode);
+
+/* The check alone, for hosts that only validate (new).  d_frames: n_frames frames, frame_stride bytes apart (multiple of 4,
+ * >= frame_bytes rounded up to 4; base 4-byte aligned; 16-byte loads when base and stride are multiples of 16), frame_bytes
+ * the size of the largest one (8..3840).  d_verdict[i]: bit 0 = CRC1 fails, bit 1 = CRC2 fails (the rule above), bit 7 =
+ * not summed - the header test on bytes 0-5 failed (a52_syncinfo's) or the frame is longer than frame_bytes; every acmod /
+ * lfeon is summed.  Asynchronous on the context's stream like the batch calls. */
+int ac3mi_crc_check_batch(ac3mi_ctx *ctx, const uint8_t *d_frames, int frame_stride, int frame_bytes, size_t n_frames,
+                          uint8_t *d_verdict);
+
 /* How ac3mi_encode_batch / ac3mi_transcode_batch pack a frame once its SNR offsets are found (new; same bytes either way -
  * the searches always run first, one wavefront per stream, frames in order):
  *   1  one wavefront per frame packs it;
@@ -463,7 +496,8 @@ int ac3mi_decode_planes(const ac3mi_decode_desc *desc, int *n_out, int *out_flag
  * d_pcm     [n_streams][frames_per_stream][6][n_out][256] float, a52_samples() plane order
  * d_status  [n_streams][frames_per_stream]: bit b (0..5) = a52_block b returned 1 (that block and
  *           the rest of the frame are silence), bit 8 = a52_syncinfo/a52_frame refused the frame,
- *           bit 9 (AC3MI_STATUS_REUSE0) = block 0 reused state the frame did not send, bits 16..23 = output
+ *           bit 9 (AC3MI_STATUS_REUSE0) = block 0 reused state the frame did not send, bits 10 / 11
+ *           (AC3MI_STATUS_CRC1 / CRC2, only with ac3mi_set_decode_crc 1 / 2) = a CRC region fails, bits 16..23 = output
  *           flags a52_frame granted
  * Across frames only d_delay and d_lfsr matter for a valid stream (block 0 of every AC-3 frame re-sends
  * exponents, coupling and bit-allocation parameters), and only they persist across calls.  Inside one call

@@ -23,6 +23,8 @@
  *     converters expect, src/AC3ACM.cpp:1555-1561) one float ulp is one 16-bit step, so converted s16 samples are within
  *     ONE step of liba52's, never promised identical.  Exponents, bit allocation and dequantised coefficients are exact,
  *     and AC3_encode_frame's bytes are exact for given samples
+ *   - like liba52, a52_syncinfo() / a52_frame() never look at a frame's CRC words (the batched calls can:
+ *     ac3mi_set_decode_crc, ac3mi_crc_check_batch in ac3mi.h); AC3_encode_frame writes both, as the reference does
  */
 #ifndef AC3MI_DROPIN_H
 #define AC3MI_DROPIN_H

@@ -28,6 +28,8 @@
  *     refused (MMSYSERR_NOTSUPPORTED) for that reason
  *   - WAVE_FORMAT_EXTENSIBLE is accepted for PCM with the default channel masks
  *     (src/AC3ACM.cpp:207-239); the reference's AC-3 EXTENSIBLE test can never pass (:303-304)
+ * Like the ACM codec, this layer never checks a frame's CRC words: ac3mi_set_decode_crc (ac3mi.h) belongs to the batched
+ * calls and is not applied here, and a false sync word is still only rejected by a52_syncinfo's header test.
  */
 #ifndef AC3MI_STREAM_H
 #define AC3MI_STREAM_H
