@@ -3,13 +3,18 @@
  * CPU restatement, written from scratch, of the reference's AC-3 encoder
  * (/root/reference/src/ac3enc/ac3enc.cpp, tables ac3tab.h).  Integer
  * arithmetic, 16-bit truncating stores and shift semantics follow the cited
- * lines so that the emitted frames are meant to be bit-identical.
+ * lines so that the emitted frames are bit-identical.
  *
- * PARITY UNPINNED: ac3enc.cpp includes <windows.h>/<crtdbg.h> and cannot be
- * compiled in this image, and the reference holds no encoder test vectors.
- * What IS checked (tests/test_oracle_encoder.py): every frame produced here is
- * decoded by the real liba52 (oracle/_ref) with zero errors, both CRCs verify,
- * the frame fills exactly, and the decoded PCM tracks the input.
+ * PINNED: tests/test_oracle_vs_ac3enc.py compares frames, every stage array,
+ * the run-time tables and init's decisions with what the reference's own
+ * ac3enc.cpp wrote (oracle/ref_ac3enc_glue.cpp -> oracle/_ref/ac3enc_ref.so,
+ * recorded in tests/golden/ac3enc_ref.npz), failed searches and overflowing
+ * frames included.  One deliberate deviation: a new context starts with a
+ * zeroed overlap state, where the reference's init keeps the previous
+ * stream's (orc_ac3enc_set_last reproduces that on request).  Besides
+ * (tests/test_oracle_encoder.py): every frame produced here is decoded by the
+ * real liba52 (oracle/_ref) with zero errors, both CRCs verify, the frame
+ * fills exactly, and the decoded PCM tracks the input.
  *
  * Differences in structure (not in results): re-entrant context instead of
  * the reference's single static state; PSD/excitation/mask are computed once
@@ -204,6 +209,7 @@ struct orc_ac3enc {
     int chbwcod[MAXCH];
     int16_t last[MAXCH][256];
     int csnroffst, fsnroffst;
+    int search_failed, bytes_written;      /* of the last frame: see orc_ac3enc_get_status */
     /* fixed allocation codes (ac3enc.cpp:861-869) */
     int sdecaycod, fdecaycod, sgaincod, dbkneecod, floorcod, fgaincod;
 
@@ -215,7 +221,7 @@ struct orc_ac3enc {
     int8_t shift[NBLK][MAXCH];
     int16_t psd[NBLK][MAXCH][256];
     int16_t mask[NBLK][MAXCH][50];
-    uint8_t scratch[3840 + 4096];
+    uint8_t scratch[24576];                 /* a whole frame at 16 bits per coefficient is under 16 KB: see orc_ac3enc_frame */
 };
 
 /* ---------------- MDCT (ac3enc.cpp:462-603) ---------------- */
@@ -770,7 +776,7 @@ void orc_ac3enc_free(orc_ac3enc_t *s) { free(s); }
 
 int orc_ac3enc_frame(orc_ac3enc_t *s, uint8_t *dst, const int16_t *samples, const uint8_t *chmap)
 {
-    int ch, b, j, frame_bits = 0, fs = s->frame_words, fs58, n;
+    int ch, b, j, frame_bits = 0, fs = s->frame_words, fs58;
     bitw w;
     unsigned crc1, crc2, inv;
 
@@ -818,7 +824,7 @@ int orc_ac3enc_frame(orc_ac3enc_t *s, uint8_t *dst, const int16_t *samples, cons
         }
     }
 
-    search_allocation(s, frame_bits);
+    s->search_failed = search_allocation(s, frame_bits) < 0;
 
     /* The reference's own bit accounting undercounts stereo frames by a few bits (rematrix flags of
      * block 0: 5 bits written, 1 counted, ac3enc.cpp:892 vs :1228-1236; author's note at :1609-1613).
@@ -843,14 +849,12 @@ int orc_ac3enc_frame(orc_ac3enc_t *s, uint8_t *dst, const int16_t *samples, cons
     put(&w, 1, 0);
     put(&w, 1, 1);
     put(&w, 3, 0);
-    for (b = 0; b < NBLK; b++) {
-        if (w.nbits > (uint32_t)(fs * 16 + 256)) return -1;       /* far outside the contract */
-        write_block(s, &w, b);
-    }
-    n = (int)((w.nbits + 7) >> 3);
-    if (n > fs * 2 + 32) return -1;
+    /* A frame whose search failed (:930-933) overflows by as much as its last attempt's allocation asks for; the
+     * reference writes all of it behind the frame and still returns the frame size (:1752, :1637).  So does this:
+     * six blocks of 1122 coefficients at 16 bits, exponents and side information stay under 16 KB of scratch. */
+    for (b = 0; b < NBLK; b++) write_block(s, &w, b);
+    s->bytes_written = (int)((w.nbits + 7) >> 3);
     memcpy(dst, s->scratch, fs * 2);
-    (void)n;
 
     fs58 = (fs >> 1) + (fs >> 3);                                  /* :1624-1635 */
     crc1 = crc_run(dst + 4, 2 * fs58 - 4, 0);
@@ -877,6 +881,29 @@ void orc_ac3enc_get_misc(orc_ac3enc_t *s, uint8_t *strat, int8_t *shift, int *cs
     memcpy(shift, s->shift, sizeof s->shift);
     *csnr = s->csnroffst;
     *fsnr = s->fsnroffst;
+}
+
+/* the last frame: whether its search gave up (the reference's "Yack" path, ac3enc.cpp:930-933) and how many bytes the
+ * bit writer produced before padding - more than frame bytes - 2 is what the reference's _ASSERT(n >= 0) (:1619) is about */
+void orc_ac3enc_get_status(orc_ac3enc_t *s, int *search_failed, int *bytes_written)
+{
+    *search_failed = s->search_failed;
+    *bytes_written = s->bytes_written;
+}
+
+/* last_samples (ac3enc.cpp:55): the 256 samples per coded channel that the next frame's first block overlaps with.
+ * A new context has zeros; the reference's AC3_encode_init leaves a previous stream's there (:1019-1110). */
+void orc_ac3enc_set_last(orc_ac3enc_t *s, const int16_t *last /*[6][256]*/) { memcpy(s->last, last, sizeof s->last); }
+void orc_ac3enc_get_last(orc_ac3enc_t *s, int16_t *last /*[6][256]*/) { memcpy(last, s->last, sizeof s->last); }
+
+/* the index tables AC3_encode_init fills beside those of orc_ac3enc_tables: fft_rev (fft_init(7), :452-458: 128 entries),
+ * bndtab and masktab (ac3_common_init, :977-993: 51 and 253 entries) */
+void orc_ac3enc_index_tables(uint8_t *fft_rev128, uint8_t *bndtab51, uint8_t *masktab253)
+{
+    enc_build_tables();
+    memcpy(fft_rev128, bitrev7, sizeof bitrev7);
+    memcpy(bndtab51, band_start, sizeof band_start);
+    memcpy(masktab253, band_of_bin, 253);
 }
 
 int orc_ac3enc_encode_frames(int freq, int bitrate, int channels, const int16_t *pcm, int n,

@@ -10,10 +10,11 @@
  *   decode  — pinned bit-for-bit against oracle/_ref/liba52_ref.so (the real
  *             liba52 compiled from /root/reference) and the fixtures in
  *             tests/golden/ generated from it.
- *   encode  — PARITY UNPINNED: ac3enc.cpp needs <windows.h>/<crtdbg.h>, which
- *             this image lacks, and the reference ships no encoder vectors.
- *             Cross-checked only indirectly: the real liba52 decodes every
- *             oracle-encoded frame without error and recovers the PCM.
+ *   encode  — pinned byte for byte against oracle/_ref/ac3enc_ref.so (the real
+ *             ac3enc.cpp, compiled unmodified behind ref_ac3enc_glue.cpp and the
+ *             stand-in headers of winstub/) and the fixture recorded from it,
+ *             tests/golden/ac3enc_ref.npz: frames, every stage array, tables,
+ *             init decisions (tests/test_oracle_vs_ac3enc.py).
  */
 #ifndef ORC_H
 #define ORC_H
@@ -86,6 +87,10 @@ void orc_ac3enc_get_misc(orc_ac3enc_t *s, uint8_t *exp_strategy /*[6][6]*/, int8
                          int *csnroffst, int *fsnroffst);
 void orc_ac3enc_tables(int16_t *costab64, int16_t *sintab64, int16_t *xcos128, int16_t *xsin128,
                        uint16_t *crc256);
+void orc_ac3enc_index_tables(uint8_t *fft_rev128, uint8_t *bndtab51, uint8_t *masktab253);
+void orc_ac3enc_get_status(orc_ac3enc_t *s, int *search_failed, int *bytes_written);
+void orc_ac3enc_set_last(orc_ac3enc_t *s, const int16_t *last /*[6][256]*/);
+void orc_ac3enc_get_last(orc_ac3enc_t *s, int16_t *last /*[6][256]*/);
 void orc_ac3enc_spec_tables(int16_t *window256, uint8_t *latab256, uint16_t *hth50x3, uint8_t *baptab64,
                             uint8_t *bndsz50, uint16_t *sdecay4, uint16_t *fdecay4, uint16_t *sgain4,
                             uint16_t *dbknee4, uint16_t *floor8, uint16_t *fgain8, uint16_t *freqs3,

@@ -6,9 +6,9 @@
  * tests/golden/make_golden.py can freeze them in tests/golden/ac3tab.npz; the CPU gate then checks
  * the encoder oracle's and the engine's tables against that fixture (tests/test_oracle_golden.py).
  *
- * Only the spec tables of ac3tab.h:3-171 are pinned this way.  The runtime tables (costab, sintab,
- * xcos1, xsin1, fft_rev, crc_table, bndtab, masktab) are filled by code in ac3enc.cpp, which needs
- * <windows.h>/<crtdbg.h> and is not built here.
+ * The spec tables of ac3tab.h:3-171 are pinned this way.  The runtime tables (costab, sintab, xcos1,
+ * xsin1, fft_rev, crc_table, bndtab, masktab) are filled by code in ac3enc.cpp: ref_ac3enc_glue.cpp
+ * builds that file itself and hands them out (tests/golden/ac3enc_ref.npz, tab_*).
  */
 #include <string.h>
 #include "common.h"

@@ -10,7 +10,9 @@ import hashlib
 import importlib
 import json
 import os
+import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -18,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORC_PATH = os.path.join(ORACLE_DIR, "liborc.so")
 REF_PATH = os.path.join(ORACLE_DIR, "_ref", "liba52_ref.so")
+REFENC_PATH = os.path.join(ORACLE_DIR, "_ref", "ac3enc_ref.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -94,6 +97,10 @@ def orc():
     L.orc_ac3enc_get_bap.argtypes = [vp, u8p]
     L.orc_ac3enc_get_misc.argtypes = [vp, u8p, i8p, ip, ip]
     L.orc_ac3enc_tables.argtypes = [i16p, i16p, i16p, i16p, u16p]
+    L.orc_ac3enc_index_tables.argtypes = [u8p, u8p, u8p]
+    L.orc_ac3enc_get_status.argtypes = [vp, ip, ip]
+    L.orc_ac3enc_set_last.argtypes = [vp, i16p]
+    L.orc_ac3enc_get_last.argtypes = [vp, i16p]
     L.orc_ac3enc_mdct512.argtypes = [i32p, i16p]
     L.orc_ac3enc_encode_frames.argtypes = [ci, ci, ci, i16p, ci, u8p, u8p]
     _orc = L
@@ -138,6 +145,88 @@ def ref():
     L.a52_imdct_init(0)
     _ref = L
     return L
+
+
+def have_refenc():
+    return os.path.exists(REFENC_PATH)
+
+
+REFENC_ARRAYS = {"mdct_coef": (np.int32, (6, 6, 256)), "exponent": (np.uint8, (6, 6, 256)), "exp_strategy": (np.uint8, (6, 6)),
+                 "encoded_exp": (np.uint8, (6, 6, 256)), "bap": (np.uint8, (6, 6, 256)), "exp_samples": (np.int8, (6, 6)),
+                 "costab": (np.int16, (64,)), "sintab": (np.int16, (64,)), "xcos1": (np.int16, (128,)), "xsin1": (np.int16, (128,)),
+                 "fft_rev": (np.int16, (512,)), "crc_table": (np.uint16, (256,)), "bndtab": (np.uint8, (51,)), "masktab": (np.uint8, (253,))}
+REFENC_TABLES = ("costab", "sintab", "xcos1", "xsin1", "fft_rev", "crc_table", "bndtab", "masktab")
+
+
+class RefEncoder:
+    """One fresh instance of the reference's own ac3enc (oracle/ref_ac3enc_glue.cpp -> oracle/_ref/ac3enc_ref.so).  The
+    reference keeps a single static context that its init does not clear, so every instance is a privately copied
+    library: its statics start zeroed and no other instance shares them."""
+
+    def __init__(self):
+        fd, self.path = tempfile.mkstemp(prefix="ac3enc_ref_", suffix=".so")
+        os.close(fd)
+        shutil.copyfile(REFENC_PATH, self.path)
+        L = self.L = ctypes.CDLL(self.path)
+        os.unlink(self.path)                               # the mapping keeps the copy alive
+        L.refenc_init.argtypes = [ci, ci, ci]
+        L.refenc_frame.argtypes = [u8p, i16p, u8p]
+        L.refenc_array.restype = vp
+        L.refenc_array.argtypes = [ctypes.c_char_p, ip, ip]
+        L.refenc_snr.argtypes = [ip]
+        L.refenc_assert_trips.argtypes = [ip]
+        self.frame_bytes = 0
+        self.nch = 0
+
+    def init(self, freq, bitrate, channels):
+        self.frame_bytes = self.L.refenc_init(freq, bitrate, channels)
+        self.nch = channels
+        return self.frame_bytes
+
+    def frame(self, samples, chmap):
+        """Encodes 1536 x nch interleaved s16 samples -> (returned size, the frame's bytes).  self.yack says whether the
+        reference reported on stderr that its search failed (ac3enc.cpp:930-933: the only trace it leaves, its caller
+        ignores the result)."""
+        dst = np.zeros(32768, np.uint8)                    # the reference's bit writer does not check its end
+        samples = np.ascontiguousarray(samples, np.int16)
+        assert samples.size == 1536 * self.nch
+        cm = (ctypes.c_uint8 * 8)(*(tuple(chmap) + (0,) * 8)[:8])
+        with tempfile.TemporaryFile() as err:
+            saved = os.dup(2)
+            os.dup2(err.fileno(), 2)
+            try:
+                r = self.L.refenc_frame(P(dst, u8p), P(samples, i16p), cm)
+            finally:
+                os.dup2(saved, 2)
+                os.close(saved)
+            err.seek(0)
+            self.yack = b"Yack" in err.read()
+        return r, dst[:self.frame_bytes].copy()
+
+    def encode(self, pcm, chmap):
+        """pcm [frames * 1536][nch] -> ([frames][frame_bytes] u8, [frames] returned sizes)."""
+        pcm = np.ascontiguousarray(pcm, np.int16).reshape(-1, 1536, self.nch)
+        out = [self.frame(x, chmap) for x in pcm]
+        return np.stack([o[1] for o in out]), np.array([o[0] for o in out], np.int32)
+
+    def array(self, name):
+        dt, shape = REFENC_ARRAYS[name]
+        n, eb = ci(), ci()
+        ptr = self.L.refenc_array(name.encode(), ctypes.byref(n), ctypes.byref(eb))
+        assert ptr and n.value == int(np.prod(shape)) and eb.value == np.dtype(dt).itemsize, name
+        return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(np.ctypeslib.as_ctypes_type(dt))), (n.value,)).reshape(shape).copy()
+
+    def snr(self):
+        """(csnroffst, fsnroffst[6], fgaincod[6]) of the context."""
+        a = np.zeros(13, np.int32)
+        self.L.refenc_snr(P(a, ip))
+        return int(a[0]), a[1:7].copy(), a[7:13].copy()
+
+    def assert_trips(self):
+        """(how many of the reference's own _ASSERT conditions did not hold so far, {source line: trips})."""
+        sites = np.zeros((16, 2), np.int32)
+        n = self.L.refenc_assert_trips(P(sites, ip))
+        return n, {int(l): int(c) for l, c in sites if l}
 
 
 # ---------------------------------------------------------------------------

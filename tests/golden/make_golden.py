@@ -3,12 +3,18 @@
 (the real liba52, compiled from /root/reference by oracle/Makefile) exists.
 
 What is pinned and by what:
-  decode_*.npz   bitstreams (made by OUR encoder oracle - ac3enc itself cannot be built here) and what
+  decode_*.npz   bitstreams (made by our encoder oracle, whose frames are ac3enc's: ac3enc_ref.npz) and what
                  the REAL liba52 decodes from them: float PCM for several output modes, exponents, bap
   imdct.npz      random coefficient planes + delay -> REAL a52_imdct_512 / a52_imdct_256 output
   downmix.npz    REAL a52_downmix_init / a52_downmix_coeff / a52_downmix / a52_upmix results
-  encoder.npz    our encoder oracle's own output and stage dumps (regression pin only: PARITY UNPINNED
-                 against ac3enc, see oracle/ac3enc_oracle.c)
+  encoder.npz    our encoder oracle's own output and stage dumps for one 5.1 stream; tests/test_oracle_golden.py holds
+                 it against the same stream as recorded from ac3enc itself in ac3enc_ref.npz
+  ac3enc_ref.npz, ac3enc_ref.json   the REAL encoder (src/ac3enc/ac3enc.cpp compiled unmodified behind
+                 oracle/ref_ac3enc_glue.cpp and the stand-in headers of oracle/winstub/, one fresh instance per stream):
+                 frames and every stage array for a small matrix, SHA-256 and returned size per frame for a wide one,
+                 the tables AC3_encode_init fills, its decision for every argument triple, re-initialisation sequences,
+                 which searches failed, which of its assertions tripped   (`--only ac3enc_ref` regenerates just these,
+                 bit for bit)
   a52dec_drivers.npz   tests/test_tools_gpu.py's streams through the reference's own liba52 + libao file drivers
                  (oracle/_ref/a52dec_ref): WAV and float output   (`--only a52dec_drivers` regenerates just this file)
   ac3tab.npz     the REAL encoder's constant tables (src/ac3enc/ac3tab.h:3-171 compiled unmodified behind
@@ -125,6 +131,184 @@ def make_mixflip():
     print("mixflip.npz", os.path.getsize(os.path.join(OUT, "mixflip.npz")))
 
 
+# ---- the reference's own encoder: tests/golden/ac3enc_ref.npz + ac3enc_ref.json -----------------------------------------
+# Every stream is encoded by a fresh instance of the unmodified ac3enc (H.RefEncoder: a privately copied
+# oracle/_ref/ac3enc_ref.so per stream); the re-initialisation cases alone run two streams through one instance.
+
+ENC_KINDS = ("tones", "noise", "quiet", "music", "bursts", "strobe", "silence", "rails", "impulses", "dc")
+ENC_RATES = (32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320, 384, 448, 512, 576, 640)
+ENC_FREQS = (48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000)
+IDMAP = (0, 1, 2, 3, 4, 5)
+# name, freq, bitrate, channels, chmap, kind, seed, frames: recorded in full (frames + every stage array)
+ENC_FULL = (("51_384k", 48000, 384000, 6, H.CHMAP6[:6], "tones", 7, 3),        # the streams of encoder.npz
+            ("51_640k", 48000, 640000, 6, H.CHMAP6[:6], "music", 11, 2),
+            ("20_192k", 48000, 192000, 2, IDMAP, "bursts", 12, 3),            # stereo: the rematrix-flag undercount (:892 / :1228-1236)
+            ("10_64k", 48000, 64000, 1, IDMAP, "noise", 13, 3),
+            ("20_44k1", 44100, 128000, 2, IDMAP, "strobe", 14, 3),
+            ("30_half", 24000, 96000, 3, IDMAP, "tones", 15, 3),              # bsid 9
+            ("40_quarter", 11025, 40000, 4, IDMAP, "music", 16, 2),           # bsid 10
+            ("30_yack", 24000, 48000, 3, IDMAP, "music", 101000 + 25 * 7, 4), # frame 3: start value 3 does not fit, 3 - 4 < 0: search fails
+            ("51_starved", 48000, 64000, 6, H.CHMAP6[:6], "noise", 880, 2))   # every frame fails and overflows by kilobytes
+# name, (freq, bitrate, channels, chmap, kind, seed, frames) of stream A and of stream B, coded one after the other in ONE instance
+ENC_REINIT = (("same_51", (48000, 384000, 6, H.CHMAP6[:6], "tones", 21, 2), (48000, 384000, 6, H.CHMAP6[:6], "music", 22, 2)),
+              ("fewer_51_to_20", (48000, 448000, 6, H.CHMAP6[:6], "bursts", 23, 2), (44100, 192000, 2, IDMAP, "tones", 24, 2)),
+              ("more_10_to_30", (32000, 96000, 1, IDMAP, "noise", 25, 2), (48000, 256000, 3, (2, 0, 1, 3, 4, 5), "strobe", 26, 2)))
+ENC_STAGES = ("mdct_coef", "exponent", "exp_strategy", "encoded_exp", "bap", "exp_samples")
+
+
+def enc_half(freq):
+    return ENC_FREQS.index(freq) // 3
+
+
+def enc_wide_matrix():
+    """(freq, bitrate, channels, chmap, kind, seed, frames) of the streams recorded by digest."""
+    out = []
+    # every channel count x every sample rate x every bit-rate code init accepts, two kinds each (all ten kinds in turn)
+    for nch in range(1, 7):
+        for fi, freq in enumerate(ENC_FREQS):
+            for code, kbps in enumerate(ENC_RATES):
+                for k in range(2):
+                    kind = ENC_KINDS[(2 * (nch + fi + code) + k) % len(ENC_KINDS)]
+                    out.append((freq, (kbps >> enc_half(freq)) * 1000, nch, H.CHMAP6[:6] if nch == 6 else IDMAP, kind,
+                                5000 + 1000 * nch + 100 * fi + 2 * code + k, 2))
+    # the six programme kinds on every channel count at a rate that codes them well, longer
+    for nch, kbps in ((1, 96), (2, 192), (3, 256), (4, 320), (5, 448), (6, 384)):
+        for k, kind in enumerate(ENC_KINDS[:6]):
+            out.append((48000, kbps * 1000, nch, H.CHMAP6[:6] if nch == 6 else IDMAP, kind, 7000 + 10 * nch + k, 5))
+    # channel maps other than the driver's
+    for k, (nch, kbps, chmap) in enumerate(((6, 384, IDMAP), (6, 384, (5, 4, 3, 2, 1, 0)), (6, 448, (3, 1, 4, 0, 5, 2)), (2, 192, (1, 0, 2, 3, 4, 5)),
+                                            (3, 256, (2, 0, 1, 3, 4, 5)), (5, 448, (4, 3, 2, 1, 0, 5)), (2, 128, (0, 0, 2, 3, 4, 5)))):
+        for j, kind in enumerate(("tones", "bursts")):
+            out.append((48000, kbps * 1000, nch, chmap, kind, 7500 + 2 * k + j, 3))
+    # long streams: the csnroffst carry-over (:921, :969) over 40 frames and more
+    out.append((48000, 384000, 6, H.CHMAP6[:6], "bursts", 7600, 48))
+    out.append((44100, 192000, 2, IDMAP, "tones", 7601, 40))
+    out.append((24000, 48000, 3, IDMAP, "music", 7602, 40))            # starves now and then: failed searches inside a long stream
+    return out
+
+
+def enc_init_triples():
+    """Argument triples of AC3_encode_init: every channel count 0..7, every accepted sample rate and some that are not,
+    every accepted bit rate of every rate family and some that are not (among them rates that are no multiple of 1000)."""
+    freqs = ENC_FREQS + (0, 4000, 6000, 47999, 48001, 64000, 88200, 96000)
+    rates = sorted({(k >> h) * 1000 for k in ENC_RATES for h in range(3)} | {0, 1000, 7000, 31000, 383000, 384999, 385000, 641000, 768000, 1000000})
+    return [(f, r, c) for c in range(0, 8) for f in freqs for r in rates]
+
+
+def enc_sha(a):
+    import hashlib
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), np.uint8)
+
+
+def enc_ref_stream(R, cfg, full):
+    """Runs one stream through instance R (initialised here).  -> dict of per-frame records."""
+    freq, bitrate, nch, chmap, kind, seed, frames = cfg
+    size = R.init(freq, bitrate, nch)
+    assert size > 0, cfg
+    pcm = H.gen_pcm(frames, nch, seed=seed, kind=kind)
+    rec = {"pcm_sha": enc_sha(pcm), "frames": [], "ret": [], "yack": [], "trips": [], "snr": []}
+    rec.update({k: [] for k in ENC_STAGES} if full else {})
+    trips0 = R.assert_trips()[0]
+    for f in range(frames):
+        r, fr = R.frame(pcm[f * 1536:(f + 1) * 1536], chmap[:nch])
+        t = R.assert_trips()[0]
+        rec["frames"].append(fr)
+        rec["ret"].append(r)
+        rec["yack"].append(int(R.yack))
+        rec["trips"].append(t - trips0)
+        trips0 = t
+        if full:
+            c, fs, fg = R.snr()
+            rec["snr"].append(np.concatenate([[c], fs, fg]))
+            for k in ENC_STAGES:
+                a = R.array(k)[:, :nch]                           # [6 blocks][channels]...: the channels beyond are not this stream's
+                if k in ("bap", "encoded_exp"):                   # beyond the coded coefficients the reference never writes
+                    for ch in range(nch):                         # encoded_exp and copies uninitialised stack into bap (:857, :940)
+                        a[:, ch, 7 if nch == 6 and ch == 5 else 223:] = 0
+                rec[k].append(a)
+    return rec
+
+
+def make_ac3enc_ref():
+    import json
+    assert H.have_refenc(), "oracle/_ref/ac3enc_ref.so missing: run `make -C oracle` in the build container"
+    d, meta = {}, {"kinds": ENC_KINDS, "full": [], "reinit": [], "assert_sites": {}}
+    sites = {}
+
+    def note_sites(R):
+        for line, n in R.assert_trips()[1].items():
+            sites[line] = sites.get(line, 0) + n
+
+    # ---- run-time tables (filled by AC3_encode_init) and init's decisions
+    R = H.RefEncoder()
+    triples = enc_init_triples()
+    d["init_args"] = np.array(triples, np.int32)
+    d["init_ret"] = np.array([R.init(*t) for t in triples], np.int32)
+    R = H.RefEncoder()
+    assert R.init(48000, 384000, 6) == 1536
+    for name in H.REFENC_TABLES:
+        d["tab_" + name] = R.array(name)
+    # ---- full records
+    for name, *cfg in ENC_FULL:
+        R = H.RefEncoder()
+        rec = enc_ref_stream(R, tuple(cfg), True)
+        note_sites(R)
+        freq, bitrate, nch, chmap, kind, seed, frames = cfg
+        meta["full"].append({"name": name, "freq": freq, "bitrate": bitrate, "channels": nch, "chmap": list(chmap[:nch]), "kind": kind,
+                             "seed": seed, "frames": frames})
+        d["full_%s_pcm_sha" % name] = rec["pcm_sha"]
+        d["full_%s_frames" % name] = np.stack(rec["frames"])
+        d["full_%s_status" % name] = np.array([rec["ret"], rec["yack"], rec["trips"]], np.int32).T      # [frames][returned size, search failed, assertions tripped]
+        d["full_%s_snr" % name] = np.stack(rec["snr"]).astype(np.int32)                               # [frames][csnroffst, fsnroffst x 6, fgaincod x 6]
+        for k in ENC_STAGES:
+            d["full_%s_%s" % (name, k)] = np.stack(rec[k])
+    # ---- re-initialisation: A, AC3_encode_init again, B in one instance; and B in a fresh one
+    for name, a, b in ENC_REINIT:
+        R = H.RefEncoder()
+        ra = enc_ref_stream(R, a, False)
+        rb = enc_ref_stream(R, b, False)
+        note_sites(R)
+        R2 = H.RefEncoder()
+        rc = enc_ref_stream(R2, b, False)
+        assert not any(ra["yack"] + rb["yack"] + rc["yack"])
+        ent = {"name": name}
+        for tag, cfg in (("a", a), ("b", b)):
+            freq, bitrate, nch, chmap, kind, seed, frames = cfg
+            ent[tag] = {"freq": freq, "bitrate": bitrate, "channels": nch, "chmap": list(chmap[:nch]), "kind": kind, "seed": seed, "frames": frames}
+        meta["reinit"].append(ent)
+        d["reinit_%s_a_pcm_sha" % name], d["reinit_%s_b_pcm_sha" % name] = ra["pcm_sha"], rb["pcm_sha"]
+        d["reinit_%s_a_frames" % name] = np.stack(ra["frames"])
+        d["reinit_%s_b_frames" % name] = np.stack(rb["frames"])            # B after A in the same instance
+        d["reinit_%s_b_fresh_frames" % name] = np.stack(rc["frames"])      # B in an instance of its own
+    # ---- the wide matrix, by digest
+    wide = enc_wide_matrix()
+    chmaps = sorted({c[3] for c in wide})
+    cfgs, shas, dig, status = [], [], [], []
+    for cfg in wide:
+        R = H.RefEncoder()
+        rec = enc_ref_stream(R, cfg, False)
+        note_sites(R)
+        freq, bitrate, nch, chmap, kind, seed, frames = cfg
+        cfgs.append([freq, bitrate, nch, chmaps.index(chmap), ENC_KINDS.index(kind), seed, frames])
+        shas.append(rec["pcm_sha"])
+        dig += [enc_sha(fr) for fr in rec["frames"]]
+        status += list(zip(rec["ret"], rec["yack"], rec["trips"]))
+    d["wide_cfg"] = np.array(cfgs, np.int32)              # [streams][freq, bitrate, channels, chmap index, kind index, seed, frames]
+    d["wide_chmaps"] = np.array(chmaps, np.uint8)
+    d["wide_pcm_sha"] = np.stack(shas)
+    d["wide_digest"] = np.stack(dig)                      # [all frames, stream after stream][32]: SHA-256 of the frame's bytes
+    d["wide_status"] = np.array(status, np.int32)         # [all frames][returned size, search failed, assertions tripped]
+    meta["assert_sites"] = {str(k): v for k, v in sorted(sites.items())}
+    meta["counts"] = {"full_frames": sum(e["frames"] for e in meta["full"]), "wide_streams": len(wide), "wide_frames": len(dig),
+                      "wide_failed_searches": int(d["wide_status"][:, 1].sum()), "init_triples": len(triples),
+                      "init_accepted": int((d["init_ret"] > 0).sum())}
+    np.savez_compressed(os.path.join(OUT, "ac3enc_ref.npz"), **d)
+    with open(os.path.join(OUT, "ac3enc_ref.json"), "w") as f:
+        json.dump(meta, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("ac3enc_ref.npz", os.path.getsize(os.path.join(OUT, "ac3enc_ref.npz")), meta["counts"], meta["assert_sites"])
+
+
 def main():
     if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "mixflip":
         make_mixflip()
@@ -134,6 +318,9 @@ def main():
         return
     if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "a52dec_drivers":
         make_a52dec_drivers()
+        return
+    if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "ac3enc_ref":
+        make_ac3enc_ref()
         return
     make_ac3tab()
     assert H.have_ref(), "oracle/_ref/liba52_ref.so missing: run `make -C oracle` in the build container"
@@ -208,7 +395,7 @@ def main():
                         init=np.array(res_init, np.float64), coeff=np.array(res_coeff, np.float32),
                         mixed=np.array(res_mix, np.float32), upmixed=np.array(res_up, np.float32))
 
-    # ---- encoder oracle regression pin (PARITY UNPINNED vs ac3enc) --------
+    # ---- encoder oracle stage dumps (the same stream from ac3enc itself: ENC_FULL "51_384k") --------
     L = H.orc()
     pcm_in = H.gen_pcm(3, 6, seed=7, kind="tones")
     fb = H.ci()
@@ -253,6 +440,7 @@ def main():
     np.savez_compressed(os.path.join(OUT, "packer.npz"), **d)
     make_mixflip()
     make_a52dec_drivers()
+    make_ac3enc_ref()
 
     for fn in sorted(os.listdir(OUT)):
         if fn.endswith(".npz"):

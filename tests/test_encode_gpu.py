@@ -1,8 +1,9 @@
 """GPU parity: ac3mi_encode_batch (HIP) vs the ac3enc restatement in oracle/.
 
 Reference behaviour under test: AC3_encode_frame (src/ac3enc/ac3enc.cpp:1640-1763).  Integer work:
-every stage and the final bitstream must be BIT-EXACT against the oracle.  (The oracle itself is
-"parity unpinned" against ac3enc - it cannot be built in this image - see DESIGN.md §3.)
+every stage and the final bitstream must be BIT-EXACT against the oracle.  (The oracle itself is pinned
+byte for byte to ac3enc by tests/test_oracle_vs_ac3enc.py; tests/test_encode_ref_gpu.py holds the engine
+against frames recorded from ac3enc directly - see DESIGN.md §3.)
 """
 import ctypes
 
@@ -215,9 +216,10 @@ def test_encode_extreme_levels(engine, kind, nch, bitrate):
 def test_starved_bit_rate_is_survivable(engine):
     """6 channels of noise at 64 kbps: AC3_encode_init accepts it, but not even csnroffst 0 fits the frame, the
     reference prints "Yack, Error !!!" (ac3enc.cpp:930-933), keeps going with stale offsets and writes past the frame
-    size; the oracle gives up (-1).  There is nothing to be bit-exact with.  The engine must stay inside its buffers,
-    produce a frame-sized output with a header, leave neighbours alone and keep working: a stream with the same
-    samples at 384 kbps, encoded right after with the same context, is still byte-exact."""
+    size (what lands inside the frame is recorded in tests/golden/ac3enc_ref.npz, stream "51_starved", and compared in
+    tests/test_encode_ref_gpu.py).  Here: the engine must stay inside its buffers, produce a frame-sized output with a
+    header, leave neighbours alone and keep working: a stream with the same samples at 384 kbps, encoded right after with
+    the same context, is still byte-exact."""
     import torch
     pkg = H.pkg()
     S, F = 3, 2

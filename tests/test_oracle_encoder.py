@@ -1,5 +1,5 @@
-"""CPU: what CAN be checked about the encoder oracle without ac3enc itself (which needs <windows.h> and
-is unbuildable in this image -> bit-exact parity with src/ac3enc is UNPINNED):
+"""CPU: what the encoder oracle's frames must satisfy whatever the reference's encoder writes (byte-for-byte parity
+with src/ac3enc is the business of tests/test_oracle_vs_ac3enc.py, against fixtures recorded from ac3enc itself):
 
  * both CRCs of every frame verify (ac3enc.cpp:1599-1638; crc1 covers the first 5/8, crc2 the rest)
  * the frame is exactly filled: sync word, header fields, zero padding only at the tail

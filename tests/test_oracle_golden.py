@@ -2,8 +2,10 @@
 
 tests/golden/decode_*.npz, imdct.npz and downmix.npz hold outputs of the REAL liba52 (built from
 /root/reference by oracle/Makefile in the build container; generator: tests/golden/make_golden.py).
-The decode oracle must reproduce them BIT FOR BIT.  encoder.npz is a regression pin of our own
-encoder oracle only (parity with ac3enc is unpinned: it cannot be compiled in this image).
+The decode oracle must reproduce them BIT FOR BIT.  encoder.npz holds the encoder oracle's output and stage
+dumps for one 5.1 stream; the same stream is recorded from the reference's own encoder in ac3enc_ref.npz (stream
+"51_384k"), and the test below holds the two files against each other: what encoder.npz pins is what ac3enc writes.
+The wide comparison with ac3enc is tests/test_oracle_vs_ac3enc.py.
 """
 import ctypes
 import os
@@ -125,9 +127,21 @@ def test_downmix_vectors_bit_exact():
 
 
 def test_encoder_oracle_regression():
-    """Regression pin of our encoder oracle (bitstream + every stage).  NOT a parity claim against
-    ac3enc: that is unpinned."""
+    """The encoder oracle's bitstream and stages against encoder.npz - and encoder.npz against the record of the same
+    stream from the reference's own encoder (ac3enc_ref.npz, stream "51_384k"): frames, mdct_coef,
+    exponent, encoded_exp, bap, exp_strategy, exp_samples, the search's offsets and the run-time tables."""
     d = _load("encoder.npz")
+    r = _load("ac3enc_ref.npz")
+    assert np.array_equal(H.gen_pcm(3, 6, seed=7, kind="tones"), d["pcm_in"])          # the input both files were recorded from
+    assert np.array_equal(d["frames"], r["full_51_384k_frames"])
+    for ours, theirs in (("mdct", "mdct_coef"), ("exponent", "exponent"), ("exp_strategy", "exp_strategy"), ("exp_samples", "exp_samples")):
+        assert np.array_equal(d[ours], r["full_51_384k_" + theirs]), ours
+    for key in ("encoded_exp", "bap"):
+        assert np.array_equal(d[key][:, :, :5, :223], r["full_51_384k_" + key][:, :, :5, :223]), key
+        assert np.array_equal(d[key][:, :, 5, :7], r["full_51_384k_" + key][:, :, 5, :7]), key
+    assert np.array_equal(d["snroffst"], r["full_51_384k_snr"][:, :2])
+    for key in ("costab", "sintab", "xcos1", "xsin1", "crc_table"):
+        assert np.array_equal(d[key], r["tab_" + key]), key
     L = H.orc()
     fb = H.ci()
     h = L.orc_ac3enc_init(48000, 384000, 6, ctypes.byref(fb))
@@ -168,7 +182,7 @@ def test_encoder_rejects_bad_parameters():
 # ---- encoder spec tables: pinned to the reference's own header ----------------------------------------------------
 # tests/golden/ac3tab.npz is frozen from src/ac3enc/ac3tab.h:3-171, compiled unmodified behind
 # oracle/ref_ac3tab_glue.cpp (oracle/Makefile, `make_golden.py --only ac3tab`).  Both the encoder oracle and the
-# engine must use exactly these numbers.  What stays PARITY UNPINNED is the code of ac3enc.cpp itself.
+# engine must use exactly these numbers.  (The code of ac3enc.cpp itself is pinned by tests/test_oracle_vs_ac3enc.py.)
 
 _SPEC_ORDER = ("ac3_window", "latab", "hth", "baptab", "bndsz", "sdecaytab", "fdecaytab", "sgaintab", "dbkneetab",
                "floortab", "fgaintab", "ac3_freqs", "ac3_bitratetab")
