@@ -206,12 +206,12 @@ def test_matrix_rates_do_not_starve_the_plain_encoder():
     its rates the plain encoder (the oracle, mode 0) does not fail on the same content, and at the lower rate of each
     channel count it does not saturate at csnroffst 63 on the matrix's six programmes (the DRC programme ends in silence)."""
     from tests import test_frame_budget_gpu as G
-    from tests.test_drc_gpu import _programme
+    from tests._tools import programme
     for nch in range(1, 7):
         chmap = H.CHMAP6 if nch == 6 else tuple(range(8))
         for sr in (48000, 44100):
             for hi in (0, 1):
-                streams = list(G.matrix_content(nch)) + ([_programme(nch, seed=11 + nch)[0]] if nch in (1, 2, 6) else [])
+                streams = list(G.matrix_content(nch)) + ([programme(nch, seed=11 + nch)[0]] if nch in (1, 2, 6) else [])
                 for k, pcm in enumerate(streams):
                     _, _, _, snr, curves = oracle_encode(pcm, nch, G.RATES[nch][hi], sr, chmap)
                     start = 40

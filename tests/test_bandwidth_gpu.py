@@ -9,93 +9,11 @@ import numpy as np
 import pytest
 
 from tests import _harness as H
+from tests import _tools as T
 from tests import bandwidth_model as W
 from tests import rematrix_model as M
-from tests.test_coupling_gpu import _content, _decodes_cleanly, _gpu_decode, _parse_block0
 
 pytestmark = pytest.mark.gpu
-
-RATE = {1: 192000, 2: 192000, 6: 384000}
-ACMOD = {1: 1, 2: 2, 6: 7}
-
-
-def _chmap(nch):
-    return H.CHMAP6 if nch == 6 else tuple(range(nch))
-
-
-def _encode(engine, pcm, nch, bw=(0, 50), cpl=(0, 0), bsw=0, remat=0, taps=False, last=None, csnr=None, rate=None,
-            sample_rate=48000):
-    """pcm [S][F*1536][nch] s16 -> frames [S][F][fb][, taps] with bandwidth `bw` = (mode, chbwcod) (None: leave the
-    context's setting), coupling `cpl` = (mode, begf), block switching and rematrixing, one call."""
-    import torch
-    pkg = H.pkg()
-    S = pcm.shape[0]
-    F = pcm.shape[1] // 1536
-    enc = pkg.EncodeDesc(sample_rate, rate or RATE[nch], nch)
-    if last is None:
-        last = torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda")
-    if csnr is None:
-        csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-    if bw is not None:
-        engine.set_encode_bandwidth(*bw)
-    engine.set_encode_coupling(*cpl)
-    engine.set_encode_block_switch(bsw)
-    engine.set_encode_rematrix(remat)
-    try:
-        r = engine.encode_batch(enc, torch.from_numpy(np.ascontiguousarray(pcm).reshape(S, F, 1536, nch)).cuda(), _chmap(nch),
-                                last, csnr, taps=taps)
-        engine.sync()
-    finally:
-        if bw is not None:
-            engine.set_encode_bandwidth(0)
-        engine.set_encode_coupling(0, 0)
-        engine.set_encode_block_switch(0)
-        engine.set_encode_rematrix(0)
-    fb = enc.frame_bytes()
-    if taps:
-        return r[0].cpu().numpy()[:, :, :fb], {k: v.cpu().numpy() for k, v in r[1].items()}
-    return r.cpu().numpy()[:, :, :fb]
-
-
-class _Bits:
-    def __init__(self, frame):
-        self.b = np.unpackbits(np.asarray(frame, np.uint8))
-        self.p = 0
-
-    def get(self, n):
-        v = 0
-        for _ in range(n):
-            v = v << 1 | int(self.b[self.p])
-            self.p += 1
-        return v
-
-
-def _block0(frame, nch):
-    """An uncoupled frame's block 0 (this encoder's BSI: no optional fields) -> (rematrixing flags or None, [chbwcod of
-    each full-bandwidth channel]).  Block 0 sends exponents for every channel, so every channel sends chbwcod."""
-    acmod, nfbw = ACMOD[nch], min(nch, 5)
-    r = _Bits(frame)
-    r.get(40)
-    r.get(5)
-    r.get(3)
-    assert r.get(3) == acmod
-    if (acmod & 1) and acmod != 1:
-        r.get(2)
-    if acmod & 4:
-        r.get(2)
-    if acmod == 2:
-        r.get(2)
-    r.get(14)
-    r.get(2 * nfbw + 1)                         # blksw, dithflag, dynrnge
-    assert r.get(1) == 1 and r.get(1) == 0      # cplstre, cplinu
-    flags = None
-    if acmod == 2:
-        flags = sum(r.get(1) << i for i in range(4)) if r.get(1) else None      # (rematflg[0] first)
-    strat = [r.get(2) for _ in range(nfbw)]
-    if nch == 6:
-        r.get(1)
-    assert all(strat)
-    return flags, [r.get(6) for _ in range(nfbw)]
 
 
 # encoder bap (0..15) -> liba52's convention (the GPU decoder's tap): grouped codes negative, plain widths in bits
@@ -105,11 +23,11 @@ _BAP52 = np.array([0, -1, -2, 3, -3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16], np.i
 def _check_band_limited(engine, pcm, nch, c, frames, t1, t0):
     n, nfbw = W.nbc(c), min(nch, 5)
     S, F = frames.shape[:2]
-    _decodes_cleanly(engine, frames, nch)
+    T.decodes_cleanly(frames, *T.layout_of(nch), engine=engine)
     for s in range(S):
         for f in range(F):
-            assert _block0(frames[s, f], nch)[1] == [c] * nfbw, (s, f)
-    _, status, _, tp = _gpu_decode(engine, frames, nch, taps=True)
+            assert T.uncoupled_view(frames[s, f], nch)[1] == [c] * nfbw, (s, f)
+    _, status, tp = T.decode(engine, frames, *T.layout_of(nch), taps=True)
     assert (status & 0x1ff).max() == 0
     o = 1 if nch == 6 else 0                    # (the decoder's planes put the LFE first)
     assert not tp["coef"][:, :, :, o:o + nfbw, n:].any()
@@ -144,26 +62,26 @@ def test_chbwcod_50_is_mode0(engine, nch):
         combos += [dict(cpl=(1, 0)), dict(cpl=(1, 2)), dict(cpl=(1, 2), bsw=1)]
     for kw in combos:
         for kind in ("music", "attack"):
-            pcm = _content(kind, nch, 2, 3, seed=11)
-            f0 = _encode(engine, pcm, nch, bw=(0, 50), **kw)
-            f1 = _encode(engine, pcm, nch, bw=(1, 50), **kw)
+            pcm = T.content(kind, nch, 2, 3, seed=11)
+            f0 = T.encode(engine, pcm, bw=(0, 50), **kw)
+            f1 = T.encode(engine, pcm, bw=(1, 50), **kw)
             assert np.array_equal(f1, f0), (kw, kind)
-    pcm = _content("music", nch, 2, 3, seed=11)
-    assert np.array_equal(_encode(engine, pcm, nch, bw=(0, 50)),
-                          np.stack([H.orc_encode(p, nch, RATE[nch], chmap=(_chmap(nch) + (0,) * 8)[:8]) for p in pcm]))
+    pcm = T.content("music", nch, 2, 3, seed=11)
+    assert np.array_equal(T.encode(engine, pcm, bw=(0, 50)),
+                          np.stack([H.orc_encode(p, nch, T.RATE[nch], chmap=(T.chmap_of(nch) + (0,) * 8)[:8]) for p in pcm]))
 
 
 @pytest.mark.parametrize("nch", [1, 2, 6])
 @pytest.mark.parametrize("c", [0, 13, 32, 49])
 def test_band_limited_streams(engine, nch, c):
     for F in (1, 4):
-        pcm = _content("music", nch, 2, F, seed=17 + c)
-        _, t0 = _encode(engine, pcm, nch, taps=True)
+        pcm = T.content("music", nch, 2, F, seed=17 + c)
+        _, t0 = T.encode(engine, pcm, taps=True)
         for pack in (1, 2):
             engine.set_encode_mode(pack)
             try:
-                frames, t1 = _encode(engine, pcm, nch, bw=(1, c), taps=True)
-                plain = _encode(engine, pcm, nch, bw=(1, c))
+                frames, t1 = T.encode(engine, pcm, bw=(1, c), taps=True)
+                plain = T.encode(engine, pcm, bw=(1, c))
             finally:
                 engine.set_encode_mode(0)
             assert np.array_equal(plain, frames)            # (taps do not change the bytes)
@@ -174,23 +92,23 @@ def test_band_limited_streams(engine, nch, c):
                                          (2, 64000, 32000), (6, 224000, 48000), (6, 384000, 48000), (6, 448000, 44100),
                                          (2, 48000, 24000)])
 def test_mode2_follows_the_table(engine, nch, rate, sr):
-    pcm = _content("music", nch, 1, 2, seed=23)
+    pcm = T.content("music", nch, 1, 2, seed=23)
     c = W.mode2_chbwcod(sr, rate, nch)
-    frames = _encode(engine, pcm, nch, bw=(2, 7), rate=rate, sample_rate=sr)
+    frames = T.encode(engine, pcm, bw=(2, 7), rate=rate, sr=sr)
     for f in range(frames.shape[1]):
-        assert _block0(frames[0, f], nch)[1] == [c] * min(nch, 5)
-    assert np.array_equal(frames, _encode(engine, pcm, nch, bw=(1, c), rate=rate, sample_rate=sr))
+        assert T.uncoupled_view(frames[0, f], nch)[1] == [c] * min(nch, 5)
+    assert np.array_equal(frames, T.encode(engine, pcm, bw=(1, c), rate=rate, sr=sr))
 
 
 @pytest.mark.parametrize("c", [13, 32])
 def test_rematrixing_band_ends_at_nbc(engine, c):
     """Coded rows and block-0 flags of 2/0 with rematrixing: the model with the fourth band [61, nbc)."""
     S, F, n = 2, 3, W.nbc(c)
-    pcm = _content("identical", 2, 1, F, seed=29)
-    pcm = np.concatenate([pcm, _content("music", 2, 1, F, seed=31)])
-    _, t0 = _encode(engine, pcm, 2, taps=True)
-    frames, t1 = _encode(engine, pcm, 2, bw=(1, c), remat=1, taps=True)
-    _decodes_cleanly(engine, frames, 2)
+    pcm = T.content("identical", 2, 1, F, seed=29)
+    pcm = np.concatenate([pcm, T.content("music", 2, 1, F, seed=31)])
+    _, t0 = T.encode(engine, pcm, taps=True)
+    frames, t1 = T.encode(engine, pcm, bw=(1, c), remat=1, taps=True)
+    T.decodes_cleanly(frames, 2, 0, engine=engine)
     n_on = 0
     for s in range(S):
         v = M.block_v(pcm[s], (0, 1))
@@ -201,7 +119,7 @@ def test_rematrixing_band_ends_at_nbc(engine, c):
                 fl = W.remat_flags(rows[0], rows[1], vl - 9, vr - 9, n)
                 n_on += fl != 0
                 if b == 0:
-                    assert _block0(frames[s, f], 2)[0] == fl, (s, f)
+                    assert T.uncoupled_view(frames[s, f], 2)[0] == fl, (s, f)
                 if not fl:
                     assert np.array_equal(t1["mdct"][s, f, b, :, :n], t0["mdct"][s, f, b, :, :n])
                     continue
@@ -226,27 +144,27 @@ def test_coupling_ends_at_cplendmant(engine, nch):
     coefficient from bin 169 on; begf 11 is beyond cplendf + 2: the bytes of coupling off at the same bandwidth."""
     begf, c, S, F = 2, 32, 2, 3
     nfbw = min(nch, 5)
-    pcm = _content("music", nch, S, F, seed=37)
-    _, t0 = _encode(engine, pcm, nch, taps=True)
-    frames = _encode(engine, pcm, nch, bw=(1, c), cpl=(1, begf))
-    _decodes_cleanly(engine, frames, nch)
+    pcm = T.content("music", nch, S, F, seed=37)
+    _, t0 = T.encode(engine, pcm, taps=True)
+    frames = T.encode(engine, pcm, bw=(1, c), cpl=(1, begf))
+    T.decodes_cleanly(frames, *T.layout_of(nch), engine=engine)
     n_on = 0
     for s in range(S):
         for f in range(F):
             want = W.cpl_decide(t0["mdct"][s, f], t0["exp_samples"][s, f], nfbw, begf, c)
-            cplinu, chincpl, bf, ef, co = _parse_block0(frames[s, f], nch)
+            cplinu, chincpl, bf, ef, co = T.coupling_view(frames[s, f], nch)
             assert cplinu == want[0], (s, f)
             if cplinu:
                 n_on += 1
                 assert chincpl == (1 << nfbw) - 1 and bf == begf and ef == W.cplendf(c) == 8
                 assert [m for m, _ in co] == want[1] and [cd for _, cd in co] == want[2], (s, f)
             else:
-                assert _block0(frames[s, f], nch)[1] == [c] * nfbw
+                assert T.uncoupled_view(frames[s, f], nch)[1] == [c] * nfbw
     assert n_on > 0
-    _, status, _, tp = _gpu_decode(engine, frames, nch, taps=True)
+    _, status, tp = T.decode(engine, frames, *T.layout_of(nch), taps=True)
     o = 1 if nch == 6 else 0
     assert (status & 0x1ff).max() == 0 and not tp["coef"][:, :, :, o:o + nfbw, W.cplendmant(c):].any()
-    assert np.array_equal(_encode(engine, pcm, nch, bw=(1, c), cpl=(1, 11)), _encode(engine, pcm, nch, bw=(1, c)))
+    assert np.array_equal(T.encode(engine, pcm, bw=(1, c), cpl=(1, 11)), T.encode(engine, pcm, bw=(1, c)))
 
 
 def test_call_shapes_agree(engine):
@@ -256,31 +174,31 @@ def test_call_shapes_agree(engine):
     S, F = 3, 4
     perm = torch.tensor([2, 0, 1], dtype=torch.int32, device="cuda")
     for nch, kw in ((6, dict(bw=(1, 32))), (2, dict(bw=(1, 13), cpl=(1, 1), remat=1)), (6, dict(bw=(2, 0), rate=224000))):
-        pcm = _content("music", nch, S, F, seed=41)
-        whole = _encode(engine, pcm, nch, **kw)
+        pcm = T.content("music", nch, S, F, seed=41)
+        whole = T.encode(engine, pcm, **kw)
         for pack in (1, 2):
             engine.set_encode_mode(pack)
             try:
-                assert np.array_equal(_encode(engine, pcm, nch, **kw), whole), (nch, pack)
+                assert np.array_equal(T.encode(engine, pcm, **kw), whole), (nch, pack)
             finally:
                 engine.set_encode_mode(0)
         last = torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda")
         csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-        a = _encode(engine, pcm[:, :2 * 1536], nch, last=last, csnr=csnr, **kw)
-        b = _encode(engine, pcm[:, 2 * 1536:], nch, last=last, csnr=csnr, **kw)
+        a = T.encode(engine, pcm[:, :2 * 1536], last=last, csnr=csnr, **kw)
+        b = T.encode(engine, pcm[:, 2 * 1536:], last=last, csnr=csnr, **kw)
         assert np.array_equal(np.concatenate([a, b], 1), whole), nch
         last6 = torch.zeros((S, 6, 256), dtype=torch.int16, device="cuda")
         csnr6 = torch.full((S,), 40, dtype=torch.int32, device="cuda")
         engine._check(engine.lib.ac3mi_set_state_slots(ctypes.c_void_p(engine.ctx), ctypes.c_void_p(perm.data_ptr())))
         try:
-            got = [_encode(engine, pcm[:, f * 1536:(f + 1) * 1536], nch, last=last6.view(-1)[:S * nch * 256].view(S, nch, 256),
+            got = [T.encode(engine, pcm[:, f * 1536:(f + 1) * 1536], last=last6.view(-1)[:S * nch * 256].view(S, nch, 256),
                            csnr=csnr6, **kw) for f in range(F)]
         finally:
             engine._check(engine.lib.ac3mi_set_state_slots(ctypes.c_void_p(engine.ctx), None))
         assert np.array_equal(np.concatenate(got, 1), whole), nch
         engine._check(engine.lib.ac3mi_set_tile_frames(ctypes.c_void_p(engine.ctx), ctypes.c_longlong(4)))
         try:
-            tiled = _encode(engine, pcm, nch, **kw)
+            tiled = T.encode(engine, pcm, **kw)
         finally:
             engine._check(engine.lib.ac3mi_set_tile_frames(ctypes.c_void_p(engine.ctx), ctypes.c_longlong(0)))
         assert np.array_equal(tiled, whole), nch
@@ -290,7 +208,7 @@ def test_transcode_equals_decode_then_encode(engine):
     import torch
     pkg = H.pkg()
     S, F, nch = 3, 3, 2
-    src = _encode(engine, _content("music", nch, S, F, seed=101), nch)
+    src = T.encode(engine, T.content("music", nch, S, F, seed=101))
     fb = src.shape[2]
     stride = (fb + 3) & ~3
     buf = np.zeros((S, F, stride), np.uint8)
@@ -325,9 +243,9 @@ def test_transcode_equals_decode_then_encode(engine):
     assert int((status.cpu() & 0x1ff).max()) == 0
     assert torch.equal(out.cpu(), out2.cpu()) and torch.equal(last.cpu(), last2.cpu()) and torch.equal(csnr.cpu(), csnr2.cpu())
     o = out.cpu().numpy()[:, :, :fb]
-    _decodes_cleanly(engine, o, 2)
+    T.decodes_cleanly(o, 2, 0, engine=engine)
     # (music at 96 kb/s: chbwcod 25 from the table, cplendf 6 in coupled frames)
-    assert any(_parse_block0(o[s, f], 2)[3] == 6 for s in range(S) for f in range(F))
+    assert any(T.coupling_view(o[s, f], 2)[3] == 6 for s in range(S) for f in range(F))
 
 
 def test_large_batch(engine):
@@ -335,17 +253,17 @@ def test_large_batch(engine):
     import bench
     S, c = 4096, 13
     rng = np.random.default_rng(91)
-    pool = np.concatenate([_content(k, 6, 4, 1, seed=92) for k in ("music", "identical", "noise")])
+    pool = np.concatenate([T.content(k, 6, 4, 1, seed=92) for k in ("music", "identical", "noise")])
     pcm = np.stack([pool[rng.integers(0, len(pool))] for _ in range(S)])
     pcm = (pcm.astype(np.int32) * rng.uniform(0.3, 1.0, (S, 1, 1))).astype(np.int16)
     for kw in (dict(), dict(cpl=(1, 0))):
-        frames = _encode(engine, pcm, 6, bw=(1, c), **kw)
+        frames = T.encode(engine, pcm, bw=(1, c), **kw)
         assert bench.ac3_crc_ok(frames.reshape(-1, frames.shape[2])) == 0
-        got, status, flags = _gpu_decode(engine, frames, 6)
+        got, status, _ = T.decode(engine, frames, 7, 1)
         assert (status & 0x1ff).max() == 0
-        ref, errs, _ = H.orc_decode(frames[:64, 0], flags, 1.0, 0.0)
+        ref, errs, _ = H.orc_decode(frames[:64, 0], 7 | 16, 1.0, 0.0)
         assert errs == 0
-        _, _, _, tp = _gpu_decode(engine, frames[:256], 6, taps=True)
+        _, _, tp = T.decode(engine, frames[:256], 7, 1, taps=True)
         assert not tp["coef"][:, :, :, 1:6, W.nbc(c):].any()
 
 
@@ -356,12 +274,12 @@ def test_coupled_exponent_tap_is_reproducible(engine):
     import torch
     pkg = H.pkg()
     S, F, nch, c = 4, 2, 6, 13
-    pcm = _content("music", nch, S, F, seed=59)
+    pcm = T.content("music", nch, S, F, seed=59)
     enc = pkg.EncodeDesc(48000, 384000, nch)
-    cm = (ctypes.c_uint8 * 8)(*(list(_chmap(nch)) + [0] * 8)[:8])
+    cm = (ctypes.c_uint8 * 8)(*(list(T.chmap_of(nch)) + [0] * 8)[:8])
     got = []
     for k, other in enumerate(("noise", "identical")):
-        _encode(engine, _content(other, nch, S, F, seed=61 + k), nch)          # (fills the workspace rows up to bin 223)
+        T.encode(engine, T.content(other, nch, S, F, seed=61 + k))          # (fills the workspace rows up to bin 223)
         t = {n: torch.full((S, F, 6, nch, 256), 0x5a, dtype=torch.uint8, device="cuda") for n in ("eexp", "bap")}
         tp = H.pkg().capi.EncodeTapsC(None, None, None, t["eexp"].data_ptr(), t["bap"].data_ptr(), None, None)
         last = torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda")
@@ -379,7 +297,7 @@ def test_coupled_exponent_tap_is_reproducible(engine):
             engine.set_encode_bandwidth(0)
             engine.set_encode_coupling(0, 0)
         got.append((out.cpu().numpy(), t["eexp"].cpu().numpy(), t["bap"].cpu().numpy()))
-    assert any(_parse_block0(got[0][0][s, f, :out.shape[2]], nch)[0] for s in range(S) for f in range(F))
+    assert any(T.coupling_view(got[0][0][s, f, :out.shape[2]], nch)[0] for s in range(S) for f in range(F))
     for a, b in zip(got[0], got[1]):
         assert np.array_equal(a, b)
 
@@ -426,18 +344,18 @@ def test_setter_rejects_bad_arguments(engine):
     for mode, c in ((-1, 50), (3, 50), (1, -1), (1, 51), (1, 60)):
         with pytest.raises(Exception):
             engine.set_encode_bandwidth(mode, c)
-    pcm = _content("music", 2, 1, 2, seed=47)
-    on = _encode(engine, pcm, 2, bw=(1, 13))
+    pcm = T.content("music", 2, 1, 2, seed=47)
+    on = T.encode(engine, pcm, bw=(1, 13))
     engine.set_encode_bandwidth(1, 13)
     try:
         with pytest.raises(Exception):
             engine.set_encode_bandwidth(1, 51)
-        assert np.array_equal(_encode(engine, pcm, 2, bw=None), on)     # the bad call left mode 1, chbwcod 13
+        assert np.array_equal(T.encode(engine, pcm, bw=T.KEEP), on)     # the bad call left mode 1, chbwcod 13
         engine.set_encode_bandwidth(2, 99)                              # (mode 2 and 0 ignore the argument)
         engine.set_encode_bandwidth(0, -5)
     finally:
         engine.set_encode_bandwidth(0)
-    assert np.array_equal(_encode(engine, pcm, 2, bw=None), _encode(engine, pcm, 2))
+    assert np.array_equal(T.encode(engine, pcm, bw=T.KEEP), T.encode(engine, pcm))
 
 
 def test_stream_layer_never_band_limits(engine):
@@ -460,9 +378,9 @@ def test_stream_layer_never_band_limits(engine):
         assert bytes(dst[:h.dst_used]) == want[:h.dst_used] and h.dst_used > 0
         # the bandwidth setting is still there for the batch calls (coupling off for this one, so that every frame is
         # an uncoupled one that sends chbwcod)
-        b = _encode(engine, np.asarray(pcm)[None], 6, bw=None, cpl=(0, 0))
-        assert not any(_parse_block0(b[0, f], 6)[0] for f in range(b.shape[1]))
-        assert all(_block0(b[0, f], 6)[1] == [0] * 5 for f in range(b.shape[1]))
+        b = T.encode(engine, np.asarray(pcm)[None], bw=T.KEEP, cpl=(0, 0))
+        assert not any(T.coupling_view(b[0, f], 6)[0] for f in range(b.shape[1]))
+        assert all(T.uncoupled_view(b[0, f], 6)[1] == [0] * 5 for f in range(b.shape[1]))
     finally:
         pool.close()
         engine.set_encode_bandwidth(0)
@@ -478,12 +396,12 @@ def test_quality_mode2_against_mode0(engine, nch, rate, min_off, min_snr):
     thresholds keep about half of each gain."""
     F = 6
     nfbw = min(nch, 5)
-    pcm = _content("music", nch, 1, F, seed=53)
+    pcm = T.content("music", nch, 1, F, seed=53)
     c = W.mode2_chbwcod(48000, rate, nch)
     n = W.nbc(c)
-    f0, t0 = _encode(engine, pcm, nch, taps=True, rate=rate)
-    f2, t2 = _encode(engine, pcm, nch, bw=(2, 0), taps=True, rate=rate)
-    _decodes_cleanly(engine, f2, nch)
+    f0, t0 = T.encode(engine, pcm, taps=True, rate=rate)
+    f2, t2 = T.encode(engine, pcm, bw=(2, 0), taps=True, rate=rate)
+    T.decodes_cleanly(f2, *T.layout_of(nch), engine=engine)
     o0 = (16 * t0["snroffst"][0, :, 0] + t0["snroffst"][0, :, 1]).astype(np.float64)
     o2 = (16 * t2["snroffst"][0, :, 0] + t2["snroffst"][0, :, 1]).astype(np.float64)
     x = t0["mdct"][0].astype(np.float64) * np.exp2(-(23.0 + t0["exp_samples"][0]))[..., None]
@@ -491,7 +409,7 @@ def test_quality_mode2_against_mode0(engine, nch, rate, min_off, min_snr):
     o = 1 if nch == 6 else 0
     snr = []
     for fr in (f0, f2):
-        coef = _gpu_decode(engine, fr, nch, taps=True)[3]["coef"][0].astype(np.float64)[:, :, o:o + nfbw, :n]
+        coef = T.decode(engine, fr, *T.layout_of(nch), taps=True)[2]["coef"][0].astype(np.float64)[:, :, o:o + nfbw, :n]
         snr.append(10 * np.log10((x ** 2).sum() / ((coef - x) ** 2).sum()))
     print("%d ch %d kb/s: chbwcod %d (nbc %d); 16 csnr + fsnr %s -> %s (mean %+.1f); coefficient SNR on [0, nbc) "
           "%.2f -> %.2f dB (%+.2f)" % (nch, rate // 1000, c, n, o0.tolist(), o2.tolist(), (o2 - o0).mean(), snr[0], snr[1],

@@ -8,100 +8,41 @@ import numpy as np
 import pytest
 
 from tests import _harness as H
+from tests import _tools as T
 from tests import block_switch_model as M
 
 pytestmark = pytest.mark.gpu
-
-RATE = {1: 192000, 2: 192000, 6: 384000}
-
-
-def _chmap(nch):
-    return H.CHMAP6 if nch == 6 else tuple(range(nch))
-
-
-def _acmod(nch):
-    return {1: 1, 2: 2, 6: 7}[nch]
-
-
-def _encode(engine, pcm, nch, mode, F=None, taps=False, last=None, csnr=None):
-    """pcm [S][F*1536][nch] s16 -> frames [S][F][fb] (numpy) with block switching `mode`, one call."""
-    import torch
-    pkg = H.pkg()
-    S = pcm.shape[0]
-    F = pcm.shape[1] // 1536
-    enc = pkg.EncodeDesc(48000, RATE[nch], nch)
-    if last is None:
-        last = torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda")
-    if csnr is None:
-        csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-    engine.set_encode_block_switch(mode)
-    try:
-        r = engine.encode_batch(enc, torch.from_numpy(np.ascontiguousarray(pcm).reshape(S, F, 1536, nch)).cuda(), _chmap(nch),
-                                last, csnr, taps=taps)
-        engine.sync()
-    finally:
-        engine.set_encode_block_switch(0)
-    fb = enc.frame_bytes()
-    if taps:
-        return r[0].cpu().numpy()[:, :, :fb], {k: v.cpu().numpy() for k, v in r[1].items()}
-    return r.cpu().numpy()[:, :, :fb]
-
-
-def _gpu_decode(engine, frames, nch, taps=True):
-    import torch
-    pkg = H.pkg()
-    S, F, fb = frames.shape
-    stride = (fb + 3) & ~3
-    buf = np.zeros((S, F, stride), np.uint8)
-    buf[:, :, :fb] = frames
-    lfe = 16 if nch == 6 else 0
-    dec = pkg.DecodeDesc(flags=_acmod(nch) | lfe, level=1.0, bias=0.0, dynrng=1, acmod=_acmod(nch), lfeon=1 if lfe else 0,
-                         frame_bytes=fb)
-    n_out = nch
-    delay = torch.zeros((S, n_out, 128), dtype=torch.float32, device="cuda")
-    lfsr = torch.ones((S,), dtype=torch.int16, device="cuda")
-    r = engine.decode_batch(dec, torch.from_numpy(buf).cuda(), delay, lfsr, taps=taps)
-    engine.sync()
-    return [x.cpu().numpy() if hasattr(x, "cpu") else {k: v.cpu().numpy() for k, v in x.items()} for x in r]
-
-
-def _pcm(kind, S, F, nch, seed):
-    if kind == "attack":
-        rng = np.random.default_rng(seed)
-        onsets = [1536 * f + 256 * int(rng.integers(0, 6)) + int(rng.integers(0, 256)) for f in range(F)]
-        return np.stack([M.attack_pcm(F, nch, [o + 37 * s for o in onsets], seed=seed + s) for s in range(S)])
-    return np.stack([H.gen_pcm(F, nch, seed=seed + s, kind=kind) for s in range(S)])
 
 
 @pytest.mark.parametrize("nch", [1, 2, 6])
 def test_off_is_the_reference(engine, nch):
     for kind in ("tones", "bursts", "impulses"):
-        pcm = _pcm(kind, 2, 2, nch, seed=31)
-        want = np.stack([H.orc_encode(p, nch, RATE[nch], chmap=(_chmap(nch) + (0,) * 8)[:8]) for p in pcm])
-        assert np.array_equal(_encode(engine, pcm, nch, 0), want), kind
-        _encode(engine, pcm, nch, 1)                    # on, then off again on the same context
-        assert np.array_equal(_encode(engine, pcm, nch, 0), want), kind
+        pcm = T.pcm(kind, 2, 2, nch, seed=31)
+        want = np.stack([H.orc_encode(p, nch, T.RATE[nch], chmap=(T.chmap_of(nch) + (0,) * 8)[:8]) for p in pcm])
+        assert np.array_equal(T.encode(engine, pcm, bsw=0), want), kind
+        T.encode(engine, pcm, bsw=1)                    # on, then off again on the same context
+        assert np.array_equal(T.encode(engine, pcm, bsw=0), want), kind
 
 
 @pytest.mark.parametrize("nch", [1, 2, 6])
 def test_on_without_transients_is_the_reference(engine, nch):
     for kind in ("music", "quiet", "silence"):
-        pcm = _pcm(kind, 2, 3, nch, seed=41).astype(np.float64)
+        pcm = T.pcm(kind, 2, 3, nch, seed=41).astype(np.float64)
         pcm *= np.minimum(1.0, np.arange(pcm.shape[1]) / 3072.0)[None, :, None]       # fade in: no onset against the zero history
         pcm = np.round(pcm).astype(np.int16)
         for p in pcm:
-            assert M.decisions(p, _chmap(nch), min(nch, 5)).sum() == 0, kind
-        want = np.stack([H.orc_encode(p, nch, RATE[nch], chmap=(_chmap(nch) + (0,) * 8)[:8]) for p in pcm])
-        assert np.array_equal(_encode(engine, pcm, nch, 1), want), kind
+            assert M.decisions(p, T.chmap_of(nch), min(nch, 5)).sum() == 0, kind
+        want = np.stack([H.orc_encode(p, nch, T.RATE[nch], chmap=(T.chmap_of(nch) + (0,) * 8)[:8]) for p in pcm])
+        assert np.array_equal(T.encode(engine, pcm, bsw=1), want), kind
 
 
 def _check_decisions(engine, frames, pcm, nch, lasts=None):
     S = frames.shape[0]
     nf = min(nch, 5)
-    pcm_out, status, taps = _gpu_decode(engine, frames, nch)
+    pcm_out, status, taps = T.decode(engine, frames, *T.layout_of(nch), taps=True)
     assert (status & 0x1ff).max() == 0
     for s in range(S):
-        want = M.decisions(pcm[s], _chmap(nch), nf, None if lasts is None else lasts[s])
+        want = M.decisions(pcm[s], T.chmap_of(nch), nf, None if lasts is None else lasts[s])
         assert np.array_equal(taps["blksw"][s], want), (s, np.argwhere(taps["blksw"][s] != want)[:8])
     return pcm_out
 
@@ -113,11 +54,11 @@ def test_decisions_equal_the_model(engine, nch, pack, F):
     engine.set_encode_mode(pack)
     try:
         for kind in ("impulses", "bursts", "strobe", "attack"):
-            pcm = _pcm(kind, 3, F, nch, seed=51)
-            frames = _encode(engine, pcm, nch, 1)
+            pcm = T.pcm(kind, 3, F, nch, seed=51)
+            frames = T.encode(engine, pcm, bsw=1)
             _check_decisions(engine, frames, pcm, nch)
             if kind in ("impulses", "attack"):
-                assert M.decisions(pcm[0], _chmap(nch), min(nch, 5)).sum() > 0
+                assert M.decisions(pcm[0], T.chmap_of(nch), min(nch, 5)).sum() > 0
     finally:
         engine.set_encode_mode(0)
 
@@ -127,13 +68,13 @@ def test_split_call_and_state_slots(engine, nch):
     """Two calls of two frames each give the bytes of one call of four; so do state slots in a permuted order."""
     import torch
     S, F = 3, 4
-    pcm = _pcm("attack", S, F, nch, seed=61)
-    whole = _encode(engine, pcm, nch, 1)
+    pcm = T.pcm("attack", S, F, nch, seed=61)
+    whole = T.encode(engine, pcm, bsw=1)
     _check_decisions(engine, whole, pcm, nch)
     last = torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda")
     csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-    a = _encode(engine, pcm[:, :2 * 1536], nch, 1, last=last, csnr=csnr)
-    b = _encode(engine, pcm[:, 2 * 1536:], nch, 1, last=last, csnr=csnr)
+    a = T.encode(engine, pcm[:, :2 * 1536], bsw=1, last=last, csnr=csnr)
+    b = T.encode(engine, pcm[:, 2 * 1536:], bsw=1, last=last, csnr=csnr)
     assert np.array_equal(np.concatenate([a, b], 1), whole)
     # state slots: stream s keeps its history in slot perm[s] (stride 6 channels); one frame per call
     perm = torch.tensor([2, 0, 1], dtype=torch.int32, device="cuda")
@@ -143,10 +84,10 @@ def test_split_call_and_state_slots(engine, nch):
     try:
         got = []
         for f in range(F):
-            enc = H.pkg().EncodeDesc(48000, RATE[nch], nch)
+            enc = H.pkg().EncodeDesc(48000, T.RATE[nch], nch)
             engine.set_encode_block_switch(1)
             out = engine.encode_batch(enc, torch.from_numpy(np.ascontiguousarray(pcm[:, f * 1536:(f + 1) * 1536])).cuda().view(S, 1, 1536, nch),
-                                      _chmap(nch), last6.view(-1)[:S * nch * 256].view(S, nch, 256), csnr6)
+                                      T.chmap_of(nch), last6.view(-1)[:S * nch * 256].view(S, nch, 256), csnr6)
             engine.sync()
             got.append(out.cpu().numpy()[:, :, :whole.shape[2]])
     finally:
@@ -157,13 +98,13 @@ def test_split_call_and_state_slots(engine, nch):
 
 @pytest.mark.parametrize("nch", [1, 2, 6])
 def test_switched_streams_decode_like_liba52(engine, nch):
-    pcm = _pcm("attack", 2, 3, nch, seed=71)
-    pcm[1] = _pcm("impulses", 1, 3, nch, seed=72)[0]
-    frames = _encode(engine, pcm, nch, 1)
+    pcm = T.pcm("attack", 2, 3, nch, seed=71)
+    pcm[1] = T.pcm("impulses", 1, 3, nch, seed=72)[0]
+    frames = T.encode(engine, pcm, bsw=1)
     got = _check_decisions(engine, frames, pcm, nch)
     lfe = 16 if nch == 6 else 0
     for s in range(2):
-        ref, errs, _ = H.orc_decode(frames[s], _acmod(nch) | lfe, 1.0, 0.0)
+        ref, errs, _ = H.orc_decode(frames[s], T.ACMOD[nch] | lfe, 1.0, 0.0)
         assert errs == 0
         err = got[s].astype(np.float64) - ref.reshape(got[s].shape)
         assert H.rms(err) <= 1e-6 and np.abs(err).max() <= 4e-6, (H.rms(err), np.abs(err).max())
@@ -180,9 +121,9 @@ def test_transform_accuracy(engine):
     """Rows from the MDCT tap against A/52's transforms in float64 on the same windowed, shifted input (X = -2/N sum ...,
     N = 512 long, 256 short, coef[2k] / coef[2k + 1] = the first / second short transform): no fitted scale."""
     nch = 1
-    pcm = _pcm("attack", 2, 3, nch, seed=81)
-    frames, taps = _encode(engine, pcm, nch, 1, taps=True)
-    sw = _gpu_decode(engine, frames, nch)[2]["blksw"]
+    pcm = T.pcm("attack", 2, 3, nch, seed=81)
+    frames, taps = T.encode(engine, pcm, bsw=1, taps=True)
+    sw = T.decode(engine, frames, *T.layout_of(nch), taps=True)[2]["blksw"]
     win = np.zeros(256, np.int16)
     H.pkg().load_library().ac3mi_encode_tables(None, None, None, None, win.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)))
     w512 = np.concatenate([win, win[::-1]]).astype(np.int64)
@@ -219,7 +160,7 @@ def test_pre_echo(engine):
     pcm = M.attack_pcm(F, nch, onsets, amp=20000.0, seed=91)[None]
     e = {}
     for mode in (0, 1):
-        frames = _encode(engine, pcm, nch, mode)[0]
+        frames = T.encode(engine, pcm, bsw=mode)[0]
         out, errs, _ = H.orc_decode(frames, 2, 1.0, 0.0)
         assert errs == 0
         dec = out.transpose(0, 1, 3, 2).reshape(-1, nch).astype(np.float64) * 32768.0
@@ -236,8 +177,8 @@ def test_transcode_equals_decode_then_encode(engine):
     import torch
     pkg = H.pkg()
     S, F = 3, 3
-    src = _encode(engine, _pcm("attack", S, F, 6, seed=101), 6, 1)
-    assert _gpu_decode(engine, src, 6)[2]["blksw"].sum() > 0
+    src = T.encode(engine, T.pcm("attack", S, F, 6, seed=101), bsw=1)
+    assert T.decode(engine, src, 7, 1, taps=True)[2]["blksw"].sum() > 0
     fb = src.shape[2]
     stride = (fb + 3) & ~3
     buf = np.zeros((S, F, stride), np.uint8)
@@ -269,7 +210,7 @@ def test_transcode_equals_decode_then_encode(engine):
         engine.set_encode_block_switch(0)
     assert int((status.cpu() & 0x1ff).max()) == 0
     assert torch.equal(out.cpu(), out2.cpu()) and torch.equal(last.cpu(), last2.cpu()) and torch.equal(csnr.cpu(), csnr2.cpu())
-    assert _gpu_decode(engine, out.cpu().numpy()[:, :, :enc.frame_bytes()], 6)[2]["blksw"].sum() > 0
+    assert T.decode(engine, out.cpu().numpy()[:, :, :enc.frame_bytes()], 7, 1, taps=True)[2]["blksw"].sum() > 0
 
 
 def test_setter_rejects_other_modes(engine):

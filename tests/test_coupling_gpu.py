@@ -8,80 +8,11 @@ import numpy as np
 import pytest
 
 from tests import _harness as H
+from tests import _tools as T
 from tests import block_switch_model as B
 from tests import coupling_model as C
 
 pytestmark = pytest.mark.gpu
-
-RATE = {1: 192000, 2: 192000, 5: 384000, 6: 384000}
-ACMOD = {1: 1, 2: 2, 5: 7, 6: 7}
-
-
-def _chmap(nch):
-    return H.CHMAP6 if nch == 6 else tuple(range(nch))
-
-
-def _encode(engine, pcm, nch, mode, begf=0, bsw=0, remat=0, taps=False, last=None, csnr=None, rate=None):
-    """pcm [S][F*1536][nch] s16 -> frames [S][F][fb][, taps] with coupling (mode, begf) (None: leave the context's
-    setting), block switching `bsw` and rematrixing `remat`, one call."""
-    import torch
-    pkg = H.pkg()
-    S = pcm.shape[0]
-    F = pcm.shape[1] // 1536
-    enc = pkg.EncodeDesc(48000, rate or RATE[nch], nch)
-    if last is None:
-        last = torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda")
-    if csnr is None:
-        csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-    if mode is not None:
-        engine.set_encode_coupling(mode, begf)
-    engine.set_encode_block_switch(bsw)
-    engine.set_encode_rematrix(remat)
-    try:
-        r = engine.encode_batch(enc, torch.from_numpy(np.ascontiguousarray(pcm).reshape(S, F, 1536, nch)).cuda(), _chmap(nch),
-                                last, csnr, taps=taps)
-        engine.sync()
-    finally:
-        if mode is not None:
-            engine.set_encode_coupling(0, 0)
-        engine.set_encode_block_switch(0)
-        engine.set_encode_rematrix(0)
-    fb = enc.frame_bytes()
-    if taps:
-        return r[0].cpu().numpy()[:, :, :fb], {k: v.cpu().numpy() for k, v in r[1].items()}
-    return r.cpu().numpy()[:, :, :fb]
-
-
-def _content(kind, nch, S, F, seed):
-    """[S][F*1536][nch] s16 (WAVE order)."""
-    out = []
-    n = F * 1536
-    for s in range(S):
-        rng = np.random.default_rng(seed + s)
-        p = H.gen_pcm(F, max(nch, 2), seed=seed + s, kind="music").astype(np.float64)
-        base = p[:, 0]
-        if kind == "music":                     # one source at per-channel gains + small independent components
-            gains = rng.uniform(0.4, 1.0, nch)
-            x = np.stack([gains[c] * base + 0.05 * p[:, c % p.shape[1]] * (c > 0) for c in range(nch)], -1)
-        elif kind == "identical":
-            x = np.stack([base] * nch, -1)
-        elif kind == "antiphase":              # (broadband: every coupling band carries energy that cancels in the sum)
-            w = base + rng.standard_normal(n) * 2000
-            x = np.stack([w, -w], -1)
-        elif kind == "noise":
-            x = rng.standard_normal((n, nch)) * 3000
-        elif kind == "attack":
-            t = np.arange(n)
-            bed = 3000 * np.sin(2 * np.pi * 200.0 / 48000.0 * t) + 600 * np.sin(2 * np.pi * 2500.0 / 48000.0 * t)
-            x = np.stack([bed + rng.integers(-20, 21, n) for _ in range(nch)], -1)
-            for f in range(0, F, 2):
-                o = 1536 * f + 256 * int(rng.integers(0, 6)) + int(rng.integers(0, 256))
-                m = (t >= o) & (t < o + 400)
-                x[m, 0] += 16000 * np.sin(2 * np.pi * 3000.0 / 48000.0 * (t[m] - o))
-        else:
-            raise ValueError(kind)
-        out.append(x)
-    return np.clip(np.round(np.array(out)), -32768, 32767).astype(np.int16)
 
 
 def _model(t0, nch, begf, sw=None):
@@ -98,62 +29,13 @@ def _model(t0, nch, begf, sw=None):
     return out
 
 
-class _Bits:
-    def __init__(self, frame):
-        self.b = np.unpackbits(np.asarray(frame, np.uint8))
-        self.p = 0
-
-    def get(self, n):
-        v = 0
-        for _ in range(n):
-            v = v << 1 | int(self.b[self.p])
-            self.p += 1
-        return v
-
-
-def _parse_block0(frame, nch, remat=None):
-    """cplinu, chincpl, begf, endf, [(mstrcplco, [codes])] of block 0 (this encoder's BSI: no optional fields); with
-    remat=[] a 2/0 frame's rematstr and flags are appended to it."""
-    acmod, nfbw = ACMOD[nch], 5 if nch == 6 else nch
-    r = _Bits(frame)
-    r.get(40)
-    r.get(5); r.get(3)
-    assert r.get(3) == acmod
-    if (acmod & 1) and acmod != 1:
-        r.get(2)
-    if acmod & 4:
-        r.get(2)
-    if acmod == 2:
-        r.get(2)
-    r.get(14)
-    r.get(2 * nfbw + 1)                         # blksw, dithflag, dynrnge
-    assert r.get(1) == 1                        # cplstre
-    if not r.get(1):
-        return 0, None, None, None, None
-    chincpl = r.get(nfbw)
-    if acmod == 2:
-        assert r.get(1) == 0                    # phsflginu
-    begf, endf = r.get(4), r.get(4)
-    nb = endf + 3 - begf
-    assert r.get(nb - 1) == 0                   # cplbndstrc
-    co = []
-    for _ in range(nfbw):
-        assert r.get(1) == 1                    # cplcoe
-        m = r.get(2)
-        co.append((m, [r.get(8) for _ in range(nb)]))
-    if remat is not None and acmod == 2:
-        remat.append(r.get(1))
-        remat.append(sum(r.get(1) << i for i in range(C.remat_bands(begf))))
-    return 1, chincpl, begf, endf, co
-
-
 def _check_side_info(frames, want, nch, begf):
     nfbw = 5 if nch == 6 else nch
     S, F = frames.shape[:2]
     n_on = 0
     for s in range(S):
         for f in range(F):
-            cplinu, chincpl, bf, ef, co = _parse_block0(frames[s, f], nch)
+            cplinu, chincpl, bf, ef, co = T.coupling_view(frames[s, f], nch)
             w = want[s][f]
             assert cplinu == w[0], (s, f)
             if cplinu:
@@ -163,51 +45,20 @@ def _check_side_info(frames, want, nch, begf):
     return n_on
 
 
-def _gpu_decode(engine, frames, nch, taps=False):
-    import torch
-    pkg = H.pkg()
-    S, F, fb = frames.shape
-    stride = (fb + 3) & ~3
-    buf = np.zeros((S, F, stride), np.uint8)
-    buf[:, :, :fb] = frames
-    flags = ACMOD[nch] | (16 if nch == 6 else 0)
-    dec = pkg.DecodeDesc(flags=flags, level=1.0, bias=0.0, dynrng=1, acmod=ACMOD[nch], lfeon=1 if nch == 6 else 0, frame_bytes=fb)
-    nout = nch
-    delay = torch.zeros((S, nout, 128), dtype=torch.float32, device="cuda")
-    lfsr = torch.ones((S,), dtype=torch.int16, device="cuda")
-    r = engine.decode_batch(dec, torch.from_numpy(buf).cuda(), delay, lfsr, taps=taps)
-    engine.sync()
-    if taps:
-        return r[0].cpu().numpy(), r[1].cpu().numpy(), flags, {k: v.cpu().numpy() for k, v in r[2].items()}
-    return r[0].cpu().numpy(), r[1].cpu().numpy(), flags
-
-
-def _decodes_cleanly(engine, frames, nch):
-    import bench
-    assert bench.ac3_crc_ok(frames.reshape(-1, frames.shape[2])) == 0
-    got, status, flags = _gpu_decode(engine, frames, nch)
-    assert (status & 0x1ff).max() == 0
-    for s in range(frames.shape[0]):
-        ref, errs, _ = H.orc_decode(frames[s], flags, 1.0, 0.0)
-        assert errs == 0
-        err = got[s].astype(np.float64) - ref.reshape(got[s].shape)
-        assert H.rms(err) <= 1e-6, H.rms(err)
-
-
 @pytest.mark.parametrize("nch", [1, 2, 6])
 def test_mode0_is_the_reference(engine, nch):
     pcm = np.stack([H.gen_pcm(2, nch, seed=31 + s, kind="music") for s in range(2)])
-    want = np.stack([H.orc_encode(p, nch, RATE[nch], chmap=(_chmap(nch) + (0,) * 8)[:8]) for p in pcm])
-    assert np.array_equal(_encode(engine, pcm, nch, 0, begf=5), want)
+    want = np.stack([H.orc_encode(p, nch, T.RATE[nch], chmap=(T.chmap_of(nch) + (0,) * 8)[:8]) for p in pcm])
+    assert np.array_equal(T.encode(engine, pcm, cpl=(0, 5)), want)
     if nch == 1:                                # one full-bandwidth channel: mode 1 changes nothing
-        assert np.array_equal(_encode(engine, pcm, nch, 1, begf=0), want)
+        assert np.array_equal(T.encode(engine, pcm, cpl=(1, 0)), want)
 
 
 def test_uncoupled_frames_are_mode0(engine):
-    pcm = _content("antiphase", 2, 2, 3, seed=37)
-    f0, t0 = _encode(engine, pcm, 2, 0, taps=True)
+    pcm = T.content("antiphase", 2, 2, 3, seed=37)
+    f0, t0 = T.encode(engine, pcm, cpl=(0, 0), taps=True)
     assert not any(w[0] for row in _model(t0, 2, 0) for w in row)
-    assert np.array_equal(_encode(engine, pcm, 2, 1, begf=0), f0)
+    assert np.array_equal(T.encode(engine, pcm, cpl=(1, 0)), f0)
 
 
 @pytest.mark.parametrize("nch", [2, 5, 6])
@@ -220,11 +71,11 @@ def test_side_information_matches_the_model(engine, nch, pack, F):
     try:
         n_on = 0
         for kind, begf in (("music", 0), ("identical", 3), ("noise", 7), ("music", 12)):
-            pcm = _content(kind, nch, 2, F, seed=43)
-            _, t0 = _encode(engine, pcm, nch, 0, taps=True)
-            frames = _encode(engine, pcm, nch, 1, begf=begf)
+            pcm = T.content(kind, nch, 2, F, seed=43)
+            _, t0 = T.encode(engine, pcm, cpl=(0, 0), taps=True)
+            frames = T.encode(engine, pcm, cpl=(1, begf))
             n_on += _check_side_info(frames, _model(t0, nch, begf), nch, begf)
-            _decodes_cleanly(engine, frames, nch)
+            T.decodes_cleanly(frames, *T.layout_of(nch), engine=engine)
         assert n_on > 0
     finally:
         engine.set_encode_mode(0)
@@ -236,7 +87,7 @@ def _coords(frames, nch):
     for s_ in range(frames.shape[0]):
         row = []
         for f in range(frames.shape[1]):
-            cplinu, _, _, _, co = _parse_block0(frames[s_, f], nch)
+            cplinu, _, _, _, co = T.coupling_view(frames[s_, f], nch)
             row.append((cplinu, None if not cplinu else np.array([[C.coord_value(c, m) for c in cc] for m, cc in co])))
         out.append(row)
     return out
@@ -244,21 +95,21 @@ def _coords(frames, nch):
 
 @pytest.mark.parametrize("nch", [2, 6])
 def test_decoded_coupling_structure(engine, nch):
-    """The GPU decoder (bit-identical to liba52, checked by _decodes_cleanly) on coupled streams: its coupling-channel taps
+    """The GPU decoder (bit-identical to liba52, checked by T.decodes_cleanly) on coupled streams: its coupling-channel taps
     (row 6) are present exactly in the frames the model couples; in coupled bins with bap > 0 channel ch's coefficient
     over channel 0's is the ratio of their decoded coordinates; over the frames, each coupled band's decoded energy per
     channel is within 1.5 dB of the input's (mode-0 MDCT rows c at exp_samples x: c 2^-(23 + x)), as the low band is,
     wherever mode 0's decode is (the top bands of this content sit at the dither floor in both modes)."""
     begf, F, S = 2, 4, 2
     nfbw = 5 if nch == 6 else nch
-    pcm = _content("music", nch, S, F, seed=47)
-    _, t0 = _encode(engine, pcm, nch, 0, taps=True)
+    pcm = T.content("music", nch, S, F, seed=47)
+    _, t0 = T.encode(engine, pcm, cpl=(0, 0), taps=True)
     want = _model(t0, nch, begf)
-    frames = _encode(engine, pcm, nch, 1, begf=begf)
-    _decodes_cleanly(engine, frames, nch)
-    _, status, _, tp = _gpu_decode(engine, frames, nch, taps=True)
-    f0 = _encode(engine, pcm, nch, 0)
-    coef0 = _gpu_decode(engine, f0, nch, taps=True)[3]["coef"].astype(np.float64)
+    frames = T.encode(engine, pcm, cpl=(1, begf))
+    T.decodes_cleanly(frames, *T.layout_of(nch), engine=engine)
+    _, status, tp = T.decode(engine, frames, *T.layout_of(nch), taps=True)
+    f0 = T.encode(engine, pcm, cpl=(0, 0))
+    coef0 = T.decode(engine, f0, *T.layout_of(nch), taps=True)[2]["coef"].astype(np.float64)
     # (the decoder's coefficient planes put the LFE first: coded channel ch is plane ch + 1 in 5.1)
     o = 1 if nch == 6 else 0
     coef0 = coef0[:, :, :, o:o + nfbw]
@@ -316,27 +167,27 @@ def test_quality_at_224_kbps(engine):
     166-220 -> 236-262); stereo music at 96 kb/s decodes better below cplstrtmant (28.07 -> 30.75 dB, +2.68).  The thresholds
     keep half of the offset gain and 1.5 dB of the SNR gain."""
     F = 6
-    pcm = _content("music", 6, 1, F, seed=53)
-    f0, t0 = _encode(engine, pcm, 6, 0, taps=True, rate=224000)
-    f1, t1 = _encode(engine, pcm, 6, 1, begf=0, taps=True, rate=224000)
-    on = np.array([_parse_block0(f1[0, f], 6)[0] for f in range(F)], bool)
+    pcm = T.content("music", 6, 1, F, seed=53)
+    f0, t0 = T.encode(engine, pcm, cpl=(0, 0), taps=True, rate=224000)
+    f1, t1 = T.encode(engine, pcm, cpl=(1, 0), taps=True, rate=224000)
+    on = np.array([T.coupling_view(f1[0, f], 6)[0] for f in range(F)], bool)
     o0 = 16 * t0["snroffst"][0, :, 0] + t0["snroffst"][0, :, 1]
     o1 = 16 * t1["snroffst"][0, :, 0] + t1["snroffst"][0, :, 1]
     print("5.1 224 kb/s: coupled %s, 16 csnr + fsnr %s -> %s (mean +%.1f)" % (on.tolist(), o0.tolist(), o1.tolist(), (o1 - o0)[on].mean()))
     assert on.all() and (o1 > o0).all() and (o1 - o0).mean() >= 25, (o0, o1)
-    _decodes_cleanly(engine, f1, 6)
+    T.decodes_cleanly(f1, 7, 1, engine=engine)
     # 5.1: the decoded coefficient planes below cplstrtmant against the mode-0 rows (scale fitted on the mode-0 decode)
     x = t0["mdct"][0].astype(np.float64) * np.exp2(-(23.0 + t0["exp_samples"][0]))[..., None]
     x = x[:, :, :5, :C.start_mant(0)]
-    d0 = _gpu_decode(engine, f0, 6, taps=True)[3]["coef"][0, :, :, 1:6, :C.start_mant(0)].astype(np.float64)    # (LFE plane first)
-    d1 = _gpu_decode(engine, f1, 6, taps=True)[3]["coef"][0, :, :, 1:6, :C.start_mant(0)].astype(np.float64)
+    d0 = T.decode(engine, f0, 7, 1, taps=True)[2]["coef"][0, :, :, 1:6, :C.start_mant(0)].astype(np.float64)    # (LFE plane first)
+    d1 = T.decode(engine, f1, 7, 1, taps=True)[2]["coef"][0, :, :, 1:6, :C.start_mant(0)].astype(np.float64)
     k = (d0 * x).sum() / (x * x).sum()
     snr0 = 10 * np.log10((x ** 2).sum() / ((d0 / k - x) ** 2).sum())
     snr1 = 10 * np.log10((x ** 2).sum() / ((d1 / k - x) ** 2).sum())
     print("5.1 224 kb/s: coefficient SNR below cplstrtmant %.2f -> %.2f dB (+%.2f)" % (snr0, snr1, snr1 - snr0))
     assert snr1 - snr0 >= 1.5, (snr0, snr1)
     # stereo at 96 kb/s, decoded SNR below cplstrtmant (FFT of the error, frame 0 aside)
-    pcm2 = _content("music", 2, 1, F, seed=59)
+    pcm2 = T.content("music", 2, 1, F, seed=59)
     cut = C.start_mant(0) * 24000.0 / 256
 
     def low_snr(frames):
@@ -350,8 +201,8 @@ def test_quality_at_224_kbps(engine):
         lo = k < 0.9 * cut
         return 10 * np.log10((np.abs(R[lo]) ** 2).sum() / (np.abs(E[lo]) ** 2).sum())
 
-    s0 = low_snr(_encode(engine, pcm2, 2, 0, rate=96000)[0])
-    s1 = low_snr(_encode(engine, pcm2, 2, 1, begf=0, rate=96000)[0])
+    s0 = low_snr(T.encode(engine, pcm2, cpl=(0, 0), rate=96000)[0])
+    s1 = low_snr(T.encode(engine, pcm2, cpl=(1, 0), rate=96000)[0])
     print("2/0 96 kb/s: decoded SNR below %.0f Hz %.2f -> %.2f dB (+%.2f)" % (cut, s0, s1, s1 - s0))
     assert s1 - s0 >= 1.5, (s0, s1)
 
@@ -360,26 +211,26 @@ def test_call_shapes_agree(engine):
     """Two calls of two frames, state slots, and small tiles give the bytes of one call."""
     import torch
     S, F, nch = 3, 4, 6
-    pcm = _content("music", nch, S, F, seed=61)
-    whole = _encode(engine, pcm, nch, 1, begf=1)
-    assert any(_parse_block0(whole[s, f], nch)[0] for s in range(S) for f in range(F))
+    pcm = T.content("music", nch, S, F, seed=61)
+    whole = T.encode(engine, pcm, cpl=(1, 1))
+    assert any(T.coupling_view(whole[s, f], nch)[0] for s in range(S) for f in range(F))
     last = torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda")
     csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-    a = _encode(engine, pcm[:, :2 * 1536], nch, 1, begf=1, last=last, csnr=csnr)
-    b = _encode(engine, pcm[:, 2 * 1536:], nch, 1, begf=1, last=last, csnr=csnr)
+    a = T.encode(engine, pcm[:, :2 * 1536], cpl=(1, 1), last=last, csnr=csnr)
+    b = T.encode(engine, pcm[:, 2 * 1536:], cpl=(1, 1), last=last, csnr=csnr)
     assert np.array_equal(np.concatenate([a, b], 1), whole)
     perm = torch.tensor([2, 0, 1], dtype=torch.int32, device="cuda")
     last6 = torch.zeros((S, 6, 256), dtype=torch.int16, device="cuda")
     csnr6 = torch.full((S,), 40, dtype=torch.int32, device="cuda")
     engine._check(engine.lib.ac3mi_set_state_slots(ctypes.c_void_p(engine.ctx), ctypes.c_void_p(perm.data_ptr())))
     try:
-        got = [_encode(engine, pcm[:, f * 1536:(f + 1) * 1536], nch, 1, begf=1, last=last6, csnr=csnr6) for f in range(F)]
+        got = [T.encode(engine, pcm[:, f * 1536:(f + 1) * 1536], cpl=(1, 1), last=last6, csnr=csnr6) for f in range(F)]
     finally:
         engine._check(engine.lib.ac3mi_set_state_slots(ctypes.c_void_p(engine.ctx), None))
     assert np.array_equal(np.concatenate(got, 1), whole)
     engine._check(engine.lib.ac3mi_set_tile_frames(ctypes.c_void_p(engine.ctx), ctypes.c_longlong(4)))
     try:
-        tiled = _encode(engine, pcm, nch, 1, begf=1)
+        tiled = T.encode(engine, pcm, cpl=(1, 1))
     finally:
         engine._check(engine.lib.ac3mi_set_tile_frames(ctypes.c_void_p(engine.ctx), ctypes.c_longlong(0)))
     assert np.array_equal(tiled, whole)
@@ -390,11 +241,11 @@ def test_with_block_switching(engine):
     switching on byte for byte; a later declined frame may differ from mode 0's through the SNR-offset search, which starts
     from the previous (possibly coupled) frame's offset, so only frame 0 is compared."""
     nch = 2
-    pcm = _content("attack", nch, 2, 4, seed=67)
-    f0, t0 = _encode(engine, pcm, nch, 0, bsw=1, taps=True)
+    pcm = T.content("attack", nch, 2, 4, seed=67)
+    f0, t0 = T.encode(engine, pcm, cpl=(0, 0), bsw=1, taps=True)
     sw = np.stack([B.decisions(p, (0, 1), 2) for p in pcm])
     want = _model(t0, nch, 0, sw=sw)
-    f1 = _encode(engine, pcm, nch, 1, begf=0, bsw=1)
+    f1 = T.encode(engine, pcm, cpl=(1, 0), bsw=1)
     on = _check_side_info(f1, want, nch, 0)
     off = [(s, f) for s in range(2) for f in range(4) if not want[s][f][0]]
     assert on > 0 and off
@@ -402,7 +253,7 @@ def test_with_block_switching(engine):
         assert sw[s, f].any()
         if f == 0:
             assert np.array_equal(f1[s, f], f0[s, f])
-    _decodes_cleanly(engine, f1, nch)
+    T.decodes_cleanly(f1, *T.layout_of(nch), engine=engine)
 
 
 def test_with_rematrixing(engine):
@@ -412,21 +263,21 @@ def test_with_rematrixing(engine):
     nch = 2
     both = 0
     for kind, begf in (("music", 0), ("music", 1), ("identical", 2), ("music", 5), ("noise", 4)):
-        pcm = _content(kind, nch, 2, 3, seed=71)
-        _, t0 = _encode(engine, pcm, nch, 0, taps=True)             # rows before rematrixing
+        pcm = T.content(kind, nch, 2, 3, seed=71)
+        _, t0 = T.encode(engine, pcm, cpl=(0, 0), taps=True)             # rows before rematrixing
         want = _model(t0, nch, begf)
-        frames = _encode(engine, pcm, nch, 1, begf=begf, remat=1)
+        frames = T.encode(engine, pcm, cpl=(1, begf), remat=1)
         _check_side_info(frames, want, nch, begf)
         for s_ in range(2):
             for f in range(3):
                 if not want[s_][f][0]:
                     continue
                 rm = []
-                _parse_block0(frames[s_, f], nch, remat=rm)
+                T.coupling_view(frames[s_, f], nch, remat=rm)
                 fl = C.remat_coupled(t0["mdct"][s_, f], t0["exp_samples"][s_, f], begf)
                 assert rm == [1, fl[0]], (kind, begf, s_, f, rm, fl)
                 both += fl[0] != 0
-        _decodes_cleanly(engine, frames, nch)
+        T.decodes_cleanly(frames, *T.layout_of(nch), engine=engine)
     assert both > 0
 
 
@@ -434,7 +285,7 @@ def test_transcode_equals_decode_then_encode(engine):
     import torch
     pkg = H.pkg()
     S, F, nch = 3, 3, 2
-    src = _encode(engine, _content("music", nch, S, F, seed=101), nch, 0)
+    src = T.encode(engine, T.content("music", nch, S, F, seed=101), cpl=(0, 0))
     fb = src.shape[2]
     stride = (fb + 3) & ~3
     buf = np.zeros((S, F, stride), np.uint8)
@@ -467,7 +318,7 @@ def test_transcode_equals_decode_then_encode(engine):
     assert int((status.cpu() & 0x1ff).max()) == 0
     assert torch.equal(out.cpu(), out2.cpu()) and torch.equal(last.cpu(), last2.cpu()) and torch.equal(csnr.cpu(), csnr2.cpu())
     o = out.cpu().numpy()[:, :, :fb]
-    assert any(_parse_block0(o[s, f], 2)[0] for s in range(S) for f in range(F))
+    assert any(T.coupling_view(o[s, f], 2)[0] for s in range(S) for f in range(F))
 
 
 def test_large_batch(engine):
@@ -475,16 +326,16 @@ def test_large_batch(engine):
     import bench
     S = 4096
     rng = np.random.default_rng(91)
-    pool = np.concatenate([_content(k, 6, 4, 1, seed=92) for k in ("music", "identical", "noise")])
+    pool = np.concatenate([T.content(k, 6, 4, 1, seed=92) for k in ("music", "identical", "noise")])
     pcm = np.stack([pool[rng.integers(0, len(pool))] for _ in range(S)])
     pcm = (pcm.astype(np.int32) * rng.uniform(0.3, 1.0, (S, 1, 1))).astype(np.int16)
-    frames = _encode(engine, pcm, 6, 1, begf=4)
+    frames = T.encode(engine, pcm, cpl=(1, 4))
     assert bench.ac3_crc_ok(frames.reshape(-1, frames.shape[2])) == 0
-    on = np.array([_parse_block0(frames[s, 0], 6)[0] for s in range(0, S, 64)])
+    on = np.array([T.coupling_view(frames[s, 0], 6)[0] for s in range(0, S, 64)])
     assert 0 < on.mean()
-    got, status, flags = _gpu_decode(engine, frames, 6)
+    got, status, _ = T.decode(engine, frames, 7, 1)
     assert (status & 0x1ff).max() == 0
-    ref, errs, _ = H.orc_decode(frames[:64, 0], flags, 1.0, 0.0)     # (64 frames as one stream: each frame stands alone)
+    ref, errs, _ = H.orc_decode(frames[:64, 0], 7 | 16, 1.0, 0.0)     # (64 frames as one stream: each frame stands alone)
     assert errs == 0
 
 

@@ -8,129 +8,17 @@ import numpy as np
 import pytest
 
 from tests import _harness as H
+from tests import _tools as T
 from tests import drc_model as D
-from tests.test_coupling_gpu import _content, _decodes_cleanly
 
 pytestmark = pytest.mark.gpu
 
-RATE = {1: 192000, 2: 192000, 6: 384000}
-ACMOD = {1: 1, 2: 2, 6: 7}
+TOOLS_ON = dict(bsw=1, remat=1, cpl=(1, 3), bw=(1, 40))
 META = dict(dialnorm=17, bsmod=3, cmixlev=2, surmixlev=0, dsurmod=2, copyrightb=1, origbs=0)
 
 
-def _chmap(nch):
-    return H.CHMAP6 if nch == 6 else tuple(range(nch))
-
-
-def _encode(engine, pcm, nch, drc=0, state=None, md=None, tools=False, last=None, csnr=None, rate=None):
-    """pcm [S][F*1536][nch] s16 -> frames [S][F][fb]: DRC profile `drc` with `state` (int32 [S] on the device; zeros when
-    None), metadata `md` (a dict of fields, None = the defaults), `tools` = block switching, rematrixing, coupling and
-    bandwidth on; every setting back to its default afterwards."""
-    import torch
-    pkg = H.pkg()
-    S, F = pcm.shape[0], pcm.shape[1] // 1536
-    enc = pkg.EncodeDesc(48000, rate or RATE[nch], nch)
-    if last is None:
-        last = torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda")
-    if csnr is None:
-        csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-    if drc and state is None:
-        state = torch.zeros((S,), dtype=torch.int32, device="cuda")
-    if md is not None:
-        engine.set_encode_metadata(**md)
-    engine.set_encode_drc(drc, state if drc else None)
-    if tools:
-        engine.set_encode_block_switch(1)
-        engine.set_encode_rematrix(1)
-        engine.set_encode_coupling(1, 3)
-        engine.set_encode_bandwidth(1, 40)
-    try:
-        r = engine.encode_batch(enc, torch.from_numpy(np.ascontiguousarray(pcm).reshape(S, F, 1536, nch)).cuda(), _chmap(nch),
-                                last, csnr)
-        engine.sync()
-    finally:
-        engine.set_encode_metadata()
-        engine.set_encode_drc(0)
-        engine.set_encode_block_switch(0)
-        engine.set_encode_rematrix(0)
-        engine.set_encode_coupling(0, 0)
-        engine.set_encode_bandwidth(0)
-    return r.cpu().numpy()[:, :, :enc.frame_bytes()]
-
-
-def _bsi(frame):
-    """A frame's BSI -> (fields, the bit positions of the fields ac3mi_set_encode_metadata writes)."""
-    bits = np.unpackbits(np.asarray(frame, np.uint8))
-    pos = [40]
-    out, where = {}, []
-
-    def get(name, n, meta=False):
-        v = 0
-        for i in range(n):
-            v = v << 1 | int(bits[pos[0] + i])
-        if meta:
-            where.extend(range(pos[0], pos[0] + n))
-        pos[0] += n
-        out[name] = v
-
-    get("bsid", 5)
-    get("bsmod", 3, True)
-    get("acmod", 3)
-    a = out["acmod"]
-    if (a & 1) and a != 1:
-        get("cmixlev", 2, True)
-    if a & 4:
-        get("surmixlev", 2, True)
-    if a == 2:
-        get("dsurmod", 2, True)
-    get("lfeon", 1)
-    get("dialnorm", 5, True)
-    get("compre", 1)
-    get("langcode", 1)
-    get("audprodie", 1)
-    get("copyrightb", 1, True)
-    get("origbs", 1, True)
-    get("timecod1e", 1)
-    get("timecod2e", 1)
-    get("addbsie", 1)
-    return out, where
-
-
-def _gpu_decode(engine, frames, acmod, lfeon, flags, taps=False):
-    import torch
-    pkg = H.pkg()
-    S, F, fb = frames.shape
-    buf = np.zeros((S, F, (fb + 3) & ~3), np.uint8)
-    buf[:, :, :fb] = frames
-    dec = pkg.DecodeDesc(flags=flags, level=1.0, bias=0.0, dynrng=1, acmod=acmod, lfeon=lfeon, frame_bytes=fb)
-    nout, _ = engine.decode_planes(dec)
-    delay = torch.zeros((S, nout, 128), dtype=torch.float32, device="cuda")
-    lfsr = torch.ones((S,), dtype=torch.int16, device="cuda")
-    r = engine.decode_batch(dec, torch.from_numpy(buf).cuda(), delay, lfsr, taps=taps)
-    engine.sync()
-    if taps:
-        return r[0].cpu().numpy(), r[1].cpu().numpy(), {k: v.cpu().numpy() for k, v in r[2].items()}
-    return r[0].cpu().numpy(), r[1].cpu().numpy()
-
-
-def _programme(nch, seed):
-    """Tone and noise segments at -60, -40, -31, -20 and -5 dBFS, two frames each, then silence: [1][12*1536][nch]."""
-    rng = np.random.default_rng(seed)
-    t = np.arange(1536 * 2)
-    segs = []
-    for i, db in enumerate((-60, -40, -31, -20, -5)):
-        a = 32767 * 10 ** (db / 20)
-        if i % 2 == 0:
-            x = a * np.sin(2 * np.pi * (400 + 300 * i) / 48000 * t)[:, None] * np.ones(nch)
-        else:
-            x = a / 3 * rng.standard_normal((t.size, nch))
-        segs.append(x)
-    segs.append(np.zeros((1536 * 2, nch)))
-    return np.clip(np.round(np.concatenate(segs)), -32768, 32767).astype(np.int16)[None]
-
-
 def _model(pcm, nch, profile, dialnorm=31, state=0):
-    return D.encode(pcm, _chmap(nch), min(nch, 5), profile, dialnorm, state)
+    return D.encode(pcm, T.chmap_of(nch), min(nch, 5), profile, dialnorm, state)
 
 
 @pytest.mark.parametrize("nch", [1, 2, 6])
@@ -142,23 +30,23 @@ def test_off_means_unchanged(engine, nch, tools):
     pcm = np.stack([H.gen_pcm(2, nch, seed=71 + s, kind="music") for s in range(2)])
     fresh = pkg.Engine(0)
     try:
-        want = _encode(fresh, pcm, nch, tools=tools)
+        want = T.encode(fresh, pcm, **(TOOLS_ON if tools else {}))
     finally:
         fresh.close()
     if not tools:
-        ref = np.stack([H.orc_encode(p, nch, RATE[nch], chmap=(_chmap(nch) + (0,) * 8)[:8]) for p in pcm])
+        ref = np.stack([H.orc_encode(p, nch, T.RATE[nch], chmap=(T.chmap_of(nch) + (0,) * 8)[:8]) for p in pcm])
         assert np.array_equal(want, ref)
     state = torch.zeros((2,), dtype=torch.int32, device="cuda")
-    assert not np.array_equal(_encode(engine, pcm, nch, drc=2, state=state, md=META, tools=tools), want)
-    assert np.array_equal(_encode(engine, pcm, nch, tools=tools), want)
+    assert not np.array_equal(T.encode(engine, pcm, drc=2, state=state, md=META, **(TOOLS_ON if tools else {})), want)
+    assert np.array_equal(T.encode(engine, pcm, **(TOOLS_ON if tools else {})), want)
     engine.set_encode_metadata(**META)
     engine.set_encode_drc(4, state)
     engine.set_encode_drc(0, state)                 # profile 0 with a state: accepted, sends nothing
     engine.set_encode_metadata()
     try:
-        assert np.array_equal(_encode(engine, pcm, nch, drc=0, md=None, tools=tools), want)
+        assert np.array_equal(T.encode(engine, pcm, drc=0, md=None, **(TOOLS_ON if tools else {})), want)
         engine.set_encode_metadata(dialnorm=31, bsmod=0, cmixlev=1, surmixlev=1, dsurmod=0, copyrightb=0, origbs=1)
-        assert np.array_equal(_encode(engine, pcm, nch, md=dict(dialnorm=31), tools=tools), want)
+        assert np.array_equal(T.encode(engine, pcm, md=dict(dialnorm=31), **(TOOLS_ON if tools else {})), want)
     finally:
         engine.set_encode_metadata()
         engine.set_encode_drc(0)
@@ -170,16 +58,16 @@ def test_metadata_reaches_the_bsi_only(engine, nch, pack):
     pcm = np.stack([H.gen_pcm(3, nch, seed=81 + s, kind="music") for s in range(2)])
     engine.set_encode_mode(pack)
     try:
-        want = _encode(engine, pcm, nch)
-        got = _encode(engine, pcm, nch, md=META)
+        want = T.encode(engine, pcm)
+        got = T.encode(engine, pcm, md=META)
     finally:
         engine.set_encode_mode(0)
-    _decodes_cleanly(engine, got, nch)
-    acmod = ACMOD[nch]
+    T.decodes_cleanly(got, *T.layout_of(nch), engine=engine)
+    acmod = T.ACMOD[nch]
     for s in range(got.shape[0]):
         for f in range(got.shape[1]):
-            fields, where = _bsi(got[s, f])
-            dflt, where0 = _bsi(want[s, f])
+            fields, where = T.bsi_view(got[s, f])
+            dflt, where0 = T.bsi_view(want[s, f])
             assert where == where0
             assert fields["dialnorm"] == 17 and fields["bsmod"] == 3 and fields["copyrightb"] == 1 and fields["origbs"] == 0
             assert dflt["dialnorm"] == 31 and dflt["bsmod"] == 0 and dflt["copyrightb"] == 0 and dflt["origbs"] == 1
@@ -202,8 +90,8 @@ def test_downmix_levels(engine):
     pcm = np.stack([H.gen_pcm(2, nch, seed=91, kind="music")])
     outs = []
     for c in (0, 2):
-        frames = _encode(engine, pcm, nch, md=dict(cmixlev=c, surmixlev=c))
-        got, status = _gpu_decode(engine, frames, 7, 1, 2)
+        frames = T.encode(engine, pcm, md=dict(cmixlev=c, surmixlev=c))
+        got, status, _ = T.decode(engine, frames, 7, 1, 2)
         assert (status & 0x1ff).max() == 0
         ref, errs, _ = H.orc_decode(frames[0], 2, 1.0, 0.0)
         assert errs == 0
@@ -216,20 +104,20 @@ def test_downmix_levels(engine):
 def test_codes_match_the_model(engine, profile):
     import torch
     nch = 2
-    pcm = _programme(nch, seed=profile)
+    pcm = T.programme(nch, seed=profile)
     seen = []
     for dialnorm in (31, 24, 1):
         state = torch.zeros((1,), dtype=torch.int32, device="cuda")
-        frames = _encode(engine, pcm, nch, drc=profile, state=state, md=dict(dialnorm=dialnorm))
+        frames = T.encode(engine, pcm, drc=profile, state=state, md=dict(dialnorm=dialnorm))
         codes, snt, s_end, _ = _model(pcm[0], nch, profile, dialnorm)
         assert int(state.cpu()[0]) == s_end
-        _, status, taps = _gpu_decode(engine, frames, 2, 0, 2, taps=True)
+        _, status, taps = T.decode(engine, frames, 2, 0, 2, taps=True)
         assert (status & 0x1ff).max() == 0
         w = taps["dynrng"][0, :, :, 0]
         assert np.array_equal(~np.isnan(w), snt), (dialnorm, snt, w)
         want = np.array([[D.decoded_gain(v) for v in row] for row in codes], np.float32)
         assert np.array_equal(w[snt], want[snt]), dialnorm
-        assert all(_bsi(fr)[0]["dialnorm"] == dialnorm for fr in frames[0])
+        assert all(T.bsi_view(fr)[0]["dialnorm"] == dialnorm for fr in frames[0])
         seen.append(codes)
     # the programme exercises boost and cut (at dialnorm 31, the loud segments sit far above the dialogue level)
     assert seen[0].max() > 0 and seen[0].min() < 0
@@ -240,7 +128,7 @@ def test_call_shapes_agree(engine):
     and both packers: the same bytes and final state."""
     import torch
     S, F, nch, prof = 3, 12, 6, 1
-    pcm = np.concatenate([_programme(nch, seed=7 + s) for s in range(S)])
+    pcm = np.concatenate([T.programme(nch, seed=7 + s) for s in range(S)])
     md = dict(dialnorm=24)
 
     def fresh():
@@ -248,7 +136,7 @@ def test_call_shapes_agree(engine):
                 torch.full((S,), 40, dtype=torch.int32, device="cuda"))
 
     st, last, csnr = fresh()
-    whole = _encode(engine, pcm, nch, drc=prof, state=st, md=md, last=last, csnr=csnr)
+    whole = T.encode(engine, pcm, drc=prof, state=st, md=md, last=last, csnr=csnr)
     st_whole = st.cpu().numpy().copy()
     for s in range(S):
         codes, snt, s_end, _ = _model(pcm[s], nch, prof, 24)
@@ -257,19 +145,19 @@ def test_call_shapes_agree(engine):
         engine.set_encode_mode(pack)
         try:
             st, last, csnr = fresh()
-            assert np.array_equal(_encode(engine, pcm, nch, drc=prof, state=st, md=md, last=last, csnr=csnr), whole), pack
+            assert np.array_equal(T.encode(engine, pcm, drc=prof, state=st, md=md, last=last, csnr=csnr), whole), pack
             assert np.array_equal(st.cpu().numpy(), st_whole)
         finally:
             engine.set_encode_mode(0)
     st, last, csnr = fresh()
-    got = [_encode(engine, pcm[:, f * 1536:(f + 1) * 1536], nch, drc=prof, state=st, md=md, last=last, csnr=csnr) for f in range(F)]
+    got = [T.encode(engine, pcm[:, f * 1536:(f + 1) * 1536], drc=prof, state=st, md=md, last=last, csnr=csnr) for f in range(F)]
     assert np.array_equal(np.concatenate(got, 1), whole)
     assert np.array_equal(st.cpu().numpy(), st_whole)
     perm = torch.tensor([2, 0, 1], dtype=torch.int32, device="cuda")
     st, last, csnr = fresh()
     engine._check(engine.lib.ac3mi_set_state_slots(ctypes.c_void_p(engine.ctx), ctypes.c_void_p(perm.data_ptr())))
     try:
-        got = [_encode(engine, pcm[:, f * 1536:(f + 1) * 1536], nch, drc=prof, state=st, md=md, last=last, csnr=csnr)
+        got = [T.encode(engine, pcm[:, f * 1536:(f + 1) * 1536], drc=prof, state=st, md=md, last=last, csnr=csnr)
                for f in range(F)]
     finally:
         engine._check(engine.lib.ac3mi_set_state_slots(ctypes.c_void_p(engine.ctx), None))
@@ -278,24 +166,24 @@ def test_call_shapes_agree(engine):
     engine._check(engine.lib.ac3mi_set_tile_frames(ctypes.c_void_p(engine.ctx), ctypes.c_longlong(3)))
     try:
         st, last, csnr = fresh()
-        tiled = _encode(engine, pcm, nch, drc=prof, state=st, md=md, last=last, csnr=csnr)
+        tiled = T.encode(engine, pcm, drc=prof, state=st, md=md, last=last, csnr=csnr)
     finally:
         engine._check(engine.lib.ac3mi_set_tile_frames(ctypes.c_void_p(engine.ctx), ctypes.c_longlong(0)))
     assert np.array_equal(tiled, whole)
     assert np.array_equal(st.cpu().numpy(), st_whole)
-    _decodes_cleanly(engine, whole, nch)
+    T.decodes_cleanly(whole, *T.layout_of(nch), engine=engine)
 
 
 def test_drc_with_every_tool(engine):
     """Block switching, rematrixing, coupling and bandwidth on: clean decodes, the model's words (2/0 and 5.1)."""
     import torch
     for nch in (2, 6):
-        pcm = _programme(nch, seed=11)
+        pcm = T.programme(nch, seed=11)
         st = torch.zeros((1,), dtype=torch.int32, device="cuda")
-        frames = _encode(engine, pcm, nch, drc=3, state=st, md=dict(dialnorm=20), tools=True)
-        _decodes_cleanly(engine, frames, nch)
+        frames = T.encode(engine, pcm, drc=3, state=st, md=dict(dialnorm=20), **TOOLS_ON)
+        T.decodes_cleanly(frames, *T.layout_of(nch), engine=engine)
         codes, snt, s_end, _ = _model(pcm[0], nch, 3, 20)
-        _, status, taps = _gpu_decode(engine, frames, ACMOD[nch], 1 if nch == 6 else 0, ACMOD[nch] | (16 if nch == 6 else 0), taps=True)
+        _, status, taps = T.decode(engine, frames, *T.layout_of(nch), taps=True)
         w = taps["dynrng"][0, :, :, 0]
         assert np.array_equal(~np.isnan(w), snt)
         assert int(st.cpu()[0]) == s_end
@@ -312,7 +200,7 @@ def _transcode_equals_decode_then_encode(engine, tile):
     import torch
     pkg = H.pkg()
     S, F, nch = 2, 4, 2
-    src = _encode(engine, _content("music", nch, S, F, seed=121), nch)
+    src = T.encode(engine, T.content("music", nch, S, F, seed=121))
     fb = src.shape[2]
     buf = np.zeros((S, F, (fb + 3) & ~3), np.uint8)
     buf[:, :, :fb] = src
@@ -354,7 +242,7 @@ def _transcode_equals_decode_then_encode(engine, tile):
     assert int((status.cpu() & 0x1ff).max()) == 0
     assert torch.equal(out.cpu(), out2.cpu()) and torch.equal(st.cpu(), st2.cpu()) and torch.equal(csnr.cpu(), csnr2.cpu())
     o = out.cpu().numpy()[:, :, :fb]
-    _decodes_cleanly(engine, o, 2)
+    T.decodes_cleanly(o, 2, 0, engine=engine)
     x = s16.cpu().numpy().reshape(S, F * 1536, 2)
     for s in range(S):
         codes, snt, s_end, _ = _model(x[s], 2, 5, 27, state=100)
@@ -367,13 +255,13 @@ def test_workspace_bytes_counts_the_drc_workspace():
     import torch
     pkg = H.pkg()
     S, F, nch = 3, 4, 2
-    pcm = _content("music", nch, S, F, seed=5)
+    pcm = T.content("music", nch, S, F, seed=5)
     held = []
     for drc in (0, 1):
         eng = pkg.Engine(0)
         try:
             state = torch.zeros((S,), dtype=torch.int32, device="cuda")
-            _encode(eng, pcm, nch, drc=drc, state=state)
+            T.encode(eng, pcm, drc=drc, state=state)
             held.append(eng.workspace_bytes())
         finally:
             eng.close()
@@ -385,13 +273,13 @@ def test_decoded_gain_follows_the_model(engine):
     block and the one before (the overlap-add mixes two blocks' gains)."""
     import torch
     nch = 2
-    pcm = _programme(nch, seed=3)
-    off = _encode(engine, pcm, nch)
+    pcm = T.programme(nch, seed=3)
+    off = T.encode(engine, pcm)
     st = torch.zeros((1,), dtype=torch.int32, device="cuda")
-    on = _encode(engine, pcm, nch, drc=1, state=st)
+    on = T.encode(engine, pcm, drc=1, state=st)
     codes, _, _, _ = _model(pcm[0], nch, 1)
-    a, sa = _gpu_decode(engine, off, 2, 0, 2)
-    b, sb = _gpu_decode(engine, on, 2, 0, 2)
+    a, sa, _ = T.decode(engine, off, 2, 0, 2)
+    b, sb, _ = T.decode(engine, on, 2, 0, 2)
     assert (sa & 0x1ff).max() == 0 and (sb & 0x1ff).max() == 0
     a = a[0].reshape(-1, 2, 256).astype(np.float64)             # [F * 6][n_out][256]
     b = b[0].reshape(-1, 2, 256).astype(np.float64)
@@ -438,7 +326,7 @@ def test_large_batch(engine):
     del delay
     sample = np.random.default_rng(1).choice(N, 24, replace=False)
     fr = frames.cpu().numpy()[sample, :, :fb]
-    _, status, taps = _gpu_decode(engine, fr, 7, 1, 7 | 16, taps=True)
+    _, status, taps = T.decode(engine, fr, 7, 1, 7 | 16, taps=True)
     assert (status & 0x1ff).max() == 0
     x = pcm.cpu().numpy()[sample]
     stc = st.cpu().numpy()

@@ -9,58 +9,16 @@ import numpy as np
 import pytest
 
 from tests import _harness as H
+from tests import _tools as T
 from tests import bandwidth_model as W
 from tests import coupling_model as C
 from tests import exp_strategy_model as X
-from tests.test_coupling_gpu import _content, _decodes_cleanly, _gpu_decode, _parse_block0
 
 pytestmark = pytest.mark.gpu
 
-RATE = {1: 192000, 2: 192000, 6: 384000}
-
-
-def _chmap(nch):
-    return H.CHMAP6 if nch == 6 else tuple(range(nch))
-
-
-def _encode(engine, pcm, nch, xs=0, bw=(0, 50), cpl=(0, 0), bsw=0, remat=0, taps=False, rate=None, sample_rate=48000,
-            last=None, csnr=None):
-    """pcm [S][F*1536][nch] s16 -> frames [S][F][fb][, taps] with exponent-strategy mode `xs` (None: leave the context's
-    setting) and the other tools as given, one call."""
-    import torch
-    pkg = H.pkg()
-    S = pcm.shape[0]
-    F = pcm.shape[1] // 1536
-    enc = pkg.EncodeDesc(sample_rate, rate or RATE[nch], nch)
-    if last is None:
-        last = torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda")
-    if csnr is None:
-        csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-    if xs is not None:
-        engine.set_encode_exp_strategy(xs)
-    engine.set_encode_bandwidth(*bw)
-    engine.set_encode_coupling(*cpl)
-    engine.set_encode_block_switch(bsw)
-    engine.set_encode_rematrix(remat)
-    try:
-        r = engine.encode_batch(enc, torch.from_numpy(np.ascontiguousarray(pcm).reshape(S, F, 1536, nch)).cuda(), _chmap(nch),
-                                last, csnr, taps=taps)
-        engine.sync()
-    finally:
-        if xs is not None:
-            engine.set_encode_exp_strategy(0)
-        engine.set_encode_bandwidth(0)
-        engine.set_encode_coupling(0, 0)
-        engine.set_encode_block_switch(0)
-        engine.set_encode_rematrix(0)
-    fb = enc.frame_bytes()
-    if taps:
-        return r[0].cpu().numpy()[:, :, :fb], {k: v.cpu().numpy() for k, v in r[1].items()}
-    return r.cpu().numpy()[:, :, :fb]
-
 
 def _pcm(nch, S, F, seed, kinds=("music", "attack", "noise", "identical")):
-    return np.concatenate([_content(k, nch, 1, F, seed=seed + i) for i, k in enumerate(kinds)])[:S]
+    return np.concatenate([T.content(k, nch, 1, F, seed=seed + i) for i, k in enumerate(kinds)])[:S]
 
 
 def _check_rows(t1, nch, n, rows=None):
@@ -87,15 +45,15 @@ def test_setter_validates_and_keeps_the_setting(engine):
         with pytest.raises(Exception):
             engine.set_encode_exp_strategy(m)
     pcm = _pcm(2, 2, 2, seed=5)
-    on = _encode(engine, pcm, 2, xs=1)
+    on = T.encode(engine, pcm, xs=1)
     engine.set_encode_exp_strategy(1)
     try:
         with pytest.raises(Exception):
             engine.set_encode_exp_strategy(2)
-        assert np.array_equal(_encode(engine, pcm, 2, xs=None), on)        # the bad call left mode 1
+        assert np.array_equal(T.encode(engine, pcm, xs=T.KEEP), on)        # the bad call left mode 1
     finally:
         engine.set_encode_exp_strategy(0)
-    assert np.array_equal(_encode(engine, pcm, 2, xs=None), _encode(engine, pcm, 2))
+    assert np.array_equal(T.encode(engine, pcm, xs=T.KEEP), T.encode(engine, pcm))
 
 
 @pytest.mark.parametrize("nch", [1, 2, 6])
@@ -108,9 +66,9 @@ def test_off_means_unchanged(engine, nch):
     if nch == 2:
         combos.append(dict(remat=1, cpl=(1, 3), bw=(1, 30)))
     for kw in combos:
-        want = _encode(engine, pcm, nch, xs=None, **kw)
-        assert np.array_equal(_encode(engine, pcm, nch, xs=0, **kw), want), kw
-        assert not np.array_equal(_encode(engine, pcm, nch, xs=1, **kw), want), kw
+        want = T.encode(engine, pcm, xs=T.KEEP, **kw)
+        assert np.array_equal(T.encode(engine, pcm, xs=0, **kw), want), kw
+        assert not np.array_equal(T.encode(engine, pcm, xs=1, **kw), want), kw
 
 
 @pytest.mark.parametrize("nch", [1, 2, 6])
@@ -123,10 +81,10 @@ def test_matches_the_model(engine, nch, sr):
     if nch == 2:
         combos += [(dict(remat=1), 223), (dict(remat=1, bsw=1, bw=(1, 25)), W.nbc(25))]
     for kw, n in combos:
-        frames, t1 = _encode(engine, pcm, nch, xs=1, taps=True, sample_rate=sr, **kw)
+        frames, t1 = T.encode(engine, pcm, xs=1, taps=True, sr=sr, **kw)
         _check_rows(t1, nch, n)
         if sr == 48000:
-            _decodes_cleanly(engine, frames, nch)
+            T.decodes_cleanly(frames, *T.layout_of(nch), engine=engine)
 
 
 def _cpl_raw(t, s, f, nfbw, begf):
@@ -143,18 +101,18 @@ def test_coupled_frames_follow_the_model(engine, nch, begf):
     channel over [cplstrtmant, 217); its exponents are read back from the GPU decoder's coupling plane."""
     nfbw = min(nch, 5)
     cs = 37 + 12 * begf
-    pcm = np.concatenate([_content("music", nch, 3, 2, seed=41), _content("identical", nch, 1, 2, seed=45)])
-    frames, t1 = _encode(engine, pcm, nch, xs=1, cpl=(1, begf), taps=True)
-    frames0, t0 = _encode(engine, pcm, nch, xs=0, cpl=(1, begf), taps=True)
-    _decodes_cleanly(engine, frames, nch)
-    _, status, _, tp = _gpu_decode(engine, frames, nch, taps=True)
+    pcm = np.concatenate([T.content("music", nch, 3, 2, seed=41), T.content("identical", nch, 1, 2, seed=45)])
+    frames, t1 = T.encode(engine, pcm, xs=1, cpl=(1, begf), taps=True)
+    frames0, t0 = T.encode(engine, pcm, xs=0, cpl=(1, begf), taps=True)
+    T.decodes_cleanly(frames, *T.layout_of(nch), engine=engine)
+    _, status, tp = T.decode(engine, frames, *T.layout_of(nch), taps=True)
     assert (status & 0x1ff).max() == 0
     S, F = frames.shape[:2]
     n_cpl = 0
     for s in range(S):
         for f in range(F):
-            cplinu = _parse_block0(frames[s, f], nch)[0]
-            assert cplinu == _parse_block0(frames0[s, f], nch)[0]            # (the coupling decision does not change)
+            cplinu = T.coupling_view(frames[s, f], nch)[0]
+            assert cplinu == T.coupling_view(frames0[s, f], nch)[0]            # (the coupling decision does not change)
             for ch in range(nch):
                 lfe = nch == 6 and ch == 5
                 k, hi = ("lfe", 7) if lfe else (("cplch", cs) if cplinu else ("fbw", 223))
@@ -180,8 +138,8 @@ def test_only_the_choice_changes(engine):
         np.sin(2 * np.pi * 1000.0 / 48000.0 * np.arange(n))[:, None] * np.full(6, 40.0))]).astype(np.int16)
     pcm = np.concatenate([_pcm(6, 4, 3, seed=61), quiet])
     for kw in (dict(), dict(bsw=1)):
-        _, t0 = _encode(engine, pcm, 6, xs=0, taps=True, **kw)
-        _, t1 = _encode(engine, pcm, 6, xs=1, taps=True, **kw)
+        _, t0 = T.encode(engine, pcm, xs=0, taps=True, **kw)
+        _, t1 = T.encode(engine, pcm, xs=1, taps=True, **kw)
         for k in ("mdct", "exponent", "exp_samples"):
             assert np.array_equal(t0[k], t1[k]), k
         seqs = _check_rows(t1, 6, 223)
@@ -215,9 +173,10 @@ def test_decodes_cleanly_and_exponents_round_trip(engine):
     GPU decoder; the decoded exponents are d_encoded_exp."""
     for nch in (2, 6):
         pcm = _pcm(nch, 4, 2, seed=71)
-        frames, t1 = _encode(engine, pcm, nch, xs=1, bsw=1, taps=True)
-        _decodes_cleanly(engine, frames, nch)
-        _, status, flags, tp = _gpu_decode(engine, frames, nch, taps=True)
+        frames, t1 = T.encode(engine, pcm, xs=1, bsw=1, taps=True)
+        T.decodes_cleanly(frames, *T.layout_of(nch), engine=engine)
+        _, status, tp = T.decode(engine, frames, *T.layout_of(nch), taps=True)
+        flags = T.ACMOD[nch] | (16 if nch == 6 else 0)
         for ch in range(nch):
             k = 7 if nch == 6 and ch == 5 else 223
             assert np.array_equal(t1["encoded_exp"][:, :, :, ch, :k], tp["exp"][:, :, :, ch, :k]), ch
@@ -235,20 +194,20 @@ def test_call_shapes_and_packers_agree(engine):
     S, F, nch = 3, 3, 6
     pcm = _pcm(nch, S, F, seed=81)
     for kw in (dict(), dict(cpl=(1, 1), bsw=1, bw=(1, 40))):
-        want = _encode(engine, pcm, nch, xs=1, **kw)
+        want = T.encode(engine, pcm, xs=1, **kw)
         last = torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda")
         csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-        per = [_encode(engine, pcm[:, 1536 * f:1536 * (f + 1)], nch, xs=1, last=last, csnr=csnr, **kw) for f in range(F)]
+        per = [T.encode(engine, pcm[:, 1536 * f:1536 * (f + 1)], xs=1, last=last, csnr=csnr, **kw) for f in range(F)]
         assert np.array_equal(np.concatenate(per, 1), want), kw
         engine.set_tile_frames(2)
         try:
-            assert np.array_equal(_encode(engine, pcm, nch, xs=1, **kw), want), kw
+            assert np.array_equal(T.encode(engine, pcm, xs=1, **kw), want), kw
         finally:
             engine.set_tile_frames(0)
         for mode in (1, 2):
             engine.set_encode_mode(mode)
             try:
-                assert np.array_equal(_encode(engine, pcm, nch, xs=1, **kw), want), (kw, mode)
+                assert np.array_equal(T.encode(engine, pcm, xs=1, **kw), want), (kw, mode)
             finally:
                 engine.set_encode_mode(0)
     # transcode
@@ -284,7 +243,7 @@ def test_call_shapes_and_packers_agree(engine):
         engine.set_encode_exp_strategy(0)
     assert int((status.cpu() & 0x1ff).max()) == 0
     assert torch.equal(out.cpu(), out2.cpu()) and torch.equal(last.cpu(), last2.cpu()) and torch.equal(csnr.cpu(), csnr2.cpu())
-    _decodes_cleanly(engine, out.cpu().numpy()[:, :, :fb], 2)
+    T.decodes_cleanly(out.cpu().numpy()[:, :, :fb], 2, 0, engine=engine)
 
 
 def test_large_batch(engine):
@@ -296,13 +255,13 @@ def test_large_batch(engine):
     idx = rng.integers(0, len(pool), S)
     gain = rng.uniform(0.3, 1.0, (S, 1, 1))
     pcm = (pool[idx].astype(np.float64) * gain).astype(np.int16)
-    frames = _encode(engine, pcm, 6, xs=1)
+    frames = T.encode(engine, pcm, xs=1)
     assert bench.ac3_crc_ok(frames.reshape(-1, frames.shape[2])) == 0
-    got, status, flags = _gpu_decode(engine, frames, 6)
+    got, status, _ = T.decode(engine, frames, 7, 1)
     assert (status & 0x1ff).max() == 0
     pick = rng.integers(0, S, 16)
-    _, t = _encode(engine, pcm[pick], 6, xs=1, taps=True)
-    assert np.array_equal(_encode(engine, pcm[pick], 6, xs=1), frames[pick])
+    _, t = T.encode(engine, pcm[pick], xs=1, taps=True)
+    assert np.array_equal(T.encode(engine, pcm[pick], xs=1), frames[pick])
     _check_rows(t, 6, 223)
 
 
@@ -323,7 +282,7 @@ def test_stream_layer_never_uses_it(engine):
         st.close()
         assert bytes(dst[:h.dst_used]) == want[:h.dst_used] and h.dst_used > 0
         # the setting is still there for the batch calls
-        assert not np.array_equal(_encode(engine, np.asarray(pcm)[None], 6, xs=None), _encode(engine, np.asarray(pcm)[None], 6))
+        assert not np.array_equal(T.encode(engine, np.asarray(pcm)[None], xs=T.KEEP), T.encode(engine, np.asarray(pcm)[None]))
     finally:
         pool.close()
         engine.set_encode_exp_strategy(0)
@@ -334,12 +293,12 @@ def _quality(engine, pcm, nch, rate, **kw):
     o = 1 if nch == 6 else 0
     res = []
     for xs in (0, 1):
-        fr, t = _encode(engine, pcm, nch, xs=xs, taps=True, rate=rate, **kw)
-        _decodes_cleanly(engine, fr, nch)
+        fr, t = T.encode(engine, pcm, xs=xs, taps=True, rate=rate, **kw)
+        T.decodes_cleanly(fr, *T.layout_of(nch), engine=engine)
         off = (16 * t["snroffst"][..., 0] + t["snroffst"][..., 1]).astype(np.float64).mean()
         x = t["mdct"].astype(np.float64) * np.exp2(-(23.0 + t["exp_samples"]))[..., None]
         x = x[:, :, :, :nfbw, :223]
-        coef = _gpu_decode(engine, fr, nch, taps=True)[3]["coef"].astype(np.float64)[:, :, :, o:o + nfbw, :223]
+        coef = T.decode(engine, fr, *T.layout_of(nch), taps=True)[2]["coef"].astype(np.float64)[:, :, :, o:o + nfbw, :223]
         res.append((off, 10 * np.log10((x ** 2).sum() / ((coef - x) ** 2).sum())))
     return res
 
@@ -359,7 +318,7 @@ def test_quality_on_music(engine, nch, rate):
     """Mean 16 csnroffst + fsnroffst and the decoded coefficients' SNR against d_mdct, mode 0 against mode 1, on the
     harness's music (figures above).  Mode 1 raises the mean SNR offset (asserted: half of the smallest measured gain,
     +1.25) and loses 0.2 - 1.2 dB of coefficient SNR (printed, not asserted)."""
-    pcm = _content("music", nch, 2, 4, seed=53)
+    pcm = T.content("music", nch, 2, 4, seed=53)
     (o0, s0), (o1, s1) = _quality(engine, pcm, nch, rate)
     print("%d ch %d kb/s: 16 csnr + fsnr %.2f -> %.2f (%+.2f); coefficient SNR %.2f -> %.2f dB (%+.2f)"
           % (nch, rate // 1000, o0, o1, o1 - o0, s0, s1, s1 - s0))
@@ -370,7 +329,7 @@ def test_quality_on_reencoded_audio(engine):
     """The transcode's input: decoded AC-3 re-encoded (2/0, 192 kb/s).  Measured +2.88 in the mean SNR offset and +1.44 dB
     coefficient SNR; the thresholds keep about half of each."""
     S, F = 2, 4
-    pcm = _content("music", 2, S, F, seed=57)
+    pcm = T.content("music", 2, S, F, seed=57)
     src = np.stack([H.orc_encode(p, 2, 192000, chmap=(0, 1, 0, 0, 0, 0, 0, 0)) for p in pcm])
     dec = np.stack([np.clip(np.round(H.orc_decode(src[s], 2, 1.0, 0.0)[0].transpose(0, 1, 3, 2).reshape(-1, 2) * 32768.0),
                             -32768, 32767) for s in range(S)]).astype(np.int16)
@@ -392,7 +351,7 @@ def test_pre_echo_with_block_switching(engine):
     pcm = M.attack_pcm(F, nch, onsets, amp=20000.0, seed=91)[None]
     e = {}
     for xs in (0, 1):
-        frames = _encode(engine, pcm, nch, xs=xs, bsw=1)[0]
+        frames = T.encode(engine, pcm, xs=xs, bsw=1)[0]
         out, errs, _ = H.orc_decode(frames, 2, 1.0, 0.0)
         assert errs == 0
         dec = out.transpose(0, 1, 3, 2).reshape(-1, nch).astype(np.float64) * 32768.0

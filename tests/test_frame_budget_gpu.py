@@ -25,11 +25,9 @@ import numpy as np
 import pytest
 
 from tests import _harness as H
+from tests import _tools as T
 from tests import ac3_syntax as A
 from tests import layout_model as M
-from tests.test_coupling_gpu import _content
-from tests.test_drc_gpu import _programme
-from tests.test_layout_gpu import _encode, _transcode, _with_lfe
 
 sys.path.insert(0, os.path.join(H.ROOT, "profiles"))
 import search_sim                                       # noqa: E402
@@ -52,7 +50,7 @@ def matrix_rate(nch, hi, names):
 
 
 META = dict(dialnorm=24, bsmod=2, cmixlev=0, surmixlev=2, dsurmod=1, copyrightb=0, origbs=0)
-TOOLS = {"bsw": dict(bsw=1), "remat": dict(remat=1), "cpl": dict(cpl=2), "bw": dict(bw=(2, 0)), "drc": dict(md=META, drc=1),
+TOOLS = {"bsw": dict(bsw=1), "remat": dict(remat=1), "cpl": dict(cpl=(1, 2)), "bw": dict(bw=(2, 0)), "drc": dict(md=META, drc=1),
          "xs": dict(xs=1)}
 APPLIES = {"remat": lambda nch: nch == 2, "cpl": lambda nch: nch >= 2}
 F = 3
@@ -75,7 +73,7 @@ def settings(names):
 def matrix_content(nch, frames=F):
     """[6][frames * 1536][nch]: the harness's music, bursts and strobe, the coupling tests' music, attack and identical"""
     a = [H.gen_pcm(frames, nch, seed=700 + i, kind=k) for i, k in enumerate(("music", "bursts", "strobe"))]
-    b = [_content(k, nch, 1, frames, seed=710 + i)[0] for i, k in enumerate(("music", "attack", "identical"))]
+    b = [T.content(k, nch, 1, frames, seed=710 + i)[0] for i, k in enumerate(("music", "attack", "identical"))]
     return np.stack(a + b)
 
 
@@ -170,14 +168,13 @@ def audit(rep, frames, taps, start, label):
             rep.n["coupled"] += P.blocks[0].cplinu
 
 
-def run_config(engine, rep, pcm, label, layout=None, rate=None, sr=48000, chmap=None, **kw):
+def run_config(engine, rep, pcm, label, layout=T.KEEP, rate=None, sr=48000, **kw):
     """One configuration: encode with taps, audit (items 1-4), then item 5."""
     import torch
     S, n, nch = pcm.shape
     nfr = n // 1536
     drc = bool(kw.get("drc"))
-    if chmap is None and layout is None and nch == 6:
-        chmap = H.CHMAP6
+    chmap = T.chmap_of(nch) if layout is T.KEEP else tuple(range(nch))     # (a layout is given the input order)
 
     def fresh():
         return dict(last=torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda"),
@@ -186,18 +183,18 @@ def run_config(engine, rep, pcm, label, layout=None, rate=None, sr=48000, chmap=
 
     rep.n["configs"] += 1
     common = dict(layout=layout, rate=rate, sr=sr, chmap=chmap, **kw)
-    frames, taps = _encode(engine, pcm, taps=True, **fresh(), **common)
+    frames, taps = T.encode(engine, pcm, taps=True, **fresh(), **common)
     audit(rep, frames, taps, np.full(S, 40), label)
     for pack in (1, 2):
         engine.set_encode_mode(pack)
         try:
-            got = _encode(engine, pcm, **fresh(), **common)
+            got = T.encode(engine, pcm, **fresh(), **common)
         finally:
             engine.set_encode_mode(0)
         if not np.array_equal(got, frames):
             rep.fail("packers", label, "pack mode %d differs in %d frames" % (pack, int((got != frames).any(axis=2).sum())))
     st = fresh()
-    parts = [_encode(engine, pcm[:, :1536], **st, **common), _encode(engine, pcm[:, 1536:], **st, **common)] if nfr > 1 else []
+    parts = [T.encode(engine, pcm[:, :1536], **st, **common), T.encode(engine, pcm[:, 1536:], **st, **common)] if nfr > 1 else []
     if parts and not np.array_equal(np.concatenate(parts, 1), frames):
         rep.fail("call-shape", label, "1 + %d frames with carried state differ in %d frames" % (
             nfr - 1, int((np.concatenate(parts, 1) != frames).any(axis=2).sum())))
@@ -244,7 +241,7 @@ def test_exponent_strategies_with_coupling(engine, nch, begf):
     pcm = matrix_content(nch)
     for hi in (0, 1):
         for extra in (dict(), dict(remat=1) if nch == 2 else dict(bsw=1)):
-            run_config(engine, rep, pcm, "%dch xs + cpl begf %d %r" % (nch, begf, extra), rate=matrix_rate(nch, hi, ("xs",) if nch == 6 else ()), xs=1, cpl=begf, **extra)
+            run_config(engine, rep, pcm, "%dch xs + cpl begf %d %r" % (nch, begf, extra), rate=matrix_rate(nch, hi, ("xs",) if nch == 6 else ()), xs=1, cpl=(1, begf), **extra)
     rep.finish("exponent strategies + coupling at begf %d, %d channels" % (begf, nch))
     assert rep.n["frames"] == 4 * 6 * F and rep.n["coupled"] > 0
 
@@ -255,7 +252,7 @@ def test_exponent_strategies_with_coupling(engine, nch, begf):
 def test_drc_programme(engine, nch, profile):
     """twelve frames from -60 dBFS to -5 dBFS and silence: some blocks send a word and some do not"""
     rep = Report()
-    pcm = _programme(nch, seed=11 + nch)
+    pcm = T.programme(nch, seed=11 + nch)
     for hi in (0, 1):
         run_config(engine, rep, pcm, "%dch drc %d" % (nch, profile), rate=RATES[nch][hi], md=META, drc=profile)
     if nch == 2:
@@ -272,8 +269,8 @@ def test_transcode_follows_a_20_lfe_source(engine):
     exponent strategies, metadata and DRC on (no taps in a transcode: items 1-3 and the packers)"""
     import torch
     rep = Report()
-    p3 = _with_lfe(matrix_content(2), 43)
-    src = _encode(engine, p3, layout=(1, 2, 1), rate=256000)
+    p3 = T.with_lfe(matrix_content(2), 43)
+    src = T.encode(engine, p3, layout=(1, 2, 1), rate=256000)
     outs = []
     for pack in (0, 1, 2):
         state = torch.zeros((src.shape[0],), dtype=torch.int32, device="cuda")
@@ -287,7 +284,7 @@ def test_transcode_follows_a_20_lfe_source(engine):
         engine.set_encode_metadata(**META)
         engine.set_encode_drc(1, state)
         try:
-            out, oflags = _transcode(engine, src, 2, 1, 2 | 16, None, rate=192000)
+            out, oflags = T.transcode(engine, src, 2, 1, 2 | 16, None, rate=192000)
         finally:
             engine.set_encode_mode(0)
             engine.set_encode_layout(0)
@@ -324,7 +321,7 @@ def test_large_batch(engine):
     sample = np.concatenate([np.array([np.nonzero(idx == k)[0][0] for k in range(len(pool))]), rng.integers(0, S, 18)])
     kw = settings(TOOLS)
     csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-    frames, taps = _encode(engine, pool[idx], rate=RATES[2][0], taps=True, csnr=csnr, **kw)
+    frames, taps = T.encode(engine, pool[idx], rate=RATES[2][0], taps=True, csnr=csnr, **kw)
     rep.n["configs"] += 1
     audit(rep, frames[sample], {k: v[sample] for k, v in taps.items()}, np.full(len(sample), 40), "large batch")
     first = {int(idx[s]): s for s in sample[::-1]}
@@ -334,12 +331,12 @@ def test_large_batch(engine):
     for pack in (1, 2):
         engine.set_encode_mode(pack)
         try:
-            got = _encode(engine, pool[idx], rate=RATES[2][0], **kw)
+            got = T.encode(engine, pool[idx], rate=RATES[2][0], **kw)
         finally:
             engine.set_encode_mode(0)
         if not np.array_equal(got, frames):
             rep.fail("packers", "large batch", "pack mode %d differs in %d frames" % (pack, int((got != frames).any(axis=2).sum())))
-    small = _encode(engine, pool, rate=RATES[2][0], **kw)
+    small = T.encode(engine, pool, rate=RATES[2][0], **kw)
     if not np.array_equal(small, frames[[first[k] for k in range(len(pool))]]):
         rep.fail("call-shape", "large batch", "a six-stream call gives other bytes")
     rep.finish("large batch, %d streams" % S)
@@ -358,8 +355,8 @@ def test_exponent_strategies_overrun_small_frames(engine, nch):
     pcm = matrix_content(nch)[5:6]
     rate = RATES[nch][0]
     chmap = H.CHMAP6 if nch == 6 else None
-    f0, t0 = _encode(engine, pcm, rate=rate, taps=True, chmap=chmap)
-    f1, t1 = _encode(engine, pcm, rate=rate, taps=True, chmap=chmap, xs=1)
+    f0, t0 = T.encode(engine, pcm, rate=rate, taps=True, chmap=chmap)
+    f1, t1 = T.encode(engine, pcm, rate=rate, taps=True, chmap=chmap, xs=1)
     nfbw = min(nch, 5)
 
     def exponent_bits(t):

@@ -9,82 +9,15 @@ import numpy as np
 import pytest
 
 from tests import _harness as H
+from tests import _tools as T
 from tests import drc_model as D
 from tests import layout_model as M
-from tests.test_coupling_gpu import _content
 
 pytestmark = pytest.mark.gpu
 
 AC3MI_ERR_ARG = -1
 WIDTH_OF_CODE = {0: 0, 1: -1, 2: -2, 3: 3, 4: -3, 5: 4, 14: 14, 15: 16}
 WIDTH_OF_CODE.update({c: c - 1 for c in range(6, 14)})
-
-
-def _rate(nch):
-    return 192000 if nch <= 2 else 384000
-
-
-def _encode(engine, pcm, layout=None, rate=None, sr=48000, taps=False, chmap=None, last=None, csnr=None,
-            bsw=0, remat=0, cpl=None, bw=(0, 50), xs=0, md=None, drc=0, state=None):
-    """pcm [S][F*1536][nch] s16 -> frames [S][F][fb][, taps]; layout (mode, acmod, lfeon) or None (the context's), the
-    tools as given, all reset afterwards."""
-    import torch
-    pkg = H.pkg()
-    S, n, nch = pcm.shape
-    F = n // 1536
-    enc = pkg.EncodeDesc(sr, rate or _rate(nch), nch)
-    if last is None:
-        last = torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda")
-    if csnr is None:
-        csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-    if drc and state is None:
-        state = torch.zeros((S,), dtype=torch.int32, device="cuda")
-    if layout is not None:
-        engine.set_encode_layout(*layout)
-    engine.set_encode_block_switch(bsw)
-    engine.set_encode_rematrix(remat)
-    engine.set_encode_coupling(*((1, cpl) if cpl is not None else (0, 0)))
-    engine.set_encode_bandwidth(*bw)
-    engine.set_encode_exp_strategy(xs)
-    if md:
-        engine.set_encode_metadata(**md)
-    engine.set_encode_drc(drc, state if drc else None)
-    try:
-        r = engine.encode_batch(enc, torch.from_numpy(np.ascontiguousarray(pcm, np.int16)).cuda().view(S, F, 1536, nch),
-                                chmap if chmap is not None else tuple(range(nch)), last, csnr, taps=taps)
-        engine.sync()
-    finally:
-        if layout is not None:
-            engine.set_encode_layout(0)
-        engine.set_encode_block_switch(0)
-        engine.set_encode_rematrix(0)
-        engine.set_encode_coupling(0, 0)
-        engine.set_encode_bandwidth(0)
-        engine.set_encode_exp_strategy(0)
-        engine.set_encode_metadata()
-        engine.set_encode_drc(0)
-    fb = enc.frame_bytes()
-    if taps:
-        return r[0].cpu().numpy()[:, :, :fb], {k: v.cpu().numpy() for k, v in r[1].items()}
-    return r.cpu().numpy()[:, :, :fb]
-
-
-def _tones(acmod, lfeon, S, F, seed):
-    """[S][F*1536][nch]: every full-bandwidth channel its own three tones and a little noise (a channel swap reads as
-    noise), the LFE two tones below 100 Hz (inside its 7 coded bins)."""
-    nch = M.channels(acmod, lfeon)
-    t = np.arange(F * 1536)
-    out = np.zeros((S, F * 1536, nch))
-    for s in range(S):
-        rng = np.random.default_rng(seed + 97 * s)
-        for c in range(nch):
-            if lfeon and c == nch - 1:
-                out[s, :, c] = 7000 * np.sin(2 * np.pi * 45 / 48000 * t) + 5000 * np.sin(2 * np.pi * 80 / 48000 * t + 1.0)
-                continue
-            f = (310 + 530 * c) * rng.uniform(0.95, 1.05) * np.array([1.0, 2.37, 4.11])
-            out[s, :, c] = sum(a * np.sin(2 * np.pi * fr / 48000 * t + rng.uniform(0, 6)) for a, fr in zip((6000, 3000, 1500), f))
-            out[s, :, c] += rng.standard_normal(F * 1536) * 60
-    return np.round(out).astype(np.int16)
 
 
 def _orc_decode(frames, flags):
@@ -132,15 +65,7 @@ def _planes(pcm):
     return pcm.transpose(2, 0, 1, 3).reshape(pcm.shape[2], -1).astype(np.float64)
 
 
-def _decodes_cleanly(frames, acmod, lfeon):
-    import bench
-    assert bench.ac3_crc_ok(frames.reshape(-1, frames.shape[2])) == 0
-    for s in range(frames.shape[0]):
-        _, errs, oflags, _, _ = _orc_decode(frames[s], M.decode_flags(acmod, lfeon))
-        assert errs == 0 and oflags == M.decode_flags(acmod, lfeon)
-
-
-TOOLS = [dict(), dict(bsw=1), dict(remat=1), dict(cpl=0), dict(bw=(2, 0)), dict(xs=1),
+TOOLS = [dict(), dict(bsw=1), dict(remat=1), dict(cpl=(1, 0)), dict(bw=(2, 0)), dict(xs=1),
          dict(md=dict(dialnorm=24, cmixlev=0, surmixlev=2, dsurmod=1), drc=1)]
 
 
@@ -148,30 +73,31 @@ TOOLS = [dict(), dict(bsw=1), dict(remat=1), dict(cpl=0), dict(bw=(2, 0)), dict(
 def test_mode0_and_reference_layouts_are_todays_encoder(engine, nch):
     """Items 1 and 2: with each tool set, the bytes of mode 0 are those before any setting, after a mode-1 layout was set
     and mode 0 restored, and those of mode 1 with the reference's own layout for the channel count."""
-    pcm = _content("music", nch, 2, 3, seed=11 + nch)
+    pcm = T.content("music", nch, 2, 3, seed=11 + nch)
     other = {1: (0, 1), 2: (0, 0), 3: (4, 0), 4: (5, 0), 5: (6, 1), 6: (7, 1)}[nch]
     for kw in TOOLS:
-        want = _encode(engine, pcm, **kw)
+        kw = dict(kw, chmap=tuple(range(nch)))          # (the input order, for six channels too)
+        want = T.encode(engine, pcm, **kw)
         engine.set_encode_layout(1, *other)
         engine.set_encode_layout(0)
-        assert np.array_equal(_encode(engine, pcm, **kw), want), kw
-        assert np.array_equal(_encode(engine, pcm, layout=(1,) + M.REF_LAYOUT[nch], **kw), want), kw
-        assert np.array_equal(_encode(engine, pcm, layout=(2, 0, 0), **kw), want), kw       # encode_batch: mode 2 codes as 0
+        assert np.array_equal(T.encode(engine, pcm, **kw), want), kw
+        assert np.array_equal(T.encode(engine, pcm, layout=(1,) + M.REF_LAYOUT[nch], **kw), want), kw
+        assert np.array_equal(T.encode(engine, pcm, layout=(2, 0, 0), **kw), want), kw       # encode_batch: mode 2 codes as 0
 
 
 def test_21_against_30_differs_in_acmod_and_crc1_only(engine):
     """Item 3: 2/1 and 3/0 have three full-bandwidth channels and a 2-bit mixlev field at the same position, so the same PCM
     must give frames that differ only in the acmod bits of byte 6 and in crc1 (bytes 2-3)."""
-    pcm = _content("music", 3, 2, 3, seed=21)
+    pcm = T.content("music", 3, 2, 3, seed=21)
     for md in (None, dict(cmixlev=0, surmixlev=0), dict(cmixlev=2, surmixlev=2, dialnorm=20)):
-        a = _encode(engine, pcm, layout=(1, 3, 0), md=md)
-        b = _encode(engine, pcm, layout=(1, 4, 0), md=md)
+        a = T.encode(engine, pcm, layout=(1, 3, 0), md=md)
+        b = T.encode(engine, pcm, layout=(1, 4, 0), md=md)
         assert (a[:, :, 6] >> 5 == 3).all() and (b[:, :, 6] >> 5 == 4).all()
         d = a != b
         assert not d[:, :, 7:].any() and not d[:, :, :2].any() and not d[:, :, 4:6].any()
         assert np.array_equal(a[:, :, 6] & 0x1f, b[:, :, 6] & 0x1f)
         assert d[:, :, 2:4].any()
-        _decodes_cleanly(b, 4, 0)
+        T.decodes_cleanly(b, 4, 0)
 
 
 # Measured on the MI355X when written (printed per case): per-channel SNR 13.3 - 41 dB; the lowest are the fifth channel
@@ -190,8 +116,8 @@ def test_every_layout_decodes(engine, acmod, lfeon, rate, sr):
     at the lowest) and no other (below 3 dB)."""
     nch = M.channels(acmod, lfeon)
     nf = M.NFCHANS[acmod]
-    pcm = _tones(acmod, lfeon, 1, 3, seed=acmod * 2 + lfeon)
-    frames, t = _encode(engine, pcm, layout=(1, acmod, lfeon), rate=rate, sr=sr, taps=True)
+    pcm = T.tones(acmod, lfeon, 1, 3, seed=acmod * 2 + lfeon)
+    frames, t = T.encode(engine, pcm, layout=(1, acmod, lfeon), rate=rate, sr=sr, taps=True, chmap=tuple(range(nch)))
     fb = frames.shape[2]
     n, fl, srr, br = _syncinfo(frames[0, 0])
     assert n == fb and srr == sr and br == rate
@@ -226,40 +152,34 @@ def test_dual_mono_fields(engine):
     """Item 5: dialnorm2 = dialnorm; under every DRC profile the second dynrng word equals the first in every block and
     both are tests/drc_model.py's code over the two channels; coupling and rematrixing leave the bytes of both off."""
     import torch
-    from tests.test_drc_gpu import _gpu_decode, _programme
-    pcm = _tones(0, 0, 2, 3, seed=5)
+    pcm = T.tones(0, 0, 2, 3, seed=5)
     for md, dn in ((None, 31), (dict(dialnorm=24), 24)):
-        fr = _encode(engine, pcm, layout=(1, 0, 0), md=md)
+        fr = T.encode(engine, pcm, layout=(1, 0, 0), md=md)
         for f in fr.reshape(-1, fr.shape[2]):
             b = M.bsi(f)
             assert b["acmod"] == 0 and b["dialnorm"] == dn and b["dialnorm2"] == dn
             assert b["compr2e"] == b["langcod2e"] == b["audprodi2e"] == 0
-        _decodes_cleanly(fr, 0, 0)
-    prog = _programme(2, seed=3)
+        T.decodes_cleanly(fr, 0, 0)
+    prog = T.programme(2, seed=3)
     for profile in (1, 2, 3, 4, 5):
         state = torch.zeros((1,), dtype=torch.int32, device="cuda")
-        fr = _encode(engine, prog, layout=(1, 0, 0), drc=profile, state=state, md=dict(dialnorm=27))
+        fr = T.encode(engine, prog, layout=(1, 0, 0), drc=profile, state=state, md=dict(dialnorm=27))
         codes, snt, s_end, _ = D.encode(prog[0], (0, 1), 2, profile, 27)
         assert int(state.cpu()[0]) == s_end
-        _, status, taps = _gpu_decode(engine, fr, 0, 0, 0, taps=True)
+        _, status, taps = T.decode(engine, fr, 0, 0, 0, taps=True)
         assert (status & 0x1ff).max() == 0
         w0, w1 = taps["dynrng"][0, :, :, 0], taps["dynrng"][0, :, :, 1]
         assert np.array_equal(w0, w1, equal_nan=True), profile
         assert np.array_equal(~np.isnan(w0), snt), profile
         want = np.array([[D.decoded_gain(v) for v in row] for row in codes], np.float32)
         assert np.array_equal(w0[snt], want[snt]), profile
-        _decodes_cleanly(fr, 0, 0)
-    pcm = _content("identical", 2, 2, 3, seed=9)               # what coupling and rematrixing would take
-    off = _encode(engine, pcm, layout=(1, 0, 0))
-    assert np.array_equal(_encode(engine, pcm, layout=(1, 0, 0), cpl=0), off)
-    assert np.array_equal(_encode(engine, pcm, layout=(1, 0, 0), remat=1), off)
-    assert np.array_equal(_encode(engine, pcm, layout=(1, 0, 0), remat=1, cpl=0, bsw=1), _encode(engine, pcm, layout=(1, 0, 0), bsw=1))
-    assert not np.array_equal(_encode(engine, pcm, layout=(1, 2, 0), remat=1), _encode(engine, pcm, layout=(1, 2, 0)))
-
-
-def _with_lfe(pcm2, seed):
-    lfe = _tones(1, 1, pcm2.shape[0], pcm2.shape[1] // 1536, seed)[:, :, 1:]
-    return np.concatenate([pcm2, lfe], 2)
+        T.decodes_cleanly(fr, 0, 0)
+    pcm = T.content("identical", 2, 2, 3, seed=9)               # what coupling and rematrixing would take
+    off = T.encode(engine, pcm, layout=(1, 0, 0))
+    assert np.array_equal(T.encode(engine, pcm, layout=(1, 0, 0), cpl=(1, 0)), off)
+    assert np.array_equal(T.encode(engine, pcm, layout=(1, 0, 0), remat=1), off)
+    assert np.array_equal(T.encode(engine, pcm, layout=(1, 0, 0), remat=1, cpl=(1, 0), bsw=1), T.encode(engine, pcm, layout=(1, 0, 0), bsw=1))
+    assert not np.array_equal(T.encode(engine, pcm, layout=(1, 2, 0), remat=1), T.encode(engine, pcm, layout=(1, 2, 0)))
 
 
 def test_20_lfe_rematrixing(engine):
@@ -267,36 +187,36 @@ def test_20_lfe_rematrixing(engine):
     flags, which tests/test_rematrix_gpu.py holds against tests/rematrix_model.py; the same exponents and strategies), the
     LFE's taps are those of the same input without rematrixing, and with coupling and bandwidth the frames decode
     cleanly; both packer variants agree."""
-    p2 = _content("music", 2, 2, 4, seed=41)
-    p3 = _with_lfe(p2, 43)
+    p2 = T.content("music", 2, 2, 4, seed=41)
+    p3 = T.with_lfe(p2, 43)
     for kw in (dict(), dict(bsw=1), dict(bw=(1, 30)), dict(xs=1)):
-        f2, t2 = _encode(engine, p2, remat=1, taps=True, rate=192000, **kw)
-        f3, t3 = _encode(engine, p3, layout=(1, 2, 1), remat=1, taps=True, rate=192000, **kw)
-        f3n, t3n = _encode(engine, p3, layout=(1, 2, 1), taps=True, rate=192000, **kw)
+        f2, t2 = T.encode(engine, p2, remat=1, taps=True, rate=192000, **kw)
+        f3, t3 = T.encode(engine, p3, layout=(1, 2, 1), remat=1, taps=True, rate=192000, **kw)
+        f3n, t3n = T.encode(engine, p3, layout=(1, 2, 1), taps=True, rate=192000, **kw)
         for k in ("encoded_exp", "exp_strategy", "exp_samples"):
             assert np.array_equal(t3[k][:, :, :, :2], t2[k]), (kw, k)
             assert np.array_equal(t3[k][:, :, :, 2], t3n[k][:, :, :, 2]), (kw, k)
         assert not np.array_equal(t3["encoded_exp"][:, :, :, :2], t3n["encoded_exp"][:, :, :, :2])   # rematrixing happened
-        _decodes_cleanly(f3, 2, 1)
-    for kw in (dict(cpl=0), dict(cpl=2, bw=(2, 0)), dict(cpl=4, bsw=1), dict(cpl=2, xs=1), dict(cpl=0, bw=(1, 24), xs=1)):
-        f3 = _encode(engine, p3, layout=(1, 2, 1), remat=1, rate=192000, **kw)
-        _decodes_cleanly(f3, 2, 1)
+        T.decodes_cleanly(f3, 2, 1)
+    for kw in (dict(cpl=(1, 0)), dict(cpl=(1, 2), bw=(2, 0)), dict(cpl=(1, 4), bsw=1), dict(cpl=(1, 2), xs=1), dict(cpl=(1, 0), bw=(1, 24), xs=1)):
+        f3 = T.encode(engine, p3, layout=(1, 2, 1), remat=1, rate=192000, **kw)
+        T.decodes_cleanly(f3, 2, 1)
         for pack in (1, 2):
             engine.set_encode_mode(pack)
             try:
-                assert np.array_equal(_encode(engine, p3, layout=(1, 2, 1), remat=1, rate=192000, **kw), f3), (kw, pack)
+                assert np.array_equal(T.encode(engine, p3, layout=(1, 2, 1), remat=1, rate=192000, **kw), f3), (kw, pack)
             finally:
                 engine.set_encode_mode(0)
     # dual mono with metadata and DRC through both packers
-    pd = _tones(0, 1, 2, 3, seed=77)
-    want = _encode(engine, pd, layout=(1, 0, 1), md=dict(dialnorm=20), drc=2)
+    pd = T.tones(0, 1, 2, 3, seed=77)
+    want = T.encode(engine, pd, layout=(1, 0, 1), md=dict(dialnorm=20), drc=2)
     for pack in (1, 2):
         engine.set_encode_mode(pack)
         try:
-            assert np.array_equal(_encode(engine, pd, layout=(1, 0, 1), md=dict(dialnorm=20), drc=2), want), pack
+            assert np.array_equal(T.encode(engine, pd, layout=(1, 0, 1), md=dict(dialnorm=20), drc=2), want), pack
         finally:
             engine.set_encode_mode(0)
-    _decodes_cleanly(want, 0, 1)
+    T.decodes_cleanly(want, 0, 1)
 
 
 def test_call_shapes(engine):
@@ -304,12 +224,12 @@ def test_call_shapes(engine):
     F calls of one frame carrying the state, permuted state slots and a tile bound give the same bytes."""
     import torch
     S, F = 3, 6
-    cases = [((1, 4, 1), dict(bsw=1, cpl=2, drc=1, md=dict(dialnorm=24))),
-             ((1, 2, 1), dict(remat=1, cpl=3, bw=(2, 0))),
+    cases = [((1, 4, 1), dict(bsw=1, cpl=(1, 2), drc=1, md=dict(dialnorm=24))),
+             ((1, 2, 1), dict(remat=1, cpl=(1, 3), bw=(2, 0))),
              ((1, 0, 0), dict(drc=3))]
     for layout, kw in cases:
         nch = M.channels(*layout[1:])
-        pcm = _content("music", nch, S, F, seed=61 + nch)
+        pcm = T.content("music", nch, S, F, seed=61 + nch)
 
         def fresh():
             # (state slots index the history as [slot][6][256]: the array holds six channel rows per slot)
@@ -318,10 +238,10 @@ def test_call_shapes(engine):
                     torch.full((S,), 40, dtype=torch.int32, device="cuda"))
 
         st, _, last, csnr = fresh()
-        whole = _encode(engine, pcm, layout=layout, state=st, last=last, csnr=csnr, **kw)
+        whole = T.encode(engine, pcm, layout=layout, state=st, last=last, csnr=csnr, **kw)
         st_whole = st.cpu().numpy().copy()
         st, _, last, csnr = fresh()
-        got = [_encode(engine, pcm[:, f * 1536:(f + 1) * 1536], layout=layout, state=st, last=last, csnr=csnr, **kw)
+        got = [T.encode(engine, pcm[:, f * 1536:(f + 1) * 1536], layout=layout, state=st, last=last, csnr=csnr, **kw)
                for f in range(F)]
         assert np.array_equal(np.concatenate(got, 1), whole), layout
         assert np.array_equal(st.cpu().numpy(), st_whole)
@@ -330,7 +250,7 @@ def test_call_shapes(engine):
         last_s = big.view(-1)[:S * nch * 256].view(S, nch, 256)
         engine._check(engine.lib.ac3mi_set_state_slots(ctypes.c_void_p(engine.ctx), ctypes.c_void_p(perm.data_ptr())))
         try:
-            got = [_encode(engine, pcm[:, f * 1536:(f + 1) * 1536], layout=layout, state=st, last=last_s, csnr=csnr, **kw)
+            got = [T.encode(engine, pcm[:, f * 1536:(f + 1) * 1536], layout=layout, state=st, last=last_s, csnr=csnr, **kw)
                    for f in range(F)]
         finally:
             engine._check(engine.lib.ac3mi_set_state_slots(ctypes.c_void_p(engine.ctx), None))
@@ -339,10 +259,10 @@ def test_call_shapes(engine):
         engine._check(engine.lib.ac3mi_set_tile_frames(ctypes.c_void_p(engine.ctx), ctypes.c_longlong(F)))
         try:
             st, _, last, csnr = fresh()
-            assert np.array_equal(_encode(engine, pcm, layout=layout, state=st, last=last, csnr=csnr, **kw), whole), layout
+            assert np.array_equal(T.encode(engine, pcm, layout=layout, state=st, last=last, csnr=csnr, **kw), whole), layout
         finally:
             engine._check(engine.lib.ac3mi_set_tile_frames(ctypes.c_void_p(engine.ctx), ctypes.c_longlong(0)))
-        _decodes_cleanly(whole, *layout[1:])
+        T.decodes_cleanly(whole, *layout[1:])
 
 
 def test_large_batch_20_lfe(engine):
@@ -351,34 +271,15 @@ def test_large_batch_20_lfe(engine):
     import bench
     S = 65536
     rng = np.random.default_rng(71)
-    pool = _with_lfe(_content("music", 2, 8, 1, seed=72), 73)
+    pool = T.with_lfe(T.content("music", 2, 8, 1, seed=72), 73)
     idx = rng.integers(0, len(pool), S)
     gain = rng.uniform(0.3, 1.0, (S, 1, 1))
     pcm = (pool[idx].astype(np.float64) * gain).astype(np.int16)
-    frames = _encode(engine, pcm, layout=(1, 2, 1), remat=1, rate=192000)
+    frames = T.encode(engine, pcm, layout=(1, 2, 1), remat=1, rate=192000)
     assert bench.ac3_crc_ok(frames.reshape(-1, frames.shape[2])) == 0
     pick = rng.integers(0, S, 16)
-    assert np.array_equal(_encode(engine, pcm[pick], layout=(1, 2, 1), remat=1, rate=192000), frames[pick])
-    _decodes_cleanly(frames[pick], 2, 1)
-
-
-def _transcode(engine, src, acmod, lfeon, flags, chmap, rate=384000):
-    import torch
-    pkg = H.pkg()
-    S, F, fb = src.shape
-    buf = np.zeros((S, F, (fb + 3) & ~3), np.uint8)
-    buf[:, :, :fb] = src
-    dec = pkg.DecodeDesc(flags=flags, level=1.0, bias=384.0, dynrng=1, acmod=acmod, lfeon=lfeon, frame_bytes=fb)
-    n_out, oflags = engine.decode_planes(dec)
-    enc = pkg.EncodeDesc(48000, rate, n_out)
-    delay = torch.zeros((S, n_out, 128), dtype=torch.float32, device="cuda")
-    lfsr = torch.ones((S,), dtype=torch.int16, device="cuda")
-    last = torch.zeros((S, n_out, 256), dtype=torch.int16, device="cuda")
-    csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-    out, status = engine.transcode_batch(dec, enc, torch.from_numpy(buf).cuda(), delay, lfsr, chmap, last, csnr)
-    engine.sync()
-    assert int((status.cpu() & 0x1ff).max()) == 0
-    return out.cpu().numpy()[:, :, :enc.frame_bytes()], oflags
+    assert np.array_equal(T.encode(engine, pcm[pick], layout=(1, 2, 1), remat=1, rate=192000), frames[pick])
+    T.decodes_cleanly(frames[pick], 2, 1)
 
 
 # (decoded input against decoded output, per channel: measured 25.6 - 41 dB when written, lowest on the fifth channel of
@@ -391,11 +292,12 @@ def test_transcode_follows_the_source(engine, acmod, lfeon):
     """Item 8: sources from this encoder in every layout, transcoded under mode 2 with the layout's own output flags: the
     new frames carry the layout, and each decoded channel matches the same decoded channel of the source."""
     nch = M.channels(acmod, lfeon)
-    src = _encode(engine, _tones(acmod, lfeon, 2, 3, seed=81 + acmod), layout=(1, acmod, lfeon), rate=384000)
+    src = T.encode(engine, T.tones(acmod, lfeon, 2, 3, seed=81 + acmod), layout=(1, acmod, lfeon), rate=384000,
+                   chmap=tuple(range(nch)))
     flags = M.decode_flags(acmod, lfeon)
     engine.set_encode_layout(2)
     try:
-        out, oflags = _transcode(engine, src, acmod, lfeon, flags, None)
+        out, oflags = T.transcode(engine, src, acmod, lfeon, flags, None)
     finally:
         engine.set_encode_layout(0)
     assert oflags == flags
@@ -413,28 +315,28 @@ def test_transcode_follows_the_source(engine, acmod, lfeon):
 def test_transcode_granted_outputs_and_mode0(engine):
     """Item 8: 3/2 -> STEREO codes 2/0, A52_DOLBY 2/0, A52_CHANNEL1 of dual mono 1/0; under mode 0 a 2/0+LFE source still
     gives the 3/0 bytes (the reference's table for three channels)."""
-    p51 = _tones(7, 1, 2, 3, seed=91)
-    s51 = _encode(engine, p51, rate=384000, chmap=(0, 1, 2, 3, 4, 5))
-    sdm = _encode(engine, _tones(0, 0, 2, 3, seed=92), layout=(1, 0, 0))
+    p51 = T.tones(7, 1, 2, 3, seed=91)
+    s51 = T.encode(engine, p51, rate=384000, chmap=(0, 1, 2, 3, 4, 5))
+    sdm = T.encode(engine, T.tones(0, 0, 2, 3, seed=92), layout=(1, 0, 0))
     engine.set_encode_layout(2)
     try:
-        out, of = _transcode(engine, s51, 7, 1, 2, None, rate=192000)
+        out, of = T.transcode(engine, s51, 7, 1, 2, None, rate=192000)
         assert of == 2 and (out[:, :, 6] >> 5 == 2).all()
-        _decodes_cleanly(out, 2, 0)
-        out, of = _transcode(engine, s51, 7, 1, M.A52_DOLBY, None, rate=192000)
+        T.decodes_cleanly(out, 2, 0)
+        out, of = T.transcode(engine, s51, 7, 1, M.A52_DOLBY, None, rate=192000)
         assert of == M.A52_DOLBY and (out[:, :, 6] >> 5 == 2).all()
-        _decodes_cleanly(out, 2, 0)
-        out, of = _transcode(engine, sdm, 0, 0, M.A52_CHANNEL1, None, rate=192000)
+        T.decodes_cleanly(out, 2, 0)
+        out, of = T.transcode(engine, sdm, 0, 0, M.A52_CHANNEL1, None, rate=192000)
         assert of == M.A52_CHANNEL1 and (out[:, :, 6] >> 5 == 1).all()
-        _decodes_cleanly(out, 1, 0)
+        T.decodes_cleanly(out, 1, 0)
     finally:
         engine.set_encode_layout(0)
-    s21 = _encode(engine, _tones(2, 1, 2, 3, seed=93), layout=(1, 2, 1))
-    out0, of = _transcode(engine, s21, 2, 1, 2 | 16, (0, 1, 2), rate=384000)
+    s21 = T.encode(engine, T.tones(2, 1, 2, 3, seed=93), layout=(1, 2, 1))
+    out0, of = T.transcode(engine, s21, 2, 1, 2 | 16, (0, 1, 2), rate=384000)
     assert (out0[:, :, 6] >> 5 == 3).all()
     engine.set_encode_layout(1, 3, 0)
     try:
-        out1, _ = _transcode(engine, s21, 2, 1, 2 | 16, (0, 1, 2), rate=384000)
+        out1, _ = T.transcode(engine, s21, 2, 1, 2 | 16, (0, 1, 2), rate=384000)
     finally:
         engine.set_encode_layout(0)
     assert np.array_equal(out0, out1)
@@ -447,14 +349,14 @@ def test_setter_validation_and_stream_layer(engine):
     import torch
     pkg = H.pkg()
     lib, ctx = engine.lib, ctypes.c_void_p(engine.ctx)
-    pcm = _tones(4, 0, 1, 2, seed=3)
+    pcm = T.tones(4, 0, 1, 2, seed=3)
     engine.set_encode_layout(1, 4, 0)
     try:
         for args in ((3, 0, 0), (-1, 0, 0), (1, 8, 0), (1, -1, 0), (1, 0, 2), (1, 0, -1)):
             assert lib.ac3mi_set_encode_layout(ctx, *args) == AC3MI_ERR_ARG, args
             with pytest.raises(pkg.AC3MIError if hasattr(pkg, "AC3MIError") else Exception):
                 engine.set_encode_layout(*args)
-        fr = _encode(engine, pcm)                               # still 2/1
+        fr = T.encode(engine, pcm)                               # still 2/1
         assert (fr[:, :, 6] >> 5 == 4).all()
         enc = pkg.EncodeDesc(48000, 192000, 2)
         last = torch.zeros((1, 2, 256), dtype=torch.int16, device="cuda")
