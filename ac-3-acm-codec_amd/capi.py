@@ -39,6 +39,24 @@ class EncodeTapsC(ctypes.Structure):
                 ("d_snroffst", c_void_p)]
 
 
+class BsiInfoC(ctypes.Structure):
+    """ac3mi_bsi_info"""
+    _fields_ = ([(k, ctypes.c_uint8) for k in ("verdict", "fscod", "frmsizecod", "bsid", "bsmod", "acmod", "lfeon", "cmixlev",
+                                               "surmixlev", "dsurmod", "dialnorm", "dialnorm2", "compr", "compr2", "langcod",
+                                               "langcod2", "audprodi", "audprodi2", "copyrightb", "origbs", "addbsil", "reserved")] +
+                [(k, ctypes.c_uint16) for k in ("present", "timecod1", "timecod2", "block0_bit", "reserved2")] +
+                [("word", ctypes.c_uint32)])
+
+
+def bsi_info_dtype():
+    """ac3mi_bsi_info as a numpy structured dtype (36 bytes; a uint8 tensor [..., 36] views as it)"""
+    import numpy as np
+    t = {ctypes.c_uint8: "u1", ctypes.c_uint16: "<u2", ctypes.c_uint32: "<u4"}
+    dt = np.dtype([(k, t[c]) for k, c in BsiInfoC._fields_])
+    assert dt.itemsize == ctypes.sizeof(BsiInfoC) == 36
+    return dt
+
+
 _lib = None
 
 
@@ -95,6 +113,11 @@ def load_library():
     lib.ac3mi_set_encode_coupling.argtypes = [c_void_p, c_int, c_int]
     lib.ac3mi_set_encode_bandwidth.argtypes = [c_void_p, c_int, c_int]
     lib.ac3mi_set_encode_metadata.argtypes = [c_void_p, c_void_p]
+    lib.ac3mi_encode_metadata_word.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+    lib.ac3mi_set_encode_metadata_frames.argtypes = [c_void_p, c_void_p]
+    lib.ac3mi_set_encode_metadata_source.argtypes = [c_void_p, c_int]
+    lib.ac3mi_bsi_read.argtypes = [c_void_p, c_int, ctypes.POINTER(BsiInfoC)]
+    lib.ac3mi_bsi_read_batch.argtypes = [c_void_p, c_void_p, c_int, c_int, c_size_t, c_void_p]
     lib.ac3mi_set_encode_drc.argtypes = [c_void_p, c_int, c_void_p]
     lib.ac3mi_set_encode_exp_strategy.argtypes = [c_void_p, c_int]
     lib.ac3mi_set_encode_layout.argtypes = [c_void_p, c_int, c_int, c_int]

@@ -186,6 +186,37 @@ constexpr uint32_t bsi_word(int dialnorm, int bsmod, int cmixlev, int surmixlev,
            (uint32_t)dsurmod << 12 | (uint32_t)copyrightb << 14 | (uint32_t)origbs << 15;
 }
 constexpr uint32_t BSI_DEFAULT = bsi_word(31, 0, 1, 1, 0, 0, 1);      // the reference's fixed BSI
+// The sanitising rule (include/ac3mi.h, ac3mi_bsi_info): what a raw bsi_word becomes before the packers code it - dialnorm 0
+// (reserved) 31, cmixlev 3 and surmixlev 3 the levels liba52's tables give the reserved code (1), dsurmod 3 0; bsmod,
+// copyrightb and origbs pass.  The BSI reader (bsi.hip) and the encoder's per-frame words (encode.hip) both go through it.
+__host__ __device__ constexpr uint32_t bsi_sanitise(uint32_t w)
+{
+    w &= 0xffffu;
+    if ((w & 31u) == 0) w |= 31u;
+    if ((w & 0x300u) == 0x300u) w ^= 0x200u;
+    if ((w & 0xc00u) == 0xc00u) w ^= 0x800u;
+    if ((w & 0x3000u) == 0x3000u) w ^= 0x3000u;
+    return w;
+}
+static_assert(bsi_sanitise(BSI_DEFAULT) == BSI_DEFAULT && bsi_sanitise(bsi_word(0, 5, 3, 3, 3, 1, 0)) == bsi_word(31, 5, 1, 1, 0, 1, 0), "rule");
+
+// bsi.hip: one lane per frame reads bytes 0-5 and the BSI.  `info` (ac3mi_bsi_read_batch): the record of every frame.
+// `words` (ac3mi_set_encode_metadata_source 1, ahead of a transcode's encoder): per frame the bsi_word the new frame codes -
+// the source's dialnorm, bsmod, copyrightb, origbs, and cmixlev / surmixlev / dsurmod where the source sent the field and
+// `coded_acmod` sends it, else ctx_word's; ctx_word whole for a frame the decoder refuses (header test, frame_bytes, another
+// acmod / lfeon than the call's, or bit 6 of its `crc` verdict byte - crc may be null).  Exactly one of info / words is set.
+struct BsiLaunch {
+    const uint8_t *frames;
+    size_t n_frames;
+    int frame_stride, frame_bytes;
+    ac3mi_bsi_info *info = nullptr;
+    uint32_t *words = nullptr;
+    const uint8_t *crc = nullptr;
+    int acmod = 0, lfeon = 0, coded_acmod = 0;
+    uint32_t ctx_word = BSI_DEFAULT;
+};
+hipError_t launch_bsi(const BsiLaunch &L, hipStream_t stream);
+void bsi_read_host(const uint8_t *buf, int len, ac3mi_bsi_info *out);
 
 struct EncodeLaunch {
     EncConfig cfg;
@@ -218,6 +249,9 @@ struct EncodeLaunch {
     int chbwcod = 50;           // ac3mi_set_encode_bandwidth: the call's chbwcod (0..50), nbc = 73 + 3 chbwcod
     bool bw = false;            // ... and whether it is on (mode 1 or 2): the runtime-bandwidth kernel variants run
     uint32_t bsi = BSI_DEFAULT; // ac3mi_set_encode_metadata, packed (bsi_word); not the default: the packers' MD variants run
+    // ac3mi_set_encode_metadata_frames / _source: [S][F] raw words by the frame's position in the call (never by slot), coded
+    // as bsi_sanitise(word) in place of `bsi`; frame f's dialnorm is also its DRC dialogue level.  Non-null: the MD variants run
+    const uint32_t *bsi_words = nullptr;
     int drc_profile = 0;        // ac3mi_set_encode_drc: 1..5, 0 = no dynrng words
     int32_t *drc_state = nullptr;   // its smoothing state, [S] (or by slot)
     int16_t *ws_drc_gain = nullptr; // [S][F][6] static-curve gains (drc_profile > 0)
@@ -255,6 +289,8 @@ struct EncTools {
     int coupling = 0, cpl_begf = 0;     // ac3mi_set_encode_coupling
     int bw_mode = 0, bw_chbwcod = 50;   // ac3mi_set_encode_bandwidth
     uint32_t bsi = BSI_DEFAULT;         // ac3mi_set_encode_metadata (bsi_word)
+    const uint32_t *bsi_words = nullptr;    // ac3mi_set_encode_metadata_frames
+    int md_source = 0;                  // ac3mi_set_encode_metadata_source
     int drc_profile = 0;                // ac3mi_set_encode_drc
     int32_t *drc_state = nullptr;
     int exp_strategy = 0;               // ac3mi_set_encode_exp_strategy
@@ -285,11 +321,12 @@ struct ac3mi_ctx {
     ac3mi::DevBuf ws_cplr;  // with rematrixing on as well: cpl_remat_frame_bytes a frame
     ac3mi::DevBuf ws_drc;   // DRC gains and codes between the DRC kernels, the search and the packers, 3 bytes a frame-block
     ac3mi::DevBuf ws_crc;   // decode with ac3mi_set_decode_crc on: the CRC kernel's verdicts for the front end, one byte per frame
+    ac3mi::DevBuf ws_bsi;   // transcode with ac3mi_set_encode_metadata_source 1: the BSI kernel's word per frame for the packers
     // every workspace above (ac3mi_destroy frees them, ac3mi_workspace_bytes sums them)
     template <class Ctx> static auto workspaces(Ctx *c)
     {
         return std::array{&c->ws_coef, &c->ws_blksw, &c->ws_draws, &c->ws_split, &c->ws_enc, &c->ws_tc,
-                          &c->ws_bsw, &c->ws_remat, &c->ws_cpl, &c->ws_cplr, &c->ws_drc, &c->ws_crc};
+                          &c->ws_bsw, &c->ws_remat, &c->ws_cpl, &c->ws_cplr, &c->ws_drc, &c->ws_crc, &c->ws_bsi};
     }
     // optional state-slot indirection for the next batch calls (ac3mi_set_state_slots)
     const int32_t *slots = nullptr;

@@ -771,6 +771,17 @@ static int call_chbwcod(const ac3mi_ctx *ctx, const ac3mi_encode_desc *d, int nf
     return c;
 }
 
+int ac3mi_encode_metadata_word(const ac3mi_encode_metadata *md, uint32_t *word)
+{
+    if (!md || !word) return AC3MI_ERR_ARG;
+    auto in = [](int v, int lo, int hi) { return v >= lo && v <= hi; };
+    if (!in(md->dialnorm, 1, 31) || !in(md->bsmod, 0, 7) || !in(md->cmixlev, 0, 2) || !in(md->surmixlev, 0, 2) ||
+        !in(md->dsurmod, 0, 2) || !in(md->copyrightb, 0, 1) || !in(md->origbs, 0, 1))
+        return AC3MI_ERR_ARG;
+    *word = ac3mi::bsi_word(md->dialnorm, md->bsmod, md->cmixlev, md->surmixlev, md->dsurmod, md->copyrightb, md->origbs);
+    return AC3MI_OK;
+}
+
 int ac3mi_set_encode_metadata(ac3mi_ctx *ctx, const ac3mi_encode_metadata *md)
 {
     if (!ctx) return AC3MI_ERR_ARG;
@@ -778,13 +789,24 @@ int ac3mi_set_encode_metadata(ac3mi_ctx *ctx, const ac3mi_encode_metadata *md)
         ctx->tools.bsi = ac3mi::BSI_DEFAULT;
         return AC3MI_OK;
     }
-    auto in = [](int v, int lo, int hi) { return v >= lo && v <= hi; };
-    if (!in(md->dialnorm, 1, 31) || !in(md->bsmod, 0, 7) || !in(md->cmixlev, 0, 2) || !in(md->surmixlev, 0, 2) ||
-        !in(md->dsurmod, 0, 2) || !in(md->copyrightb, 0, 1) || !in(md->origbs, 0, 1)) {
+    if (ac3mi_encode_metadata_word(md, &ctx->tools.bsi) != AC3MI_OK) {
         ctx->err = "ac3mi_set_encode_metadata: field out of range";
         return AC3MI_ERR_ARG;
     }
-    ctx->tools.bsi = ac3mi::bsi_word(md->dialnorm, md->bsmod, md->cmixlev, md->surmixlev, md->dsurmod, md->copyrightb, md->origbs);
+    return AC3MI_OK;
+}
+
+int ac3mi_set_encode_metadata_frames(ac3mi_ctx *ctx, const uint32_t *d_words)
+{
+    if (!ctx || ((uintptr_t)d_words & 3)) return AC3MI_ERR_ARG;
+    ctx->tools.bsi_words = d_words;
+    return AC3MI_OK;
+}
+
+int ac3mi_set_encode_metadata_source(ac3mi_ctx *ctx, int mode)
+{
+    if (!ctx || mode < 0 || mode > 1) return AC3MI_ERR_ARG;
+    ctx->tools.md_source = mode;
     return AC3MI_OK;
 }
 
@@ -845,19 +867,23 @@ static int tile_streams(const ac3mi_ctx *ctx, int n_streams, int frames_per_stre
 
 // The context's per-stream pointers while a batch goes through in tiles: at(s0) points them at the tile's first stream s0
 // (the state slots when set, else the mix state of mix_n_out chains a stream - 0: it stays - and with `drc` the encoder's
-// DRC state); the destructor puts them back.
+// DRC state; with `drc` also the per-frame metadata words, which go by the frame's position in the call, slots or not); the
+// destructor puts them back.
 struct TileState {
     ac3mi_ctx *ctx;
     int mix_n_out;
     bool drc;
+    int frames_per_stream;
     const int32_t *slots;
     float *mix_pending;
     int32_t *mix_flags, *drc_state;
-    TileState(ac3mi_ctx *c, int mix_n_out, bool drc)
-        : ctx(c), mix_n_out(mix_n_out), drc(drc), slots(c->slots), mix_pending(c->mix_pending), mix_flags(c->mix_flags),
-          drc_state(c->tools.drc_state) {}
+    const uint32_t *bsi_words;
+    TileState(ac3mi_ctx *c, int mix_n_out, bool drc, int frames_per_stream)
+        : ctx(c), mix_n_out(mix_n_out), drc(drc), frames_per_stream(frames_per_stream), slots(c->slots), mix_pending(c->mix_pending),
+          mix_flags(c->mix_flags), drc_state(c->tools.drc_state), bsi_words(c->tools.bsi_words) {}
     void at(int s0)
     {
+        if (drc && bsi_words) ctx->tools.bsi_words = bsi_words + (size_t)s0 * frames_per_stream;
         if (slots) { ctx->slots = slots + s0; return; }
         if (mix_n_out && mix_pending) {
             ctx->mix_pending = mix_pending + (size_t)s0 * mix_n_out * 128;
@@ -871,6 +897,7 @@ struct TileState {
         ctx->mix_pending = mix_pending;
         ctx->mix_flags = mix_flags;
         ctx->tools.drc_state = drc_state;
+        ctx->tools.bsi_words = bsi_words;
     }
 };
 
@@ -1082,6 +1109,7 @@ static int encode_setup(ac3mi_ctx *ctx, EncodeLaunch &E, const ac3mi_encode_desc
         }
     }
     E.bsi = t.bsi;
+    E.bsi_words = t.bsi_words;
     E.drc_profile = t.drc_profile;
     if (t.drc_profile) {                            // [nfr][6] int16 gains, then [nfr][6] codes
         TRY(ws_grow(ctx, ctx->ws_drc, 18 * nfr));
@@ -1208,6 +1236,33 @@ int ac3mi_crc_check_batch(ac3mi_ctx *ctx, const uint8_t *d_frames, int frame_str
     return AC3MI_OK;
 }
 
+int ac3mi_bsi_read(const uint8_t *buf, int len, ac3mi_bsi_info *out)
+{
+    if (!buf || !out || len < 0) return AC3MI_ERR_ARG;
+    bsi_read_host(buf, len, out);
+    return AC3MI_OK;
+}
+
+int ac3mi_bsi_read_batch(ac3mi_ctx *ctx, const uint8_t *d_frames, int frame_stride, int frame_bytes, size_t n_frames,
+                         ac3mi_bsi_info *d_info)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (!d_frames || !d_info || n_frames > 0x7fffffffu || frame_bytes < 8 || frame_bytes > 3840 ||
+        frame_stride < ((frame_bytes + 3) & ~3) || (frame_stride & 3) || ((uintptr_t)d_frames & 3) || ((uintptr_t)d_info & 3)) {
+        ctx->err = "ac3mi_bsi_read_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    BsiLaunch B;
+    B.frames = d_frames;
+    B.n_frames = n_frames;
+    B.frame_stride = frame_stride;
+    B.frame_bytes = frame_bytes;
+    B.info = d_info;
+    HIPCHK(ctx, launch_bsi(B, ctx->stream));
+    return AC3MI_OK;
+}
+
 int ac3mi_decode_planes(const ac3mi_decode_desc *desc, int *n_out, int *out_flags)
 {
     if (!desc || desc->acmod < 0 || desc->acmod > 7) return AC3MI_ERR_ARG;
@@ -1245,7 +1300,7 @@ static int decode_impl(ac3mi_ctx *ctx, const ac3mi_decode_desc *desc, const uint
     const FrontEnd fe = front_end(ctx, X.plan, n_streams, frames_per_stream, d_pcm16 != nullptr, taps != nullptr, true);
     if (const int g = (taps || fe.fused) ? 0 : tile_streams(ctx, n_streams, frames_per_stream)) {
         // bounded workspace: whole streams at a time (streams are independent; state arrays move with them)
-        TileState tile(ctx, n_out, false);
+        TileState tile(ctx, n_out, false, frames_per_stream);
         int rc = AC3MI_OK;
         for (int s0 = 0; s0 < n_streams && rc == AC3MI_OK; s0 += g) {
             const int ns = n_streams - s0 < g ? n_streams - s0 : g;
@@ -1415,7 +1470,7 @@ int ac3mi_encode_batch(ac3mi_ctx *ctx, const ac3mi_encode_desc *desc, const int1
         }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (const int g = taps ? 0 : tile_streams(ctx, n_streams, frames_per_stream)) {
-        TileState tile(ctx, 0, true);
+        TileState tile(ctx, 0, true, frames_per_stream);
         int rc = AC3MI_OK;
         for (int s0 = 0; s0 < n_streams && rc == AC3MI_OK; s0 += g) {
             const int ns = n_streams - s0 < g ? n_streams - s0 : g;
@@ -1497,7 +1552,7 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         if (E.chmap[i] >= enc->channels) { ctx->err = "ac3mi_transcode_batch: chmap entry out of range"; return AC3MI_ERR_ARG; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (const int g = tile_streams(ctx, n_streams, frames_per_stream)) {
-        TileState tile(ctx, n_out, true);
+        TileState tile(ctx, n_out, true, frames_per_stream);
         int rc = AC3MI_OK;
         for (int s0 = 0; s0 < n_streams && rc == AC3MI_OK; s0 += g) {
             const int ns = n_streams - s0 < g ? n_streams - s0 : g;
@@ -1518,6 +1573,7 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     TRY(ws_grow(ctx, ctx->ws_tc, s16_ws_bytes(nfr, n_out)));
     TRY(grow_front_ws(ctx, fe, nfr));
     TRY(encode_setup(ctx, E, enc, nfr, nullptr));
+    if (t.md_source == 1) TRY(ws_grow(ctx, ctx->ws_bsi, nfr * sizeof(uint32_t)));
     uint8_t *const zs = fe.mixstate ? ctx->ws_blksw.at<uint8_t>(zs_off(nfr, X.plan.nfchans)) : nullptr;
     int16_t *const ws_s16 = ctx->ws_tc.at<int16_t>();
     // Decoder front end, transform to s16, encoder: back to back on the context's stream.  (Until round 2 two chunks were
@@ -1530,6 +1586,23 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     // whole before the other stream's (the others), so the chunks' latency floors add up instead of overlapping.)
     DecodeLaunch D = decode_launch(ctx, fe, &dd, d_frames_in, in_stride, n_streams, frames_per_stream, d_lfsr, d_status);
     TRY(crc_pass(ctx, &dd, d_frames_in, in_stride, nfr, &D.crc));
+    if (t.md_source == 1 && nfr) {
+        // ac3mi_set_encode_metadata_source 1: the BSI kernel over this call's (or tile's) input frames, after the CRC kernel whose
+        // verdicts it reads, ahead of the encoder that codes from its words; an array of ac3mi_set_encode_metadata_frames is not read
+        BsiLaunch B;
+        B.frames = d_frames_in;
+        B.n_frames = nfr;
+        B.frame_stride = in_stride;
+        B.frame_bytes = dd.frame_bytes;
+        B.words = ctx->ws_bsi.at<uint32_t>();
+        B.crc = D.crc;
+        B.acmod = dd.acmod;
+        B.lfeon = dd.lfeon ? 1 : 0;
+        B.coded_acmod = E.cfg.acmod;
+        B.ctx_word = t.bsi;
+        HIPCHK(ctx, launch_bsi(B, ctx->stream));
+        E.bsi_words = B.words;
+    }
     D.coef = fe.mantx ? nullptr : ctx->ws_coef.at<float>();
     D.blksw = ctx->ws_blksw.at<uint8_t>();
     D.zs = zs;

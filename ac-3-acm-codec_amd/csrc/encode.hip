@@ -78,7 +78,16 @@ struct PackParams {
     int cpl_endf;               // cplendf of a coupled frame: 12, min(12, chbwcod >> 2) in the BW variants (cplendmant 73 + 12 cplendf)
     const uint8_t *drc;         // the DRC variants: [S][F][6] dynrng codes (enc_drc_smooth_kernel); null in the others
     uint32_t bsi;               // the MD packers: the BSI fields (bsi_word)
+    const uint32_t *bsi_words;  // the MD packers: optional, [S][F] raw words by the frame's position in the call; frame f then codes bsi_sanitise(bsi_words[f])
 };
+
+// the BSI fields frame fidx codes (MD packers): the call's word, or the frame's own from the array (ac3mi_set_encode_metadata_frames /
+// _source), sanitised here so that no array can make the packers write a reserved code.  Read where the header is written and
+// nowhere else: a scalar load, nothing kept live across the frame
+__device__ __forceinline__ uint32_t pack_bsi(const PackParams &P, size_t fidx)
+{
+    return P.bsi_words ? bsi_sanitise((uint32_t)__builtin_amdgcn_readfirstlane((int)P.bsi_words[fidx])) : P.bsi;
+}
 
 // dynrng words of a frame (ac3mi_set_encode_drc): block 0 sends its code, block b > 0 only when it differs from block b - 1's
 __device__ __forceinline__ bool drc_sends(const uint8_t *code, int b) { return b == 0 || code[b] != code[b - 1]; }
@@ -2117,7 +2126,8 @@ struct alignas(16) PackfLDS {
 // CPL: coupled frames (channel coupling on, never with FIXED51): the coupling fields, exponents and mantissa pass
 // BW (ac3mi_set_encode_bandwidth 1 or 2): FIXED51 with the run-time nbc; CPL with the coupling range ending at cplendmant =
 // 73 + 12 P.cpl_endf (3 + cpl_endf - cpl_begf bands, cplendf = P.cpl_endf)
-// MD (ac3mi_set_encode_metadata / ac3mi_set_encode_drc): the BSI fields of P.bsi, and the dynrng words of P.drc if it is set
+// MD (ac3mi_set_encode_metadata / _frames / _source, ac3mi_set_encode_drc): the BSI fields of P.bsi or of the frame's own word
+// (pack_bsi), and the dynrng words of P.drc if it is set
 // DUAL (dual mono, acmod 0; generic and uncoupled only): the second programme's BSI fields and dynrng2e / dynrng2
 template <bool FIXED51, bool CPL = false, bool BW = false, bool MD = false, bool DUAL = false>
 __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackParams P)
@@ -2198,7 +2208,7 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         }
     };
     if constexpr (MD) {
-        const uint32_t m = P.bsi;
+        const uint32_t m = pack_bsi(P, fidx);
         put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, (m >> 5) & 7u); put(3, acmod);
         flush();
         if ((acmod & 1) && acmod != 1) put(2, (m >> 8) & 3u);
@@ -2481,7 +2491,8 @@ struct alignas(16) PackbLDS {
                               // counts, not occupancy: cold encode 0.107 / 0.113 / 0.189 / 0.286 ms per 64 / 256 / 1 024 / 2 048 frames against 0.110 /
                               // 0.121 / 0.186 / 0.291 at 6
 #endif
-// MD (ac3mi_set_encode_metadata / ac3mi_set_encode_drc): the BSI fields of P.bsi, and the dynrng words of P.drc if it is set
+// MD (ac3mi_set_encode_metadata / _frames / _source, ac3mi_set_encode_drc): the BSI fields of P.bsi or of the frame's own word
+// (pack_bsi), and the dynrng words of P.drc if it is set
 template <bool MD = false>
 __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const PackParams P)
 {
@@ -2609,7 +2620,7 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
             const uint32_t mine = pos;
             pos = 0;
             if constexpr (MD) {
-                const uint32_t m = P.bsi;
+                const uint32_t m = pack_bsi(P, fidx);
                 put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, (m >> 5) & 7u); put(3, P.acmod);
                 flush();
                 if ((P.acmod & 1) && P.acmod != 1) put(2, (m >> 8) & 3u);
@@ -2786,7 +2797,7 @@ static uint32_t h_gf_pow(uint32_t a, uint32_t n)
 //                          MDCT kernels stay as they are), levels relative to dialnorm and the profile's static gain
 //   enc_drc_smooth_kernel  one lane per stream, its frames in order: the attack / release smoothing and the codes
 // The tables are exact (no entry within 1e-4 of a rounding tie), computed once in double precision and frozen here:
-//   DRC_LG[m] = round(256 log2(1 + m / 256)), DRC_XT[f] = round(32 (2^(f / 256) - 1)); DN[d] is folded in on the host.
+//   DRC_LG[m] = round(256 log2(1 + m / 256)), DRC_XT[f] = round(32 (2^(f / 256) - 1)); DN[d] is folded in on the host, or, with a word per frame, picked by the frame's wavefront.
 __constant__ uint8_t DRC_LG[256] = {
     0, 1, 3, 4, 6, 7, 9, 10, 11, 13, 14, 16, 17, 18, 20, 21, 22, 24, 25, 26, 28, 29, 30, 32, 33, 34, 36, 37, 38, 40, 41, 42,
     44, 45, 46, 47, 49, 50, 51, 52, 54, 55, 56, 57, 59, 60, 61, 62, 63, 65, 66, 67, 68, 69, 71, 72, 73, 74, 75, 77, 78, 79, 80, 81,
@@ -2821,6 +2832,8 @@ struct DrcParams {
     int n_streams, frames, nch;
     uint32_t fbw_in;            // bit c: input channel c is a coded full-bandwidth channel (chmap[0 .. nfbw - 1])
     int dn;                     // DN[dialnorm]
+    const uint32_t *bsi_words;  // optional, [S][F]: frame f's level is relative to its own dialnorm, dn_tab[bsi_sanitise(bsi_words[f]) & 31]
+    int16_t dn_tab[32];         // DN, for the frames' own picks (read from the kernel-argument segment)
     int mb, rb, n0, n1, c0, re, rc;
 };
 
@@ -2877,6 +2890,7 @@ __global__ __launch_bounds__(64) void enc_drc_gain_kernel(const DrcParams Q)
             e6[b] = e;
         }
     }
+    const int dn = Q.bsi_words ? (int)Q.dn_tab[bsi_sanitise(Q.bsi_words[fidx]) & 31u] : Q.dn;
     int g_lane = 0;
 #pragma unroll
     for (int b = 0; b < 6; b++) {
@@ -2890,7 +2904,7 @@ __global__ __launch_bounds__(64) void enc_drc_gain_kernel(const DrcParams Q)
             const int m = (int)(((e << 8) >> k) & 255u);
             lev = max(-4096, 256 * k + (int)DRC_LG[m] - 37 * 256);
         }
-        const int r = lev + Q.dn;
+        const int r = lev + dn;
         int g;
         if (r < Q.n0) g = min(Q.mb, ((Q.n0 - r) * (Q.rb - 1)) / Q.rb);
         else if (r <= Q.n1) g = 0;
@@ -2940,6 +2954,8 @@ static hipError_t launch_drc(const EncodeLaunch &E, hipStream_t stream)
     Q.fbw_in = 0;
     for (int ch = 0; ch < c.nfbw; ch++) Q.fbw_in |= 1u << E.chmap[ch];
     Q.dn = DRC_DN[E.bsi & 31u];
+    Q.bsi_words = E.bsi_words;
+    for (int d = 0; d < 32; d++) Q.dn_tab[d] = DRC_DN[d];
     const int16_t *k = DRC_CURVE[E.drc_profile - 1];
     Q.mb = k[0]; Q.rb = k[1]; Q.n0 = k[2]; Q.n1 = k[3]; Q.c0 = k[4]; Q.re = k[5]; Q.rc = k[6];
     const dim3 frames((unsigned)E.n_streams * (unsigned)E.frames_per_stream);
@@ -2961,8 +2977,8 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     // the packers' member lists (enc_mant.h) hold the grouped mantissas of at most 5 x MAX_NBC + 7 coefficients a block
     if (c.nfbw * nbc + 7 > MANT_MAX_COEFS) return hipErrorInvalidValue;
     // metadata and dynamic range control: the DRC kernels write the frames' codes first; with DRC on the search costs the words
-    // (DRC variants), with either on the packers write them (MD variants).  Both off: exactly the kernels of before
-    const bool drc = E.drc_profile != 0, md = drc || E.bsi != BSI_DEFAULT;
+    // (DRC variants), with either on, or a word per frame (bsi_words), the packers write them (MD variants).  All off: exactly the kernels of before
+    const bool drc = E.drc_profile != 0, md = drc || E.bsi != BSI_DEFAULT || E.bsi_words != nullptr;
     if (drc) {
         const hipError_t ed = launch_drc(E, stream);
         if (ed != hipSuccess) return ed;
@@ -3124,6 +3140,7 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.cpl_endf = bw ? cpl_endf : 12;
     P.drc = drc ? E.ws_drc_code : nullptr;
     P.bsi = E.bsi;
+    P.bsi_words = E.bsi_words;
 #ifndef ENC_FR_HEADROOM
 #define ENC_FR_HEADROOM 256
 #endif

@@ -61,6 +61,31 @@ def syncinfo(buf):
     return n, fl.value, sr.value, br.value
 
 
+def bsi_read(buf):
+    """ac3mi_bsi_read on host bytes (a frame, or only its head) -> a numpy record of capi.bsi_info_dtype()."""
+    import numpy as np
+    lib = capi.load_library()
+    data = bytes(bytearray(buf))
+    b = (ctypes.c_uint8 * max(1, len(data))).from_buffer_copy(data or b"\0")
+    info = capi.BsiInfoC()
+    if lib.ac3mi_bsi_read(b, len(data), ctypes.byref(info)) != 0:
+        raise capi.AC3MIError("ac3mi_bsi_read: bad argument")
+    return np.frombuffer(bytes(info), capi.bsi_info_dtype())[0]
+
+
+def encode_metadata_word(**fields):
+    """ac3mi_encode_metadata_word: the fields of Engine.set_encode_metadata (those not given: the defaults) -> the packed
+    word; raises on a field out of range."""
+    unknown = set(fields) - set(Engine._METADATA_FIELDS)
+    if unknown:
+        raise TypeError("unknown metadata field(s): %s" % ", ".join(sorted(unknown)))
+    md = (ctypes.c_int * 7)(*[int(fields.get(k, d)) for k, d in zip(Engine._METADATA_FIELDS, Engine._METADATA_DEFAULTS)])
+    w = ctypes.c_uint32()
+    if capi.load_library().ac3mi_encode_metadata_word(ctypes.cast(md, ctypes.c_void_p), ctypes.byref(w)) != 0:
+        raise capi.AC3MIError("ac3mi_encode_metadata_word: field out of range")
+    return w.value
+
+
 class Engine:
     def __init__(self, device=0):
         self.lib = capi.load_library()
@@ -322,6 +347,42 @@ class Engine:
         vals = [int(fields.get(k, d)) for k, d in zip(self._METADATA_FIELDS, self._METADATA_DEFAULTS)]
         md = (ctypes.c_int * 7)(*vals)
         self._check(self.lib.ac3mi_set_encode_metadata(ctypes.c_void_p(self.ctx), ctypes.cast(md, ctypes.c_void_p)))
+
+    def set_encode_metadata_frames(self, words=None):
+        """BSI metadata per frame (ac3mi_set_encode_metadata_frames): `words` int32 / uint32 [S][F] on the device, one
+        encode_metadata_word per frame of the following encode_batch / transcode_batch calls (sanitised by the engine; kept
+        referenced while set); None returns to the context's one word."""
+        if words is not None:
+            import torch
+            if words.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not words.is_cuda or not words.is_contiguous():
+                raise ValueError("words must be a contiguous int32 / uint32 tensor on the device")
+            torch.cuda.current_stream().synchronize()       # their fill was queued on torch's stream
+        self._check(self.lib.ac3mi_set_encode_metadata_frames(ctypes.c_void_p(self.ctx),
+                                                              ctypes.c_void_p(words.data_ptr()) if words is not None else None))
+        self._md_words = words
+
+    def set_encode_metadata_source(self, mode):
+        """Where transcode_batch takes the new frames' BSI metadata from (ac3mi_set_encode_metadata_source): 0 = the context's
+        settings, 1 = each source frame's own BSI (flags.MD_SOURCE_FOLLOW)."""
+        self._check(self.lib.ac3mi_set_encode_metadata_source(ctypes.c_void_p(self.ctx), int(mode)))
+
+    def bsi_read_batch(self, frames, frame_bytes=None, out=None, wait_torch=True):
+        """ac3mi_bsi_read_batch: frames [...][stride] u8 on the device (stride multiple of 4; frame_bytes = the largest frame's
+        size, default the stride) -> records u8 [...][36]; `.cpu().numpy().view(capi.bsi_info_dtype())[..., 0]` names the fields."""
+        import torch
+        assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.is_cuda and frames.dim() >= 2
+        stride = frames.shape[-1]
+        n = frames.numel() // stride if stride else 0
+        size = ctypes.sizeof(capi.BsiInfoC)
+        if out is None:
+            out = torch.zeros(tuple(frames.shape[:-1]) + (size,), dtype=torch.uint8, device=frames.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n * size
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_bsi_read_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(frames.data_ptr()), int(stride),
+                                                  int(stride if frame_bytes is None else frame_bytes), ctypes.c_size_t(n),
+                                                  ctypes.c_void_p(out.data_ptr())))
+        self._keep.append((frames, out))
+        return out
 
     def set_encode_drc(self, profile, state=None):
         """Dynamic range control (ac3mi_set_encode_drc): profile 0 = no dynrng words, 1..5 = film standard / film light /

@@ -29,3 +29,9 @@ STATUS_CRC2 = 0x800         # CRC-16 of bytes [2 fs58, 2 fs) is not 0
 CRC_OFF, CRC_REPORT, CRC_CONCEAL = 0, 1, 2
 # ac3mi_crc_check_batch verdict bits
 VERDICT_CRC1, VERDICT_CRC2, VERDICT_NOT_SUMMED = 1, 2, 0x80
+# ac3mi_bsi_info: verdict bits and the bits of `present`
+BSI_NOT_READ, BSI_OVERRUN = 0x80, 0x40
+BSI_PRESENT = {"compre": 0x001, "langcode": 0x002, "audprodie": 0x004, "compr2e": 0x008, "langcod2e": 0x010,
+               "audprodi2e": 0x020, "timecod1e": 0x040, "timecod2e": 0x080, "addbsie": 0x100}
+# ac3mi_set_encode_metadata_source modes
+MD_SOURCE_CONTEXT, MD_SOURCE_FOLLOW = 0, 1

@@ -196,6 +196,58 @@ int ac3mi_set_decode_crc(ac3mi_ctx *ctx, int mode);
 int ac3mi_crc_check_batch(ac3mi_ctx *ctx, const uint8_t *d_frames, int frame_stride, int frame_bytes, size_t n_frames,
                           uint8_t *d_verdict);
 
+/* A frame's syncinfo and BSI, read without decoding it (new).  One parser, compiled for the host and for gfx950, is the only
+ * statement of the syntax behind both entry points: a52_syncinfo's header test on bytes 0-5 (the one of ac3mi_crc_check_batch's
+ * bit 7), then A/52 5.3.2's field list up to the first audio block.
+ *   verdict     bit 7: the frame was not read - the header test fails (no sync word, frmsizecod >= 38, fscod 3, bsid >= 12) or,
+ *               in ac3mi_bsi_read_batch, the frame is longer than frame_bytes; nothing else in the record is set then.
+ *               bit 6: the BSI runs past the bytes given (len / frame_bytes); fields up to that point are set, block0_bit is 0.
+ *   cmixlev, surmixlev, dsurmod   raw 2-bit codes, 0xff where the acmod does not send the field
+ *   dialnorm, dialnorm2           raw 5-bit codes; dialnorm2 is 0xff unless acmod 0
+ *   present     AC3MI_BSI_* bits: which optional fields the frame carries; compr .. audprodi2 (audprodi: mixlevel << 2 |
+ *               roomtyp) hold the field where its bit is set, 0 otherwise; timecod1 / timecod2 14 bits, addbsil the raw 6-bit
+ *               length code (addbsil + 1 bytes follow)
+ *   block0_bit  bit offset of audio block 0 in the frame: where the BSI ends, addbsi skipped
+ *   word        the frame's metadata as an encoder word (ac3mi_encode_metadata_word's layout) after the sanitising rule:
+ *               dialnorm 0 (reserved) -> 31; cmixlev 3 -> 1 and surmixlev 3 -> 1 (the levels liba52's tables give the reserved
+ *               code); dsurmod 3 -> 0; a field the acmod does not send takes the default (cmixlev 1, surmixlev 1, dsurmod 0);
+ *               bsmod, copyrightb and origbs as they are.
+ * The byte fields, the four 16-bit ones and the word take 36 bytes. */
+#define AC3MI_BSI_NOT_READ 0x80u
+#define AC3MI_BSI_OVERRUN 0x40u
+#define AC3MI_BSI_COMPRE 0x001u
+#define AC3MI_BSI_LANGCODE 0x002u
+#define AC3MI_BSI_AUDPRODIE 0x004u
+#define AC3MI_BSI_COMPR2E 0x008u
+#define AC3MI_BSI_LANGCOD2E 0x010u
+#define AC3MI_BSI_AUDPRODI2E 0x020u
+#define AC3MI_BSI_TIMECOD1E 0x040u
+#define AC3MI_BSI_TIMECOD2E 0x080u
+#define AC3MI_BSI_ADDBSIE 0x100u
+typedef struct {
+    uint8_t verdict, fscod, frmsizecod, bsid;
+    uint8_t bsmod, acmod, lfeon, cmixlev;
+    uint8_t surmixlev, dsurmod, dialnorm, dialnorm2;
+    uint8_t compr, compr2, langcod, langcod2;
+    uint8_t audprodi, audprodi2, copyrightb, origbs;
+    uint8_t addbsil, reserved;      /* reserved: 0 */
+    uint16_t present;
+    uint16_t timecod1, timecod2;
+    uint16_t block0_bit, reserved2; /* reserved2: 0 */
+    uint32_t word;
+} ac3mi_bsi_info;
+
+/* Host side, no GPU and no context (like ac3mi_syncinfo): `len` bytes of a frame's head at buf.  The frame's own size is not
+ * held against len - a caller may hand over no more than the head -, so bit 7 is the header test alone (or len < 6) and bit 6
+ * says that len bytes do not hold the whole BSI.  AC3MI_ERR_ARG for a NULL pointer or a negative len, else AC3MI_OK. */
+int ac3mi_bsi_read(const uint8_t *buf, int len, ac3mi_bsi_info *out);
+/* The same for n_frames frames on the device, one record each in d_info (4-byte aligned), asynchronous on the context's stream.
+ * d_frames, frame_stride and frame_bytes as in ac3mi_crc_check_batch (stride a multiple of 4 and >= frame_bytes rounded up to
+ * 4, base 4-byte aligned, frame_bytes 8..3840 the size of the largest frame); every acmod / lfeon is read.  No byte behind
+ * frame_bytes rounded up to 4 of a frame's slot is touched. */
+int ac3mi_bsi_read_batch(ac3mi_ctx *ctx, const uint8_t *d_frames, int frame_stride, int frame_bytes, size_t n_frames,
+                         ac3mi_bsi_info *d_info);
+
 /* How ac3mi_encode_batch / ac3mi_transcode_batch pack a frame once its SNR offsets are found (new; same bytes either way -
  * the searches always run first, one wavefront per stream, frames in order):
  *   1  one wavefront per frame packs it;
@@ -367,6 +419,40 @@ typedef struct {
     int origbs;      /* 0/1,   default 1 */
 } ac3mi_encode_metadata;
 int ac3mi_set_encode_metadata(ac3mi_ctx *ctx, const ac3mi_encode_metadata *md);   /* NULL: the defaults */
+
+/* ac3mi_set_encode_metadata's validation and packing without a context: *word = dialnorm (bits 0-4) | bsmod << 5 | cmixlev << 8
+ * | surmixlev << 10 | dsurmod << 12 | copyrightb << 14 | origbs << 15.  A field out of range: AC3MI_ERR_ARG, *word untouched. */
+int ac3mi_encode_metadata_word(const ac3mi_encode_metadata *md, uint32_t *word);
+
+/* BSI metadata per frame (new; applies to every following ac3mi_encode_batch / ac3mi_transcode_batch on `ctx` until set to
+ * NULL, in either packer variant and the coupled-frame packer, dual mono, with or without state slots, tiled or not).
+ * d_words: [n_streams][frames_per_stream] uint32 on the device, one word in ac3mi_encode_metadata_word's layout per frame,
+ * indexed by the frame's position in the call like d_pcm - never by state slot; a tiled call reads each tile's slice.  Frame f
+ * codes the fields of sanitise(d_words[f]) (the rule of ac3mi_bsi_info's `word`; bits 16-31 are ignored) in place of
+ * ac3mi_set_encode_metadata's: a device array can not make the packers write a reserved code.  Everything else holds per frame:
+ * the fields are sent by the coded acmod, dual mono sends dialnorm2 = dialnorm, the widths are fixed - with DRC off the bit
+ * allocation, the SNR offsets and every bit outside the BSI fields and the two CRC words are those of the defaults -, and under
+ * ac3mi_set_encode_drc a block's level is taken relative to the dialnorm of its own frame.  The array must stay alive until the
+ * calls that read it have finished.  NULL (the default): the context's one word, and exactly the kernels of before.  Ignored by
+ * a transcode under ac3mi_set_encode_metadata_source 1.  The drop-in AC3_encode_* and the byte-stream layer (ac3mi_stream.h)
+ * never read it. */
+int ac3mi_set_encode_metadata_frames(ac3mi_ctx *ctx, const uint32_t *d_words);
+
+/* Where a transcode's new frames take their BSI metadata from (new):
+ *   0  (default) the context: ac3mi_set_encode_metadata / ac3mi_set_encode_metadata_frames, whatever the source said;
+ *   1  the source: ac3mi_transcode_batch reads the BSI of its input frames (the kernel of ac3mi_bsi_read_batch, per tile, ahead
+ *      of the encoder; one word per frame in a workspace of the context - ac3mi_workspace_bytes counts it,
+ *      ac3mi_transcode_workspace_plan, which plans the default mode, does not) and codes each new frame by
+ *      ac3mi_set_encode_metadata_frames' rule from it: dialnorm, bsmod, copyrightb and origbs are the source frame's (sanitised);
+ *      cmixlev, surmixlev and dsurmod are the source's where the source's acmod sent the field and the coded acmod sends it
+ *      (a decode that downmixes and ac3mi_set_encode_layout 0 to 2 alike), else ac3mi_set_encode_metadata's.  A frame the
+ *      decoder refuses (status bit 8: no sync word, reserved codes, other acmod / lfeon, longer than frame_bytes, or concealed
+ *      by ac3mi_set_decode_crc 2) takes ac3mi_set_encode_metadata's word whole.  An array set with
+ *      ac3mi_set_encode_metadata_frames is ignored by such a transcode.  ac3mi_encode_batch has no source and is unchanged.
+ * Not carried: the source's dynrng, compr, langcod, audprod, timecode and addbsi fields - they change a frame's bit budget or
+ * lie behind the parse kernels.  The drop-in and the byte-stream layer (ac3mi_dropin.h, ac3mi_stream.h) never follow.  Any
+ * other mode: AC3MI_ERR_ARG, and the setting is unchanged. */
+int ac3mi_set_encode_metadata_source(ac3mi_ctx *ctx, int mode);
 
 /* Dynamic range control in the encoder (new; applies to every following ac3mi_encode_batch / ac3mi_transcode_batch on
  * `ctx`, in either packer variant, with or without state slots, tiled or not, with every other encoder tool on or off):
