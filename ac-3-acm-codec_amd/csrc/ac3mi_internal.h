@@ -128,6 +128,7 @@ struct DecodeLaunch {
     const XformLaunch *fuse = nullptr;
     // ac3mi_set_decode_crc 1 / 2: the CRC kernel's verdict byte per frame, [S][F] (crc.hip); null: the frames are not checked
     const uint8_t *crc = nullptr;
+    bool fixed_shape = true;            // ac3mi_set_fixed_shape: a 5.1 call may take the kernels with that shape compiled in (fixed51_shape)
 };
 hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStream_t stream);
 // decode_wg.hip: one workgroup per stream; X == nullptr: coefficient planes (+ taps) to HBM as launch_decode does;
@@ -218,6 +219,14 @@ struct BsiLaunch {
 hipError_t launch_bsi(const BsiLaunch &L, hipStream_t stream);
 void bsi_read_host(const uint8_t *buf, int len, ac3mi_bsi_info *out);
 
+// The shape large batches run at - 5.1: acmod 7 with the LFE, six planes in and out, five full-bandwidth channels.  The one
+// predicate behind every kernel variant that has it compiled in (ac3mi_set_fixed_shape): a launcher adds its own conditions -
+// one frame per stream, its stage's tools and taps off - and anything else takes the generic kernels.
+constexpr bool fixed51_shape(int acmod, int lfeon, int n_in, int n_out, int nfbw)
+{
+    return acmod == 7 && lfeon != 0 && n_in == 6 && n_out == 6 && nfbw == 5;
+}
+
 struct EncodeLaunch {
     EncConfig cfg;
     const int16_t *pcm;         // [S][F][1536][nch]
@@ -257,6 +266,7 @@ struct EncodeLaunch {
     int16_t *ws_drc_gain = nullptr; // [S][F][6] static-curve gains (drc_profile > 0)
     uint8_t *ws_drc_code = nullptr; // [S][F][6] dynrng codes for the search and the packers
     int exp_strategy = 0;       // ac3mi_set_encode_exp_strategy: 1 = strategies by cost (the XS kernel variants), 0 = the reference's rule
+    bool fixed_shape = true;    // ac3mi_set_fixed_shape: a 5.1 call may take the kernels with that shape compiled in (fixed51_shape)
 };
 // carves CPL_FRAME_BYTES * nfr bytes at `base` into the arrays of CplWs (base 16-byte aligned)
 CplWs cpl_slices(void *base, size_t nfr);
@@ -336,5 +346,6 @@ struct ac3mi_ctx {
     long long tile_frames = 131072;    // workspace bound: batches above this many frames go through in tiles of whole streams (0 = never)
     int decode_mode = 0;    // ac3mi_set_decode_mode
     int decode_crc = 0;     // ac3mi_set_decode_crc
+    int fixed_shape = 1;    // ac3mi_set_fixed_shape
     std::string err;
 };

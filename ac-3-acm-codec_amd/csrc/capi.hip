@@ -712,6 +712,13 @@ int ac3mi_set_decode_mode(ac3mi_ctx *ctx, int mode)
     return AC3MI_OK;
 }
 
+int ac3mi_set_fixed_shape(ac3mi_ctx *ctx, int on)
+{
+    if (!ctx || on < 0 || on > 1) return AC3MI_ERR_ARG;
+    ctx->fixed_shape = on;
+    return AC3MI_OK;
+}
+
 int ac3mi_set_decode_crc(ac3mi_ctx *ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 2) return AC3MI_ERR_ARG;
@@ -1046,6 +1053,7 @@ static DecodeLaunch decode_launch(const ac3mi_ctx *ctx, const FrontEnd &fe, cons
     D.status = status;
     D.lfsr = lfsr;
     D.slot = ctx->slots;
+    D.fixed_shape = ctx->fixed_shape != 0;
     D.tap_exp = nullptr;
     D.tap_bap = nullptr;
     D.frame_parallel = fe.fp ? 1 : 0;
@@ -1138,6 +1146,7 @@ static int encode_setup(ac3mi_ctx *ctx, EncodeLaunch &E, const ac3mi_encode_desc
     E.bw = t.bw_mode != 0;
     E.exp_strategy = t.exp_strategy;
     E.pack_mode = ctx->encode_mode;
+    E.fixed_shape = ctx->fixed_shape != 0;
     E.slot = ctx->slots;
     return AC3MI_OK;
 }

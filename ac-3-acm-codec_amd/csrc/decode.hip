@@ -59,11 +59,15 @@ __device__ unsigned long long g_dec_cycles[8];
 #endif
 
 // (crc_verdicts() reads DecodeParams::crc from the kernel-argument segment: P must stay this kernel's first argument)
-template <int MODE>
+// FX (MODE 4; launch_decode's fixed-shape rule): one-frame 5.1 streams - a single frame (no frame loop, nothing carried from
+// frame to frame), acmod 7 with the LFE, five full-bandwidth channels, six planes and no stage taps as constants.  A frame
+// whose header says otherwise is refused by the same tests, and its blocks then run none of the code that uses them.
+template <int MODE, bool FX = false>
 __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kernel(const DecodeParams P)
 {
     static_assert(MODE == 0 || MODE == 4 || MODE == 5, "the one-kernel front ends per frame (1, 2) were retired in round 4");
     constexpr bool SERIAL = MODE == 0 || MODE == 4;         // one wavefront per stream, frames in order
+    static_assert(!FX || MODE == 4, "the fixed 5.1 shape is the per-stream parse kernel's");
     constexpr bool PARSE = MODE >= 4;                       // no mantissa values: block descriptors + rows for mant_kernel
     __shared__ DecLDS L;
     extern __shared__ uint32_t frw[];
@@ -71,7 +75,8 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
     const int lane = threadIdx.x;
     const int s = SERIAL ? (int)blockIdx.x : (int)(blockIdx.x / (unsigned)P.frames_per_stream);
     const int f_first = SERIAL ? 0 : (int)(blockIdx.x - (unsigned)s * (unsigned)P.frames_per_stream);
-    const int f_end = SERIAL ? P.frames_per_stream : f_first + 1;
+    const int f_end = SERIAL ? (FX ? 1 : P.frames_per_stream) : f_first + 1;
+    const int n_in = FX ? 6 : P.n_in, nfchans = FX ? 5 : P.nfchans;
     if (s >= P.n_streams) return;
 
     // ---- constant tables into LDS ----
@@ -118,9 +123,9 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
     if (PARSE && lane < 7) L.tot[lane][2] = 0;
 
     for (int f = f_first; f < f_end; f++) {
-        const size_t fidx = (size_t)s * P.frames_per_stream + f;
+        const size_t fidx = FX ? (size_t)s : (size_t)s * P.frames_per_stream + f;
         const uint8_t *src = P.frames + fidx * P.frame_stride;
-        float *cout = P.coef + fidx * 6 * P.n_in * 256;
+        float *cout = P.coef + fidx * 6 * n_in * 256;
         uint32_t status = 0;
         // block 0 takes exponents, coupling or bit-allocation parameters the frame did not send (not a conforming frame):
         // what it reuses is whatever the variant at hand has carried so far, so results may depend on the batch shape
@@ -175,26 +180,26 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                 const int bsid = b5 >> 3;
                 st.set_halfrate(bsid < 9 ? 0 : bsid - 8);
                 st.acmod = b6 >> 5;
-                if (st.acmod != P.acmod) hdr_ok = false;
+                if (st.acmod != (FX ? 7 : P.acmod)) hdr_ok = false;
                 const int code = b4 & 63, rate = k_kbps[code >> 1];
                 const int fbytes = st.fscod() == 0 ? 4 * rate : st.fscod() == 1 ? 2 * (320 * rate / 147 + (code & 1)) : 6 * rate;
                 if (fbytes > P.frame_bytes) hdr_ok = false;        // frame_bytes = the largest frame of the batch (44.1 kHz alternates)
             }
         }
         if (hdr_ok) {
-            int acmod = st.acmod;
+            int acmod = FX ? 7 : st.acmod;
             rd.seek(6 * 8 + 3);
             if (acmod == 2 && rd.get(2) == 2) acmod = 10;                 // dsurmod -> DOLBY
             st.clev = st.slev = 0.f;
             if ((acmod & 1) && acmod != 1) st.clev = k_clev[rd.get(2)];
             if (acmod & 4) st.slev = k_slev[rd.get(2)];
             st.lfeon = rd.get(1);
-            if (st.lfeon != P.lfeon) hdr_ok = false;
+            if (st.lfeon != (FX ? 1 : P.lfeon)) hdr_ok = false;
             float level = P.level;
             st.output = a52_downmix_init_hd(acmod, P.req_flags, &level, st.clev, st.slev);
             if (st.output < 0) hdr_ok = false;
             if (hdr_ok) {
-                if (st.lfeon && (P.req_flags & AC3MI_LFE)) st.output |= AC3MI_LFE;
+                if ((FX || st.lfeon) && (P.req_flags & AC3MI_LFE)) st.output |= AC3MI_LFE;
                 st.dynrng = st.level = level * 2;
                 st.set_dynrnge(P.dynrng_on ? 1 : 0);
                 st.deltbae2 = 0xaaau;
@@ -212,7 +217,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                     int len = rd.get(6);
                     do rd.get(8); while (len--);
                 }
-                st.nf = k_nfchans[st.acmod];
+                st.nf = FX ? 5 : k_nfchans[st.acmod];
                 if (hth_fscod != st.fscod()) {
                     if (lane < 50) L.hth[lane] = P.tab->hth[st.fscod()][lane];
                     hth_fscod = st.fscod();
@@ -223,22 +228,24 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
         if (!hdr_ok) status |= 0x100u | 0x3fu;
 
         bool frame_dead = !hdr_ok;
+        // (the blocks of a frame that passed the header test: its acmod and lfeon are the call's)
+        const int acm = FX ? 7 : st.acmod, lfeon = FX ? 1 : st.lfeon;
         DK_LAP(0);
         for (int blk = 0; blk < 6; blk++) {
-            float *cblk = cout + (size_t)blk * P.n_in * 256;
-            const int in_lfe = P.lfeon ? 1 : 0;
+            float *cblk = cout + (size_t)blk * n_in * 256;
+            const int in_lfe = FX ? 1 : P.lfeon ? 1 : 0;
             int err = frame_dead ? 1 : 0;
             int blkswm = 0, dithmask = 0;
             bool bd_ok = false;
             float gain[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-            const int nf = st.nf;
+            const int nf = FX ? 5 : st.nf;
 
             if (!err) do {
                 // ---- side information: parse.c:572-701 ----
                 // blksw[ch], dithflag[ch]: nf flags each, channel 0 first = in the field's top bit
                 blkswm = (int)(__builtin_bitreverse32(rd.get(nf)) >> (32 - nf));
                 dithmask = (int)(__builtin_bitreverse32(rd.get(nf)) >> (32 - nf));
-                int twice = !st.acmod, word = 0;
+                int twice = !acm, word = 0;
                 do {
                     if (rd.get(1)) {
                         const int code = rd.sget(8);
@@ -251,8 +258,8 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                     st.chincpl = 0;
                     if (rd.get(1)) {                                        // cplinu
                         st.chincpl = (int)(__builtin_bitreverse32(rd.get(nf)) >> (32 - nf));
-                        if (st.acmod < 2) { err = 1; break; }
-                        if (st.acmod == 2) st.set_phsflginu(rd.get(1));
+                        if (acm < 2) { err = 1; break; }
+                        if (acm == 2) st.set_phsflginu(rd.get(1));
                         const int begf = rd.get(4), endf = rd.get(4);
                         if (endf + 3 - begf < 0) { err = 1; break; }
                         const int nsub = endf + 3 - begf;
@@ -282,11 +289,11 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                                 }
                             } else if (blk == 0) reuse0 = true;
                         }
-                    if (st.acmod == 2 && st.phsflginu() && any)
+                    if (acm == 2 && st.phsflginu() && any)
                         for (int j = 0, nb = st.ncplbnd(); j < nb; j++)
                             if (rd.get(1) && lane == 0) L.cplco[1][j] = -L.cplco[1][j];
                 }
-                if (st.acmod == 2) {
+                if (acm == 2) {
                     if (rd.get(1)) {                                        // rematstr
                         const int end = st.chincpl ? st.cplstrtmant : 253;
                         int i = 0;
@@ -301,10 +308,10 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                     const uint32_t r = __builtin_bitreverse32(rd.get(2 * nf)) >> (32 - 2 * nf);       // channel order right, each code's bits swapped
                     chexp = (int)(((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u));
                 }
-                if (st.lfeon) lfeexpstr = rd.get(1);
+                if (lfeon) lfeexpstr = rd.get(1);
                 if (blk == 0) {
                     if (st.chincpl && !cplexpstr) reuse0 = true;
-                    if (st.lfeon && !lfeexpstr) reuse0 = true;
+                    if (lfeon && !lfeexpstr) reuse0 = true;
                     for (int i = 0; i < nf; i++) if (!((chexp >> (2 * i)) & 3)) reuse0 = true;
                 }
 #pragma unroll
@@ -362,7 +369,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                     if (st.chincpl) st.set_cbai(6, rd.get(7));
 #pragma unroll
                     for (int i = 0; i < 5; i++) if (i < nf) st.set_cbai(i, rd.get(7));
-                    if (st.lfeon) st.set_cbai(5, rd.get(7));
+                    if (lfeon) st.set_cbai(5, rd.get(7));
                 } else if (blk == 0) reuse0 = true;
                 if (st.chincpl) {
                     if (rd.get(1)) {
@@ -403,7 +410,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
 
                 // ---- bit allocation: parse.c:774-798 ----
                 if (redo) {
-                    bool allzero = !st.csnroffst() && !(st.chincpl && (st.cbai(6) >> 3)) && !(st.lfeon && (st.cbai(5) >> 3));
+                    bool allzero = !st.csnroffst() && !(st.chincpl && (st.cbai(6) >> 3)) && !(lfeon && (st.cbai(5) >> 3));
 #pragma unroll
                     for (int i = 0; i < 5; i++)
                         if (i < nf && (st.cbai(i) >> 3)) allzero = false;
@@ -415,7 +422,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                         // the channel slots that need a new allocation, two per sweep of the band PSDs (wave-uniform; written
                         // out rather than as lambdas over `st`: a closure that holds its address keeps the whole state in scratch)
 #define AC3MI_SLOT_END(slot) st.endm(slot)
-                        int todo = redo & (((1 << nf) - 1) | (st.lfeon ? 32 : 0) | (st.chincpl ? 64 : 0));
+                        int todo = redo & (((1 << nf) - 1) | (lfeon ? 32 : 0) | (st.chincpl ? 64 : 0));
 #pragma unroll
                         for (int i = 0; i < 5; i++) if (st.endm(i) <= 0) todo &= ~(1 << i);
                         if (st.cplendmant() <= st.cplstrtmant) todo &= ~64;
@@ -463,7 +470,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
             } while (0);
 
             // optional stage taps
-            if (P.tap_exp) {
+            if (!FX && P.tap_exp) {
                 uint8_t *te = P.tap_exp + (fidx * 6 + blk) * 7 * 256;
                 int8_t *tb = P.tap_bap + (fidx * 6 + blk) * 7 * 256;
                 for (int c = 0; c < 7; c++)
@@ -477,7 +484,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
             if (!err) {
                 DK_LAP(3);
                 // ---- gains: parse.c:810-811 ----
-                a52_downmix_coeff_hd(gain, st.acmod, st.output, st.dynrng, st.clev, st.slev);
+                a52_downmix_coeff_hd(gain, acm, st.output, st.dynrng, st.clev, st.slev);
 
                 // ---- mantissas: the segments of the block in bitstream order (mant_block, decode_common.h) ----
                 if (!PARSE && st.chincpl && lane < 18) {                    // sub-band -> band (parse.c:448-456)
@@ -489,7 +496,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                 sb.r3 = sb.r5 = sb.r11 = sb.draw = 0;
                 if constexpr (!PARSE) {
                     MantBlk B;
-                    B.nf = nf; B.lfeon = st.lfeon; B.acmod = st.acmod; B.in_lfe = in_lfe;
+                    B.nf = nf; B.lfeon = lfeon; B.acmod = acm; B.in_lfe = in_lfe;
                     B.chincpl = st.chincpl; B.dithmask = dithmask; B.rematflg = st.rematflg();
                     B.cplstrtmant = st.cplstrtmant; B.cplendmant = st.cplendmant();
 #pragma unroll
@@ -509,7 +516,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                     // Lane k takes segment k (the scalar unit is this kernel's bottleneck: a loop over the segments on
                     // wave-uniform values costs 600 scalar instructions per block, this form about 80 vector ones).
                     const int cplfirst = st.chincpl ? __builtin_ctz(st.chincpl) : 99;
-                    const int nseg = nf + (st.chincpl ? 1 : 0) + (st.lfeon ? 1 : 0);
+                    const int nseg = nf + (st.chincpl ? 1 : 0) + (lfeon ? 1 : 0);
                     const int ncpl_dith = __popc(st.chincpl & dithmask);
                     const int k = lane;
                     const int slot_l = st.chincpl ? (k <= cplfirst ? k : k == cplfirst + 1 ? 6 : k - 1 < nf ? k - 1 : 5) : (k < nf ? k : 5);
@@ -543,7 +550,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                     }
                     {
                         uint8_t *rowset = P.rows + (fidx * 6 + blk) * (size_t)ROWSET;
-                        const int used = ((1 << nf) - 1) | (st.lfeon ? 32 : 0) | (st.chincpl ? 64 : 0);
+                        const int used = ((1 << nf) - 1) | (lfeon ? 32 : 0) | (st.chincpl ? 64 : 0);
                         const int we = dirty_exp & used, wb = dirty_bap & used;
                         for (int m = we; m; m &= m - 1) {
                             const int s0 = __builtin_ctz(m);
@@ -601,10 +608,10 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
             }
             {
                 if (err && !PARSE)
-                    for (int c = 0; c < P.n_in; c++)
+                    for (int c = 0; c < n_in; c++)
                         *reinterpret_cast<float4 *>(cblk + (size_t)c * 256 + 4 * lane) = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (P.blksw && lane < P.nfchans)
-                    P.blksw[(fidx * 6 + blk) * P.nfchans + lane] = (uint8_t)(err ? 0 : ((blkswm >> lane) & 1));
+                if (P.blksw && lane < nfchans)
+                    P.blksw[(fidx * 6 + blk) * nfchans + lane] = (uint8_t)(err ? 0 : ((blkswm >> lane) & 1));
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -618,7 +625,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
             if (!(status & 0x100u) || (cv & 0x40u)) status |= (cv & 3u) << 10;
         }
         if (lane == 0) P.status[fidx] = status | (reuse0 ? 0x200u : 0u);
-        if (lane == 0 && P.zs) P.zs[fidx] = (uint8_t)((status & 0x100u) ? 0 : surround_level_is_zero(st.acmod, st.output, st.slev));
+        if (lane == 0 && P.zs) P.zs[fidx] = (uint8_t)((status & 0x100u) ? 0 : surround_level_is_zero(acm, st.output, st.slev));
         if (MODE == 5 && lane == 0) P.frame_draws[fidx] = frame_draws;
         if (MODE == 4) {
             if (lane == 0) P.frame_pos[fidx] = pos_live ? lfsr_pos : 0xffffffffu;
@@ -758,7 +765,7 @@ extern "C" __attribute__((visibility("default"))) int ac3mi_debug_dec_cycles(uns
 namespace ac3mi {
 #endif
 
-hipError_t launch_mantx(const DeviceTables &tab, const DecodeLaunch &L, const MantParams &M, hipStream_t stream);       // decode_mx.hip
+hipError_t launch_mantx(const DeviceTables &tab, const DecodeLaunch &L, const MantParams &M, bool fixed51, hipStream_t stream);       // decode_mx.hip
 
 hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStream_t stream)
 {
@@ -806,7 +813,12 @@ hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStre
         P.rows = L.ws_rows;
         P.cplco = L.ws_cplco;
         P.frame_pos = L.ws_fpos;
-        if (!L.frame_parallel) hipLaunchKernelGGL(decode_kernel<4>, dim3(L.n_streams), dim3(64), fr_bytes, stream, P);
+        // the fixed-shape rule (ac3mi_set_fixed_shape): one-frame 5.1 streams whose six planes are the output's (the fused
+        // kernel's calls), no stage taps - parse and mantissa kernel with that shape compiled in.  Same results either way
+        const bool fx = L.fixed_shape && L.fuse && L.frames_per_stream == 1 && !L.tap_exp && !L.tap_bap &&
+                        fixed51_shape(L.acmod, L.lfeon, P.n_in, L.fuse->plan.n_out, P.nfchans);
+        if (!L.frame_parallel && fx) hipLaunchKernelGGL((decode_kernel<4, true>), dim3(L.n_streams), dim3(64), fr_bytes, stream, P);
+        else if (!L.frame_parallel) hipLaunchKernelGGL(decode_kernel<4>, dim3(L.n_streams), dim3(64), fr_bytes, stream, P);
         else {
             hipLaunchKernelGGL(decode_kernel<5>, dim3(units), dim3(64), fr_bytes, stream, P);
             hipLaunchKernelGGL(lfsr_prefix_kernel, dim3((L.n_streams + 63) / 64), dim3(64), 0, stream, (const uint32_t *)L.frame_draws,
@@ -829,7 +841,7 @@ hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStre
         M.n_in = P.n_in;
         M.nfchans = P.nfchans;
         static const int mant_pad = getenv("AC3MI_MANT_LDS_PAD") ? atoi(getenv("AC3MI_MANT_LDS_PAD")) : 0;      // profiling aid: occupancy proxy of a fused mantissa + transform workgroup
-        if (L.fuse) return launch_mantx(tab, L, M, stream);         // one-frame streams, no downmix: the transform in the same kernel
+        if (L.fuse) return launch_mantx(tab, L, M, fx, stream);         // one-frame streams, no downmix: the transform in the same kernel
         hipLaunchKernelGGL(mant_kernel, dim3(units), dim3(384), (size_t)(((L.frame_bytes + 3) >> 2) + 6) * 4 + mant_pad, stream, M);
         return hipGetLastError();
     }

@@ -64,10 +64,13 @@ __device__ unsigned long long g_mx_cycles[6][8];
 #define MX_T0() do { } while (0)
 #define MX_LAP(id) do { } while (0)
 #endif
-template <bool S16>
+// FX (launch_decode's fixed-shape rule): 5.1 - six planes, five full-bandwidth channels, acmod 7 (no rematrixing) with the
+// LFE, as constants instead of P's members; the WAVE slot of a plane comes out of one packed word instead of a chain of selects.
+template <bool S16, bool FX = false>
 __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams Q)
 {
     const MantParams &P = Q.m;
+    const int n_in = FX ? 6 : P.n_in, nfchans = FX ? 5 : P.nfchans;
     __shared__ MantxLDS L;
     extern __shared__ uint32_t frw[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -108,7 +111,7 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
     const uint32_t flags = rfl(w0v.z);
     const bool failed = (flags & 1u) != 0u;
     MantBlk B;
-    B.nf = P.nfchans; B.lfeon = P.lfeon; B.acmod = P.acmod; B.in_lfe = P.lfeon ? 1 : 0;
+    B.nf = nfchans; B.lfeon = FX ? 1 : P.lfeon; B.acmod = FX ? 7 : P.acmod; B.in_lfe = FX ? 1 : P.lfeon ? 1 : 0;
     B.chincpl = (int)((flags >> 8) & 31u); B.dithmask = (int)((flags >> 16) & 31u); B.rematflg = (int)((flags >> 24) & 15u);
     const uint64_t rve = (uint64_t)rfl(w2v.x) | ((uint64_t)rfl(w2v.y) << 32), rvb = (uint64_t)rfl(w2v.z) | ((uint64_t)rfl(w2v.w) << 32);
     const uint8_t *rowbase = P.rows + (size_t)fidx * 6 * ROWSET;
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
 
     // ---- mantissas -> planes in LDS (a failed block leaves zero planes) ----
     if (failed) {
-        for (int c = 0; c < P.n_in; c++)
+        for (int c = 0; c < n_in; c++)
             *reinterpret_cast<float4 *>(planes + c * MX_PLANE + 4 * lane) = make_float4(0.f, 0.f, 0.f, 0.f);
     } else {
         {
@@ -155,10 +158,10 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
     MX_LAP(1);
     // ---- transform: 8-lane group g takes plane g (left-over groups shadow plane 0 and store nothing) ----
     const int l8 = lane & 7, grp = lane >> 3;
-    const bool own = grp < P.n_in;
+    const bool own = grp < n_in;
     const int o = own ? grp : 0;
     const int fb = o - B.in_lfe;
-    const bool sw = fb >= 0 && Q.blksw[unit * P.nfchans + fb] != 0;
+    const bool sw = fb >= 0 && Q.blksw[unit * nfchans + fb] != 0;
     const size_t sidx = Q.slot ? (size_t)Q.slot[fidx] : (size_t)fidx;      // one frame per stream: stream = frame
     float *const dptr = Q.delay + sidx * Q.delay_stride + (size_t)o * 128;
     float2 dl[8];
@@ -246,9 +249,16 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
     // ---- window + overlap-add + bias (xform.hip's output stage) ----
     int16_t *tile = reinterpret_cast<int16_t *>(region + MX_TILE);
     int wsl = 0;
+    if constexpr (FX) {
+        uint64_t w = 0;
 #pragma unroll
-    for (int oo = 0; oo < 6; oo++) wsl = oo == o ? Q.wslot[oo] : wsl;
-    float *oblk = S16 ? nullptr : Q.pcm + (unit * P.n_in + o) * 256;
+        for (int oo = 0; oo < 6; oo++) w |= (uint64_t)(uint8_t)Q.wslot[oo] << (8 * oo);
+        wsl = (int)((uint32_t)(w >> (8 * o)) & 0xffu);
+    } else {
+#pragma unroll
+        for (int oo = 0; oo < 6; oo++) wsl = oo == o ? Q.wslot[oo] : wsl;
+    }
+    float *oblk = S16 ? nullptr : Q.pcm + (unit * n_in + o) * 256;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         const int i = ((j & 1) ? 15 - l8 : l8) + 16 * (j >> 1);
@@ -261,19 +271,19 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
             *reinterpret_cast<float2 *>(oblk + 254 - 2 * i) = hi;
         }
         if (S16 && own) {                                           // (24-bit multiplies: v_mul_lo_u32 runs at a quarter of the rate)
-            const int at = wsl + (int)__umul24((uint32_t)(2 * i), (uint32_t)P.n_in), top = wsl + (int)__umul24(254u, (uint32_t)P.n_in) - (at - wsl);
+            const int at = wsl + (int)__umul24((uint32_t)(2 * i), (uint32_t)n_in), top = wsl + (int)__umul24(254u, (uint32_t)n_in) - (at - wsl);
             tile[at] = to_s16(lo.x);
-            tile[at + P.n_in] = to_s16(lo.y);
+            tile[at + n_in] = to_s16(lo.y);
             tile[top] = to_s16(hi.x);
-            tile[top + P.n_in] = to_s16(hi.y);
+            tile[top + n_in] = to_s16(hi.y);
         }
     }
     if (S16) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int upb = 32 * P.n_in;                                // 16-byte units of the block
-        int16_t *dst = Q.pcm16 + unit * 256 * P.n_in;
+        const int upb = 32 * n_in;                                // 16-byte units of the block
+        int16_t *dst = Q.pcm16 + unit * 256 * n_in;
 #pragma unroll
         for (int it = 0; it < 3; it++) {
             const int u = it * 64 + lane;
@@ -284,7 +294,7 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
 }
 
 // mant_kernel + xform_kernel in one launch (launch_decode calls this when DecodeLaunch::fuse is set)
-hipError_t launch_mantx(const DeviceTables &tab, const DecodeLaunch &L, const MantParams &M, hipStream_t stream)
+hipError_t launch_mantx(const DeviceTables &tab, const DecodeLaunch &L, const MantParams &M, bool fixed51, hipStream_t stream)
 {
     const XformLaunch &X = *L.fuse;
     if (L.frames_per_stream != 1 || X.plan.n_in != X.plan.n_out || M.n_in > 6) return hipErrorInvalidValue;
@@ -308,7 +318,9 @@ hipError_t launch_mantx(const DeviceTables &tab, const DecodeLaunch &L, const Ma
         int map[6];
         if (s16_channel_map(X.s16_flags, map) != X.plan.n_out || ((uintptr_t)X.pcm16 & 15)) return hipErrorInvalidValue;
         for (int w = 0; w < X.plan.n_out; w++) Q.wslot[map[w]] = (int8_t)w;
-        hipLaunchKernelGGL(mantx_kernel<true>, dim3(M.n_frames), dim3(384), dyn, stream, Q);
+        // (fixed51: launch_decode's fixed-shape rule held for this call)
+        if (fixed51) hipLaunchKernelGGL((mantx_kernel<true, true>), dim3(M.n_frames), dim3(384), dyn, stream, Q);
+        else hipLaunchKernelGGL(mantx_kernel<true>, dim3(M.n_frames), dim3(384), dyn, stream, Q);
     } else {
         hipLaunchKernelGGL(mantx_kernel<false>, dim3(M.n_frames), dim3(384), dyn, stream, Q);
     }

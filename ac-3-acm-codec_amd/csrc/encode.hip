@@ -455,12 +455,13 @@ struct ExpLDS {
 // the rest is recomputed for the P.nbc = cplstrtmant bins the channel codes.
 // XS (ac3mi_set_encode_exp_strategy 1): the strategies are xs_choose's over the coded bins [0, n); 1: a set also sends
 // gainrng and chbwcod (enc_mdct_kernel), 2: gainrng only (a coupled channel, enc_cpl_kernel).
-template <bool KEEP = false, int XS = 0>
+// FX (enc_mdct_kernel's fixed 5.1 shape): six channels, the last the LFE, 223 coefficients - constants instead of P's.
+template <bool KEEP = false, int XS = 0, bool FX = false>
 __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, int lane)
 {
-    const int nch = P.nch;
-    const bool is_lfe = P.lfe && ch == nch - 1;
-    const int n = is_lfe ? 7 : P.nbc;
+    const int nch = FX ? 6 : P.nch;
+    const bool is_lfe = (FX || P.lfe) && ch == nch - 1;
+    const int n = is_lfe ? 7 : FX ? 223 : P.nbc;
     uint32_t raw[6];
 #pragma unroll
     for (int b = 0; b < 6; b++) raw[b] = *reinterpret_cast<const uint32_t *>(&L.E[b][4 * lane]);
@@ -697,7 +698,9 @@ __device__ __forceinline__ void bfly(c16 &p, c16 &q, int bx, int by, int ax, int
 // LFEROW (2/0+LFE with rematrixing, never with BSW or REMAT): the plain kernel restricted to the LFE row, one wavefront per
 // frame (unit = frame, channel nch - 1), launched beside the two-wavefront REMAT workgroups, which code channels 0 and 1.
 // The LFE never switches: with block switching on it leaves its row's decision 0.
-template <bool BSW, bool REMAT, bool BW = false, bool XS = false, bool LFEROW = false>
+// FX (the plain kernel only; launch_encode's fixed-shape rule): one-frame 5.1 streams - six channels, the last the LFE, one
+// frame, 223 coefficients, the history stored here and no tap, as constants: no division by nch or frames, strides of 6.
+template <bool BSW, bool REMAT, bool BW = false, bool XS = false, bool LFEROW = false, bool FX = false>
 __global__ __launch_bounds__(REMAT ? 128 : 64, REMAT ? (BSW ? ENC_MDCT_BSW_REMAT_LB : ENC_MDCT_REMAT_LB) : BSW ? ENC_MDCT_BSW_LB : ENC_MDCT_LB)
 void enc_mdct_kernel(const MdctParams P)
 {
@@ -720,10 +723,12 @@ void enc_mdct_kernel(const MdctParams P)
         unit = __builtin_amdgcn_readfirstlane(unit);        // (wave-uniform by construction: row and state addresses on the scalar unit)
     }
     static_assert(!(LFEROW && (BSW || REMAT)), "the LFE row alone takes the plain kernel");
-    const int ch = REMAT ? wave : LFEROW ? P.nch - 1 : unit % P.nch;
-    const int sf = REMAT || LFEROW ? unit : unit / P.nch;
-    const int f = sf % P.frames;
-    const int s = sf / P.frames;
+    static_assert(!(FX && (BSW || REMAT || BW || XS || LFEROW)), "the fixed 5.1 shape is the plain kernel's");
+    const int nch = FX ? 6 : P.nch, frames = FX ? 1 : P.frames, nbc = FX ? 223 : P.x.nbc;
+    const int ch = REMAT ? wave : LFEROW ? nch - 1 : unit % nch;
+    const int sf = REMAT || LFEROW ? unit : unit / nch;
+    const int f = sf % frames;
+    const int s = sf / frames;
 
     // Which samples a lane owns.  Point i of the pre-rotation (:578-591) takes four samples of the 512 windowed ones:
     //   i < 64 :  re <- -in[384 + 2i], in[383 - 2i]     im <- in[128 + 2i], in[127 - 2i]
@@ -759,20 +764,20 @@ void enc_mdct_kernel(const MdctParams P)
     // the short pair: lane = 32 tsh + ls holds points Ls = bitrev5(ls) and Ls + 32 of transform tsh before the passes, ls and
     // ls + 32 after them (rotation factors read per switched block, from L1: held across the loop they spill)
     const int ls = lane & 31, Ls = (int)(__builtin_bitreverse32((unsigned)ls) >> 27), tsh = lane >> 5;
-    const bool lfe_ch = P.x.lfe && ch == P.nch - 1;
+    const bool lfe = FX ? true : P.x.lfe != 0, lfe_ch = lfe && ch == nch - 1;
 
-    const int16_t *frame_pcm = P.pcm + ((size_t)s * P.frames + f) * 1536 * P.nch + P.chmap[ch];
+    const int16_t *frame_pcm = P.pcm + ((size_t)s * frames + f) * 1536 * nch + P.chmap[ch];
     // the lane's four samples of: the block before (history), this block, and - in flight while this block is
     // transformed - the next one.  Every sample is read from HBM once.
     int16_t oldv[4], newv[4], nxtv[4];
     int joff[4];                                    // the lane's positions as sample offsets (32-bit index arithmetic)
 #pragma unroll
-    for (int k = 0; k < 4; k++) joff[k] = __mul24(jpos[k], P.nch);
+    for (int k = 0; k < 4; k++) joff[k] = __mul24(jpos[k], nch);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int j = jpos[k];
-        if (f > 0) oldv[k] = frame_pcm[joff[k] - 256 * P.nch];                   // block 5 of the previous frame
-        else oldv[k] = P.slot ? P.last[((size_t)P.slot[s] * 6 + ch) * 256 + j] : P.last[((size_t)s * P.nch + ch) * 256 + j];
+        if (f > 0) oldv[k] = frame_pcm[joff[k] - 256 * nch];                   // block 5 of the previous frame
+        else oldv[k] = P.slot ? P.last[((size_t)P.slot[s] * 6 + ch) * 256 + j] : P.last[((size_t)s * nch + ch) * 256 + j];
         newv[k] = frame_pcm[joff[k]];
     }
     int rprev = 0;                                  // REMAT: the flags of the block before
@@ -812,10 +817,10 @@ void enc_mdct_kernel(const MdctParams P)
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int j = jpos[k];
-            nxtv[k] = blk < 5 ? frame_pcm[(blk + 1) * 256 * P.nch + joff[k]] : (int16_t)0;
-            if (P.store_history && blk == 5) {
+            nxtv[k] = blk < 5 ? frame_pcm[(blk + 1) * 256 * nch + joff[k]] : (int16_t)0;
+            if ((FX || P.store_history) && blk == 5) {
                 if (P.slot) P.last[((size_t)P.slot[s] * 6 + ch) * 256 + j] = newv[k];
-                else P.last[((size_t)s * P.nch + ch) * 256 + j] = newv[k];
+                else P.last[((size_t)s * nch + ch) * 256 + j] = newv[k];
             }
             // (a 16-bit sample times a window value in 0 .. 32767, >> 15, is a 16-bit value again: no truncation to restate)
             win_[k] = __mul24(oldv[k], wa[k]) >> 15;
@@ -959,7 +964,7 @@ void enc_mdct_kernel(const MdctParams P)
         }
         WAVE_SYNC();
         // ---- exponents (:1707-1722) ----
-        const size_t row = (((size_t)s * P.frames + f) * 6 + blk) * P.nch + ch;
+        const size_t row = (((size_t)s * frames + f) * 6 + blk) * nch + ch;
         int4 cv = *reinterpret_cast<const int4 *>(&out[4 * lane]);
         int cc[4] = {cv.x, cv.y, cv.z, cv.w};
         if constexpr (REMAT) {
@@ -972,7 +977,7 @@ void enc_mdct_kernel(const MdctParams P)
             const int r0 = rv_[par][0], r1 = rv_[par][1];
             const int vl = r0 & 0xff, vr = r1 & 0xff, vm = min(vl, vr), dl = vl - vm, dr = vr - vm;
             const int32_t *rl = out_[2 * par], *rr = out_[2 * par + 1];
-            const int jend = BW ? P.x.nbc : 223;                    // the fourth band's end
+            const int jend = BW ? nbc : 223;                    // the fourth band's end
             uint64_t el = 0, er = 0, em = 0, es = 0;
             if (lane < 53) {
 #pragma unroll
@@ -1045,9 +1050,9 @@ void enc_mdct_kernel(const MdctParams P)
         // (the packers read a row's coded bins only: nbc of a full-bandwidth channel, 7 of the LFE - a quarter of the store traffic.
         //  Every reader of a row masks what lies beyond: the search and the packers give bins >= nbc exponent 255 (bap 0, no bits),
         //  enc_cpl_kernel reads [cplstrtmant, cplendmant) and, for a coupled channel's exponents, bins below cplstrtmant only)
-        if (P.full_rows || 4 * lane < ((P.x.lfe && ch == P.nch - 1) ? 7 : P.x.nbc))
+        if ((!FX && P.full_rows) || 4 * lane < (lfe_ch ? 7 : nbc))
             *reinterpret_cast<int4 *>(P.mdct + row * 256 + 4 * lane) = make_int4(cc[0], cc[1], cc[2], cc[3]);
-        if (P.expo) *reinterpret_cast<uint32_t *>(P.expo + row * 256 + 4 * lane) = epack;       // tap only
+        if (!FX && P.expo) *reinterpret_cast<uint32_t *>(P.expo + row * 256 + 4 * lane) = epack;       // tap only
         *reinterpret_cast<uint32_t *>(&XL.E[blk][4 * lane]) = epack;
         if (lane == 0) P.shift[row] = (int8_t)shift;
         if constexpr (BSW) if (lane == 0) P.bsw[row] = sw ? 1 : 0;
@@ -1057,7 +1062,7 @@ void enc_mdct_kernel(const MdctParams P)
         for (int k = 0; k < 4; k++) newv[k] = nxtv[k];
         WAVE_SYNC();
     }
-    exp_stage<false, XS ? 1 : 0>(P.x, XL, (size_t)sf, ch, lane);
+    exp_stage<false, XS ? 1 : 0, FX>(P.x, XL, (size_t)sf, ch, lane);
 }
 
 
@@ -1611,16 +1616,19 @@ __device__ unsigned long long g_pack_cycles[16];
 // CPL (enc_search_cpl_kernel: channel coupling on, P.cpl): the coupling rows join the costed rows of a coupled frame.
 // BW (with CPL; ac3mi_set_encode_bandwidth 1 or 2): a coupled frame ends at cplendmant = 73 + 12 P.cpl_endf, not 217.
 // DRC (ac3mi_set_encode_drc 1..5): every block that sends a dynrng word (P.drc) costs its 8 bits.
-template <int PART, bool CPL = false, bool BW = false, bool DRC = false>
+// FX (PART 1 with none of the above; launch_encode's fixed-shape rule): one-frame 5.1 streams - six channels, five of them
+// full-bandwidth, acmod 7, 223 coefficients, a single frame and neither taps nor a verdict table, as constants instead of P's members.
+template <int PART, bool CPL = false, bool BW = false, bool DRC = false, bool FX = false>
 __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const PackParams P)
 {
     static_assert(PART == 1 || PART == 3, "the packers are enc_packf_kernel / enc_packb_kernel");
+    static_assert(!FX || (PART == 1 && !CPL && !BW && !DRC), "the fixed 5.1 shape is the plain per-stream search's");
     __shared__ SearchLDS<CPL> L;
     const int lane = threadIdx.x;
     constexpr bool PER_FRAME = PART == 3;
     const int s = PER_FRAME ? (int)(blockIdx.x / (unsigned)P.frames_per_stream) : (int)blockIdx.x;
     const int f_first = PER_FRAME ? (int)(blockIdx.x - (unsigned)s * (unsigned)P.frames_per_stream) : 0;
-    const int f_end = PER_FRAME ? f_first + 1 : P.frames_per_stream;
+    const int f_end = PER_FRAME ? f_first + 1 : FX ? 1 : P.frames_per_stream;
     if (s >= P.n_streams) return;
 
     for (int i = lane; i < 256; i += 64) L.band_of_bin[i] = P.tab->band_of_bin[i];
@@ -1629,7 +1637,9 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
         L.bitlut[lane] = (uint32_t)plain_bits(bp) | ((bp == 1) << 9) | ((bp == 2) << 14) | ((bp == 4) << 19);
     }
 
-    const int nch = P.nch, nfbw = P.nfbw, nbc = P.nbc;
+    const int nch = FX ? 6 : P.nch, nfbw = FX ? 5 : P.nfbw, nbc = FX ? 223 : P.nbc;
+    const int acmod = FX ? 7 : P.acmod;
+    const bool lfe = FX ? true : P.lfe != 0;
     const int fs = P.frame_words;
 
     const int sslot = P.slot ? P.slot[s] : s;
@@ -1642,7 +1652,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
     PK_DECL();
 
     for (int f = f_first; f < f_end; f++) {
-        const size_t fidx = (size_t)s * P.frames_per_stream + f;
+        const size_t fidx = FX ? (size_t)s : (size_t)s * P.frames_per_stream + f;
         PK_T0();
         PK_COUNT(5);
         const uint8_t *ex = P.eexp + fidx * 6 * nch * 256;
@@ -1686,7 +1696,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                     const uint32_t later = (uint32_t)((run_starts >> (8 * c6)) & 0x3f) | 0x40u;       // bit b: block b of this channel sends exponents
                     const int b1 = __builtin_ctz(later >> (b6 + 1)) + b6 + 1;
                     const uint32_t cover = ((1u << b1) - 1u) & ~((1u << b6) - 1u);
-                    uint32_t d = (uint32_t)((b6 * nch + c6) * 256) | ((P.lfe && c6 == nch - 1) ? 1u << 14 : 0u) | (cover << 16) | ((uint32_t)(b6 * nch + c6) << 24);
+                    uint32_t d = (uint32_t)((b6 * nch + c6) * 256) | ((lfe && c6 == nch - 1) ? 1u << 14 : 0u) | (cover << 16) | ((uint32_t)(b6 * nch + c6) << 24);
                     if constexpr (CPL) d |= cplf && c6 < nfbw ? 1u << 22 : 0u;
                     L.rowdesc[__builtin_popcountll(row_set & ((1ull << lane) - 1ull))] = d;
                 }
@@ -1695,8 +1705,8 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
             {
                 // (dual mono: dialnorm2, compr2e, langcod2e, audprodi2e in the BSI; dynrng2e in every block)
                 const int extra[8] = {8, 0, 2, 2, 2, 4, 2, 4};
-                frame_bits += 65 + extra[P.acmod & 7];
-                frame_bits += 6 * (nfbw * 2 + 2 + (P.acmod == 2 ? 1 : 0) + (P.acmod == 0 ? 1 : 0) + 2 * nfbw + (P.lfe ? 1 : 0) + 1 + 1 + 2);
+                frame_bits += 65 + extra[acmod & 7];
+                frame_bits += 6 * (nfbw * 2 + 2 + (acmod == 2 ? 1 : 0) + (acmod == 0 ? 1 : 0) + 2 * nfbw + (lfe ? 1 : 0) + 1 + 1 + 2);
                 // chbwcod (6 bits) and gainrng (2 bits) of every full-bandwidth channel-block that sends exponents
                 uint64_t fbw_rows = 0;
                 for (int b = 0; b < 6; b++) fbw_rows |= ((1ull << nfbw) - 1) << (6 * b);
@@ -1707,17 +1717,17 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                 frame_bits += 16;
                 if constexpr (DRC) {
                     const uint8_t *code = P.drc + fidx * 6;
-                    for (int b = 0; b < 6; b++) frame_bits += drc_sends(code, b) ? (P.acmod == 0 ? 16 : 8) : 0;     // (dual mono: dynrng2 too)
+                    for (int b = 0; b < 6; b++) frame_bits += drc_sends(code, b) ? (acmod == 0 ? 16 : 8) : 0;     // (dual mono: dynrng2 too)
                 }
                 // rematrixing: the four flags of every block 1..5 that sends them (block 0's stay uncounted, as above)
-                if (P.remat)
+                if (!FX && P.remat)
                     for (int b = 1; b < 6; b++) frame_bits += (P.remat[fidx * 6 + b] & 0x10) ? 4 : 0;
                 if (CPL && cplf) {
                     // coupling: chincpl, phsflginu (2/0), cplbegf / cplendf, cplbndstrc; cplcoe, mstrcplco and the coordinates
                     // in block 0, cplcoe 0 in blocks 1..5; cplexpstr; cplfsnroffst / cplfgaincod; cplleake (+ the two leaks in
                     // block 0); the coupling exponents; no chbwcod for the coupled channels
                     const int nb = cpl_nb;
-                    frame_bits += nfbw + (P.acmod == 2 ? 1 : 0) + 8 + (nb - 1) + nfbw * (3 + 8 * nb) + 5 * nfbw + 6 * 2 + 7 + 7 + 5;
+                    frame_bits += nfbw + (acmod == 2 ? 1 : 0) + 8 + (nb - 1) + nfbw * (3 + 8 * nb) + 5 * nfbw + 6 * 2 + 7 + 7 + 5;
                     frame_bits += __builtin_amdgcn_readfirstlane(P.cpl.ebits[fidx]) - 6 * __builtin_popcountll(row_set & fbw_rows);
                     if (P.remat) {                  // a coupled frame's blocks 1..5 send liba52's cplinu-1 flag count, not 4
                         const int nrem = P.cpl_begf == 0 ? 2 : P.cpl_begf <= 2 ? 3 : 4;
@@ -1742,7 +1752,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
             }
         };
         // PART 1 replays the search from tabulated verdicts and needs the frame's data only for a verdict that is missing
-        if (PART != 1 || P.tap_strat) load_frame();
+        if (PART != 1 || (!FX && P.tap_strat)) load_frame();
 
         // ---- SNR offset search, exactly the reference's sequence (:921-967).  Up to three candidates are
         //      evaluated per sweep over the coefficients, chosen by running the reference's loop ahead on
@@ -1755,7 +1765,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
         uint64_t known_c = 0, fits_c = 0;
         uint32_t known_f = 0, fits_f = 0;
         int f_cc = -1;
-        if (PART == 1 && P.memo) {                                  // tabulated by PART 3
+        if (PART == 1 && !FX && P.memo) {                                  // tabulated by PART 3
             const uint32_t *m = P.memo + fidx * 8;
             auto word = [&](int i) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)m[i]); };    // (the builtin returns int)
             known_c = (uint64_t)word(0) | ((uint64_t)word(1) << 32);
@@ -2087,8 +2097,8 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                 fsnr = fsnr_prev;
             }
         }
-        if (P.tap_snr && lane == 0) { P.tap_snr[fidx * 2] = csnr; P.tap_snr[fidx * 2 + 1] = fsnr; }
-        if (P.tap_strat && lane < 36) {
+        if (!FX && P.tap_snr && lane == 0) { P.tap_snr[fidx * 2] = csnr; P.tap_snr[fidx * 2 + 1] = fsnr; }
+        if (!FX && P.tap_strat && lane < 36) {
             const int b = lane / 6, ch = lane - 6 * b;
             if (ch < nch) P.tap_strat[(fidx * 6 + b) * nch + ch] = L.strat[b][ch];
         }
@@ -3010,6 +3020,11 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     M.bsw = E.ws_bsw;
     M.remat = c.acmod == 2 ? E.ws_remat : nullptr;      // (rematrixing is a 2/0 tool, with or without the LFE: other layouts ignore it)
     const dim3 units(E.n_streams * E.frames_per_stream * c.nch), frames(E.n_streams * E.frames_per_stream);
+    // The fixed-shape rule (ac3mi_set_fixed_shape): a 5.1 call takes the kernels that have that shape compiled in
+    // (the FX / FIXED51 instantiations) - the front kernel and the search when, besides, the streams are one frame long, the
+    // bandwidth is the full one and no tool of theirs is on (fx_plain; each adds "no stage tap of mine" below).  Same bytes either way
+    const bool fixed51 = E.fixed_shape && fixed51_shape(c.acmod, c.lfe, c.nch, c.nch, c.nfbw);
+    const bool fx_plain = fixed51 && E.frames_per_stream == 1 && !bw && !E.ws_bsw && !E.ws_remat && E.cpl_begf < 0 && !drc && !E.exp_strategy;
     // (begf > cplendf + 2: no coupling band - no frame couples, the bytes are coupling off's; dual mono's two programmes are
     // never coupled)
     const bool cpl = E.cpl_begf >= 0 && c.nfbw >= 2 && c.acmod != 0 && E.cpl_begf <= cpl_endf + 2;
@@ -3045,6 +3060,7 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     else if (M.remat && M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, true>), frames, dim3(128), 0, stream, M);
     else if (M.remat) hipLaunchKernelGGL((enc_mdct_kernel<false, true>), frames, dim3(128), 0, stream, M);
     else if (M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, false>), units, dim3(64), 0, stream, M);
+    else if (fx_plain && !M.full_rows && !M.expo) hipLaunchKernelGGL((enc_mdct_kernel<false, false, false, false, false, true>), units, dim3(64), 0, stream, M);
     else hipLaunchKernelGGL((enc_mdct_kernel<false, false>), units, dim3(64), 0, stream, M);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -3175,9 +3191,10 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
         }
         if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<1, true, true, DRC>), dim3(E.n_streams), dim3(64), 0, stream, P);
         else if (cpl) hipLaunchKernelGGL((enc_search_kernel<1, true, false, DRC>), dim3(E.n_streams), dim3(64), 0, stream, P);
+        else if (!DRC && fx_plain && !P.memo && !P.tap_strat && !P.tap_snr)
+            hipLaunchKernelGGL((enc_search_kernel<1, false, false, false, true>), dim3(E.n_streams), dim3(64), 0, stream, P);
         else hipLaunchKernelGGL((enc_search_kernel<1, false, false, DRC>), dim3(E.n_streams), dim3(64), 0, stream, P);
     };
-    const bool fixed51 = c.nch == 6 && c.nfbw == 5 && c.lfe && c.acmod == 7;
     auto packers = [&](auto X) {
         constexpr bool MD = decltype(X)::value;
         if (packb) hipLaunchKernelGGL((enc_packb_kernel<MD>), dim3(nfr), dim3(384), fr_lds, stream, P);

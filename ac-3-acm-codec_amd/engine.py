@@ -281,6 +281,11 @@ class Engine:
         in the mantissa kernel for one-frame streams without a downmix (ac3mi_set_decode_mode)."""
         self._check(self.lib.ac3mi_set_decode_mode(ctypes.c_void_p(self.ctx), int(mode)))
 
+    def set_fixed_shape(self, on):
+        """1 (default) = 5.1 calls take the kernels that have that shape compiled in where their stage allows it, 0 = always the
+        generic kernels; the bytes are the same (ac3mi_set_fixed_shape)."""
+        self._check(self.lib.ac3mi_set_fixed_shape(ctypes.c_void_p(self.ctx), int(on)))
+
     def set_decode_crc(self, mode):
         """CRC verification of the frames the decode and transcode calls read (ac3mi_set_decode_crc): 0 = none (liba52),
         1 = report in status bits 10 / 11 (flags.STATUS_CRC1 / STATUS_CRC2), 2 = also decode a failing frame as a refused

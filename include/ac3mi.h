@@ -163,6 +163,13 @@ int ac3mi_set_mix_state(ac3mi_ctx *ctx, float *d_pending, int32_t *d_flags);
 #define AC3MI_STATUS_REUSE0 0x200u
 int ac3mi_set_decode_mode(ac3mi_ctx *ctx, int mode);
 
+/* The fixed-shape kernels (new; applies to every following batch call on `ctx`).  The shape large batches run at - 5.1: acmod
+ * 7 with the LFE, six planes in and out - is compiled into a second instantiation of the parse, mantissa + transform, MDCT,
+ * search and frame-packer kernels, which a call takes when it has that shape and, per kernel, one frame per stream and none
+ * of that stage's tools or taps on; every other call takes the generic kernels.  Outputs and state are byte-identical either
+ * way (tests/test_fixed_shape_gpu.py).  on = 1 (default): that rule; 0: always the generic kernels (A/B runs, tests). */
+int ac3mi_set_fixed_shape(ac3mi_ctx *ctx, int on);
+
 /* CRC verification of the frames ac3mi_decode_batch / ac3mi_decode_s16_batch / ac3mi_transcode_batch read (new; applies to
  * every following such call on `ctx`, under every ac3mi_set_decode_mode, with or without state slots, mix state, taps and
  * tiling).  liba52 never looks at a frame's two CRC words, so a frame damaged in its mantissas parses without a block error,
