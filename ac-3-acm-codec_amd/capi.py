@@ -119,6 +119,8 @@ def load_library():
     lib.ac3mi_bsi_read.argtypes = [c_void_p, c_int, ctypes.POINTER(BsiInfoC)]
     lib.ac3mi_bsi_read_batch.argtypes = [c_void_p, c_void_p, c_int, c_int, c_size_t, c_void_p]
     lib.ac3mi_set_encode_drc.argtypes = [c_void_p, c_int, c_void_p]
+    lib.ac3mi_set_encode_dynrng_frames.argtypes = [c_void_p, c_void_p, c_void_p]
+    lib.ac3mi_set_encode_drc_source.argtypes = [c_void_p, c_int]
     lib.ac3mi_set_encode_exp_strategy.argtypes = [c_void_p, c_int]
     lib.ac3mi_set_encode_layout.argtypes = [c_void_p, c_int, c_int, c_int]
     lib.ac3mi_memcpy_d2d.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t]

@@ -129,6 +129,10 @@ struct DecodeLaunch {
     // ac3mi_set_decode_crc 1 / 2: the CRC kernel's verdict byte per frame, [S][F] (crc.hip); null: the frames are not checked
     const uint8_t *crc = nullptr;
     bool fixed_shape = true;            // ac3mi_set_fixed_shape: a 5.1 call may take the kernels with that shape compiled in (fixed51_shape)
+    // ac3mi_set_encode_drc_source 1 (transcode): [S][F][6] the raw dynamic-range fields of every block the front end reads - bit 8
+    // dynrnge, bits 0-7 dynrng, bit 24 dynrng2e, bits 16-23 dynrng2 (acmod 0) - for enc_dynrng_source_kernel.  Non-null: the SRC
+    // instantiations of the front ends run (generic shape only); a block that is not reached leaves its word unwritten
+    uint32_t *src_dyn = nullptr;
 };
 hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStream_t stream);
 // decode_wg.hip: one workgroup per stream; X == nullptr: coefficient planes (+ taps) to HBM as launch_decode does;
@@ -217,6 +221,23 @@ struct BsiLaunch {
     uint32_t ctx_word = BSI_DEFAULT;
 };
 hipError_t launch_bsi(const BsiLaunch &L, hipStream_t stream);
+
+// bsi.hip, enc_dynrng_source_kernel (ac3mi_set_encode_drc_source 1, after a transcode's front end and ahead of its encoder): one
+// lane per frame resolves the source's words into the arrays of ac3mi_set_encode_dynrng_frames - `codes` [n][6][2] the code in
+// force in every block (0 at the frame's start, a word holds to its end), `compr` [n][2] - from the front end's raw words
+// (DecodeLaunch::src_dyn), the frame's own BSI and its status word: a frame with bit 8 or any of bits 0-5 set carries nothing.
+// prog: -1 both programmes of a dual-mono source (coded as dual mono), else the one programme (0, 1) that becomes programme 0
+struct DynSrcLaunch {
+    const uint8_t *frames;
+    size_t n_frames;
+    int frame_stride, frame_bytes;
+    const uint32_t *src_dyn;
+    const uint32_t *status;
+    uint8_t *codes;
+    uint16_t *compr;
+    int prog = 0;
+};
+hipError_t launch_dynrng_source(const DynSrcLaunch &L, hipStream_t stream);
 void bsi_read_host(const uint8_t *buf, int len, ac3mi_bsi_info *out);
 
 // The shape large batches run at - 5.1: acmod 7 with the LFE, six planes in and out, five full-bandwidth channels.  The one
@@ -267,6 +288,11 @@ struct EncodeLaunch {
     uint8_t *ws_drc_code = nullptr; // [S][F][6] dynrng codes for the search and the packers
     int exp_strategy = 0;       // ac3mi_set_encode_exp_strategy: 1 = strategies by cost (the XS kernel variants), 0 = the reference's rule
     bool fixed_shape = true;    // ac3mi_set_fixed_shape: a 5.1 call may take the kernels with that shape compiled in (fixed51_shape)
+    // ac3mi_set_encode_dynrng_frames / ac3mi_set_encode_drc_source, by the frame's position in the call (never by slot): the dynrng
+    // code in force in every block, [S][F][6][2] (programme 0, 1), and the compr words, [S][F][2] (bit 8 compre, bits 0-7 compr).
+    // Either non-null: the DW variants of the search and the packers run (never with drc_profile and dyn_codes together)
+    const uint8_t *dyn_codes = nullptr;
+    const uint16_t *compr_words = nullptr;
 };
 // carves CPL_FRAME_BYTES * nfr bytes at `base` into the arrays of CplWs (base 16-byte aligned)
 CplWs cpl_slices(void *base, size_t nfr);
@@ -303,6 +329,9 @@ struct EncTools {
     int md_source = 0;                  // ac3mi_set_encode_metadata_source
     int drc_profile = 0;                // ac3mi_set_encode_drc
     int32_t *drc_state = nullptr;
+    const uint8_t *dyn_codes = nullptr;     // ac3mi_set_encode_dynrng_frames
+    const uint16_t *compr_words = nullptr;
+    int drc_source = 0;                 // ac3mi_set_encode_drc_source
     int exp_strategy = 0;               // ac3mi_set_encode_exp_strategy
     int layout_mode = 0, layout_acmod = 0, layout_lfeon = 0;    // ac3mi_set_encode_layout
 };
@@ -332,11 +361,12 @@ struct ac3mi_ctx {
     ac3mi::DevBuf ws_drc;   // DRC gains and codes between the DRC kernels, the search and the packers, 3 bytes a frame-block
     ac3mi::DevBuf ws_crc;   // decode with ac3mi_set_decode_crc on: the CRC kernel's verdicts for the front end, one byte per frame
     ac3mi::DevBuf ws_bsi;   // transcode with ac3mi_set_encode_metadata_source 1: the BSI kernel's word per frame for the packers
+    ac3mi::DevBuf ws_dyn;   // transcode with ac3mi_set_encode_drc_source 1: per frame the front end's raw words (24 bytes), the codes (12) and compr words (4)
     // every workspace above (ac3mi_destroy frees them, ac3mi_workspace_bytes sums them)
     template <class Ctx> static auto workspaces(Ctx *c)
     {
         return std::array{&c->ws_coef, &c->ws_blksw, &c->ws_draws, &c->ws_split, &c->ws_enc, &c->ws_tc,
-                          &c->ws_bsw, &c->ws_remat, &c->ws_cpl, &c->ws_cplr, &c->ws_drc, &c->ws_crc, &c->ws_bsi};
+                          &c->ws_bsw, &c->ws_remat, &c->ws_cpl, &c->ws_cplr, &c->ws_drc, &c->ws_crc, &c->ws_bsi, &c->ws_dyn};
     }
     // optional state-slot indirection for the next batch calls (ac3mi_set_state_slots)
     const int32_t *slots = nullptr;

@@ -173,4 +173,77 @@ hipError_t launch_bsi(const BsiLaunch &L, hipStream_t stream)
     return hipGetLastError();
 }
 
+// ac3mi_set_encode_drc_source 1: the source's dynamic-range words as the encoder's arrays (DynSrcLaunch, ac3mi_internal.h; the
+// rule is include/ac3mi.h's).  One lane per frame, as above and for the same reason: the frame's compr fields come from
+// bsi_parse, the six blocks' raw words from the front end (24 bytes a frame, two 16-byte-aligned loads' worth), and the result
+// is 16 bytes a frame.  Runs after the front end (its status words and raw words) and ahead of the encoder.
+struct DynSrcParams {
+    const uint8_t *frames;
+    const uint32_t *src_dyn, *status;
+    uint8_t *codes;
+    uint16_t *compr;
+    unsigned n_frames;
+    int frame_stride, frame_bytes, prog;
+};
+
+__global__ __launch_bounds__(64) void enc_dynrng_source_kernel(const DynSrcParams P)
+{
+    const unsigned f = blockIdx.x * 64u + threadIdx.x;
+    if (f >= P.n_frames) return;
+    uint32_t code[2][6] = {{0u, 0u, 0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u, 0u, 0u}}, compr[2] = {0u, 0u};
+    // a frame the decoder refused or concealed (bit 8) or one with a failed block (bits 0-5) carries nothing
+    if (!(P.status[f] & 0x13fu)) {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(P.frames + (size_t)f * P.frame_stride);
+        const uint32_t ndw = (uint32_t)(P.frame_bytes + 3) >> 2;
+        const uint32_t h0 = src[0], h1 = src[1], h2 = ndw > 2 ? src[2] : 0u;
+        auto fetch = [=](uint32_t i) {
+            const uint32_t v = i == 0 ? h0 : i == 1 ? h1 : i == 2 ? h2 : i < ndw ? src[i] : 0u;
+            return __builtin_bswap32(v);
+        };
+        ac3mi_bsi_info o;
+        bsi_parse(fetch, P.frame_bytes, P.frame_bytes, o);
+        if (o.verdict == 0) {                           // (always: the front end read the same header)
+            const bool dual = o.acmod == 0;
+            uint32_t c[2], e[2] = {0u, 0u};
+            c[0] = (o.present & AC3MI_BSI_COMPRE) ? 0x100u | o.compr : 0u;
+            c[1] = dual && (o.present & AC3MI_BSI_COMPR2E) ? 0x100u | o.compr2 : 0u;
+            const int p0 = P.prog < 0 ? 0 : dual ? P.prog : 0;     // the source programme that becomes programme 0
+            compr[0] = c[p0];
+            compr[1] = P.prog < 0 ? c[1] : 0u;
+            const uint32_t *raw = P.src_dyn + (size_t)f * 6;
+            for (int b = 0; b < 6; b++) {
+                const uint32_t w = raw[b];
+                if (w & 0x100u) e[0] = w & 0xffu;
+                if (dual && (w & 0x1000000u)) e[1] = (w >> 16) & 0xffu;
+                code[0][b] = e[p0];
+                code[1][b] = P.prog < 0 ? e[1] : 0u;
+            }
+        }
+    }
+    uint32_t *out = reinterpret_cast<uint32_t *>(P.codes + (size_t)f * 12);
+    for (int k = 0; k < 3; k++)                          // [6][2] bytes: blocks 2k and 2k + 1
+        out[k] = code[0][2 * k] | code[1][2 * k] << 8 | code[0][2 * k + 1] << 16 | code[1][2 * k + 1] << 24;
+    reinterpret_cast<uint32_t *>(P.compr)[f] = compr[0] | compr[1] << 16;
+}
+
+hipError_t launch_dynrng_source(const DynSrcLaunch &L, hipStream_t stream)
+{
+    if (L.n_frames == 0) return hipSuccess;
+    if (L.n_frames > 0x7fffffffu || L.frame_bytes < 8 || L.frame_bytes > 3840 || !L.frames || !L.src_dyn || !L.status || !L.codes ||
+        !L.compr || ((uintptr_t)L.codes & 3) || ((uintptr_t)L.compr & 3) || L.prog < -1 || L.prog > 1)
+        return hipErrorInvalidValue;
+    DynSrcParams P;
+    P.frames = L.frames;
+    P.src_dyn = L.src_dyn;
+    P.status = L.status;
+    P.codes = L.codes;
+    P.compr = L.compr;
+    P.n_frames = (unsigned)L.n_frames;
+    P.frame_stride = L.frame_stride;
+    P.frame_bytes = L.frame_bytes;
+    P.prog = L.prog;
+    hipLaunchKernelGGL(enc_dynrng_source_kernel, dim3((P.n_frames + 63u) / 64u), dim3(64), 0, stream, P);
+    return hipGetLastError();
+}
+
 }  // namespace ac3mi

@@ -820,8 +820,31 @@ int ac3mi_set_encode_metadata_source(ac3mi_ctx *ctx, int mode)
 int ac3mi_set_encode_drc(ac3mi_ctx *ctx, int profile, int32_t *d_drc_state)
 {
     if (!ctx || profile < 0 || profile > 5 || (profile != 0 && !d_drc_state)) return AC3MI_ERR_ARG;
+    if (profile != 0 && ctx->tools.dyn_codes) {
+        ctx->err = "ac3mi_set_encode_drc: the dynrng words are set by ac3mi_set_encode_dynrng_frames";
+        return AC3MI_ERR_ARG;
+    }
     ctx->tools.drc_profile = profile;
     ctx->tools.drc_state = profile ? d_drc_state : nullptr;
+    return AC3MI_OK;
+}
+
+int ac3mi_set_encode_dynrng_frames(ac3mi_ctx *ctx, const uint8_t *d_dynrng, const uint16_t *d_compr)
+{
+    if (!ctx || ((uintptr_t)d_compr & 1)) return AC3MI_ERR_ARG;
+    if (d_dynrng && ctx->tools.drc_profile) {
+        ctx->err = "ac3mi_set_encode_dynrng_frames: the dynrng words are a profile's (ac3mi_set_encode_drc)";
+        return AC3MI_ERR_ARG;
+    }
+    ctx->tools.dyn_codes = d_dynrng;
+    ctx->tools.compr_words = d_compr;
+    return AC3MI_OK;
+}
+
+int ac3mi_set_encode_drc_source(ac3mi_ctx *ctx, int mode)
+{
+    if (!ctx || mode < 0 || mode > 1) return AC3MI_ERR_ARG;
+    ctx->tools.drc_source = mode;
     return AC3MI_OK;
 }
 
@@ -874,8 +897,8 @@ static int tile_streams(const ac3mi_ctx *ctx, int n_streams, int frames_per_stre
 
 // The context's per-stream pointers while a batch goes through in tiles: at(s0) points them at the tile's first stream s0
 // (the state slots when set, else the mix state of mix_n_out chains a stream - 0: it stays - and with `drc` the encoder's
-// DRC state; with `drc` also the per-frame metadata words, which go by the frame's position in the call, slots or not); the
-// destructor puts them back.
+// DRC state; with `drc` also the per-frame metadata words and the per-frame dynrng / compr arrays, which go by the frame's
+// position in the call, slots or not); the destructor puts them back.
 struct TileState {
     ac3mi_ctx *ctx;
     int mix_n_out;
@@ -885,12 +908,17 @@ struct TileState {
     float *mix_pending;
     int32_t *mix_flags, *drc_state;
     const uint32_t *bsi_words;
+    const uint8_t *dyn_codes;
+    const uint16_t *compr_words;
     TileState(ac3mi_ctx *c, int mix_n_out, bool drc, int frames_per_stream)
         : ctx(c), mix_n_out(mix_n_out), drc(drc), frames_per_stream(frames_per_stream), slots(c->slots), mix_pending(c->mix_pending),
-          mix_flags(c->mix_flags), drc_state(c->tools.drc_state), bsi_words(c->tools.bsi_words) {}
+          mix_flags(c->mix_flags), drc_state(c->tools.drc_state), bsi_words(c->tools.bsi_words),
+          dyn_codes(c->tools.dyn_codes), compr_words(c->tools.compr_words) {}
     void at(int s0)
     {
         if (drc && bsi_words) ctx->tools.bsi_words = bsi_words + (size_t)s0 * frames_per_stream;
+        if (drc && dyn_codes) ctx->tools.dyn_codes = dyn_codes + (size_t)s0 * frames_per_stream * 12;
+        if (drc && compr_words) ctx->tools.compr_words = compr_words + (size_t)s0 * frames_per_stream * 2;
         if (slots) { ctx->slots = slots + s0; return; }
         if (mix_n_out && mix_pending) {
             ctx->mix_pending = mix_pending + (size_t)s0 * mix_n_out * 128;
@@ -905,6 +933,8 @@ struct TileState {
         ctx->mix_flags = mix_flags;
         ctx->tools.drc_state = drc_state;
         ctx->tools.bsi_words = bsi_words;
+        ctx->tools.dyn_codes = dyn_codes;
+        ctx->tools.compr_words = compr_words;
     }
 };
 
@@ -1118,6 +1148,8 @@ static int encode_setup(ac3mi_ctx *ctx, EncodeLaunch &E, const ac3mi_encode_desc
     }
     E.bsi = t.bsi;
     E.bsi_words = t.bsi_words;
+    E.dyn_codes = t.dyn_codes;
+    E.compr_words = t.compr_words;
     E.drc_profile = t.drc_profile;
     if (t.drc_profile) {                            // [nfr][6] int16 gains, then [nfr][6] codes
         TRY(ws_grow(ctx, ctx->ws_drc, 18 * nfr));
@@ -1520,6 +1552,12 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         ctx->err = "ac3mi_transcode_batch: bad argument";
         return AC3MI_ERR_ARG;
     }
+    if (t.drc_source == 1 && (dec->dynrng || t.drc_profile)) {
+        ctx->err = dec->dynrng ? "ac3mi_transcode_batch: ac3mi_set_encode_drc_source 1 carries the source's dynrng words - a decode with dynrng != 0 "
+                                 "would apply the gains twice"
+                               : "ac3mi_transcode_batch: ac3mi_set_encode_drc_source 1 with a profile of ac3mi_set_encode_drc set";
+        return AC3MI_ERR_ARG;
+    }
     ac3mi_decode_desc dd = *dec;
     dd.level = 1.0f;                                    // the s16 converter reads the 16-bit value out of the float (bias 384)
     dd.bias = 384.0f;
@@ -1583,6 +1621,7 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     TRY(grow_front_ws(ctx, fe, nfr));
     TRY(encode_setup(ctx, E, enc, nfr, nullptr));
     if (t.md_source == 1) TRY(ws_grow(ctx, ctx->ws_bsi, nfr * sizeof(uint32_t)));
+    if (t.drc_source == 1) TRY(ws_grow(ctx, ctx->ws_dyn, nfr * 40));      // raw words [nfr][6] u32 | codes [nfr][6][2] | compr [nfr][2] u16
     uint8_t *const zs = fe.mixstate ? ctx->ws_blksw.at<uint8_t>(zs_off(nfr, X.plan.nfchans)) : nullptr;
     int16_t *const ws_s16 = ctx->ws_tc.at<int16_t>();
     // Decoder front end, transform to s16, encoder: back to back on the context's stream.  (Until round 2 two chunks were
@@ -1612,6 +1651,7 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         HIPCHK(ctx, launch_bsi(B, ctx->stream));
         E.bsi_words = B.words;
     }
+    if (t.drc_source == 1 && nfr) D.src_dyn = ctx->ws_dyn.at<uint32_t>();      // the SRC front ends
     D.coef = fe.mantx ? nullptr : ctx->ws_coef.at<float>();
     D.blksw = ctx->ws_blksw.at<uint8_t>();
     D.zs = zs;
@@ -1635,6 +1675,24 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
         if (fe.mantx) D.fuse = &X;
         HIPCHK(ctx, launch_decode(ctx->tab, D, ctx->stream));
         if (!fe.mantx) HIPCHK(ctx, launch_xform(ctx->tab, X, ctx->stream));
+    }
+    if (D.src_dyn) {
+        // ac3mi_set_encode_drc_source 1: the front end's raw words, the frames' status and their BSI resolved into the arrays the
+        // encoder codes from, for this call (or tile); arrays of ac3mi_set_encode_dynrng_frames are not read
+        DynSrcLaunch R;
+        R.frames = d_frames_in;
+        R.n_frames = nfr;
+        R.frame_stride = in_stride;
+        R.frame_bytes = dd.frame_bytes;
+        R.src_dyn = D.src_dyn;
+        R.status = d_status;
+        R.codes = ctx->ws_dyn.at<uint8_t>(nfr * 24);
+        R.compr = ctx->ws_dyn.at<uint16_t>(nfr * 36);
+        // a dual-mono source coded as dual mono keeps both programmes; else the one the request names becomes programme 0
+        R.prog = dd.acmod == 0 && E.cfg.acmod == 0 ? -1 : dd.acmod == 0 && (dd.flags & AC3MI_CHANNEL_MASK) == AC3MI_CHANNEL2 ? 1 : 0;
+        HIPCHK(ctx, launch_dynrng_source(R, ctx->stream));
+        E.dyn_codes = R.codes;
+        E.compr_words = R.compr;
     }
     E.pcm = ws_s16;
     E.last = d_last;

@@ -182,7 +182,13 @@ struct DecodeParams {
     const int32_t *slot;    // optional: stream s keeps its LFSR state in lfsr_state[slot[s]]
     uint32_t *frame_draws;  // [S][F] dither draws of each frame (written by the counting pass)
     const uint16_t *frame_lfsr;   // [S][F] LFSR state at the start of each frame (frame-parallel pass)
-    float *dyn_out;               // optional [S][F][6][2], see ac3mi_decode_taps
+    // dyn_out: optional [S][F][6][2], see ac3mi_decode_taps - written only while the gains are applied (dynrng_on).  The SRC
+    // instantiations run with dynrng_on 0 and find here instead src_dyn: [S][F][6] raw dynamic-range fields of every block
+    // (DecodeLaunch::src_dyn).  One slot: the kernel arguments of every other instantiation are what they were
+    union {
+        float *dyn_out;
+        uint32_t *src_dyn;
+    };
     const float *dyn_in;
     const uint8_t *crc;           // optional [S][F] verdicts of crc_kernel: bits 0-1 -> status bits 10-11, bit 6: refuse the frame
 };
@@ -201,6 +207,9 @@ __device__ __forceinline__ const uint8_t *crc_verdicts()
     typedef const uint8_t *__attribute__((address_space(4))) const *slot_t;
     return *(slot_t)((const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + off);
 }
+
+// a block's raw dynamic-range field of programme `word` (0, 1) in that array's word: dynrnge bit 8, dynrng bits 0-7, shifted by 16 for programme 1
+__device__ __forceinline__ uint32_t src_dyn_field(int code, int word) { return (0x100u | ((uint32_t)code & 0xffu)) << (16 * word); }
 
 // the range factor of a dynamic-range word (parse.c:587-595), through the optional per-word taps
 __device__ __forceinline__ float dynrng_range(const DecodeParams &P, int code, size_t word_index, int lane)

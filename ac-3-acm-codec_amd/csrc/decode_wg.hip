@@ -201,6 +201,7 @@ struct ParserState {
 #else
 #define PSTAMP(i) do { } while (0)
 #endif
+template <bool SRC = false>
 __device__ __forceinline__ void parse_block_a(const FrameBits FB, ParserState &S, BlkInfo &B, const BlkInfo &prev, int blk, int lane, const DecodeParams &P, size_t fidx,
                               unsigned long long *dbg = nullptr)
 {
@@ -216,13 +217,16 @@ __device__ __forceinline__ void parse_block_a(const FrameBits FB, ParserState &S
         for (int i = 0; i < nf; i++) blkswm |= rd.get(1) << i;
         for (int i = 0; i < nf; i++) dithmask |= rd.get(1) << i;
         int twice = !acmod, word = 0;
+        [[maybe_unused]] uint32_t raw = 0;
         do {
             if (rd.get(1)) {
                 const int code = rd.sget(8);
+                if constexpr (SRC) raw |= src_dyn_field(code, word);
                 if (ldsu(S.dynrnge)) PSET(S.dynrng, ldsf(S.level) * dynrng_range(P, code, (fidx * 6 + blk) * 2 + word, lane));
             }
             word++;
         } while (twice--);
+        if constexpr (SRC) if (lane == 0) P.src_dyn[fidx * 6 + blk] = raw;
 
         PSTAMP(2);
         int chincpl = ldsu(S.chincpl);
@@ -750,7 +754,9 @@ using namespace wg;
 // crc_verdicts() reads DecodeParams::crc from the kernel-argument segment: W stays this kernel's first argument and the
 // DecodeParams its first member
 static_assert(offsetof(WgParams, d) == 0, "crc_verdicts(): the DecodeParams leads the kernel arguments");
-template <int OUT>
+// SRC (ac3mi_set_encode_drc_source 1; a transcode's fused front end, OUT 2): the parser leaves every block's raw dynamic-range
+// fields in P.src_dyn (decode_kernel's SRC)
+template <int OUT, bool SRC = false>
 __global__ __launch_bounds__(512, WG_LB) void decode_wg_kernel(const WgParams W)
 {
     __shared__ WgLDS L;
@@ -840,7 +846,7 @@ __global__ __launch_bounds__(512, WG_LB) void decode_wg_kernel(const WgParams W)
                 if (!ok) PSET(S.status, 0x100u);
                 BlkInfo &B0 = L.bi[0];
                 if (ok) {
-                    parse_block_a(FB, S, B0, L.bi[1], 0, lane, P, fidx);
+                    parse_block_a<SRC>(FB, S, B0, L.bi[1], 0, lane, P, fidx);
                     wave_sync();
                     parse_block_b(FB, S, B0, L.deltba, 0, lane);
                 } else PSET(B0.err, 1);
@@ -953,9 +959,9 @@ __global__ __launch_bounds__(512, WG_LB) void decode_wg_kernel(const WgParams W)
                     }
                     if (blk < 5) {
 #ifdef WG_STAMPS
-                        if (!dead) parse_block_a(FB, S, Bn, B, blk + 1, lane, P, fidx, (W.stamps && blockIdx.x == 0 && s == (int)gridDim.x && f == 0 && blk == 2) ? W.stamps + wave * 64 + 56 : nullptr);
+                        if (!dead) parse_block_a<SRC>(FB, S, Bn, B, blk + 1, lane, P, fidx, (W.stamps && blockIdx.x == 0 && s == (int)gridDim.x && f == 0 && blk == 2) ? W.stamps + wave * 64 + 56 : nullptr);
 #else
-                        if (!dead) parse_block_a(FB, S, Bn, B, blk + 1, lane, P, fidx);
+                        if (!dead) parse_block_a<SRC>(FB, S, Bn, B, blk + 1, lane, P, fidx);
 #endif
                         else PSET(Bn.err, 1);
                     }
@@ -1164,6 +1170,10 @@ hipError_t launch_decode_wg(const DeviceTables &tab, const DecodeLaunch &D, cons
     P.dyn_out = D.dyn_out;
     P.dyn_in = D.dyn_in;
     P.crc = D.crc;
+    if (D.src_dyn) {                    // the raw words take the tap's slot: never with gains applied, or with the tap
+        if (D.dynrng_on || D.dyn_out || D.dyn_in) return hipErrorInvalidValue;
+        P.src_dyn = D.src_dyn;
+    }
     W.tw_long = tab.tw_long;
     W.tw_short = tab.tw_short;
     W.window = tab.window;
@@ -1182,7 +1192,8 @@ hipError_t launch_decode_wg(const DeviceTables &tab, const DecodeLaunch &D, cons
         int dev = 0, cus = 256, occ = 0;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const void *fn = !X ? (const void *)decode_wg_kernel<0> : X->pcm16 ? (const void *)decode_wg_kernel<2> : (const void *)decode_wg_kernel<1>;
+        const void *fn = !X ? (const void *)decode_wg_kernel<0> : !X->pcm16 ? (const void *)decode_wg_kernel<1>
+                         : D.src_dyn ? (const void *)decode_wg_kernel<2, true> : (const void *)decode_wg_kernel<2>;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 512, fr_bytes) != hipSuccess || occ < 1) occ = 1;
         grid_cap = occ * cus;
     }
@@ -1215,6 +1226,7 @@ hipError_t launch_decode_wg(const DeviceTables &tab, const DecodeLaunch &D, cons
         }
     } dump{d_stamps, stream};
 #endif
+    if (D.src_dyn && !(X && X->pcm16)) return hipErrorInvalidValue;     // the raw words are a transcode's (s16, fused)
     if (!X) {
         hipLaunchKernelGGL(decode_wg_kernel<0>, dim3(grid), dim3(512), fr_bytes, stream, W);
         return hipGetLastError();
@@ -1233,7 +1245,8 @@ hipError_t launch_decode_wg(const DeviceTables &tab, const DecodeLaunch &D, cons
         if (s16_channel_map(X->s16_flags, map) != W.n_out || ((uintptr_t)X->pcm16 & 15)) return hipErrorInvalidValue;
         for (int w = 0; w < W.n_out; w++) W.wslot[map[w]] = (int8_t)w;
         W.pcm16 = X->pcm16;
-        hipLaunchKernelGGL(decode_wg_kernel<2>, dim3(grid), dim3(512), fr_bytes, stream, W);
+        if (D.src_dyn) hipLaunchKernelGGL((decode_wg_kernel<2, true>), dim3(grid), dim3(512), fr_bytes, stream, W);
+        else hipLaunchKernelGGL(decode_wg_kernel<2>, dim3(grid), dim3(512), fr_bytes, stream, W);
     } else {
         W.pcm = X->pcm;
         hipLaunchKernelGGL(decode_wg_kernel<1>, dim3(grid), dim3(512), fr_bytes, stream, W);

@@ -79,6 +79,9 @@ struct PackParams {
     const uint8_t *drc;         // the DRC variants: [S][F][6] dynrng codes (enc_drc_smooth_kernel); null in the others
     uint32_t bsi;               // the MD packers: the BSI fields (bsi_word)
     const uint32_t *bsi_words;  // the MD packers: optional, [S][F] raw words by the frame's position in the call; frame f then codes bsi_sanitise(bsi_words[f])
+    // the DW variants (ac3mi_set_encode_dynrng_frames / ac3mi_set_encode_drc_source), by the frame's position in the call:
+    const uint8_t *dyn;         // optional, [S][F][6][2]: the dynrng code in force in each block, programme 0 and 1 (1: acmod 0 only)
+    const uint16_t *compr;      // optional, [S][F][2]: bit 8 compre (compr2e), bits 0-7 compr (compr2)
 };
 
 // the BSI fields frame fidx codes (MD packers): the call's word, or the frame's own from the array (ac3mi_set_encode_metadata_frames /
@@ -91,6 +94,14 @@ __device__ __forceinline__ uint32_t pack_bsi(const PackParams &P, size_t fidx)
 
 // dynrng words of a frame (ac3mi_set_encode_drc): block 0 sends its code, block b > 0 only when it differs from block b - 1's
 __device__ __forceinline__ bool drc_sends(const uint8_t *code, int b) { return b == 0 || code[b] != code[b - 1]; }
+// ... and of a frame's [6][2] codes in force (PackParams::dyn), per programme p: a frame starts at word 0 (gain 1.0) and a word
+// holds to the frame's end, so block b sends iff its code differs from the one before it - block 0's from 0
+__device__ __forceinline__ bool dyn_sends(const uint8_t *code, int b, int p) { return code[2 * b + p] != (b ? code[2 * b - 2 + p] : 0); }
+// the frame's compr word of programme p (bit 8: sent), wave-uniform
+__device__ __forceinline__ uint32_t compr_word(const PackParams &P, size_t fidx, int p)
+{
+    return P.compr ? (uint32_t)__builtin_amdgcn_readfirstlane((int)P.compr[fidx * 2 + p]) & 0x1ffu : 0u;
+}
 
 
 
@@ -1616,12 +1627,15 @@ __device__ unsigned long long g_pack_cycles[16];
 // CPL (enc_search_cpl_kernel: channel coupling on, P.cpl): the coupling rows join the costed rows of a coupled frame.
 // BW (with CPL; ac3mi_set_encode_bandwidth 1 or 2): a coupled frame ends at cplendmant = 73 + 12 P.cpl_endf, not 217.
 // DRC (ac3mi_set_encode_drc 1..5): every block that sends a dynrng word (P.drc) costs its 8 bits.
+// DW (with DRC; P.dyn / P.compr): the words of the caller's or the source's arrays instead - 8 bits per word a programme sends
+// (dyn_sends) and per compr word; P.drc may then be null (no profile).
 // FX (PART 1 with none of the above; launch_encode's fixed-shape rule): one-frame 5.1 streams - six channels, five of them
 // full-bandwidth, acmod 7, 223 coefficients, a single frame and neither taps nor a verdict table, as constants instead of P's members.
-template <int PART, bool CPL = false, bool BW = false, bool DRC = false, bool FX = false>
+template <int PART, bool CPL = false, bool BW = false, bool DRC = false, bool FX = false, bool DW = false>
 __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const PackParams P)
 {
     static_assert(PART == 1 || PART == 3, "the packers are enc_packf_kernel / enc_packb_kernel");
+    static_assert(!DW || DRC, "the array words are costed where the profiles' are");
     static_assert(!FX || (PART == 1 && !CPL && !BW && !DRC), "the fixed 5.1 shape is the plain per-stream search's");
     __shared__ SearchLDS<CPL> L;
     const int lane = threadIdx.x;
@@ -1715,9 +1729,18 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                 frame_bits += 2 * 4 + 3 + 6 + nch * (4 + 3);
                 frame_bits += 2;
                 frame_bits += 16;
-                if constexpr (DRC) {
+                if constexpr (DRC) if (!DW || P.drc) {
                     const uint8_t *code = P.drc + fidx * 6;
                     for (int b = 0; b < 6; b++) frame_bits += drc_sends(code, b) ? (acmod == 0 ? 16 : 8) : 0;     // (dual mono: dynrng2 too)
+                }
+                if constexpr (DW) {                 // each programme's own sends; compr / compr2
+                    const int np = acmod == 0 ? 2 : 1;
+                    if (P.dyn) {
+                        const uint8_t *code = P.dyn + fidx * 12;
+                        for (int b = 0; b < 6; b++)
+                            for (int p = 0; p < np; p++) frame_bits += dyn_sends(code, b, p) ? 8 : 0;
+                    }
+                    for (int p = 0; p < np; p++) frame_bits += (compr_word(P, fidx, p) & 0x100u) ? 8 : 0;
                 }
                 // rematrixing: the four flags of every block 1..5 that sends them (block 0's stay uncounted, as above)
                 if (!FX && P.remat)
@@ -2139,9 +2162,12 @@ struct alignas(16) PackfLDS {
 // MD (ac3mi_set_encode_metadata / _frames / _source, ac3mi_set_encode_drc): the BSI fields of P.bsi or of the frame's own word
 // (pack_bsi), and the dynrng words of P.drc if it is set
 // DUAL (dual mono, acmod 0; generic and uncoupled only): the second programme's BSI fields and dynrng2e / dynrng2
-template <bool FIXED51, bool CPL = false, bool BW = false, bool MD = false, bool DUAL = false>
+// DW (with MD; ac3mi_set_encode_dynrng_frames / ac3mi_set_encode_drc_source): compre / compr (compr2e / compr2) of P.compr, and
+// the dynrng words of P.dyn - each programme's own, sent by dyn_sends - when it is set, else P.drc's as above
+template <bool FIXED51, bool CPL = false, bool BW = false, bool MD = false, bool DUAL = false, bool DW = false>
 __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackParams P)
 {
+    static_assert(!DW || MD, "the array words are written where the profiles' are");
     static_assert(!(FIXED51 && CPL), "coupled frames take the generic packer");
     static_assert(!(DUAL && (FIXED51 || CPL)), "dual mono is neither 5.1 nor coupled");
     __shared__ PackfLDS<CPL> L;
@@ -2224,8 +2250,15 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         if ((acmod & 1) && acmod != 1) put(2, (m >> 8) & 3u);
         if (acmod & 4) put(2, (m >> 10) & 3u);
         if (acmod == 2) put(2, (m >> 12) & 3u);
-        put(1, lfe); put(5, m & 31u); put(3, 0);
-        if constexpr (DUAL) { put(5, m & 31u); put(3, 0); }    // dual mono: dialnorm2 = dialnorm, compr2e langcod2e audprodi2e
+        if constexpr (DW) {
+            // compre (+ compr), langcode, audprodie; dual mono: dialnorm2 = dialnorm, compr2e (+ compr2), langcod2e, audprodi2e
+            auto put_compr = [&](uint32_t c) { if (c & 0x100u) { put(1, 1); put(8, c & 0xffu); } else put(1, 0); };
+            put(1, lfe); put(5, m & 31u); put_compr(compr_word(P, fidx, 0)); put(2, 0);
+            if constexpr (DUAL) { put(5, m & 31u); put_compr(compr_word(P, fidx, 1)); put(2, 0); }
+        } else {
+            put(1, lfe); put(5, m & 31u); put(3, 0);
+            if constexpr (DUAL) { put(5, m & 31u); put(3, 0); }    // dual mono: dialnorm2 = dialnorm, compr2e langcod2e audprodi2e
+        }
         put(1, (m >> 14) & 1u); put(1, (m >> 15) & 1u); put(3, 0);
     } else {
         put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, 0); put(3, acmod);
@@ -2271,7 +2304,14 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         else
             for (int ch = 0; ch < nfbw; ch++) put(1, 0);
         for (int ch = 0; ch < nfbw; ch++) put(1, 1);
-        if constexpr (MD) {
+        if constexpr (DW) {
+            // dynrnge + dynrng, dual mono: dynrng2e + dynrng2 - the arrays' (each programme's own code and sends), else the profile's
+            for (int p = 0; p < (DUAL ? 2 : 1); p++) {
+                const bool word = P.dyn ? dyn_sends(P.dyn + fidx * 12, b, p) : P.drc && drc_sends(P.drc + fidx * 6, b);
+                if (word) { put(1, 1); put(8, P.dyn ? P.dyn[fidx * 12 + 2 * b + p] : P.drc[fidx * 6 + b]); flush(); }
+                else put(1, 0);
+            }
+        } else if constexpr (MD) {
             // dynrnge + dynrng (flushed: the block's first stretch of fields stays within the accumulator)
             const bool word = P.drc && drc_sends(P.drc + fidx * 6, b);
             if (word) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
@@ -2503,9 +2543,12 @@ struct alignas(16) PackbLDS {
 #endif
 // MD (ac3mi_set_encode_metadata / _frames / _source, ac3mi_set_encode_drc): the BSI fields of P.bsi or of the frame's own word
 // (pack_bsi), and the dynrng words of P.drc if it is set
-template <bool MD = false>
+// DW (with MD): compre / compr (compr2e / compr2) of P.compr, and the dynrng words of P.dyn - each programme's own - when it is
+// set (enc_packf_kernel's DW)
+template <bool MD = false, bool DW = false>
 __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const PackParams P)
 {
+    static_assert(!DW || MD, "the array words are written where the profiles' are");
     __shared__ PackbLDS L;
     extern __shared__ uint4 pk_dyn[];
     uint32_t *fr = reinterpret_cast<uint32_t *>(pk_dyn);
@@ -2560,14 +2603,25 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
     const uint32_t strat_set = (uint32_t)__ballot(strat_l != 0);        // bit ch: the channel sends exponents in this block
     auto strat_of = [&](int ch) { return __builtin_amdgcn_readlane(strat_l, ch); };
     // bits of the frame header (:1113-1147) and of this block's side information with its exponents (:1194-1332)
-    const int hdr_bits = 16 + 16 + 2 + 6 + 5 + 3 + 3 + (((P.acmod & 1) && P.acmod != 1) ? 2 : 0) + ((P.acmod & 4) ? 2 : 0) +
-                         (P.acmod == 2 ? 2 : 0) + 1 + 5 + 3 + (P.acmod == 0 ? 8 : 0) + 1 + 1 + 3;
+    int hdr_bits = 16 + 16 + 2 + 6 + 5 + 3 + 3 + (((P.acmod & 1) && P.acmod != 1) ? 2 : 0) + ((P.acmod & 4) ? 2 : 0) +
+                   (P.acmod == 2 ? 2 : 0) + 1 + 5 + 3 + (P.acmod == 0 ? 8 : 0) + 1 + 1 + 3;
+    uint32_t compr[2] = {0u, 0u};                       // (DW) the frame's compr / compr2 words
+    if constexpr (DW)
+        for (int p = 0; p < (P.acmod == 0 ? 2 : 1); p++) {
+            compr[p] = compr_word(P, fidx, p);
+            if (compr[p] & 0x100u) hdr_bits += 8;
+        }
     int side_bits = 2 * nfbw + 1 + (P.acmod == 0 ? 1 : 0) + (b == 0 ? 2 : 1) + (P.acmod == 2 ? (b == 0 ? 5 : 1) : 0) + 2 * nfbw + (P.lfe ? 1 : 0) +
                     1 + (b == 0 ? 11 : 0) + 1 + (b == 0 ? 6 + 7 * nch : 0) + 2;
     const int rem = P.remat ? (int)P.remat[fidx * 6 + b] : -1;     // rematrixing: block b > 0 sends its four flags when rematstr
     if (b > 0 && rem >= 0 && (rem & 0x10)) side_bits += 4;
     const bool drc_word = MD && P.drc && drc_sends(P.drc + fidx * 6, b);
-    if (drc_word) side_bits += P.acmod == 0 ? 16 : 8;
+    bool dyn_word[2] = {drc_word, drc_word};            // (DW) per programme
+    if constexpr (DW) {
+        if (P.dyn)
+            for (int p = 0; p < 2; p++) dyn_word[p] = dyn_sends(P.dyn + fidx * 12, b, p);
+        side_bits += (dyn_word[0] ? 8 : 0) + (P.acmod == 0 && dyn_word[1] ? 8 : 0);
+    } else if (drc_word) side_bits += P.acmod == 0 ? 16 : 8;
     for (int ch = 0; ch < nch; ch++) {
         const int stg = strat_of(ch);
         if (stg == 0) continue;
@@ -2636,8 +2690,14 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
                 if ((P.acmod & 1) && P.acmod != 1) put(2, (m >> 8) & 3u);
                 if (P.acmod & 4) put(2, (m >> 10) & 3u);
                 if (P.acmod == 2) put(2, (m >> 12) & 3u);
-                put(1, P.lfe); put(5, m & 31u); put(3, 0);
-                if (P.acmod == 0) { put(5, m & 31u); put(3, 0); }      // dual mono: dialnorm2 = dialnorm, compr2e langcod2e audprodi2e
+                if constexpr (DW) {
+                    auto put_compr = [&](uint32_t c) { if (c & 0x100u) { put(1, 1); put(8, c & 0xffu); } else put(1, 0); };
+                    put(1, P.lfe); put(5, m & 31u); put_compr(compr[0]); put(2, 0);
+                    if (P.acmod == 0) { put(5, m & 31u); put_compr(compr[1]); put(2, 0); }
+                } else {
+                    put(1, P.lfe); put(5, m & 31u); put(3, 0);
+                    if (P.acmod == 0) { put(5, m & 31u); put(3, 0); }      // dual mono: dialnorm2 = dialnorm, compr2e langcod2e audprodi2e
+                }
                 put(1, (m >> 14) & 1u); put(1, (m >> 15) & 1u); put(3, 0);
             } else {
                 put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, 0); put(3, P.acmod);
@@ -2657,7 +2717,12 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
         else
             for (int ch = 0; ch < nfbw; ch++) put(1, 0);
         for (int ch = 0; ch < nfbw; ch++) put(1, 1);
-        if constexpr (MD) {
+        if constexpr (DW) {
+            for (int p = 0; p < (P.acmod == 0 ? 2 : 1); p++) {
+                if (dyn_word[p]) { put(1, 1); put(8, P.dyn ? P.dyn[fidx * 12 + 2 * b + p] : P.drc[fidx * 6 + b]); flush(); }
+                else put(1, 0);
+            }
+        } else if constexpr (MD) {
             // dynrnge + dynrng (flushed: the fields up to the first exponent would overflow the accumulator by up to 2 bits)
             if (drc_word) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
             else put(1, 0);
@@ -2988,7 +3053,11 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     if (c.nfbw * nbc + 7 > MANT_MAX_COEFS) return hipErrorInvalidValue;
     // metadata and dynamic range control: the DRC kernels write the frames' codes first; with DRC on the search costs the words
     // (DRC variants), with either on, or a word per frame (bsi_words), the packers write them (MD variants).  All off: exactly the kernels of before
-    const bool drc = E.drc_profile != 0, md = drc || E.bsi != BSI_DEFAULT || E.bsi_words != nullptr;
+    // Words from the caller's or the source's arrays (E.dyn_codes / E.compr_words): the DW variants of the search and the packers,
+    // which cost and write them; with neither array the kernels are the ones of before
+    const bool dw = E.dyn_codes != nullptr || E.compr_words != nullptr;
+    if (E.dyn_codes && E.drc_profile) return hipErrorInvalidValue;         // (the C API refuses the pair)
+    const bool drc = E.drc_profile != 0, md = dw || drc || E.bsi != BSI_DEFAULT || E.bsi_words != nullptr;
     if (drc) {
         const hipError_t ed = launch_drc(E, stream);
         if (ed != hipSuccess) return ed;
@@ -3024,7 +3093,7 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     // (the FX / FIXED51 instantiations) - the front kernel and the search when, besides, the streams are one frame long, the
     // bandwidth is the full one and no tool of theirs is on (fx_plain; each adds "no stage tap of mine" below).  Same bytes either way
     const bool fixed51 = E.fixed_shape && fixed51_shape(c.acmod, c.lfe, c.nch, c.nch, c.nfbw);
-    const bool fx_plain = fixed51 && E.frames_per_stream == 1 && !bw && !E.ws_bsw && !E.ws_remat && E.cpl_begf < 0 && !drc && !E.exp_strategy;
+    const bool fx_plain = fixed51 && E.frames_per_stream == 1 && !bw && !E.ws_bsw && !E.ws_remat && E.cpl_begf < 0 && !drc && !dw && !E.exp_strategy;
     // (begf > cplendf + 2: no coupling band - no frame couples, the bytes are coupling off's; dual mono's two programmes are
     // never coupled)
     const bool cpl = E.cpl_begf >= 0 && c.nfbw >= 2 && c.acmod != 0 && E.cpl_begf <= cpl_endf + 2;
@@ -3157,6 +3226,8 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.drc = drc ? E.ws_drc_code : nullptr;
     P.bsi = E.bsi;
     P.bsi_words = E.bsi_words;
+    P.dyn = E.dyn_codes;
+    P.compr = E.compr_words;
 #ifndef ENC_FR_HEADROOM
 #define ENC_FR_HEADROOM 256
 #endif
@@ -3182,33 +3253,36 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     // (the uncoupled search and enc_packb_kernel take nbc / chbwcod at run time in every mode; bw picks the variants whose coupling
     // end or 5.1 band edge is a run-time value)
     // (the same chains for DRC on / off and MD on / off: D and X below are std::bool_constant tags)
-    auto searches = [&](auto D) {
-        constexpr bool DRC = decltype(D)::value;
+    // (... and for the array words: W)
+    auto searches = [&](auto D, auto W) {
+        constexpr bool DRC = decltype(D)::value, DW = decltype(W)::value;
         if (P.memo) {
-            if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<3, true, true, DRC>), dim3(nfr), dim3(64), 0, stream, P);
-            else if (cpl) hipLaunchKernelGGL((enc_search_kernel<3, true, false, DRC>), dim3(nfr), dim3(64), 0, stream, P);
-            else hipLaunchKernelGGL((enc_search_kernel<3, false, false, DRC>), dim3(nfr), dim3(64), 0, stream, P);
+            if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<3, true, true, DRC, false, DW>), dim3(nfr), dim3(64), 0, stream, P);
+            else if (cpl) hipLaunchKernelGGL((enc_search_kernel<3, true, false, DRC, false, DW>), dim3(nfr), dim3(64), 0, stream, P);
+            else hipLaunchKernelGGL((enc_search_kernel<3, false, false, DRC, false, DW>), dim3(nfr), dim3(64), 0, stream, P);
         }
-        if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<1, true, true, DRC>), dim3(E.n_streams), dim3(64), 0, stream, P);
-        else if (cpl) hipLaunchKernelGGL((enc_search_kernel<1, true, false, DRC>), dim3(E.n_streams), dim3(64), 0, stream, P);
+        if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<1, true, true, DRC, false, DW>), dim3(E.n_streams), dim3(64), 0, stream, P);
+        else if (cpl) hipLaunchKernelGGL((enc_search_kernel<1, true, false, DRC, false, DW>), dim3(E.n_streams), dim3(64), 0, stream, P);
         else if (!DRC && fx_plain && !P.memo && !P.tap_strat && !P.tap_snr)
             hipLaunchKernelGGL((enc_search_kernel<1, false, false, false, true>), dim3(E.n_streams), dim3(64), 0, stream, P);
-        else hipLaunchKernelGGL((enc_search_kernel<1, false, false, DRC>), dim3(E.n_streams), dim3(64), 0, stream, P);
+        else hipLaunchKernelGGL((enc_search_kernel<1, false, false, DRC, false, DW>), dim3(E.n_streams), dim3(64), 0, stream, P);
     };
-    auto packers = [&](auto X) {
-        constexpr bool MD = decltype(X)::value;
-        if (packb) hipLaunchKernelGGL((enc_packb_kernel<MD>), dim3(nfr), dim3(384), fr_lds, stream, P);
-        else if (cpl && bw) hipLaunchKernelGGL((enc_packf_kernel<false, true, true, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
-        else if (cpl) hipLaunchKernelGGL((enc_packf_kernel<false, true, false, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
-        else if (fixed51 && bw) hipLaunchKernelGGL((enc_packf_kernel<true, false, true, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
-        else if (fixed51 && P.nbc == 223) hipLaunchKernelGGL((enc_packf_kernel<true, false, false, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
-        else if (c.acmod == 0) hipLaunchKernelGGL((enc_packf_kernel<false, false, false, MD, true>), dim3(nfr), dim3(64), fr_lds, stream, P);
-        else hipLaunchKernelGGL((enc_packf_kernel<false, false, false, MD>), dim3(nfr), dim3(64), fr_lds, stream, P);
+    auto packers = [&](auto X, auto W) {
+        constexpr bool MD = decltype(X)::value, DW = decltype(W)::value;
+        if (packb) hipLaunchKernelGGL((enc_packb_kernel<MD, DW>), dim3(nfr), dim3(384), fr_lds, stream, P);
+        else if (cpl && bw) hipLaunchKernelGGL((enc_packf_kernel<false, true, true, MD, false, DW>), dim3(nfr), dim3(64), fr_lds, stream, P);
+        else if (cpl) hipLaunchKernelGGL((enc_packf_kernel<false, true, false, MD, false, DW>), dim3(nfr), dim3(64), fr_lds, stream, P);
+        else if (fixed51 && bw) hipLaunchKernelGGL((enc_packf_kernel<true, false, true, MD, false, DW>), dim3(nfr), dim3(64), fr_lds, stream, P);
+        else if (fixed51 && P.nbc == 223) hipLaunchKernelGGL((enc_packf_kernel<true, false, false, MD, false, DW>), dim3(nfr), dim3(64), fr_lds, stream, P);
+        else if (c.acmod == 0) hipLaunchKernelGGL((enc_packf_kernel<false, false, false, MD, true, DW>), dim3(nfr), dim3(64), fr_lds, stream, P);
+        else hipLaunchKernelGGL((enc_packf_kernel<false, false, false, MD, false, DW>), dim3(nfr), dim3(64), fr_lds, stream, P);
     };
-    if (drc) searches(std::true_type{});
-    else searches(std::false_type{});
-    if (md) packers(std::true_type{});
-    else packers(std::false_type{});
+    if (dw) searches(std::true_type{}, std::true_type{});
+    else if (drc) searches(std::true_type{}, std::false_type{});
+    else searches(std::false_type{}, std::false_type{});
+    if (dw) packers(std::true_type{}, std::true_type{});
+    else if (md) packers(std::true_type{}, std::false_type{});
+    else packers(std::false_type{}, std::false_type{});
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     // the new history: last 256 samples per channel of each stream's final frame

@@ -402,6 +402,30 @@ class Engine:
         self._check(self.lib.ac3mi_set_encode_drc(ctypes.c_void_p(self.ctx), int(profile), ptr))
         self._drc_state = state if int(profile) else None
 
+    def set_encode_dynrng_frames(self, dynrng=None, compr=None):
+        """Dynamic range words per frame (ac3mi_set_encode_dynrng_frames): `dynrng` uint8 [S][F][6][2] on the device, the
+        dynrng word in force in each block for programme 0 / 1 (a block sends when its word differs from the block before it,
+        block 0 when it is not 0); `compr` int16 / uint16 [S][F][2], bit 8 compre, bits 0-7 the word.  Both by the frame's
+        position in the following encode_batch / transcode_batch calls (kept referenced while set); None: none."""
+        import torch
+        if dynrng is not None and (dynrng.dtype != torch.uint8 or not dynrng.is_cuda or not dynrng.is_contiguous()):
+            raise ValueError("dynrng must be a contiguous uint8 tensor on the device")
+        if compr is not None and (compr.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) or not compr.is_cuda
+                                  or not compr.is_contiguous()):
+            raise ValueError("compr must be a contiguous int16 / uint16 tensor on the device")
+        if dynrng is not None or compr is not None:
+            torch.cuda.current_stream().synchronize()       # their fill was queued on torch's stream
+        self._check(self.lib.ac3mi_set_encode_dynrng_frames(ctypes.c_void_p(self.ctx),
+                                                            ctypes.c_void_p(dynrng.data_ptr()) if dynrng is not None else None,
+                                                            ctypes.c_void_p(compr.data_ptr()) if compr is not None else None))
+        self._dyn_words = (dynrng, compr)
+
+    def set_encode_drc_source(self, mode):
+        """Where transcode_batch takes the new frames' dynrng and compr words from (ac3mi_set_encode_drc_source): 0 = the
+        context's settings, 1 = each source frame's own words (flags.DRC_SOURCE_FOLLOW; the decode descriptor must have
+        dynrng 0).  Meant to be used together with set_encode_metadata_source(1): the words are relative to dialnorm."""
+        self._check(self.lib.ac3mi_set_encode_drc_source(ctypes.c_void_p(self.ctx), int(mode)))
+
     def set_encode_exp_strategy(self, mode):
         """Exponent strategies (ac3mi_set_encode_exp_strategy): 0 = the reference's rule, 1 = the partition of each frame's
         six blocks into exponent sets that costs the fewest bits under the header's model.  Applies to encode_batch and

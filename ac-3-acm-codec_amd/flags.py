@@ -35,3 +35,7 @@ BSI_PRESENT = {"compre": 0x001, "langcode": 0x002, "audprodie": 0x004, "compr2e"
                "audprodi2e": 0x020, "timecod1e": 0x040, "timecod2e": 0x080, "addbsie": 0x100}
 # ac3mi_set_encode_metadata_source modes
 MD_SOURCE_CONTEXT, MD_SOURCE_FOLLOW = 0, 1
+# ac3mi_set_encode_drc_source modes
+DRC_SOURCE_CONTEXT, DRC_SOURCE_FOLLOW = 0, 1
+# ac3mi_set_encode_dynrng_frames: bit 8 of a compr word of the array says that the word is sent (compre / compr2e)
+COMPR_SENT = 0x100

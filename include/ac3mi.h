@@ -456,8 +456,8 @@ int ac3mi_set_encode_metadata_frames(ac3mi_ctx *ctx, const uint32_t *d_words);
  *      decoder refuses (status bit 8: no sync word, reserved codes, other acmod / lfeon, longer than frame_bytes, or concealed
  *      by ac3mi_set_decode_crc 2) takes ac3mi_set_encode_metadata's word whole.  An array set with
  *      ac3mi_set_encode_metadata_frames is ignored by such a transcode.  ac3mi_encode_batch has no source and is unchanged.
- * Not carried: the source's dynrng, compr, langcod, audprod, timecode and addbsi fields - they change a frame's bit budget or
- * lie behind the parse kernels.  The drop-in and the byte-stream layer (ac3mi_dropin.h, ac3mi_stream.h) never follow.  Any
+ * Not carried: the source's langcod, audprod, timecode and addbsi fields (its dynrng and compr words:
+ * ac3mi_set_encode_drc_source).  The drop-in and the byte-stream layer (ac3mi_dropin.h, ac3mi_stream.h) never follow.  Any
  * other mode: AC3MI_ERR_ARG, and the setting is unchanged. */
 int ac3mi_set_encode_metadata_source(ac3mi_ctx *ctx, int mode);
 
@@ -497,6 +497,53 @@ int ac3mi_set_encode_metadata_source(ac3mi_ctx *ctx, int mode);
  * A profile outside 0..5, or a profile other than 0 with d_drc_state NULL: AC3MI_ERR_ARG, and the setting is unchanged.
  * The drop-in AC3_encode_* and the byte-stream layer (ac3mi_stream.h) never send dynrng. */
 int ac3mi_set_encode_drc(ac3mi_ctx *ctx, int profile, int32_t *d_drc_state);
+
+/* Dynamic range words per frame from the caller (new; applies to every following ac3mi_encode_batch / ac3mi_transcode_batch on
+ * `ctx` until set to NULL, in either packer variant and the coupled-frame packer, with every other encoder tool on or off, with
+ * or without state slots, tiled or not).  Both arrays live on the device and are indexed by the frame's position in the call
+ * like d_pcm - never by state slot; a tiled call reads each tile's slice - and must stay alive until the calls that read them
+ * have finished.
+ *   d_dynrng: [n_streams][frames_per_stream][6][2] bytes, the dynrng word IN FORCE in each block for programme 0 and programme 1
+ *      (programme 1 is read only when the coded acmod is 0, dual mono, where it is dynrng2).  Per programme, block b sends
+ *      dynrnge 1 and the word iff code[b] != (b ? code[b - 1] : 0): word 0 decodes to gain 1.0, and A/52 and liba52 start every
+ *      frame at gain 1.0 and hold a word to the end of the frame, so the gain a decoder applies in every block is the array's,
+ *      and an all-zero array sends nothing.  (ac3mi_set_encode_drc's profiles always send in block 0; their rule and bytes are
+ *      unchanged.)  NULL (the default): no words.
+ *   d_compr: [n_streams][frames_per_stream][2] uint16, programme 0 and programme 1 (read only for acmod 0, as compr2e /
+ *      compr2): bit 8 is compre, bits 0-7 the word, other bits are ignored.  The BSI then carries compre 1 and compr instead
+ *      of compre 0.  NULL (the default): none.
+ * Each dynrng word sent costs 8 bits and each compr word 8 bits of its frame; the SNR-offset search counts exactly these, per
+ * frame and per programme.  With both NULL the kernels launched and the bytes written are exactly those of before.
+ * A non-NULL d_dynrng while a profile of ac3mi_set_encode_drc is set, and a profile set while d_dynrng is: AC3MI_ERR_ARG, and
+ * the setting is unchanged; d_compr may be combined with a profile (dual mono under a profile sends the same dynrng word for
+ * both programmes, as before).  d_compr not 2-byte aligned: AC3MI_ERR_ARG.  Ignored by a transcode under
+ * ac3mi_set_encode_drc_source 1.  The drop-in AC3_encode_* and the byte-stream layer (ac3mi_stream.h) never read them. */
+int ac3mi_set_encode_dynrng_frames(ac3mi_ctx *ctx, const uint8_t *d_dynrng, const uint16_t *d_compr);
+
+/* Where a transcode's new frames take their dynrng and compr words from (new):
+ *   0  (default) the context: ac3mi_set_encode_drc / ac3mi_set_encode_dynrng_frames, whatever the source said;
+ *   1  the source: ac3mi_transcode_batch codes each new frame with the words of the input frame it was decoded from, so that
+ *      the listener's decoder, not this one, applies the programme's own compression.  The decode descriptor must then have
+ *      dynrng == 0 - AC3MI_ERR_ARG otherwise, the gains would be applied twice (ac3mi_last_error says so) - and no profile of
+ *      ac3mi_set_encode_drc may be set (AC3MI_ERR_ARG at the call).  Arrays of ac3mi_set_encode_dynrng_frames are ignored by
+ *      such a transcode.  The decoder front end leaves every block's raw dynrnge / dynrng (dynrng2e / dynrng2) fields in a
+ *      workspace, and a kernel after it, ahead of the encoder, resolves them per tile into ac3mi_set_encode_dynrng_frames'
+ *      arrays in a workspace of the context (40 bytes a frame; ac3mi_workspace_bytes counts it,
+ *      ac3mi_transcode_workspace_plan, which plans the default mode, does not):
+ *        - per source frame and programme p: e = 0 at the frame's start; in block b, if the source sends dynrng[p]e, e becomes
+ *          its word; the new frame's code for block b is e.  compre / compr of each programme are carried as they are;
+ *        - a dual-mono source coded as dual mono (ac3mi_set_encode_layout 2, or 1 with acmod 0) keeps both programmes; coded
+ *          as anything else it carries programme 1's words when the request is AC3MI_CHANNEL2 and programme 0's otherwise;
+ *          every other source has one programme; a decode that downmixes carries the words unchanged;
+ *        - a source frame whose d_status has bit 8 or any of bits 0-5 set (refused, concealed by ac3mi_set_decode_crc 2, or
+ *          any block failed) carries nothing: six zero codes, no compr.
+ *      The outcome equals, byte for byte, a mode-0 transcode (same dynrng 0) given these values through
+ *      ac3mi_set_encode_dynrng_frames; a source without any dynrng or compr word gives the bytes of mode 0.  The words are
+ *      relative to the programme's dialnorm: use it together with ac3mi_set_encode_metadata_source 1.  A call in this mode
+ *      takes the generic kernels, not the fixed-shape ones (ac3mi_set_fixed_shape).
+ * ac3mi_encode_batch has no source and is unchanged.  The drop-in and the byte-stream layer never follow.  Any other mode:
+ * AC3MI_ERR_ARG, and the setting is unchanged. */
+int ac3mi_set_encode_drc_source(ac3mi_ctx *ctx, int mode);
 
 /* Workspace bound (new; results do not depend on it, except for frames flagged AC3MI_STATUS_REUSE0 at a tile boundary).  ac3mi_decode_batch, ac3mi_encode_batch and ac3mi_transcode_batch keep
  * their intermediates (coefficient planes, MDCT coefficients, exponents, PCM between decoder and encoder: 37 / 60 /
