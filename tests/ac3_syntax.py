@@ -8,8 +8,12 @@ audblk) and the parametric bit allocation (§7.2), independently of the kernels 
 
 Rows: 0..4 the full-bandwidth channels, LFE = 5, CPL = 6.  The allocation tables come from the pinned fixture
 tests/golden/ac3tab.npz (the reference's ENC/ac3tab.h, frozen entry by entry).  One thing below is not in A/52: the
-half-sample-rate streams (bsid 9 / 10) follow liba52 (decays shifted right, hearing threshold indexed by band >> 1).  The reader does not decode mantissa values: it only counts their bits, grouped codes (bap 1, 2: three to a
-code, bap 4: two) shared over the channels of a block in coding order.
+half-sample-rate streams (bsid 9 / 10) follow liba52 (decays shifted right, hearing threshold indexed by band >> 1).
+parse_frame does not decode mantissa values: it only counts their bits, grouped codes (bap 1, 2: three to a code, bap 4:
+two) shared over the channels of a block in coding order.
+
+    read_mantissas(bytes, fr)      the mantissa codes of every block, bin by bin (A/52 7.3), and the unclaimed members of each
+                                   block's last groups; tests/mantissa_audit.py compares them with a quantiser model
 """
 import os
 
@@ -466,6 +470,88 @@ def parse_frame(data, check_size=True, nblocks=6):
         B.end = br.pos
         fr.blocks.append(B)
     return fr
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the mantissas
+
+SYM_LEVELS = {1: 3, 2: 5, 3: 7, 4: 11, 5: 15}                        # bap -> levels of the symmetric quantisers
+GROUPS = {1: (3, 3, 5), 2: (5, 3, 7), 4: (11, 2, 7)}                  # bap -> (levels, members of a group, bits of its code)
+
+
+class Mantissas:
+    """one block's mantissa codes, rows as in Block: `codes` [7][256], -1 where bap is 0 or the bin is not coded (a
+    member of a grouped code holds its own digit); `pos` [7][256] the first bit of the field that carries the bin's code
+    (a group's, for each of its members); `bad` [7][256] true where the code is no level of its quantiser (a group code
+    >= 27 / 125 / 121, or code 7 of bap 3, 15 of bap 5): reported, never to be compared; `unused` bap -> the digits of the
+    block's last group that no bin claimed."""
+
+    def __init__(self):
+        self.codes = np.full((7, 256), -1, np.int64)
+        self.pos = np.full((7, 256), -1, np.int64)
+        self.width = np.zeros((7, 256), np.int64)
+        self.bad = np.zeros((7, 256), bool)
+        self.unused = {1: [], 2: [], 4: []}
+
+
+def _fields(data, pos, width):
+    """the unsigned fields of `width` bits (0..16) that start at bits `pos` of the uint8 array `data`"""
+    d = np.concatenate([np.asarray(data, np.uint8), np.zeros(4, np.uint8)]).astype(np.int64)
+    k = pos >> 3
+    word = d[k] << 24 | d[k + 1] << 16 | d[k + 2] << 8 | d[k + 3]
+    return (word >> (32 - (pos & 7) - width)) & ((1 << width) - 1)
+
+
+def read_mantissas(frame, P):
+    """The mantissa codes of every block of `frame` (its bytes), whose parse P = parse_frame(frame) is.  A/52 5.4.3.61 and
+    7.3: from the end of a block's side information the rows follow in the order of Block.rng - channel order, the
+    coupling row after the first coupled channel, the LFE last - each with the codes of its coded bins in bin order.  bap 3
+    and bap 5 and up are fields of their own; bap 1, 2 and 4 are grouped, three, three and two to a code (5, 7, 7 bits:
+    g // 9, (g // 3) % 3, g % 3; g // 25, (g // 5) % 5, g % 5; g // 11, g % 11), the code standing where its first member
+    would and ONE pending group per bap shared by all rows of the block.  -> a list of Mantissas, one per block.  The walk
+    has to end exactly at Block.end."""
+    data = np.frombuffer(bytes(bytearray(frame)), np.uint8)
+    out = []
+    for blk, B in enumerate(P.blocks):
+        M = Mantissas()
+        rows = np.concatenate([np.full(hi - lo, r, np.int64) for r, (lo, hi) in B.rng.items()])
+        bins = np.concatenate([np.arange(lo, hi, dtype=np.int64) for lo, hi in B.rng.values()])
+        bap = B.bap[rows, bins].astype(np.int64)
+        width = _BITS[bap].copy()
+        member = {}
+        for b, (levels, per, bits) in GROUPS.items():
+            idx = np.nonzero(bap == b)[0]
+            member[b] = idx
+            width[idx[::per]] = bits
+        pos = B.start + B.side_bits + np.cumsum(width) - width
+        end = B.start + B.side_bits + int(width.sum())
+        if end != B.end or end > 8 * data.size:
+            raise SyntaxError_("block %d's mantissas end at bit %d, the block at %d" % (blk, end, B.end))
+        raw = _fields(data, pos, width)
+        code, bad = raw.copy(), np.zeros(raw.size, bool)
+        for b, levels in SYM_LEVELS.items():
+            if b not in GROUPS:
+                bad |= (bap == b) & (raw >= levels)
+        for b, (levels, per, bits) in GROUPS.items():
+            idx = member[b]
+            k = np.arange(idx.size)
+            first = idx[k - k % per]                                      # the bin that opens this member's group
+            g = raw[first]
+            digit = g // levels ** (per - 1 - k % per)
+            code[idx] = np.where(k % per == 0, digit, digit % levels)
+            bad[idx] = g >= levels ** per
+            pos[idx] = pos[first]
+            width[idx] = bits
+            if idx.size % per:
+                g = int(raw[idx[idx.size - idx.size % per]])
+                M.unused[b] = [g // levels ** (per - 1 - j) % levels for j in range(idx.size % per, per)]
+        coded = bap > 0
+        M.codes[rows[coded], bins[coded]] = code[coded]
+        M.pos[rows[coded], bins[coded]] = pos[coded]
+        M.width[rows[coded], bins[coded]] = width[coded]
+        M.bad[rows[coded], bins[coded]] = bad[coded]
+        out.append(M)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """The packer's single-form mantissa quantiser (csrc/enc_mant.h: mant_quant_lut over the table entries mant_pack_entry builds)
-against the encoder's two quantisers (ac3enc.cpp:1150-1190, restated below as enc_mant.h documents them), in numpy and
+against the encoder's two quantisers (ac3enc.cpp:1150-1190, restated in tests/quantiser_model.py as enc_mant.h documents them), in numpy and
 without a GPU.  `quant_words` restates mant_pack_entry's arithmetic by hand: this pins the algebra, not the C table - a wrong
 entry in mant_pack_entry is caught by the GPU parity tests (test_packer_quantiser_gpu.py, test_packer_golden_gpu.py,
 test_encode_gpu.py), not here.
@@ -11,29 +11,7 @@ This pins that algebra for every level count and every width, every e and a dens
 import numpy as np
 import pytest
 
-SYM_LEVELS = {1: 3, 2: 5, 3: 7, 4: 11, 5: 15}               # bap -> levels of the symmetric quantiser
-ASYM_BITS = {b: b - 1 for b in range(6, 14)}
-ASYM_BITS.update({14: 14, 15: 16})                            # bap -> width of the asymmetric quantiser
-
-
-def sym_quant(c, e, levels):
-    """ac3enc.cpp:1150-1166, 32-bit arithmetic (int64 here: in contract nothing wraps)."""
-    c = c.astype(np.int64)
-    a = np.abs(c) << e
-    v = ((levels * a) >> 24) + 1 >> 1
-    return np.where(c >= 0, (levels >> 1) + v, (levels >> 1) - v)
-
-
-def asym_quant(c, e, qbits):
-    """ac3enc.cpp:1169-1190."""
-    c = c.astype(np.int64)
-    lshift = e + qbits - 24
-    v = (c << lshift) if lshift >= 0 else (c >> -lshift)
-    v = (v + 1) >> 1
-    m = 1 << (qbits - 1)
-    v = np.minimum(v, m - 1)
-    assert (v >= -m).all()
-    return v & ((1 << qbits) - 1)
+from tests.quantiser_model import ASYM_BITS, SYM_LEVELS, asym_quant, sym_quant
 
 
 def quant_words(bap):
