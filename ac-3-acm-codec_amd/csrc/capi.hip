@@ -960,6 +960,14 @@ size_t ac3mi_workspace_bytes(const ac3mi_ctx *ctx)
     return n;
 }
 
+int ac3mi_fill_workspaces(ac3mi_ctx *ctx, int byte)
+{
+    if (!ctx || byte < 0 || byte > 255) return AC3MI_ERR_ARG;
+    for (const DevBuf *b : ac3mi_ctx::workspaces(ctx))
+        if (b->bytes) HIPCHK(ctx, hipMemsetAsync(b->p, byte, b->bytes, ctx->stream));
+    return AC3MI_OK;
+}
+
 // one workgroup per stream (decode_wg.hip)?  Its eight wavefronts cut the latency of a frame to a third and nothing but the
 // frame and the PCM touches HBM, but a workgroup's wavefronts wait for each other at the block's barriers, so the chip holds
 // fewer busy wavefronts than the other front ends.  Measured on one-frame streams to s16 (round 3, profiles/decode_ab.py;

@@ -271,6 +271,11 @@ class Engine:
         self.lib.ac3mi_workspace_bytes.restype = ctypes.c_size_t
         return int(self.lib.ac3mi_workspace_bytes(ctypes.c_void_p(self.ctx)))
 
+    def fill_workspaces(self, byte):
+        """Test aid: fills every workspace the context holds right now with `byte` (0..255) on the engine's stream
+        (ac3mi_fill_workspaces); a call's results must not depend on it."""
+        self._check(self.lib.ac3mi_fill_workspaces(ctypes.c_void_p(self.ctx), int(byte)))
+
     def set_tile_frames(self, frames):
         """Workspace bound: batches above `frames` frames go through in tiles of whole streams (ac3mi_set_tile_frames)."""
         self._check(self.lib.ac3mi_set_tile_frames(ctypes.c_void_p(self.ctx), int(frames)))

@@ -170,6 +170,14 @@ int ac3mi_set_decode_mode(ac3mi_ctx *ctx, int mode);
  * way (tests/test_fixed_shape_gpu.py).  on = 1 (default): that rule; 0: always the generic kernels (A/B runs, tests). */
 int ac3mi_set_fixed_shape(ac3mi_ctx *ctx, int on);
 
+/* A test aid (new): fills every device workspace the context holds right now, over its whole extent, with `byte` (0..255),
+ * asynchronously on the context's stream - nothing else: no state is set, no launch changes, a context that is never asked
+ * pays nothing.  The workspaces come from hipMalloc, are never cleared and are reused by every call whatever its shape; every
+ * byte a batch call returns, and all state it hands back, must be a function of its arguments and the context's settings
+ * alone, so the same call after fills with different bytes must return the same bytes
+ * (tests/test_workspace_independence_gpu.py).  AC3MI_ERR_ARG: null context, byte outside 0..255. */
+int ac3mi_fill_workspaces(ac3mi_ctx *ctx, int byte);
+
 /* CRC verification of the frames ac3mi_decode_batch / ac3mi_decode_s16_batch / ac3mi_transcode_batch read (new; applies to
  * every following such call on `ctx`, under every ac3mi_set_decode_mode, with or without state slots, mix state, taps and
  * tiling).  liba52 never looks at a frame's two CRC words, so a frame damaged in its mantissas parses without a block error,

@@ -324,6 +324,49 @@ def orc_decode(frames, flags=7 | 16, level=1.0, bias=0.0, dynrng_off=False):
     return _decode_stream(orc(), "orc_a52_", frames, flags, level, bias, dynrng_off)
 
 
+def orc_decode_status(frames, flags, bias=0.0):
+    """the restatement on [S][F][fb], a fresh decoder per stream -> (status bits 0-5 and 8 per frame, pcm [S][F][6][n_out][256],
+    per stream the number of leading frames it decoded whole).  A frame is refused by a52_syncinfo (as the drivers call it
+    ahead of a52_frame), for a size above the batch's or a layout other than the batch's (stream 0's), or by a52_frame.  After
+    a frame it refuses or a block that fails, liba52's caller decides what the overlap tails become, so a stream's PCM is
+    compared up to there only."""
+    L = orc()
+    S, F, fb = frames.shape
+    layout = None
+    status = np.zeros((S, F), np.uint32)
+    whole = np.zeros(S, np.int64)
+    pcm = None
+    for s in range(S):
+        st = L.orc_a52_init()
+        ok = True
+        for f in range(F):
+            buf = np.zeros(fb + 64, np.uint8)
+            buf[:fb] = frames[s, f]
+            fl, lv = ci(flags), cf(1.0)
+            sf, sr, br = ci(), ci(), ci()
+            n = L.orc_a52_syncinfo(P(buf, u8p), ctypes.byref(sf), ctypes.byref(sr), ctypes.byref(br))
+            if layout is None:
+                assert n == fb and (s, f) == (0, 0)
+                layout = sf.value & 0x1f
+            if n == 0 or n > fb or (sf.value & 0x1f) != layout or L.orc_a52_frame(st, P(buf, u8p), ctypes.byref(fl), ctypes.byref(lv), bias):
+                status[s, f] = 0x13f
+                ok = False
+                continue
+            n_out = NFCHANS[fl.value & 15] + (1 if fl.value & 16 else 0)
+            if pcm is None:
+                pcm = np.zeros((S, F, 6, n_out, 256), np.float32)
+            for b in range(6):
+                if L.orc_a52_block(st):
+                    status[s, f] = (0x3f << b) & 0x3f
+                    ok = False
+                    break
+                if ok:
+                    pcm[s, f, b] = np.ctypeslib.as_array(L.orc_a52_samples(st), (1536,))[:n_out * 256].reshape(n_out, 256)
+            whole[s] += ok
+        L.orc_a52_free(st)
+    return status, pcm, whole
+
+
 def ref_decode(frames, flags=7 | 16, level=1.0, bias=0.0, dynrng_off=False):
     return _decode_stream(ref(), "a52_", frames, flags, level, bias, dynrng_off)
 

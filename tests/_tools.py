@@ -35,10 +35,11 @@ TOOLS = {"layout": ("set_encode_layout", KEEP, (0,)),
          "drc": ("set_encode_drc", 0, (0,))}                # the profile; its state is `state`
 
 
-def encode(engine, pcm, *, rate=None, sr=48000, chmap=None, last=None, csnr=None, state=None, taps=False, **tools):
+def encode(engine, pcm, *, rate=None, sr=48000, chmap=None, last=None, csnr=None, state=None, taps=False, out=None, **tools):
     """pcm [S][F*1536][nch] s16 -> frames [S][F][fb][, taps], one call.  `tools`: layout=(mode, acmod, lfeon), pack, bsw,
     remat, cpl=(mode, begf), bw=(mode, chbwcod), xs, md=dict, drc (with `state`, int32 [S] on the device, zeros when None).
-    Every tool not given is set to its default (layout and pack: kept); everything set is reset afterwards."""
+    Every tool not given is set to its default (layout and pack: kept); everything set is reset afterwards.  `out`: the
+    output tensor [S][F][stride] u8 (Engine.encode_batch), whatever it holds."""
     import torch
     unknown = set(tools) - set(TOOLS)
     if unknown:
@@ -66,7 +67,7 @@ def encode(engine, pcm, *, rate=None, sr=48000, chmap=None, last=None, csnr=None
             else:
                 setter(*(v if isinstance(v, tuple) else (v,)))
         r = engine.encode_batch(enc, torch.from_numpy(np.ascontiguousarray(pcm, np.int16).reshape(S, F, 1536, nch)).cuda(),
-                                chmap if chmap is not None else chmap_of(nch), last, csnr, taps=taps)
+                                chmap if chmap is not None else chmap_of(nch), last, csnr, out=out, taps=taps)
         engine.sync()
     finally:
         for k, v in want.items():

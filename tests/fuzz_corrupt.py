@@ -81,8 +81,10 @@ def make_damaged(seed, acmod, lfe, S=96, fscod=0, bsid=8, frmsizecod=30, base_st
     return frames, want_coef, want_fail, want_foreign, want_lfsr
 
 
-def damaged_round(eng, seed, acmod, lfe, **kw):
-    """One batch on the GPU.  Returns (n_mismatching_frames, n_failed_frames, n_foreign_frames)."""
+def damaged_round(eng, seed, acmod, lfe, fill=None, **kw):
+    """One batch on the GPU.  Returns (n_mismatching_frames, n_failed_frames, n_foreign_frames).  fill (0..255): the context's
+    workspaces are filled with that byte right before the call (ac3mi_fill_workspaces), so that a round run under one front
+    end after another does not find the previous variant's rows and descriptors where its own parse kernel wrote none."""
     import torch
     pkg = H.pkg()
     frames, want_coef, want_fail, want_foreign, want_lfsr = make_damaged(seed, acmod, lfe, **kw)
@@ -96,6 +98,8 @@ def damaged_round(eng, seed, acmod, lfe, **kw):
     n_out, _ = eng.decode_planes(desc)
     delay = torch.zeros((S, n_out, 128), dtype=torch.float32, device="cuda")
     lfsr = torch.ones((S,), dtype=torch.int16, device="cuda")
+    if fill is not None:
+        eng.fill_workspaces(fill)
     pcm, status, taps = eng.decode_batch(desc, torch.from_numpy(padded).cuda(), delay, lfsr, taps=True)
     eng.sync()
     status = status.cpu().numpy()[:, 0]
@@ -137,7 +141,8 @@ def main():
         fscod, bsid = int(rng.integers(0, 3)), int(rng.choice([8, 8, 9, 10]))
         fsz = int(rng.integers(24, 38))
         try:
-            bad, failed, foreign = damaged_round(eng, seed0 * 7919 + r, acmod, lfe, fscod=fscod, bsid=bsid, frmsizecod=fsz)
+            bad, failed, foreign = damaged_round(eng, seed0 * 7919 + r, acmod, lfe, fill=(0x00, 0xff, 0xa5)[r % 3], fscod=fscod, bsid=bsid,
+                                                 frmsizecod=fsz)
         except RuntimeError as e:                        # the packer could not fit a frame at this size
             print("round %d skipped: %s" % (r, e))
             continue

@@ -49,6 +49,14 @@ def test_no_cpu_fallback_without_gpu():
         pkg.Engine(0)
 
 
+def test_fill_workspaces_refuses_a_null_context():
+    """ac3mi_fill_workspaces, the test aid of tests/test_workspace_independence_gpu.py: AC3MI_ERR_ARG without a context,
+    whatever the byte (no GPU needed to say so)"""
+    lib = H.pkg().load_library()
+    for byte in (0, 0xa5, 255, -1, 256):
+        assert lib.ac3mi_fill_workspaces(None, byte) == -1
+
+
 def test_host_side_syncinfo_matches_oracle():
     """ac3mi_syncinfo is a52_syncinfo (parse.c:86-129): pure host logic, testable without a GPU."""
     import numpy as np

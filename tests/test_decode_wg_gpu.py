@@ -137,7 +137,7 @@ def test_wg_packer_streams(wg_engine, acmod, lfe, fscod, bsid, fsz):
 @pytest.mark.parametrize("seed,acmod,lfe", [(3, 7, 1), (4, 2, 0), (5, 5, 1), (6, 3, 0)])
 def test_wg_damaged_frames_match_liba52_block_by_block(wg_engine, seed, acmod, lfe):
     from tests import fuzz_corrupt
-    bad, failed, foreign = fuzz_corrupt.damaged_round(wg_engine, seed, acmod, lfe)
+    bad, failed, foreign = fuzz_corrupt.damaged_round(wg_engine, seed, acmod, lfe, fill=(0x00, 0xff, 0xa5)[seed % 3])
     assert bad == 0 and failed > 0
 
 
@@ -184,8 +184,9 @@ def test_status_flags_frames_whose_block_0_reuses_unsent_state(wg_engine):
     padded[:, 0, :fb] = frames
     desc = pkg.DecodeDesc(flags=7 | 16, level=1.0, bias=0.0, dynrng=1, acmod=acmod, lfeon=lfe, frame_bytes=fb)
     res = {}
-    for mode in (1, 3, 4):
+    for mode, fill in ((1, 0x00), (3, 0xff), (4, 0xa5)):
         wg_engine.set_decode_mode(mode)
+        wg_engine.fill_workspaces(fill)                      # no variant runs on the rows and descriptors of the one before it
         delay = torch.zeros((S, 6, 128), dtype=torch.float32, device="cuda")
         lfsr = torch.ones((S,), dtype=torch.int16, device="cuda")
         pcm, status, taps = wg_engine.decode_batch(desc, torch.from_numpy(padded).cuda(), delay, lfsr, taps=True)
