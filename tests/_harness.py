@@ -324,9 +324,11 @@ def orc_decode(frames, flags=7 | 16, level=1.0, bias=0.0, dynrng_off=False):
     return _decode_stream(orc(), "orc_a52_", frames, flags, level, bias, dynrng_off)
 
 
-def orc_decode_status(frames, flags, bias=0.0):
+def orc_decode_status(frames, flags, bias=0.0, level=1.0, dynrng_off=False, state=None):
     """the restatement on [S][F][fb], a fresh decoder per stream -> (status bits 0-5 and 8 per frame, pcm [S][F][6][n_out][256],
-    per stream the number of leading frames it decoded whole).  A frame is refused by a52_syncinfo (as the drivers call it
+    per stream the number of leading frames it decoded whole).  level: a52_frame's; dynrng_off: a52_dynrng(state, NULL, NULL)
+    after every a52_frame, as the drivers call it; state = (delay [S][n_out][128], lfsr [S]): what each stream's overlap planes
+    (one per output plane, for requests without a downmix) and dither generator hold at its start, instead of zeros and 1.  A frame is refused by a52_syncinfo (as the drivers call it
     ahead of a52_frame), for a size above the batch's or a layout other than the batch's (stream 0's), or by a52_frame.  After
     a frame it refuses or a block that fails, liba52's caller decides what the overlap tails become, so a stream's PCM is
     compared up to there only."""
@@ -338,20 +340,29 @@ def orc_decode_status(frames, flags, bias=0.0):
     pcm = None
     for s in range(S):
         st = L.orc_a52_init()
+        if state is not None:
+            planes = np.ctypeslib.as_array(L.orc_a52_samples(st), (3072,))[1536:].reshape(6, 256)
+            planes[:state[0].shape[1], :128] = state[0][s]
+            L.orc_a52_set_lfsr(st, int(state[1][s]) & 0xffff)
         ok = True
         for f in range(F):
             buf = np.zeros(fb + 64, np.uint8)
             buf[:fb] = frames[s, f]
-            fl, lv = ci(flags), cf(1.0)
+            fl, lv = ci(flags), cf(level)
             sf, sr, br = ci(), ci(), ci()
             n = L.orc_a52_syncinfo(P(buf, u8p), ctypes.byref(sf), ctypes.byref(sr), ctypes.byref(br))
+            coded = sf.value & 0x1f
+            if coded & 15 == 10:                   # a 2/0 frame whose dsurmod says Dolby Surround: the same coded layout
+                coded ^= 8
             if layout is None:
                 assert n == fb and (s, f) == (0, 0)
-                layout = sf.value & 0x1f
-            if n == 0 or n > fb or (sf.value & 0x1f) != layout or L.orc_a52_frame(st, P(buf, u8p), ctypes.byref(fl), ctypes.byref(lv), bias):
+                layout = coded
+            if n == 0 or n > fb or coded != layout or L.orc_a52_frame(st, P(buf, u8p), ctypes.byref(fl), ctypes.byref(lv), bias):
                 status[s, f] = 0x13f
                 ok = False
                 continue
+            if dynrng_off:
+                L.orc_a52_dynrng(st, None, None)
             n_out = NFCHANS[fl.value & 15] + (1 if fl.value & 16 else 0)
             if pcm is None:
                 pcm = np.zeros((S, F, 6, n_out, 256), np.float32)

@@ -44,6 +44,7 @@ from tests import dynrng_model as D
 from tests import mantissa_audit as MA
 from tests import packer
 from tests import test_frame_budget_gpu as B
+from tests._decode_matrix import held_to_liba52 as _held_to_liba52, same      # (shared with tests/test_decode_matrix_gpu.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -139,17 +140,6 @@ def prime_large(engine, S, F, what):
         engine.sync()
     finally:
         _restore(engine)
-
-
-def same(a, b, what):
-    assert a.keys() == b.keys()
-    for k in a:
-        x, y = a[k], b[k]
-        assert x.shape == y.shape and x.dtype == y.dtype, (what, k)
-        if x.tobytes() != y.tobytes():
-            d = np.argwhere(x.view(np.uint8).reshape(x.shape[0], -1) != y.view(np.uint8).reshape(y.shape[0], -1))
-            raise AssertionError("%s: `%s` differs in %d bytes of %d rows, first (row, byte) %r" % (
-                what, k, len(d), len(set(d[:, 0].tolist())), d[:6].tolist()))
 
 
 def four_runs(engine, call, configure=None, primer=prime):
@@ -297,40 +287,6 @@ def _decode_reference(key, frames, flags, bias=0.0):
     if (key, flags, bias) not in _REF:
         _REF[(key, flags, bias)] = _liba52(frames, flags, bias)
     return _REF[(key, flags, bias)]
-
-
-def _held_to_liba52(got, ref, first_bad, s16=False):
-    """status bits 0-5 and 8 of every frame; PCM of every stream's frames before its damaged one (first_bad[s]; F: none).  A
-    damaged frame's PCM is compared among the engine's runs only: where damage leaves bins that liba52 never writes, its
-    buffers' contents are no reference (tests/fuzz_corrupt.py blanks them)."""
-    want_status, want_pcm, whole = ref
-    assert np.array_equal(got["status"].astype(np.uint32) & 0x13f, want_status), (got["status"] & 0x13f, want_status)
-    assert (whole >= first_bad).all(), (whole, first_bad)
-    L = H.orc()
-    for s in range(got["pcm"].shape[0]):
-        n = int(first_bad[s])
-        if not n:
-            continue
-        g = got["pcm"][s, :n]
-        w = want_pcm[s, :n]
-        if s16:
-            # the reference's converter on the restatement's planes at bias 384.  One float32 ulp there is one s16 step, so one
-            # step is the floor (as in tests/test_decode_wg_gpu.py); above it the bound is the float path's, 1e-5 of the level
-            # where packer mantissas at random exponents reach above +-1.0 (samples that cancel out of such planes carry the
-            # rounding of the large terms), in steps - and 4e-5 RMS of the level, the project's figure at bias 384
-            oflags = int(got["status"][s, 0] >> 16) & 0xff
-            w16 = np.zeros(g.shape, np.int16)
-            for f in range(n):
-                for b in range(6):
-                    L.orc_convert_s16(H.P(np.ascontiguousarray(w[f, b]), H.fp), H.P(w16[f, b], H.i16p), oflags)
-            err = g.astype(np.float64) - w16
-            level_max, level_rms = max(1.0, float(np.abs(w - 384.0).max())), max(1.0, H.rms(w - 384.0))
-            steps = max(1, int(np.ceil(1e-5 * level_max * 32768.0)))
-            assert np.abs(err).max() <= steps and H.rms(err) <= 4e-5 * level_rms * 32768.0, (s, np.abs(err).max(), steps, H.rms(err), level_rms)
-        else:
-            # (packer mantissas at random exponents reach far above +-1.0: the bar is relative to full scale or to the level)
-            err = g.astype(np.float64) - w
-            assert H.rms(err) <= 1e-6 * max(1.0, H.rms(w)), (s, H.rms(err), H.rms(w))
 
 
 DECODE_MODES = (1, 3, 4, 5, 6, 0)
