@@ -57,6 +57,34 @@ def bsi_info_dtype():
     return dt
 
 
+class FrameRefC(ctypes.Structure):
+    """ac3mi_frame_ref"""
+    _fields_ = [("offset", ctypes.c_uint32), ("bytes", ctypes.c_uint16), ("sizecod", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
+
+
+class ScanInfoC(ctypes.Structure):
+    """ac3mi_scan_info"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("n_frames", "consumed", "skipped", "rejected", "flags", "reserved")]
+
+
+def _struct_dtype(cls, size):
+    import numpy as np
+    t = {ctypes.c_uint8: "u1", ctypes.c_uint16: "<u2", ctypes.c_uint32: "<u4"}
+    dt = np.dtype([(k, t[c]) for k, c in cls._fields_])
+    assert dt.itemsize == ctypes.sizeof(cls) == size
+    return dt
+
+
+def frame_ref_dtype():
+    """ac3mi_frame_ref as a numpy structured dtype (8 bytes; a uint8 tensor [..., 8] views as it)"""
+    return _struct_dtype(FrameRefC, 8)
+
+
+def scan_info_dtype():
+    """ac3mi_scan_info as a numpy structured dtype (24 bytes; a uint8 tensor [..., 24] views as it)"""
+    return _struct_dtype(ScanInfoC, 24)
+
+
 _lib = None
 
 
@@ -118,6 +146,10 @@ def load_library():
     lib.ac3mi_set_encode_metadata_source.argtypes = [c_void_p, c_int]
     lib.ac3mi_bsi_read.argtypes = [c_void_p, c_int, ctypes.POINTER(BsiInfoC)]
     lib.ac3mi_bsi_read_batch.argtypes = [c_void_p, c_void_p, c_int, c_int, c_size_t, c_void_p]
+    lib.ac3mi_frame_scan.argtypes = [c_void_p, c_size_t, c_int, c_int, ctypes.POINTER(FrameRefC), ctypes.POINTER(ScanInfoC)]
+    lib.ac3mi_frame_scan_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+    lib.ac3mi_frame_gather_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                             c_void_p, c_int, c_int]
     lib.ac3mi_set_encode_drc.argtypes = [c_void_p, c_int, c_void_p]
     lib.ac3mi_set_encode_dynrng_frames.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.ac3mi_set_encode_drc_source.argtypes = [c_void_p, c_int]

@@ -240,6 +240,35 @@ struct DynSrcLaunch {
 hipError_t launch_dynrng_source(const DynSrcLaunch &L, hipStream_t stream);
 void bsi_read_host(const uint8_t *buf, int len, ac3mi_bsi_info *out);
 
+// scan.hip: frames found in byte streams (ac3mi_frame_scan_batch).  One wavefront per stream walks bytes [0, len[s]) of
+// bytes + s * stride by the rule of include/ac3mi.h (mode 1: a candidate counts only if both CRC regions sum to 0) and
+// lists up to max_frames frames in refs[s][max_frames] and the walk's end in info[s].  bytes and stride: multiples of 16,
+// stride < 2^32; entries of refs at or behind n_frames are not written
+struct ScanLaunch {
+    const uint8_t *bytes;
+    uint64_t stride;
+    const uint32_t *len;
+    size_t n_streams;
+    int mode, max_frames;
+    ac3mi_frame_ref *refs;
+    ac3mi_scan_info *info;
+};
+hipError_t launch_frame_scan(const ScanLaunch &L, hipStream_t stream);
+// ... and laid out for the batched calls (ac3mi_frame_gather_batch): one wavefront per slot copies frame first_frame + f of
+// stream s to frames + (s * frames_per_stream + f) * frame_stride and zeroes the rest of the slot; a slot without a frame, or
+// whose frame is longer than frame_bytes, is all zeros.  bytes, stride, frames, frame_stride: multiples of 4
+struct GatherLaunch {
+    const uint8_t *bytes;
+    uint64_t stride;
+    size_t n_streams;
+    const ac3mi_frame_ref *refs;
+    const ac3mi_scan_info *info;
+    int max_frames, first_frame, frames_per_stream;
+    uint8_t *frames;
+    int frame_stride, frame_bytes;
+};
+hipError_t launch_frame_gather(const GatherLaunch &L, hipStream_t stream);
+
 // The shape large batches run at - 5.1: acmod 7 with the LFE, six planes in and out, five full-bandwidth channels.  The one
 // predicate behind every kernel variant that has it compiled in (ac3mi_set_fixed_shape): a launcher adds its own conditions -
 // one frame per stream, its stage's tools and taps off - and anything else takes the generic kernels.

@@ -1312,6 +1312,62 @@ int ac3mi_bsi_read_batch(ac3mi_ctx *ctx, const uint8_t *d_frames, int frame_stri
     return AC3MI_OK;
 }
 
+// (ac3mi_frame_scan, the host twin, lives in scan.hip beside the rule it shares with the kernel)
+int ac3mi_frame_scan_batch(ac3mi_ctx *ctx, const uint8_t *d_bytes, size_t stream_stride, const uint32_t *d_len, int n_streams,
+                           int mode, int max_frames, ac3mi_frame_ref *d_refs, ac3mi_scan_info *d_info)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (!d_bytes || !d_len || !d_refs || !d_info || n_streams < 0 || (mode != 0 && mode != 1) || max_frames < 1 ||
+        (uint64_t)stream_stride > 0xffffffffull || (stream_stride & 15) || ((uintptr_t)d_bytes & 15) || ((uintptr_t)d_len & 3) ||
+        ((uintptr_t)d_refs & 3) || ((uintptr_t)d_info & 3)) {
+        ctx->err = "ac3mi_frame_scan_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    if (n_streams == 0) return AC3MI_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ScanLaunch S;
+    S.bytes = d_bytes;
+    S.stride = stream_stride;
+    S.len = d_len;
+    S.n_streams = (size_t)n_streams;
+    S.mode = mode;
+    S.max_frames = max_frames;
+    S.refs = d_refs;
+    S.info = d_info;
+    HIPCHK(ctx, launch_frame_scan(S, ctx->stream));
+    return AC3MI_OK;
+}
+
+int ac3mi_frame_gather_batch(ac3mi_ctx *ctx, const uint8_t *d_bytes, size_t stream_stride, int n_streams,
+                             const ac3mi_frame_ref *d_refs, const ac3mi_scan_info *d_info, int max_frames, int first_frame,
+                             int frames_per_stream, uint8_t *d_frames, int frame_stride, int frame_bytes)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (!d_bytes || !d_refs || !d_info || !d_frames || n_streams < 0 || max_frames < 1 || first_frame < 0 || frames_per_stream < 1 ||
+        (uint64_t)n_streams * (uint64_t)frames_per_stream > 0x7fffffffu || (uint64_t)stream_stride > 0xffffffffull || (stream_stride & 3) ||
+        ((uintptr_t)d_bytes & 3) || ((uintptr_t)d_refs & 3) || ((uintptr_t)d_info & 3) || frame_bytes < 8 || frame_bytes > 3840 ||
+        frame_stride < ((frame_bytes + 3) & ~3) || (frame_stride & 3) || ((uintptr_t)d_frames & 3)) {
+        ctx->err = "ac3mi_frame_gather_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    if (n_streams == 0) return AC3MI_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    GatherLaunch G;
+    G.bytes = d_bytes;
+    G.stride = stream_stride;
+    G.n_streams = (size_t)n_streams;
+    G.refs = d_refs;
+    G.info = d_info;
+    G.max_frames = max_frames;
+    G.first_frame = first_frame;
+    G.frames_per_stream = frames_per_stream;
+    G.frames = d_frames;
+    G.frame_stride = frame_stride;
+    G.frame_bytes = frame_bytes;
+    HIPCHK(ctx, launch_frame_gather(G, ctx->stream));
+    return AC3MI_OK;
+}
+
 int ac3mi_decode_planes(const ac3mi_decode_desc *desc, int *n_out, int *out_flags)
 {
     if (!desc || desc->acmod < 0 || desc->acmod > 7) return AC3MI_ERR_ARG;

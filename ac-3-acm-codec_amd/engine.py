@@ -73,6 +73,24 @@ def bsi_read(buf):
     return np.frombuffer(bytes(info), capi.bsi_info_dtype())[0]
 
 
+def frame_scan(buf, mode=0, max_frames=None):
+    """ac3mi_frame_scan on host bytes: the frames of a byte stream by the reference's resync rule (mode 1: a candidate counts
+    only if both of its CRC regions check) -> (refs, info): numpy records of capi.frame_ref_dtype() [n_frames] and one of
+    capi.scan_info_dtype().  max_frames: room in the list, default every frame the bytes can hold."""
+    import numpy as np
+    lib = capi.load_library()
+    data = bytes(bytearray(buf))
+    if max_frames is None:
+        max_frames = len(data) // 128 + 1
+    b = (ctypes.c_uint8 * max(1, len(data))).from_buffer_copy(data or b"\0")
+    refs = (capi.FrameRefC * max(1, int(max_frames)))()
+    info = capi.ScanInfoC()
+    if lib.ac3mi_frame_scan(b, len(data), int(mode), int(max_frames), refs, ctypes.byref(info)) != 0:
+        raise capi.AC3MIError("ac3mi_frame_scan: bad argument")
+    out = np.frombuffer(bytes(info), capi.scan_info_dtype())[0]
+    return np.frombuffer(bytes(refs), capi.frame_ref_dtype())[:int(out["n_frames"])].copy(), out
+
+
 def encode_metadata_word(**fields):
     """ac3mi_encode_metadata_word: the fields of Engine.set_encode_metadata (those not given: the defaults) -> the packed
     word; raises on a field out of range."""
@@ -392,6 +410,52 @@ class Engine:
                                                   int(stride if frame_bytes is None else frame_bytes), ctypes.c_size_t(n),
                                                   ctypes.c_void_p(out.data_ptr())))
         self._keep.append((frames, out))
+        return out
+
+    def frame_scan_batch(self, streams, lens, mode=0, max_frames=16, refs=None, info=None, wait_torch=True):
+        """ac3mi_frame_scan_batch: streams [S][stride] u8 on the device (stride a multiple of 16, base 16-byte aligned), lens
+        int32 / uint32 [S] on the device (stream s is streams[s, :lens[s]]) -> (refs u8 [S][max_frames][8], info u8 [S][24]);
+        `.cpu().numpy().view(capi.frame_ref_dtype())[..., 0]` and `.view(capi.scan_info_dtype())[..., 0]` name the fields.
+        Entries of refs at or behind a stream's n_frames keep what they held (zeros in a tensor allocated here)."""
+        import torch
+        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.is_cuda and streams.dim() == 2
+        S, stride = streams.shape
+        assert lens.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and lens.is_contiguous() and lens.is_cuda and lens.numel() == S
+        if refs is None:
+            refs = torch.zeros((S, int(max_frames), 8), dtype=torch.uint8, device=streams.device)
+        if info is None:
+            info = torch.zeros((S, 24), dtype=torch.uint8, device=streams.device)
+        assert refs.dtype == torch.uint8 and refs.is_contiguous() and refs.numel() == S * int(max_frames) * 8
+        assert info.dtype == torch.uint8 and info.is_contiguous() and info.numel() == S * 24
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_frame_scan_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(streams.data_ptr()), ctypes.c_size_t(stride),
+                                                    ctypes.c_void_p(lens.data_ptr()), int(S), int(mode), int(max_frames),
+                                                    ctypes.c_void_p(refs.data_ptr()), ctypes.c_void_p(info.data_ptr())))
+        self._keep.append((streams, lens, refs, info))
+        return refs, info
+
+    def frame_gather_batch(self, streams, refs, info, frames_per_stream, frame_bytes, first_frame=0, frame_stride=None, out=None,
+                           wait_torch=True):
+        """ac3mi_frame_gather_batch: the frames first_frame .. first_frame + frames_per_stream - 1 of every stream of a
+        frame_scan_batch (its streams [S][stride], refs and info) -> frames u8 [S][frames_per_stream][frame_stride] (default:
+        frame_bytes rounded up to 16), as decode_batch / decode_s16_batch / transcode_batch take them; a slot without a frame,
+        or whose frame is longer than frame_bytes, is all zeros."""
+        import torch
+        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.is_cuda and streams.dim() == 2
+        S, stride = streams.shape
+        assert refs.dtype == torch.uint8 and refs.is_contiguous() and refs.dim() == 3 and refs.shape[0] == S and refs.shape[2] == 8
+        assert info.dtype == torch.uint8 and info.is_contiguous() and info.numel() == S * 24
+        if frame_stride is None:
+            frame_stride = (int(frame_bytes) + 15) & ~15
+        if out is None:
+            out = torch.empty((S, int(frames_per_stream), int(frame_stride)), dtype=torch.uint8, device=streams.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == S * int(frames_per_stream) * int(frame_stride)
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_frame_gather_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(streams.data_ptr()), ctypes.c_size_t(stride),
+                                                      int(S), ctypes.c_void_p(refs.data_ptr()), ctypes.c_void_p(info.data_ptr()),
+                                                      int(refs.shape[1]), int(first_frame), int(frames_per_stream),
+                                                      ctypes.c_void_p(out.data_ptr()), int(frame_stride), int(frame_bytes)))
+        self._keep.append((streams, refs, info, out))
         return out
 
     def set_encode_drc(self, profile, state=None):

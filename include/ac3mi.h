@@ -263,6 +263,59 @@ int ac3mi_bsi_read(const uint8_t *buf, int len, ac3mi_bsi_info *out);
 int ac3mi_bsi_read_batch(ac3mi_ctx *ctx, const uint8_t *d_frames, int frame_stride, int frame_bytes, size_t n_frames,
                          ac3mi_bsi_info *d_info);
 
+/* Frames found in byte streams (new): the way from the bytes of elementary streams that lie in device memory - capture
+ * buffers, demultiplexer output, a file read once - to the batched calls above and below, which take frames somebody has found
+ * and laid out at a fixed stride.  The rule is the resync rule of the ACM codec's stream_convert_ac3 (src/AC3ACM.cpp:1430-1628,
+ * the one ac3mi_stream_convert applies on the host, a byte at a time):
+ *     p = 0
+ *     while p + 8 <= len and fewer than max_frames frames are listed:
+ *         fs = ac3mi_syncinfo's frame size of bytes p .. p + 5 (sync word, bsid byte < 0x60, frmsizecod < 38, fscod != 3), 0: none
+ *         if fs:
+ *             if p + fs > len: stop                              (AC3MI_SCAN_INCOMPLETE)
+ *             if mode == 0, or both CRC regions of [p, p + fs) sum to 0 (the rule of ac3mi_set_decode_crc):
+ *                 list (p, fs); p += fs; continue
+ *             rejected += 1                                      (mode 1 only)
+ *         p += 1; skipped += 1
+ *     consumed = p
+ * mode 0 is the reference's behaviour: a sync word in the payload of garbage is taken for a frame, and the bytes it claims
+ * are lost with whatever true frame began in them.  mode 1 accepts a candidate only if crc1's and crc2's regions both check,
+ * so a false sync word is rejected and the walk goes on one byte behind it.
+ *   consumed   where the walk stopped.  A caller that keeps bytes [consumed, len) and puts them in front of the next chunk
+ *              of the stream gets exactly the frames of the unchunked stream, in either mode.
+ *              consumed == skipped + the bytes of the listed frames, always.
+ *   flags      AC3MI_SCAN_CAPPED: max_frames frames are listed and bytes the walk would still test follow (scan again from
+ *              consumed); AC3MI_SCAN_INCOMPLETE: the walk stopped at a header whose frame runs past len.
+ *   a frame's sizecod is its byte 4 (fscod << 6 | frmsizecod).  Frames are 128..3840 bytes. */
+typedef struct { uint32_t offset; uint16_t bytes; uint8_t sizecod; uint8_t reserved; } ac3mi_frame_ref;     /* 8 bytes; reserved: 0 */
+typedef struct { uint32_t n_frames, consumed, skipped, rejected, flags, reserved; } ac3mi_scan_info;       /* 24 bytes; reserved: 0 */
+#define AC3MI_SCAN_CAPPED 1         /* stopped because max_frames were listed */
+#define AC3MI_SCAN_INCOMPLETE 2     /* stopped at a header whose frame runs past len */
+
+/* Host side, no GPU and no context (like ac3mi_syncinfo): the walk over len bytes at buf (len < 2^32), frames into refs[0 ..
+ * n_frames) (room for max_frames), the rest into *info.  It shares the header test with the kernel below and sums the CRCs in
+ * plain C.  AC3MI_ERR_ARG: a NULL pointer, mode not 0 / 1, max_frames < 1, len >= 2^32. */
+int ac3mi_frame_scan(const uint8_t *buf, size_t len, int mode, int max_frames, ac3mi_frame_ref *refs, ac3mi_scan_info *info);
+/* The same for n_streams streams on the device, one wavefront per stream, asynchronous on the context's stream.  Stream s is
+ * d_bytes[s * stream_stride .. + d_len[s]): d_bytes 16-byte aligned, stream_stride a multiple of 16 and < 2^32, d_len[s] <=
+ * stream_stride (a larger one is read as stream_stride).  Bytes between a stream's len and its stride may be read; they never
+ * influence a result, and nothing outside a stream's stride is read.  d_refs[s][max_frames] and d_info[s] (both 4-byte aligned):
+ * entries of d_refs at index >= n_frames are left untouched; d_info[s] is written whole for every stream.  No workspace is
+ * used.  n_streams 0: AC3MI_OK, nothing is launched. */
+int ac3mi_frame_scan_batch(ac3mi_ctx *ctx, const uint8_t *d_bytes, size_t stream_stride, const uint32_t *d_len, int n_streams,
+                           int mode, int max_frames, ac3mi_frame_ref *d_refs, ac3mi_scan_info *d_info);
+/* The frames of such a list laid out as the batched calls want them, one wavefront per slot.  Slot (s, f) of d_frames
+ * ([n_streams][frames_per_stream] slots of frame_stride bytes) receives frame first_frame + f of stream s followed by zeros up to
+ * frame_stride; it is all zeros if the stream has no such frame or the frame is longer than frame_bytes (8..3840) - the decoders
+ * then refuse that slot with status bit 8, as they refuse any non-frame.  d_frames, frame_stride and frame_bytes as in
+ * ac3mi_decode_batch (stride a multiple of 4 and >= frame_bytes rounded up to 4, base 4-byte aligned); d_bytes and
+ * stream_stride as above or, here, only multiples of 4 (16-byte loads and stores when all four are multiples of 16, else
+ * dwords).  d_refs, d_info and max_frames are the scan's; a reference that does not lie inside its stream's stride gives a
+ * zero slot.  AC3MI_ERR_ARG: a NULL pointer, max_frames < 1, first_frame < 0, frames_per_stream < 1, frame_bytes outside
+ * 8..3840, misalignment.  n_streams 0: AC3MI_OK, nothing is launched. */
+int ac3mi_frame_gather_batch(ac3mi_ctx *ctx, const uint8_t *d_bytes, size_t stream_stride, int n_streams,
+                             const ac3mi_frame_ref *d_refs, const ac3mi_scan_info *d_info, int max_frames, int first_frame,
+                             int frames_per_stream, uint8_t *d_frames, int frame_stride, int frame_bytes);
+
 /* How ac3mi_encode_batch / ac3mi_transcode_batch pack a frame once its SNR offsets are found (new; same bytes either way -
  * the searches always run first, one wavefront per stream, frames in order):
  *   1  one wavefront per frame packs it;

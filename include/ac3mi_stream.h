@@ -29,7 +29,9 @@
  *   - WAVE_FORMAT_EXTENSIBLE is accepted for PCM with the default channel masks
  *     (src/AC3ACM.cpp:207-239); the reference's AC-3 EXTENSIBLE test can never pass (:303-304)
  * Like the ACM codec, this layer never checks a frame's CRC words: ac3mi_set_decode_crc (ac3mi.h) belongs to the batched
- * calls and is not applied here, and a false sync word is still only rejected by a52_syncinfo's header test.
+ * calls and is not applied here, and a false sync word is still only rejected by a52_syncinfo's header test.  A host whose
+ * streams lie in device memory finds their frames with ac3mi_frame_scan_batch (ac3mi.h; mode 1 confirms every sync word by the
+ * frame's two CRCs) and lays them out for the batched calls with ac3mi_frame_gather_batch.
  */
 #ifndef AC3MI_STREAM_H
 #define AC3MI_STREAM_H
