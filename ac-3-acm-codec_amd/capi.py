@@ -67,6 +67,27 @@ class ScanInfoC(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint32) for k in ("n_frames", "consumed", "skipped", "rejected", "flags", "reserved")]
 
 
+class LoudnessDescC(ctypes.Structure):
+    """ac3mi_loudness_desc"""
+    _fields_ = [("sample_rate", ctypes.c_int), ("channels", ctypes.c_int), ("role", ctypes.c_uint8 * 6)]
+
+
+class LoudnessResultC(ctypes.Structure):
+    """ac3mi_loudness_result"""
+    _fields_ = [("mean_energy", ctypes.c_double), ("max_block_energy", ctypes.c_double), ("lkfs", ctypes.c_float),
+                ("blocks", ctypes.c_uint32), ("blocks_abs", ctypes.c_uint32), ("blocks_rel", ctypes.c_uint32),
+                ("dialnorm", ctypes.c_uint8), ("flags", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 6)]
+
+
+def loudness_result_dtype():
+    """ac3mi_loudness_result as a numpy structured dtype (40 bytes; a uint8 tensor [..., 40] views as it)"""
+    import numpy as np
+    dt = np.dtype([("mean_energy", "<f8"), ("max_block_energy", "<f8"), ("lkfs", "<f4"), ("blocks", "<u4"), ("blocks_abs", "<u4"),
+                   ("blocks_rel", "<u4"), ("dialnorm", "u1"), ("flags", "u1"), ("reserved", "u1", (6,))])
+    assert dt.itemsize == ctypes.sizeof(LoudnessResultC) == 40
+    return dt
+
+
 def _struct_dtype(cls, size):
     import numpy as np
     t = {ctypes.c_uint8: "u1", ctypes.c_uint16: "<u2", ctypes.c_uint32: "<u4"}
@@ -150,6 +171,14 @@ def load_library():
     lib.ac3mi_frame_scan_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.ac3mi_frame_gather_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                              c_void_p, c_int, c_int]
+    lib.ac3mi_loudness_state_bytes.restype = c_size_t
+    lib.ac3mi_loudness_state_bytes.argtypes = []
+    lib.ac3mi_loudness_roles.argtypes = [c_int, c_void_p]
+    lib.ac3mi_loudness_tables.argtypes = [c_int, c_void_p, c_void_p, c_void_p]
+    lib.ac3mi_loudness_batch.argtypes = [c_void_p, ctypes.POINTER(LoudnessDescC), c_void_p, c_int, c_int, c_void_p]
+    lib.ac3mi_loudness_read_batch.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
+    lib.ac3mi_loudness_read.argtypes = [c_void_p, ctypes.POINTER(LoudnessResultC)]
+    lib.ac3mi_loudness_words_batch.argtypes = [c_void_p, c_void_p, c_int, c_int, ctypes.c_uint32, c_void_p]
     lib.ac3mi_set_encode_drc.argtypes = [c_void_p, c_int, c_void_p]
     lib.ac3mi_set_encode_dynrng_frames.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.ac3mi_set_encode_drc_source.argtypes = [c_void_p, c_int]

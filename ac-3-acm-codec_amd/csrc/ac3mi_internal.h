@@ -269,6 +269,23 @@ struct GatherLaunch {
 };
 hipError_t launch_frame_gather(const GatherLaunch &L, hipStream_t stream);
 
+// loudness.hip: the BS.1770 meter (ac3mi_loudness_*; the rule is include/ac3mi.h's, its decisions loudness_rule.h's).  tab:
+// LOUD_TAB_DOUBLES doubles on the device, E_0 .. E_900 then the 30 dialnorm thresholds (loud_fill_tab writes them on the host)
+constexpr int LOUD_TAB_DOUBLES = 901 + 30;
+void loud_fill_tab(double *h_tab);
+struct LoudnessLaunch {
+    const int16_t *pcm;             // [S][F][1536][channels]
+    int sample_rate, channels;
+    uint8_t role[6];
+    int n_streams, frames_per_stream;
+    void *state;                    // [S] LoudState
+    const double *tab;
+};
+hipError_t launch_loudness(const LoudnessLaunch &L, hipStream_t stream);
+hipError_t launch_loudness_read(const void *state, int n_streams, const double *tab, ac3mi_loudness_result *results, hipStream_t stream);
+hipError_t launch_loudness_words(const ac3mi_loudness_result *results, int n_streams, int frames_per_stream, uint32_t base_word,
+                                 uint32_t *words, hipStream_t stream);
+
 // The shape large batches run at - 5.1: acmod 7 with the LFE, six planes in and out, five full-bandwidth channels.  The one
 // predicate behind every kernel variant that has it compiled in (ac3mi_set_fixed_shape): a launcher adds its own conditions -
 // one frame per stream, its stage's tools and taps off - and anything else takes the generic kernels.
@@ -406,5 +423,6 @@ struct ac3mi_ctx {
     int decode_mode = 0;    // ac3mi_set_decode_mode
     int decode_crc = 0;     // ac3mi_set_decode_crc
     int fixed_shape = 1;    // ac3mi_set_fixed_shape
+    double *loud_tab = nullptr;     // ac3mi_loudness_*: bin edges and dialnorm thresholds on the device, put there by the first call (no workspace: it is a table)
     std::string err;
 };

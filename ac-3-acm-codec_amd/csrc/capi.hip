@@ -510,6 +510,7 @@ void ac3mi_destroy(ac3mi_ctx *ctx)
     (void)hipFree(ctx->tab.lfsr_idx);
     for (DevBuf *b : ac3mi_ctx::workspaces(ctx)) (void)hipFree(b->p);
     (void)hipFree(ctx->tab.enc);
+    (void)hipFree(ctx->loud_tab);
     (void)hipEventDestroy(ctx->ev0);
     (void)hipEventDestroy(ctx->ev1);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -1365,6 +1366,77 @@ int ac3mi_frame_gather_batch(ac3mi_ctx *ctx, const uint8_t *d_bytes, size_t stre
     G.frame_stride = frame_stride;
     G.frame_bytes = frame_bytes;
     HIPCHK(ctx, launch_frame_gather(G, ctx->stream));
+    return AC3MI_OK;
+}
+
+// (ac3mi_loudness_state_bytes, _roles, _tables and _read, the host side, live in loudness.hip beside the rule)
+static int loud_tab_ready(ac3mi_ctx *ctx, const char *who)
+{
+    if (ctx->loud_tab) return AC3MI_OK;
+    double h[LOUD_TAB_DOUBLES];
+    loud_fill_tab(h);
+    double *d = nullptr;
+    if (hipMalloc((void **)&d, sizeof h) != hipSuccess) { ctx->err = std::string(who) + ": out of memory"; return AC3MI_ERR_HIP; }
+    hipError_t e = hipMemcpyAsync(d, h, sizeof h, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);       // h leaves scope
+    if (e != hipSuccess) { (void)hipFree(d); ctx->err = std::string(who) + ": " + hipGetErrorString(e); return AC3MI_ERR_HIP; }
+    ctx->loud_tab = d;
+    return AC3MI_OK;
+}
+
+int ac3mi_loudness_batch(ac3mi_ctx *ctx, const ac3mi_loudness_desc *desc, const int16_t *d_pcm, int n_streams,
+                         int frames_per_stream, void *d_state)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    bool ok = desc && d_pcm && d_state && n_streams >= 0 && frames_per_stream >= 1 && !((uintptr_t)d_pcm & 1) && !((uintptr_t)d_state & 7);
+    ok = ok && (desc->sample_rate == 48000 || desc->sample_rate == 44100 || desc->sample_rate == 32000) && desc->channels >= 1 && desc->channels <= 6;
+    for (int c = 0; ok && c < desc->channels; c++) ok = desc->role[c] <= 2;
+    if (!ok) {
+        ctx->err = "ac3mi_loudness_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    if (n_streams == 0) return AC3MI_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = loud_tab_ready(ctx, "ac3mi_loudness_batch")) return rc;
+    LoudnessLaunch L;
+    L.pcm = d_pcm;
+    L.sample_rate = desc->sample_rate;
+    L.channels = desc->channels;
+    for (int c = 0; c < 6; c++) L.role[c] = c < desc->channels ? desc->role[c] : 0;
+    L.n_streams = n_streams;
+    L.frames_per_stream = frames_per_stream;
+    L.state = d_state;
+    L.tab = ctx->loud_tab;
+    HIPCHK(ctx, launch_loudness(L, ctx->stream));
+    return AC3MI_OK;
+}
+
+int ac3mi_loudness_read_batch(ac3mi_ctx *ctx, const void *d_state, int n_streams, ac3mi_loudness_result *d_results)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (!d_state || !d_results || n_streams < 0 || ((uintptr_t)d_state & 7) || ((uintptr_t)d_results & 7)) {
+        ctx->err = "ac3mi_loudness_read_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    if (n_streams == 0) return AC3MI_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = loud_tab_ready(ctx, "ac3mi_loudness_read_batch")) return rc;
+    HIPCHK(ctx, launch_loudness_read(d_state, n_streams, ctx->loud_tab, d_results, ctx->stream));
+    return AC3MI_OK;
+}
+
+int ac3mi_loudness_words_batch(ac3mi_ctx *ctx, const ac3mi_loudness_result *d_results, int n_streams, int frames_per_stream,
+                               uint32_t base_word, uint32_t *d_words)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (!d_results || !d_words || n_streams < 0 || frames_per_stream < 1 || (uint64_t)n_streams * (uint64_t)frames_per_stream > 0x7fffffffu ||
+        ((uintptr_t)d_results & 7) || ((uintptr_t)d_words & 3)) {
+        ctx->err = "ac3mi_loudness_words_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    if (n_streams == 0) return AC3MI_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, launch_loudness_words(d_results, n_streams, frames_per_stream, base_word, d_words, ctx->stream));
     return AC3MI_OK;
 }
 

@@ -91,6 +91,45 @@ def frame_scan(buf, mode=0, max_frames=None):
     return np.frombuffer(bytes(refs), capi.frame_ref_dtype())[:int(out["n_frames"])].copy(), out
 
 
+def loudness_state_bytes():
+    """ac3mi_loudness_state_bytes: bytes of one stream's meter state (all zeros: a new stream)"""
+    return int(capi.load_library().ac3mi_loudness_state_bytes())
+
+
+def loudness_roles(a52_flags):
+    """ac3mi_loudness_roles: the roles (0 not measured, 1 weight 1.0, 2 weight 1.41) of the WAVE-order slots that the s16
+    decoders write for these liba52 output flags -> a list, one per channel"""
+    role = (ctypes.c_uint8 * 6)()
+    n = capi.load_library().ac3mi_loudness_roles(int(a52_flags), role)
+    if n <= 0:
+        raise capi.AC3MIError("ac3mi_loudness_roles: no layout for flags %d" % a52_flags)
+    return list(role)[:n]
+
+
+def loudness_tables(sample_rate):
+    """ac3mi_loudness_tables -> (coef float64 [10]: shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2; bin edges [901];
+    dialnorm thresholds [30])"""
+    import numpy as np
+    coef, edges, thr = np.zeros(10), np.zeros(901), np.zeros(30)
+    if capi.load_library().ac3mi_loudness_tables(int(sample_rate), coef.ctypes.data, edges.ctypes.data, thr.ctypes.data) != 0:
+        raise capi.AC3MIError("ac3mi_loudness_tables: %r is not a rate the meter takes" % (sample_rate,))
+    return coef, edges, thr
+
+
+def loudness_read(state):
+    """ac3mi_loudness_read, the host read-out: one state's bytes (ac3mi_loudness_state_bytes of them) -> a numpy record of
+    capi.loudness_result_dtype()"""
+    import numpy as np
+    lib = capi.load_library()
+    data = bytes(bytearray(state))
+    if len(data) != lib.ac3mi_loudness_state_bytes():
+        raise ValueError("a state is %d bytes" % lib.ac3mi_loudness_state_bytes())
+    res = capi.LoudnessResultC()
+    if lib.ac3mi_loudness_read(data, ctypes.byref(res)) != 0:
+        raise capi.AC3MIError("ac3mi_loudness_read: bad argument")
+    return np.frombuffer(bytes(res), capi.loudness_result_dtype())[0]
+
+
 def encode_metadata_word(**fields):
     """ac3mi_encode_metadata_word: the fields of Engine.set_encode_metadata (those not given: the defaults) -> the packed
     word; raises on a field out of range."""
@@ -456,6 +495,58 @@ class Engine:
                                                       int(refs.shape[1]), int(first_frame), int(frames_per_stream),
                                                       ctypes.c_void_p(out.data_ptr()), int(frame_stride), int(frame_bytes)))
         self._keep.append((streams, refs, info, out))
+        return out
+
+    def loudness_batch(self, sample_rate, roles, pcm, state=None, wait_torch=True):
+        """ac3mi_loudness_batch: meters pcm [S][F][1536][channels] s16 on the device (any 2-byte aligned view that is
+        contiguous) into state u8 [S][loudness_state_bytes()] (zeros: new streams; default: allocated here) -> state.  roles:
+        one of 0 / 1 / 2 per channel (loudness_roles)."""
+        import torch
+        assert pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.is_cuda and pcm.dim() == 4 and pcm.shape[2] == 1536
+        S, F, _, nch = pcm.shape
+        nb = int(self.lib.ac3mi_loudness_state_bytes())
+        if state is None:
+            state = torch.zeros((S, nb), dtype=torch.uint8, device=pcm.device)
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == S * nb
+        desc = capi.LoudnessDescC(int(sample_rate), int(nch), (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6]))
+        if len(roles) != nch:
+            raise ValueError("one role per channel")
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_loudness_batch(ctypes.c_void_p(self.ctx), ctypes.byref(desc), ctypes.c_void_p(pcm.data_ptr()), int(S), int(F),
+                                                  ctypes.c_void_p(state.data_ptr())))
+        self._keep.append((pcm, state))
+        return state
+
+    def loudness_read_batch(self, state, out=None, wait_torch=True):
+        """ac3mi_loudness_read_batch: state u8 [S][loudness_state_bytes()] -> results u8 [S][40];
+        `.cpu().numpy().view(capi.loudness_result_dtype())[..., 0]` names the fields."""
+        import torch
+        nb = int(self.lib.ac3mi_loudness_state_bytes())
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.is_cuda and state.numel() % nb == 0
+        S = state.numel() // nb
+        if out is None:
+            out = torch.zeros((S, 40), dtype=torch.uint8, device=state.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == S * 40
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_loudness_read_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(state.data_ptr()), int(S),
+                                                       ctypes.c_void_p(out.data_ptr())))
+        self._keep.append((state, out))
+        return out
+
+    def loudness_words_batch(self, results, frames_per_stream, base_word, out=None, wait_torch=True):
+        """ac3mi_loudness_words_batch: results u8 [S][40] (loudness_read_batch) -> words int32 [S][frames_per_stream], base_word
+        with each stream's dialnorm (base_word's own where a stream is flagged empty), for set_encode_metadata_frames."""
+        import torch
+        assert results.dtype == torch.uint8 and results.is_contiguous() and results.is_cuda and results.numel() % 40 == 0
+        S = results.numel() // 40
+        if out is None:
+            out = torch.zeros((S, int(frames_per_stream)), dtype=torch.int32, device=results.device)
+        assert out.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and out.is_contiguous() and out.numel() == S * int(frames_per_stream)
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_loudness_words_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(results.data_ptr()), int(S),
+                                                        int(frames_per_stream), ctypes.c_uint32(int(base_word) & 0xffffffff),
+                                                        ctypes.c_void_p(out.data_ptr())))
+        self._keep.append((results, out))
         return out
 
     def set_encode_drc(self, profile, state=None):

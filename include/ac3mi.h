@@ -316,6 +316,85 @@ int ac3mi_frame_gather_batch(ac3mi_ctx *ctx, const uint8_t *d_bytes, size_t stre
                              const ac3mi_frame_ref *d_refs, const ac3mi_scan_info *d_info, int max_frames, int first_frame,
                              int frames_per_stream, uint8_t *d_frames, int frame_stride, int frame_bytes);
 
+/* Programme loudness on the device and the dialnorm it implies (new): integrated loudness after ITU-R BS.1770-4 of the s16
+ * PCM that ac3mi_decode_s16_batch writes and ac3mi_encode_batch reads, per stream, with the state carried from call to call,
+ * and the result as the dialnorm word array that ac3mi_set_encode_metadata_frames takes.  The whole rule:
+ *   input      d_pcm [n_streams][frames_per_stream][1536][channels] s16 interleaved, x = s / 32768.
+ *   roles      per input slot: 0 = not measured (the LFE), 1 = weight w 1.0 (L, R, C, mono, both halves of dual mono),
+ *              2 = weight 1.41 (surrounds).
+ *   K-weighting  per measured slot two biquads in double, y1 = shelf(x), y = highpass(y1), each
+ *                  out = b0 in + s1;  s1' = b1 in - a1 out + s2;  s2' = b2 in - a2 out      (a new stream: s1 = s2 = 0)
+ *              with, for fs = sample_rate and K = tan(pi f0 / fs), a0 = 1 + K / Q + K^2:
+ *                shelf     f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, Vh = 10^(G / 20),
+ *                          Vb = Vh^0.4996667741545416;  b = ((Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0,
+ *                          (Vh - Vb K / Q + K^2) / a0),  a1 = 2 (K^2 - 1) / a0,  a2 = (1 - K / Q + K^2) / a0
+ *                high-pass f0 = 38.13547087602444, Q = 0.5003270373238773;  b = (1, -2, 1),  a1 = 2 (K^2 - 1) / a0,
+ *                          a2 = (1 - K / Q + K^2) / a0
+ *              At 48 kHz these are BS.1770's table to its printed digits.  The three sets are frozen as literals
+ *              (ac3mi_loudness_tables hands them out).
+ *   blocks     hop = fs / 10 samples (4800 / 4410 / 3200).  A hop's energy is h = sum over measured slots of w * sum of y^2
+ *              over the hop's samples; hops run on across frames and calls.  From the fourth hop of a stream on, every hop
+ *              closes one 400 ms block of energy z = (h[-3] + h[-2] + h[-1] + h[0]) / (4 hop).
+ *   bins       900 bins of 0.1 LU over [-70, +20) LKFS with edges E_b = 10^((-70 + 0.1 b + 0.691) / 10), b = 0..900,
+ *              built once on the host in double; bin b holds the blocks with E_b <= z < E_(b+1), found by comparison
+ *              (no logarithm decides anything).  z < E_0 fails the absolute gate and is only counted (blocks);
+ *              z >= E_900 goes to bin 899.  Per bin a u32 count and a double sum of z, added in time order.
+ *   read-out   Gamma = 0.1 * (sum of all bins' sums / sum of all bins' counts), the relative gate.  A bin with E_b >= Gamma
+ *              counts whole; the one bin with E_b < Gamma < E_(b+1) counts whole iff its own sum / count >= Gamma; no
+ *              other bin counts.  mean_energy = the counted sums / the counted counts (blocks_rel).  This is BS.1770's
+ *              gating except inside the one bin Gamma cuts, where blocks up to 0.1 LU under the gate may be kept or
+ *              blocks up to 0.1 LU above it dropped - together.
+ *   result     lkfs = -0.691 + 10 log10(mean_energy) (informative, a float);  dialnorm = 1 + the number of d in 1..30
+ *              with mean_energy < 10^((-d - 0.5 + 0.691) / 10), i.e. -lkfs rounded half up and clamped to 1..31, decided on
+ *              energies;  AC3MI_LOUDNESS_EMPTY when no block counts: mean_energy 0, lkfs -70, dialnorm 31.
+ * The arithmetic is float64 throughout; a frame's samples are filtered in 64 segments of 24 (zero-state response, the segment
+ * end states combined across the wavefront, zero-input correction), which differs from the sample-by-sample recursion by
+ * parts in 10^12 and gives the same bits for every way of cutting a stream into calls and for either alignment of d_pcm. */
+typedef struct { int sample_rate; int channels; uint8_t role[6]; } ac3mi_loudness_desc;
+typedef struct {
+    double mean_energy;             /* the gated mean block energy: the pinned quantity */
+    double max_block_energy;        /* the largest block energy, gated or not */
+    float lkfs;                     /* -0.691 + 10 log10(mean_energy) */
+    uint32_t blocks, blocks_abs, blocks_rel;    /* blocks formed; at or above the absolute gate; counted after the relative gate */
+    uint8_t dialnorm;               /* 1..31 */
+    uint8_t flags;                  /* AC3MI_LOUDNESS_EMPTY */
+    uint8_t reserved[6];            /* 0 */
+} ac3mi_loudness_result;            /* 40 bytes */
+#define AC3MI_LOUDNESS_EMPTY 1      /* no block passed the gates */
+
+/* Bytes of one stream's state.  The state is opaque and lies in the caller's device memory, d_state[n_streams] records of this
+ * size (8-byte aligned); all zeros is a new stream, and every ac3mi_loudness_batch reads and rewrites it.  It is indexed by
+ * the stream's position in the call, NOT through ac3mi_set_state_slots.  It holds, per input slot, the two biquads' states;
+ * the sample position inside the open hop; the open hop's sum and the last three hops' sums; the hop count; the bins; the
+ * block counters and the maximum. */
+size_t ac3mi_loudness_state_bytes(void);
+/* Host helper: the roles of the WAVE-order slots that ac3mi_decode_s16_batch / ac3mi_convert_s16_batch write for liba52
+ * output flags a52_flags (A52_LFE included): the LFE slot 0, surround slots 2, the rest 1; slots past the channel count 0.
+ * Returns the channel count, or AC3MI_ERR_ARG for flags liba52 has no layout for. */
+int ac3mi_loudness_roles(int a52_flags, uint8_t role[6]);
+/* The frozen tables (any pointer may be NULL): coef10 = shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 for sample_rate
+ * (48000, 44100 or 32000; else AC3MI_ERR_ARG), edges901 = E_0 .. E_900, dialnorm30 = the thresholds for d = 1 .. 30. */
+int ac3mi_loudness_tables(int sample_rate, double *coef10, double *edges901, double *dialnorm30);
+/* Meters frames_per_stream more frames of every stream, one wavefront per stream, asynchronous on the context's stream.
+ * d_pcm as above, 2-byte aligned (a 16-byte aligned base is read with 16-byte loads, same bits); nothing outside
+ * [d_pcm, d_pcm + n_streams * frames_per_stream * 3072 * channels) is read.  AC3MI_ERR_ARG, with the state untouched: a
+ * sample_rate other than 48000 / 44100 / 32000 (the half and quarter rates have no whole 100 ms hop), channels outside
+ * 1..6, a role > 2, a NULL or misaligned pointer, frames_per_stream < 1.  The first call on a context puts the bin edges
+ * into device memory (an allocation and a copy: not inside a graph capture).  n_streams 0: AC3MI_OK, nothing is launched. */
+int ac3mi_loudness_batch(ac3mi_ctx *ctx, const ac3mi_loudness_desc *desc, const int16_t *d_pcm, int n_streams,
+                         int frames_per_stream, void *d_state);
+/* The read-out of n_streams states into d_results[n_streams] (8-byte aligned), one wavefront per stream; the states are not
+ * changed, so a programme may be read while it is still being metered. */
+int ac3mi_loudness_read_batch(ac3mi_ctx *ctx, const void *d_state, int n_streams, ac3mi_loudness_result *d_results);
+/* Host twin of the read-out, no GPU and no context: the same rule code on one state copied to host memory (any alignment). */
+int ac3mi_loudness_read(const void *h_state, ac3mi_loudness_result *out);
+/* d_words[s][f] = (base_word & ~31) | d_results[s].dialnorm for f < frames_per_stream, one lane per frame; a stream flagged
+ * AC3MI_LOUDNESS_EMPTY keeps base_word's dialnorm.  base_word as ac3mi_encode_metadata_word packs it; d_words is what
+ * ac3mi_set_encode_metadata_frames takes.  Two passes over a programme in HBM: ac3mi_decode_s16_batch ->
+ * ac3mi_loudness_batch (all of it) -> ac3mi_loudness_read_batch -> ac3mi_loudness_words_batch -> ac3mi_transcode_batch. */
+int ac3mi_loudness_words_batch(ac3mi_ctx *ctx, const ac3mi_loudness_result *d_results, int n_streams, int frames_per_stream,
+                               uint32_t base_word, uint32_t *d_words);
+
 /* How ac3mi_encode_batch / ac3mi_transcode_batch pack a frame once its SNR offsets are found (new; same bytes either way -
  * the searches always run first, one wavefront per stream, frames in order):
  *   1  one wavefront per frame packs it;
