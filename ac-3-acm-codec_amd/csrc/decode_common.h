@@ -67,6 +67,22 @@ __device__ __forceinline__ int32_t speek(const FrameBits fr, uint32_t pos, int n
     return ((int32_t)(peek(fr, pos, n) << (32 - n))) >> (32 - n);
 }
 
+// A frame shorter than the batch's frame_bytes (a 44.1 kHz stream's short frame, a batch of several bit rates): the staging
+// loops mask and pad at frame_bytes, so the staged words still hold what the slot holds behind the frame's own last byte.
+// That is not the frame's and reads as zero (include/ac3mi.h, ac3mi_decode_desc.frame_bytes), as it does to liba52's caller's
+// padded buffer, to frame_gather_kernel and to crc_kernel: thread t of nt clears it - the bytes of the staged word that
+// holds byte fbytes from that byte on (a staged word is byte-swapped: its first byte is its top one), and the words behind
+// it up to nw.  Only frames whose mantissas run on behind their own end read there.  Thread t takes the words t, t + nt,
+// ... - the words it staged itself in every staging loop, so its own stores stay in order and nothing has to separate the
+// two; the caller's barrier ahead of the readers covers both.
+__device__ __forceinline__ void trim_staged_frame(uint32_t *frw, int fbytes, int nw, int t, int nt)
+{
+    const int w = fbytes >> 2, keep = fbytes & 3;
+    int i = t;
+    if (i < w) i += (w - t + nt - 1) / nt * nt;
+    for (; i < nw; i += nt) frw[i] = (i == w && keep) ? frw[i] & (0xffffffffu << (8 * (4 - keep))) : 0u;
+}
+
 struct Rd {                                   // wave-uniform serial reader
     FrameBits fr;
     // 64-bit window (scalar registers): one LDS read per ~32 bits instead of one per field.  The next bit to read is the
@@ -892,13 +908,14 @@ struct alignas(16) BlkDesc {
     uint32_t draw_off;          // dither draws of the frame before this block
     uint32_t flags;             // bit 0: the block failed (zero planes); 8-12 chincpl; 16-20 dither flags; 24-27 rematflg
     uint32_t cplbndstrc;
-    uint16_t endmant[5], cplstrt, cplend, pad0;
+    uint16_t endmant[5], cplstrt, cplend;
+    uint16_t own_bytes;         // the frame's own size where it is below frame_bytes, else 0 (every block of a frame, failed ones too)
     uint8_t rv_exp[8], rv_bap[8];   // block of THIS frame whose row holds the slot's current exponents / bap
     float gain[5], lfe_gain;        // parse.c:810-811 (dynamic range folded in); LFE: 0 when it is not an output
     uint32_t src_snr;           // 16 csnroffst + fsnroffst (channel 0) the frame was coded with, as of this block
     uint32_t pad1;
 };
-static_assert(sizeof(BlkDesc) == 80 && offsetof(BlkDesc, src_snr) == 72, "BlkDesc layout");
+static_assert(sizeof(BlkDesc) == 80 && offsetof(BlkDesc, src_snr) == 72 && offsetof(BlkDesc, own_bytes) == 30, "BlkDesc layout");
 
 constexpr int ROWSET = 7 * 512;         // bytes of one (frame, block) row set: 7 slots x (256 exponents + 256 row bytes)
 

@@ -112,6 +112,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
         const uint8_t *src = P.frames + fidx * P.frame_stride;
         float *cout = P.coef + fidx * 6 * n_in * 256;
         uint32_t status = 0;
+        [[maybe_unused]] int short_bytes = 0;       // the frame's own size where it is below frame_bytes (BlkDesc::own_bytes), else 0
         // block 0 takes exponents, coupling or bit-allocation parameters the frame did not send (not a conforming frame):
         // what it reuses is whatever the variant at hand has carried so far, so results may depend on the batch shape
         bool reuse0 = false;
@@ -169,6 +170,13 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                 const int code = b4 & 63, rate = k_kbps[code >> 1];
                 const int fbytes = st.fscod() == 0 ? 4 * rate : st.fscod() == 1 ? 2 * (320 * rate / 147 + (code & 1)) : 6 * rate;
                 if (fbytes > P.frame_bytes) hdr_ok = false;        // frame_bytes = the largest frame of the batch (44.1 kHz alternates)
+                else if (fbytes < P.frame_bytes) {                 // (wave-uniform) the slot's bytes behind a shorter frame are not the frame's
+                    trim_staged_frame(frw, fbytes, (P.frame_bytes + 3) >> 2, lane, 64);
+                    short_bytes = fbytes;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                }
             }
         }
         if (hdr_ok) {
@@ -567,8 +575,8 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                         const uint32_t fl = ((uint32_t)st.chincpl << 8) | ((uint32_t)dithmask << 16) | ((uint32_t)st.rematflg() << 24);
                         const uint32_t w0 = lane == 0 ? rd.pos() : lane == 1 ? frame_draws : lane == 2 ? fl : st.cplbndstrc;
                         if (lane < 4) reinterpret_cast<uint32_t *>(dp)[lane] = w0;
-                        const int em = lane == 5 ? st.cplstrtmant : (int)((uint32_t)(st.ends >> (8 * (lane & 7))) & 0xffu);
-                        if (lane < 7) reinterpret_cast<uint16_t *>(dp + 16)[lane] = (uint16_t)em;
+                        const int em = lane == 5 ? st.cplstrtmant : lane == 7 ? short_bytes : (int)((uint32_t)(st.ends >> (8 * (lane & 7))) & 0xffu);
+                        if (lane < 8) reinterpret_cast<uint16_t *>(dp + 16)[lane] = (uint16_t)em;
                         if (lane < 8) { dp[32 + lane] = (uint8_t)rv_exp; dp[40 + lane] = (uint8_t)rv_bap; }
                         const float gl = lane == 0 ? gain[0] : lane == 1 ? gain[1] : lane == 2 ? gain[2] : lane == 3 ? gain[3] : lane == 4 ? gain[4]
                                        : (st.output & AC3MI_LFE) ? st.dynrng : 0.f;
@@ -592,6 +600,8 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                     // (no descriptor was stored: the word a transcode's encoder reads as its search hint must not be a leftover
                     // of an earlier call - 0 = no hint, see enc_search_kernel)
                     P.desc[fidx * 6 + blk].src_snr = 0u;
+                    // (its wavefront of mant_kernel / mantx_kernel reads no mantissas but has staged a share of the frame)
+                    P.desc[fidx * 6 + blk].own_bytes = (uint16_t)short_bytes;
                 }
             }
             {

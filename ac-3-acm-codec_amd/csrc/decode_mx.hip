@@ -98,6 +98,9 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
             }
             frw[i] = v;
         }
+        // the slot's bytes behind a frame shorter than frame_bytes are not the frame's.  The parse kernel leaves such a frame's own
+        // size in every block's descriptor (0: full size - every frame of a batch of one frame size); each thread clears what it staged
+        if (const int own = (int)(rfl(w1v.w) >> 16)) trim_staged_frame(frw, own, nw, tid, 384);
         if (tid < M2_NDESC) L.dsc[tid] = mant_desc2((uint32_t)tid);
         for (int i = tid; i < 760; i += 384) L.qtab[i] = P.tab->qtab[i];
         if (tid < 128) L.tw[0][tid] = Q.tw_long[tid];

@@ -440,7 +440,7 @@ __device__ __forceinline__ void parse_block_b(const FrameBits FB, ParserState &S
 
 // ---- a52_syncinfo (parse.c:86-129) + a52_frame (parse.c:131-205): frame header and BSI; returns false for a frame the
 // batch cannot hold (no sync word, other channel configuration, too long, an output liba52 would refuse) ----
-__device__ __forceinline__ bool parse_frame_header(const FrameBits FB, const uint32_t *frw, ParserState &S, uint16_t *hth, const DecodeParams &P, int lane)
+__device__ __forceinline__ bool parse_frame_header(const FrameBits FB, uint32_t *frw, ParserState &S, uint16_t *hth, const DecodeParams &P, int lane)
 {
     const uint32_t w0 = rfl(frw[0]), w1 = rfl(frw[1]);
     const int b4 = (w1 >> 24) & 0xff, b5 = (w1 >> 16) & 0xff, b6 = (w1 >> 8) & 0xff;
@@ -456,6 +456,10 @@ __device__ __forceinline__ bool parse_frame_header(const FrameBits FB, const uin
         const int code = b4 & 63, rate = k_kbps[code >> 1];
         const int fbytes = fscod == 0 ? 4 * rate : fscod == 1 ? 2 * (320 * rate / 147 + (code & 1)) : 6 * rate;
         if (fbytes > P.frame_bytes) return false;                // frame_bytes = the largest frame of the batch (44.1 kHz alternates)
+        if (fbytes < P.frame_bytes) {                            // (wave-uniform) the slot's bytes behind a shorter frame are not the frame's:
+            trim_staged_frame(frw, fbytes, (P.frame_bytes + 3) >> 2, lane, 64);      // cleared by the parser wave, ahead of barrier B1 of block 0
+            wave_sync();
+        }
     }
     VRd rd = make_reader(FB, 6 * 8 + 3, lane);
     int acmod = acmod0;

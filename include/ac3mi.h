@@ -737,7 +737,10 @@ int ac3mi_imdct_batch(ac3mi_ctx *ctx, const ac3mi_xform_desc *desc,
  *          reports for any one of them); frames that disagree are reported in d_status and
  *          produce silence
  *  frame_bytes    size of the largest frame of the batch (44.1 kHz streams alternate between two
- *          sizes); every frame starts on its frame_stride slot and carries its own size
+ *          sizes); every frame starts on its frame_stride slot and carries its own size.  What a
+ *          frame decodes to is a function of its own bytes, by its header's size: whatever its
+ *          slot holds behind them reads as zero, as it does to ac3mi_frame_gather_batch (which
+ *          writes zeros there) and to the CRC check (which sums by the frame's own size)
  */
 typedef struct {
     int flags;

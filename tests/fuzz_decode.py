@@ -1,6 +1,9 @@
 """Extended randomised decoder parity run (not collected by pytest): random packer streams over all channel modes,
 sample rates, bsid 8..10 and feature mixes, GPU coefficient planes bit-exact against the oracle.
-    python tests/fuzz_decode.py [n_rounds] [seed0]"""
+    python tests/fuzz_decode.py [n_rounds] [seed0] [--mixed]
+--mixed: every stream alternates between the round's frmsizecod and a second one of the same fscod, drawn per stream, and the
+frames lie in slots of the round's largest size whose tails hold 0x00, 0xff or random bytes (tests/_mixed_sizes.py).  Off by
+default, and its draws come from a generator of their own: a campaign's seeds mean what they meant."""
 import ctypes
 import sys
 
@@ -13,8 +16,10 @@ from tests import packer                 # noqa: E402
 
 def main():
     import torch
-    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    args = [a for a in sys.argv[1:] if a != "--mixed"]
+    mixed = "--mixed" in sys.argv[1:]
+    rounds = int(args[0]) if len(args) > 0 else 40
+    seed0 = int(args[1]) if len(args) > 1 else 1
     pkg = H.pkg()
     eng = pkg.Engine(0)
     L = H.orc()
@@ -28,9 +33,18 @@ def main():
         bsid = int(rng.choice([8, 8, 9, 10]))
         fsz = int(rng.integers(20, 38))
         S, F = 6, 3
+        fill = 0
         try:
-            frames = np.stack([packer.make_stream(seed0 * 100000 + r * 97 + s, F, acmod, lfe, fscod=fscod, bsid=bsid, frmsizecod=fsz)
-                               for s in range(S)])
+            if mixed:
+                from tests import _mixed_sizes as X
+                rng2 = np.random.default_rng([seed0, r, 0x6d78])
+                second = [int(c) for c in rng2.integers(20, 38, S)]
+                fill = (0x00, 0xff, "random")[int(rng2.integers(0, 3))]
+                streams = [X.mixed_stream(seed0 * 100000 + r * 97 + s, F, acmod, lfe, fscod, (fsz, second[s]), bsid) for s in range(S)]
+                frames = X.lay(streams, max(len(fr) for st in streams for fr in st), fill, seed=r)
+            else:
+                frames = np.stack([packer.make_stream(seed0 * 100000 + r * 97 + s, F, acmod, lfe, fscod=fscod, bsid=bsid, frmsizecod=fsz)
+                                   for s in range(S)])
         except Exception as e:      # the packer could not fit a frame at this size
             print("round %d skipped: %s" % (r, e))
             continue
@@ -67,7 +81,8 @@ def main():
         ok = ok and np.array_equal(got[:, :, :, lfe:lfe + nf].view(np.uint32), want_coef[:, :, :, lfe:lfe + nf].view(np.uint32))
         if lfe:
             ok = ok and np.array_equal(got[:, :, :, 0].view(np.uint32), want_coef[:, :, :, 0].view(np.uint32))
-        print("round %3d acmod %d lfe %d fscod %d bsid %2d frmsizecod %2d: %s" % (r, acmod, lfe, fscod, bsid, fsz, "ok" if ok else "MISMATCH"), flush=True)
+        print("round %3d acmod %d lfe %d fscod %d bsid %2d frmsizecod %2d%s: %s" % (r, acmod, lfe, fscod, bsid, fsz,
+              " and %r in slots of %d, tails %r" % (second, fb, fill) if mixed else "", "ok" if ok else "MISMATCH"), flush=True)
         bad += not ok
     print("mismatching rounds:", bad)
     return 1 if bad else 0

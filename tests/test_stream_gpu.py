@@ -91,6 +91,66 @@ def test_decode_any_chunking(S, pool, seed):
     assert int(np.abs(g.astype(np.int32) - want).max()) <= 1
 
 
+def _alternating(seed, phase):
+    """a 44.1 kHz 2/0 stream of six packer frames whose sizes alternate as every real 44.1 kHz stream's do (836 and 834 bytes:
+    case A of tests/_mixed_sizes.py) -> (the frames, its bytes, the oracle's s16 samples)"""
+    from tests import _mixed_sizes as X
+    frames = X.mixed_stream(seed, 6, 2, 0, 1, (21, 20) if phase == 0 else (20, 21))
+    assert sorted({len(fr) for fr in frames}) == [834, 836]
+    return frames, b"".join(fr.tobytes() for fr in frames), _oracle_s16(X.lay([frames], 836)[0], 2).reshape(-1)
+
+
+def test_decode_a_stream_whose_frame_size_alternates(S, pool):
+    """one such stream in random chunks: the byte accounting of the model, which reads every frame's own header, and the
+    oracle's samples within one step"""
+    rng = np.random.default_rng(11)
+    frames, data, want = _alternating(9701, 0)
+    rc, st = pool.open(S.ac3_format(2, 44100, 192, block_align=836), S.pcm_format(2, 44100))
+    assert rc == 0 and st is not None
+    model = M.DecodeModel(src_channels=2, dst_channels=2)
+    got, used = _run_calls(S, st, data, rng, 1500, [1536 * 4, 512 * 2 * 2, 4000, 40000], model)
+    st.close()
+    assert used == len(data)
+    g = np.frombuffer(got, np.int16)
+    assert g.size == want.size
+    assert int(np.abs(g.astype(np.int32) - want).max()) <= 1
+
+
+def test_two_alternating_streams_in_opposite_phases_share_a_round(S, pool):
+    """two such streams, one beginning with its long frame and one with its short one, advanced together by
+    ac3mi_stream_convert_many: in every round their frames differ in size"""
+    rng = np.random.default_rng(12)
+    made = [_alternating(9702, 0), _alternating(9703, 1)]
+    streams = []
+    for _ in made:
+        rc, st = pool.open(S.ac3_format(2, 44100, 192, block_align=836), S.pcm_format(2, 44100))
+        assert rc == 0 and st is not None
+        streams.append(st)
+    pos = [0, 0]
+    outs = [bytearray(), bytearray()]
+    first = True
+    for _ in range(24):
+        hs, keep = [], []
+        for i, (_, data, _) in enumerate(made):
+            k = int(min(len(data) - pos[i], rng.integers(0, 1700)))
+            src = np.frombuffer(data[pos[i]:pos[i] + k] if k else b"\0", np.uint8).copy()
+            dst = np.zeros(40000, np.uint8)
+            keep.append((src, dst))
+            hs.append(S.StreamHeader(src.ctypes.data, k, 0, dst.ctypes.data, dst.size, 0, S.STREAMCONVERTF_START if first else 0))
+        assert pool.convert_many(streams, hs) == 0
+        for i in range(2):
+            assert hs[i].src_used == hs[i].src_len          # a large destination always drains the source
+            pos[i] += hs[i].src_used
+            outs[i] += keep[i][1][:hs[i].dst_used].tobytes()
+        first = False
+    for i, (_, data, want) in enumerate(made):
+        assert pos[i] == len(data)
+        g = np.frombuffer(bytes(outs[i]), np.int16).astype(np.int32)
+        assert g.size == want.size and int(np.abs(g - want).max()) <= 1, i
+    for st in streams:
+        st.close()
+
+
 def test_decode_downmix_and_leftover_blocks(S, pool):
     frames = H.orc_encode(H.gen_pcm(4, 6, seed=77, kind="tones"))
     fb = frames.shape[1]
