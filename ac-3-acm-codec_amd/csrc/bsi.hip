@@ -1,7 +1,7 @@
 // bsi.hip — syncinfo and BSI of AC-3 frames, read without decoding them (ac3mi_bsi_read, ac3mi_bsi_read_batch,
 // ac3mi_set_encode_metadata_source).  bsi_parse below is the product's one statement of that syntax (A/52 5.3.1 - 5.3.2; the
-// header test is a52_syncinfo's, parse.c:86-129, as crc.hip restates it): the host entry point and the kernel both call it,
-// each with its own way of fetching the frame's dwords.
+// header test and the frame's size are sync_rule.h's): the host entry point and the kernel both call it, each with its own
+// way of fetching the frame's dwords.
 //
 // One lane per frame: the BSI is a serial chain of about 20 conditional fields, each of which decides where the next one
 // lies, so a wavefront per frame would keep 63 lanes idle.  The loads are per-lane dword loads at the frame's stride - bytes
@@ -11,19 +11,9 @@
 // the same 64 lines; it would only turn the rare later dwords of a long BSI (timecodes, addbsi) from a second request on a
 // line already in L2 into an LDS read, for an LDS buffer, a barrier and a guess at how many bytes to stage.
 #include "ac3mi_internal.h"
+#include "sync_rule.h"
 
 namespace ac3mi {
-
-__host__ __device__ inline int bsi_kbps(int i)
-{
-    // (a switch, not a table: one definition serves the host and the device)
-    switch (i) {
-    case 0: return 32; case 1: return 40; case 2: return 48; case 3: return 56; case 4: return 64; case 5: return 80;
-    case 6: return 96; case 7: return 112; case 8: return 128; case 9: return 160; case 10: return 192; case 11: return 224;
-    case 12: return 256; case 13: return 320; case 14: return 384; case 15: return 448; case 16: return 512; case 17: return 576;
-    default: return 640;
-    }
-}
 
 // MSB-first reader over the frame's big-endian dwords: fetch(i) = bytes 4i .. 4i + 3.  A field that would end behind `end`
 // (bits) reads as 0 and sets `over`; no dword that starts at or behind `end` is ever fetched.
@@ -53,13 +43,11 @@ __host__ __device__ inline void bsi_parse(F fetch, int avail, int max_frame, ac3
     if (avail < 6) return;
     const uint32_t w0 = fetch(0), w1 = fetch(1);
     const int b4 = w1 >> 24, b5 = (w1 >> 16) & 0xff;
-    if ((w0 >> 16) != 0x0b77u || b5 >= 0x60 || (b4 & 63) >= 38 || (b4 & 0xc0) == 0xc0) return;
-    const int fscod = b4 >> 6, code = b4 & 63, rate = bsi_kbps(code >> 1);
-    const int fbytes = fscod == 0 ? 4 * rate : fscod == 1 ? 2 * (320 * rate / 147 + (code & 1)) : 6 * rate;
-    if (max_frame > 0 && fbytes > max_frame) return;
+    if (!sync_header_ok(w0 >> 16, b4, b5)) return;
+    if (max_frame > 0 && (int)sync_frame_bytes(b4) > max_frame) return;
     o.verdict = 0;
-    o.fscod = (uint8_t)fscod;
-    o.frmsizecod = (uint8_t)code;
+    o.fscod = (uint8_t)(b4 >> 6);
+    o.frmsizecod = (uint8_t)(b4 & 63);
     o.bsid = (uint8_t)(b5 >> 3);
     o.bsmod = (uint8_t)(b5 & 7);
     o.cmixlev = o.surmixlev = o.dsurmod = o.dialnorm2 = 0xff;

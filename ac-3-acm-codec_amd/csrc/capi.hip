@@ -3,6 +3,7 @@
 #include "ac3mi_internal.h"
 #include "a52_levels.h"
 #include "spec_tables.h"
+#include "sync_rule.h"
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -201,7 +202,7 @@ void build_enc_tables(EncTables *t)
 int enc_config(int freq, int bitrate, int channels, EncConfig *c, int acmod, int lfeon)
 {
     static const uint8_t acmod_of[6] = {1, 2, 3, 6, 7, 7};
-    const int *rates = kSampleRates, *kbps = kKbps;
+    const int *rates = kSampleRates;
     if (channels < 1 || channels > 6) return 0;
     c->nch = channels;
     if (acmod < 0) {
@@ -222,7 +223,7 @@ int enc_config(int freq, int bitrate, int channels, EncConfig *c, int acmod, int
     c->bsid = 8 + c->halfrate;
     bitrate /= 1000;
     int i;
-    for (i = 0; i < 19; i++) if ((kbps[i] >> c->halfrate) == bitrate) break;
+    for (i = 0; i < 19; i++) if ((int)(sync_kbps(i) >> c->halfrate) == bitrate) break;
     if (i == 19) return 0;
     c->frmsizecod = i << 1;
     c->frame_words = (bitrate * 1000 * 1536) / (freq * 16);
@@ -1247,23 +1248,18 @@ int ac3mi_imdct_batch(ac3mi_ctx *ctx, const ac3mi_xform_desc *desc, const float 
 
 int ac3mi_syncinfo(const uint8_t *buf, int *flags, int *sample_rate, int *bit_rate)
 {
-    static const int kbps[19] = {32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320, 384, 448, 512, 576, 640};
-    static const uint8_t lfebit[8] = {0x10, 0x10, 0x04, 0x04, 0x04, 0x01, 0x04, 0x01};
-    if (!buf || buf[0] != 0x0b || buf[1] != 0x77) return 0;
-    if (buf[5] >= 0x60) return 0;
-    const int bsid = buf[5] >> 3, half = bsid < 9 ? 0 : bsid - 8;
-    const int acmod = buf[6] >> 5;
-    if (flags) *flags = (((buf[6] & 0xf8) == 0x50) ? AC3MI_DOLBY : acmod) | ((buf[6] & lfebit[acmod]) ? AC3MI_LFE : 0);
-    const int code = buf[4] & 63;
-    if (code >= 38) return 0;
-    const int rate = kbps[code >> 1];
-    if (bit_rate) *bit_rate = (rate * 1000) >> half;
-    switch (buf[4] & 0xc0) {
-    case 0x00: if (sample_rate) *sample_rate = 48000 >> half; return 4 * rate;
-    case 0x40: if (sample_rate) *sample_rate = 44100 >> half; return 2 * (320 * rate / 147 + (code & 1));
-    case 0x80: if (sample_rate) *sample_rate = 32000 >> half; return 6 * rate;
-    }
-    return 0;
+    // a52_syncinfo's order (parse.c:86-129), outputs included: it writes *flags once the sync word and bsid pass, *bit_rate
+    // once frmsizecod passes as well, *sample_rate with the size.  The partial tests are the one rule's on a byte 4 of 0
+    // (which passes byte 4's part) and on frmsizecod alone (fscod 0)
+    if (!buf || !ac3mi::sync_header_ok((uint32_t)buf[0] << 8 | buf[1], 0, buf[5])) return 0;
+    const int half = ac3mi::sync_halfrate(buf[5] >> 3), acmod = buf[6] >> 5;
+    const int lfebit = 0x80 >> ac3mi::sync_lfeon_pos(acmod);            // (always in byte 6)
+    if (flags) *flags = (((buf[6] & 0xf8) == 0x50) ? AC3MI_DOLBY : acmod) | ((buf[6] & lfebit) ? AC3MI_LFE : 0);
+    if (!ac3mi::sync_frame_bytes(buf[4] & 63)) return 0;
+    if (bit_rate) *bit_rate = (int)(ac3mi::sync_kbps((buf[4] & 63) >> 1) * 1000) >> half;
+    const int size = (int)ac3mi::sync_frame_bytes(buf[4]);
+    if (size && sample_rate) *sample_rate = kSampleRates[buf[4] >> 6] >> half;
+    return size;
 }
 
 int ac3mi_crc_check_batch(ac3mi_ctx *ctx, const uint8_t *d_frames, int frame_stride, int frame_bytes, size_t n_frames,
@@ -1614,7 +1610,7 @@ int ac3mi_encode_spec_tables(int16_t *window256, uint8_t *latab256, uint16_t *ht
         if (fgain8) fgain8[i] = (uint16_t)enc_fgain(i);
     }
     for (int i = 0; i < 3; i++) if (freqs3) freqs3[i] = (uint16_t)kSampleRates[i];
-    for (int i = 0; i < 19; i++) if (bitrate19) bitrate19[i] = (uint16_t)kKbps[i];
+    for (int i = 0; i < 19; i++) if (bitrate19) bitrate19[i] = (uint16_t)sync_kbps(i);
     return AC3MI_OK;
 }
 

@@ -4,7 +4,7 @@
 // size in 16-bit words from its own header, fs58 = (fs >> 1) + (fs >> 3)).
 //
 // One wavefront per frame, four frames per workgroup, every frame of the call in one launch before the decoder's front
-// end.  The header test and the frame's size run on wave-uniform values (the frame's first two dwords, a scalar read of their
+// end.  The header test and the frame's size (sync_rule.h's) run on wave-uniform values (the frame's first two dwords, a scalar read of their
 // own); then the frame is read once into LDS (16-byte loads where base and stride allow, else dwords).  Each lane then sums
 // a chunk of C bytes of a region through the 256-entry table (LDS), and six steps combine the 64 chunk sums: crc = left * x^(8 C 2^k) + crc in GF(2)[x] / poly, the scheme of
 // the encoder's region_crc (encode.hip).  Chunks are aligned to the region's END and the front is padded with zero bytes -
@@ -13,6 +13,7 @@
 // The verdict is one byte per frame, stored by lane 0 (a vector store): bit 0 crc1's region fails, bit 1 crc2's, bit 6
 // the decoder is to treat the frame as refused (ac3mi_set_decode_crc 2), bit 7 not summed (no frame, or not this batch's).
 #include "ac3mi_internal.h"
+#include "sync_rule.h"
 
 namespace ac3mi {
 
@@ -27,8 +28,6 @@ struct CrcParams {
     int c1, c2;             // chunk bytes per lane of the two regions
     uint16_t pw1[6][16], pw2[6][16];    // pw[k][i] = x^(8 c 2^k + i) mod poly
 };
-
-__device__ const uint16_t k_crc_kbps[19] = {32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320, 384, 448, 512, 576, 640};
 
 __device__ __forceinline__ uint32_t crc_rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
@@ -60,27 +59,17 @@ __global__ __launch_bounds__(64 * CRC_WAVES) void crc_kernel(const CrcParams P)
     if (fidx >= P.n_frames) return;
     const uint8_t *src = P.frames + (size_t)fidx * P.frame_stride;
 
-    // ---- a52_syncinfo's test (parse.c:86-129) and the frame's size, on bytes 0-5; the decode call's acmod / lfeon on 6-7 ----
-    // The front ends' refusal rules (decode.hip, decode_wg.hip: parse_frame_header), restated so that a frame they refuse is not
-    // summed.  One refusal is out of reach here, a52_downmix_init_hd() < 0: it depends on the call's request only, which
-    // ac3mi_decode_planes screens before any launch; the front ends also mask bits 10 / 11 of a frame they refused themselves.
+    // ---- the header rule (sync_rule.h) and the frame's size, on bytes 0-5; the decode call's acmod / lfeon on 6-7 ----
+    // A frame the front ends refuse (decode_common.h: frame_own_bytes, then their acmod / lfeon tests) is not summed: both
+    // sides call the one rule.  One refusal is out of reach here, a52_downmix_init_hd() < 0: it depends on the call's request only,
+    // which ac3mi_decode_planes screens before any launch; the front ends also mask bits 10 / 11 of a frame they refused themselves.
     const uint32_t h0 = crc_rfl(reinterpret_cast<const uint32_t *>(src)[0]), h1 = crc_rfl(reinterpret_cast<const uint32_t *>(src)[1]);
-    const int b4 = h1 & 0xff, b5 = (h1 >> 8) & 0xff;
-    bool ok = (h0 & 0xffffu) == 0x770bu && b5 < 0x60 && (b4 & 63) < 38 && (b4 & 0xc0) != 0xc0;
-    int fbytes = 0;
-    if (ok) {
-        const int code = b4 & 63, rate = k_crc_kbps[code >> 1], fscod = b4 >> 6;
-        fbytes = fscod == 0 ? 4 * rate : fscod == 1 ? 2 * (320 * rate / 147 + (code & 1)) : 6 * rate;
-        if (fbytes > P.frame_bytes) ok = false;
-    }
+    const int fbytes = sync_header_ok_le(h0, h1) ? (int)sync_frame_bytes(h1 & 0xffu) : 0;
+    bool ok = fbytes != 0 && fbytes <= P.frame_bytes;
     if (ok && P.acmod >= 0) {
         const uint32_t w = ((h1 >> 8) & 0xff00u) | (h1 >> 24);          // bytes 6 and 7, MSB first
         const int acmod = (int)(w >> 13);
-        int pos = 3;
-        if ((acmod & 1) && acmod != 1) pos += 2;                        // cmixlev
-        if (acmod & 4) pos += 2;                                        // surmixlev
-        if (acmod == 2) pos += 2;                                       // dsurmod
-        const int lfeon = (int)((w >> (15 - pos)) & 1u);
+        const int lfeon = (int)((w >> (15 - sync_lfeon_pos(acmod))) & 1u);
         if (acmod != P.acmod || lfeon != P.lfeon) ok = false;
     }
     if (!ok) {

@@ -1,10 +1,11 @@
 // decode_common.h — device-side pieces shared by the two AC-3 front ends (decode.hip: one wavefront per stream or
-// per frame; decode_wg.hip: one workgroup per stream, one wavefront per channel, transform fused in): bit reader,
-// exponent decode (L52/parse.c:218-270), parametric bit allocation (L52/bit_allocate.c:124-265), dither access.
+// per frame; decode_wg.hip: one workgroup per stream, one wavefront per channel, transform fused in): frame staging, the
+// header decision (sync_rule.h's rule) and the BSI skip, bit reader, exponent decode (L52/parse.c:218-270), parametric bit allocation (L52/bit_allocate.c:124-265), dither access.
 #pragma once
 #include <type_traits>
 #include "ac3mi_internal.h"
 #include "a52_levels.h"
+#include "sync_rule.h"
 #include "wave_ops.h"
 
 namespace ac3mi {
@@ -26,7 +27,6 @@ __device__ const int k_remat_edge[5] = {13, 25, 37, 61, 253};
 __device__ const int k_slowgain[4] = {0x540, 0x4d8, 0x478, 0x410};
 __device__ const int k_dbpb[4] = {0xc00, 0x500, 0x300, 0x100};
 __device__ const int k_floors[8] = {0x910, 0x950, 0x990, 0x9d0, 0xa10, 0xa90, 0xb10, 0x1400};
-__device__ const uint16_t k_kbps[19] = {32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320, 384, 448, 512, 576, 640};
 
 // channel slots: 0..4 = fbw, 5 = lfe, 6 = coupling channel
 struct DecLDS {
@@ -67,20 +67,50 @@ __device__ __forceinline__ int32_t speek(const FrameBits fr, uint32_t pos, int n
     return ((int32_t)(peek(fr, pos, n) << (32 - n))) >> (32 - n);
 }
 
-// A frame shorter than the batch's frame_bytes (a 44.1 kHz stream's short frame, a batch of several bit rates): the staging
-// loops mask and pad at frame_bytes, so the staged words still hold what the slot holds behind the frame's own last byte.
+// Stage the frame_bytes bytes at src (dword-aligned; the slot is a whole number of dwords): byte-swapped dwords, the last
+// partial word masked, six zero words behind them.  Thread t of nt stages the words t, t + nt, ... - and trim_staged_frame
+// below, called with the same t and nt (mant_kernel, mantx_kernel), clears words of that same set, so a thread's trim stores
+// follow its own staging stores in order and nothing has to separate the two; the caller's barrier ahead of the readers
+// covers both.  (A caller that trims with another t and nt - decode_wg_kernel's parser wave - does so behind a barrier.)
+__device__ __forceinline__ void stage_frame(uint32_t *frw, const uint8_t *src, int frame_bytes, int t, int nt)
+{
+    const uint32_t *s32 = reinterpret_cast<const uint32_t *>(src);
+    const int nw = (frame_bytes + 3) >> 2;
+    for (int i = t; i < nw + 6; i += nt) {
+        uint32_t v = 0;
+        if (i < nw) {
+            v = s32[i];
+            const int rem = frame_bytes - 4 * i;
+            if (rem < 4) v &= (1u << (8 * rem)) - 1u;
+            v = __builtin_bswap32(v);
+        }
+        frw[i] = v;
+    }
+}
+
+// A frame shorter than the batch's frame_bytes (a 44.1 kHz stream's short frame, a batch of several bit rates): staging masks
+// and pads at frame_bytes, so the staged words still hold what the slot holds behind the frame's own last byte.
 // That is not the frame's and reads as zero (include/ac3mi.h, ac3mi_decode_desc.frame_bytes), as it does to liba52's caller's
 // padded buffer, to frame_gather_kernel and to crc_kernel: thread t of nt clears it - the bytes of the staged word that
 // holds byte fbytes from that byte on (a staged word is byte-swapped: its first byte is its top one), and the words behind
-// it up to nw.  Only frames whose mantissas run on behind their own end read there.  Thread t takes the words t, t + nt,
-// ... - the words it staged itself in every staging loop, so its own stores stay in order and nothing has to separate the
-// two; the caller's barrier ahead of the readers covers both.
+// it up to nw.  Only frames whose mantissas run on behind their own end read there.
 __device__ __forceinline__ void trim_staged_frame(uint32_t *frw, int fbytes, int nw, int t, int nt)
 {
     const int w = fbytes >> 2, keep = fbytes & 3;
     int i = t;
     if (i < w) i += (w - t + nt - 1) / nt * nt;
     for (; i < nw; i += nt) frw[i] = (i == w && keep) ? frw[i] & (0xffffffffu << (8 * (4 - keep))) : 0u;
+}
+
+// The front ends' decision on a staged frame's head (w0 = frw[0], w1 = frw[1], wave-uniform): the frame's own size in bytes, or
+// 0 - the header rule (sync_rule.h) refuses it, or it is longer than frame_bytes, the largest frame of the batch (44.1 kHz
+// alternates).  A size below frame_bytes is the caller's to trim (above), with the fence that suits its kernel.
+__device__ __forceinline__ int frame_own_bytes(uint32_t w0, uint32_t w1, int frame_bytes)
+{
+    const uint32_t b4 = w1 >> 24, b5 = (w1 >> 16) & 0xffu;
+    if (!sync_header_ok(w0 >> 16, b4, b5)) return 0;
+    const int fbytes = (int)sync_frame_bytes(b4);
+    return fbytes <= frame_bytes ? fbytes : 0;
 }
 
 struct Rd {                                   // wave-uniform serial reader
@@ -118,6 +148,27 @@ struct Rd {                                   // wave-uniform serial reader
     }
     __device__ __forceinline__ void skip(uint32_t n) { seek(pos() + n); }
 };
+
+// The BSI behind lfeon, which the decoder reads past (a52_frame, parse.c:131-205): dialnorm, compr, langcod, audprodi (twice for 1+1),
+// copyrightb + origbs, the two timecodes, addbsi.  R: a reader with get(n) - Rd above, the workgroup kernel's VRd
+template <class R>
+__device__ __forceinline__ void skip_bsi_tail(R &rd, bool dual_mono)
+{
+    int twice = dual_mono;
+    do {
+        rd.get(5);
+        if (rd.get(1)) rd.get(8);
+        if (rd.get(1)) rd.get(8);
+        if (rd.get(1)) rd.get(7);
+    } while (twice--);
+    rd.get(2);
+    if (rd.get(1)) rd.get(14);
+    if (rd.get(1)) rd.get(14);
+    if (rd.get(1)) {
+        int len = rd.get(6);
+        do rd.get(8); while (len--);
+    }
+}
 
 __device__ __forceinline__ float sf_of(int e) { return __int_as_float((127 - 15 - e) << 23); }   // 2^-(15+e)
 

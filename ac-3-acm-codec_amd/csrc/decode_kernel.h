@@ -1,5 +1,6 @@
 // decode_kernel.h — decode_kernel<MODE, FX, SRC>, the front end of decode.hip (see there), as a header: decode.hip instantiates
 // it, and decode_src.hip instantiates the one variant that must not share a translation unit with its twin.
+// Which heads it refuses and a frame's own size: frame_own_bytes (decode_common.h) on sync_rule.h, as the workgroup kernel.
 #pragma once
 #include "decode_common.h"
 #include "mant2.h"
@@ -151,28 +152,22 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
         Rd rd{FB, 0, 0, 0};
-        // ---- a52_syncinfo (parse.c:86-129) + a52_frame (parse.c:131-205) ----
+        // ---- a52_syncinfo (the header rule: sync_rule.h through frame_own_bytes) + a52_frame (parse.c:131-205) ----
         bool hdr_ok = true;
         if (const uint8_t *crcp = crc_verdicts())           // ac3mi_set_decode_crc 2: the CRC kernel's verdict (wave-uniform) refuses the frame
             if (crcp[fidx] & 0x40u) hdr_ok = false;
         {
             const uint32_t w0 = rfl(frw[0]), w1 = rfl(frw[1]);
-            const int b4 = (w1 >> 24) & 0xff, b5 = (w1 >> 16) & 0xff, b6 = (w1 >> 8) & 0xff;
-            if ((w0 >> 16) != 0x0b77) hdr_ok = false;
-            if (b5 >= 0x60) hdr_ok = false;
-            if ((b4 & 63) >= 38 || (b4 & 0xc0) == 0xc0) hdr_ok = false;
+            const int own = frame_own_bytes(w0, w1, P.frame_bytes);
+            if (!own) hdr_ok = false;
             if (hdr_ok) {
-                st.set_fscod(b4 >> 6);
-                const int bsid = b5 >> 3;
-                st.set_halfrate(bsid < 9 ? 0 : bsid - 8);
-                st.acmod = b6 >> 5;
+                st.set_fscod(w1 >> 30);                            // w1 = bytes 4-7: fscod | frmsizecod, bsid | bsmod, acmod | ...
+                st.set_halfrate(sync_halfrate((w1 >> 19) & 31));
+                st.acmod = (w1 >> 13) & 7;
                 if (st.acmod != (FX ? 7 : P.acmod)) hdr_ok = false;
-                const int code = b4 & 63, rate = k_kbps[code >> 1];
-                const int fbytes = st.fscod() == 0 ? 4 * rate : st.fscod() == 1 ? 2 * (320 * rate / 147 + (code & 1)) : 6 * rate;
-                if (fbytes > P.frame_bytes) hdr_ok = false;        // frame_bytes = the largest frame of the batch (44.1 kHz alternates)
-                else if (fbytes < P.frame_bytes) {                 // (wave-uniform) the slot's bytes behind a shorter frame are not the frame's
-                    trim_staged_frame(frw, fbytes, (P.frame_bytes + 3) >> 2, lane, 64);
-                    short_bytes = fbytes;
+                if (own < P.frame_bytes) {                         // (wave-uniform) the slot's bytes behind a shorter frame are not the frame's
+                    trim_staged_frame(frw, own, (P.frame_bytes + 3) >> 2, lane, 64);
+                    short_bytes = own;
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -196,20 +191,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                 st.dynrng = st.level = level * 2;
                 st.set_dynrnge(P.dynrng_on ? 1 : 0);
                 st.deltbae2 = 0xaaau;
-                int twice = !acmod;
-                do {
-                    rd.get(5);
-                    if (rd.get(1)) rd.get(8);
-                    if (rd.get(1)) rd.get(8);
-                    if (rd.get(1)) rd.get(7);
-                } while (twice--);
-                rd.get(2);
-                if (rd.get(1)) rd.get(14);
-                if (rd.get(1)) rd.get(14);
-                if (rd.get(1)) {
-                    int len = rd.get(6);
-                    do rd.get(8); while (len--);
-                }
+                skip_bsi_tail(rd, !acmod);
                 st.nf = FX ? 5 : k_nfchans[st.acmod];
                 if (hth_fscod != st.fscod()) {
                     if (lane < 50) L.hth[lane] = P.tab->hth[st.fscod()][lane];

@@ -87,17 +87,7 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
     const uint32_t fposv = P.frame_pos[fidx];
     const int nw = (P.frame_bytes + 3) >> 2;
     {
-        const uint32_t *s32 = reinterpret_cast<const uint32_t *>(P.frames + (size_t)fidx * P.frame_stride);
-        for (int i = tid; i < nw + 6; i += 384) {
-            uint32_t v = 0;
-            if (i < nw) {
-                v = s32[i];
-                const int rem = P.frame_bytes - 4 * i;
-                if (rem < 4) v &= (1u << (8 * rem)) - 1u;
-                v = __builtin_bswap32(v);
-            }
-            frw[i] = v;
-        }
+        stage_frame(frw, P.frames + (size_t)fidx * P.frame_stride, P.frame_bytes, tid, 384);
         // the slot's bytes behind a frame shorter than frame_bytes are not the frame's.  The parse kernel leaves such a frame's own
         // size in every block's descriptor (0: full size - every frame of a batch of one frame size); each thread clears what it staged
         if (const int own = (int)(rfl(w1v.w) >> 16)) trim_staged_frame(frw, own, nw, tid, 384);

@@ -30,6 +30,7 @@
 //
 // Built with -ffp-contract=off: dequantised coefficients are bit-identical to liba52's; the transform arithmetic is
 // xform_core.h's with its fused multiply-adds written out: the same bits as xform.hip produces from the same planes.
+// Staging, the header decision (sync_rule.h's rule) and the BSI skip are decode_common.h's, shared with decode.hip's kernels.
 #include "decode_common.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -438,28 +439,21 @@ __device__ __forceinline__ void parse_block_b(const FrameBits FB, ParserState &S
     }
 }
 
-// ---- a52_syncinfo (parse.c:86-129) + a52_frame (parse.c:131-205): frame header and BSI; returns false for a frame the
+// ---- a52_syncinfo (frame_own_bytes) + a52_frame (parse.c:131-205): frame header and BSI; returns false for a frame the
 // batch cannot hold (no sync word, other channel configuration, too long, an output liba52 would refuse) ----
 __device__ __forceinline__ bool parse_frame_header(const FrameBits FB, uint32_t *frw, ParserState &S, uint16_t *hth, const DecodeParams &P, int lane)
 {
     const uint32_t w0 = rfl(frw[0]), w1 = rfl(frw[1]);
-    const int b4 = (w1 >> 24) & 0xff, b5 = (w1 >> 16) & 0xff, b6 = (w1 >> 8) & 0xff;
-    if ((w0 >> 16) != 0x0b77) return false;
-    if (b5 >= 0x60) return false;
-    if ((b4 & 63) >= 38 || (b4 & 0xc0) == 0xc0) return false;
-    const int fscod = b4 >> 6, bsid = b5 >> 3, acmod0 = b6 >> 5;
+    const int own = frame_own_bytes(w0, w1, P.frame_bytes);
+    if (!own) return false;
+    const int fscod = w1 >> 30, acmod0 = (w1 >> 13) & 7;             // w1 = bytes 4-7: fscod | frmsizecod, bsid | bsmod, acmod | ...
     PSET(S.fscod, fscod);
-    PSET(S.halfrate, bsid < 9 ? 0 : bsid - 8);
+    PSET(S.halfrate, sync_halfrate((w1 >> 19) & 31));
     PSET(S.acmod, acmod0);
     if (acmod0 != P.acmod) return false;
-    {
-        const int code = b4 & 63, rate = k_kbps[code >> 1];
-        const int fbytes = fscod == 0 ? 4 * rate : fscod == 1 ? 2 * (320 * rate / 147 + (code & 1)) : 6 * rate;
-        if (fbytes > P.frame_bytes) return false;                // frame_bytes = the largest frame of the batch (44.1 kHz alternates)
-        if (fbytes < P.frame_bytes) {                            // (wave-uniform) the slot's bytes behind a shorter frame are not the frame's:
-            trim_staged_frame(frw, fbytes, (P.frame_bytes + 3) >> 2, lane, 64);      // cleared by the parser wave, ahead of barrier B1 of block 0
-            wave_sync();
-        }
+    if (own < P.frame_bytes) {                                   // (wave-uniform) the slot's bytes behind a shorter frame are not the frame's:
+        trim_staged_frame(frw, own, (P.frame_bytes + 3) >> 2, lane, 64);             // cleared by the parser wave, ahead of barrier B1 of block 0
+        wave_sync();
     }
     VRd rd = make_reader(FB, 6 * 8 + 3, lane);
     int acmod = acmod0;
@@ -481,20 +475,7 @@ __device__ __forceinline__ bool parse_frame_header(const FrameBits FB, uint32_t 
     PSET(S.dynrng, level * 2);
     PSET(S.dynrnge, P.dynrng_on);
     if (lane < 6) S.deltbae[lane] = 2;
-    int twice = !acmod;
-    do {
-        rd.get(5);
-        if (rd.get(1)) rd.get(8);
-        if (rd.get(1)) rd.get(8);
-        if (rd.get(1)) rd.get(7);
-    } while (twice--);
-    rd.get(2);
-    if (rd.get(1)) rd.get(14);
-    if (rd.get(1)) rd.get(14);
-    if (rd.get(1)) {
-        int len = rd.get(6);
-        do rd.get(8); while (len--);
-    }
+    skip_bsi_tail(rd, !acmod);
     PSET(S.nf, (int)k_nfchans[acmod0]);
     if (ldsu(S.hth_fscod) != fscod) {
         if (lane < 50) hth[lane] = P.tab->hth[fscod][lane];
@@ -815,22 +796,8 @@ __global__ __launch_bounds__(512, WG_LB) void decode_wg_kernel(const WgParams W)
 
         for (int f = 0; f < P.frames_per_stream; f++) {
             const size_t fidx = (size_t)s * P.frames_per_stream + f;
-            // ---- stage the frame: byte-swapped dwords, zero padded ----
-            {
-                const uint32_t *s32 = reinterpret_cast<const uint32_t *>(P.frames + fidx * P.frame_stride);
-                const int nw = (P.frame_bytes + 3) >> 2;
-                for (int i = tid; i < nw + 6; i += 512) {
-                    uint32_t v = 0;
-                    if (i < nw) {
-                        v = s32[i];
-                        const int rem = P.frame_bytes - 4 * i;
-                        if (rem < 4) v &= (1u << (8 * rem)) - 1u;
-                        v = __builtin_bswap32(v);
-                    }
-                    frw[i] = v;
-                }
-                if (tid == 0) L.exp_err = 0;
-            }
+            stage_frame(frw, P.frames + fidx * P.frame_stride, P.frame_bytes, tid, 512);
+            if (tid == 0) L.exp_err = 0;
             STAMP(0);
             wg_barrier();
             STAMP(1);

@@ -1,7 +1,8 @@
 // scan.hip — AC-3 frames found in device byte streams (ac3mi_frame_scan, ac3mi_frame_scan_batch, ac3mi_frame_gather_batch).
 // The rule is stream_convert_ac3's resync rule (run_decode in stream.hip restates it for the byte-stream layer): test a
 // header at p, hop over the frame if it is one, else move on by one byte - optionally (mode 1) with a candidate accepted only
-// when both of its CRC regions sum to 0 (crc.hip's sums).  scan_rule.h holds the header test, shared with the host twin.
+// when both of its CRC regions sum to 0 (crc.hip's sums).  The header test is sync_rule.h's; scan_rule.h holds the walk's
+// host twin.
 //
 // frame_scan_kernel: one wavefront per stream, four per workgroup.  The walk is serial per stream by design - the next
 // position depends on this header - so the parallelism is across streams; inside a stream the wave works together where there
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(64 * SCAN_WAVES) void frame_scan_kernel(const ScanP
                     const uint64_t x = mine + (uint32_t)j;
                     const uint32_t h0 = scan_align(d[(j >> 2) + 1], d[j >> 2], j & 3);
                     const uint32_t h1 = scan_align(d[(j >> 2) + 2], d[(j >> 2) + 1], j & 3);
-                    if (x > (uint64_t)p && x <= (uint64_t)last && scan_header_ok(h0, h1)) hits |= 1u << j;
+                    if (x > (uint64_t)p && x <= (uint64_t)last && sync_header_ok_le(h0, h1)) hits |= 1u << j;
                 }
             }
             const uint64_t any = __ballot(hits != 0u);

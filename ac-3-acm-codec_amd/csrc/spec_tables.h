@@ -60,7 +60,6 @@ constexpr int enc_sgain(int cod) { return cod == 0 ? 0x540 : cod == 1 ? 0x4d8 : 
 constexpr int enc_dbknee(int cod) { return cod == 0 ? 0 : 0x500 + 0x200 * cod; }
 constexpr int enc_floor(int cod) { return cod < 5 ? 0x2f0 - 0x40 * cod : cod == 5 ? 0x170 : cod == 6 ? 0x0f0 : 0xf800; }
 static const int kSampleRates[3] = {48000, 44100, 32000};
-static const int kKbps[19] = {32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320, 384, 448, 512, 576, 640};
 
 static inline void build_logadd(uint8_t *tab256)
 {
