@@ -5,6 +5,7 @@
 #include <array>
 #include <string>
 #include "../../include/ac3mi.h"
+#include "launch_rule.h"
 
 namespace ac3mi {
 
@@ -68,6 +69,16 @@ struct MixPlan {
     uint8_t nobias_mask;
 };
 
+// every coded plane is an output plane, routed to itself: no mixing
+inline bool mix_plan_identity(const MixPlan &plan)
+{
+    if (plan.n_in != plan.n_out) return false;
+    for (int o = 0; o < plan.n_out; o++)
+        for (int c = 0; c < plan.n_in; c++)
+            if (plan.mix[o][c] != (o == c ? 1 : 0)) return false;
+    return true;
+}
+
 struct XformLaunch {
     const float *coef;
     const uint8_t *blksw;
@@ -113,12 +124,12 @@ struct DecodeLaunch {
     float *dyn_out = nullptr;           // [S][F][6][2] range factors of the stream's dynamic-range words (NaN: none)
     const float *dyn_in = nullptr;      // [S][F][6][2] replacements (NaN: keep)
     const int32_t *slot;
-    // few long streams: counting pass + LFSR prefix + one wavefront per frame (decode.hip, MODE 1/2)
-    int frame_parallel;
+    // the front end and its kernels (launch_rule.h): the launchers launch choice.launch in order
+    DecChoice choice;
+    // frame-parallel (choice.fp): workspaces
     uint32_t *frame_draws;  // [S][F] workspace
     uint16_t *frame_lfsr;   // [S][F] workspace
-    // split front end (parse kernel + one wavefront per audio block): workspaces, all or none
-    int split = 0;
+    // split front end (choice.split: parse kernel + one wavefront per audio block): workspaces, all or none
     void *ws_desc = nullptr;        // [S][F][6] BlkDesc (80 bytes)
     uint8_t *ws_rows = nullptr;     // [S][F][6][7][512]
     float *ws_cplco = nullptr;      // [S][F][6][90]
@@ -128,7 +139,6 @@ struct DecodeLaunch {
     const XformLaunch *fuse = nullptr;
     // ac3mi_set_decode_crc 1 / 2: the CRC kernel's verdict byte per frame, [S][F] (crc.hip); null: the frames are not checked
     const uint8_t *crc = nullptr;
-    bool fixed_shape = true;            // ac3mi_set_fixed_shape: a 5.1 call may take the kernels with that shape compiled in (fixed51_shape)
     // ac3mi_set_encode_drc_source 1 (transcode): [S][F][6] the raw dynamic-range fields of every block the front end reads - bit 8
     // dynrnge, bits 0-7 dynrng, bit 24 dynrng2e, bits 16-23 dynrng2 (acmod 0) - for enc_dynrng_source_kernel.  Non-null: the SRC
     // instantiations of the front ends run (generic shape only); a block that is not reached leaves its word unwritten
@@ -183,14 +193,6 @@ constexpr int cpl_remat_frame_bytes(int nrow)
 constexpr int CPL_REMAT_FRAME_BYTES = cpl_remat_frame_bytes(2);
 static_assert(CPL_REMAT_FRAME_BYTES == 6 * 2 * 256 * 4 + 16 + 6 * 2 * 256 + 6 * 2 * 50 * 2 + 16 + 16, "2/0 layout");
 
-// the encoder's BSI fields (ac3mi_set_encode_metadata) in one word: dialnorm bits 0-4, bsmod 5-7, cmixlev 8-9, surmixlev
-// 10-11, dsurmod 12-13, copyrightb 14, origbs 15
-constexpr uint32_t bsi_word(int dialnorm, int bsmod, int cmixlev, int surmixlev, int dsurmod, int copyrightb, int origbs)
-{
-    return (uint32_t)dialnorm | (uint32_t)bsmod << 5 | (uint32_t)cmixlev << 8 | (uint32_t)surmixlev << 10 |
-           (uint32_t)dsurmod << 12 | (uint32_t)copyrightb << 14 | (uint32_t)origbs << 15;
-}
-constexpr uint32_t BSI_DEFAULT = bsi_word(31, 0, 1, 1, 0, 0, 1);      // the reference's fixed BSI
 // The sanitising rule (include/ac3mi.h, ac3mi_bsi_info): what a raw bsi_word becomes before the packers code it - dialnorm 0
 // (reserved) 31, cmixlev 3 and surmixlev 3 the levels liba52's tables give the reserved code (1), dsurmod 3 0; bsmod,
 // copyrightb and origbs pass.  The BSI reader (bsi.hip) and the encoder's per-frame words (encode.hip) both go through it.
@@ -285,14 +287,6 @@ hipError_t launch_loudness(const LoudnessLaunch &L, hipStream_t stream);
 hipError_t launch_loudness_read(const void *state, int n_streams, const double *tab, ac3mi_loudness_result *results, hipStream_t stream);
 hipError_t launch_loudness_words(const ac3mi_loudness_result *results, int n_streams, int frames_per_stream, uint32_t base_word,
                                  uint32_t *words, hipStream_t stream);
-
-// The shape large batches run at - 5.1: acmod 7 with the LFE, six planes in and out, five full-bandwidth channels.  The one
-// predicate behind every kernel variant that has it compiled in (ac3mi_set_fixed_shape): a launcher adds its own conditions -
-// one frame per stream, its stage's tools and taps off - and anything else takes the generic kernels.
-constexpr bool fixed51_shape(int acmod, int lfeon, int n_in, int n_out, int nfbw)
-{
-    return acmod == 7 && lfeon != 0 && n_in == 6 && n_out == 6 && nfbw == 5;
-}
 
 struct EncodeLaunch {
     EncConfig cfg;

@@ -13,7 +13,6 @@ namespace ac3mi {
 
 static std::string g_err;   // errors raised without a context
 
-static const uint8_t kNfchans[11] = {2, 1, 2, 3, 3, 4, 4, 5, 1, 1, 2};
 
 // ---------------------------------------------------------------------------
 // tables (double precision on the host, rounded once to float)
@@ -210,10 +209,10 @@ int enc_config(int freq, int bitrate, int channels, EncConfig *c, int acmod, int
         c->lfe = channels == 6;
         c->nfbw = channels > 5 ? 5 : channels;
     } else {
-        if (acmod > 7 || lfeon < 0 || lfeon > 1 || channels != kNfchans[acmod] + lfeon) return 0;
+        if (acmod > 7 || lfeon < 0 || lfeon > 1 || channels != sync_nfchans(acmod) + lfeon) return 0;
         c->acmod = acmod;
         c->lfe = lfeon;
-        c->nfbw = kNfchans[acmod];
+        c->nfbw = sync_nfchans(acmod);
     }
     bool found = false;
     for (int i = 0; i < 3 && !found; i++)
@@ -248,11 +247,11 @@ int build_mix_plan(int acmod, int lfeon, int output, MixPlan *plan)
     if ((output & AC3MI_LFE) && !lfeon) return AC3MI_ERR_ARG;
 
     memset(plan, 0, sizeof *plan);
-    plan->nfchans = kNfchans[acmod];
+    plan->nfchans = sync_nfchans(acmod);
     plan->in_lfe = lfeon ? 1 : 0;
     plan->n_in = plan->nfchans + plan->in_lfe;
     const int out_lfe = (output & AC3MI_LFE) ? 1 : 0;
-    const int nfo = kNfchans[out];
+    const int nfo = sync_nfchans(out);
     plan->n_out = nfo + out_lfe;
 
     int8_t m[5][5];
@@ -970,71 +969,6 @@ int ac3mi_fill_workspaces(ac3mi_ctx *ctx, int byte)
     return AC3MI_OK;
 }
 
-// one workgroup per stream (decode_wg.hip)?  Its eight wavefronts cut the latency of a frame to a third and nothing but the
-// frame and the PCM touches HBM, but a workgroup's wavefronts wait for each other at the block's barriers, so the chip holds
-// fewer busy wavefronts than the other front ends.  Measured on one-frame streams to s16 (round 3, profiles/decode_ab.py;
-// fused / split front end + transform / one-kernel front end + transform): 64 streams 0.084 / 0.118 / 0.167 ms, 256: 0.086 /
-// 0.121 / 0.165, 1 024: 0.188 / 0.150 / 0.184, 2 048: 0.362 / 0.186 / 0.206, 4 096: 0.70 / 0.28 / 0.28, 65 536: 10.7 / 3.5 / 4.2.
-// auto: batches of up to 512 streams of at most four frames (round 2: 1 024, against the one-kernel front end); mode 3 forces it.
-static bool use_wg_kernel(const ac3mi_ctx *ctx, int n_streams, int frames_per_stream)
-{
-    if (ctx->decode_mode) return ctx->decode_mode == 3;
-    return n_streams <= 512 && frames_per_stream <= 4;
-}
-
-// frame-parallel front end for few long streams?  (auto: more than one frame per stream and too few streams to fill
-// the chip with one wavefront each: 256 CUs x 20 wavefronts)
-static bool use_frame_parallel(const ac3mi_ctx *ctx, int n_streams, int frames_per_stream)
-{
-    if (ctx->decode_mode) return ctx->decode_mode == 5;            // (forced: also for one-frame streams, A/B runs)
-    if (frames_per_stream < 2) return false;
-    return n_streams < 5120;
-}
-
-// split front end (parse kernel, then one wavefront per audio block: decode.hip MODE 4 / 5 + mant_kernel)?  auto: yes;
-// mode 1 forces the one-kernel front end (one wavefront per stream), 4 / 5 the split one per stream / per frame.
-static bool use_split(const ac3mi_ctx *ctx)
-{
-    return ctx->decode_mode == 0 || ctx->decode_mode >= 4;
-}
-
-// ... and its mantissa kernel with the transform fused in (decode_mx.hip: no coefficient planes in HBM)?  Needs one-frame
-// streams (a block's overlap tail goes to the next block inside the frame's workgroup) and every coded plane an output
-// plane.  Mode 6: wherever that holds; auto: for s16 output only - measured per 65 536 5.1 frames (profiles/r04_kernel_stats.csv,
-// profiles/EXPERIMENTS.md): to s16 2.12 - 2.17 ms fused against 1.31 + 0.77 = 2.08 - 2.15 ms in two kernels (a wash in time,
-// 36.9 KB per frame less HBM traffic and workspace), to float 2.45 against 1.31 + 0.97 = 2.28 ms (the two kernels stay);
-// modes 4 / 5 always keep the two kernels (the bit-identity reference, A/B runs).
-static bool use_mantx(int decode_mode, int frames_per_stream, bool identity, bool s16)
-{
-    return ((decode_mode == 0 && s16) || decode_mode == 6) && frames_per_stream == 1 && identity;
-}
-
-// The decoder front end of a call.  `taps`: the call writes stage taps; `wg_planes`: the one-workgroup-per-stream kernel may
-// also write coefficient planes for the transform kernel (decode) - else it is taken only with the transform fused in.
-struct FrontEnd {
-    bool identity;      // every coded plane is an output plane
-    bool mixstate;      // liba52's overlap bookkeeping around frames with surround level 0 (ac3mi_set_mix_state)
-    bool wg, fused;     // decode_wg.hip; with the transform fused in (no workspace at all)
-    bool split, mantx;  // the split front end; its mantissa kernel with the transform fused in
-    bool fp;            // frame-parallel
-};
-static FrontEnd front_end(const ac3mi_ctx *ctx, const MixPlan &plan, int n_streams, int frames_per_stream, bool s16, bool taps,
-                          bool wg_planes)
-{
-    FrontEnd f;
-    f.identity = plan.n_in == plan.n_out;
-    for (int o = 0; o < plan.n_out && f.identity; o++)
-        for (int c = 0; c < plan.n_in; c++)
-            if (plan.mix[o][c] != (o == c ? 1 : 0)) f.identity = false;
-    f.mixstate = ctx->mix_pending && plan.surr_mask && !f.identity;
-    f.wg = use_wg_kernel(ctx, n_streams, frames_per_stream) && (wg_planes || f.identity);
-    f.fused = f.wg && f.identity && !taps;
-    f.split = !f.wg && use_split(ctx);
-    f.mantx = f.split && !taps && use_mantx(ctx->decode_mode, frames_per_stream, f.identity, s16);
-    f.fp = !f.wg && use_frame_parallel(ctx, n_streams, frames_per_stream);
-    return f;
-}
-
 // the decoder's workspaces for nfr frames: coefficient planes (ws_coef), block-switch flags with the per-frame "surround
 // level 0" flags after them at zs_off (ws_blksw), the frame-parallel front end's draw counts and LFSR states (ws_draws), the
 // split front end's descriptors, generator positions, coupling coordinates and row sets (ws_split)
@@ -1042,7 +976,7 @@ static size_t coef_bytes(size_t nfr, int n_in) { return nfr * 6 * n_in * 256 * s
 static size_t zs_off(size_t nfr, int nfchans) { return nfr * 6 * nfchans + 4; }
 static size_t split_bytes(size_t nfr) { return nfr * (6 * 80 + 16 + 6 * 90 * 4 + 6 * 7 * 512) + 256; }
 
-static int grow_front_ws(ac3mi_ctx *ctx, const FrontEnd &fe, size_t nfr)
+static int grow_front_ws(ac3mi_ctx *ctx, const DecChoice &fe, size_t nfr)
 {
     if (fe.fp) TRY(ws_grow(ctx, ctx->ws_draws, nfr * 4 + nfr * 2 + 256));
     if (fe.split) TRY(ws_grow(ctx, ctx->ws_split, split_bytes(nfr)));
@@ -1073,7 +1007,7 @@ static int crc_pass(ac3mi_ctx *ctx, const ac3mi_decode_desc *desc, const uint8_t
 
 // The DecodeLaunch of a call: its frames, descriptor and state, and the front end's workspaces (grow_front_ws).  Coefficient
 // planes, flags, taps and a fused transform are the caller's.
-static DecodeLaunch decode_launch(const ac3mi_ctx *ctx, const FrontEnd &fe, const ac3mi_decode_desc *desc, const uint8_t *frames,
+static DecodeLaunch decode_launch(const ac3mi_ctx *ctx, const DecChoice &fe, const ac3mi_decode_desc *desc, const uint8_t *frames,
                                   int frame_stride, int n_streams, int frames_per_stream, uint16_t *lfsr, uint32_t *status)
 {
     const size_t nfr = (size_t)n_streams * frames_per_stream;
@@ -1093,15 +1027,13 @@ static DecodeLaunch decode_launch(const ac3mi_ctx *ctx, const FrontEnd &fe, cons
     D.status = status;
     D.lfsr = lfsr;
     D.slot = ctx->slots;
-    D.fixed_shape = ctx->fixed_shape != 0;
     D.tap_exp = nullptr;
     D.tap_bap = nullptr;
-    D.frame_parallel = fe.fp ? 1 : 0;
+    D.choice = fe;
     D.frame_draws = fe.fp ? ctx->ws_draws.at<uint32_t>() : nullptr;
     D.frame_lfsr = fe.fp ? ctx->ws_draws.at<uint16_t>(nfr * 4) : nullptr;
     if (fe.split) {
         uint8_t *p = ctx->ws_split.at<uint8_t>();
-        D.split = 1;
         D.ws_desc = p;
         D.ws_fpos = (uint32_t *)(p + nfr * 6 * 80);
         D.ws_cplco = (float *)(p + nfr * (6 * 80 + 16));
@@ -1197,7 +1129,7 @@ size_t ac3mi_transcode_workspace_plan(size_t frames, int frames_per_stream, int 
 {
     // what ac3mi_transcode_batch grows for a call (or tile) of `frames` frames in the default decode mode, with the
     // per-frame level flags and the split front end: the call's own expressions (n_in == n_out stands for identity routing)
-    const bool mantx = use_mantx(0, frames_per_stream, n_in == n_out, true);
+    const bool mantx = dec_mantx(0, frames_per_stream, n_in == n_out, true);
     return (mantx ? 0 : coef_bytes(frames, n_in)) + (zs_off(frames, nfchans) + frames) + split_bytes(frames) +
            s16_ws_bytes(frames, n_out) + enc_ws_layout(frames * 6 * (size_t)n_out).need;
 }
@@ -1442,7 +1374,7 @@ int ac3mi_decode_planes(const ac3mi_decode_desc *desc, int *n_out, int *out_flag
     const int out = a52_granted_output(desc->flags & AC3MI_CHANNEL_MASK, desc->acmod);
     if (out < 0) return AC3MI_ERR_ARG;
     const int lfe = (desc->lfeon && (desc->flags & AC3MI_LFE)) ? AC3MI_LFE : 0;
-    if (n_out) *n_out = kNfchans[out] + (lfe ? 1 : 0);
+    if (n_out) *n_out = sync_nfchans(out) + (lfe ? 1 : 0);
     if (out_flags) *out_flags = out | lfe;
     return AC3MI_OK;
 }
@@ -1470,7 +1402,9 @@ static int decode_impl(ac3mi_ctx *ctx, const ac3mi_decode_desc *desc, const uint
         return AC3MI_ERR_ARG;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const FrontEnd fe = front_end(ctx, X.plan, n_streams, frames_per_stream, d_pcm16 != nullptr, taps != nullptr, true);
+    // the front end (launch_rule.h); the one-workgroup-per-stream kernel may also write planes for the transform kernel
+    const DecChoice fe = dec_choice(ctx->decode_mode, n_streams, frames_per_stream, d_pcm16 != nullptr, taps != nullptr, true, mix_plan_identity(X.plan),
+                                    ctx->mix_pending && X.plan.surr_mask, ctx->fixed_shape != 0, desc->acmod, desc->lfeon ? 1 : 0, false);
     if (const int g = (taps || fe.fused) ? 0 : tile_streams(ctx, n_streams, frames_per_stream)) {
         // bounded workspace: whole streams at a time (streams are independent; state arrays move with them)
         TileState tile(ctx, n_out, false, frames_per_stream);
@@ -1746,7 +1680,9 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     }
     const size_t nfr = (size_t)n_streams * frames_per_stream;
     // workspaces: decoder planes, s16 PCM (the transform writes s16 itself: no float PCM in between), the front end's, the encoder's
-    const FrontEnd fe = front_end(ctx, X.plan, n_streams, frames_per_stream, true, false, false);   // wg: only fused (s16 PCM itself)
+    // the front end (launch_rule.h): s16 PCM itself, so the one-workgroup-per-stream kernel only with the transform fused in
+    const DecChoice fe = dec_choice(ctx->decode_mode, n_streams, frames_per_stream, true, false, false, mix_plan_identity(X.plan),
+                                    ctx->mix_pending && X.plan.surr_mask, ctx->fixed_shape != 0, dd.acmod, dd.lfeon ? 1 : 0, t.drc_source == 1 && nfr);
     TRY(ws_grow(ctx, ctx->ws_coef, fe.mantx ? 0 : coef_bytes(nfr, X.plan.n_in)));
     TRY(ws_grow(ctx, ctx->ws_blksw, zs_off(nfr, X.plan.nfchans) + (fe.mixstate ? nfr : 0)));
     TRY(ws_grow(ctx, ctx->ws_tc, s16_ws_bytes(nfr, n_out)));

@@ -147,12 +147,16 @@ extern "C" __attribute__((visibility("default"))) int ac3mi_debug_dec_cycles(uns
 namespace ac3mi {
 #endif
 
-hipError_t launch_mantx(const DeviceTables &tab, const DecodeLaunch &L, const MantParams &M, bool fixed51, hipStream_t stream);       // decode_mx.hip
+hipError_t launch_mantx(const DeviceTables &tab, const DecodeLaunch &L, const MantParams &M, const KernelLaunch &k, hipStream_t stream);     // decode_mx.hip
 void launch_decode0_src(const DecodeParams &P, unsigned n_streams, size_t fr_bytes, hipStream_t stream);         // decode_src.hip
 
-hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStream_t stream)
+hipError_t decode_params(const DeviceTables &tab, const DecodeLaunch &L, DecodeParams &P)
 {
-    DecodeParams P;
+    const bool split = L.choice.split;
+    P.desc = split ? (BlkDesc *)L.ws_desc : nullptr;
+    P.rows = split ? L.ws_rows : nullptr;
+    P.cplco = split ? L.ws_cplco : nullptr;
+    P.frame_pos = split ? L.ws_fpos : nullptr;
     P.frames = L.frames;
     P.coef = L.coef;
     P.blksw = L.blksw;
@@ -174,75 +178,74 @@ hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStre
     P.dynrng_on = L.dynrng_on;
     P.acmod = L.acmod;
     P.lfeon = L.lfeon;
-    static const int nfch[8] = {2, 1, 2, 3, 3, 4, 4, 5};
-    P.nfchans = nfch[L.acmod & 7];
+    P.nfchans = sync_nfchans(L.acmod & 7);
     P.n_in = P.nfchans + (L.lfeon ? 1 : 0);
-    if (L.n_streams <= 0 || L.frames_per_stream <= 0) return hipSuccess;
     P.frame_draws = L.frame_draws;
     P.frame_lfsr = L.frame_lfsr;
-    P.desc = nullptr;
-    P.rows = nullptr;
-    P.cplco = nullptr;
-    P.frame_pos = nullptr;
     P.dyn_out = L.dyn_out;
     P.dyn_in = L.dyn_in;
     P.crc = L.crc;
-    const bool src = L.src_dyn != nullptr;
-    if (src) {                          // the raw words take the tap's slot: never with gains applied, or with the tap
+    if (L.src_dyn) {                    // the raw words take the tap's slot: never with gains applied, or with the tap
         if (L.dynrng_on || L.dyn_out || L.dyn_in) return hipErrorInvalidValue;
         P.src_dyn = L.src_dyn;
     }
+    return hipSuccess;
+}
+
+// decode_kernel under a word of DECODE_VARIANTS (null: decode_src.hip's, launched there)
+template <uint32_t V> constexpr auto decode_variant()
+{
+    using Fn = void (*)(DecodeParams);
+    if constexpr (V == V_SRC) return (Fn) nullptr;
+    else return (Fn)decode_kernel<(int)(V & V_NUM), (V & V_FX) != 0, (V & V_SRC) != 0>;
+}
+template <uint32_t V> struct DecodeVariant { static constexpr auto fn = decode_variant<V>(); };
+
+// the kernels of L.choice (launch_rule.h: dec_choice) in order
+hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStream_t stream)
+{
+    DecodeParams P;
+    const hipError_t ep = decode_params(tab, L, P);
+    if (ep != hipSuccess) return ep;
+    if (L.n_streams <= 0 || L.frames_per_stream <= 0) return hipSuccess;
+    const DecChoice &c = L.choice;
+    if (c.err || c.wg) return hipErrorInvalidValue;
     static const int lds_pad = getenv("AC3MI_DEC_LDS_PAD") ? atoi(getenv("AC3MI_DEC_LDS_PAD")) : 0;      // profiling aid: occupancy sweeps
-    const size_t fr_bytes = (size_t)(((L.frame_bytes + 3) >> 2) + 6) * 4 + lds_pad;
-    const unsigned units = (unsigned)L.n_streams * (unsigned)L.frames_per_stream;
-    if (L.split) {
-        // parse (per stream, or per frame + the generator's prefix), then one wavefront per audio block
-        P.desc = (BlkDesc *)L.ws_desc;
-        P.rows = L.ws_rows;
-        P.cplco = L.ws_cplco;
-        P.frame_pos = L.ws_fpos;
-        // the fixed-shape rule (ac3mi_set_fixed_shape): one-frame 5.1 streams whose six planes are the output's (the fused
-        // kernel's calls), no stage taps - parse and mantissa kernel with that shape compiled in.  Same results either way
-        const bool fx = !src && L.fixed_shape && L.fuse && L.frames_per_stream == 1 && !L.tap_exp && !L.tap_bap &&
-                        fixed51_shape(L.acmod, L.lfeon, P.n_in, L.fuse->plan.n_out, P.nfchans);
-        if (!L.frame_parallel && fx) hipLaunchKernelGGL((decode_kernel<4, true>), dim3(L.n_streams), dim3(64), fr_bytes, stream, P);
-        else if (!L.frame_parallel && src) hipLaunchKernelGGL((decode_kernel<4, false, true>), dim3(L.n_streams), dim3(64), fr_bytes, stream, P);
-        else if (!L.frame_parallel) hipLaunchKernelGGL(decode_kernel<4>, dim3(L.n_streams), dim3(64), fr_bytes, stream, P);
-        else {
-            if (src) hipLaunchKernelGGL((decode_kernel<5, false, true>), dim3(units), dim3(64), fr_bytes, stream, P);
-            else hipLaunchKernelGGL(decode_kernel<5>, dim3(units), dim3(64), fr_bytes, stream, P);
-            hipLaunchKernelGGL(lfsr_prefix_kernel, dim3((L.n_streams + 63) / 64), dim3(64), 0, stream, (const uint32_t *)L.frame_draws,
-                               (uint16_t *)nullptr, L.ws_fpos, L.lfsr, L.slot, tab.lfsr_seq, tab.lfsr_idx, L.n_streams, L.frames_per_stream);
-        }
-        MantParams M;
-        M.frames = L.frames;
-        M.desc = (const BlkDesc *)L.ws_desc;
-        M.rows = L.ws_rows;
-        M.cplco = L.ws_cplco;
-        M.frame_pos = L.ws_fpos;
-        M.coef = L.coef;
-        M.lfsr_seq = tab.lfsr_seq;
-        M.tab = tab.dec;
-        M.n_frames = units;
-        M.frame_stride = L.frame_stride;
-        M.frame_bytes = L.frame_bytes;
-        M.acmod = L.acmod;
-        M.lfeon = L.lfeon;
-        M.n_in = P.n_in;
-        M.nfchans = P.nfchans;
-        static const int mant_pad = getenv("AC3MI_MANT_LDS_PAD") ? atoi(getenv("AC3MI_MANT_LDS_PAD")) : 0;      // profiling aid: occupancy proxy of a fused mantissa + transform workgroup
-        if (L.fuse) return launch_mantx(tab, L, M, fx, stream);         // one-frame streams, no downmix: the transform in the same kernel
-        hipLaunchKernelGGL(mant_kernel, dim3(units), dim3(384), (size_t)(((L.frame_bytes + 3) >> 2) + 6) * 4 + mant_pad, stream, M);
-        return hipGetLastError();
+    static const int mant_pad = getenv("AC3MI_MANT_LDS_PAD") ? atoi(getenv("AC3MI_MANT_LDS_PAD")) : 0;      // profiling aid: occupancy proxy of a fused mantissa + transform workgroup
+    const size_t fr_bytes = staged_frame_lds(L.frame_bytes);
+    for (int i = 0; i < c.n; i++) {
+        const KernelLaunch &k = c.launch[i];
+        const dim3 grid(grid_size(k, L.n_streams, L.frames_per_stream, 1)), block(k.block);
+        if (k.family == K_DECODE && k.variant == V_SRC) launch_decode0_src(P, grid.x, fr_bytes + lds_pad, stream);
+        else if (k.family == K_DECODE) {
+            const auto fn = variant_fn<DECODE_VARIANTS, DecodeVariant>(k.variant);
+            if (!fn) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(fn, grid, block, fr_bytes + lds_pad, stream, P);
+        } else if (k.family == K_LFSR_PREFIX) {
+            hipLaunchKernelGGL(lfsr_prefix_kernel, grid, block, 0, stream, (const uint32_t *)L.frame_draws, (uint16_t *)nullptr, L.ws_fpos,
+                               L.lfsr, L.slot, tab.lfsr_seq, tab.lfsr_idx, L.n_streams, L.frames_per_stream);
+        } else if (k.family == K_MANT || k.family == K_MANTX) {
+            MantParams M;
+            M.frames = L.frames;
+            M.desc = (const BlkDesc *)L.ws_desc;
+            M.rows = L.ws_rows;
+            M.cplco = L.ws_cplco;
+            M.frame_pos = L.ws_fpos;
+            M.coef = L.coef;
+            M.lfsr_seq = tab.lfsr_seq;
+            M.tab = tab.dec;
+            M.n_frames = grid.x;
+            M.frame_stride = L.frame_stride;
+            M.frame_bytes = L.frame_bytes;
+            M.acmod = L.acmod;
+            M.lfeon = L.lfeon;
+            M.n_in = P.n_in;
+            M.nfchans = P.nfchans;
+            if (k.family == K_MANTX) return launch_mantx(tab, L, M, k, stream);     // the transform in the same kernel
+            hipLaunchKernelGGL(mant_kernel, grid, block, fr_bytes + mant_pad, stream, M);
+        } else return hipErrorInvalidValue;
     }
-    if (!L.frame_parallel) {
-        if (src) launch_decode0_src(P, (unsigned)L.n_streams, fr_bytes, stream);
-        else hipLaunchKernelGGL(decode_kernel<0>, dim3(L.n_streams), dim3(64), fr_bytes, stream, P);
-        return hipGetLastError();
-    }
-    // (rounds 1-2 also had a one-kernel front end per FRAME for few long streams - counting pass, generator prefix, full pass;
-    // the split front end's per-frame parse kernel replaced it in round 3 and it was retired in round 4)
-    return hipErrorInvalidValue;
+    return hipGetLastError();
 }
 
 }  // namespace ac3mi

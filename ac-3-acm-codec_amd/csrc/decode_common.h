@@ -260,6 +260,9 @@ struct DecodeParams {
     const uint8_t *crc;           // optional [S][F] verdicts of crc_kernel: bits 0-1 -> status bits 10-11, bit 6: refuse the frame
 };
 
+// a call's DecodeParams (decode.hip): everything but the workspaces a front end does not have stays null
+hipError_t decode_params(const DeviceTables &tab, const DecodeLaunch &L, DecodeParams &P);
+
 // DecodeParams::crc, read from the kernel-argument segment where it is used (behind an opaque offset, so the load is not
 // hoisted): the front ends sit on spilled scalar registers, and a pointer held across a frame would cost them two more.
 // Holds ONLY for kernels whose first argument is a DecodeParams or a struct that begins with one - decode_kernel (decode.hip)

@@ -286,9 +286,12 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
     MX_LAP(4);
 }
 
-// mant_kernel + xform_kernel in one launch (launch_decode calls this when DecodeLaunch::fuse is set)
-hipError_t launch_mantx(const DeviceTables &tab, const DecodeLaunch &L, const MantParams &M, bool fixed51, hipStream_t stream)
+template <uint32_t V> struct MantxVariant { static constexpr auto fn = mantx_kernel<(V & V_S16) != 0, (V & V_FX) != 0>; };
+
+// mant_kernel + xform_kernel in one launch (launch_decode calls this for the rule's K_MANTX launch; L.fuse is set)
+hipError_t launch_mantx(const DeviceTables &tab, const DecodeLaunch &L, const MantParams &M, const KernelLaunch &k, hipStream_t stream)
 {
+    if (!L.fuse) return hipErrorInvalidValue;
     const XformLaunch &X = *L.fuse;
     if (L.frames_per_stream != 1 || X.plan.n_in != X.plan.n_out || M.n_in > 6) return hipErrorInvalidValue;
     MantxParams Q;
@@ -306,17 +309,15 @@ hipError_t launch_mantx(const DeviceTables &tab, const DecodeLaunch &L, const Ma
     Q.bias = X.bias;
     for (int o = 0; o < 6; o++) Q.wslot[o] = 0;
     static const int lds_pad = getenv("AC3MI_MANTX_LDS_PAD") ? atoi(getenv("AC3MI_MANTX_LDS_PAD")) : 0;      // profiling aid: occupancy sweeps
-    const size_t dyn = (size_t)(((L.frame_bytes + 3) >> 2) + 6) * 4 + lds_pad;
+    if (((k.variant & V_S16) != 0) != (X.pcm16 != nullptr)) return hipErrorInvalidValue;
     if (X.pcm16) {
         int map[6];
         if (s16_channel_map(X.s16_flags, map) != X.plan.n_out || ((uintptr_t)X.pcm16 & 15)) return hipErrorInvalidValue;
         for (int w = 0; w < X.plan.n_out; w++) Q.wslot[map[w]] = (int8_t)w;
-        // (fixed51: launch_decode's fixed-shape rule held for this call)
-        if (fixed51) hipLaunchKernelGGL((mantx_kernel<true, true>), dim3(M.n_frames), dim3(384), dyn, stream, Q);
-        else hipLaunchKernelGGL(mantx_kernel<true>, dim3(M.n_frames), dim3(384), dyn, stream, Q);
-    } else {
-        hipLaunchKernelGGL(mantx_kernel<false>, dim3(M.n_frames), dim3(384), dyn, stream, Q);
     }
+    const auto fn = variant_fn<MANTX_VARIANTS, MantxVariant>(k.variant);
+    if (!fn) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fn, dim3(M.n_frames), dim3(k.block), staged_frame_lds(L.frame_bytes) + lds_pad, stream, Q);
     return hipGetLastError();
 }
 

@@ -1108,43 +1108,14 @@ __global__ __launch_bounds__(512, WG_LB) void decode_wg_kernel(const WgParams W)
     }
 }
 
+template <uint32_t V> struct WgVariant { static constexpr auto fn = decode_wg_kernel<(int)(V & V_NUM), (V & V_SRC) != 0>; };
+
 hipError_t launch_decode_wg(const DeviceTables &tab, const DecodeLaunch &D, const XformLaunch *X, int grid_cap, hipStream_t stream)
 {
     WgParams W;
     DecodeParams &P = W.d;
-    P.frames = D.frames;
-    P.coef = D.coef;
-    P.blksw = D.blksw;
-    P.zs = D.zs;
-    P.status = D.status;
-    P.lfsr_state = D.lfsr;
-    P.slot = D.slot;
-    P.tap_exp = D.tap_exp;
-    P.tap_bap = D.tap_bap;
-    P.lfsr_seq = tab.lfsr_seq;
-    P.lfsr_idx = tab.lfsr_idx;
-    P.tab = tab.dec;
-    P.n_streams = D.n_streams;
-    P.frames_per_stream = D.frames_per_stream;
-    P.frame_stride = D.frame_stride;
-    P.frame_bytes = D.frame_bytes;
-    P.req_flags = D.req_flags;
-    P.level = D.level;
-    P.dynrng_on = D.dynrng_on;
-    P.acmod = D.acmod;
-    P.lfeon = D.lfeon;
-    static const int nfch[8] = {2, 1, 2, 3, 3, 4, 4, 5};
-    P.nfchans = nfch[D.acmod & 7];
-    P.n_in = P.nfchans + (D.lfeon ? 1 : 0);
-    P.frame_draws = nullptr;
-    P.frame_lfsr = nullptr;
-    P.dyn_out = D.dyn_out;
-    P.dyn_in = D.dyn_in;
-    P.crc = D.crc;
-    if (D.src_dyn) {                    // the raw words take the tap's slot: never with gains applied, or with the tap
-        if (D.dynrng_on || D.dyn_out || D.dyn_in) return hipErrorInvalidValue;
-        P.src_dyn = D.src_dyn;
-    }
+    const hipError_t ep = decode_params(tab, D, P);
+    if (ep != hipSuccess) return ep;
     W.tw_long = tab.tw_long;
     W.tw_short = tab.tw_short;
     W.window = tab.window;
@@ -1157,15 +1128,21 @@ hipError_t launch_decode_wg(const DeviceTables &tab, const DecodeLaunch &D, cons
     for (int i = 0; i < 6; i++) W.wslot[i] = (int8_t)i;
     W.stamps = nullptr;
     if (D.n_streams <= 0 || D.frames_per_stream <= 0) return hipSuccess;
-    const size_t fr_bytes = (size_t)(((D.frame_bytes + 3) >> 2) + 6) * 4;
+    // the rule's one launch: planes (OUT 0, no X), or the transform fused in to float or s16 PCM
+    const DecChoice &c = D.choice;
+    if (c.err || !c.wg || c.n != 1 || c.launch[0].family != K_DECODE_WG) return hipErrorInvalidValue;
+    const KernelLaunch &k = c.launch[0];
+    const int out = (int)(k.variant & V_NUM);
+    if ((out != 0) != (X != nullptr) || (X && (out == 2) != (X->pcm16 != nullptr))) return hipErrorInvalidValue;
+    const auto fn = variant_fn<DECODE_WG_VARIANTS, WgVariant>(k.variant);
+    if (!fn) return hipErrorInvalidValue;
+    const size_t fr_bytes = staged_frame_lds(D.frame_bytes);
     // persistent grid: as many workgroups as the chip holds at once (each walks streams blockIdx.x, + gridDim.x, ...)
     if (grid_cap <= 0) {
         int dev = 0, cus = 256, occ = 0;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const void *fn = !X ? (const void *)decode_wg_kernel<0> : !X->pcm16 ? (const void *)decode_wg_kernel<1>
-                         : D.src_dyn ? (const void *)decode_wg_kernel<2, true> : (const void *)decode_wg_kernel<2>;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 512, fr_bytes) != hipSuccess || occ < 1) occ = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, k.block, fr_bytes) != hipSuccess || occ < 1) occ = 1;
         grid_cap = occ * cus;
     }
     int grid = D.n_streams < grid_cap ? D.n_streams : grid_cap;
@@ -1197,31 +1174,23 @@ hipError_t launch_decode_wg(const DeviceTables &tab, const DecodeLaunch &D, cons
         }
     } dump{d_stamps, stream};
 #endif
-    if (D.src_dyn && !(X && X->pcm16)) return hipErrorInvalidValue;     // the raw words are a transcode's (s16, fused)
-    if (!X) {
-        hipLaunchKernelGGL(decode_wg_kernel<0>, dim3(grid), dim3(512), fr_bytes, stream, W);
-        return hipGetLastError();
+    if (X) {
+        // fused: identity routing only (every coded plane is an output plane)
+        if (!mix_plan_identity(X->plan) || X->plan.n_in != P.n_in) return hipErrorInvalidValue;
+        W.delay = X->delay;
+        W.delay_stride = X->slot ? X->delay_stride : X->plan.n_out * 128;
+        W.bias = X->bias;
+        W.n_out = X->plan.n_out;
+        W.pcm = X->pcm;
     }
-    // fused: identity routing only (every coded plane is an output plane)
-    if (X->plan.n_in != X->plan.n_out || X->plan.n_in != P.n_in) return hipErrorInvalidValue;
-    for (int o = 0; o < X->plan.n_out; o++)
-        for (int c = 0; c < X->plan.n_in; c++)
-            if (X->plan.mix[o][c] != (o == c ? 1 : 0)) return hipErrorInvalidValue;
-    W.delay = X->delay;
-    W.delay_stride = X->slot ? X->delay_stride : X->plan.n_out * 128;
-    W.bias = X->bias;
-    W.n_out = X->plan.n_out;
-    if (X->pcm16) {
+    if (X && X->pcm16) {
         int map[6];
         if (s16_channel_map(X->s16_flags, map) != W.n_out || ((uintptr_t)X->pcm16 & 15)) return hipErrorInvalidValue;
         for (int w = 0; w < W.n_out; w++) W.wslot[map[w]] = (int8_t)w;
         W.pcm16 = X->pcm16;
-        if (D.src_dyn) hipLaunchKernelGGL((decode_wg_kernel<2, true>), dim3(grid), dim3(512), fr_bytes, stream, W);
-        else hipLaunchKernelGGL(decode_wg_kernel<2>, dim3(grid), dim3(512), fr_bytes, stream, W);
-    } else {
-        W.pcm = X->pcm;
-        hipLaunchKernelGGL(decode_wg_kernel<1>, dim3(grid), dim3(512), fr_bytes, stream, W);
+        W.pcm = nullptr;
     }
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(k.block), fr_bytes, stream, W);
     return hipGetLastError();
 }
 

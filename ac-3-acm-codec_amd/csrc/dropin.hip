@@ -37,7 +37,6 @@ __global__ __launch_bounds__(256) void convert_s16_kernel(const CvtParams P)
 // WAVE slot -> liba52 plane for the output described by `flags` (see ac3mi.h)
 int s16_channel_map(int flags, int map[6])
 {
-    static const uint8_t nfch[11] = {2, 1, 2, 3, 3, 4, 4, 5, 1, 1, 2};
     const int cfg = flags & 15;
     if (cfg > 10) return -1;
     const int lfe = (flags & 16) ? 1 : 0, o = lfe;
@@ -51,7 +50,7 @@ int s16_channel_map(int flags, int map[6])
     case 6: map[n++] = o; map[n++] = o + 1; put_lfe(); map[n++] = o + 2; map[n++] = o + 3; break;      // L R SL SR
     case 7: map[n++] = o; map[n++] = o + 2; map[n++] = o + 1; put_lfe(); map[n++] = o + 3; map[n++] = o + 4; break;
     default:
-        for (int i = 0; i < nfch[cfg]; i++) map[n++] = o + i;                                          // mono / 2 ch
+        for (int i = 0; i < sync_nfchans(cfg); i++) map[n++] = o + i;                                          // mono / 2 ch
         break;
     }
     put_lfe();

@@ -3040,28 +3040,41 @@ static hipError_t launch_drc(const EncodeLaunch &E, hipStream_t stream)
     return hipGetLastError();
 }
 
+// the kernels under the words of launch_rule.h's lists
+template <uint32_t V> struct MdctVariant {
+    static constexpr auto fn = enc_mdct_kernel<(V & V_BSW) != 0, (V & V_REMAT) != 0, (V & V_BW) != 0, (V & V_XS) != 0, (V & V_LFEROW) != 0, (V & V_FX) != 0>;
+};
+template <uint32_t V> struct CplVariant { static constexpr auto fn = enc_cpl_kernel<(V & V_BW) != 0, (V & V_XS) != 0, (V & V_R3) != 0>; };
+template <uint32_t V> struct SearchVariant {
+    static constexpr auto fn = enc_search_kernel<(int)(V & V_NUM), (V & V_CPL) != 0, (V & V_BW) != 0, (V & V_DRC) != 0, (V & V_FX) != 0, (V & V_DW) != 0>;
+};
+template <uint32_t V> struct PackfVariant {
+    static constexpr auto fn = enc_packf_kernel<(V & V_FX) != 0, (V & V_CPL) != 0, (V & V_BW) != 0, (V & V_MD) != 0, (V & V_DUAL) != 0, (V & V_DW) != 0>;
+};
+template <uint32_t V> struct PackbVariant { static constexpr auto fn = enc_packb_kernel<(V & V_MD) != 0, (V & V_DW) != 0>; };
+static_assert(ENC_MAX_COEFS == MANT_MAX_COEFS, "the rule's limit is the packers' member lists'");
+
+// one stage of the rule's chain: the kernel under its word, on its grid (a stage that does not run: nothing)
+template <const auto &LIST, template <uint32_t> class K, class Params>
+static hipError_t launch_stage(const KernelLaunch &k, const EncodeLaunch &E, size_t lds, hipStream_t stream, const Params &P)
+{
+    if (k.family == K_NONE) return hipSuccess;
+    const auto fn = variant_fn<LIST, K>(k.variant);
+    if (!fn) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fn, dim3(grid_size(k, E.n_streams, E.frames_per_stream, E.cfg.nch)), dim3(k.block), lds, stream, P);
+    return hipGetLastError();
+}
+
+// the chain of launch_rule.h's enc_choice: DRC kernels, (pre-pass,) front kernel, (LFE row, coupling, tabulation,) search,
+// packer, (history)
 hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStream_t stream)
 {
     if (E.n_streams <= 0 || E.frames_per_stream <= 0) return hipSuccess;
     const EncConfig &c = E.cfg;
-    // the call's bandwidth (ac3mi_set_encode_bandwidth): nbc coefficients per full-bandwidth channel, a coupled frame ends at
-    // cplendf.  E.bw, or any chbwcod below 50: the runtime-bandwidth variants run (mode 0 launches exactly the kernels it always did)
-    if (E.chbwcod < 0 || E.chbwcod > 50) return hipErrorInvalidValue;
-    const int nbc = 73 + 3 * E.chbwcod, cpl_endf = E.chbwcod >> 2 < 12 ? E.chbwcod >> 2 : 12;
-    const bool bw = E.bw || E.chbwcod != 50;
-    // the packers' member lists (enc_mant.h) hold the grouped mantissas of at most 5 x MAX_NBC + 7 coefficients a block
-    if (c.nfbw * nbc + 7 > MANT_MAX_COEFS) return hipErrorInvalidValue;
-    // metadata and dynamic range control: the DRC kernels write the frames' codes first; with DRC on the search costs the words
-    // (DRC variants), with either on, or a word per frame (bsi_words), the packers write them (MD variants).  All off: exactly the kernels of before
-    // Words from the caller's or the source's arrays (E.dyn_codes / E.compr_words): the DW variants of the search and the packers,
-    // which cost and write them; with neither array the kernels are the ones of before
-    const bool dw = E.dyn_codes != nullptr || E.compr_words != nullptr;
-    if (E.dyn_codes && E.drc_profile) return hipErrorInvalidValue;         // (the C API refuses the pair)
-    const bool drc = E.drc_profile != 0, md = dw || drc || E.bsi != BSI_DEFAULT || E.bsi_words != nullptr;
-    if (drc) {
-        const hipError_t ed = launch_drc(E, stream);
-        if (ed != hipSuccess) return ed;
-    }
+    const EncChoice R = enc_choice(E);
+    if (R.err) return hipErrorInvalidValue;
+    hipError_t e;
+    if (R.drc && (e = launch_drc(E, stream)) != hipSuccess) return e;
     MdctParams M;
     M.pcm = E.pcm;
     M.last = E.last;
@@ -3075,7 +3088,7 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     M.nch = c.nch;
     for (int i = 0; i < 8; i++) M.chmap[i] = E.chmap[i];
     M.slot = E.slot;
-    M.store_history = E.frames_per_stream == 1;
+    M.store_history = !R.history;
     M.x.eexp = E.ws_eexp;
     M.x.emask = E.ws_emask;
     M.x.strat = E.ws_strat;
@@ -3085,19 +3098,10 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     M.x.lfe = c.lfe;
     M.x.fscod = c.fscod;
     M.x.halfrate = c.halfrate;
-    M.x.nbc = nbc;      // the only reader of last[] is this same wavefront's block 0
+    M.x.nbc = R.nbc;    // the only reader of last[] is this same wavefront's block 0
     M.bsw = E.ws_bsw;
-    M.remat = c.acmod == 2 ? E.ws_remat : nullptr;      // (rematrixing is a 2/0 tool, with or without the LFE: other layouts ignore it)
-    const dim3 units(E.n_streams * E.frames_per_stream * c.nch), frames(E.n_streams * E.frames_per_stream);
-    // The fixed-shape rule (ac3mi_set_fixed_shape): a 5.1 call takes the kernels that have that shape compiled in
-    // (the FX / FIXED51 instantiations) - the front kernel and the search when, besides, the streams are one frame long, the
-    // bandwidth is the full one and no tool of theirs is on (fx_plain; each adds "no stage tap of mine" below).  Same bytes either way
-    const bool fixed51 = E.fixed_shape && fixed51_shape(c.acmod, c.lfe, c.nch, c.nch, c.nfbw);
-    const bool fx_plain = fixed51 && E.frames_per_stream == 1 && !bw && !E.ws_bsw && !E.ws_remat && E.cpl_begf < 0 && !drc && !dw && !E.exp_strategy;
-    // (begf > cplendf + 2: no coupling band - no frame couples, the bytes are coupling off's; dual mono's two programmes are
-    // never coupled)
-    const bool cpl = E.cpl_begf >= 0 && c.nfbw >= 2 && c.acmod != 0 && E.cpl_begf <= cpl_endf + 2;
-    if (cpl && M.remat) {
+    M.remat = R.remat ? E.ws_remat : nullptr;
+    if (R.stage[ES_PRE].family != K_NONE) {
         // coupling with rematrixing: the rows without rematrixing first (before the history is rewritten), for enc_cpl_kernel
         MdctParams M0 = M;
         M0.mdct = E.ws_cpl.prow;
@@ -3110,40 +3114,15 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
         M0.x.emask = E.ws_cpl.pemask;
         M0.x.strat = E.ws_cpl.pstrat;
         M0.x.ebits = E.ws_cpl.pebits;
-        if (M0.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, false>), units, dim3(64), 0, stream, M0);
-        else hipLaunchKernelGGL((enc_mdct_kernel<false, false>), units, dim3(64), 0, stream, M0);
-        const hipError_t e0 = hipGetLastError();
-        if (e0 != hipSuccess) return e0;
+        if ((e = launch_stage<ENC_MDCT_VARIANTS, MdctVariant>(R.stage[ES_PRE], E, 0, stream, M0)) != hipSuccess) return e;
     }
-    // (the pre-pass above keeps mode 0's strategy rule: of its exponent stage only the rows and exp_samples are read)
-    if (E.exp_strategy) {
-        if (M.remat && M.bsw && bw) hipLaunchKernelGGL((enc_mdct_kernel<true, true, true, true>), frames, dim3(128), 0, stream, M);
-        else if (M.remat && bw) hipLaunchKernelGGL((enc_mdct_kernel<false, true, true, true>), frames, dim3(128), 0, stream, M);
-        else if (M.remat && M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, true, false, true>), frames, dim3(128), 0, stream, M);
-        else if (M.remat) hipLaunchKernelGGL((enc_mdct_kernel<false, true, false, true>), frames, dim3(128), 0, stream, M);
-        else if (M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, false, false, true>), units, dim3(64), 0, stream, M);
-        else hipLaunchKernelGGL((enc_mdct_kernel<false, false, false, true>), units, dim3(64), 0, stream, M);
-    }
-    else if (M.remat && M.bsw && bw) hipLaunchKernelGGL((enc_mdct_kernel<true, true, true>), frames, dim3(128), 0, stream, M);
-    else if (M.remat && bw) hipLaunchKernelGGL((enc_mdct_kernel<false, true, true>), frames, dim3(128), 0, stream, M);
-    else if (M.remat && M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, true>), frames, dim3(128), 0, stream, M);
-    else if (M.remat) hipLaunchKernelGGL((enc_mdct_kernel<false, true>), frames, dim3(128), 0, stream, M);
-    else if (M.bsw) hipLaunchKernelGGL((enc_mdct_kernel<true, false>), units, dim3(64), 0, stream, M);
-    else if (fx_plain && !M.full_rows && !M.expo) hipLaunchKernelGGL((enc_mdct_kernel<false, false, false, false, false, true>), units, dim3(64), 0, stream, M);
-    else hipLaunchKernelGGL((enc_mdct_kernel<false, false>), units, dim3(64), 0, stream, M);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    // 2/0+LFE with rematrixing: the REMAT workgroups code channels 0 and 1, a launch of the plain kernel the LFE row beside them
-    if (M.remat && c.lfe) {
-        MdctParams ML = M;
+    if ((e = launch_stage<ENC_MDCT_VARIANTS, MdctVariant>(R.stage[ES_MDCT], E, 0, stream, M)) != hipSuccess) return e;
+    {
+        MdctParams ML = M;                              // the LFE row beside the REMAT workgroups' two channels
         ML.remat = nullptr;
-        if (E.exp_strategy) hipLaunchKernelGGL((enc_mdct_kernel<false, false, false, true, true>), frames, dim3(64), 0, stream, ML);
-        else hipLaunchKernelGGL((enc_mdct_kernel<false, false, false, false, true>), frames, dim3(64), 0, stream, ML);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
+        if ((e = launch_stage<ENC_MDCT_VARIANTS, MdctVariant>(R.stage[ES_LFEROW], E, 0, stream, ML)) != hipSuccess) return e;
     }
-    // channel coupling: layouts with two or more full-bandwidth channels
-    if (cpl) {
+    if (R.cpl) {
         CplParams C;
         C.mdct = E.ws_mdct;
         C.shift = E.ws_shift;
@@ -3157,20 +3136,9 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
         C.nfbw = c.nfbw;
         C.begf = E.cpl_begf;
         C.nfr = E.n_streams * E.frames_per_stream;
-        C.endf = bw ? cpl_endf : 12;
-        C.nbc = nbc;
-        if (M.remat && c.lfe) {                         // 2/0+LFE with rematrixing: three rows a block in the rematrixing arrays
-            if (E.exp_strategy && bw) hipLaunchKernelGGL((enc_cpl_kernel<true, true, true>), dim3(C.nfr), dim3(64), 0, stream, C);
-            else if (E.exp_strategy) hipLaunchKernelGGL((enc_cpl_kernel<false, true, true>), dim3(C.nfr), dim3(64), 0, stream, C);
-            else if (bw) hipLaunchKernelGGL((enc_cpl_kernel<true, false, true>), dim3(C.nfr), dim3(64), 0, stream, C);
-            else hipLaunchKernelGGL((enc_cpl_kernel<false, false, true>), dim3(C.nfr), dim3(64), 0, stream, C);
-        }
-        else if (E.exp_strategy && bw) hipLaunchKernelGGL((enc_cpl_kernel<true, true>), dim3(C.nfr), dim3(64), 0, stream, C);
-        else if (E.exp_strategy) hipLaunchKernelGGL((enc_cpl_kernel<false, true>), dim3(C.nfr), dim3(64), 0, stream, C);
-        else if (bw) hipLaunchKernelGGL(enc_cpl_kernel<true>, dim3(C.nfr), dim3(64), 0, stream, C);
-        else hipLaunchKernelGGL(enc_cpl_kernel<false>, dim3(C.nfr), dim3(64), 0, stream, C);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
+        C.endf = R.cpl_endf;
+        C.nbc = R.nbc;
+        if ((e = launch_stage<ENC_CPL_VARIANTS, CplVariant>(R.stage[ES_CPL], E, 0, stream, C)) != hipSuccess) return e;
     }
 
     PackParams P;
@@ -3200,7 +3168,7 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.bsid = c.bsid;
     P.frmsizecod = c.frmsizecod;
     P.frame_words = c.frame_words;
-    P.nbc = nbc;
+    P.nbc = R.nbc;
     P.chbwcod = E.chbwcod;
     const int fs = c.frame_words, fs58 = (fs >> 1) + (fs >> 3);
     auto times_x = [](uint16_t *t, uint32_t v) {                    // t[i] = v * x^i mod poly
@@ -3215,15 +3183,15 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
         times_x(P.pw2_t[k], h_gf_pow(2, 8u * P.c2 * (1u << k)));
     }
     P.snr = E.ws_snr;
-    P.memo = nullptr;
+    P.memo = R.memo ? E.ws_memo : nullptr;
     P.hint = E.search_hint;
     P.hint_stride = E.search_hint_stride;
     P.bsw = E.ws_bsw;
     P.remat = M.remat;
-    P.cpl = cpl ? E.ws_cpl : CplWs{};
-    P.cpl_begf = cpl ? E.cpl_begf : 0;
-    P.cpl_endf = bw ? cpl_endf : 12;
-    P.drc = drc ? E.ws_drc_code : nullptr;
+    P.cpl = R.cpl ? E.ws_cpl : CplWs{};
+    P.cpl_begf = R.cpl ? E.cpl_begf : 0;
+    P.cpl_endf = R.cpl_endf;
+    P.drc = R.drc ? E.ws_drc_code : nullptr;
     P.bsi = E.bsi;
     P.bsi_words = E.bsi_words;
     P.dyn = E.dyn_codes;
@@ -3235,59 +3203,13 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.marker = getenv("AC3MI_ENC_MARKER") ? atoi(getenv("AC3MI_ENC_MARKER")) : 128;      // test aid (read per launch), see PackParams::marker
     static const int lds_pad = getenv("AC3MI_ENC_LDS_PAD") ? atoi(getenv("AC3MI_ENC_LDS_PAD")) : 0;      // profiling aid: occupancy sweeps
     const size_t fr_lds = (size_t)P.frw * 4 + lds_pad;
-    // The SNR-offset searches run one wavefront per stream (PART 1; for few long streams behind PART 3's frame-parallel
-    // tabulation), then every frame is packed by a workgroup of six wavefronts, one per audio block (enc_packb_kernel).
-    // Measured per call on one-frame streams, cold (profiles/encode_cold.py, end of round 3): 64 frames 0.107 against 0.162 ms
-    // with one wavefront per frame, 256: 0.111 / 0.168, 512: 0.134 / 0.179, 1 024: 0.191 / 0.192, 2 048: 0.291 / 0.262,
-    // 4 096: 0.497 / 0.394, 8 192: 0.917 / 0.700 - a frame's chain is a sixth as long, but a workgroup's wavefronts wait for each
-    // other five times per frame, so the chip holds fewer busy wavefronts: the block packer takes batches of up to 1 024
-    // frames (the byte-stream layer's chunks), one wavefront per frame the rest.
-    // E.pack_mode (ac3mi_set_encode_mode): 0 = that rule, 1 = never, 2 = always the block packer.
-    const unsigned nfr = (unsigned)E.n_streams * (unsigned)E.frames_per_stream;
-    const bool long_streams = E.frames_per_stream > 1 && E.n_streams < 5120;
-    // (coupled frames are packed by enc_packf_kernel<false> only)
-    const bool packb = !cpl && (E.pack_mode == 2 || (E.pack_mode == 0 && nfr <= 1024));
-    // Always two steps: the searches (enc_search_kernel), then the packers - one wavefront per frame (enc_packf_kernel) beyond
-    // 1 024 frames.  (Rounds 1-3 also had a one-kernel packer per stream; it held neither half's registers comfortably.)
-    P.memo = long_streams && E.n_streams < 2048 ? E.ws_memo : nullptr;      // worth its cost only when the per-stream replay is the long pole
-    // (the uncoupled search and enc_packb_kernel take nbc / chbwcod at run time in every mode; bw picks the variants whose coupling
-    // end or 5.1 band edge is a run-time value)
-    // (the same chains for DRC on / off and MD on / off: D and X below are std::bool_constant tags)
-    // (... and for the array words: W)
-    auto searches = [&](auto D, auto W) {
-        constexpr bool DRC = decltype(D)::value, DW = decltype(W)::value;
-        if (P.memo) {
-            if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<3, true, true, DRC, false, DW>), dim3(nfr), dim3(64), 0, stream, P);
-            else if (cpl) hipLaunchKernelGGL((enc_search_kernel<3, true, false, DRC, false, DW>), dim3(nfr), dim3(64), 0, stream, P);
-            else hipLaunchKernelGGL((enc_search_kernel<3, false, false, DRC, false, DW>), dim3(nfr), dim3(64), 0, stream, P);
-        }
-        if (cpl && bw) hipLaunchKernelGGL((enc_search_kernel<1, true, true, DRC, false, DW>), dim3(E.n_streams), dim3(64), 0, stream, P);
-        else if (cpl) hipLaunchKernelGGL((enc_search_kernel<1, true, false, DRC, false, DW>), dim3(E.n_streams), dim3(64), 0, stream, P);
-        else if (!DRC && fx_plain && !P.memo && !P.tap_strat && !P.tap_snr)
-            hipLaunchKernelGGL((enc_search_kernel<1, false, false, false, true>), dim3(E.n_streams), dim3(64), 0, stream, P);
-        else hipLaunchKernelGGL((enc_search_kernel<1, false, false, DRC, false, DW>), dim3(E.n_streams), dim3(64), 0, stream, P);
-    };
-    auto packers = [&](auto X, auto W) {
-        constexpr bool MD = decltype(X)::value, DW = decltype(W)::value;
-        if (packb) hipLaunchKernelGGL((enc_packb_kernel<MD, DW>), dim3(nfr), dim3(384), fr_lds, stream, P);
-        else if (cpl && bw) hipLaunchKernelGGL((enc_packf_kernel<false, true, true, MD, false, DW>), dim3(nfr), dim3(64), fr_lds, stream, P);
-        else if (cpl) hipLaunchKernelGGL((enc_packf_kernel<false, true, false, MD, false, DW>), dim3(nfr), dim3(64), fr_lds, stream, P);
-        else if (fixed51 && bw) hipLaunchKernelGGL((enc_packf_kernel<true, false, true, MD, false, DW>), dim3(nfr), dim3(64), fr_lds, stream, P);
-        else if (fixed51 && P.nbc == 223) hipLaunchKernelGGL((enc_packf_kernel<true, false, false, MD, false, DW>), dim3(nfr), dim3(64), fr_lds, stream, P);
-        else if (c.acmod == 0) hipLaunchKernelGGL((enc_packf_kernel<false, false, false, MD, true, DW>), dim3(nfr), dim3(64), fr_lds, stream, P);
-        else hipLaunchKernelGGL((enc_packf_kernel<false, false, false, MD, false, DW>), dim3(nfr), dim3(64), fr_lds, stream, P);
-    };
-    if (dw) searches(std::true_type{}, std::true_type{});
-    else if (drc) searches(std::true_type{}, std::false_type{});
-    else searches(std::false_type{}, std::false_type{});
-    if (dw) packers(std::true_type{}, std::true_type{});
-    else if (md) packers(std::true_type{}, std::false_type{});
-    else packers(std::false_type{}, std::false_type{});
-    e = hipGetLastError();
+    if ((e = launch_stage<ENC_SEARCH_VARIANTS, SearchVariant>(R.stage[ES_TABULATE], E, 0, stream, P)) != hipSuccess) return e;
+    if ((e = launch_stage<ENC_SEARCH_VARIANTS, SearchVariant>(R.stage[ES_SEARCH], E, 0, stream, P)) != hipSuccess) return e;
+    e = R.packb ? launch_stage<ENC_PACKB_VARIANTS, PackbVariant>(R.stage[ES_PACK], E, fr_lds, stream, P)
+                : launch_stage<ENC_PACKF_VARIANTS, PackfVariant>(R.stage[ES_PACK], E, fr_lds, stream, P);
     if (e != hipSuccess) return e;
     // the new history: last 256 samples per channel of each stream's final frame
-    if (M.store_history) return hipSuccess;
-    return launch_enc_history(E, stream);
+    return R.history ? launch_enc_history(E, stream) : hipSuccess;
 }
 
 __global__ void enc_history_kernel(const int16_t *pcm, int16_t *last, int n_streams, int frames, int nch, const uint8_t c0,

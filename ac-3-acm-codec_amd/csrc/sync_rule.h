@@ -43,6 +43,14 @@ __host__ __device__ inline bool sync_header_ok_le(uint32_t w0, uint32_t w1)
     return (w0 & 0xffffu) == 0x770bu && (w1 & 0xff00u) < 0x6000u && (w1 & 63u) < 38u && (w1 & 0xc0u) != 0xc0u;
 }
 
+// full-bandwidth channels of an acmod (A/52 table 5.8) and of liba52's three output configurations behind them (8 and 9:
+// one programme of dual mono, 10: Dolby surround stereo); the kernels read k_nfchans (decode_common.h)
+__host__ __device__ inline int sync_nfchans(int cfg)
+{
+    constexpr uint8_t n[11] = {2, 1, 2, 3, 3, 4, 4, 5, 1, 1, 2};
+    return n[cfg];
+}
+
 __host__ __device__ inline int sync_halfrate(int bsid) { return bsid < 9 ? 0 : bsid - 8; }
 
 // lfeon's place in bytes 6-7 taken as a 16-bit word, counted from the word's top bit: behind acmod and the two-bit cmixlev,
