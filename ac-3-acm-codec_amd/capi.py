@@ -88,6 +88,25 @@ def loudness_result_dtype():
     return dt
 
 
+class TruePeakResultC(ctypes.Structure):
+    """ac3mi_truepeak_result"""
+    _fields_ = [("true_peak_index", ctypes.c_uint64), ("samples", ctypes.c_uint64), ("true_peak", ctypes.c_uint32),
+                ("sample_peak", ctypes.c_uint32), ("full_scale", ctypes.c_uint32), ("slot_true_peak", ctypes.c_uint32 * 6),
+                ("slot_sample_peak", ctypes.c_uint32 * 6), ("dbtp", ctypes.c_float), ("dbfs", ctypes.c_float),
+                ("true_peak_slot", ctypes.c_uint8), ("sample_peak_slot", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 9)]
+
+
+def truepeak_result_dtype():
+    """ac3mi_truepeak_result as a numpy structured dtype (96 bytes; a uint8 tensor [..., 96] views as it)"""
+    import numpy as np
+    dt = np.dtype([("true_peak_index", "<u8"), ("samples", "<u8"), ("true_peak", "<u4"), ("sample_peak", "<u4"), ("full_scale", "<u4"),
+                   ("slot_true_peak", "<u4", (6,)), ("slot_sample_peak", "<u4", (6,)), ("dbtp", "<f4"), ("dbfs", "<f4"),
+                   ("true_peak_slot", "u1"), ("sample_peak_slot", "u1"), ("flags", "u1"), ("reserved", "u1", (9,))])
+    assert dt.itemsize == ctypes.sizeof(TruePeakResultC) == 96
+    return dt
+
+
 def _struct_dtype(cls, size):
     import numpy as np
     t = {ctypes.c_uint8: "u1", ctypes.c_uint16: "<u2", ctypes.c_uint32: "<u4"}
@@ -179,6 +198,15 @@ def load_library():
     lib.ac3mi_loudness_read_batch.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
     lib.ac3mi_loudness_read.argtypes = [c_void_p, ctypes.POINTER(LoudnessResultC)]
     lib.ac3mi_loudness_words_batch.argtypes = [c_void_p, c_void_p, c_int, c_int, ctypes.c_uint32, c_void_p]
+    lib.ac3mi_truepeak_state_bytes.restype = c_size_t
+    lib.ac3mi_truepeak_state_bytes.argtypes = []
+    lib.ac3mi_truepeak_tables.argtypes = [c_void_p]
+    lib.ac3mi_truepeak_ceiling.restype = ctypes.c_uint32
+    lib.ac3mi_truepeak_ceiling.argtypes = [ctypes.c_double]
+    lib.ac3mi_truepeak_batch.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]
+    lib.ac3mi_truepeak_read_batch.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_uint32, c_void_p]
+    lib.ac3mi_truepeak_read.argtypes = [c_void_p, ctypes.c_uint32, ctypes.POINTER(TruePeakResultC)]
+    lib.ac3mi_truepeak_host.argtypes = [c_int, c_void_p, c_void_p, c_int, c_void_p]
     lib.ac3mi_set_encode_drc.argtypes = [c_void_p, c_int, c_void_p]
     lib.ac3mi_set_encode_dynrng_frames.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.ac3mi_set_encode_drc_source.argtypes = [c_void_p, c_int]

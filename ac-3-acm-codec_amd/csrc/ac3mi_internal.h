@@ -288,6 +288,18 @@ hipError_t launch_loudness_read(const void *state, int n_streams, const double *
 hipError_t launch_loudness_words(const ac3mi_loudness_result *results, int n_streams, int frames_per_stream, uint32_t base_word,
                                  uint32_t *words, hipStream_t stream);
 
+// truepeak.hip: the true-peak meter (ac3mi_truepeak_*; the rule is include/ac3mi.h's, its steps truepeak_rule.h's).  No table
+// and no workspace in device memory
+struct TruePeakLaunch {
+    const int16_t *pcm;             // [S][F][1536][channels]
+    int channels;
+    uint8_t role[6];
+    int n_streams, frames_per_stream;
+    void *state;                    // [S] TruePeakState
+};
+hipError_t launch_truepeak(const TruePeakLaunch &L, hipStream_t stream);
+hipError_t launch_truepeak_read(const void *state, int n_streams, uint32_t ceiling_q28, ac3mi_truepeak_result *results, hipStream_t stream);
+
 struct EncodeLaunch {
     EncConfig cfg;
     const int16_t *pcm;         // [S][F][1536][nch]

@@ -1368,6 +1368,42 @@ int ac3mi_loudness_words_batch(ac3mi_ctx *ctx, const ac3mi_loudness_result *d_re
     return AC3MI_OK;
 }
 
+// (ac3mi_truepeak_state_bytes, _tables, _ceiling, _read and _host, the host side, live in truepeak.hip beside the rule)
+int ac3mi_truepeak_batch(ac3mi_ctx *ctx, int channels, const uint8_t *role, const int16_t *d_pcm, int n_streams,
+                         int frames_per_stream, void *d_state)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (channels < 1 || channels > 6 || !role || !d_pcm || !d_state || n_streams < 0 || frames_per_stream < 1 || ((uintptr_t)d_pcm & 1) ||
+        ((uintptr_t)d_state & 7)) {
+        ctx->err = "ac3mi_truepeak_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    if (n_streams == 0) return AC3MI_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    TruePeakLaunch L;
+    L.pcm = d_pcm;
+    L.channels = channels;
+    for (int c = 0; c < 6; c++) L.role[c] = c < channels ? role[c] : 0;
+    L.n_streams = n_streams;
+    L.frames_per_stream = frames_per_stream;
+    L.state = d_state;
+    HIPCHK(ctx, launch_truepeak(L, ctx->stream));
+    return AC3MI_OK;
+}
+
+int ac3mi_truepeak_read_batch(ac3mi_ctx *ctx, const void *d_state, int n_streams, uint32_t ceiling_q28, ac3mi_truepeak_result *d_results)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (!d_state || !d_results || n_streams < 0 || ((uintptr_t)d_state & 7) || ((uintptr_t)d_results & 7)) {
+        ctx->err = "ac3mi_truepeak_read_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    if (n_streams == 0) return AC3MI_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, launch_truepeak_read(d_state, n_streams, ceiling_q28, d_results, ctx->stream));
+    return AC3MI_OK;
+}
+
 int ac3mi_decode_planes(const ac3mi_decode_desc *desc, int *n_out, int *out_flags)
 {
     if (!desc || desc->acmod < 0 || desc->acmod > 7) return AC3MI_ERR_ARG;

@@ -130,6 +130,55 @@ def loudness_read(state):
     return np.frombuffer(bytes(res), capi.loudness_result_dtype())[0]
 
 
+def truepeak_state_bytes():
+    """ac3mi_truepeak_state_bytes: bytes of one stream's true-peak state (all zeros: a new stream)"""
+    return int(capi.load_library().ac3mi_truepeak_state_bytes())
+
+
+def truepeak_tables():
+    """ac3mi_truepeak_tables -> H int16 [4][12]: BS.1770-4 Annex 2's interpolator by phase, times 8192"""
+    import numpy as np
+    h = np.zeros((4, 12), np.int16)
+    if capi.load_library().ac3mi_truepeak_tables(h.ctypes.data) != 0:
+        raise capi.AC3MIError("ac3mi_truepeak_tables: bad argument")
+    return h
+
+
+def truepeak_ceiling(dbtp):
+    """ac3mi_truepeak_ceiling: a ceiling in dBTP -> the integer (2^-28 of full scale) that the read-out compares with"""
+    return int(capi.load_library().ac3mi_truepeak_ceiling(float(dbtp)))
+
+
+def truepeak_read(state, ceiling_q28=0):
+    """ac3mi_truepeak_read, the host read-out: one state's bytes (ac3mi_truepeak_state_bytes of them) -> a numpy record of
+    capi.truepeak_result_dtype()"""
+    import numpy as np
+    lib = capi.load_library()
+    data = bytes(bytearray(state))
+    if len(data) != lib.ac3mi_truepeak_state_bytes():
+        raise ValueError("a state is %d bytes" % lib.ac3mi_truepeak_state_bytes())
+    res = capi.TruePeakResultC()
+    if lib.ac3mi_truepeak_read(data, int(ceiling_q28), ctypes.byref(res)) != 0:
+        raise capi.AC3MIError("ac3mi_truepeak_read: bad argument")
+    return np.frombuffer(bytes(res), capi.truepeak_result_dtype())[0]
+
+
+def truepeak_host(roles, pcm, state=None):
+    """ac3mi_truepeak_host, the host meter (no GPU): pcm int16 [n][channels] of ONE stream, n a multiple of 1536, on the
+    state's bytes (None: a new stream) -> the new state's bytes.  roles: 0 = not measured, else measured, one per channel."""
+    import numpy as np
+    lib = capi.load_library()
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+    if pcm.ndim != 2 or pcm.shape[0] % 1536 or len(roles) != pcm.shape[1]:
+        raise ValueError("pcm is [frames * 1536][channels], one role per channel")
+    nb = lib.ac3mi_truepeak_state_bytes()
+    buf = ctypes.create_string_buffer(bytes(bytearray(state)) if state is not None else bytes(nb), nb)
+    role = (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6])
+    if lib.ac3mi_truepeak_host(int(pcm.shape[1]), role, pcm.ctypes.data, pcm.shape[0] // 1536, buf) != 0:
+        raise capi.AC3MIError("ac3mi_truepeak_host: bad argument")
+    return buf.raw
+
+
 def encode_metadata_word(**fields):
     """ac3mi_encode_metadata_word: the fields of Engine.set_encode_metadata (those not given: the defaults) -> the packed
     word; raises on a field out of range."""
@@ -547,6 +596,42 @@ class Engine:
                                                         int(frames_per_stream), ctypes.c_uint32(int(base_word) & 0xffffffff),
                                                         ctypes.c_void_p(out.data_ptr())))
         self._keep.append((results, out))
+        return out
+
+    def truepeak_batch(self, roles, pcm, state=None, wait_torch=True):
+        """ac3mi_truepeak_batch: meters pcm [S][F][1536][channels] s16 on the device (any 2-byte aligned view that is
+        contiguous) into state u8 [S][truepeak_state_bytes()] (zeros: new streams; default: allocated here) -> state.  roles:
+        0 = not measured, anything else = measured, one per channel (loudness_roles' list can be passed as it is)."""
+        import torch
+        assert pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.is_cuda and pcm.dim() == 4 and pcm.shape[2] == 1536
+        S, F, _, nch = pcm.shape
+        nb = int(self.lib.ac3mi_truepeak_state_bytes())
+        if state is None:
+            state = torch.zeros((S, nb), dtype=torch.uint8, device=pcm.device)
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == S * nb
+        if len(roles) != nch:
+            raise ValueError("one role per channel")
+        role = (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6])
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_truepeak_batch(ctypes.c_void_p(self.ctx), int(nch), role, ctypes.c_void_p(pcm.data_ptr()), int(S), int(F),
+                                                  ctypes.c_void_p(state.data_ptr())))
+        self._keep.append((pcm, state))
+        return state
+
+    def truepeak_read_batch(self, state, ceiling_q28=0, out=None, wait_torch=True):
+        """ac3mi_truepeak_read_batch: state u8 [S][truepeak_state_bytes()] -> results u8 [S][96];
+        `.cpu().numpy().view(capi.truepeak_result_dtype())[..., 0]` names the fields.  ceiling_q28: truepeak_ceiling(dBTP), 0 = none."""
+        import torch
+        nb = int(self.lib.ac3mi_truepeak_state_bytes())
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.is_cuda and state.numel() % nb == 0
+        S = state.numel() // nb
+        if out is None:
+            out = torch.zeros((S, 96), dtype=torch.uint8, device=state.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == S * 96
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_truepeak_read_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(state.data_ptr()), int(S),
+                                                       ctypes.c_uint32(int(ceiling_q28)), ctypes.c_void_p(out.data_ptr())))
+        self._keep.append((state, out))
         return out
 
     def set_encode_drc(self, profile, state=None):

@@ -395,6 +395,74 @@ int ac3mi_loudness_read(const void *h_state, ac3mi_loudness_result *out);
 int ac3mi_loudness_words_batch(ac3mi_ctx *ctx, const ac3mi_loudness_result *d_results, int n_streams, int frames_per_stream,
                                uint32_t base_word, uint32_t *d_words);
 
+/* True peak and clipping on the device (new): the maximum true-peak level after ITU-R BS.1770-4 Annex 2, the sample peak and
+ * the number of full-scale samples of the same s16 PCM, per stream, with the state carried from call to call - a second meter
+ * beside the loudness one, independent of it.  The whole rule, exact 32-bit integer arithmetic throughout:
+ *   input      d_pcm [n_streams][frames_per_stream][1536][channels] s16 interleaved, as ac3mi_loudness_batch takes it.
+ *   roles      per input slot: 0 = not measured, anything else = measured (the array ac3mi_loudness_roles returns can be
+ *              passed as it is; a caller who wants the LFE measured sets its role to 1).  No sample rate: the rule has none.
+ *   table      H[4][12], int16, frozen (ac3mi_truepeak_tables hands it out): Annex 2's 48-tap 4x interpolator by phase,
+ *              times 8192 - every coefficient of the Recommendation is a whole multiple of 2^-13:
+ *                H[0] = {   14,   90, -161,  272,  -487, 1125, 7964,  -838,  390, -218,  122,  -68 }
+ *                H[1] = { -239,  240, -424,  730, -1364, 3810, 6388, -1641,  832, -477,  271, -155 }
+ *                H[2] = H[1] reversed,  H[3] = H[0] reversed
+ *   signal     per measured slot x[n] = the slot's sample at instant n of the stream, counted from the stream's first sample
+ *              over all calls, x[n] = 0 for n < 0;  y[4 n + p] = sum over k = 0..11 of H[p][k] x[n - k],  p = 0..3, an int32 in
+ *              units of 2^-28 of full scale: |y| <= 32768 * 16571 = 542 998 528 < 2^31, it never wraps.
+ *   state      per measured slot true_peak = max |y| (u32); true_peak_index = the smallest 4 n + p at which it occurs (u64; a
+ *              new value replaces the old only when strictly greater); sample_peak = max |x| (0..32768); full_scale = the
+ *              number of samples equal to -32768 or 32767 (u32, saturating); the last 11 samples.  Per stream `samples`, the
+ *              instants metered (u64).  An unmeasured slot's fields stay all zero.
+ *   read-out   the stream's maximum over the slots - the larger value, then the smaller index, then the lower slot - with its
+ *              slot and index; the sample peak and its slot (the lower on a tie); full_scale summed over the slots,
+ *              saturating; the per-slot peaks;  dbtp = 20 log10(true_peak / 2^28) and dbfs = 20 log10(sample_peak / 32768) as
+ *              floats, informative, -200 when the integer is 0;  AC3MI_TRUEPEAK_EMPTY when samples == 0 or no slot was
+ *              measured;  AC3MI_TRUEPEAK_OVER when true_peak > ceiling_q28 (an argument of the read; 0 = no ceiling) - decided
+ *              on integers.
+ * The result is the same bits for every way of cutting a stream into calls, for either alignment of d_pcm, and on the host
+ * twins, which run the same rule code sample by sample. */
+typedef struct {
+    uint64_t true_peak_index;       /* the smallest 4 n + p at which true_peak occurs (in true_peak_slot) */
+    uint64_t samples;               /* sample instants metered */
+    uint32_t true_peak;             /* max |y| over the measured slots, 2^-28 of full scale: the pinned quantity */
+    uint32_t sample_peak;           /* max |x|, 0..32768 */
+    uint32_t full_scale;            /* samples equal to -32768 or 32767, all slots, saturating */
+    uint32_t slot_true_peak[6];
+    uint32_t slot_sample_peak[6];
+    float dbtp, dbfs;               /* informative; -200 when the integer is 0 */
+    uint8_t true_peak_slot, sample_peak_slot;
+    uint8_t flags;                  /* AC3MI_TRUEPEAK_EMPTY, AC3MI_TRUEPEAK_OVER */
+    uint8_t reserved[9];            /* 0 */
+} ac3mi_truepeak_result;            /* 96 bytes */
+#define AC3MI_TRUEPEAK_EMPTY 1      /* nothing was metered */
+#define AC3MI_TRUEPEAK_OVER 2       /* true_peak > ceiling_q28 */
+
+/* Bytes of one stream's state.  Opaque, in the caller's device memory, d_state[n_streams] records of this size (8-byte
+ * aligned); all zeros is a new stream, and every ac3mi_truepeak_batch reads and rewrites it.  It is indexed by the stream's
+ * position in the call, like the loudness state. */
+size_t ac3mi_truepeak_state_bytes(void);
+/* The frozen table: h48 = H[4][12], row by row. */
+int ac3mi_truepeak_tables(int16_t *h48);
+/* floor(2^28 * 10^(dbtp / 20)) clamped to a u32: a ceiling in dBTP (-1 for EBU R128, -2 for ATSC A/85) as the integer the
+ * read-out compares with.  Once, on the host. */
+uint32_t ac3mi_truepeak_ceiling(double dbtp);
+/* Meters frames_per_stream more frames of every stream, one wavefront per stream, asynchronous on the context's stream.
+ * d_pcm 2-byte aligned (a 16-byte aligned base is read with 16-byte loads, same bits); nothing outside
+ * [d_pcm, d_pcm + n_streams * frames_per_stream * 3072 * channels) is read; no workspace and no table in device memory.
+ * AC3MI_ERR_ARG, with the state untouched: channels outside 1..6, a NULL or misaligned pointer, frames_per_stream < 1,
+ * n_streams < 0.  n_streams 0: AC3MI_OK, nothing is launched.  The same PCM may go to ac3mi_loudness_batch before or after. */
+int ac3mi_truepeak_batch(ac3mi_ctx *ctx, int channels, const uint8_t *role, const int16_t *d_pcm, int n_streams,
+                         int frames_per_stream, void *d_state);
+/* The read-out of n_streams states into d_results[n_streams] (8-byte aligned), one stream per lane; the states are not
+ * changed. */
+int ac3mi_truepeak_read_batch(ac3mi_ctx *ctx, const void *d_state, int n_streams, uint32_t ceiling_q28,
+                              ac3mi_truepeak_result *d_results);
+/* Host twin of the read-out, no GPU and no context: the same rule code on one state copied to host memory (any alignment). */
+int ac3mi_truepeak_read(const void *h_state, uint32_t ceiling_q28, ac3mi_truepeak_result *out);
+/* Host twin of the meter, no GPU and no context: `frames` more frames of ONE stream, h_pcm [frames][1536][channels], sample by
+ * sample on a state in host memory (any alignment).  The same errors. */
+int ac3mi_truepeak_host(int channels, const uint8_t *role, const int16_t *h_pcm, int frames, void *h_state);
+
 /* How ac3mi_encode_batch / ac3mi_transcode_batch pack a frame once its SNR offsets are found (new; same bytes either way -
  * the searches always run first, one wavefront per stream, frames in order):
  *   1  one wavefront per frame packs it;
