@@ -80,14 +80,12 @@ __global__ __launch_bounds__(384, MANT_LB) void mant_kernel(const MantParams P)
     const uint4 w0v = dq[0], w1v = dq[1], w2v = dq[2], w3v = dq[3], w4v = dq[4];
     const uint32_t fposv = P.frame_pos[fidx];
     const int nw = (P.frame_bytes + 3) >> 2;
-    {
-        stage_frame(frw, P.frames + (size_t)fidx * P.frame_stride, P.frame_bytes, tid, 384);
-        // the slot's bytes behind a frame shorter than frame_bytes are not the frame's.  The parse kernel leaves such a frame's own
-        // size in every block's descriptor (0: full size - every frame of a batch of one frame size); each thread clears what it staged
-        if (const int own = (int)(rfl(w1v.w) >> 16)) trim_staged_frame(frw, own, nw, tid, 384);
-        if (tid < M2_NDESC) L.dsc[tid] = mant_desc2((uint32_t)tid);
-        for (int i = tid; i < 760; i += 384) L.qtab[i] = P.tab->qtab[i];
-    }
+    // the frame's words and the thread's two dequantiser words are all requested before the first is waited for (as
+    // mantx_kernel, decode_mx.hip; its earlier row request is not taken over: here it cost 12 bytes of scratch)
+    const auto fw = stage_frame_fetch<384>(P.frames + (size_t)fidx * P.frame_stride, P.frame_bytes, tid);
+    const float q0 = P.tab->qtab[tid];
+    float q1 = 0.f;
+    if (tid < 760 - 384) q1 = P.tab->qtab[384 + tid];
     float *cblk = P.coef + unit * P.n_in * 256;
     const uint32_t flags = rfl(w0v.z);
     const bool failed = (flags & 1u) != 0u;
@@ -102,6 +100,15 @@ __global__ __launch_bounds__(384, MANT_LB) void mant_kernel(const MantParams P)
         if (slot == 5) return lane < 7 ? make_uint2(br[lane], er[lane]) : make_uint2(1u, 0u);
         return make_uint2(reinterpret_cast<const uint32_t *>(br)[lane], reinterpret_cast<const uint32_t *>(er)[lane]);
     };
+    {
+        stage_frame_store<384>(frw, fw, P.frame_bytes, tid);
+        // the slot's bytes behind a frame shorter than frame_bytes are not the frame's.  The parse kernel leaves such a frame's own
+        // size in every block's descriptor (0: full size - every frame of a batch of one frame size); each thread clears what it staged
+        if (const int own = (int)(rfl(w1v.w) >> 16)) trim_staged_frame(frw, own, nw, tid, 384);
+        if (tid < M2_NDESC) L.dsc[tid] = mant_desc2((uint32_t)tid);
+        L.qtab[tid] = q0;
+        if (tid < 760 - 384) L.qtab[384 + tid] = q1;
+    }
     // the first segment's rows are requested before the workgroup meets at the barrier
     const int slot0 = seg_slot(0, B.nf, B.chincpl, B.chincpl ? __builtin_ctz(B.chincpl) : 99);
     uint2 first = make_uint2(0u, 0u);
@@ -152,6 +159,7 @@ void launch_decode0_src(const DecodeParams &P, unsigned n_streams, size_t fr_byt
 
 hipError_t decode_params(const DeviceTables &tab, const DecodeLaunch &L, DecodeParams &P)
 {
+    if (L.frame_bytes > STAGE_MAX_BYTES) return hipErrorInvalidValue;      // (stage_frame's fixed words per thread; the C entry points refuse it first)
     const bool split = L.choice.split;
     P.desc = split ? (BlkDesc *)L.ws_desc : nullptr;
     P.rows = split ? L.ws_rows : nullptr;

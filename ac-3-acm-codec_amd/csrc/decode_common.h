@@ -68,24 +68,56 @@ __device__ __forceinline__ int32_t speek(const FrameBits fr, uint32_t pos, int n
 }
 
 // Stage the frame_bytes bytes at src (dword-aligned; the slot is a whole number of dwords): byte-swapped dwords, the last
-// partial word masked, six zero words behind them.  Thread t of nt stages the words t, t + nt, ... - and trim_staged_frame
+// partial word masked, six zero words behind them.  Thread t of NT stages the words t, t + NT, ... - and trim_staged_frame
 // below, called with the same t and nt (mant_kernel, mantx_kernel), clears words of that same set, so a thread's trim stores
 // follow its own staging stores in order and nothing has to separate the two; the caller's barrier ahead of the readers
 // covers both.  (A caller that trims with another t and nt - decode_wg_kernel's parser wave - does so behind a barrier.)
-__device__ __forceinline__ void stage_frame(uint32_t *frw, const uint8_t *src, int frame_bytes, int t, int nt)
+//
+// In two steps, so that a kernel's set-up is one round trip to memory instead of one per word and table: stage_frame_fetch
+// only ISSUES the thread's loads - a fixed number of guarded, straight-line ones (a loop over the words was compiled as load,
+// wait, store per turn) - the caller issues its other set-up loads behind them, and stage_frame_store, which is the first to
+// wait, masks, swaps and stores.  K words per thread cover the largest frame the host lets through (decode_params): 3840
+// bytes = 960 + 6 words are three each for the 384 threads of the mantissa kernels, two for decode_wg_kernel's 512.
+constexpr int STAGE_MAX_BYTES = 3840;
+constexpr int stage_words(int nt) { return ((STAGE_MAX_BYTES + 3) / 4 + 6 + nt - 1) / nt; }
+template <int K> struct StagedWords { uint32_t v[K]; };
+
+template <int NT>
+__device__ __forceinline__ StagedWords<stage_words(NT)> stage_frame_fetch(const uint8_t *src, int frame_bytes, int t)
 {
     const uint32_t *s32 = reinterpret_cast<const uint32_t *>(src);
     const int nw = (frame_bytes + 3) >> 2;
-    for (int i = t; i < nw + 6; i += nt) {
-        uint32_t v = 0;
+    StagedWords<stage_words(NT)> W;
+#pragma unroll
+    for (int k = 0; k < stage_words(NT); k++) {
+        const int i = t + k * NT;
+        W.v[k] = 0;
+        if (i < nw) W.v[k] = s32[i];
+    }
+    return W;
+}
+
+template <int NT>
+__device__ __forceinline__ void stage_frame_store(uint32_t *frw, const StagedWords<stage_words(NT)> &W, int frame_bytes, int t)
+{
+    const int nw = (frame_bytes + 3) >> 2;
+#pragma unroll
+    for (int k = 0; k < stage_words(NT); k++) {
+        const int i = t + k * NT;
+        uint32_t v = W.v[k];
         if (i < nw) {
-            v = s32[i];
             const int rem = frame_bytes - 4 * i;
             if (rem < 4) v &= (1u << (8 * rem)) - 1u;
             v = __builtin_bswap32(v);
         }
-        frw[i] = v;
+        if (i < nw + 6) frw[i] = v;
     }
+}
+
+template <int NT>
+__device__ __forceinline__ void stage_frame(uint32_t *frw, const uint8_t *src, int frame_bytes, int t)
+{
+    stage_frame_store<NT>(frw, stage_frame_fetch<NT>(src, frame_bytes, t), frame_bytes, t);
 }
 
 // A frame shorter than the batch's frame_bytes (a 44.1 kHz stream's short frame, a batch of several bit rates): staging masks

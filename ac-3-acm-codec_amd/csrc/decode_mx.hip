@@ -86,19 +86,19 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
     const uint4 w0v = dq[0], w1v = dq[1], w2v = dq[2], w3v = dq[3], w4v = dq[4];
     const uint32_t fposv = P.frame_pos[fidx];
     const int nw = (P.frame_bytes + 3) >> 2;
-    {
-        stage_frame(frw, P.frames + (size_t)fidx * P.frame_stride, P.frame_bytes, tid, 384);
-        // the slot's bytes behind a frame shorter than frame_bytes are not the frame's.  The parse kernel leaves such a frame's own
-        // size in every block's descriptor (0: full size - every frame of a batch of one frame size); each thread clears what it staged
-        if (const int own = (int)(rfl(w1v.w) >> 16)) trim_staged_frame(frw, own, nw, tid, 384);
-        if (tid < M2_NDESC) L.dsc[tid] = mant_desc2((uint32_t)tid);
-        for (int i = tid; i < 760; i += 384) L.qtab[i] = P.tab->qtab[i];
-        if (tid < 128) L.tw[0][tid] = Q.tw_long[tid];
-        else if (tid < 256) L.tw[1][tid - 128] = Q.tw_short[tid - 128];
-        else L.win[tid - 256] = Q.window[tid - 256];
-        if (tid < 128) L.win[128 + tid] = Q.window[128 + tid];
-        if (tid < 6) L.ready[tid] = 0u;
-    }
+    // Set-up.  Every load is issued before the first wait on any of them (a copy loop, or a load and its LDS store inside one
+    // branch, was a round trip to memory each: profiles/EXPERIMENTS.md): the frame's words, which miss in cache, then the
+    // chip-resident tables - two dequantiser words a thread, and ONE float2 of the twiddles and the window, which lie
+    // back to back in LDS (wavefronts 0-1 the long twiddles, 2-3 the short ones, 4-5 the window as 128 pairs).  The first
+    // use of any of it is the descriptor's, for the one dependent request - the first segment's rows - which then travels
+    // while the LDS stores wait for the words requested before it, and on across the barrier.
+    static_assert(offsetof(MantxLDS, win) == offsetof(MantxLDS, tw) + sizeof(float2) * 256, "tw and win are one 3-KB stretch");
+    const auto fw = stage_frame_fetch<384>(P.frames + (size_t)fidx * P.frame_stride, P.frame_bytes, tid);
+    const float q0 = P.tab->qtab[tid];
+    float q1 = 0.f;
+    if (tid < 760 - 384) q1 = P.tab->qtab[384 + tid];
+    const float2 *twsrc = blk < 2 ? Q.tw_long + tid : blk < 4 ? Q.tw_short + (tid - 128) : reinterpret_cast<const float2 *>(Q.window) + (tid - 256);
+    const float2 twv = *twsrc;
     uint8_t *const region = L.wave[blk];
     float *const planes = reinterpret_cast<float *>(region);
     const uint32_t flags = rfl(w0v.z);
@@ -106,7 +106,11 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
     MantBlk B;
     B.nf = nfchans; B.lfeon = FX ? 1 : P.lfeon; B.acmod = FX ? 7 : P.acmod; B.in_lfe = FX ? 1 : P.lfeon ? 1 : 0;
     B.chincpl = (int)((flags >> 8) & 31u); B.dithmask = (int)((flags >> 16) & 31u); B.rematflg = (int)((flags >> 24) & 15u);
-    const uint64_t rve = (uint64_t)rfl(w2v.x) | ((uint64_t)rfl(w2v.y) << 32), rvb = (uint64_t)rfl(w2v.z) | ((uint64_t)rfl(w2v.w) << 32);
+    // (a failed block's row indices read as 0: its request below then goes to the frame's own first row set and is never looked
+    // at.  Behind a branch on `failed` the request would not cross the barrier - the waits for the words requested before it
+    // have to assume the fewest loads in flight behind them - and it is the one load that should)
+    const uint64_t rve = failed ? 0ull : (uint64_t)rfl(w2v.x) | ((uint64_t)rfl(w2v.y) << 32);
+    const uint64_t rvb = failed ? 0ull : (uint64_t)rfl(w2v.z) | ((uint64_t)rfl(w2v.w) << 32);
     const uint8_t *rowbase = P.rows + (size_t)fidx * 6 * ROWSET;
     auto fetch = [&](int slot) -> uint2 {
         const uint8_t *er = rowbase + (size_t)((rve >> (8 * slot)) & 7u) * ROWSET + slot * 512;
@@ -114,9 +118,20 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
         if (slot == 5) return lane < 7 ? make_uint2(br[lane], er[lane]) : make_uint2(1u, 0u);
         return make_uint2(reinterpret_cast<const uint32_t *>(br)[lane], reinterpret_cast<const uint32_t *>(er)[lane]);
     };
+    __builtin_assume(B.nf >= 1);                                // (every acmod has a channel: the first segment is slot 0's, and its request below sits behind no branch)
     const int slot0 = seg_slot(0, B.nf, B.chincpl, B.chincpl ? __builtin_ctz(B.chincpl) : 99);
-    uint2 first = make_uint2(0u, 0u);
-    if (!failed) first = fetch(slot0);
+    const uint2 first = fetch(slot0);
+    {
+        stage_frame_store<384>(frw, fw, P.frame_bytes, tid);
+        // the slot's bytes behind a frame shorter than frame_bytes are not the frame's.  The parse kernel leaves such a frame's own
+        // size in every block's descriptor (0: full size - every frame of a batch of one frame size); each thread clears what it staged
+        if (const int own = (int)(rfl(w1v.w) >> 16)) trim_staged_frame(frw, own, nw, tid, 384);
+        if (tid < M2_NDESC) L.dsc[tid] = mant_desc2((uint32_t)tid);
+        L.qtab[tid] = q0;
+        if (tid < 760 - 384) L.qtab[384 + tid] = q1;
+        reinterpret_cast<float2 *>(&L.tw[0][0])[tid] = twv;
+        if (tid < 6) L.ready[tid] = 0u;
+    }
     __syncthreads();
     MX_LAP(0);
 

@@ -796,7 +796,7 @@ __global__ __launch_bounds__(512, WG_LB) void decode_wg_kernel(const WgParams W)
 
         for (int f = 0; f < P.frames_per_stream; f++) {
             const size_t fidx = (size_t)s * P.frames_per_stream + f;
-            stage_frame(frw, P.frames + fidx * P.frame_stride, P.frame_bytes, tid, 512);
+            stage_frame<512>(frw, P.frames + fidx * P.frame_stride, P.frame_bytes, tid);
             if (tid == 0) L.exp_err = 0;
             STAMP(0);
             wg_barrier();

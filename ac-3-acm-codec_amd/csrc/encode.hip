@@ -2176,7 +2176,9 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
     const int lane = threadIdx.x;
     PK_DECL();
 
-    // (byte loop kept: copying the table as dwords measured 4 % SLOWER in round 3 - code placement, not work)
+    // (loop kept.  Copying the table as dwords measured 4 % SLOWER in round 3 - code placement, not work.  Measured again as four
+    // 16-bit loads a lane issued with every other set-up load ahead of ONE wait instead of a wait per turn: 1.584 -> 1.574 ms per
+    // 65 536 frames, inside the traces' standard deviation of 0.03 - no gain to keep: profiles/EXPERIMENTS.md, set-up loads)
     for (int i = lane; i < 256; i += 64) L.crc_tab[i] = P.tab->crc_tab[i];
     {
         const int bp = P.tab->baptab[lane];
