@@ -14,6 +14,9 @@
 //  enc_packf_kernel    one wavefront per frame packs it: header, side information, exponent groups, the mantissas
 //                      (enc_mant.h), both CRCs by per-lane chunk CRC + GF(2) combine    [ac3enc.cpp:1113-1638]
 //  enc_packb_kernel    the same with a workgroup of six wavefronts per frame, one per audio block (small batches)
+//  The frame's side-information syntax - the field lists both packers write through, the field accumulator, enc_packb_kernel's
+//  closed-form counts and the search's price for the same fields - is enc_syntax.h's; here are the sink that puts the fields
+//  into the LDS frame (PackSink) and the values each kernel feeds the lists.
 //
 // Integer arithmetic only (no -ffast-math dependence); the Q15 tables come from the host (capi.hip)
 // with the reference's expressions.
@@ -21,6 +24,7 @@
 #include "wave_ops.h"
 #include "spec_tables.h"
 #include "enc_mant.h"
+#include "enc_syntax.h"
 
 #include <type_traits>
 
@@ -103,7 +107,15 @@ __device__ __forceinline__ uint32_t compr_word(const PackParams &P, size_t fidx,
     return P.compr ? (uint32_t)__builtin_amdgcn_readfirstlane((int)P.compr[fidx * 2 + p]) & 0x1ffu : 0u;
 }
 
-
+// the dynrng word programme p sends in block b of the frame, bit 8 = sent (the packers; enc_syntax.h's dynrng): the arrays' (DW
+// with P.dyn: each programme's own code and sends), else the profile's - the same word for both programmes of dual mono
+template <bool MD, bool DW>
+__device__ __forceinline__ uint32_t pack_dynrng(const PackParams &P, size_t fidx, int b, int p)
+{
+    if constexpr (DW) if (P.dyn) return dyn_sends(P.dyn + fidx * 12, b, p) ? 0x100u | P.dyn[fidx * 12 + 2 * b + p] : 0u;
+    if constexpr (MD) if (P.drc && drc_sends(P.drc + fidx * 6, b)) return 0x100u | P.drc[fidx * 6 + b];
+    return 0u;
+}
 
 // tables of the PSD / masking-curve computation
 struct MaskTabs {
@@ -142,6 +154,52 @@ __device__ __forceinline__ void put_bits(uint32_t *fr, int frw, uint32_t pos, in
     if (hi) atomicOr(&fr[w], hi);
     if (lo) atomicOr(&fr[w + 1], lo);
 }
+
+// row `row` of a block's exponent dwords (no indexing of the register array), `other` for any row but 0..5
+__device__ __forceinline__ uint32_t pick_row(const uint32_t (&ew)[6], int row, uint32_t other)
+{
+    uint32_t dw = other;
+#pragma unroll
+    for (int c2 = 0; c2 < 6; c2++) dw = c2 == row ? ew[c2] : dw;
+    return dw;
+}
+
+// The packers' sink of enc_syntax.h's field lists: the accumulator's bits reach the LDS frame from lane 0, and `flush` empties
+// it before the lanes write at `pos` themselves (exponent groups, mantissas).  One per stretch of fields that starts and ends
+// flushed - the header, each block - from the frame's bit `at`.  row_of(row): the lane's dword (four bins) of a row's encoded
+// exponents, row SYN_CPL the coupling row's, whose exponents start at bin `cs`.
+template <class Row>
+struct PackSink : SynWriter<PackSink<Row>> {
+    uint32_t *fr;
+    int frw, lane;
+    uint8_t *erow;                      // 256 bytes of LDS: the encoded exponents of the row whose groups are being packed
+    Row row_of;
+    int cs;
+    __device__ __forceinline__ PackSink(uint32_t *fr_, int frw_, int lane_, uint8_t *erow_, Row row_of_, int cs_, uint32_t at)
+        : fr(fr_), frw(frw_), lane(lane_), erow(erow_), row_of(row_of_), cs(cs_) { this->pos = at; }
+    __device__ __forceinline__ void store(uint32_t at, int n, uint32_t v) { if (lane == 0) put_bits(fr, frw, at, n, v); }
+    // a row's exponents: the absolute exponent (the coupling row's: bin cs - 1 holds 2 cplabsexp), then lanes over the ng groups.
+    // (tests/enc_syntax_c's HostSink::exponents mirrors the put(4) - flush - groups sequence: the 64-bit bound it proves
+    // holds here as long as the two keep the same flush)
+    __device__ __forceinline__ void exponents(int row, int strat, int ng)
+    {
+        const int gs = syn_grpsize(strat), first = row == SYN_CPL ? cs : 1;
+        const uint8_t *e = erow;
+        const uint32_t dw = row_of(row);
+        WAVE_SYNC();                                                // the previous row's groups have read the row
+        *reinterpret_cast<uint32_t *>(&erow[4 * lane]) = dw;
+        WAVE_SYNC();
+        this->put(4, (uint32_t)__builtin_amdgcn_readfirstlane((int)e[first - 1]) >> (row == SYN_CPL ? 1 : 0));
+        this->flush();
+        for (int g = lane; g < ng; g += 64) {
+            const int k0 = first + 3 * g * gs;
+            const int prev = g ? e[k0 - gs] : e[first - 1];
+            const int d0 = e[k0] - prev + 2, d1 = e[k0 + gs] - e[k0] + 2, d2 = e[k0 + 2 * gs] - e[k0 + gs] + 2;
+            put_bits(fr, frw, this->pos + 7 * g, 7, (uint32_t)((d0 * 5 + d1) * 5 + d2));
+        }
+        this->pos += 7 * ng;
+    }
+};
 
 // ---------------------------------------------------------------------------------------------
 // exp_stage's routines, wavefront-wide.
@@ -1108,8 +1166,6 @@ struct CplLDS {
     int sh[6][8];                       // [block][channel]: exp_samples
 };
 
-constexpr int CPL_FLEAK = 0, CPL_SLEAK = 0;     // cplfleak / cplsleak, sent with cplleake 1 in block 0
-
 __host__ __device__ constexpr int cpl_g(int nfbw) { return nfbw <= 2 ? 1 : nfbw <= 4 ? 2 : 3; }
 
 // The coordinate of one channel and band under mstrcplco M (liba52 parse.c:642-656): the largest value mant 2^-s,
@@ -1717,18 +1773,12 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
             }
             // ---- fixed side information (:880-916) ----
             {
-                // (dual mono: dialnorm2, compr2e, langcod2e, audprodi2e in the BSI; dynrng2e in every block)
-                const int extra[8] = {8, 0, 2, 2, 2, 4, 2, 4};
-                frame_bits += 65 + extra[acmod & 7];
-                frame_bits += 6 * (nfbw * 2 + 2 + (acmod == 2 ? 1 : 0) + (acmod == 0 ? 1 : 0) + 2 * nfbw + (lfe ? 1 : 0) + 1 + 1 + 2);
+                // what every frame of the layout sends (enc_syntax.h, with the reference's quirks); then what this frame adds
+                frame_bits += syn_priced_fixed(acmod, lfe, nfbw, nch);
                 // chbwcod (6 bits) and gainrng (2 bits) of every full-bandwidth channel-block that sends exponents
                 uint64_t fbw_rows = 0;
                 for (int b = 0; b < 6; b++) fbw_rows |= ((1ull << nfbw) - 1) << (6 * b);
                 frame_bits += 8 * __builtin_popcountll(row_set & fbw_rows);
-                frame_bits++;
-                frame_bits += 2 * 4 + 3 + 6 + nch * (4 + 3);
-                frame_bits += 2;
-                frame_bits += 16;
                 if constexpr (DRC) if (!DW || P.drc) {
                     const uint8_t *code = P.drc + fidx * 6;
                     for (int b = 0; b < 6; b++) frame_bits += drc_sends(code, b) ? (acmod == 0 ? 16 : 8) : 0;     // (dual mono: dynrng2 too)
@@ -1742,18 +1792,15 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                     }
                     for (int p = 0; p < np; p++) frame_bits += (compr_word(P, fidx, p) & 0x100u) ? 8 : 0;
                 }
-                // rematrixing: the four flags of every block 1..5 that sends them (block 0's stay uncounted, as above)
+                // rematrixing: the four flags of every block 1..5 that sends them (block 0's stay uncounted)
                 if (!FX && P.remat)
                     for (int b = 1; b < 6; b++) frame_bits += (P.remat[fidx * 6 + b] & 0x10) ? 4 : 0;
                 if (CPL && cplf) {
-                    // coupling: chincpl, phsflginu (2/0), cplbegf / cplendf, cplbndstrc; cplcoe, mstrcplco and the coordinates
-                    // in block 0, cplcoe 0 in blocks 1..5; cplexpstr; cplfsnroffst / cplfgaincod; cplleake (+ the two leaks in
-                    // block 0); the coupling exponents; no chbwcod for the coupled channels
-                    const int nb = cpl_nb;
-                    frame_bits += nfbw + (acmod == 2 ? 1 : 0) + 8 + (nb - 1) + nfbw * (3 + 8 * nb) + 5 * nfbw + 6 * 2 + 7 + 7 + 5;
+                    // the coupling fields; the coupling exponents; no chbwcod for the coupled channels
+                    frame_bits += syn_priced_cpl(acmod, nfbw, cpl_nb);
                     frame_bits += __builtin_amdgcn_readfirstlane(P.cpl.ebits[fidx]) - 6 * __builtin_popcountll(row_set & fbw_rows);
                     if (P.remat) {                  // a coupled frame's blocks 1..5 send liba52's cplinu-1 flag count, not 4
-                        const int nrem = P.cpl_begf == 0 ? 2 : P.cpl_begf <= 2 ? 3 : 4;
+                        const int nrem = syn_cpl_nrem(P.cpl_begf);
                         for (int b = 1; b < 6; b++) frame_bits -= (P.remat[fidx * 6 + b] & 0x10) ? 4 - nrem : 0;
                     }
                 }
@@ -2186,8 +2233,6 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
     }
     mant_lists_init(L.glist, lane);
     const uint32_t bandoff = *reinterpret_cast<const uint32_t *>(&P.tab->band_of_bin[4 * lane]);     // bands of bins 4*lane..+3
-    // fixed allocation codes (:861-879)
-    constexpr int sdecaycod = 2, fdecaycod = 1, sgaincod = 1, dbkneecod = 2, floorcod = 4, fgaincod = 4;
     const int nch = FIXED51 ? 6 : P.nch, nfbw = FIXED51 ? 5 : P.nfbw, nbc = FIXED51 && !BW ? 223 : P.nbc;
     const int acmod = FIXED51 ? 7 : P.acmod;
     const bool lfe = FIXED51 ? true : P.lfe != 0;
@@ -2200,7 +2245,7 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
     // channel coupling (enc_cpl_kernel): every full-bandwidth channel in coupling, one set of coordinates in block 0
     const uint32_t cplw = CPL ? (uint32_t)__builtin_amdgcn_readfirstlane((int)P.cpl.word[fidx]) : 0u;
     const bool cplf = (cplw & 1u) != 0;
-    const int cs = 37 + 12 * P.cpl_begf, ncb = BW ? 3 + P.cpl_endf - P.cpl_begf : 15 - P.cpl_begf;
+    const int cs = 37 + 12 * P.cpl_begf;
     const int cendf = BW ? P.cpl_endf : 12, ce = 73 + 12 * cendf;
     PK_T0();
     PK_COUNT(7);
@@ -2225,53 +2270,16 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
     PK_LAP(6);
 
     // ---- header (:1113-1147) ----
-    // Side information is wave-uniform: its fields collect in a 64-bit accumulator that stays in scalar registers and
-    // reach the LDS frame up to 64 bits at a time (one lane, two put_bits): `flush` empties it before the lanes write at
-    // `pos` themselves (exponent groups, mantissas) and wherever the next stretch of fields could overflow it - the block's
-    // first stretch is 54 bits at most, the one after the exponents 63 (block 0 of six channels).
-    uint32_t pos = 0;                   // first bit not yet in the frame
-    uint64_t acc = 0;
-    int nacc = 0;                       // pending bits, the low `nacc` of acc
-    auto put = [&](int n, uint32_t v) { acc = (acc << n) | v; nacc += n; };       // (no test per field: at most 64 bits between two flushes)
-    auto flush = [&]() {
-        if (nacc > 32) {
-            if (lane == 0) put_bits(fr, P.frw, pos, nacc - 32, (uint32_t)(acc >> 32) & (0xffffffffu >> (64 - nacc)));
-            pos += nacc - 32;
-            nacc = 32;
-        }
-        if (nacc > 0) {
-            if (lane == 0) put_bits(fr, P.frw, pos, nacc, (uint32_t)acc & (0xffffffffu >> (32 - nacc)));
-            pos += nacc;
-            nacc = 0;
-        }
-    };
-    if constexpr (MD) {
-        const uint32_t m = pack_bsi(P, fidx);
-        put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, (m >> 5) & 7u); put(3, acmod);
-        flush();
-        if ((acmod & 1) && acmod != 1) put(2, (m >> 8) & 3u);
-        if (acmod & 4) put(2, (m >> 10) & 3u);
-        if (acmod == 2) put(2, (m >> 12) & 3u);
-        if constexpr (DW) {
-            // compre (+ compr), langcode, audprodie; dual mono: dialnorm2 = dialnorm, compr2e (+ compr2), langcod2e, audprodi2e
-            auto put_compr = [&](uint32_t c) { if (c & 0x100u) { put(1, 1); put(8, c & 0xffu); } else put(1, 0); };
-            put(1, lfe); put(5, m & 31u); put_compr(compr_word(P, fidx, 0)); put(2, 0);
-            if constexpr (DUAL) { put(5, m & 31u); put_compr(compr_word(P, fidx, 1)); put(2, 0); }
-        } else {
-            put(1, lfe); put(5, m & 31u); put(3, 0);
-            if constexpr (DUAL) { put(5, m & 31u); put(3, 0); }    // dual mono: dialnorm2 = dialnorm, compr2e langcod2e audprodi2e
-        }
-        put(1, (m >> 14) & 1u); put(1, (m >> 15) & 1u); put(3, 0);
-    } else {
-        put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, 0); put(3, acmod);
-        flush();
-        if ((acmod & 1) && acmod != 1) put(2, 1);
-        if (acmod & 4) put(2, 1);
-        if (acmod == 2) put(2, 0);
-        put(1, lfe); put(5, 31); put(3, 0);
-        if constexpr (DUAL) { put(5, 31); put(3, 0); }
-        put(1, 0); put(1, 1); put(3, 0);
+    // Side information is wave-uniform: the field lists of enc_syntax.h through its 64-bit accumulator (PackSink), which stays
+    // in scalar registers.
+    uint32_t pos;                       // first bit not yet in the frame
+    {
+        PackSink k(fr, P.frw, lane, L.erow, [](int) { return 0u; }, cs, 0u);
+        syn_header(k, P.fscod, P.frmsizecod, P.bsid, acmod, lfe, DUAL, MD ? pack_bsi(P, fidx) : BSI_DEFAULT,
+                   DW ? compr_word(P, fidx, 0) : 0u, DW && DUAL ? compr_word(P, fidx, 1) : 0u);
+        pos = k.pos;
     }
+    const SynShape shape{acmod, nfbw, nch, lfe, DUAL, nbc, (uint32_t)P.chbwcod};
 
     // ---- audio blocks (:1194-1502) ----
 #pragma unroll 1
@@ -2300,130 +2308,14 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
                 if (lane + 64 * j < nch * 25) reinterpret_cast<uint32_t *>(&L.mask[0][0])[lane + 64 * j] = mant_band_terms(mv[j], snroffset);
         }
         auto strat_of = [&](int ch) { return (uint32_t)__builtin_amdgcn_readlane(strat_l, 6 * b + ch); };
-        flush();
-        if (const uint8_t *bs = P.bsw ? P.bsw + (fidx * 6 + b) * nch : nullptr)
-            for (int ch = 0; ch < nfbw; ch++) put(1, bs[ch]);
-        else
-            for (int ch = 0; ch < nfbw; ch++) put(1, 0);
-        for (int ch = 0; ch < nfbw; ch++) put(1, 1);
-        if constexpr (DW) {
-            // dynrnge + dynrng, dual mono: dynrng2e + dynrng2 - the arrays' (each programme's own code and sends), else the profile's
-            for (int p = 0; p < (DUAL ? 2 : 1); p++) {
-                const bool word = P.dyn ? dyn_sends(P.dyn + fidx * 12, b, p) : P.drc && drc_sends(P.drc + fidx * 6, b);
-                if (word) { put(1, 1); put(8, P.dyn ? P.dyn[fidx * 12 + 2 * b + p] : P.drc[fidx * 6 + b]); flush(); }
-                else put(1, 0);
-            }
-        } else if constexpr (MD) {
-            // dynrnge + dynrng (flushed: the block's first stretch of fields stays within the accumulator)
-            const bool word = P.drc && drc_sends(P.drc + fidx * 6, b);
-            if (word) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
-            else put(1, 0);
-            if constexpr (DUAL) {                   // dual mono: dynrng2e + dynrng2, the same word in the same blocks
-                if (word) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
-                else put(1, 0);
-            }
-        } else {
-            put(1, 0);
-            if constexpr (DUAL) put(1, 0);
-        }
-        if (cplf) {
-            // cplstre, cplinu, chincpl, phsflginu, cplbegf, cplendf, cplbndstrc (all 0); cplcoe, mstrcplco, the coordinates
-            if (b == 0) {
-                put(1, 1); put(1, 1);
-                for (int ch = 0; ch < nfbw; ch++) put(1, 1);
-                if (acmod == 2) put(1, 0);
-                put(4, (uint32_t)P.cpl_begf); put(4, (uint32_t)cendf); put(ncb - 1, 0);
-                flush();
-                const uint8_t *co = P.cpl.co + fidx * 80;
-                for (int ch = 0; ch < nfbw; ch++) {
-                    put(1, 1); put(2, (cplw >> (8 + 2 * ch)) & 3u);
-                    for (int bd = 0; bd < ncb; bd++) { put(8, co[ch * 16 + bd]); if ((bd & 3) == 3) flush(); }
-                    flush();
-                }
-            } else {
-                put(1, 0);
-                for (int ch = 0; ch < nfbw; ch++) put(1, 0);
-            }
-        } else if (b == 0) { put(1, 1); put(1, 0); } else put(1, 0);
-        if (acmod == 2) {
-            if (cplf) {                     // liba52's band set for cplinu 1: 2, 3 or 4 flags
-                const int nrem = P.cpl_begf == 0 ? 2 : P.cpl_begf <= 2 ? 3 : 4;
-                if (P.remat) {
-                    const uint32_t r = P.remat[fidx * 6 + b];
-                    put(1, r >> 4);
-                    if (r & 0x10) for (int i = 0; i < nrem; i++) put(1, (r >> i) & 1);
-                } else if (b == 0) { put(1, 1); put(nrem, 0); } else put(1, 0);
-            } else if (P.remat) {
-                const uint32_t r = P.remat[fidx * 6 + b];
-                put(1, r >> 4);
-                if (r & 0x10) { put(1, r & 1); put(1, (r >> 1) & 1); put(1, (r >> 2) & 1); put(1, (r >> 3) & 1); }
-            } else if (b == 0) { put(1, 1); put(4, 0); } else put(1, 0);
-        }
-        if (cplf) put(2, (uint32_t)cstg);
-        for (int ch = 0; ch < nfbw; ch++) put(2, strat_of(ch));
-        if (lfe) put(1, strat_of(nch - 1));
-        for (int ch = 0; ch < nfbw; ch++) if (strat_of(ch) != 0 && !cplf) put(6, P.chbwcod);
-        if (cplf && cstg != 0) {
-            // the coupling exponents: cplabsexp (bin cs - 1 holds 2 cplabsexp), groups from cplstrtmant
-            const int gs = cstg == 1 ? 1 : cstg == 2 ? 2 : 4;
-            const int ng = (ce - cs) / (3 * gs);
-            const uint8_t *e = &L.erow[0];
-            WAVE_SYNC();
-            *reinterpret_cast<uint32_t *>(&L.erow[4 * lane]) = cew;
-            WAVE_SYNC();
-            put(4, (uint32_t)__builtin_amdgcn_readfirstlane((int)e[cs - 1]) >> 1);
-            flush();
-            for (int g = lane; g < ng; g += 64) {
-                const int k0 = cs + 3 * g * gs;
-                const int prev = g ? e[k0 - gs] : e[cs - 1];
-                const int d0 = e[k0] - prev + 2, d1 = e[k0 + gs] - e[k0] + 2, d2 = e[k0 + 2 * gs] - e[k0 + gs] + 2;
-                put_bits(fr, P.frw, pos + 7 * g, 7, (uint32_t)((d0 * 5 + d1) * 5 + d2));
-            }
-            pos += 7 * ng;
-        }
-        // exponents: lanes over groups
-        for (int ch = 0; ch < nch; ch++) {
-            const int stg = (int)strat_of(ch);
-            if (stg == 0) continue;
-            const bool is_lfe = lfe && ch == nch - 1;
-            const int gs = stg == 1 ? 1 : stg == 2 ? 2 : 4;
-            const int ng = ((is_lfe ? 7 : cplf ? cs : nbc) + gs * 3 - 4) / (3 * gs);
-            const uint8_t *e = &L.erow[0];
-            {
-                uint32_t row = 0;
-#pragma unroll
-                for (int c2 = 0; c2 < 6; c2++) row = c2 == ch ? ew[c2] : row;      // (no indexing of the register array)
-                WAVE_SYNC();                                            // the previous channel's groups have read the row
-                *reinterpret_cast<uint32_t *>(&L.erow[4 * lane]) = row;
-                WAVE_SYNC();
-            }
-            put(4, (uint32_t)__builtin_amdgcn_readfirstlane((int)e[0]));
-            flush();
-            for (int g = lane; g < ng; g += 64) {
-                const int k0 = 1 + 3 * g * gs;
-                const int prev = g ? e[k0 - gs] : e[0];
-                const int d0 = e[k0] - prev + 2, d1 = e[k0 + gs] - e[k0] + 2, d2 = e[k0 + 2 * gs] - e[k0 + gs] + 2;
-                put_bits(fr, P.frw, pos + 7 * g, 7, (uint32_t)((d0 * 5 + d1) * 5 + d2));
-            }
-            pos += 7 * ng;
-            if (!is_lfe) put(2, 0);
-        }
-        if (b == 0) flush();
-        put(1, b == 0);
-        if (b == 0) { put(2, sdecaycod); put(2, fdecaycod); put(2, sgaincod); put(2, dbkneecod); put(3, floorcod); }
-        put(1, b == 0);
-        if (b == 0) {
-            put(6, csnr);
-            if (cplf) { put(4, fsnr); put(3, fgaincod); flush(); }
-            for (int ch = 0; ch < nch; ch++) { put(4, fsnr); put(3, fgaincod); }
-        }
-        if (cplf) {                         // cplleake (+ cplfleak, cplsleak in block 0)
-            put(1, b == 0);
-            if (b == 0) { put(3, CPL_FLEAK); put(3, CPL_SLEAK); }
-        }
-        put(1, 0);
-        put(1, 0);
-        flush();
+        const uint8_t *bs = P.bsw ? P.bsw + (fidx * 6 + b) * nch : nullptr;
+        PackSink k(fr, P.frw, lane, L.erow, [&](int row) { return pick_row(ew, row, cew); }, cs, pos);
+        syn_block(k, shape, SynCpl{cplw, P.cpl_begf, cendf, (uint32_t)cstg}, b,
+                  [&](int ch) -> uint32_t { return bs ? bs[ch] : 0u; },
+                  [&](int p) { return pack_dynrng<MD, DW>(P, fidx, b, p); },
+                  acmod == 2 && P.remat ? (uint32_t)P.remat[fidx * 6 + b] : b == 0 ? 0x10u : 0u, strat_of,
+                  [&](int ch, int bd) -> uint32_t { return P.cpl.co[fidx * 80 + ch * 16 + bd]; }, (uint32_t)csnr, (uint32_t)fsnr);
+        pos = k.pos;
         PK_LAP(1);
 
         // ---- mantissas (:1341-1501): enc_mant.h ----
@@ -2564,7 +2456,6 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
         fidx = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
     }
     const int nch = P.nch, nfbw = P.nfbw, nbc = P.nbc, fs = P.frame_words;
-    constexpr int sdecaycod = 2, fdecaycod = 1, sgaincod = 1, dbkneecod = 2, floorcod = 4, fgaincod = 4;
 
     for (int i = tid; i < 256; i += 384) {
         L.band_of_bin[i] = P.tab->band_of_bin[i];
@@ -2602,35 +2493,17 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
     const uint32_t bandoff = *reinterpret_cast<const uint32_t *>(&P.tab->band_of_bin[4 * lane]);
     __syncthreads();
 
-    const uint32_t strat_set = (uint32_t)__ballot(strat_l != 0);        // bit ch: the channel sends exponents in this block
-    auto strat_of = [&](int ch) { return __builtin_amdgcn_readlane(strat_l, ch); };
-    // bits of the frame header (:1113-1147) and of this block's side information with its exponents (:1194-1332)
-    int hdr_bits = 16 + 16 + 2 + 6 + 5 + 3 + 3 + (((P.acmod & 1) && P.acmod != 1) ? 2 : 0) + ((P.acmod & 4) ? 2 : 0) +
-                   (P.acmod == 2 ? 2 : 0) + 1 + 5 + 3 + (P.acmod == 0 ? 8 : 0) + 1 + 1 + 3;
-    uint32_t compr[2] = {0u, 0u};                       // (DW) the frame's compr / compr2 words
-    if constexpr (DW)
-        for (int p = 0; p < (P.acmod == 0 ? 2 : 1); p++) {
-            compr[p] = compr_word(P, fidx, p);
-            if (compr[p] & 0x100u) hdr_bits += 8;
-        }
-    int side_bits = 2 * nfbw + 1 + (P.acmod == 0 ? 1 : 0) + (b == 0 ? 2 : 1) + (P.acmod == 2 ? (b == 0 ? 5 : 1) : 0) + 2 * nfbw + (P.lfe ? 1 : 0) +
-                    1 + (b == 0 ? 11 : 0) + 1 + (b == 0 ? 6 + 7 * nch : 0) + 2;
-    const int rem = P.remat ? (int)P.remat[fidx * 6 + b] : -1;     // rematrixing: block b > 0 sends its four flags when rematstr
-    if (b > 0 && rem >= 0 && (rem & 0x10)) side_bits += 4;
-    const bool drc_word = MD && P.drc && drc_sends(P.drc + fidx * 6, b);
-    bool dyn_word[2] = {drc_word, drc_word};            // (DW) per programme
-    if constexpr (DW) {
-        if (P.dyn)
-            for (int p = 0; p < 2; p++) dyn_word[p] = dyn_sends(P.dyn + fidx * 12, b, p);
-        side_bits += (dyn_word[0] ? 8 : 0) + (P.acmod == 0 && dyn_word[1] ? 8 : 0);
-    } else if (drc_word) side_bits += P.acmod == 0 ? 16 : 8;
-    for (int ch = 0; ch < nch; ch++) {
-        const int stg = strat_of(ch);
-        if (stg == 0) continue;
-        const bool is_lfe = P.lfe && ch == nch - 1;
-        const int gs = stg == 1 ? 1 : stg == 2 ? 2 : 4;
-        side_bits += 4 + 7 * (((is_lfe ? 7 : nbc) + gs * 3 - 4) / (3 * gs)) + (is_lfe ? 0 : 8);      // (fbw: chbwcod 6 + gainrng 2)
-    }
+    const uint32_t strat_lo = (uint32_t)__ballot(strat_l & 1), strat_hi = (uint32_t)__ballot(strat_l & 2);     // bit ch: the channel's strategy, bit 0 and 1
+    auto strat_of = [&](int ch) { return ((strat_lo >> ch) & 1u) | (((strat_hi >> ch) & 1u) << 1); };
+    // the frame's compr / compr2 words (DW), this block's dynrng words and its rematrixing word; then the bits of the frame header
+    // (:1113-1147) and of this block's side information with its exponents (:1194-1332), i.e. where the blocks start:
+    // enc_syntax.h's closed forms of the two field lists written below
+    const bool dual = P.acmod == 0;
+    const uint32_t compr0 = DW ? compr_word(P, fidx, 0) : 0u, compr1 = DW && dual ? compr_word(P, fidx, 1) : 0u;
+    const uint32_t dynw0 = pack_dynrng<MD, DW>(P, fidx, b, 0), dynw1 = dual ? pack_dynrng<MD, DW>(P, fidx, b, 1) : 0u;
+    const uint32_t rem = P.acmod == 2 && P.remat ? (uint32_t)P.remat[fidx * 6 + b] : b == 0 ? 0x10u : 0u;
+    const SynShape shape{P.acmod, nfbw, nch, P.lfe != 0, dual, nbc, (uint32_t)P.chbwcod};
+    const int hdr_bits = syn_header_bits(P.acmod, compr0, compr1), side_bits = syn_block_bits(shape, b, dynw0, dynw1, rem, strat_of);
 
     // the addresses of the block's coefficients into the bap table (:393-420), four per lane and channel
     uint32_t ad[6], em[6];
@@ -2666,124 +2539,16 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
         uint32_t pos = (uint32_t)hdr_bits;
         for (int q = 0; q < b; q++) pos += attempt == 0 ? L.blk_bits[q] : L.blk_bits2[q];
 
-        // ---- side information (wave-uniform fields through a 64-bit accumulator, see enc_pack_kernel) ----
-        uint64_t acc = 0;
-        int nacc = 0;
-        auto put = [&](int n, uint32_t v) { acc = (acc << n) | v; nacc += n; };       // (no test per field: at most 64 bits between two flushes)
-        auto flush = [&]() {
-            if (nacc > 32) {
-                if (lane == 0) put_bits(fr, P.frw, pos, nacc - 32, (uint32_t)(acc >> 32) & (0xffffffffu >> (64 - nacc)));
-                pos += nacc - 32;
-                nacc = 32;
-            }
-            if (nacc > 0) {
-                if (lane == 0) put_bits(fr, P.frw, pos, nacc, (uint32_t)acc & (0xffffffffu >> (32 - nacc)));
-                pos += nacc;
-                nacc = 0;
-            }
-        };
-        if (b == 0) {                               // the frame header is block 0's to write
-            const uint32_t mine = pos;
-            pos = 0;
-            if constexpr (MD) {
-                const uint32_t m = pack_bsi(P, fidx);
-                put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, (m >> 5) & 7u); put(3, P.acmod);
-                flush();
-                if ((P.acmod & 1) && P.acmod != 1) put(2, (m >> 8) & 3u);
-                if (P.acmod & 4) put(2, (m >> 10) & 3u);
-                if (P.acmod == 2) put(2, (m >> 12) & 3u);
-                if constexpr (DW) {
-                    auto put_compr = [&](uint32_t c) { if (c & 0x100u) { put(1, 1); put(8, c & 0xffu); } else put(1, 0); };
-                    put(1, P.lfe); put(5, m & 31u); put_compr(compr[0]); put(2, 0);
-                    if (P.acmod == 0) { put(5, m & 31u); put_compr(compr[1]); put(2, 0); }
-                } else {
-                    put(1, P.lfe); put(5, m & 31u); put(3, 0);
-                    if (P.acmod == 0) { put(5, m & 31u); put(3, 0); }      // dual mono: dialnorm2 = dialnorm, compr2e langcod2e audprodi2e
-                }
-                put(1, (m >> 14) & 1u); put(1, (m >> 15) & 1u); put(3, 0);
-            } else {
-                put(16, 0x0b77); put(16, 0); put(2, P.fscod); put(6, P.frmsizecod); put(5, P.bsid); put(3, 0); put(3, P.acmod);
-                flush();
-                if ((P.acmod & 1) && P.acmod != 1) put(2, 1);
-                if (P.acmod & 4) put(2, 1);
-                if (P.acmod == 2) put(2, 0);
-                put(1, P.lfe); put(5, 31); put(3, 0);
-                if (P.acmod == 0) { put(5, 31); put(3, 0); }
-                put(1, 0); put(1, 1); put(3, 0);
-            }
-            flush();
-            pos = mine;
-        }
-        if (const uint8_t *bs = P.bsw ? P.bsw + (fidx * 6 + b) * nch : nullptr)
-            for (int ch = 0; ch < nfbw; ch++) put(1, bs[ch]);
-        else
-            for (int ch = 0; ch < nfbw; ch++) put(1, 0);
-        for (int ch = 0; ch < nfbw; ch++) put(1, 1);
-        if constexpr (DW) {
-            for (int p = 0; p < (P.acmod == 0 ? 2 : 1); p++) {
-                if (dyn_word[p]) { put(1, 1); put(8, P.dyn ? P.dyn[fidx * 12 + 2 * b + p] : P.drc[fidx * 6 + b]); flush(); }
-                else put(1, 0);
-            }
-        } else if constexpr (MD) {
-            // dynrnge + dynrng (flushed: the fields up to the first exponent would overflow the accumulator by up to 2 bits)
-            if (drc_word) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
-            else put(1, 0);
-            if (P.acmod == 0) {                     // dual mono: dynrng2e + dynrng2, the same word in the same blocks
-                if (drc_word) { put(1, 1); put(8, P.drc[fidx * 6 + b]); flush(); }
-                else put(1, 0);
-            }
-        } else {
-            put(1, 0);
-            if (P.acmod == 0) put(1, 0);
-        }
-        if (b == 0) { put(1, 1); put(1, 0); } else put(1, 0);
-        if (P.acmod == 2) {
-            if (rem >= 0) {
-                put(1, (uint32_t)rem >> 4);
-                if (rem & 0x10) { put(1, rem & 1); put(1, (rem >> 1) & 1); put(1, (rem >> 2) & 1); put(1, (rem >> 3) & 1); }
-            } else if (b == 0) { put(1, 1); put(4, 0); } else put(1, 0);
-        }
-        for (int ch = 0; ch < nfbw; ch++) put(2, (uint32_t)strat_of(ch));
-        if (P.lfe) put(1, (uint32_t)strat_of(nch - 1));
-        for (int ch = 0; ch < nfbw; ch++) if ((strat_set >> ch) & 1u) put(6, P.chbwcod);
-        // exponents: lanes over groups
-        for (int ch = 0; ch < nch; ch++) {
-            const int stg = strat_of(ch);
-            if (stg == 0) continue;
-            const bool is_lfe = P.lfe && ch == nch - 1;
-            const int gs = stg == 1 ? 1 : stg == 2 ? 2 : 4;
-            const int ng = ((is_lfe ? 7 : nbc) + gs * 3 - 4) / (3 * gs);
-            const uint8_t *e = &W.erow[0];
-            {
-                uint32_t row = 0;
-#pragma unroll
-                for (int c2 = 0; c2 < 6; c2++) row = c2 == ch ? ew[c2] : row;
-                WAVE_SYNC();                                            // the previous channel's groups have read the row
-                *reinterpret_cast<uint32_t *>(&W.erow[4 * lane]) = row;
-                WAVE_SYNC();
-            }
-            put(4, (uint32_t)__builtin_amdgcn_readfirstlane((int)e[0]));
-            flush();
-            for (int g = lane; g < ng; g += 64) {
-                const int k0 = 1 + 3 * g * gs;
-                const int prev = g ? e[k0 - gs] : e[0];
-                const int d0 = e[k0] - prev + 2, d1 = e[k0 + gs] - e[k0] + 2, d2 = e[k0 + 2 * gs] - e[k0 + gs] + 2;
-                put_bits(fr, P.frw, pos + 7 * g, 7, (uint32_t)((d0 * 5 + d1) * 5 + d2));
-            }
-            pos += 7 * ng;
-            if (!is_lfe) put(2, 0);
-        }
-        if (b == 0) flush();
-        put(1, b == 0);
-        if (b == 0) { put(2, sdecaycod); put(2, fdecaycod); put(2, sgaincod); put(2, dbkneecod); put(3, floorcod); }
-        put(1, b == 0);
+        // ---- side information (the frame header, from bit 0, is block 0's to write) ----
         if (b == 0) {
-            put(6, (uint32_t)csnr);
-            for (int ch = 0; ch < nch; ch++) { put(4, (uint32_t)fsnr); put(3, fgaincod); }
+            PackSink k(fr, P.frw, lane, W.erow, [](int) { return 0u; }, 0, 0u);
+            syn_header(k, P.fscod, P.frmsizecod, P.bsid, P.acmod, P.lfe != 0, dual, MD ? pack_bsi(P, fidx) : BSI_DEFAULT, compr0, compr1);
         }
-        put(1, 0);
-        put(1, 0);
-        flush();
+        PackSink k(fr, P.frw, lane, W.erow, [&](int row) { return pick_row(ew, row, 0u); }, 0, pos);
+        const uint8_t *bs = P.bsw ? P.bsw + rowb : nullptr;
+        syn_block(k, shape, SynCpl{0u, 0, 12, 0u}, b, [&](int ch) -> uint32_t { return bs ? bs[ch] : 0u; },
+                  [&](int p) { return p ? dynw1 : dynw0; }, rem, strat_of, [](int, int) { return 0u; }, (uint32_t)csnr, (uint32_t)fsnr);
+        pos = k.pos;
 
         // ---- mantissas (:1341-1501): enc_mant.h ----
         {
