@@ -320,6 +320,7 @@ struct EncodeLaunch {
     uint32_t *ws_memo;          // [S][F][8] tabulated fit verdicts (may be null: the replay then costs everything itself)
     uint8_t *tap_eexp, *tap_bap, *tap_strat;
     int32_t *tap_snr;
+    int32_t *tap_curve = nullptr;   // ac3mi_debug_search_curve: [S][F][1024][2], what the search costed (generic search kernel only)
     const int32_t *slot;
     int pack_mode = 0;          // ac3mi_set_encode_mode
     const uint32_t *search_hint = nullptr;     // transcode: per frame, an offset 16 csnroffst + fsnroffst near which to start costing (stride in dwords)
@@ -429,6 +430,7 @@ struct ac3mi_ctx {
     int decode_mode = 0;    // ac3mi_set_decode_mode
     int decode_crc = 0;     // ac3mi_set_decode_crc
     int fixed_shape = 1;    // ac3mi_set_fixed_shape
+    int32_t *debug_search_curve = nullptr;  // ac3mi_debug_search_curve
     double *loud_tab = nullptr;     // ac3mi_loudness_*: bin edges and dialnorm thresholds on the device, put there by the first call (no workspace: it is a table)
     std::string err;
 };

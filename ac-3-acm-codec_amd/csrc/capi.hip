@@ -720,6 +720,13 @@ int ac3mi_set_fixed_shape(ac3mi_ctx *ctx, int on)
     return AC3MI_OK;
 }
 
+int ac3mi_debug_search_curve(ac3mi_ctx *ctx, int32_t *d_curve)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    ctx->debug_search_curve = d_curve;
+    return AC3MI_OK;
+}
+
 int ac3mi_set_decode_crc(ac3mi_ctx *ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 2) return AC3MI_ERR_ARG;
@@ -1120,7 +1127,8 @@ static int encode_setup(ac3mi_ctx *ctx, EncodeLaunch &E, const ac3mi_encode_desc
     E.bw = t.bw_mode != 0;
     E.exp_strategy = t.exp_strategy;
     E.pack_mode = ctx->encode_mode;
-    E.fixed_shape = ctx->fixed_shape != 0;
+    E.tap_curve = ctx->debug_search_curve;
+    E.fixed_shape = ctx->fixed_shape != 0 && !ctx->debug_search_curve;    // (the tap is the generic search kernel's)
     E.slot = ctx->slots;
     return AC3MI_OK;
 }

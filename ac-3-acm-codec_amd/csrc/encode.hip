@@ -8,9 +8,10 @@
 //                      min-merge over reuse runs, the +-2 constraint in closed form, band PSDs and masking curves of
 //                      the blocks that send exponents                                   [ac3enc.cpp:606-761, 220-367]
 //  enc_search_kernel   <1>: one wavefront per stream, frames in order (the SNR-offset search starts from the previous
-//                      frame's csnroffst): the reference's exact search sequence replayed from exact verdicts, three
-//                      offsets costed per sweep over the frame's run-start rows; <3>: one wavefront per frame
-//                      tabulates verdicts for few long streams                          [ac3enc.cpp:764-975]
+//                      frame's csnroffst): the reference's exact search sequence replayed from exact verdicts, a window
+//                      of sixteen consecutive offsets costed per sweep over the frame's run-start rows (snr_window.h);
+//                      <3>: one wavefront per frame tabulates verdicts for few long streams, three offsets per sweep
+//                                                                                       [ac3enc.cpp:764-975]
 //  enc_packf_kernel    one wavefront per frame packs it: header, side information, exponent groups, the mantissas
 //                      (enc_mant.h), both CRCs by per-lane chunk CRC + GF(2) combine    [ac3enc.cpp:1113-1638]
 //  enc_packb_kernel    the same with a workgroup of six wavefronts per frame, one per audio block (small batches)
@@ -25,6 +26,7 @@
 #include "spec_tables.h"
 #include "enc_mant.h"
 #include "enc_syntax.h"
+#include "snr_window.h"
 
 #include <type_traits>
 
@@ -62,6 +64,7 @@ struct PackParams {
     uint8_t *tap_bap;           // [S][F][6][nch][256]
     uint8_t *tap_strat;         // [S][F][6][nch]
     int32_t *tap_snr;           // [S][F][2]
+    int32_t *tap_curve;         // [S][F][1024][2]: spare bits and ceiling sixths of every offset the search costed (ac3mi_debug_search_curve)
     int n_streams, frames_per_stream, frame_stride;
     int nch, nfbw, lfe, acmod, fscod, halfrate, bsid, frmsizecod, frame_words;
     int nbc;                    // coefficients per full-bandwidth channel (223)
@@ -125,10 +128,25 @@ struct MaskTabs {
     uint8_t band_start[52];
 };
 
-// The search kernel's LDS: the frame's 36 masking curves (+ 6 of a coupling row), the cost table and the list of run-start rows.
+// The search kernel's LDS: the cost table and the list of run-start rows, and
+// - the three-offset sweep (PART 3): the frame's 36 masking curves (+ 6 of a coupling row), read once per sweep and candidate;
+// - the window sweep (PART 1; about one sweep per frame, the band lanes read their mask words from memory a row ahead): the
+//   per-bin prefix sums a row's band lanes take their band sums from, and the per-block histogram of the bands' steps.
 template <bool CPL>
-struct alignas(16) SearchLDS {
+struct SearchMaskRows {
     int16_t mask[CPL ? 42 : 36][50];       // masking curve minus the floor, row blk * nch + ch as exp_stage leaves them (a straight copy); 36 + blk: coupling
+};
+struct SearchWindowBufs {
+    // [4 + bin]: inclusive prefix sum over the row's bins of one packed cost word ([3] = 0: a band's sum is [3 + end] - [3 + start])
+    alignas(16) uint32_t scan[4 + 256];
+    // [copy][b][t - 1][word]: what the bands whose k steps at offset g_lo + t (1..15) add to the wide words A, B (snr_window.h)
+    // of the blocks b.., entered at the run's first block and taken back at the block behind its last (nothing to take back
+    // behind block 5).  Four copies, lane & 3's: a row's fifty band lanes step at eight offsets t1 and at t1 + 8, so ten or
+    // more of them would meet on one address, and LDS atomics on one address take their turns
+    alignas(16) uint32_t hist[4][6][15][2];
+};
+template <bool CPL, bool WIN>
+struct alignas(16) SearchLDS : std::conditional_t<WIN, SearchWindowBufs, SearchMaskRows<CPL>> {
     uint32_t bitlut[64];        // see "bap of one coefficient" below
     uint8_t strat[6][6];
     uint8_t band_of_bin[256];
@@ -138,7 +156,7 @@ struct alignas(16) SearchLDS {
     uint32_t rowdesc[CPL ? 42 : 36];
     // per band of the row being costed (two buffers: the next row's are worked out a row ahead), for each candidate offset:
     // 320 - max(0, ((mask - snroffset) >> 3) & ~3) as int16, so that a coefficient's table address x 4 is
-    // clamp(term - 16 exponent, 0, 252)
+    // clamp(term - 16 exponent, 0, 252); the window sweep: the same for the window's first offset, + 4 and + 8 (win_term)
     uint2 terms[2][50];
 };
 
@@ -1688,12 +1706,16 @@ __device__ unsigned long long g_pack_cycles[16];
 // FX (PART 1 with none of the above; launch_encode's fixed-shape rule): one-frame 5.1 streams - six channels, five of them
 // full-bandwidth, acmod 7, 223 coefficients, a single frame and neither taps nor a verdict table, as constants instead of P's members.
 template <int PART, bool CPL = false, bool BW = false, bool DRC = false, bool FX = false, bool DW = false>
-__global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const PackParams P)
+__global__ __launch_bounds__(64, FX ? 7 : ENC_SEARCH_LB) void enc_search_kernel(const PackParams P)      // (FX: profiles/search_window_resources.md)
 {
     static_assert(PART == 1 || PART == 3, "the packers are enc_packf_kernel / enc_packb_kernel");
     static_assert(!DW || DRC, "the array words are costed where the profiles' are");
     static_assert(!FX || (PART == 1 && !CPL && !BW && !DRC), "the fixed 5.1 shape is the plain per-stream search's");
-    __shared__ SearchLDS<CPL> L;
+    // The two sweeps live here.  WIN (PART 1, every instantiation): cost_window - one pass costs the sixteen offsets lo .. lo + 15
+    // (snr_window.h).  PART 3 tabulates csnroffst values, offsets 16 apart, which no window holds two of: it keeps the
+    // three-offset sweep cost_and_record, with ENC_NC and the probe policy around it.
+    constexpr bool WIN = PART == 1;
+    __shared__ SearchLDS<CPL, WIN> L;
     const int lane = threadIdx.x;
     constexpr bool PER_FRAME = PART == 3;
     const int s = PER_FRAME ? (int)(blockIdx.x / (unsigned)P.frames_per_stream) : (int)blockIdx.x;
@@ -1705,6 +1727,14 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
     {
         const int bp = P.tab->baptab[lane];
         L.bitlut[lane] = (uint32_t)plain_bits(bp) | ((bp == 1) << 9) | ((bp == 2) << 14) | ((bp == 4) << 19);
+    }
+    // (window sweep) lane = band: the band's bins [band_lo, band_hi) as indices into L.scan
+    int band_lo = 0, band_hi = 0;
+    if constexpr (WIN) {
+        const int b = lane < 50 ? lane : 49;
+        band_lo = 3 + P.tab->band_start[b];
+        band_hi = 3 + (b < 49 ? P.tab->band_start[b + 1] : 256);      // (band_of_bin: the last band holds every bin to 255)
+        if (lane == 0) L.scan[3] = 0;
     }
 
     const int nch = FX ? 6 : P.nch, nfbw = FX ? 5 : P.nfbw, nbc = FX ? 223 : P.nbc;
@@ -1735,8 +1765,8 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
         auto load_frame = [&]() {
             loaded = true;
         // ---- masking curves, strategies and exponent bit counts from exp_stage (the encoded exponents
-            //      stay in HBM/L2: [blk][ch][256] bytes at `ex`) ----
-            {
+            //      stay in HBM/L2: [blk][ch][256] bytes at `ex`; the window sweep leaves the masks there too) ----
+            if constexpr (!WIN) {
                 const uint32_t *gm = reinterpret_cast<const uint32_t *>(P.emask + fidx * 6 * nch * 50);
                 uint32_t mv[15];
 #pragma unroll
@@ -1807,8 +1837,10 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
             }
             if constexpr (CPL) if (cplf) {
                 // the coupling rows: masks to rows 36.., run starts behind the channels' in rowdesc
-                const uint32_t *gm = reinterpret_cast<const uint32_t *>(P.cpl.emask + fidx * 6 * 50);
-                for (int i = lane; i < 150; i += 64) reinterpret_cast<uint32_t *>(&L.mask[36][0])[i] = gm[i];
+                if constexpr (!WIN) {
+                    const uint32_t *gm = reinterpret_cast<const uint32_t *>(P.cpl.emask + fidx * 6 * 50);
+                    for (int i = lane; i < 150; i += 64) reinterpret_cast<uint32_t *>(&L.mask[36][0])[i] = gm[i];
+                }
                 const int st = lane < 6 ? (int)P.cpl.strat[fidx * 8 + lane] : 0;
                 const uint32_t cst = (uint32_t)__ballot(lane < 6 && st != 0) | 0x40u;
                 const int n0 = __builtin_popcountll(row_set);
@@ -1822,12 +1854,14 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
             }
         };
         // PART 1 replays the search from tabulated verdicts and needs the frame's data only for a verdict that is missing
-        if (PART != 1 || (!FX && P.tap_strat)) load_frame();
+        // (FX has no table: its first question always costs a sweep - loaded here, no address is kept across the search loop)
+        if (PART != 1 || FX || P.tap_strat) load_frame();
 
-        // ---- SNR offset search, exactly the reference's sequence (:921-967).  Up to three candidates are
+        // ---- SNR offset search, exactly the reference's sequence (:921-967).  PART 3: up to three candidates are
         //      evaluated per sweep over the coefficients, chosen by running the reference's loop ahead on
         //      the assumption that each one fits; the verdicts are then consumed in the reference's order
-        //      and everything after the first surprise is discarded. ----
+        //      and everything after the first surprise is discarded.  PART 1: a window of sixteen consecutive
+        //      offsets per sweep (cost_window below), the reference's loop replayed from the verdicts it leaves. ----
         const uint32_t bandoff = *reinterpret_cast<const uint32_t *>(&L.band_of_bin[4 * lane]);    // bands of bins 4*lane..+3
         SnrSearch ss{csnr_prev, 0, 0, false};
         // Verdicts already known for this frame: bit cc of known_c / fits_c for (cc, fsnroffst 0), bit ff of
@@ -1844,7 +1878,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
             fits_f = word(5);
             f_cc = (int)word(6);
         }
-        bool went_down = false, went_up = false;
+        bool went_down = false, went_up = false;           // (the three-offset policy's: PART 3 alone reads them)
         // Verdicts that follow from a costed offset WITHOUT costing.  A frame's mantissa bits are N + E: N = the sum over the
         // coefficients of a nominal width (0, 5/3, 7/3, 3, 7/2, 4, 5 ... 16 by bap), E = what the grouped codes' ceilings add - per
         // block 10/3 or 5/3 bits for one or two 3-level mantissas left over, 14/3 or 7/3 for 5-level ones, 7/2 for an odd 11-level
@@ -1859,7 +1893,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
         // lane w of one register each; and the two costed offsets that enclose the boundary most closely, with their spare bits.
         uint32_t costed_map = 0, fits_map = 0;
         int gl = -1, spare_l = 0, gh = -1, spare_h = 0;
-        int probe_sweeps = 0;
+        int probe_sweeps = 0;                               // (PART 3 alone)
         auto lookup = [&](int cc, int ff, bool &fits) {
             const int g = 16 * cc + ff;
             if (g <= fit_hi) { fits = true; return true; }
@@ -1877,6 +1911,7 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
         // channel's counts of the block that sent them: every run of blocks is counted once, 64 bins per step, and
         // added to the per-lane accumulators of all blocks of the run.
         auto cost_and_record = [&](const int (&cg)[ENC_NC], int n_cand, bool probing) {
+          if constexpr (!WIN) {                 // (PART 3 alone)
             if (!loaded) load_frame();
             int so[ENC_NC];                 // snroffset (:393-420) of the candidates; unused slots repeat the first
 #pragma unroll
@@ -2026,9 +2061,212 @@ __global__ __launch_bounds__(64, ENC_SEARCH_LB) void enc_search_kernel(const Pac
                     fits_f |= (uint32_t)ok << cand_fi;
                 }
             }
+          }
         };
-        bool first_sweep = true;
+        // The window sweep (snr_window.h): the frame's exact cost at the sixteen offsets lo .. lo + 15 from ONE pass over the
+        // run-start rows.  Per row: the band lanes (lane = band) work out k0 and the steps t1, t2 of their band a row ahead
+        // (win_steps) from the row's mask word, which they read from memory two rows ahead; every bin looks up three cost words,
+        // at the addresses of k0, k0 - 1 and k0 - 2 (the same packed arithmetic as the three-offset sweep, on the terms win_term
+        // + 0, 4, 8); the first goes to the blocks' accounts as before (acc: the cost at lo itself); a wave prefix sum of each word
+        // over the bins - modulo 2^32, exact: packing is linear and a band's own sum fits its fields, whatever overflowed before
+        // it - gives the band lanes W0, W1, W2, and these add W1 - W0 at t1 and W2 - W1 at t2 to the histogram of the run's
+        // first block and take them back at the block behind the run (L.hist).  Behind the rows: lane t sums the histogram over
+        // the blocks up to B and over the steps up to t, adds B's account and has the block's totals at lo + t; ceilings and
+        // sixths lane-parallel (win_block_bits); the sixteen verdicts into the maps and bounds.
+        // known_c / known_f are the tabulation's (PART 3 -> memo) and stay as loaded: lookup asks the maps first.
+        int win_sweeps = 0, win_slope15 = 0, win_cmin = 1 << 20, win_cmax = -1;
+        auto cost_window = [&](int lo) {
+          if constexpr (WIN) {
+            if (!loaded) load_frame();
+            PK_COUNT(4);
+            const int so_lo = win_snroffset(lo);
+            const int budget = 16 * fs - frame_bits;
+            uint32_t acc[6];
+#pragma unroll
+            for (int B = 0; B < 6; B++) acc[B] = 0;
+            static_assert(sizeof L.hist == 180 * sizeof(uint4), "cleared as 180 uint4");
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+                if (lane + 64 * i < 180) reinterpret_cast<uint4 *>(&L.hist[0][0][0][0])[lane + 64 * i] = make_uint4(0, 0, 0, 0);
+            {
+                const int nrows = __builtin_popcountll(row_set) + (CPL ? ncplrows : 0);
+                auto desc_of = [&](int i) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)L.rowdesc[i < nrows ? i : nrows - 1]); };
+                auto fetch = [&](uint32_t d) {
+                    if constexpr (CPL) return *reinterpret_cast<const uint32_t *>(((d & (1u << 15)) ? cex : ex) + (d & 0x3fffu) + 4 * lane);
+                    else return *reinterpret_cast<const uint32_t *>(ex + (d & 0x3fffu) + 4 * lane);
+                };
+                // the row's mask word of the lane's band (rows 36 + blk: the coupling's)
+                const int bl = lane < 50 ? lane : 49;
+                const int16_t *gmask = P.emask + fidx * 6 * nch * 50 + bl;
+                auto mask_of = [&](uint32_t d) {
+                    if constexpr (CPL) if (d & (1u << 15)) return (int)P.cpl.emask[(fidx * 6 + ((d >> 24) - 36)) * 50 + bl];
+                    return (int)gmask[(d >> 24) * 50u];
+                };
+                uint32_t d0 = desc_of(0), d1 = desc_of(1), d2 = desc_of(2);
+                uint32_t ev = fetch(d0), ev1 = fetch(d1), ev2 = fetch(d2);
+                int t1c = 0, t2c = 0;                   // the steps of the lane's band in the row being costed
+                auto terms = [&](int m, int buf, int &t1, int &t2) {
+                    int k0;
+                    win_steps(m - so_lo, k0, t1, t2);
+                    const int D = win_term(k0);
+                    if (lane < 50) L.terms[buf][lane] = make_uint2((uint32_t)(D & 0xffff) | ((uint32_t)(D + 4) << 16), (uint32_t)((D + 8) & 0xffff));
+                };
+                int mv1 = mask_of(d1);
+                terms(mask_of(d0), 0, t1c, t2c);
+                // bins the row does not code: exponent 255 - term - 16 x 255 < 0, table address 0, bap 0, no bits
+                auto beyond = [&](int n) { const int k = n - 4 * lane; return k >= 4 ? 0u : k <= 0 ? 0xffffffffu : 0xffffffffu << (8 * k); };
+                const uint32_t um_fbw = beyond(nbc), um_lfe = beyond(7);
+                uint32_t boff[4];                                           // byte offsets of the lane's four bands in a terms buffer
+#pragma unroll
+                for (int j = 0; j < 4; j++) boff[j] = ((bandoff >> (8 * j)) & 0xffu) * 8u;
+#pragma unroll 1
+                for (int i = 0; i < nrows; i++) {
+                    const uint32_t d3 = desc_of(i + 3);
+                    const uint32_t ev3 = fetch(d3);
+                    const int mv2 = mask_of(d2);
+                    const char *Tr = reinterpret_cast<const char *>(&L.terms[i & 1][0]);
+                    uint32_t em;
+                    if constexpr (CPL) {
+                        const uint32_t um_cch = beyond(cpl_cs), um_cpl = ~beyond(cpl_cs) | beyond(cpl_ce);
+                        em = ev | ((d0 & (1u << 14)) ? um_lfe : (d0 & (1u << 15)) ? um_cpl : (d0 & (1u << 22)) ? um_cch : um_fbw);
+                    } else {
+                        em = ev | ((d0 & (1u << 14)) ? um_lfe : um_fbw);
+                    }
+                    uint32_t p[3][4];                   // the three words, summed over the lane's bins up to j
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const uint32_t e16 = __umul24((em >> (8 * j)) & 0xffu, 0x00100010u);           // 16 x exponent, twice
+                        const uint2 t = *reinterpret_cast<const uint2 *>(Tr + boff[j]);
+                        pk2 a01 = __builtin_bit_cast(pk2, t.x) - __builtin_bit_cast(pk2, e16);
+                        pk2 a2 = __builtin_bit_cast(pk2, t.y) - __builtin_bit_cast(pk2, e16);
+                        a01 = __builtin_elementwise_min(__builtin_elementwise_max(a01, (pk2){0, 0}), (pk2){252, 252});
+                        a2 = __builtin_elementwise_min(__builtin_elementwise_max(a2, (pk2){0, 0}), (pk2){252, 252});
+                        const char *lut = reinterpret_cast<const char *>(&L.bitlut[0]);
+                        const uint32_t v0 = *reinterpret_cast<const uint32_t *>(lut + (uint16_t)a01.x);
+                        const uint32_t v1 = *reinterpret_cast<const uint32_t *>(lut + (uint16_t)a01.y);
+                        const uint32_t v2 = *reinterpret_cast<const uint32_t *>(lut + (uint16_t)a2.x);
+                        p[0][j] = j ? p[0][j - 1] + v0 : v0;
+                        p[1][j] = j ? p[1][j - 1] + v1 : v1;
+                        p[2][j] = j ? p[2][j - 1] + v2 : v2;
+                    }
+#pragma unroll
+                    for (int B = 0; B < 6; B++) {
+                        const uint32_t in_run = (d0 >> (16 + B)) & 1u;               // wave-uniform
+                        asm("v_mad_u32_u24 %0, %1, %2, %0" : "+v"(acc[B]) : "v"(p[0][3]), "s"(in_run));
+                    }
+                    // bins -> bands: one buffer for the three words (a wavefront's LDS accesses keep their order)
+                    uint32_t W[3];
+#pragma unroll
+                    for (int c = 0; c < 3; c++) {
+                        const uint32_t incl = wave_incl_scan_u32(p[c][3]);
+                        const uint32_t before = incl - p[c][3];
+                        *reinterpret_cast<uint4 *>(&L.scan[4 + 4 * lane]) = make_uint4(before + p[c][0], before + p[c][1], before + p[c][2], incl);
+                        W[c] = L.scan[band_hi] - L.scan[band_lo];
+                    }
+                    // bands -> histogram, at the run's first block and behind its last
+                    {
+                        const uint32_t cover = (d0 >> 16) & 0x3fu;                      // wave-uniform, a run of ones
+                        const int b_in = __builtin_ctz(cover), b_out = b_in + __builtin_popcount(cover);
+                        const uint32_t a0 = win_wide_a(W[0]), a1 = win_wide_a(W[1]), a2 = win_wide_a(W[2]);
+                        const uint32_t b0 = win_wide_b(W[0]), b1 = win_wide_b(W[1]), b2 = win_wide_b(W[2]);
+                        // (no lane adds where nothing steps inside the window: the many lanes of a quiet row would meet on one address)
+                        // ... nor where the step changes nothing: neighbouring table addresses mostly hold the same bap)
+                        const bool s1 = lane < 50 && t1c < WIN_N && ((a1 ^ a0) | (b1 ^ b0)) != 0, s2 = lane < 50 && t2c < WIN_N && ((a2 ^ a1) | (b2 ^ b1)) != 0;
+                        uint32_t *h1 = &L.hist[lane & 3][b_in][s1 ? t1c - 1 : 0][0], *h2 = &L.hist[lane & 3][b_in][s2 ? t2c - 1 : 0][0];
+                        if (s1) { atomicAdd(h1, a1 - a0); atomicAdd(h1 + 1, b1 - b0); }
+                        if (s2) { atomicAdd(h2, a2 - a1); atomicAdd(h2 + 1, b2 - b1); }
+                        if (b_out < 6) {                                                // wave-uniform
+                            const int behind = (b_out - b_in) * 30;
+                            if (s1) { atomicAdd(h1 + behind, a0 - a1); atomicAdd(h1 + behind + 1, b0 - b1); }
+                            if (s2) { atomicAdd(h2 + behind, a1 - a2); atomicAdd(h2 + behind + 1, b1 - b2); }
+                        }
+                    }
+                    // the next row's terms and steps, behind this row's last use of its own (two registers fewer than a row ahead)
+                    if (i + 1 < nrows) terms(mv1, (i + 1) & 1, t1c, t2c);
+                    d0 = d1; d1 = d2; d2 = d3;
+                    ev = ev1; ev1 = ev2; ev2 = ev3;
+                    mv1 = mv2;
+                }
+            }
+            // Frame totals at lo + t in lane t (every row of sixteen lanes the same)
+            int spare, extra6;
+            {
+                const int t = lane & 15;
+                uint32_t run_a = 0, run_b = 0, total = 0, x6 = 0;
+#pragma unroll
+                for (int B = 0; B < 6; B++) {
+                    const uint32_t base_a = wave_sum_u32(win_wide_a(acc[B])), base_b = wave_sum_u32(win_wide_b(acc[B]));
+#pragma unroll
+                    for (int c = 0; c < 4; c++) {
+                        const uint2 h = *reinterpret_cast<const uint2 *>(&L.hist[c][B][t ? t - 1 : 0][0]);
+                        run_a += t ? h.x : 0u;
+                        run_b += t ? h.y : 0u;
+                    }
+                    uint32_t e6;
+                    total += win_block_bits(base_a + row_incl_scan_u32(run_a), base_b + row_incl_scan_u32(run_b), e6);
+                    x6 += e6;
+                }
+                spare = budget - (int)total;
+                extra6 = (int)x6;
+            }
+            {
+                const uint32_t fits16 = (uint32_t)__ballot(spare >= 0) & 0xffffu, fails16 = fits16 ^ 0xffffu;
+                const uint32_t sure_fit = (uint32_t)__ballot(6 * spare >= 414 - extra6) & 0xffffu;
+                const uint32_t sure_fail = (uint32_t)__ballot(6 * spare < -extra6) & 0xffffu;
+                const int g_fit = sure_fit ? lo + 31 - __builtin_clz(sure_fit) : -1, g_fail = sure_fail ? lo + __builtin_ctz(sure_fail) : 1 << 20;
+                fit_hi = g_fit > fit_hi ? g_fit : fit_hi;
+                fail_lo = g_fail < fail_lo ? g_fail : fail_lo;
+                {                                   // sixteen bits from bit lo of the 1024-bit maps: word lo >> 5 and, past bit 16 of it, the next
+                    const uint64_t c16 = (uint64_t)0xffffu << (lo & 31), f16 = (uint64_t)fits16 << (lo & 31);
+                    const int w = lo >> 5;
+                    costed_map |= lane == w ? (uint32_t)c16 : lane == w + 1 ? (uint32_t)(c16 >> 32) : 0u;
+                    fits_map |= lane == w ? (uint32_t)f16 : lane == w + 1 ? (uint32_t)(f16 >> 32) : 0u;
+                }
+                {                                   // the costed offsets that enclose the boundary most closely (selects, as above)
+                    const int il = fits16 ? 31 - __builtin_clz(fits16) : 0, ih = fails16 ? __builtin_ctz(fails16) : 0;
+                    const int sp_l = __builtin_amdgcn_readlane(spare, il), sp_h = __builtin_amdgcn_readlane(spare, ih);
+                    const bool up = fits16 && lo + il > gl, dn = fails16 && (gh < 0 || lo + ih < gh);
+                    gl = up ? lo + il : gl; spare_l = up ? sp_l : spare_l;
+                    gh = dn ? lo + ih : gh; spare_h = dn ? sp_h : spare_h;
+                }
+                win_slope15 = __builtin_amdgcn_readlane(spare, 0) - __builtin_amdgcn_readlane(spare, 15);
+                win_cmin = lo < win_cmin ? lo : win_cmin;
+                win_cmax = lo + 15 > win_cmax ? lo + 15 : win_cmax;
+                if constexpr (!FX) if (P.tap_curve && lane < WIN_N) {
+                    P.tap_curve[(fidx * 1024 + lo + lane) * 2] = spare;
+                    P.tap_curve[(fidx * 1024 + lo + lane) * 2 + 1] = extra6;
+                }
+            }
+          }
+        };
+        bool first_sweep = true;                            // (PART 3 alone; the window loop counts win_sweeps)
         const bool cold_hint = csnr_prev == 40 && fsnr_prev == 0;          // the state AC3_encode_init leaves (a guess that only steers which offsets are costed first)
+        if constexpr (WIN) {
+            // Windows until the verdicts answer every question of the reference's loop: the first around the source frame's
+            // offsets (a transcode), where fresh material lands (a cold stream) or around the stream's last offsets; the next where
+            // the line through the enclosing costed offsets crosses zero, along the last window's slope while only one side is
+            // known, then by halving, at last around the open question itself (win_first_lo / win_next_lo; sweeps per frame:
+            // profiles/search_window_sim.py)
+            for (;;) {
+                int cc, ff;
+                bool more;
+                while ((more = ss.next(cc, ff))) {
+                    bool fits;
+                    if (!lookup(cc, ff, fits)) break;
+                    ss.consume(fits);
+                }
+                if (!more) break;
+                int lo;
+                if (win_sweeps == 0) {
+                    const int hint0 = (cold_hint && P.hint) ? (int)__builtin_amdgcn_readfirstlane((int)P.hint[fidx * (size_t)P.hint_stride]) : 0;    // (0: no hint)
+                    lo = win_first_lo(hint0, cold_hint, 16 * csnr_prev + fsnr_prev);
+                } else {
+                    lo = win_next_lo(win_sweeps, gl, spare_l, gh, spare_h, win_slope15, win_cmin, win_cmax, 16 * cc + ff);
+                }
+                win_sweeps++;
+                cost_window(lo);
+            }
+        } else
         for (;;) {
             // advance the reference's loop as far as the known verdicts reach
             int cc, ff;
@@ -2923,6 +3161,7 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.tap_bap = E.tap_bap;
     P.tap_strat = E.tap_strat;
     P.tap_snr = E.tap_snr;
+    P.tap_curve = E.tap_curve;
     P.n_streams = E.n_streams;
     P.frames_per_stream = E.frames_per_stream;
     P.frame_stride = E.frame_stride;

@@ -18,6 +18,16 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v)
     return v;
 }
 
+// the same inside each row of 16 lanes (the four row_shr steps alone)
+__device__ __forceinline__ uint32_t row_incl_scan_u32(uint32_t v)
+{
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
+    return v;
+}
+
 // lane 63's value as a wave-uniform scalar
 __device__ __forceinline__ uint32_t wave_last(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); }
 

@@ -397,6 +397,12 @@ class Engine:
         generic kernels; the bytes are the same (ac3mi_set_fixed_shape)."""
         self._check(self.lib.ac3mi_set_fixed_shape(ctypes.c_void_p(self.ctx), int(on)))
 
+    def debug_search_curve(self, curve):
+        """Test aid (ac3mi_debug_search_curve): `curve` = an int32 CUDA tensor [streams][frames][1024][2] that the encoder's
+        SNR-offset search of the following encode / transcode calls fills, for every offset it costs, with the frame's spare
+        bits and ceiling sixths there, or None to end the tap.  The caller keeps the tensor alive while the tap is set."""
+        self._check(self.lib.ac3mi_debug_search_curve(ctypes.c_void_p(self.ctx), ctypes.c_void_p(curve.data_ptr() if curve is not None else None)))
+
     def set_decode_crc(self, mode):
         """CRC verification of the frames the decode and transcode calls read (ac3mi_set_decode_crc): 0 = none (liba52),
         1 = report in status bits 10 / 11 (flags.STATUS_CRC1 / STATUS_CRC2), 2 = also decode a failing frame as a refused

@@ -178,6 +178,14 @@ int ac3mi_set_fixed_shape(ac3mi_ctx *ctx, int on);
  * (tests/test_workspace_independence_gpu.py).  AC3MI_ERR_ARG: null context, byte outside 0..255. */
 int ac3mi_fill_workspaces(ac3mi_ctx *ctx, int byte);
 
+/* A test aid (new): what the encoder's SNR-offset search costed.  d_curve: device memory, [streams][frames][1024][2] int32 for
+ * the following encode / transcode calls on `ctx`, or null to end the tap.  For every offset g = 16 csnroffst + fsnroffst the
+ * search costs for a frame it stores the frame's spare bits at g in [g][0] and the grouped codes' ceilings inside that count,
+ * in sixths of a bit, in [g][1]; entries of offsets it did not cost are left as they were.  While the tap is set the calls
+ * take the generic kernels (as under ac3mi_set_fixed_shape 0); frames and state are the same bytes with or without it
+ * (tests/test_search_window_gpu.py).  AC3MI_ERR_ARG: null context. */
+int ac3mi_debug_search_curve(ac3mi_ctx *ctx, int32_t *d_curve);
+
 /* CRC verification of the frames ac3mi_decode_batch / ac3mi_decode_s16_batch / ac3mi_transcode_batch read (new; applies to
  * every following such call on `ctx`, under every ac3mi_set_decode_mode, with or without state slots, mix state, taps and
  * tiling).  liba52 never looks at a frame's two CRC words, so a frame damaged in its mantissas parses without a block error,
