@@ -103,6 +103,15 @@ struct SynCpl {
 };
 
 SYN_FN int syn_grpsize(int strat) { return strat == 1 ? 1 : strat == 2 ? 2 : 4; }
+// 7-bit groups (three differentials, each held for syn_grpsize bins) behind the absolute exponent: of a channel coding bins
+// [0, n), from bin 1 (A/52's nchgrps; nlfegrps at n = 7: the last group may reach beyond n); of the coupling channel over
+// [cs, ce), from cs (ncplgrps)
+SYN_FN int syn_exp_groups(int n, int strat)
+{
+    const int gs = syn_grpsize(strat);
+    return (n + gs * 3 - 4) / (3 * gs);
+}
+SYN_FN int syn_cpl_exp_groups(int cs, int ce, int strat) { return (ce - cs) / (3 * syn_grpsize(strat)); }
 // rematrixing flags a coupled 2/0 block sends: liba52's band set for cplinu 1
 SYN_FN int syn_cpl_nrem(int begf) { return begf == 0 ? 2 : begf <= 2 ? 3 : 4; }
 
@@ -154,13 +163,12 @@ SYN_FN void syn_block(K &k, const SynShape &s, const SynCpl &c, int b, Blksw blk
     if (s.lfe) k.put(1, strat_of(nch - 1));
     for (int ch = 0; ch < nfbw; ch++) if (strat_of(ch) != 0 && !cplf) k.put(6, s.chbwcod);
     // exponents: cplabsexp and the groups from cplstrtmant; then each channel's exps[0], its groups from bin 1 and gainrng
-    if (cplf && c.strat != 0) k.exponents(SYN_CPL, (int)c.strat, (ce - cs) / (3 * syn_grpsize((int)c.strat)));
+    if (cplf && c.strat != 0) k.exponents(SYN_CPL, (int)c.strat, syn_cpl_exp_groups(cs, ce, (int)c.strat));
     for (int ch = 0; ch < nch; ch++) {
         const int stg = (int)strat_of(ch);
         if (stg == 0) continue;
         const bool is_lfe = s.lfe && ch == nch - 1;
-        const int gs = syn_grpsize(stg);
-        k.exponents(ch, stg, ((is_lfe ? 7 : cplf ? cs : s.nbc) + gs * 3 - 4) / (3 * gs));
+        k.exponents(ch, stg, syn_exp_groups(is_lfe ? 7 : cplf ? cs : s.nbc, stg));
         if (!is_lfe) k.put(2, 0);
     }
     if (b == 0) k.flush();
@@ -201,8 +209,7 @@ SYN_FN int syn_block_bits(const SynShape &s, int b, uint32_t dynrng0, uint32_t d
         const int stg = (int)strat_of(ch);
         if (stg == 0) continue;
         const bool is_lfe = s.lfe && ch == nch - 1;
-        const int gs = syn_grpsize(stg);
-        bits += 4 + 7 * (((is_lfe ? 7 : s.nbc) + gs * 3 - 4) / (3 * gs)) + (is_lfe ? 0 : 8);      // (fbw: chbwcod 6 + gainrng 2)
+        bits += 4 + 7 * syn_exp_groups(is_lfe ? 7 : s.nbc, stg) + (is_lfe ? 0 : 8);      // (fbw: chbwcod 6 + gainrng 2)
     }
     return bits;
 }

@@ -5,7 +5,7 @@
 //                      butterfly per lane and pass with exactly the reference's operands, shifts and int16
 //                      truncations; lanes trade one point per pass), post-rotation, exponent extraction
 //                      [ac3enc.cpp:1665-1722, 462-603]; then, still per channel (exp_stage): exponent strategy,
-//                      min-merge over reuse runs, the +-2 constraint in closed form, band PSDs and masking curves of
+//                      min-merge over reuse runs, the +-2 constraint in closed form (enc_exp.h), band PSDs and masking curves of
 //                      the blocks that send exponents                                   [ac3enc.cpp:606-761, 220-367]
 //  enc_search_kernel   <1>: one wavefront per stream, frames in order (the SNR-offset search starts from the previous
 //                      frame's csnroffst): the reference's exact search sequence replayed from exact verdicts, a window
@@ -26,6 +26,7 @@
 #include "spec_tables.h"
 #include "enc_mant.h"
 #include "enc_syntax.h"
+#include "enc_exp.h"
 #include "snr_window.h"
 
 #include <type_traits>
@@ -230,75 +231,29 @@ __device__ __forceinline__ uint32_t bytes_min_where(uint32_t a, uint32_t b, uint
     return (b & m) | (a & ~m);
 }
 
-// encode_exp (:684-761) on one 256-byte row in LDS, a dword per lane.  Lane l takes bins 4l+1 .. 4l+4: four entries for D15,
-// two for D25, one for D45 (entry i covers bins 1 + (i-1) gs .. + gs-1, so groups never straddle lanes).  The +-2 delta
-// constraint, min over j of g[j] + 2|i-j|, is a prefix minimum of g[j] - 2j followed by a suffix minimum of g[j] + 2j: inside
-// the lane first, then ONE scan over the lane totals per direction.
+// encode_exp (:684-761) on one 256-byte row in LDS, a dword per lane: the lane's entries (chan_exp_entries) under the +-2 delta
+// constraint (exp_constrain, both enc_exp.h), written back to the bins they cover, bin 0 with them.  Returns the set's bits.
 // PER = entries per lane, a compile-time constant per strategy (D15 4, D25 2, D45 1): a reuse-poor frame (decoded audio
 // re-encoded sends 24 sets, most of them D45 / D25) spends its exponent stage here, and the coarse strategies need a quarter /
 // half of the per-entry work.
 template <int PER>
 __device__ __forceinline__ int encode_exp_wave_t(uint8_t *row, int n, int lane)
 {
-    constexpr int INF = 0x3fffffff;
-    constexpr int gs = PER == 4 ? 1 : PER == 2 ? 2 : 4;
-    const int ng = ((n + gs * 3 - 4) / (3 * gs)) * 3;
+    const int groups = syn_exp_groups(n, exp_strategy_of<PER>), ng = 3 * groups;
     uint32_t *q = reinterpret_cast<uint32_t *>(row);
     const uint32_t own = q[lane], nxt = q[lane + 1];        // lane 63 reads the dword behind the row: entries beyond ng, never used
-    const uint32_t S = __builtin_amdgcn_alignbyte(nxt, own, 1u);
-    const int b0 = (int)(S & 0xffu), b1 = (int)((S >> 8) & 0xffu), b2 = (int)((S >> 16) & 0xffu), b3 = (int)(S >> 24);
-    int row0 = (int)(__builtin_amdgcn_readfirstlane((int)own) & 0xff);
-    row0 = row0 > 15 ? 15 : row0;
-    int g[PER], ix[PER];
+    int bin[4], g[PER], ix[PER];
     bool valid[PER];
-    if (PER == 4) { g[0] = b0; g[PER > 1 ? 1 : 0] = b1; g[PER > 2 ? 2 : 0] = b2; g[PER > 3 ? 3 : 0] = b3; }
-    else if (PER == 2) { g[0] = b1 < b0 ? b1 : b0; g[PER > 1 ? 1 : 0] = b3 < b2 ? b3 : b2; }
-    else { const int m01 = b1 < b0 ? b1 : b0, m23 = b3 < b2 ? b3 : b2; g[0] = m23 < m01 ? m23 : m01; }
-#pragma unroll
-    for (int c = 0; c < PER; c++) {
-        ix[c] = 2 * (PER * lane + 1 + c);
-        valid[c] = PER * lane + 1 + c <= ng;
-    }
-    int t[PER];
-#pragma unroll
-    for (int c = 0; c < PER; c++) {
-        const int a = valid[c] ? g[c] - ix[c] : INF;
-        t[c] = c == 0 ? a : (a < t[c > 0 ? c - 1 : 0] ? a : t[c > 0 ? c - 1 : 0]);
-    }
-    {
-        int ex = __builtin_amdgcn_update_dpp(INF, wave_incl_scan_min(t[PER - 1]), 0x138, 0xf, 0xf, false);       // wave_shr:1
-        ex = row0 < ex ? row0 : ex;
-#pragma unroll
-        for (int c = 0; c < PER; c++) g[c] = (t[c] < ex ? t[c] : ex) + ix[c];
-    }
-#pragma unroll
-    for (int c = PER - 1; c >= 0; c--) {
-        const int a = valid[c] ? g[c] + ix[c] : INF;
-        t[c] = c == PER - 1 ? a : (a < t[c < PER - 1 ? c + 1 : c] ? a : t[c < PER - 1 ? c + 1 : c]);
-    }
-    const int suf = wave_suffix_scan_min(t[0], lane);
-    {
-        const int ex = __builtin_amdgcn_update_dpp(INF, suf, 0x130, 0xf, 0xf, false);                       // wave_shl:1
-#pragma unroll
-        for (int c = 0; c < PER; c++) g[c] = (t[c] < ex ? t[c] : ex) - ix[c];
-    }
-    const int head = __builtin_amdgcn_readfirstlane(suf);
+    const int row0 = chan_exp_entries<PER>(own, nxt, ng, lane, bin, g, ix, valid);
+    const int head = exp_constrain<PER, true>(g, ix, valid, row0, lane);
     const int row0new = head < row0 ? head : row0;
-    // back to bins (entries beyond ng leave their bins alone)
-    int o0, o1, o2, o3;
-    if (PER == 4) {
-        o0 = valid[0] ? g[0] : b0; o1 = valid[PER > 1 ? 1 : 0] ? g[PER > 1 ? 1 : 0] : b1;
-        o2 = valid[PER > 2 ? 2 : 0] ? g[PER > 2 ? 2 : 0] : b2; o3 = valid[PER > 3 ? 3 : 0] ? g[PER > 3 ? 3 : 0] : b3;
-    } else if (PER == 2) {
-        o0 = valid[0] ? g[0] : b0; o1 = valid[0] ? g[0] : b1;
-        o2 = valid[PER > 1 ? 1 : 0] ? g[PER > 1 ? 1 : 0] : b2; o3 = valid[PER > 1 ? 1 : 0] ? g[PER > 1 ? 1 : 0] : b3;
-    } else {
-        o0 = valid[0] ? g[0] : b0; o1 = valid[0] ? g[0] : b1; o2 = valid[0] ? g[0] : b2; o3 = valid[0] ? g[0] : b3;
-    }
-    const uint32_t o = (uint32_t)o0 | (uint32_t)o1 << 8 | (uint32_t)o2 << 16 | (uint32_t)o3 << 24;
+    // back to bins, 4 / PER of them an entry (entries beyond ng leave their bins alone)
+    uint32_t o = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) o |= (uint32_t)(valid[k * PER / 4] ? g[k * PER / 4] : bin[k]) << (8 * k);
     const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp(row0new << 24, (int)o, 0x138, 0xf, 0xf, false);
     q[lane] = __builtin_amdgcn_alignbyte(o, prev, 3u);
-    return 4 + (ng / 3) * 7;
+    return 4 + 7 * groups;
 }
 
 __device__ int encode_exp_wave(uint8_t *row, int n, int strategy, int lane)
@@ -314,48 +269,13 @@ __device__ int encode_exp_wave(uint8_t *row, int n, int strategy, int lane)
 template <int PER>
 __device__ __forceinline__ int encode_exp_sum_t(uint32_t own, int n, int lane)
 {
-    constexpr int INF = 0x3fffffff;
-    constexpr int gs = PER == 4 ? 1 : PER == 2 ? 2 : 4;
-    const int ng = ((n + gs * 3 - 4) / (3 * gs)) * 3;
+    constexpr int gs = 4 / PER;
+    const int ng = 3 * syn_exp_groups(n, exp_strategy_of<PER>);
     const uint32_t nxt = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)own, 0x130, 0xf, 0xf, false);      // wave_shl:1
-    const uint32_t S = __builtin_amdgcn_alignbyte(nxt, own, 1u);
-    const int b0 = (int)(S & 0xffu), b1 = (int)((S >> 8) & 0xffu), b2 = (int)((S >> 16) & 0xffu), b3 = (int)(S >> 24);
-    int row0 = (int)(__builtin_amdgcn_readfirstlane((int)own) & 0xff);
-    row0 = row0 > 15 ? 15 : row0;
-    int g[PER], ix[PER];
+    int bin[4], g[PER], ix[PER];
     bool valid[PER];
-    if (PER == 4) { g[0] = b0; g[PER > 1 ? 1 : 0] = b1; g[PER > 2 ? 2 : 0] = b2; g[PER > 3 ? 3 : 0] = b3; }
-    else if (PER == 2) { g[0] = b1 < b0 ? b1 : b0; g[PER > 1 ? 1 : 0] = b3 < b2 ? b3 : b2; }
-    else { const int m01 = b1 < b0 ? b1 : b0, m23 = b3 < b2 ? b3 : b2; g[0] = m23 < m01 ? m23 : m01; }
-#pragma unroll
-    for (int c = 0; c < PER; c++) {
-        ix[c] = 2 * (PER * lane + 1 + c);
-        valid[c] = PER * lane + 1 + c <= ng;
-    }
-    int t[PER];
-#pragma unroll
-    for (int c = 0; c < PER; c++) {
-        const int a = valid[c] ? g[c] - ix[c] : INF;
-        t[c] = c == 0 ? a : (a < t[c > 0 ? c - 1 : 0] ? a : t[c > 0 ? c - 1 : 0]);
-    }
-    {
-        int ex = __builtin_amdgcn_update_dpp(INF, wave_incl_scan_min(t[PER - 1]), 0x138, 0xf, 0xf, false);       // wave_shr:1
-        ex = row0 < ex ? row0 : ex;
-#pragma unroll
-        for (int c = 0; c < PER; c++) g[c] = (t[c] < ex ? t[c] : ex) + ix[c];
-    }
-#pragma unroll
-    for (int c = PER - 1; c >= 0; c--) {
-        const int a = valid[c] ? g[c] + ix[c] : INF;
-        t[c] = c == PER - 1 ? a : (a < t[c < PER - 1 ? c + 1 : c] ? a : t[c < PER - 1 ? c + 1 : c]);
-    }
-    const int suf = wave_suffix_scan_min(t[0], lane);
-    {
-        const int ex = __builtin_amdgcn_update_dpp(INF, suf, 0x130, 0xf, 0xf, false);                       // wave_shl:1
-#pragma unroll
-        for (int c = 0; c < PER; c++) g[c] = (t[c] < ex ? t[c] : ex) - ix[c];
-    }
-    const int head = __builtin_amdgcn_readfirstlane(suf);
+    const int row0 = chan_exp_entries<PER>(own, nxt, ng, lane, bin, g, ix, valid);
+    const int head = exp_constrain<PER, true>(g, ix, valid, row0, lane);
     int sum = lane == 0 ? (head < row0 ? head : row0) : 0;
 #pragma unroll
     for (int c = 0; c < PER; c++) {
@@ -369,40 +289,14 @@ __device__ __forceinline__ int encode_exp_sum_t(uint32_t own, int n, int lane)
 // cpl_encode_exp's coded exponents summed over [cs, ce) (this lane's share), the row in LDS left as it is
 __device__ __forceinline__ int cpl_exp_sum(const uint8_t *row, int cs, int ce, int strategy, int lane)
 {
-    constexpr int INF = 0x3fffffff;
-    const int gs = strategy == 1 ? 1 : strategy == 2 ? 2 : 4, ne = (ce - cs) / gs;
-    int g[3], t[3], ix[3];
+    const int gs = syn_grpsize(strategy);
+    int g[3], ix[3];
     bool valid[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const int i = 3 * lane + c;
-        ix[c] = 2 * i;
-        valid[c] = i < ne;
-        int m = INF;
-        if (valid[c])
-            for (int k = 0; k < gs; k++) { const int e = row[cs + i * gs + k]; m = e < m ? e : m; }
-        g[c] = m;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const int a = valid[c] ? g[c] - ix[c] : INF;
-        t[c] = c == 0 ? a : (a < t[c > 0 ? c - 1 : 0] ? a : t[c > 0 ? c - 1 : 0]);
-    }
-    {
-        const int ex = __builtin_amdgcn_update_dpp(INF, wave_incl_scan_min(t[2]), 0x138, 0xf, 0xf, false);     // wave_shr:1
-#pragma unroll
-        for (int c = 0; c < 3; c++) g[c] = (t[c] < ex ? t[c] : ex) + ix[c];
-    }
-#pragma unroll
-    for (int c = 2; c >= 0; c--) {
-        const int a = valid[c] ? g[c] + ix[c] : INF;
-        t[c] = c == 2 ? a : (a < t[c < 2 ? c + 1 : c] ? a : t[c < 2 ? c + 1 : c]);
-    }
-    const int suf = wave_suffix_scan_min(t[0], lane);
-    const int ex = __builtin_amdgcn_update_dpp(INF, suf, 0x130, 0xf, 0xf, false);                             // wave_shl:1
+    cpl_exp_entries(row, cs, 3 * syn_cpl_exp_groups(cs, ce, strategy), gs, lane, g, ix, valid);
+    exp_constrain<3, false>(g, ix, valid, 0, lane);
     int sum = 0;
 #pragma unroll
-    for (int c = 0; c < 3; c++) sum += valid[c] ? ((t[c] < ex ? t[c] : ex) - ix[c]) * gs : 0;
+    for (int c = 0; c < 3; c++) sum += valid[c] ? g[c] * gs : 0;
     return sum;
 }
 
@@ -421,11 +315,7 @@ __device__ uint32_t xs_choose(const uint8_t (*E)[256], uint8_t *scratch, uint32_
 {
     int bits[3];
 #pragma unroll
-    for (int s = 0; s < 3; s++) {
-        const int gs = 1 << s;
-        const int groups = CPLROW ? (ce - cs) / gs / 3 : (n + gs * 3 - 4) / (3 * gs);
-        bits[s] = 4 + 7 * groups + extra;
-    }
+    for (int s = 0; s < 3; s++) bits[s] = 4 + 7 * (CPLROW ? syn_cpl_exp_groups(cs, ce, s + 1) : syn_exp_groups(n, s + 1)) + extra;
     int J1 = 0, J2 = 0, J3 = 0, J4 = 0, J5 = 0, J6 = 0;         // J(1) .. J(6) (J(6) = 0)
     uint32_t choice = 0;                                        // per block i: L | s << 3, 5 bits each
 #pragma unroll 1
@@ -479,9 +369,30 @@ __device__ uint32_t xs_choose(const uint8_t (*E)[256], uint8_t *scratch, uint32_
     return st;
 }
 
+// The two masking-curve routines' common parts, one lane per band b (:259-367).
+// The fast / slow leaks at band b from the `live` bands up to it: prefix maxima of psd - gain + band * decay (two scans
+// interleaved, wave_ops.h), taken back by b * decay
+__device__ __forceinline__ void mask_leaks(int psd, bool live, int b, int sdecay, int fdecay, int sgain, int fgain, int &fast, int &slow)
+{
+    constexpr int NEG = -0x3fffffff;
+    fast = live ? psd - fgain + b * fdecay : NEG;
+    slow = live ? psd - sgain + b * sdecay : NEG;
+    wave_incl_scan_max2(fast, slow);
+    fast -= b * fdecay;
+    slow -= b * sdecay;
+}
+// ... and what follows the excitation: the knee's correction, the hearing threshold, and the store - 0 in a band outside the row
+__device__ __forceinline__ void mask_store(const MaskTabs &T, int16_t *mask, int b, bool inside, int excite, int psd, int dbknee, int halfrate)
+{
+    const int t = dbknee - psd;
+    if (t > 0) excite += t >> 2;
+    const int h = T.hth[(b < 50 ? b : 49) >> halfrate];
+    if (b < 50) mask[b] = inside ? (int16_t)(excite > h ? excite : h) : (int16_t)0;
+}
+
 // Masking curve of one row, one lane per band (:220-367).  bndpsd[] must hold the band PSDs.
 //  * lowcomp is a reset-or-decrement automaton: value = max(0, R(last reset) - 64 * decrements since)
-//  * the fast / slow leaks are prefix maxima of psd - gain + band * decay, seeded at band begin-1
+//  * the leaks are seeded at band begin-1
 __device__ void mask_row_wave(const MaskTabs &T, int16_t *bndpsd, int bndend, bool is_lfe, int sdecay, int fdecay, int sgain,
                               int dbknee, int fgain, int halfrate, int lane)
 {
@@ -502,18 +413,13 @@ __device__ void mask_row_wave(const MaskTabs &T, int16_t *bndpsd, int bndend, bo
     const unsigned long long sm = __ballot(stop);
     const int begin = sm ? __builtin_ctzll(sm) + 1 : 7;
     const bool live = b >= begin - 1 && b < bndend;
-    int fast = live ? cur - fgain + b * fdecay : NEG, slow = live ? cur - sgain + b * sdecay : NEG;
-    wave_incl_scan_max2(fast, slow);                    // (two scans interleaved, wave_ops.h)
-    fast -= b * fdecay;
-    slow -= b * sdecay;
+    int fast, slow;
+    mask_leaks(cur, live, b, sdecay, fdecay, sgain, fgain, fast, slow);
     int excite;
     if (b < begin) excite = (int16_t)(cur - fgain - lowcomp);
     else if (b < 22) { const int v = fast - lowcomp; excite = (int16_t)(slow > v ? slow : v); }
     else excite = (int16_t)(fast > slow ? fast : slow);
-    const int t = dbknee - cur;
-    if (t > 0) excite += t >> 2;
-    const int h = T.hth[(b < 50 ? b : 49) >> halfrate];
-    if (b < 50) bndpsd[b] = b < bndend ? (int16_t)(excite > h ? excite : h) : (int16_t)0;
+    mask_store(T, bndpsd, b, b < bndend, excite, cur, dbknee, halfrate);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -552,6 +458,9 @@ __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, in
     uint32_t raw[6];
 #pragma unroll
     for (int b = 0; b < 6; b++) raw[b] = *reinterpret_cast<const uint32_t *>(&L.E[b][4 * lane]);
+    uint32_t below = 0;                                         // this lane's bytes of bins below n
+#pragma unroll
+    for (int c = 0; c < 4; c++) below |= (4 * lane + c < n ? 0xffu : 0u) << (8 * c);
 
     // ---- exponent strategy (:617-669): sum of |differences| over all 256 bins against the block before (two sums per
     //      reduction: each stays below 2^16) ----
@@ -561,9 +470,6 @@ __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, in
 #pragma unroll
         for (int b = 0; b < 6; b++) st[b] = (int)P.strat[(fidx * 6 + b) * nch + ch];
     } else if constexpr (XS != 0) {
-        uint32_t below = 0;
-#pragma unroll
-        for (int c = 0; c < 4; c++) below |= (4 * lane + c < n ? 0xffu : 0u) << (8 * c);
         const uint32_t x = xs_choose<false>(L.E, nullptr, below, n, 0, 0, is_lfe ? 0 : XS == 1 ? 8 : 2, is_lfe, lane);
 #pragma unroll
         for (int b = 0; b < 6; b++) st[b] = (int)((x >> (4 * b)) & 15u);
@@ -595,22 +501,17 @@ __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, in
     }
 
     // ---- min-merge over reuse runs (:1731-1737), bins below n only: in registers, four bins per lane ----
-    {
-        uint32_t below = 0;
 #pragma unroll
-        for (int c = 0; c < 4; c++) below |= (4 * lane + c < n ? 0xffu : 0u) << (8 * c);
+    for (int b = 0; b < 5; b++) {
+        if (!((starts >> b) & 1u)) continue;
+        bool open = true;
+        bool touched = false;
 #pragma unroll
-        for (int b = 0; b < 5; b++) {
-            if (!((starts >> b) & 1u)) continue;
-            bool open = true;
-            bool touched = false;
-#pragma unroll
-            for (int e = b + 1; e < 6; e++) {
-                open = open && !((starts >> e) & 1u);
-                if (open) { raw[b] = bytes_min_where(raw[b], raw[e], below); touched = true; }
-            }
-            if (touched) *reinterpret_cast<uint32_t *>(&L.E[b][4 * lane]) = raw[b];
+        for (int e = b + 1; e < 6; e++) {
+            open = open && !((starts >> e) & 1u);
+            if (open) { raw[b] = bytes_min_where(raw[b], raw[e], below); touched = true; }
         }
+        if (touched) *reinterpret_cast<uint32_t *>(&L.E[b][4 * lane]) = raw[b];
     }
     WAVE_SYNC();
 
@@ -1209,54 +1110,23 @@ __device__ __forceinline__ int cpl_quant(unsigned long long ech, unsigned long l
     return 15 << 4 | m;
 }
 
-// The coupling row's exponents (encode_exp with the coupling start, cf. A/52 7.1.3): entry i of the ne = (ce - cs) / gs
-// entries is the minimum of bins cs + i gs .. + gs - 1; the +-2 constraint as a prefix then a suffix minimum (three entries
-// per lane, one scan over the lane totals per direction); the reference exponent in front, 2 cplabsexp = entry 0 & ~1, goes
-// to bin cs - 1.  Returns the bits of cplabsexp and the groups.
+// The coupling row's exponents (encode_exp with the coupling start, cf. A/52 7.1.3): three entries a group from cs (the range
+// is a multiple of 12 bins: no entry is left over) under the +-2 constraint (cpl_exp_entries, exp_constrain: enc_exp.h),
+// written back to their bins; the reference exponent in front, 2 cplabsexp = entry 0 & ~1, goes to bin cs - 1.  Returns the
+// bits of cplabsexp and the groups.
 __device__ int cpl_encode_exp(uint8_t *row, int cs, int ce, int strategy, int lane)
 {
-    constexpr int INF = 0x3fffffff;
-    const int gs = strategy == 1 ? 1 : strategy == 2 ? 2 : 4, ne = (ce - cs) / gs;
-    int g[3], t[3], ix[3];
+    const int gs = syn_grpsize(strategy), groups = syn_cpl_exp_groups(cs, ce, strategy);
+    int g[3], ix[3];
     bool valid[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const int i = 3 * lane + c;
-        ix[c] = 2 * i;
-        valid[c] = i < ne;
-        int m = INF;
-        if (valid[c])
-            for (int k = 0; k < gs; k++) { const int e = row[cs + i * gs + k]; m = e < m ? e : m; }
-        g[c] = m;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const int a = valid[c] ? g[c] - ix[c] : INF;
-        t[c] = c == 0 ? a : (a < t[c > 0 ? c - 1 : 0] ? a : t[c > 0 ? c - 1 : 0]);
-    }
-    {
-        const int ex = __builtin_amdgcn_update_dpp(INF, wave_incl_scan_min(t[2]), 0x138, 0xf, 0xf, false);     // wave_shr:1
-#pragma unroll
-        for (int c = 0; c < 3; c++) g[c] = (t[c] < ex ? t[c] : ex) + ix[c];
-    }
-#pragma unroll
-    for (int c = 2; c >= 0; c--) {
-        const int a = valid[c] ? g[c] + ix[c] : INF;
-        t[c] = c == 2 ? a : (a < t[c < 2 ? c + 1 : c] ? a : t[c < 2 ? c + 1 : c]);
-    }
-    {
-        const int suf = wave_suffix_scan_min(t[0], lane);
-        const int ex = __builtin_amdgcn_update_dpp(INF, suf, 0x130, 0xf, 0xf, false);                         // wave_shl:1
-#pragma unroll
-        for (int c = 0; c < 3; c++) g[c] = (t[c] < ex ? t[c] : ex) - ix[c];
-    }
-    const int ref = __builtin_amdgcn_readfirstlane(g[0]) & ~1;
+    cpl_exp_entries(row, cs, 3 * groups, gs, lane, g, ix, valid);
+    const int ref = exp_constrain<3, false>(g, ix, valid, 0, lane) & ~1;        // (the head is entry 0, whose index is 0)
 #pragma unroll
     for (int c = 0; c < 3; c++)
         if (valid[c])
             for (int k = 0; k < gs; k++) row[cs + (3 * lane + c) * gs + k] = (uint8_t)g[c];
     if (lane == 0) row[cs - 1] = (uint8_t)ref;
-    return 4 + 7 * (ne / 3);
+    return 4 + 7 * groups;
 }
 
 // The coupling row's masking curve (A/52 7.2.2: the coupling channel's loop, no lowcomp), one lane per band: band PSDs of
@@ -1265,7 +1135,6 @@ __device__ int cpl_encode_exp(uint8_t *row, int cs, int ce, int strategy, int la
 __device__ void cpl_mask_wave(const MaskTabs &T, const uint8_t *row, int16_t *mask, int cs, int ce, int sdecay, int fdecay,
                               int sgain, int dbknee, int fgain, int halfrate, int lane)
 {
-    constexpr int NEG = -0x3fffffff;
     const int b = lane, bs = T.band_of_bin[cs], bend = T.band_of_bin[ce - 1] + 1;
     const bool live = b >= bs && b < bend;
     int psd = 0;
@@ -1280,18 +1149,12 @@ __device__ void cpl_mask_wave(const MaskTabs &T, const uint8_t *row, int16_t *ma
             psd = (psd > pj ? psd : pj) + (int)T.latab[t];
         }
     }
-    int fast = live ? psd - fgain + b * fdecay : NEG, slow = live ? psd - sgain + b * sdecay : NEG;
-    wave_incl_scan_max2(fast, slow);
-    fast -= b * fdecay;
-    slow -= b * sdecay;
+    int fast, slow;
+    mask_leaks(psd, live, b, sdecay, fdecay, sgain, fgain, fast, slow);
     const int f0 = (CPL_FLEAK << 8) + 768 - (b - bs + 1) * fdecay, s0 = (CPL_SLEAK << 8) + 768 - (b - bs + 1) * sdecay;
     fast = fast > f0 ? fast : f0;
     slow = slow > s0 ? slow : s0;
-    int excite = (int16_t)(fast > slow ? fast : slow);
-    const int t = dbknee - psd;
-    if (t > 0) excite += t >> 2;
-    const int h = T.hth[(b < 50 ? b : 49) >> halfrate];
-    if (b < 50) mask[b] = live ? (int16_t)(excite > h ? excite : h) : (int16_t)0;
+    mask_store(T, mask, b, live, (int16_t)(fast > slow ? fast : slow), psd, dbknee, halfrate);
 }
 
 // BW (ac3mi_set_encode_bandwidth 1 or 2): the coupling range ends at cplendmant = 73 + 12 P.endf, 3 + endf - begf bands.

@@ -197,6 +197,84 @@ def remat_view(frames):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# exponent strategies and coded exponents against tests/exp_strategy_model.py
+
+def check_rows(t1, nch, n):
+    """Every channel-frame of an uncoupled call: strategies and exponents on [0, n) are the model's on the d_exponent tap.
+    Returns the strategy sequences seen."""
+    from tests import exp_strategy_model as X
+    S, F = t1["exponent"].shape[:2]
+    seqs = []
+    for s in range(S):
+        for f in range(F):
+            for ch in range(nch):
+                lfe = nch == 6 and ch == 5
+                k, hi = ("lfe", 7) if lfe else ("fbw", n)
+                raw = t1["exponent"][s, f, :, ch].astype(np.int64)
+                J, st = X.choose(k, raw, 0, hi)
+                got = [int(v) for v in t1["exp_strategy"][s, f, :, ch]]
+                assert got == st, (s, f, ch, got, st)
+                assert np.array_equal(t1["encoded_exp"][s, f, :, ch, :hi], X.coded(k, raw, st, 0, hi)), (s, f, ch)
+                seqs.append((k, st))
+    return seqs
+
+
+def cpl_raw(t, s, f, nfbw, begf):
+    """The coupling row's raw exponents [6][256] (24 outside [cs, 217)) from the mode-0 taps."""
+    from tests import coupling_model as C
+    v, xb = C.coupling_rows(t["mdct"][s, f], t["exp_samples"][s, f], nfbw, begf)
+    a = np.abs(v)
+    lg = np.where(a > 0, np.frexp(np.maximum(a, 1).astype(np.float64))[1] - 1, 0)
+    return np.where(a > 0, 23 - lg + xb[:, None], 24).astype(np.int64)
+
+
+def check_coupled_frames(engine, pcm, nch, begf, c=None, mode0=False):
+    """Cost-based strategies with coupling at `begf` (and bandwidth mode 1 at chbwcod `c`): in a coupled frame the coupled
+    channels choose over [0, cplstrtmant) (gainrng, no chbwcod) and the coupling channel over [cplstrtmant, cplendmant); its
+    exponents are read back from the GPU decoder's coupling plane.  mode0: the strategy-mode-0 call is held to its own model
+    too - the channels to bandwidth_model.encode_exp under the tapped strategies, the coupling row to the reference's rule.
+    Returns the number of coupled frames."""
+    from tests import bandwidth_model as W
+    from tests import exp_strategy_model as X
+    nfbw = min(nch, 5)
+    cs, ce, n = 37 + 12 * begf, 217 if c is None else W.cplendmant(c), 223 if c is None else W.nbc(c)
+    kw = dict(cpl=(1, begf)) if c is None else dict(cpl=(1, begf), bw=(1, c))
+    frames, t1 = encode(engine, pcm, xs=1, taps=True, **kw)
+    frames0, t0 = encode(engine, pcm, xs=0, taps=True, **kw)
+    decodes_cleanly(frames, *layout_of(nch), engine=engine)
+    _, status, tp = decode(engine, frames, *layout_of(nch), taps=True)
+    assert (status & 0x1ff).max() == 0
+    if mode0:
+        _, status0, tp0 = decode(engine, frames0, *layout_of(nch), taps=True)
+        assert (status0 & 0x1ff).max() == 0
+    S, F = frames.shape[:2]
+    n_cpl = 0
+    for s in range(S):
+        for f in range(F):
+            cplinu = coupling_view(frames[s, f], nch)[0]
+            assert cplinu == coupling_view(frames0[s, f], nch)[0]            # (the coupling decision does not change)
+            for ch in range(nch):
+                lfe = nch == 6 and ch == 5
+                k, hi = ("lfe", 7) if lfe else (("cplch", cs) if cplinu else ("fbw", n))
+                raw = t0["exponent"][s, f, :, ch].astype(np.int64)
+                _, st = X.choose(k, raw, 0, hi)
+                assert [int(v) for v in t1["exp_strategy"][s, f, :, ch]] == st, (s, f, ch, k)
+                assert np.array_equal(t1["encoded_exp"][s, f, :, ch, :hi], X.coded(k, raw, st, 0, hi)), (s, f, ch)
+                if mode0:
+                    want = W.encode_exp(raw, t0["exp_strategy"][s, f, :, ch], hi)
+                    assert np.array_equal(t0["encoded_exp"][s, f, :, ch, :hi], want), (s, f, ch)
+            if cplinu:
+                n_cpl += 1
+                raw = cpl_raw(t0, s, f, nfbw, begf)
+                _, st = X.choose("cpl", raw, cs, ce)
+                assert np.array_equal(tp["exp"][s, f, :, 6, cs:ce].astype(np.int64), X.coded("cpl", raw, st, cs, ce)), (s, f)
+                if mode0:
+                    st0 = X.ref_rule(raw, lo=cs, hi=ce)
+                    assert np.array_equal(tp0["exp"][s, f, :, 6, cs:ce].astype(np.int64), X.coded("cpl", raw, st0, cs, ce)), (s, f)
+    return n_cpl
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # content
 
 def content(kind, nch, S, F, seed):

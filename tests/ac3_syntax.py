@@ -244,6 +244,17 @@ def _exponents(br, strat, absexp, ngrps, out, first):
                 k += 1
 
 
+def chan_ngrps(endmant, strat):
+    """§5.4.3 nchgrps of a channel ending at `endmant` (the LFE: nlfegrps = 2, which is this at 7 with D15)"""
+    gs = 3 << (strat - 1)
+    return (endmant + gs - 4) // gs
+
+
+def cpl_ngrps(cplstrtmant, cplendmant, strat):
+    """§5.4.3 ncplgrps"""
+    return (cplendmant - cplstrtmant) // (3 << (strat - 1))
+
+
 def parse_frame(data, check_size=True, nblocks=6):
     br = Bits(data)
     fr = Frame()
@@ -385,14 +396,13 @@ def parse_frame(data, check_size=True, nblocks=6):
                     endmant[ch] = 73 + 3 * c
         # exponents
         if cplinu and strat[CPL]:
-            ngrps = (cplendmant - cplstrtmant) // (3 << (strat[CPL] - 1))
+            ngrps = cpl_ngrps(cplstrtmant, cplendmant, strat[CPL])
             _exponents(br, strat[CPL], f("cplabsexp", 4) << 1, ngrps, exps[CPL], cplstrtmant)
             have[CPL] = True
         for ch in range(nf):
             if strat[ch]:
-                gs = 3 << (strat[ch] - 1)
                 exps[ch, 0] = f("exps%d_0" % ch, 4)
-                _exponents(br, strat[ch], int(exps[ch, 0]), (endmant[ch] + gs - 4) // gs, exps[ch], 1)
+                _exponents(br, strat[ch], int(exps[ch, 0]), chan_ngrps(endmant[ch], strat[ch]), exps[ch], 1)
                 f("gainrng%d" % ch, 2)
                 have[ch] = True
         if lfeon and strat[LFE]:

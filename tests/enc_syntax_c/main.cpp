@@ -11,7 +11,8 @@
  *     fixed=                       the search's sum for the case: syn_priced_fixed (+ syn_priced_cpl) and the frame's own terms
  *     expbits=                     4 + 7 groups over the channels' exponent sets (what the search adds from exp_stage)
  *     hex=                         the frame up to the last bit written (cases of the first STRATS_READ strategy patterns)
- *   enc_syntax SEED DRAWS STRATS_READ */
+ *   enc_syntax SEED DRAWS STRATS_READ
+ *   enc_syntax groups              the exponent group counts instead (print_groups) */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -109,13 +110,12 @@ static void run(const Case &c, bool with_hex)
             const int st = (int)c.strat[b][ch];
             if (!st) continue;
             const bool is_lfe = c.lfe && ch == c.nch - 1;
-            const int gs = syn_grpsize(st);
             if (!is_lfe) exp_rows++;
-            expbits += 4 + 7 * (((is_lfe ? 7 : cplf ? cs : nbc) + gs * 3 - 4) / (3 * gs));
+            expbits += 4 + 7 * syn_exp_groups(is_lfe ? 7 : cplf ? cs : nbc, st);
         }
         for (int p = 0; p < (c.acmod == 0 ? 2 : 1); p++) dyn_words += (c.dyn[b][p] & 0x100u) ? 1 : 0;
         if (b > 0 && c.remat_on && (c.remat[b] & 0x10u)) remat_blocks++;
-        if (cplf && c.cstrat[b]) cpl_ebits += 4 + 7 * ((ce - cs) / (3 * syn_grpsize((int)c.cstrat[b])));
+        if (cplf && c.cstrat[b]) cpl_ebits += 4 + 7 * syn_cpl_exp_groups(cs, ce, (int)c.cstrat[b]);
     }
     const int compr_words = ((c.compr[0] & 0x100u) ? 1 : 0) + ((c.compr[1] & 0x100u) ? 1 : 0);
     // the search's sum, formed as enc_search_kernel forms it: the layout's part, then what the frame adds
@@ -150,8 +150,24 @@ static void run(const Case &c, bool with_hex)
     g_case++;
 }
 
+// syn_exp_groups for every n a row can have and syn_cpl_exp_groups for every range ac3mi_set_encode_coupling / _bandwidth can
+// produce, per strategy: "ch n strat groups" and "cpl cs ce strat groups" lines
+static int print_groups()
+{
+    for (int n = 1; n <= 253; n++)
+        for (int s = 1; s <= 3; s++) printf("ch %d %d %d\n", n, s, syn_exp_groups(n, s));
+    for (int begf = 0; begf <= 12; begf++)
+        for (int endf = 0; endf <= 12; endf++) {
+            const int cs = 37 + 12 * begf, ce = 73 + 12 * endf;
+            if (cs >= ce) continue;
+            for (int s = 1; s <= 3; s++) printf("cpl %d %d %d %d\n", cs, ce, s, syn_cpl_exp_groups(cs, ce, s));
+        }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 2 && !strcmp(argv[1], "groups")) return print_groups();
     if (argc != 4) return 2;
     g_lcg = (uint32_t)strtoul(argv[1], nullptr, 10);
     const int draws = atoi(argv[2]), strats_read = atoi(argv[3]);

@@ -15,7 +15,7 @@ GS = {1: 1, 2: 2, 3: 4}
 
 
 def groups(n, s):
-    """Exponent groups of a channel coding bins [0, n) with strategy s (encode.hip: ng / 3)."""
+    """Exponent groups of a channel coding bins [0, n) with strategy s (enc_syntax.h: syn_exp_groups; cpl_groups: syn_cpl_exp_groups)."""
     gs = GS[s]
     return (n + gs * 3 - 4) // (3 * gs)
 
@@ -79,8 +79,18 @@ def seq_cost(kind, raw, strat, lo, hi):
     return tot
 
 
+_CHOSEN = {}
+
+
 def choose(kind, raw, lo, hi):
-    """The rule: -> (J(0), strategies [6])."""
+    """The rule: -> (J(0), strategies [6]).  (Remembered per argument set: sweeps over one content ask the same rows again.)"""
+    key = (kind, np.asarray(raw, np.int64).tobytes(), lo, hi)
+    if key not in _CHOSEN:
+        _CHOSEN[key] = _choose(kind, raw, lo, hi)
+    return _CHOSEN[key][0], list(_CHOSEN[key][1])
+
+
+def _choose(kind, raw, lo, hi):
     J = [0] * 7
     pick = [None] * 6
     for i in range(5, -1, -1):

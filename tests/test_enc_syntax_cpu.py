@@ -21,13 +21,18 @@ def _ints(s):
 
 
 @pytest.fixture(scope="module")
-def cases(tmp_path_factory):
+def exe(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("enc_syntax")
     csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
     exe = str(tmp / "enc_syntax")
     r = subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1", "-Wall", "-Werror",
                         "-I", csrc, os.path.join(H.ROOT, "tests", "enc_syntax_c", "main.cpp"), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+    return exe
+
+
+@pytest.fixture(scope="module")
+def cases(exe):
     r = subprocess.run([exe, "20250", str(DRAWS), str(STRATS_READ)], capture_output=True, text=True)
     # (b) the accumulator never held more than 64 bits (the sink aborts with the field's position), and neither sanitiser spoke
     assert r.returncode == 0 and r.stderr == "", r.stderr[-2000:]
@@ -43,6 +48,27 @@ def cases(tmp_path_factory):
         c["strat"] = [[int(d) for d in c["strat"][b * c["nch"]:(b + 1) * c["nch"]]] for b in range(6)]
         out.append(c)
     return out
+
+
+def test_group_counts(exe):
+    """syn_exp_groups and syn_cpl_exp_groups, the one statement of the 7-bit group counts in csrc/, against the exponent-strategy
+    model and the frame reader's own counts: every n in 1..253, every coupling range the setters can produce (cs = 37 + 12
+    begf, ce = 73 + 12 endf, cs < ce), the three strategies"""
+    from tests import exp_strategy_model as X
+    r = subprocess.run([exe, "groups"], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stderr == "", r.stderr[-2000:]
+    ch, cpl = {}, {}
+    for line in r.stdout.splitlines():
+        kind, *v = line.split()
+        v = [int(x) for x in v]
+        (ch if kind == "ch" else cpl)[tuple(v[:-1])] = v[-1]
+    assert set(ch) == {(n, s) for n in range(1, 254) for s in (1, 2, 3)}
+    assert set(cpl) == {(37 + 12 * b, 73 + 12 * e, s) for b in range(13) for e in range(13) if b <= e + 2 for s in (1, 2, 3)}
+    for (n, s), g in ch.items():
+        assert g == X.groups(n, s) == AS.chan_ngrps(n, s), (n, s, g)
+    for (cs, ce, s), g in cpl.items():
+        assert g == X.cpl_groups(cs, ce, s) == AS.cpl_ngrps(cs, ce, s), (cs, ce, s, g)
+    assert ch[(7, 1)] == 2                  # nlfegrps
 
 
 def test_the_matrix_is_whole(cases):

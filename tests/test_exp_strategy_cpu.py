@@ -24,7 +24,7 @@ def test_setter_declared_exported_and_bound():
 
 
 def _packer_groups(n, s):
-    """encode.hip encode_exp_wave_t: ng = ((n + gs 3 - 4) / (3 gs)) 3 entries, ng / 3 groups."""
+    """enc_syntax.h syn_exp_groups (encode_exp_wave_t codes three entries a group)."""
     gs = {1: 1, 2: 2, 3: 4}[s]
     return ((n + gs * 3 - 4) // (3 * gs)) * 3 // 3
 
@@ -41,7 +41,7 @@ def test_group_counts():
             ce = 73 + 12 * endf
             for s in (1, 2, 3):
                 gs = {1: 1, 2: 2, 3: 4}[s]
-                assert X.cpl_groups(cs, ce, s) == ((ce - cs) // gs) // 3       # cpl_encode_exp: 4 + 7 (ne / 3)
+                assert X.cpl_groups(cs, ce, s) == ((ce - cs) // gs) // 3       # enc_syntax.h syn_cpl_exp_groups
     assert X.bits("fbw", 1, 0, 223) == 4 + 7 * 74 + 8 and X.bits("cplch", 3, 0, 37) == 4 + 7 * 3 + 2
     assert X.bits("cpl", 2, 37, 217) == 4 + 7 * 30
 

@@ -11,7 +11,6 @@ import pytest
 from tests import _harness as H
 from tests import _tools as T
 from tests import bandwidth_model as W
-from tests import coupling_model as C
 from tests import exp_strategy_model as X
 
 pytestmark = pytest.mark.gpu
@@ -19,25 +18,6 @@ pytestmark = pytest.mark.gpu
 
 def _pcm(nch, S, F, seed, kinds=("music", "attack", "noise", "identical")):
     return np.concatenate([T.content(k, nch, 1, F, seed=seed + i) for i, k in enumerate(kinds)])[:S]
-
-
-def _check_rows(t1, nch, n, rows=None):
-    """Every channel-frame of an uncoupled call: strategies and exponents on [0, n) are the model's on the d_exponent tap.
-    Returns the strategy sequences seen."""
-    S, F = t1["exponent"].shape[:2]
-    seqs = []
-    for s in range(S):
-        for f in range(F):
-            for ch in range(nch):
-                lfe = nch == 6 and ch == 5
-                k, hi = ("lfe", 7) if lfe else ("fbw", n)
-                raw = t1["exponent"][s, f, :, ch].astype(np.int64)
-                J, st = X.choose(k, raw, 0, hi)
-                got = [int(v) for v in t1["exp_strategy"][s, f, :, ch]]
-                assert got == st, (s, f, ch, got, st)
-                assert np.array_equal(t1["encoded_exp"][s, f, :, ch, :hi], X.coded(k, raw, st, 0, hi)), (s, f, ch)
-                seqs.append((k, st))
-    return seqs
 
 
 def test_setter_validates_and_keeps_the_setting(engine):
@@ -82,50 +62,18 @@ def test_matches_the_model(engine, nch, sr):
         combos += [(dict(remat=1), 223), (dict(remat=1, bsw=1, bw=(1, 25)), W.nbc(25))]
     for kw, n in combos:
         frames, t1 = T.encode(engine, pcm, xs=1, taps=True, sr=sr, **kw)
-        _check_rows(t1, nch, n)
+        T.check_rows(t1, nch, n)
         if sr == 48000:
             T.decodes_cleanly(frames, *T.layout_of(nch), engine=engine)
-
-
-def _cpl_raw(t, s, f, nfbw, begf):
-    """The coupling row's raw exponents [6][256] (24 outside [cs, 217)) from the mode-0 taps."""
-    v, xb = C.coupling_rows(t["mdct"][s, f], t["exp_samples"][s, f], nfbw, begf)
-    a = np.abs(v)
-    lg = np.where(a > 0, np.frexp(np.maximum(a, 1).astype(np.float64))[1] - 1, 0)
-    return np.where(a > 0, 23 - lg + xb[:, None], 24).astype(np.int64)
 
 
 @pytest.mark.parametrize("nch,begf", [(2, 0), (2, 5), (6, 2)])
 def test_coupled_frames_follow_the_model(engine, nch, begf):
     """In a coupled frame the coupled channels choose over [0, cplstrtmant) (gainrng, no chbwcod) and the coupling
-    channel over [cplstrtmant, 217); its exponents are read back from the GPU decoder's coupling plane."""
-    nfbw = min(nch, 5)
-    cs = 37 + 12 * begf
+    channel over [cplstrtmant, 217); its exponents are read back from the GPU decoder's coupling plane
+    (tests/_tools.check_coupled_frames)."""
     pcm = np.concatenate([T.content("music", nch, 3, 2, seed=41), T.content("identical", nch, 1, 2, seed=45)])
-    frames, t1 = T.encode(engine, pcm, xs=1, cpl=(1, begf), taps=True)
-    frames0, t0 = T.encode(engine, pcm, xs=0, cpl=(1, begf), taps=True)
-    T.decodes_cleanly(frames, *T.layout_of(nch), engine=engine)
-    _, status, tp = T.decode(engine, frames, *T.layout_of(nch), taps=True)
-    assert (status & 0x1ff).max() == 0
-    S, F = frames.shape[:2]
-    n_cpl = 0
-    for s in range(S):
-        for f in range(F):
-            cplinu = T.coupling_view(frames[s, f], nch)[0]
-            assert cplinu == T.coupling_view(frames0[s, f], nch)[0]            # (the coupling decision does not change)
-            for ch in range(nch):
-                lfe = nch == 6 and ch == 5
-                k, hi = ("lfe", 7) if lfe else (("cplch", cs) if cplinu else ("fbw", 223))
-                raw = t0["exponent"][s, f, :, ch].astype(np.int64)
-                _, st = X.choose(k, raw, 0, hi)
-                assert [int(v) for v in t1["exp_strategy"][s, f, :, ch]] == st, (s, f, ch, k)
-                assert np.array_equal(t1["encoded_exp"][s, f, :, ch, :hi], X.coded(k, raw, st, 0, hi)), (s, f, ch)
-            if cplinu:
-                n_cpl += 1
-                raw = _cpl_raw(t0, s, f, nfbw, begf)
-                _, st = X.choose("cpl", raw, cs, 217)
-                assert np.array_equal(tp["exp"][s, f, :, 6, cs:217].astype(np.int64), X.coded("cpl", raw, st, cs, 217)), (s, f)
-    assert n_cpl > 0
+    assert T.check_coupled_frames(engine, pcm, nch, begf) > 0
 
 
 def test_only_the_choice_changes(engine):
@@ -142,7 +90,7 @@ def test_only_the_choice_changes(engine):
         _, t1 = T.encode(engine, pcm, xs=1, taps=True, **kw)
         for k in ("mdct", "exponent", "exp_samples"):
             assert np.array_equal(t0[k], t1[k]), k
-        seqs = _check_rows(t1, 6, 223)
+        seqs = T.check_rows(t1, 6, 223)
         S, F = pcm.shape[0], pcm.shape[1] // 1536
         for s in range(S):
             for f in range(F):
@@ -262,7 +210,7 @@ def test_large_batch(engine):
     pick = rng.integers(0, S, 16)
     _, t = T.encode(engine, pcm[pick], xs=1, taps=True)
     assert np.array_equal(T.encode(engine, pcm[pick], xs=1), frames[pick])
-    _check_rows(t, 6, 223)
+    T.check_rows(t, 6, 223)
 
 
 def test_stream_layer_never_uses_it(engine):
