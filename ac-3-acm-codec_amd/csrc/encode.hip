@@ -1089,9 +1089,15 @@ __host__ __device__ constexpr int cpl_g(int nfbw) { return nfbw <= 2 ? 1 : nfbw 
 
 // The coordinate of one channel and band under mstrcplco M (liba52 parse.c:642-656): the largest value mant 2^-s,
 // E < 15: mant = 16 + m, s = E + 3M + 2;  E = 15: mant = m, s = 16 + 3M, with mant^2 Ecpl <= Ech (exact, 128-bit).
+// Ech = 0 gives the zero coordinate (E 15, m 0) whatever Ecpl is: with Ecpl = 0 as well - a band of digital silence - every
+// value fits, and the largest would play the decoder's dither of the coupling channel 7.75 times louder.
 // Returns E << 4 | m, and mant, s.
 __device__ __forceinline__ int cpl_quant(unsigned long long ech, unsigned long long ecpl, int M, int &mant, int &sv)
 {
+    if (ech == 0) {
+        mant = 0; sv = 16 + 3 * M;
+        return 15 << 4;
+    }
     auto fits = [&](int mt, int s_) {
         return (unsigned __int128)(unsigned)(mt * mt) * ecpl <= ((unsigned __int128)ech << (2 * s_));
     };

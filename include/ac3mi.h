@@ -530,7 +530,7 @@ int ac3mi_set_encode_rematrix(ac3mi_ctx *ctx, int mode);
  *      - coordinates, one set per frame in block 0 (cplcoe 1; cplcoe 0 in blocks 1..5; phsflginu 0): under mstrcplco M
  *        the value of (cplcoexp E, cplcomant m) is liba52's (parse.c:642-656, the x8 included): (16 + m) 2^-(E + 3M + 2)
  *        for E < 15, m 2^-(16 + 3M) for E = 15; the code is the largest value v with v^2 Ecpl <= Ech (exact; Ech = 0
- *        gives E 15, m 0); a channel's mstrcplco is the M whose codes give the largest sum over its bands of v^2, ties to
+ *        gives E 15, m 0, also where Ecpl = 0 lets every value fit: a silent band stays silent); a channel's mstrcplco is the M whose codes give the largest sum over its bands of v^2, ties to
  *        the smaller M;
  *      - the coupling channel: exponent strategies by the reference's rule on its raw exponents (24 outside the coupling
  *        range), min-merged over reuse runs, groups from cplstrtmant under the +-2 constraint, 2 cplabsexp = the first

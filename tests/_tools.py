@@ -309,6 +309,33 @@ def content(kind, nch, S, F, seed):
     return np.clip(np.round(np.array(out)), -32768, 32767).astype(np.int16)
 
 
+CORNER_KINDS = ("silence", "rails", "impulses", "dc", "noise", "rails_identical", "rails_antiphase", "onset")
+
+
+def corner(kind, nch, F, seed):
+    """[F*1536][nch] s16: the level corners.  silence, rails, impulses, dc, noise: the harness's; rails_identical: one
+    full-scale square (period 10, -32768 included) in every channel; rails_antiphase: the same with the rails swapped in the
+    odd channels (the sum of a pair is -1 everywhere); onset: rails_identical after 1536 + 700 samples of digital silence."""
+    if kind in ("silence", "rails", "impulses", "dc", "noise"):
+        return H.gen_pcm(F, nch, seed=seed, kind=kind)
+    t = np.arange(F * 1536)
+    sq = np.where((t // 5) % 2 == 0, 32767, -32768)
+    if kind == "rails_identical":
+        x = np.stack([sq] * nch, -1)
+    elif kind == "rails_antiphase":
+        x = np.stack([sq if c % 2 == 0 else -1 - sq for c in range(nch)], -1)
+    elif kind == "onset":
+        x = np.stack([np.where(t < 1536 + 700, 0, sq)] * nch, -1)
+    else:
+        raise ValueError(kind)
+    return x.astype(np.int16)
+
+
+def corner_batch(nch, F=3):
+    """[8][F*1536][nch]: CORNER_KINDS in order, kind i with seed 900 + i"""
+    return np.stack([corner(k, nch, F, 900 + i) for i, k in enumerate(CORNER_KINDS)])
+
+
 def stereo(kind, S, F, seed):
     """[S][F*1536][2] s16 stereo test content."""
     n = F * 1536

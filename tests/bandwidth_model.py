@@ -120,6 +120,8 @@ def _coord(code, M):
 
 
 def _quant(ech, ecpl, M):
+    if ech == 0:                            # the zero coordinate, also where Ecpl = 0 lets every value fit
+        return 15 << 4
     for E in range(15):
         s = E + 3 * M + 2
         if 256 * ecpl <= ech << (2 * s):

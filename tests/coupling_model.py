@@ -32,8 +32,11 @@ def coord_value(code, M):
 
 
 def quant(ech, ecpl, M):
-    """The largest coordinate value v (code) with v^2 Ecpl <= Ech, exactly."""
+    """The largest coordinate value v (code) with v^2 Ecpl <= Ech, exactly; Ech = 0 gives the zero coordinate (E 15, m 0),
+    with Ecpl = 0 as well (a band of digital silence, where every value fits)."""
     ech, ecpl = int(ech), int(ecpl)
+    if ech == 0:
+        return 15 << 4
     for E in range(15):
         s = E + 3 * M + 2
         if 256 * ecpl <= ech << (2 * s):
