@@ -236,6 +236,8 @@ def load_library():
         lib.ac3mi_fill_workspaces.argtypes = [c_void_p, ctypes.c_int]
     if hasattr(lib, "ac3mi_debug_search_curve"):    # (likewise)
         lib.ac3mi_debug_search_curve.argtypes = [c_void_p, c_void_p]
+    if hasattr(lib, "ac3mi_debug_launch_log"):      # (likewise)
+        lib.ac3mi_debug_launch_log.argtypes = [c_void_p, c_void_p, ctypes.c_int]
     lib.ac3mi_set_decode_crc.argtypes = [c_void_p, ctypes.c_int]
     lib.ac3mi_crc_check_batch.argtypes = [c_void_p, c_void_p, c_int, c_int, c_size_t, c_void_p]
     lib.ac3mi_set_mix_state.argtypes = [c_void_p, c_void_p, c_void_p]

@@ -143,6 +143,7 @@ struct DecodeLaunch {
     // dynrnge, bits 0-7 dynrng, bit 24 dynrng2e, bits 16-23 dynrng2 (acmod 0) - for enc_dynrng_source_kernel.  Non-null: the SRC
     // instantiations of the front ends run (generic shape only); a block that is not reached leaves its word unwritten
     uint32_t *src_dyn = nullptr;
+    const LaunchLog *log = nullptr;     // ac3mi_debug_launch_log: the launchers append what they launch (launch_rule.h); null: no tap
 };
 hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStream_t stream);
 // decode_wg.hip: one workgroup per stream; X == nullptr: coefficient planes (+ taps) to HBM as launch_decode does;
@@ -346,6 +347,7 @@ struct EncodeLaunch {
     // Either non-null: the DW variants of the search and the packers run (never with drc_profile and dyn_codes together)
     const uint8_t *dyn_codes = nullptr;
     const uint16_t *compr_words = nullptr;
+    const LaunchLog *log = nullptr;     // ac3mi_debug_launch_log: launch_stage appends what it launches (launch_rule.h); null: no tap
 };
 // carves CPL_FRAME_BYTES * nfr bytes at `base` into the arrays of CplWs (base 16-byte aligned)
 CplWs cpl_slices(void *base, size_t nfr);
@@ -431,6 +433,7 @@ struct ac3mi_ctx {
     int decode_crc = 0;     // ac3mi_set_decode_crc
     int fixed_shape = 1;    // ac3mi_set_fixed_shape
     int32_t *debug_search_curve = nullptr;  // ac3mi_debug_search_curve
+    ac3mi::LaunchLog launch_log;            // ac3mi_debug_launch_log (host memory; words null: no tap)
     double *loud_tab = nullptr;     // ac3mi_loudness_*: bin edges and dialnorm thresholds on the device, put there by the first call (no workspace: it is a table)
     std::string err;
 };

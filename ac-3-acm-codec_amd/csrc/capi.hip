@@ -727,6 +727,15 @@ int ac3mi_debug_search_curve(ac3mi_ctx *ctx, int32_t *d_curve)
     return AC3MI_OK;
 }
 
+int ac3mi_debug_launch_log(ac3mi_ctx *ctx, uint32_t *h_log, int capacity)
+{
+    if (!ctx || (h_log && capacity < 1)) return AC3MI_ERR_ARG;
+    ctx->launch_log.words = h_log;
+    ctx->launch_log.capacity = h_log ? capacity : 0;
+    if (h_log) h_log[0] = 0;
+    return AC3MI_OK;
+}
+
 int ac3mi_set_decode_crc(ac3mi_ctx *ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 2) return AC3MI_ERR_ARG;
@@ -1037,6 +1046,7 @@ static DecodeLaunch decode_launch(const ac3mi_ctx *ctx, const DecChoice &fe, con
     D.tap_exp = nullptr;
     D.tap_bap = nullptr;
     D.choice = fe;
+    D.log = ctx->launch_log.words ? &ctx->launch_log : nullptr;
     D.frame_draws = fe.fp ? ctx->ws_draws.at<uint32_t>() : nullptr;
     D.frame_lfsr = fe.fp ? ctx->ws_draws.at<uint16_t>(nfr * 4) : nullptr;
     if (fe.split) {
@@ -1130,6 +1140,7 @@ static int encode_setup(ac3mi_ctx *ctx, EncodeLaunch &E, const ac3mi_encode_desc
     E.tap_curve = ctx->debug_search_curve;
     E.fixed_shape = ctx->fixed_shape != 0 && !ctx->debug_search_curve;    // (the tap is the generic search kernel's)
     E.slot = ctx->slots;
+    E.log = ctx->launch_log.words ? &ctx->launch_log : nullptr;
     return AC3MI_OK;
 }
 

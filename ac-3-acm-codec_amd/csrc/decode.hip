@@ -224,12 +224,17 @@ hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStre
     for (int i = 0; i < c.n; i++) {
         const KernelLaunch &k = c.launch[i];
         const dim3 grid(grid_size(k, L.n_streams, L.frames_per_stream, 1)), block(k.block);
-        if (k.family == K_DECODE && k.variant == V_SRC) launch_decode0_src(P, grid.x, fr_bytes + lds_pad, stream);
+        if (k.family == K_DECODE && k.variant == V_SRC) {
+            log_launch(L.log, k);
+            launch_decode0_src(P, grid.x, fr_bytes + lds_pad, stream);
+        }
         else if (k.family == K_DECODE) {
             const auto fn = variant_fn<DECODE_VARIANTS, DecodeVariant>(k.variant);
             if (!fn) return hipErrorInvalidValue;
+            log_launch(L.log, k);
             hipLaunchKernelGGL(fn, grid, block, fr_bytes + lds_pad, stream, P);
         } else if (k.family == K_LFSR_PREFIX) {
+            log_launch(L.log, k);
             hipLaunchKernelGGL(lfsr_prefix_kernel, grid, block, 0, stream, (const uint32_t *)L.frame_draws, (uint16_t *)nullptr, L.ws_fpos,
                                L.lfsr, L.slot, tab.lfsr_seq, tab.lfsr_idx, L.n_streams, L.frames_per_stream);
         } else if (k.family == K_MANT || k.family == K_MANTX) {
@@ -250,6 +255,7 @@ hipError_t launch_decode(const DeviceTables &tab, const DecodeLaunch &L, hipStre
             M.n_in = P.n_in;
             M.nfchans = P.nfchans;
             if (k.family == K_MANTX) return launch_mantx(tab, L, M, k, stream);     // the transform in the same kernel
+            log_launch(L.log, k);
             hipLaunchKernelGGL(mant_kernel, grid, block, fr_bytes + mant_pad, stream, M);
         } else return hipErrorInvalidValue;
     }

@@ -332,6 +332,7 @@ hipError_t launch_mantx(const DeviceTables &tab, const DecodeLaunch &L, const Ma
     }
     const auto fn = variant_fn<MANTX_VARIANTS, MantxVariant>(k.variant);
     if (!fn) return hipErrorInvalidValue;
+    log_launch(L.log, k);
     hipLaunchKernelGGL(fn, dim3(M.n_frames), dim3(k.block), staged_frame_lds(L.frame_bytes) + lds_pad, stream, Q);
     return hipGetLastError();
 }

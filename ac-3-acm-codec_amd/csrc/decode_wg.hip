@@ -1190,6 +1190,7 @@ hipError_t launch_decode_wg(const DeviceTables &tab, const DecodeLaunch &D, cons
         W.pcm16 = X->pcm16;
         W.pcm = nullptr;
     }
+    log_launch(D.log, k);
     hipLaunchKernelGGL(fn, dim3(grid), dim3(k.block), fr_bytes, stream, W);
     return hipGetLastError();
 }

@@ -2935,6 +2935,7 @@ static hipError_t launch_stage(const KernelLaunch &k, const EncodeLaunch &E, siz
     if (k.family == K_NONE) return hipSuccess;
     const auto fn = variant_fn<LIST, K>(k.variant);
     if (!fn) return hipErrorInvalidValue;
+    log_launch(E.log, k);
     hipLaunchKernelGGL(fn, dim3(grid_size(k, E.n_streams, E.frames_per_stream, E.cfg.nch)), dim3(k.block), lds, stream, P);
     return hipGetLastError();
 }

@@ -80,6 +80,22 @@ inline constexpr unsigned grid_size(const KernelLaunch &l, int n_streams, int fr
     return l.grid == G_FRAME ? nfr : l.grid == G_CHANNEL ? nfr * (unsigned)nch : l.grid == G_64_STREAMS ? ((unsigned)n_streams + 63u) / 64u : (unsigned)n_streams;
 }
 
+// The launch log (ac3mi_debug_launch_log, a test aid): `words` is host memory of `capacity` words; words[0] counts the launches
+// since the tap was set, those that no longer fit included, words[1..] holds family << 24 | variant word of each in launch
+// order.  The launchers call log_launch where they resolve variant_fn (and at the two plain kernels' launches), on the host
+// thread that makes the batch call: nothing on the device, and a null log costs one test.
+struct LaunchLog {
+    uint32_t *words = nullptr;
+    int capacity = 0;
+};
+inline constexpr uint32_t launch_word(uint8_t family, uint32_t variant) { return (uint32_t)family << 24 | variant; }
+inline void log_launch(const LaunchLog *log, const KernelLaunch &k)
+{
+    if (!log || !log->words) return;
+    const uint32_t n = ++log->words[0];
+    if (n < (uint32_t)log->capacity) log->words[n] = launch_word(k.family, k.variant);
+}
+
 // dynamic LDS of a kernel that stages a frame (stage_frame, decode_common.h): its dwords and six of slack for the bit window
 inline constexpr size_t staged_frame_lds(int frame_bytes) { return (size_t)(((frame_bytes + 3) >> 2) + 6) * 4; }
 
@@ -245,8 +261,7 @@ template <class Call> inline EncChoice enc_choice(const Call &in)
     if (c.remat && cfg.lfe) c.stage[ES_LFEROW] = kernel_launch(K_ENC_MDCT, V_LFEROW | vxs, G_FRAME, 64);
     // channel coupling: layouts with two or more full-bandwidth channels (R3: 2/0+LFE with rematrixing, three rows a block in
     // the rematrixing arrays)
-    if (c.cpl) c.stage[ES_CPL] = kernel_launch(K_ENC_CPL, vbw | vxs | (c.remat && cfg.lfe ? V_R3 : 0u), G_FRAME, 64);
-    // The SNR-offset searches run one wavefront per stream (PART 1; for few long streams behind PART 3's frame-parallel
+    if (c.cpl) c.stage[ES_CPL] = kernel_launch(K_ENC_CPL, vbw | vxs | (c.remat && cfg.lfe ? V_R3 : 0u), G_FRAME, 64);    // The SNR-offset searches run one wavefront per stream (PART 1; for few long streams behind PART 3's frame-parallel
     // tabulation, worth its cost only when the per-stream replay is the long pole), then every frame is packed.
     // (the uncoupled search and enc_packb_kernel take nbc / chbwcod at run time in every mode)
     c.memo = in.frames_per_stream > 1 && in.n_streams < 2048 && in.ws_memo;

@@ -403,6 +403,18 @@ class Engine:
         bits and ceiling sixths there, or None to end the tap.  The caller keeps the tensor alive while the tap is set."""
         self._check(self.lib.ac3mi_debug_search_curve(ctypes.c_void_p(self.ctx), ctypes.c_void_p(curve.data_ptr() if curve is not None else None)))
 
+    def debug_launch_log(self, log):
+        """Test aid (ac3mi_debug_launch_log): `log` = a C-contiguous uint32 numpy array in host memory that the following
+        decode / encode / transcode calls fill - log[0] counts the launches of the launch rule's kernels since the tap was
+        set, log[1:] holds family << 24 | variant word of each in launch order - or None to end the tap.  The caller keeps
+        the array alive while the tap is set."""
+        if log is None:
+            self._check(self.lib.ac3mi_debug_launch_log(ctypes.c_void_p(self.ctx), None, 0))
+            return
+        import numpy as np
+        assert isinstance(log, np.ndarray) and log.dtype == np.uint32 and log.flags.c_contiguous and log.flags.writeable and log.ndim == 1
+        self._check(self.lib.ac3mi_debug_launch_log(ctypes.c_void_p(self.ctx), ctypes.c_void_p(log.ctypes.data), int(log.size)))
+
     def set_decode_crc(self, mode):
         """CRC verification of the frames the decode and transcode calls read (ac3mi_set_decode_crc): 0 = none (liba52),
         1 = report in status bits 10 / 11 (flags.STATUS_CRC1 / STATUS_CRC2), 2 = also decode a failing frame as a refused

@@ -186,6 +186,20 @@ int ac3mi_fill_workspaces(ac3mi_ctx *ctx, int byte);
  * (tests/test_search_window_gpu.py).  AC3MI_ERR_ARG: null context. */
 int ac3mi_debug_search_curve(ac3mi_ctx *ctx, int32_t *d_curve);
 
+/* A test aid (new): which kernels a batch call launched.  h_log: HOST memory of `capacity` 32-bit words that the caller keeps
+ * alive while the tap is set, or null to end the tap.  Setting it writes h_log[0] = 0.  While it is set, every launch that
+ * ac3mi_decode_batch, ac3mi_decode_s16_batch, ac3mi_encode_batch and ac3mi_transcode_batch make (tiled by
+ * ac3mi_set_tile_frames or not) of a kernel of the launch rule's ten families (csrc/launch_rule.h: the decoder's front ends,
+ * mantissa kernels and generator prefix, the encoder's front, coupling, search and packer kernels) increments h_log[0] and,
+ * while h_log[0] < capacity, stores family << 24 | variant word (the rule's KernelFamily value and variant word; the two
+ * kernels that are no templates log word 0) at h_log[h_log[0]]: in launch order, at launch time, by the host thread that
+ * makes the call - so h_log[0] counts the launches since the tap was set, those that no longer fit included.  Kernels outside
+ * those families (transform, CRC, DRC, history, BSI, converters) are not logged.  Host-side bookkeeping only: nothing is
+ * written on the device, no launch, workspace or result changes, and a context that never sets it pays nothing
+ * (tests/test_variant_matrix_gpu.py decodes the words through tests/launch_rule_c's table).
+ * AC3MI_ERR_ARG: null context, or h_log set with capacity < 1. */
+int ac3mi_debug_launch_log(ac3mi_ctx *ctx, uint32_t *h_log, int capacity);
+
 /* CRC verification of the frames ac3mi_decode_batch / ac3mi_decode_s16_batch / ac3mi_transcode_batch read (new; applies to
  * every following such call on `ctx`, under every ac3mi_set_decode_mode, with or without state slots, mix state, taps and
  * tiling).  liba52 never looks at a frame's two CRC words, so a frame damaged in its mantissas parses without a block error,

@@ -1,6 +1,8 @@
 // The launch rule of csrc/launch_rule.h on the rows of grid.h, one canonical line a row, for tests/test_launch_rule_cpu.py:
 //   main enc | dec     the reduced grids
 //   main lists         every listed variant, by its kernel's name
+//   main words         "family word name" of every listed variant: the one table that ties a word of the launch log
+//                      (ac3mi_debug_launch_log; written here by log_launch itself) to a kernel's name
 //   main pairs         a row on either side of every threshold
 //   main plan          dec_choice's mantx answer for the calls ac3mi_transcode_workspace_plan describes
 // Built with the host compiler under -fsanitize=address,undefined; nothing here but the header under test and grid.h.
@@ -83,6 +85,19 @@ template <size_t N> static void list(int family, const uint32_t (&v)[N])
     for (uint32_t w : v) puts(kernel_name(family, w).c_str());
 }
 
+// the listed variants through log_launch, as the launchers log them: family, variant word and name of each logged word
+template <size_t N> static void words(KernelFamily family, const uint32_t (&v)[N])
+{
+    uint32_t h[2 + N] = {};
+    const LaunchLog log = {h, (int)(1 + N)};        // (one word short of the array: the last slot must stay as it is)
+    h[1 + N] = 0xa5a5a5a5u;
+    for (uint32_t w : v) log_launch(&log, kernel_launch(family, w, G_STREAM, 64));
+    log_launch(&log, kernel_launch(family, v[0], G_STREAM, 64));       // no longer fits: counted, not stored
+    log_launch(nullptr, kernel_launch(family, v[0], G_STREAM, 64));
+    if (h[0] != N + 1 || h[1 + N] != 0xa5a5a5a5u) abort();
+    for (size_t i = 1; i <= N; i++) printf("%u %u %s\n", h[i] >> 24, h[i] & 0xffffffu, kernel_name((int)(h[i] >> 24), h[i] & 0xffffffu).c_str());
+}
+
 int main(int argc, char **argv)
 {
     const char *what = argc > 1 ? argv[1] : "";
@@ -99,6 +114,17 @@ int main(int argc, char **argv)
         list(K_ENC_SEARCH, ENC_SEARCH_VARIANTS);
         list(K_ENC_PACKF, ENC_PACKF_VARIANTS);
         list(K_ENC_PACKB, ENC_PACKB_VARIANTS);
+    } else if (!strcmp(what, "words")) {
+        words(K_DECODE, DECODE_VARIANTS);
+        words(K_DECODE_WG, DECODE_WG_VARIANTS);
+        words(K_LFSR_PREFIX, PLAIN_VARIANT);
+        words(K_MANT, PLAIN_VARIANT);
+        words(K_MANTX, MANTX_VARIANTS);
+        words(K_ENC_MDCT, ENC_MDCT_VARIANTS);
+        words(K_ENC_CPL, ENC_CPL_VARIANTS);
+        words(K_ENC_SEARCH, ENC_SEARCH_VARIANTS);
+        words(K_ENC_PACKF, ENC_PACKF_VARIANTS);
+        words(K_ENC_PACKB, ENC_PACKB_VARIANTS);
     } else if (!strcmp(what, "pairs")) {
         // decoder, 5.1 to s16, auto: 512 | 513 streams of one frame; four | five frames at 512 streams; 5 119 | 5 120 streams of two
         grid::DecRow d = {0, 512, 1, 1, 0, 0, 1, 0, 1, 7, 1, 0};

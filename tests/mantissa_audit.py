@@ -67,6 +67,19 @@ def frame_rows(mdct, shift, nfchans, lfeon, cpl=None):
     return rows, shifts
 
 
+def tap_rows(t):
+    """rows(s, f, P) for audit_mantissas from the `mdct` / `exp_samples` taps [S][F]... of the encode call that made the
+    frames: the coded rows as the taps show them, the coupling row of a coupled frame from tests/coupling_model.py"""
+    from tests import coupling_model as C
+
+    def rows(s, f, P):
+        cpl = None
+        if P.blocks[0].cplinu:
+            cpl = C.coupling_rows(t["mdct"][s, f], t["exp_samples"][s, f], P.nfchans, P.blocks[0].cplbegf)
+        return frame_rows(t["mdct"][s, f], t["exp_samples"][s, f], P.nfchans, P.lfeon, cpl)
+    return rows
+
+
 def audit_mantissas(rep, frames, rows, shifts, label, parsed=None):
     """see the module docstring; parsed[s][f], when given, receives each frame's parse (for the caller's own checks)"""
     S, nfr = frames.shape[:2]

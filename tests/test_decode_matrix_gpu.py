@@ -18,6 +18,7 @@ import pytest
 
 from tests import _decode_matrix as M
 from tests import _harness as H
+from tests import variant_matrix as V
 
 pytestmark = pytest.mark.gpu
 
@@ -27,6 +28,26 @@ ALL = pytest.mark.parametrize("case", M.CASE_LIST, ids=M.case_id)
 def _restore(engine):
     engine.set_decode_mode(int(os.environ.get("AC3MI_DECODE_MODE", "0")))
     engine.set_fixed_shape(1)
+
+
+FRONT = {1: [V.dec(0)], 4: [V.dec(4), V.MANT], 5: [V.dec(5), V.LFSR, V.MANT]}
+
+
+def _forced(engine, mode, frames, case, flags, **kw):
+    """M.decode under ac3mi_set_decode_mode `mode` - and the call launched that mode's front end (ac3mi_debug_launch_log): 1, 4
+    and 5 their kernels exactly, 3 the one-workgroup-per-stream kernel alone, 6 the per-stream parse kernel and then
+    mantx_kernel where the call is one it fuses (one-frame streams, no downmix, no taps), else mant_kernel"""
+    engine.set_decode_mode(mode)
+    with V.tap(engine) as log:
+        got = M.decode(engine, frames, case, flags, **kw)
+    if mode in FRONT:
+        assert log == FRONT[mode], (mode, log)
+    elif mode == 3:
+        assert len(log) == 1 and V.families(log) == {"decode_wg_kernel"}, log
+    elif mode == 6:
+        fuses = frames.shape[1] == 1 and flags == M.requests(case)[0] and not kw.get("taps")
+        assert len(log) == 2 and log[0].startswith("decode_kernel<4,") and log[1].startswith("mantx_kernel" if fuses else "mant_kernel"), log
+    return got
 
 
 def _bits(a):
@@ -53,8 +74,7 @@ def test_stages(engine, case):
     res = {}
     try:
         for mode in (1, 3, 4, 5):
-            engine.set_decode_mode(mode)
-            res[mode] = M.decode(engine, frames, case, flags, taps=True)
+            res[mode] = _forced(engine, mode, frames, case, flags, taps=True)
     finally:
         _restore(engine)
     got = res[1]
@@ -87,8 +107,7 @@ def test_bytes_behind_a_frame_are_not_the_frame(engine, case):
     want = M.liba52_stages((case, "overrun"), frames, acmod, flags)
     try:
         for mode in (1, 3, 4, 5):
-            engine.set_decode_mode(mode)
-            got = M.decode(engine, frames, case, flags, taps=True)
+            got = _forced(engine, mode, frames, case, flags, taps=True)
             assert (got["status"] & 0x1ff).max() == 0, (mode, got["status"])
             assert np.array_equal(got["lfsr"].astype(np.int64) & 0xffff, want["lfsr"]), mode
             assert np.array_equal(_bits(got["coef"]), _bits(want["coef"][:, :, :, :nf + lfe])), "mode %d: coefficient planes differ" % mode
@@ -154,14 +173,12 @@ def test_requests(engine, case):
             differs = M.forgotten_bias(case, frames, req, 384.0 if s16 else 0.0)
             for mix in (True, False):
                 how = what + (", mix state" if mix else ", plain mix")
-                engine.set_decode_mode(1)
-                base = M.decode(engine, frames, case, req, s16=s16, level=level, dynrng=dynrng, mix=mix)
+                base = _forced(engine, 1, frames, case, req, s16=s16, level=level, dynrng=dynrng, mix=mix)
                 assert base["pcm"].any()
                 hold(how, base, ref, _whole(frames) if mix else np.where(differs, 0, _whole(frames)), s16)
                 for mode in (3, 4, 5, 0):
-                    engine.set_decode_mode(mode)
                     try:
-                        M.same(M.decode(engine, frames, case, req, s16=s16, level=level, dynrng=dynrng, mix=mix), base,
+                        M.same(_forced(engine, mode, frames, case, req, s16=s16, level=level, dynrng=dynrng, mix=mix), base,
                                "%s: mode %d against mode 1" % (how, mode))
                     except AssertionError as e:
                         missed.append(str(e))
@@ -192,8 +209,7 @@ def _fused_reference(engine, case, s16):
     """mode 4 on the nine one-frame streams from the mid-run state, held to the restatement fed the same state; once"""
     if (case, s16) not in _FUSED:
         frames, flags, state = M.single(case), M.requests(case)[0], _single_state(case)
-        engine.set_decode_mode(4)
-        base = M.decode(engine, frames, case, flags, s16=s16, state=state)
+        base = _forced(engine, 4, frames, case, flags, s16=s16, state=state)
         ref = M.liba52((case, "single"), frames, flags, 384.0 if s16 else 0.0, state=state)
         fig = M.held_to_liba52(base, ref, _whole(frames), s16)
         print("%s one-frame streams from mid-run state, %s" % (M.case_id(case),
@@ -213,11 +229,10 @@ def test_fused_kernel(engine, case):
         for s16 in (False, True):
             base = _fused_reference(engine, case, s16)
             for mode in (6, 0):
-                engine.set_decode_mode(mode)
-                M.same(M.decode(engine, frames, case, flags, s16=s16, state=state), base, "mode %d against mode 4" % mode)
+                M.same(_forced(engine, mode, frames, case, flags, s16=s16, state=state), base, "mode %d against mode 4" % mode)
                 if case == M.FIXED_SHAPE_CASE:
                     engine.set_fixed_shape(0)
-                    M.same(M.decode(engine, frames, case, flags, s16=s16, state=state), base, "mode %d, generic kernels, against mode 4" % mode)
+                    M.same(_forced(engine, mode, frames, case, flags, s16=s16, state=state), base, "mode %d, generic kernels, against mode 4" % mode)
                     engine.set_fixed_shape(1)
             # the state decided something: from new streams' state, other samples
             engine.set_decode_mode(4)
@@ -237,11 +252,10 @@ def test_two_calls_equal_one(engine, case):
     head, tail = np.ascontiguousarray(frames[:, :1]), np.ascontiguousarray(frames[:, 1:])
     try:
         for mode in (4, 5):
-            engine.set_decode_mode(mode)
             for req, s16 in ((M.requests(case)[0], False), (M.requests(case)[0], True), (M.downmix_request(case), False)):
-                one = M.decode(engine, frames, case, req, s16=s16)
-                a = M.decode(engine, head, case, req, s16=s16)
-                b = M.decode(engine, tail, case, req, s16=s16, state=(a["delay"], a["lfsr"]))
+                one = _forced(engine, mode, frames, case, req, s16=s16)
+                a = _forced(engine, mode, head, case, req, s16=s16)
+                b = _forced(engine, mode, tail, case, req, s16=s16, state=(a["delay"], a["lfsr"]))
                 two = dict(pcm=np.concatenate([a["pcm"], b["pcm"]], axis=1), status=np.concatenate([a["status"], b["status"]], axis=1),
                            delay=b["delay"], lfsr=b["lfsr"])
                 M.same(two, one, "mode %d request %d%s: two calls against one" % (mode, req, " s16" if s16 else ""))

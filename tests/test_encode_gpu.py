@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import _harness as H
+from tests import variant_matrix as V
 
 pytestmark = pytest.mark.gpu
 
@@ -286,15 +287,20 @@ def test_batch_shape_paths_agree(engine):
     x = torch.from_numpy(np.stack(pcm).reshape(S, F, 1536, 6)).cuda()
     last = torch.zeros((S, 6, 256), dtype=torch.int16, device="cuda")
     csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-    whole = engine.encode_batch(desc, x, H.CHMAP6, last, csnr)
-    engine.sync()
+    with V.tap(engine) as whole_log:
+        whole = engine.encode_batch(desc, x, H.CHMAP6, last, csnr)
+        engine.sync()
     last1 = torch.zeros((S, 6, 256), dtype=torch.int16, device="cuda")
     csnr1 = torch.full((S,), 40, dtype=torch.int32, device="cuda")
     parts = []
-    for f in range(F):
-        parts.append(engine.encode_batch(desc, x[:, f:f + 1].contiguous(), H.CHMAP6, last1, csnr1))
-        engine.sync()
+    with V.tap(engine) as step_log:
+        for f in range(F):
+            parts.append(engine.encode_batch(desc, x[:, f:f + 1].contiguous(), H.CHMAP6, last1, csnr1))
+            engine.sync()
     step = torch.cat(parts, dim=1)
+    # the routes the name speaks of were taken (ac3mi_debug_launch_log): the tabulating search in the whole call alone
+    assert V.search(3) in whole_log and V.search(1) in whole_log, whole_log
+    assert len(step_log) == 3 * F and not any(k.startswith("enc_search_kernel<3") for k in step_log), step_log
     assert torch.equal(whole.cpu(), step.cpu())
     assert torch.equal(last.cpu(), last1.cpu()) and torch.equal(csnr.cpu(), csnr1.cpu())
     want, _ = _oracle(pcm, 6, 384000)
@@ -321,8 +327,12 @@ def test_block_packer_equals_the_stream_packer(engine, nch, bitrate, freq):
                 engine.set_encode_mode(mode)
                 last = torch.zeros((S, nch, 256), dtype=torch.int16, device="cuda")
                 csnr = torch.full((S,), 40, dtype=torch.int32, device="cuda")
-                frames, taps = engine.encode_batch(desc, pcm, chmap, last, csnr, taps=True)
-                engine.sync()
+                with V.tap(engine) as log:
+                    frames, taps = engine.encode_batch(desc, pcm, chmap, last, csnr, taps=True)
+                    engine.sync()
+                # mode 1 packed with one wavefront per frame, mode 2 with one per audio block
+                assert ("enc_packf_kernel" if mode == 1 else "enc_packb_kernel") in V.families(log), (mode, log)
+                assert ("enc_packb_kernel" if mode == 1 else "enc_packf_kernel") not in V.families(log), (mode, log)
                 res[mode] = [x.cpu().numpy() for x in (frames, last, csnr, taps["bap"], taps["snroffst"], taps["exp_strategy"])]
         finally:
             engine.set_encode_mode(int(os.environ.get("AC3MI_ENCODE_MODE", "0")))

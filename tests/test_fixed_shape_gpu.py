@@ -12,6 +12,7 @@ import pytest
 from tests import _harness as H
 from tests import _tools as T
 from tests import ac3_syntax as A
+from tests import variant_matrix as V
 
 pytestmark = pytest.mark.gpu
 
@@ -53,15 +54,32 @@ def _state(S, n_out, seed):
                 csnr=(rng.integers(6, 34, S) | (rng.integers(0, 16, S) << 8)).astype(np.int32))
 
 
-def _both(engine, call):
-    """call() with the switch on and off -> the two lists of host arrays"""
+def _fx(log):
+    """the fixed-shape kernels among a log's names: the five FX instantiations of csrc/launch_rule.h"""
+    fx = {V.dec(4, fx=1), V.mantx(s16=1, fx=1), V.mdct(fx=1), V.search(1, fx=1)} | {V.packf(fx=1, bw=b, md=m, dw=w) for b in (0, 1) for m, w in ((0, 0), (1, 0), (1, 1))}
+    return [k for k in log if k in fx]
+
+
+DEC_FX = {V.dec(4, fx=1), V.mantx(s16=1, fx=1)}
+
+
+def _both(engine, call, fixed=True, mode=0):
+    """call() with the switch on and off, under ac3mi_set_decode_mode `mode` -> the two lists of host arrays.  What the switch
+    is said to do, it did (ac3mi_debug_launch_log): a call of the fixed shape (`fixed`) launched fixed-shape kernels with the
+    switch on and none with it off; any other call launched none either way.  Mode 6: the decoder's two among them (the
+    default mode hands batches of up to 512 streams to the one-workgroup-per-stream kernel, which has no such instantiation)"""
     res = []
     try:
+        engine.set_decode_mode(mode)
         for on in (1, 0):
             engine.set_fixed_shape(on)
-            res.append([np.ascontiguousarray(t.cpu().numpy()) for t in call()])
+            with V.tap(engine) as log:
+                res.append([np.ascontiguousarray(t.cpu().numpy()) for t in call()])
+            assert bool(_fx(log)) == bool(fixed and on), (on, log)
+            assert mode != 6 or DEC_FX <= set(log) or not (fixed and on), (on, log)
     finally:
         engine.set_fixed_shape(1)
+        engine.set_decode_mode(0)
     return res
 
 
@@ -95,9 +113,10 @@ TC_NAMES = "frames status delay lfsr last_samples csnroffst".split()
 @pytest.mark.parametrize("S", SIZES)
 @pytest.mark.parametrize("kind", sorted(SOURCES))
 def test_transcode(engine, sources, kind, S):
-    on, off = _both(engine, _transcode(engine, sources[kind][:S], seed=10 + S))
-    _same(TC_NAMES, on, off)
-    assert int((on[1] & 0x1ff).max()) == 0 and on[0].any()
+    for mode in (0, 6):         # (6: the split front end's fixed-shape kernels, whatever the batch size)
+        on, off = _both(engine, _transcode(engine, sources[kind][:S], seed=10 + S), mode=mode)
+        _same(TC_NAMES, on, off)
+        assert int((on[1] & 0x1ff).max()) == 0 and on[0].any()
 
 
 def test_transcode_refused_frames(engine, sources):
@@ -126,8 +145,13 @@ def test_decode_s16(engine, sources, kind, S):
         pcm, status = engine.decode_s16_batch(dec, src, delay, lfsr)
         engine.sync()
         return pcm, status, delay, lfsr
-    on, off = _both(engine, call)
+    # the default mode decodes so small a batch in the one-workgroup-per-stream kernel, which has no fixed-shape
+    # instantiation; mode 6 takes the split front end, whose parse and mantissa kernels have
+    on, off = _both(engine, call, fixed=False)
     _same("pcm status delay lfsr".split(), on, off)
+    on6, off6 = _both(engine, call, mode=6)
+    _same("pcm status delay lfsr".split(), on6, off6)
+    _same("pcm status delay lfsr".split(), on6, on)
     assert int((on[1] & 0x1ff).max()) == 0 and on[0].any()
 
 
@@ -170,7 +194,7 @@ def test_other_calls_take_the_generic_kernels(engine, sources):
              "3/2": _transcode(engine, T.encode(engine, _bursts(S, nch=5, seed=7500)), 7, 0, 7, tuple(range(5)), 384000, seed=92),
              "two frames": _transcode(engine, T.encode(engine, _bursts(S, F=2, seed=7600)), seed=93)}
     for name, call in calls.items():
-        on, off = _both(engine, call)
+        on, off = _both(engine, call, fixed=False)
         _same(TC_NAMES, on, off)
         assert int((on[1] & 0x1ff).max()) == 0, name
     plain = _transcode(engine, sources["plain"][:S], seed=94)
@@ -181,6 +205,6 @@ def test_other_calls_take_the_generic_kernels(engine, sources):
             return plain()
         finally:
             engine.set_encode_drc(0)
-    on, off = _both(engine, with_drc)
+    on, off = _both(engine, with_drc, fixed=False)
     _same(TC_NAMES, on, off)
     assert not np.array_equal(on[0], plain()[0].cpu().numpy())          # (DRC was on: other bytes than without)

@@ -24,7 +24,6 @@ import numpy as np
 import pytest
 
 from tests import _tools as T
-from tests import coupling_model as C
 from tests import layout_model as M
 from tests import mantissa_audit as MA
 from tests.test_frame_budget_gpu import RATES, TOOLS, matrix_content, matrix_rate, settings, tool_sets
@@ -39,14 +38,7 @@ def audited_encode(engine, rep, pcm, label, **kw):
     frames, t = T.encode(engine, pcm, taps=True, **kw)
     S, F = frames.shape[:2]
     parsed = [[None] * F for _ in range(S)]
-
-    def rows(s, f, P):
-        cpl = None
-        if P.blocks[0].cplinu:
-            cpl = C.coupling_rows(t["mdct"][s, f], t["exp_samples"][s, f], P.nfchans, P.blocks[0].cplbegf)
-        return MA.frame_rows(t["mdct"][s, f], t["exp_samples"][s, f], P.nfchans, P.lfeon, cpl)
-
-    MA.audit_mantissas(rep, frames, rows, None, label, parsed)
+    MA.audit_mantissas(rep, frames, MA.tap_rows(t), None, label, parsed)
     return frames, parsed
 
 
