@@ -12,6 +12,7 @@ The directory name contains hyphens, so import it with
 from .capi import LIB_PATH, load_library, declared_symbols, AC3MIError  # noqa: F401
 from .engine import Engine, XformDesc, DecodeDesc, EncodeDesc, syncinfo, bsi_read, frame_scan, encode_metadata_word  # noqa: F401
 from .engine import loudness_state_bytes, loudness_roles, loudness_tables, loudness_read  # noqa: F401
+from .engine import loudness_range_state_bytes, loudness_range_read  # noqa: F401
 from .engine import truepeak_state_bytes, truepeak_tables, truepeak_ceiling, truepeak_read, truepeak_host  # noqa: F401
 from . import flags  # noqa: F401
 from . import sharding  # noqa: F401

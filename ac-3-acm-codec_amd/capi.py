@@ -88,6 +88,24 @@ def loudness_result_dtype():
     return dt
 
 
+class LoudnessRangeResultC(ctypes.Structure):
+    """ac3mi_loudness_range_result"""
+    _fields_ = [("max_short_energy", ctypes.c_double), ("lra", ctypes.c_float), ("low_lkfs", ctypes.c_float), ("high_lkfs", ctypes.c_float),
+                ("max_short_lkfs", ctypes.c_float), ("blocks", ctypes.c_uint32), ("blocks_abs", ctypes.c_uint32),
+                ("blocks_rel", ctypes.c_uint32), ("lra_tenths", ctypes.c_uint16), ("low_bin", ctypes.c_uint16),
+                ("high_bin", ctypes.c_uint16), ("flags", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 5)]
+
+
+def loudness_range_result_dtype():
+    """ac3mi_loudness_range_result as a numpy structured dtype (48 bytes; a uint8 tensor [..., 48] views as it)"""
+    import numpy as np
+    dt = np.dtype([("max_short_energy", "<f8"), ("lra", "<f4"), ("low_lkfs", "<f4"), ("high_lkfs", "<f4"), ("max_short_lkfs", "<f4"),
+                   ("blocks", "<u4"), ("blocks_abs", "<u4"), ("blocks_rel", "<u4"), ("lra_tenths", "<u2"), ("low_bin", "<u2"),
+                   ("high_bin", "<u2"), ("flags", "u1"), ("reserved", "u1", (5,))])
+    assert dt.itemsize == ctypes.sizeof(LoudnessRangeResultC) == 48
+    return dt
+
+
 class TruePeakResultC(ctypes.Structure):
     """ac3mi_truepeak_result"""
     _fields_ = [("true_peak_index", ctypes.c_uint64), ("samples", ctypes.c_uint64), ("true_peak", ctypes.c_uint32),
@@ -198,6 +216,11 @@ def load_library():
     lib.ac3mi_loudness_read_batch.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
     lib.ac3mi_loudness_read.argtypes = [c_void_p, ctypes.POINTER(LoudnessResultC)]
     lib.ac3mi_loudness_words_batch.argtypes = [c_void_p, c_void_p, c_int, c_int, ctypes.c_uint32, c_void_p]
+    lib.ac3mi_loudness_range_state_bytes.restype = c_size_t
+    lib.ac3mi_loudness_range_state_bytes.argtypes = []
+    lib.ac3mi_loudness_range_batch.argtypes = [c_void_p, ctypes.POINTER(LoudnessDescC), c_void_p, c_int, c_int, c_void_p, c_void_p]
+    lib.ac3mi_loudness_range_read_batch.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
+    lib.ac3mi_loudness_range_read.argtypes = [c_void_p, ctypes.POINTER(LoudnessRangeResultC)]
     lib.ac3mi_truepeak_state_bytes.restype = c_size_t
     lib.ac3mi_truepeak_state_bytes.argtypes = []
     lib.ac3mi_truepeak_tables.argtypes = [c_void_p]

@@ -283,9 +283,12 @@ struct LoudnessLaunch {
     int n_streams, frames_per_stream;
     void *state;                    // [S] LoudState
     const double *tab;
+    void *range_state = nullptr;    // [S] RangeState: the range meter beside it (ac3mi_loudness_range_batch); nullptr: the plain meter
 };
 hipError_t launch_loudness(const LoudnessLaunch &L, hipStream_t stream);
 hipError_t launch_loudness_read(const void *state, int n_streams, const double *tab, ac3mi_loudness_result *results, hipStream_t stream);
+hipError_t launch_loudness_range_read(const void *range_state, int n_streams, const double *tab, ac3mi_loudness_range_result *results,
+                                      hipStream_t stream);
 hipError_t launch_loudness_words(const ac3mi_loudness_result *results, int n_streams, int frames_per_stream, uint32_t base_word,
                                  uint32_t *words, hipStream_t stream);
 

@@ -1331,20 +1331,22 @@ static int loud_tab_ready(ac3mi_ctx *ctx, const char *who)
     return AC3MI_OK;
 }
 
-int ac3mi_loudness_batch(ac3mi_ctx *ctx, const ac3mi_loudness_desc *desc, const int16_t *d_pcm, int n_streams,
-                         int frames_per_stream, void *d_state)
+// the plain meter (d_range_state nullptr, with_range false) and the one that meters the range beside it
+static int loudness_batch(ac3mi_ctx *ctx, const char *who, const ac3mi_loudness_desc *desc, const int16_t *d_pcm, int n_streams,
+                          int frames_per_stream, void *d_state, void *d_range_state, bool with_range)
 {
     if (!ctx) return AC3MI_ERR_ARG;
     bool ok = desc && d_pcm && d_state && n_streams >= 0 && frames_per_stream >= 1 && !((uintptr_t)d_pcm & 1) && !((uintptr_t)d_state & 7);
+    ok = ok && (!with_range || (d_range_state && !((uintptr_t)d_range_state & 7)));
     ok = ok && (desc->sample_rate == 48000 || desc->sample_rate == 44100 || desc->sample_rate == 32000) && desc->channels >= 1 && desc->channels <= 6;
     for (int c = 0; ok && c < desc->channels; c++) ok = desc->role[c] <= 2;
     if (!ok) {
-        ctx->err = "ac3mi_loudness_batch: bad argument";
+        ctx->err = std::string(who) + ": bad argument";
         return AC3MI_ERR_ARG;
     }
     if (n_streams == 0) return AC3MI_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (int rc = loud_tab_ready(ctx, "ac3mi_loudness_batch")) return rc;
+    if (int rc = loud_tab_ready(ctx, who)) return rc;
     LoudnessLaunch L;
     L.pcm = d_pcm;
     L.sample_rate = desc->sample_rate;
@@ -1354,7 +1356,34 @@ int ac3mi_loudness_batch(ac3mi_ctx *ctx, const ac3mi_loudness_desc *desc, const 
     L.frames_per_stream = frames_per_stream;
     L.state = d_state;
     L.tab = ctx->loud_tab;
+    L.range_state = with_range ? d_range_state : nullptr;
     HIPCHK(ctx, launch_loudness(L, ctx->stream));
+    return AC3MI_OK;
+}
+
+int ac3mi_loudness_batch(ac3mi_ctx *ctx, const ac3mi_loudness_desc *desc, const int16_t *d_pcm, int n_streams,
+                         int frames_per_stream, void *d_state)
+{
+    return loudness_batch(ctx, "ac3mi_loudness_batch", desc, d_pcm, n_streams, frames_per_stream, d_state, nullptr, false);
+}
+
+int ac3mi_loudness_range_batch(ac3mi_ctx *ctx, const ac3mi_loudness_desc *desc, const int16_t *d_pcm, int n_streams,
+                               int frames_per_stream, void *d_state, void *d_range_state)
+{
+    return loudness_batch(ctx, "ac3mi_loudness_range_batch", desc, d_pcm, n_streams, frames_per_stream, d_state, d_range_state, true);
+}
+
+int ac3mi_loudness_range_read_batch(ac3mi_ctx *ctx, const void *d_range_state, int n_streams, ac3mi_loudness_range_result *d_results)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (!d_range_state || !d_results || n_streams < 0 || ((uintptr_t)d_range_state & 7) || ((uintptr_t)d_results & 7)) {
+        ctx->err = "ac3mi_loudness_range_read_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    if (n_streams == 0) return AC3MI_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = loud_tab_ready(ctx, "ac3mi_loudness_range_read_batch")) return rc;
+    HIPCHK(ctx, launch_loudness_range_read(d_range_state, n_streams, ctx->loud_tab, d_results, ctx->stream));
     return AC3MI_OK;
 }
 

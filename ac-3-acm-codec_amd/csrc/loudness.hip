@@ -22,6 +22,16 @@
 // loudness_read_kernel: one wavefront per stream; lane l sums bins l, l + 64, ... (loud_total_part / loud_gated_part, the code
 // the host twin runs with stride 1), butterflies combine them, lane 0 writes the record.
 // loudness_words_kernel: one lane per frame.
+//
+// The loudness range meter (ac3mi_loudness_range_*, EBU Tech 3342) is loudness_kernel<.., RANGE = true>: where a hop closes, in
+// the branch that is the same in every lane, lane 0 hands the hop's energy to range_push_hop (loudness_rule.h) - ring, ordered
+// sum of 30, bin, counters, all in the range state in HBM with plain loads and stores; nothing of it is carried in registers
+// across the frame's filter work, and the RANGE = false instantiations are the kernels they were.
+// loudness_range_read_kernel: one wavefront per stream; lane l < 60 owns bins 15 l .. 15 l + 14 and reads them once, as what
+// each adds to the blocks that pass the relative gate (range_counted); a prefix scan over the lanes gives each the blocks
+// counted below its run, the lane whose run holds a rank finds its bin (range_bin_of_rank, the code the host twin runs over
+// all 900), lane 0 writes the record.  Integer work once Gamma3 is fixed, and Gamma3 is one division of two values every lane
+// reads alike: the record is the host twin's bit for bit.
 #include "loudness_rule.h"
 
 extern "C" size_t ac3mi_loudness_state_bytes(void) { return sizeof(ac3mi::LoudState); }
@@ -40,6 +50,15 @@ extern "C" int ac3mi_loudness_read(const void *h_state, ac3mi_loudness_result *o
 {
     if (!h_state || !out) return AC3MI_ERR_ARG;
     ac3mi::loudness_read_host(h_state, out);
+    return AC3MI_OK;
+}
+
+extern "C" size_t ac3mi_loudness_range_state_bytes(void) { return sizeof(ac3mi::RangeState); }
+
+extern "C" int ac3mi_loudness_range_read(const void *h_range_state, ac3mi_loudness_range_result *out)
+{
+    if (!h_range_state || !out) return AC3MI_ERR_ARG;
+    ac3mi::loudness_range_read_host(h_range_state, out);
     return AC3MI_OK;
 }
 
@@ -87,6 +106,7 @@ struct LoudParams {
     double block_samples;               // 4 hop
     double M[6][16];                    // A^(24 2^k)
     double Z[LOUD_SEG][4];              // C A^n
+    RangeState *range;                  // RANGE variants only (behind everything the others read: their arguments lie where they lay)
 };
 
 __device__ __forceinline__ double loud_readlane(double v, int l)
@@ -103,7 +123,7 @@ __device__ __forceinline__ double loud_wave_sum(double v)
     return v;
 }
 
-template <int NCH, bool VEC>
+template <int NCH, bool VEC, bool RANGE>
 __global__ __launch_bounds__(64 * LOUD_WAVES, LOUD_MIN_WAVES) void loudness_kernel(const LoudParams P)
 {
     const int lane = threadIdx.x & 63;
@@ -220,6 +240,9 @@ __global__ __launch_bounds__(64 * LOUD_WAVES, LOUD_MIN_WAVES) void loudness_kern
                     }
                 }
             }
+            if constexpr (RANGE) {
+                if (lane == 0) range_push_hop(P.range + s, P.edges, hn, 7.5 * P.block_samples);
+            }
             h0 = h1;
             h1 = h2;
             h2 = hn;
@@ -267,6 +290,44 @@ __global__ __launch_bounds__(64 * LOUD_WAVES) void loudness_read_kernel(const Lo
     if (lane == 0) loud_result(st, tab + LOUD_BINS + 1, sum, n, results + s);
 }
 
+__global__ __launch_bounds__(64 * LOUD_WAVES) void loudness_range_read_kernel(const RangeState *state, unsigned n_streams, const double *edges,
+                                                                             ac3mi_loudness_range_result *results)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned s = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * LOUD_WAVES + (threadIdx.x >> 6)));
+    if (s >= n_streams) return;
+    const RangeState *rs = state + s;
+    const double gamma = range_gamma(rs->sum_abs, rs->blocks_abs);
+    const bool owner = lane < RANGE_LANES;              // lanes 60..63 own no bins
+    const int first = owner ? lane * RANGE_RUN : 0;
+    uint32_t c[RANGE_RUN];              // what each of this lane's bins adds to the counted blocks: the state is read once
+#pragma unroll
+    for (int k = 0; k < RANGE_RUN; k++) {
+        const uint32_t v = range_counted(rs, edges, first + k, gamma);
+        c[k] = owner ? v : 0;
+    }
+    const uint64_t part = range_counted_sum(c, RANGE_RUN);
+    uint64_t incl = part;               // the blocks counted in this lane's bins and all below
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint64_t t = __shfl_up((unsigned long long)incl, (unsigned)o);
+        incl += lane >= o ? t : 0;
+    }
+    const uint64_t n = __shfl((unsigned long long)incl, 63);
+    int lo = -1, hi = -1;               // one lane's run holds each rank
+    if (n) {
+        lo = range_bin_of_rank(c, first, RANGE_RUN, incl - part, range_rank(n, 10));
+        hi = range_bin_of_rank(c, first, RANGE_RUN, incl - part, range_rank(n, 95));
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int a = __shfl_xor(lo, o), b = __shfl_xor(hi, o);
+        lo = a > lo ? a : lo;
+        hi = b > hi ? b : hi;
+    }
+    if (lane == 0) range_result(rs, n, lo, hi, results + s);
+}
+
 __global__ __launch_bounds__(256) void loudness_words_kernel(const ac3mi_loudness_result *results, unsigned n_frames, unsigned frames_per_stream,
                                                              uint32_t base_word, uint32_t *words)
 {
@@ -280,8 +341,13 @@ template <int NCH>
 static void loud_launch_nch(const LoudParams &P, bool vec, hipStream_t stream)
 {
     const dim3 grid((P.n_streams + LOUD_WAVES - 1) / LOUD_WAVES), block(64 * LOUD_WAVES);
-    if (vec) hipLaunchKernelGGL((loudness_kernel<NCH, true>), grid, block, 0, stream, P);
-    else hipLaunchKernelGGL((loudness_kernel<NCH, false>), grid, block, 0, stream, P);
+    if (P.range) {
+        if (vec) hipLaunchKernelGGL((loudness_kernel<NCH, true, true>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((loudness_kernel<NCH, false, true>), grid, block, 0, stream, P);
+    } else {
+        if (vec) hipLaunchKernelGGL((loudness_kernel<NCH, true, false>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((loudness_kernel<NCH, false, false>), grid, block, 0, stream, P);
+    }
 }
 
 hipError_t launch_loudness(const LoudnessLaunch &L, hipStream_t stream)
@@ -292,6 +358,7 @@ hipError_t launch_loudness(const LoudnessLaunch &L, hipStream_t stream)
     LoudParams P;
     P.pcm = L.pcm;
     P.state = (LoudState *)L.state;
+    P.range = (RangeState *)L.range_state;
     P.edges = L.tab;
     P.n_streams = (unsigned)L.n_streams;
     P.frames = L.frames_per_stream;
@@ -318,6 +385,14 @@ hipError_t launch_loudness_read(const void *state, int n_streams, const double *
     if (n_streams <= 0) return hipSuccess;
     hipLaunchKernelGGL(loudness_read_kernel, dim3(((unsigned)n_streams + LOUD_WAVES - 1) / LOUD_WAVES), dim3(64 * LOUD_WAVES), 0, stream,
                        (const LoudState *)state, (unsigned)n_streams, tab, results);
+    return hipGetLastError();
+}
+
+hipError_t launch_loudness_range_read(const void *range_state, int n_streams, const double *tab, ac3mi_loudness_range_result *results, hipStream_t stream)
+{
+    if (n_streams <= 0) return hipSuccess;
+    hipLaunchKernelGGL(loudness_range_read_kernel, dim3(((unsigned)n_streams + LOUD_WAVES - 1) / LOUD_WAVES), dim3(64 * LOUD_WAVES), 0, stream,
+                       (const RangeState *)range_state, (unsigned)n_streams, tab, results);
     return hipGetLastError();
 }
 

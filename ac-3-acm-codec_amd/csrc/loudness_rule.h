@@ -2,8 +2,10 @@
 // the frozen K-weighting coefficients, the bin-edge and dialnorm tables, and the three decisions - a block's bin, the gated
 // read-out of the bins, the dialnorm word - as __host__ __device__ functions that loudness_kernel / loudness_read_kernel
 // (loudness.hip) and the host twin ac3mi_loudness_read both call.  No decision uses a logarithm: blocks and means are
-// compared as energies against tables built once on the host in double.
-// Plain C++: compiles without HIP (a host-only build of loudness.hip for the sanitiser program of tests/loudness_c).
+// compared as energies against tables built once on the host in double.  Behind it the same for the loudness range meter
+// (ac3mi_loudness_range_*, EBU Tech 3342): RangeState, the one step that advances it, and the percentile read-out.
+// Plain C++: compiles without HIP (a host-only build of loudness.hip for the sanitiser programs of tests/loudness_c and
+// tests/loudness_range_c).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -188,6 +190,142 @@ inline void loudness_read_host(const void *h_state, ac3mi_loudness_result *out)
     loud_gated_part(st, T.edges, gamma, 0, 1, &s, &n);
     loud_result(st, T.thr, s, n, out);
     delete st;
+}
+
+// ---- the loudness range meter (ac3mi_loudness_range_*, EBU Tech 3342; the rule is include/ac3mi.h's): a second consumer of
+// the closed hop energies.  One stream's state (ac3mi_loudness_range_state_bytes() = sizeof): all zeros is a new stream.
+constexpr int RANGE_HOPS = 30;          // hops in a 3 s block
+constexpr int RANGE_LANES = 60;         // lanes of the read-out that own bins ...
+constexpr int RANGE_RUN = 15;           // ... this many each, one behind the other: 60 x 15 = 900
+
+struct RangeState {
+    double ring[RANGE_HOPS];            // ring[k]: the closed hop that was written at ring position k
+    double sum_abs;                     // the sum of z3 over the blocks at or above the absolute gate, added in time order
+    double max_short;                   // the largest short-term block energy z3 seen
+    uint32_t hops;                      // closed hops this state has seen, saturating (a block per hop from the 30th on)
+    uint32_t ring_pos;                  // 0..29, where the next closed hop goes (read modulo 30: garbage can only give wrong numbers)
+    uint32_t blocks, blocks_abs;        // 3 s blocks formed, and those at or above the absolute gate
+    uint32_t count[LOUD_BINS];          // per bin: the blocks in it
+};
+static_assert(sizeof(RangeState) == 3872 && offsetof(RangeState, count) == 272, "RangeState layout");
+static_assert(RANGE_LANES * RANGE_RUN == LOUD_BINS && RANGE_LANES <= 64, "the read-out's runs cover the bins");
+
+// A hop of energy h has closed: into the ring, and from the 30th on the 3 s block behind it - its 30 hops added oldest first,
+// one addition after the other (the order is the rule's: the same bits for every way of cutting a stream into calls) - into
+// the bins and counters.  block_samples = 30 hop.  The one place the state changes; plain loads and stores
+__host__ __device__ inline void range_push_hop(RangeState *rs, const double *edges, double h, double block_samples)
+{
+    const uint32_t pos = rs->ring_pos % (uint32_t)RANGE_HOPS;
+    uint32_t hops = rs->hops;
+    if (hops != 0xffffffffu) hops++;
+    rs->hops = hops;
+    rs->ring[pos] = h;
+    rs->ring_pos = pos + 1 == (uint32_t)RANGE_HOPS ? 0 : pos + 1;
+    if (hops < (uint32_t)RANGE_HOPS) return;
+    double s = 0.0;                     // oldest first: the entry behind pos is the oldest, pos itself the hop just closed
+    for (int k = 1; k <= RANGE_HOPS; k++) {
+        const uint32_t i = pos + (uint32_t)k;
+        const double v = rs->ring[i >= (uint32_t)RANGE_HOPS ? i - RANGE_HOPS : i];
+        s = k == 1 ? v : s + v;
+    }
+    const double z3 = s / block_samples;
+    rs->blocks += 1;
+    if (z3 > rs->max_short) rs->max_short = z3;
+    const int b = loud_bin(edges, z3);
+    if (b >= 0) {
+        rs->blocks_abs += 1;
+        rs->sum_abs += z3;
+        rs->count[b] += 1;
+    }
+}
+
+// Read-out.  The relative gate: -20 LU under the mean of the blocks above the absolute gate (no such block: 0)
+__host__ __device__ inline double range_gamma(double sum_abs, uint32_t blocks_abs) { return blocks_abs ? 0.01 * (sum_abs / (double)blocks_abs) : 0.0; }
+
+// ... a bin counts, whole, iff it has blocks and its upper edge lies above the gate (so the one bin the gate cuts counts)
+__host__ __device__ inline bool range_bin_included(const RangeState *rs, const double *edges, int b, double gamma)
+{
+    return rs->count[b] != 0 && edges[b + 1] > gamma;
+}
+
+// ... what bin b adds to the counted blocks: its count, or 0
+__host__ __device__ inline uint32_t range_counted(const RangeState *rs, const double *edges, int b, double gamma)
+{
+    return range_bin_included(rs, edges, b, gamma) ? rs->count[b] : 0;
+}
+
+// ... the blocks counted in a part of n bins, c[k] = range_counted of the part's k-th bin (the host: all 900; lane l: the 15
+// from 15 l on, in registers)
+__host__ __device__ inline uint64_t range_counted_sum(const uint32_t *c, int n)
+{
+    uint64_t t = 0;
+    for (int k = 0; k < n; k++) t += c[k];
+    return t;
+}
+
+// ... the 0-based rank, ascending, of the pct-th percentile among n >= 1 counted blocks: (n - 1) pct / 100 + 0.5, truncated
+__host__ __device__ inline uint64_t range_rank(uint64_t n, uint32_t pct) { return ((uint64_t)pct * (n - 1) + 50) / 100; }
+
+// ... the bin that holds the counted block of that rank, if it is one of the part's n bins from bin `first` on, `before`
+// blocks being counted in the bins below: the smallest b whose cumulative counted count exceeds rank; -1: not in this part
+__host__ __device__ inline int range_bin_of_rank(const uint32_t *c, int first, int n, uint64_t before, uint64_t rank)
+{
+    int found = -1;
+    uint64_t t = before;
+    for (int k = 0; k < n; k++) {
+        const bool here = found < 0 && t <= rank && t + c[k] > rank;
+        found = here ? first + k : found;
+        t += c[k];
+    }
+    return found;
+}
+
+// ... a bin's centre in LKFS, -70 + 0.1 b + 0.05, as one division of integers (the same float wherever it is evaluated)
+__host__ __device__ inline float range_bin_lkfs(int b) { return (float)((double)(10 * b - 6995) / 100.0); }
+
+// ... and the record, from the counted total and the two bins (low_bin, high_bin: anything when n == 0)
+__host__ __device__ inline void range_result(const RangeState *rs, uint64_t n, int low_bin, int high_bin, ac3mi_loudness_range_result *out)
+{
+    ac3mi_loudness_range_result r;
+    const double m = rs->max_short;
+    r.max_short_energy = m;
+    r.max_short_lkfs = m > 0.0 ? (float)(-0.691 + 10.0 * log10(m)) : -200.0f;
+    r.blocks = rs->blocks;
+    r.blocks_abs = rs->blocks_abs;
+    r.blocks_rel = n > 0xffffffffu ? 0xffffffffu : (uint32_t)n;         // (more than a state's counters can hold: garbage)
+    for (int i = 0; i < 5; i++) r.reserved[i] = 0;
+    if (n == 0 || low_bin < 0 || high_bin < low_bin) low_bin = high_bin = 0;
+    r.low_bin = (uint16_t)low_bin;
+    r.high_bin = (uint16_t)high_bin;
+    r.lra_tenths = (uint16_t)(high_bin - low_bin);
+    r.lra = 0.1f * (float)r.lra_tenths;
+    r.low_lkfs = n ? range_bin_lkfs(low_bin) : -70.0f;
+    r.high_lkfs = n ? range_bin_lkfs(high_bin) : -70.0f;
+    r.flags = n ? 0 : AC3MI_LOUDNESS_RANGE_EMPTY;
+    *out = r;
+}
+
+// The whole read-out on a state in host memory (any alignment)
+inline void loudness_range_read_host(const void *h_range_state, ac3mi_loudness_range_result *out)
+{
+    static const struct Edges {
+        double e[LOUD_BINS + 1];
+        Edges() { loud_build_edges(e); }
+    } T;
+    RangeState *rs = new RangeState;
+    memcpy(rs, h_range_state, sizeof *rs);
+    const double gamma = range_gamma(rs->sum_abs, rs->blocks_abs);
+    uint32_t *c = new uint32_t[LOUD_BINS];
+    for (int b = 0; b < LOUD_BINS; b++) c[b] = range_counted(rs, T.e, b, gamma);
+    const uint64_t n = range_counted_sum(c, LOUD_BINS);
+    int lo = 0, hi = 0;
+    if (n) {
+        lo = range_bin_of_rank(c, 0, LOUD_BINS, 0, range_rank(n, 10));
+        hi = range_bin_of_rank(c, 0, LOUD_BINS, 0, range_rank(n, 95));
+    }
+    delete[] c;
+    range_result(rs, n, lo, hi, out);
+    delete rs;
 }
 
 }  // namespace ac3mi

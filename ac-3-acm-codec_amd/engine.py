@@ -130,6 +130,25 @@ def loudness_read(state):
     return np.frombuffer(bytes(res), capi.loudness_result_dtype())[0]
 
 
+def loudness_range_state_bytes():
+    """ac3mi_loudness_range_state_bytes: bytes of one stream's range-meter state (all zeros: a new stream)"""
+    return int(capi.load_library().ac3mi_loudness_range_state_bytes())
+
+
+def loudness_range_read(state):
+    """ac3mi_loudness_range_read, the host read-out: one range state's bytes (ac3mi_loudness_range_state_bytes of them) -> a
+    numpy record of capi.loudness_range_result_dtype()"""
+    import numpy as np
+    lib = capi.load_library()
+    data = bytes(bytearray(state))
+    if len(data) != lib.ac3mi_loudness_range_state_bytes():
+        raise ValueError("a range state is %d bytes" % lib.ac3mi_loudness_range_state_bytes())
+    res = capi.LoudnessRangeResultC()
+    if lib.ac3mi_loudness_range_read(data, ctypes.byref(res)) != 0:
+        raise capi.AC3MIError("ac3mi_loudness_range_read: bad argument")
+    return np.frombuffer(bytes(res), capi.loudness_range_result_dtype())[0]
+
+
 def truepeak_state_bytes():
     """ac3mi_truepeak_state_bytes: bytes of one stream's true-peak state (all zeros: a new stream)"""
     return int(capi.load_library().ac3mi_truepeak_state_bytes())
@@ -598,6 +617,46 @@ class Engine:
         self._check(self.lib.ac3mi_loudness_read_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(state.data_ptr()), int(S),
                                                        ctypes.c_void_p(out.data_ptr())))
         self._keep.append((state, out))
+        return out
+
+    def loudness_range_batch(self, sample_rate, roles, pcm, state=None, range_state=None, wait_torch=True):
+        """ac3mi_loudness_range_batch: loudness_batch and the EBU Tech 3342 range meter in one pass over pcm -> (state,
+        range_state); range_state u8 [S][loudness_range_state_bytes()] belongs to the state it was started with (zeros: new
+        streams; default: allocated here, both together)."""
+        import torch
+        assert pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.is_cuda and pcm.dim() == 4 and pcm.shape[2] == 1536
+        S, F, _, nch = pcm.shape
+        nb, nr = int(self.lib.ac3mi_loudness_state_bytes()), int(self.lib.ac3mi_loudness_range_state_bytes())
+        if (state is None) != (range_state is None):
+            raise ValueError("a range state belongs to the loudness state it was started with: pass both or neither")
+        if state is None:
+            state = torch.zeros((S, nb), dtype=torch.uint8, device=pcm.device)
+            range_state = torch.zeros((S, nr), dtype=torch.uint8, device=pcm.device)
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == S * nb
+        assert range_state.dtype == torch.uint8 and range_state.is_contiguous() and range_state.is_cuda and range_state.numel() == S * nr
+        desc = capi.LoudnessDescC(int(sample_rate), int(nch), (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6]))
+        if len(roles) != nch:
+            raise ValueError("one role per channel")
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_loudness_range_batch(ctypes.c_void_p(self.ctx), ctypes.byref(desc), ctypes.c_void_p(pcm.data_ptr()), int(S),
+                                                        int(F), ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(range_state.data_ptr())))
+        self._keep.append((pcm, state, range_state))
+        return state, range_state
+
+    def loudness_range_read_batch(self, range_state, out=None, wait_torch=True):
+        """ac3mi_loudness_range_read_batch: range_state u8 [S][loudness_range_state_bytes()] -> results u8 [S][48];
+        `.cpu().numpy().view(capi.loudness_range_result_dtype())[..., 0]` names the fields."""
+        import torch
+        nr = int(self.lib.ac3mi_loudness_range_state_bytes())
+        assert range_state.dtype == torch.uint8 and range_state.is_contiguous() and range_state.is_cuda and range_state.numel() % nr == 0
+        S = range_state.numel() // nr
+        if out is None:
+            out = torch.zeros((S, 48), dtype=torch.uint8, device=range_state.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == S * 48
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_loudness_range_read_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(range_state.data_ptr()), int(S),
+                                                             ctypes.c_void_p(out.data_ptr())))
+        self._keep.append((range_state, out))
         return out
 
     def loudness_words_batch(self, results, frames_per_stream, base_word, out=None, wait_torch=True):

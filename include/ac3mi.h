@@ -417,6 +417,69 @@ int ac3mi_loudness_read(const void *h_state, ac3mi_loudness_result *out);
 int ac3mi_loudness_words_batch(ac3mi_ctx *ctx, const ac3mi_loudness_result *d_results, int n_streams, int frames_per_stream,
                                uint32_t base_word, uint32_t *d_words);
 
+/* Loudness range and maximum short-term loudness on the device (new): the third number of an EBU R128 / ATSC A/85 delivery
+ * check, LRA after EBU Tech 3342, and the largest 3 s loudness that short-form deliveries ask for in its place - metered in the
+ * same pass over the PCM as the integrated loudness, per stream, with the state carried from call to call.  (The maximum
+ * momentary loudness is not repeated here: it is ac3mi_loudness_result.max_block_energy.)  The whole rule; as in the loudness
+ * meter every decision is taken on energies and integers, never on a logarithm:
+ *   input, roles, K-weighting, hops   exactly ac3mi_loudness_batch's: the range meter is a second consumer of the same closed
+ *              hop energies h (the sum over measured slots of w * sum of y^2 over a hop of fs / 10 samples).
+ *   ring       the last 30 closed hop energies are kept per stream.
+ *   blocks     from the 30th closed hop of a stream on, every hop closes one 3 s block:
+ *                s = (((h[-29] + h[-28]) + h[-27]) + ... ) + h[0],  oldest first, one addition after the other, in double
+ *                (h[0]: the hop just closed);  z3 = s / (30 hop).
+ *              The order is part of the rule: it makes the state the same bits for every way of cutting a stream into calls.
+ *   bins       the loudness meter's edges E_b = 10^((-70 + 0.1 b + 0.691) / 10), b = 0..900, and its search.  z3 < E_0 fails
+ *              the absolute gate (-70 LUFS) and is only counted (blocks);  z3 >= E_900 goes to bin 899.  Per bin a u32 count
+ *              and no sum; beside the bins one double sum_abs, the sum of z3 over the blocks at or above the absolute gate,
+ *              added in time order, and max_short, the largest z3, gated or not.
+ *   read-out   Gamma3 = 0.01 * (sum_abs / blocks_abs), the relative gate: -20 LU under the mean of the absolutely gated blocks
+ *              (blocks_abs 0: Gamma3 = 0).  A bin counts iff its count is not 0 and its upper edge E_(b+1) > Gamma3: the one
+ *              bin the gate cuts counts whole.  This is the deviation from Tech 3342: blocks up to 0.1 LU under the gate may
+ *              be kept.  n = the blocks counted (blocks_rel).  With 64-bit integers
+ *                i10 = (10 (n - 1) + 50) / 100,  i95 = (95 (n - 1) + 50) / 100      ((n - 1) p + 0.5, truncated)
+ *              low_bin = the bin that holds the counted block of rank i10 (0-based, ascending): the smallest b whose
+ *              cumulative counted count exceeds i10;  high_bin the same for i95.
+ *   result     lra_tenths = high_bin - low_bin, an integer in tenths of a LU: the pinned quantity.  Informative floats, from
+ *              those integers, so that the host and the device give the same bits:  lra = 0.1f * lra_tenths;  low_lkfs and
+ *              high_lkfs = -70 + 0.1 b + 0.05, the bin's centre, evaluated as (10 b - 6995) / 100 in double and rounded to
+ *              float;  max_short_lkfs = -0.691 + 10 log10(max_short_energy), -200 when that is not above 0.
+ *              AC3MI_LOUDNESS_RANGE_EMPTY when n == 0 (silence, or less than 3 s): lra_tenths and both bins 0, lra 0,
+ *              low_lkfs and high_lkfs -70.
+ * The binned percentiles both floor into 0.1 LU bins, so lra_tenths / 10 lies within 0.1 LU of the percentiles taken over
+ * the list of z3 wherever no counted block lies in the bin the gate cuts. */
+typedef struct {
+    double max_short_energy;        /* the largest 3 s block energy, gated or not */
+    float lra;                      /* 0.1f * lra_tenths */
+    float low_lkfs, high_lkfs;      /* the centres of low_bin and high_bin */
+    float max_short_lkfs;           /* -0.691 + 10 log10(max_short_energy) */
+    uint32_t blocks, blocks_abs, blocks_rel;    /* 3 s blocks formed; at or above the absolute gate; counted after the relative gate */
+    uint16_t lra_tenths;            /* high_bin - low_bin: the pinned quantity */
+    uint16_t low_bin, high_bin;     /* the bins of the 10th and the 95th percentile */
+    uint8_t flags;                  /* AC3MI_LOUDNESS_RANGE_EMPTY */
+    uint8_t reserved[5];            /* 0 */
+} ac3mi_loudness_range_result;      /* 48 bytes */
+#define AC3MI_LOUDNESS_RANGE_EMPTY 1    /* no block passed the gates */
+
+/* Bytes of one stream's range state: opaque, in the caller's device memory, d_range_state[n_streams] records of this size
+ * (8-byte aligned); all zeros is a new stream.  It holds the ring of 30 hop energies and its position, the hop count, the
+ * bins, sum_abs, the block counters and the maximum.  A range state belongs to the loudness state it was started with (the
+ * filters and the position inside the open hop live there): zero both together, pass both to every call.  Hops metered
+ * through plain ac3mi_loudness_batch are simply missing from it. */
+size_t ac3mi_loudness_range_state_bytes(void);
+/* ac3mi_loudness_batch and the range meter in one pass over the PCM: d_state (not NULL) is left byte for byte as
+ * ac3mi_loudness_batch on the same arguments leaves it, d_range_state is advanced beside it.  AC3MI_ERR_ARG, with both states
+ * untouched: whatever ac3mi_loudness_batch refuses, and a NULL or misaligned d_range_state.  n_streams 0: AC3MI_OK, nothing
+ * is launched. */
+int ac3mi_loudness_range_batch(ac3mi_ctx *ctx, const ac3mi_loudness_desc *desc, const int16_t *d_pcm, int n_streams,
+                               int frames_per_stream, void *d_state, void *d_range_state);
+/* The read-out of n_streams range states into d_results[n_streams] (8-byte aligned), one wavefront per stream; the states are
+ * not changed. */
+int ac3mi_loudness_range_read_batch(ac3mi_ctx *ctx, const void *d_range_state, int n_streams, ac3mi_loudness_range_result *d_results);
+/* Host twin of the read-out, no GPU and no context: the same rule code on one state copied to host memory (any alignment);
+ * the record is the device's bit for bit. */
+int ac3mi_loudness_range_read(const void *h_range_state, ac3mi_loudness_range_result *out);
+
 /* True peak and clipping on the device (new): the maximum true-peak level after ITU-R BS.1770-4 Annex 2, the sample peak and
  * the number of full-scale samples of the same s16 PCM, per stream, with the state carried from call to call - a second meter
  * beside the loudness one, independent of it.  The whole rule, exact 32-bit integer arithmetic throughout:
