@@ -109,6 +109,10 @@ int build_mix_plan(int acmod, int lfeon, int output, MixPlan *plan);
 
 hipError_t launch_xform(const DeviceTables &tab, const XformLaunch &L, hipStream_t stream);
 
+// what the host needs of the split front end's block descriptor (BlkDesc, mant2.h, asserts both): its size, and the byte
+// offset of src_snr, the word a transcode's encoder reads as its search hint
+constexpr int BLKDESC_BYTES = 80, BLKDESC_SRC_SNR = 72;
+
 struct DecodeLaunch {
     const uint8_t *frames;
     int frame_bytes, frame_stride, n_streams, frames_per_stream;
@@ -130,7 +134,7 @@ struct DecodeLaunch {
     uint32_t *frame_draws;  // [S][F] workspace
     uint16_t *frame_lfsr;   // [S][F] workspace
     // split front end (choice.split: parse kernel + one wavefront per audio block): workspaces, all or none
-    void *ws_desc = nullptr;        // [S][F][6] BlkDesc (80 bytes)
+    void *ws_desc = nullptr;        // [S][F][6] BlkDesc (BLKDESC_BYTES)
     uint8_t *ws_rows = nullptr;     // [S][F][6][7][512]
     float *ws_cplco = nullptr;      // [S][F][6][90]
     uint32_t *ws_fpos = nullptr;    // [S][F]

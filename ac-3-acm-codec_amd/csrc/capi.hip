@@ -990,7 +990,7 @@ int ac3mi_fill_workspaces(ac3mi_ctx *ctx, int byte)
 // split front end's descriptors, generator positions, coupling coordinates and row sets (ws_split)
 static size_t coef_bytes(size_t nfr, int n_in) { return nfr * 6 * n_in * 256 * sizeof(float); }
 static size_t zs_off(size_t nfr, int nfchans) { return nfr * 6 * nfchans + 4; }
-static size_t split_bytes(size_t nfr) { return nfr * (6 * 80 + 16 + 6 * 90 * 4 + 6 * 7 * 512) + 256; }
+static size_t split_bytes(size_t nfr) { return nfr * (6 * BLKDESC_BYTES + 16 + 6 * 90 * 4 + 6 * 7 * 512) + 256; }
 
 static int grow_front_ws(ac3mi_ctx *ctx, const DecChoice &fe, size_t nfr)
 {
@@ -1052,9 +1052,9 @@ static DecodeLaunch decode_launch(const ac3mi_ctx *ctx, const DecChoice &fe, con
     if (fe.split) {
         uint8_t *p = ctx->ws_split.at<uint8_t>();
         D.ws_desc = p;
-        D.ws_fpos = (uint32_t *)(p + nfr * 6 * 80);
-        D.ws_cplco = (float *)(p + nfr * (6 * 80 + 16));
-        D.ws_rows = p + nfr * (6 * 80 + 16 + 6 * 90 * 4);
+        D.ws_fpos = (uint32_t *)(p + nfr * 6 * BLKDESC_BYTES);
+        D.ws_cplco = (float *)(p + nfr * (6 * BLKDESC_BYTES + 16));
+        D.ws_rows = p + nfr * (6 * BLKDESC_BYTES + 16 + 6 * 90 * 4);
     }
     return D;
 }
@@ -1854,8 +1854,8 @@ int ac3mi_transcode_batch(ac3mi_ctx *ctx, const ac3mi_decode_desc *dec, const ac
     E.n_streams = n_streams;
     E.frames_per_stream = frames_per_stream;
     if (fe.split) {                                     // block 0's descriptor of every frame carries the source's SNR offsets
-        E.search_hint = reinterpret_cast<const uint32_t *>(D.ws_desc) + 72 / 4;      // BlkDesc::src_snr (decode_common.h asserts the offset)
-        E.search_hint_stride = 6 * 80 / 4;                                           // six 80-byte descriptors per frame
+        E.search_hint = reinterpret_cast<const uint32_t *>(D.ws_desc) + BLKDESC_SRC_SNR / 4;      // BlkDesc::src_snr
+        E.search_hint_stride = 6 * BLKDESC_BYTES / 4;                                            // six descriptors per frame
     }
     HIPCHK(ctx, launch_encode(ctx->tab, E, ctx->stream));
     return AC3MI_OK;

@@ -14,6 +14,7 @@
 // the decoder is to treat the frame as refused (ac3mi_set_decode_crc 2), bit 7 not summed (no frame, or not this batch's).
 #include "ac3mi_internal.h"
 #include "sync_rule.h"
+#include "wave_ops.h"
 
 namespace ac3mi {
 
@@ -110,9 +111,7 @@ __global__ __launch_bounds__(64 * CRC_WAVES) void crc_kernel(const CrcParams P)
             }
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
 
     // ---- per-lane chunk sums; bytes in front of a region count as 0 ----
     const int fs = fbytes >> 1, end1 = 2 * ((fs >> 1) + (fs >> 3)), end2 = 2 * fs;

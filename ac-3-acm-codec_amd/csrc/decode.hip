@@ -11,8 +11,8 @@
 //  * side information is serial: parsed by all lanes on wave-uniform values through a 64-bit
 //    scalar bit window (struct Rd)
 //  * exponents: one lane per 7-bit group, DPP prefix sum of the deltas
-//  * bit allocation: the whole wavefront per channel (bit_allocate_wave): one lane per band for
-//    the PSD integration, lowcomp as an automaton evaluated by scans, leaks as prefix minima
+//  * bit allocation: the whole wavefront per channel (ba_wide_psd + bit_allocate_finish): the band PSDs
+//    of two channels per sweep, lowcomp as an automaton evaluated by scans, leaks as prefix minima
 //  * mantissas: one sweep, 64 consecutive coefficients of a channel segment per step; two packed
 //    DPP scans give grouped-code ranks, bit offsets and dither draw indices (the LFSR is
 //    GF(2)-linear, so the k-th draw is a table lookup: lfsr_seq[(lfsr_idx[state] + k) mod 65535]);
@@ -67,17 +67,12 @@ __global__ __launch_bounds__(384, MANT_LB) void mant_kernel(const MantParams P)
     extern __shared__ uint32_t frw[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int blk = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // consecutive frames on one XCD (its L2 then serves each frame's bytes and rows to the six wavefronts once):
-    // the bijective remap of cdna_hip_programming.md T1
-    unsigned fidx;
-    {
-        const unsigned n = gridDim.x, q = n >> 3, r = n & 7u, x = blockIdx.x & 7u, i = blockIdx.x >> 3;
-        fidx = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
+    // consecutive frames on one XCD: its L2 then serves each frame's bytes and rows to the six wavefronts once
+    const unsigned fidx = xcd_remap(blockIdx.x, gridDim.x);
     const size_t unit = (size_t)fidx * 6 + blk;
     // the block's descriptor: five 16-byte loads of one address, in flight while the frame is staged
     const uint4 *dq = reinterpret_cast<const uint4 *>(P.desc + unit);
-    const uint4 w0v = dq[0], w1v = dq[1], w2v = dq[2], w3v = dq[3], w4v = dq[4];
+    const BlkWords D{{dq[0], dq[1], dq[2], dq[3], dq[4]}};
     const uint32_t fposv = P.frame_pos[fidx];
     const int nw = (P.frame_bytes + 3) >> 2;
     // the frame's words and the thread's two dequantiser words are all requested before the first is waited for (as
@@ -87,24 +82,17 @@ __global__ __launch_bounds__(384, MANT_LB) void mant_kernel(const MantParams P)
     float q1 = 0.f;
     if (tid < 760 - 384) q1 = P.tab->qtab[384 + tid];
     float *cblk = P.coef + unit * P.n_in * 256;
-    const uint32_t flags = rfl(w0v.z);
-    const bool failed = (flags & 1u) != 0u;
     MantBlk B;
     B.nf = P.nfchans; B.lfeon = P.lfeon; B.acmod = P.acmod; B.in_lfe = P.lfeon ? 1 : 0;
-    B.chincpl = (int)((flags >> 8) & 31u); B.dithmask = (int)((flags >> 16) & 31u); B.rematflg = (int)((flags >> 24) & 15u);
-    const uint64_t rve = (uint64_t)rfl(w2v.x) | ((uint64_t)rfl(w2v.y) << 32), rvb = (uint64_t)rfl(w2v.z) | ((uint64_t)rfl(w2v.w) << 32);
-    const uint8_t *rowbase = P.rows + (size_t)fidx * 6 * ROWSET;
-    auto fetch = [&](int slot) -> uint2 {
-        const uint8_t *er = rowbase + (size_t)((rve >> (8 * slot)) & 7u) * ROWSET + slot * 512;
-        const uint8_t *br = rowbase + (size_t)((rvb >> (8 * slot)) & 7u) * ROWSET + slot * 512 + 256;
-        if (slot == 5) return lane < 7 ? make_uint2(br[lane], er[lane]) : make_uint2(1u, 0u);
-        return make_uint2(reinterpret_cast<const uint32_t *>(br)[lane], reinterpret_cast<const uint32_t *>(er)[lane]);
-    };
+    const bool failed = D.head(B);
+    const uint64_t rve = D.rv_exp(), rvb = D.rv_bap();
+    const uint8_t *const rowbase = P.rows + (size_t)fidx * 6 * ROWSET;
+    const RowFetch fetch{rowbase, rve, rvb, lane};
     {
         stage_frame_store<384>(frw, fw, P.frame_bytes, tid);
         // the slot's bytes behind a frame shorter than frame_bytes are not the frame's.  The parse kernel leaves such a frame's own
         // size in every block's descriptor (0: full size - every frame of a batch of one frame size); each thread clears what it staged
-        if (const int own = (int)(rfl(w1v.w) >> 16)) trim_staged_frame(frw, own, nw, tid, 384);
+        if (const int own = D.own_bytes()) trim_staged_frame(frw, own, nw, tid, 384);
         if (tid < M2_NDESC) L.dsc[tid] = mant_desc2((uint32_t)tid);
         L.qtab[tid] = q0;
         if (tid < 760 - 384) L.qtab[384 + tid] = q1;
@@ -119,24 +107,18 @@ __global__ __launch_bounds__(384, MANT_LB) void mant_kernel(const MantParams P)
             *reinterpret_cast<float4 *>(cblk + (size_t)c * 256 + 4 * lane) = make_float4(0.f, 0.f, 0.f, 0.f);
         return;
     }
-    {
-        const uint32_t a = rfl(w1v.x), b = rfl(w1v.y), c = rfl(w1v.z), d = rfl(w1v.w);
-        B.cplstrtmant = (int)(c >> 16); B.cplendmant = (int)(d & 0xffffu);
-        B.ends = (uint64_t)((a & 0xffu) | ((a >> 8) & 0xff00u) | ((b & 0xffu) << 16) | ((b << 8) & 0xff000000u)) | ((uint64_t)(c & 0xffu) << 32);
-    }
-    // the gains, lane k = slot k's (lane 5: the LFE's): one v_readlane per segment in mant_block2
-    B.gainv = lane == 0 ? __uint_as_float(w3v.x) : lane == 1 ? __uint_as_float(w3v.y) : lane == 2 ? __uint_as_float(w3v.z)
-            : lane == 3 ? __uint_as_float(w3v.w) : lane == 4 ? __uint_as_float(w4v.x) : __uint_as_float(w4v.y);
+    D.ranges(B);
+    B.gainv = D.gainv(lane);
     if (B.chincpl && lane < 18) {                               // sub-band -> band (parse.c:448-456)
-        const uint32_t below = rfl(w0v.w) & ((1u << lane) - 1u);
+        const uint32_t below = D.cplbndstrc() & ((1u << lane) - 1u);
         L.cplbnd[blk][lane] = (uint8_t)(lane - __popc(below));
     }
     const uint32_t fpos = rfl(fposv);
     const bool lfsr_live = fpos != 0xffffffffu;
-    const uint32_t i0 = lfsr_live ? (fpos + rfl(w0v.y)) % 65535u : 0u;            // the generator's position before the block's first draw
+    const uint32_t i0 = lfsr_live ? (fpos + D.draw_off()) % 65535u : 0u;            // the generator's position before the block's first draw
     const float *cc = P.cplco + unit * 90;
     mant_block2<256, true>(B, fetch, first, [&](int c, int bnd) { return cc[c * 18 + bnd]; }, L.cplbnd[blk], L.dsc, L.ring[blk], frw, (uint32_t)nw + 2u,
-                L.qtab, reinterpret_cast<const int16_t *>(P.lfsr_seq) + 1 + i0, lfsr_live, cblk, rfl(w0v.x), lane);
+                L.qtab, reinterpret_cast<const int16_t *>(P.lfsr_seq) + 1 + i0, lfsr_live, cblk, D.bitpos(), lane);
 }
 
 }  // namespace ac3mi

@@ -11,7 +11,7 @@
 namespace ac3mi {
 
 constexpr int ROW = 260;                  // exp/bap row pitch (bytes): 65 dwords, conflict-free across rows
-// The LFE row holds 7 exponents (bit_allocate_wave's lowcomp stage looks at bins up to 64 of any row): kept short and
+// The LFE row holds 7 exponents (ba_from_psd's lowcomp stage looks at bins up to 64 of any row): kept short and
 // last; with the dequantiser table read through L1 the wavefront's LDS is 6.5 KB = 24 wavefronts per CU, what the
 // 80 VGPRs of __launch_bounds__(64, 6) allow (the kernel is latency-bound, occupancy pays).
 constexpr int LFE_ROW = 68;
@@ -61,10 +61,6 @@ __device__ __forceinline__ uint32_t peek(const FrameBits fr, uint32_t pos, int n
     w = w < fr.last ? w : fr.last;
     const uint64_t v = ((uint64_t)fr.w[w] << 32) | fr.w[w + 1];
     return (uint32_t)((v << (pos & 31)) >> (64 - n));
-}
-__device__ __forceinline__ int32_t speek(const FrameBits fr, uint32_t pos, int n)
-{
-    return ((int32_t)(peek(fr, pos, n) << (32 - n))) >> (32 - n);
 }
 
 // Stage the frame_bytes bytes at src (dword-aligned; the slot is a whole number of dwords): byte-swapped dwords, the last
@@ -128,6 +124,9 @@ __device__ __forceinline__ void stage_frame(uint32_t *frw, const uint8_t *src, i
 // it up to nw.  Only frames whose mantissas run on behind their own end read there.
 __device__ __forceinline__ void trim_staged_frame(uint32_t *frw, int fbytes, int nw, int t, int nt)
 {
+    // (said here, so that it does not hang on what the compiler can see of every caller's argument: with one caller's hidden
+    // behind a function, each kernel of that translation unit came out four instructions longer)
+    __builtin_assume(fbytes >= 0);
     const int w = fbytes >> 2, keep = fbytes & 3;
     int i = t;
     if (i < w) i += (w - t + nt - 1) / nt * nt;
@@ -204,8 +203,6 @@ __device__ __forceinline__ void skip_bsi_tail(R &rd, bool dual_mono)
 
 __device__ __forceinline__ float sf_of(int e) { return __int_as_float((127 - 15 - e) << 23); }   // 2^-(15+e)
 
-__device__ __forceinline__ int wave_incl_scan(int v, int) { return (int)wave_incl_scan_u32((uint32_t)v); }
-
 // liba52 drops the surround channels of such a frame from transform and mix instead of mixing them at level 0
 // (L52/downmix.c:494-583: the slev == 0 cases of MONO, STEREO and 3F outputs)
 __device__ __forceinline__ int surround_level_is_zero(int acmod, int output, float slev)
@@ -253,7 +250,7 @@ struct St {
     uint32_t lfsr;
 };
 
-struct BlkDesc;
+struct BlkDesc;                 // mant2.h
 struct DecodeParams {
     // split front end (decode_kernel<4 / 5> -> mant_kernel): block descriptors, row sets, coupling coordinates, and the
     // dither generator's position at the start of every frame
@@ -344,7 +341,7 @@ __device__ int read_exponents(const FrameBits fr, uint32_t pos, int strategy, in
             d2 = code % 5 - 2;
             if (!ok) d0 = d1 = d2 = 0;
         }
-        const int incl = wave_incl_scan(d0 + d1 + d2, lane);
+        const int incl = (int)wave_incl_scan_u32((uint32_t)(d0 + d1 + d2));
         const int e0 = carry + incl - (d1 + d2), e1 = e0 + d1, e2 = e1 + d2;
         if (g < ngrps) {
             if (!ok || e0 < 0 || e0 > 24 || e1 < 0 || e1 > 24 || e2 < 0 || e2 > 24) bad = 1;
@@ -361,7 +358,9 @@ __device__ int read_exponents(const FrameBits fr, uint32_t pos, int strategy, in
 }
 
 // ---------------------------------------------------------------------------
-// bit allocation, one lane = one channel: L52/bit_allocate.c:124-265
+// bit allocation of one channel with the whole wavefront (one lane per band, then per bin): L52/bit_allocate.c:124-265.
+// The band PSDs come from one of two sweeps (bit_allocate_wave: one row, a lane per band; ba_wide_psd + bit_allocate_finish:
+// the wide bands of two rows at once); everything behind them is ba_from_psd, stated once.
 
 struct BaCtx {
     int fdecay, fgain, sdecay, sgain, dbknee, floor, snroffset, halfrate, fast, slow;
@@ -369,12 +368,27 @@ struct BaCtx {
     const int8_t *deltba;       // may be null
 };
 
-__device__ __forceinline__ void ba_leak(BaCtx &c, int psd)
+// The allocation parameters of one slot (parse.c:774-798): bai = the frame's 11-bit sdcycod | fdcycod | sgaincod | dbpbcod |
+// floorcod, mybai = the slot's fsnroffst << 3 | fgaincod; deltba: the slot's delta row, or null where the frame sends none;
+// fleak / sleak: the leak seeds, cplfleak << 8 / cplsleak << 8 for the coupling channel and 0 for every other slot.
+__device__ __forceinline__ BaCtx ba_ctx(int bai, int mybai, int csnroffst, int halfrate, const uint16_t *hth, const int8_t *deltba,
+                                        int fleak, int sleak)
 {
-    c.fast += c.fdecay;
-    if (c.fast > psd + c.fgain) c.fast = psd + c.fgain;
-    c.slow += c.sdecay;
-    if (c.slow > psd + c.sgain) c.slow = psd + c.sgain;
+    BaCtx c;
+    c.halfrate = halfrate;
+    c.fdecay = (63 + 20 * ((bai >> 7) & 3)) >> halfrate;
+    c.fgain = 128 + 128 * (mybai & 7);
+    c.sdecay = (15 + 2 * (bai >> 9)) >> halfrate;
+    c.sgain = k_slowgain[(bai >> 5) & 3];
+    c.dbknee = k_dbpb[(bai >> 3) & 3];
+    c.hth = hth;
+    c.deltba = deltba;
+    const int fl = k_floors[bai & 7];
+    c.snroffset = 960 - 64 * csnroffst - 4 * (mybai >> 3) + fl;
+    c.floor = fl >> 5;
+    c.fast = fleak;
+    c.slow = sleak;
+    return c;
 }
 
 __device__ __forceinline__ int ba_mask(const BaCtx &c, int mask, int psd, int band)
@@ -392,108 +406,17 @@ __device__ __forceinline__ int8_t ba_width(const int8_t *width, int a)
     return a <= -64 ? 16 : a >= 0 ? 0 : width[a + 63];
 }
 
-__device__ void bit_allocate_lane(const DecLDS &L, BaCtx c, int bndstart, int start, int end, const uint8_t *e,
-                                  int8_t *bap)
-{
-    int band = bndstart, bin = start, psd = 0, mask;
-    if (start == 0) {
-        int lowcomp = 0;
-        const int last = end - 1;
-        do {
-            if (band < last) {
-                if (e[band + 1] == e[band] - 2) lowcomp = 384;
-                else if (lowcomp && e[band + 1] > e[band]) lowcomp -= 64;
-            }
-            psd = 128 * e[band];
-            mask = ba_mask(c, psd + c.fgain + lowcomp, psd, band);
-            bap[band] = ba_width(L.width, mask + 4 * e[band]);
-            band++;
-        } while (band < 3 || (band < 7 && e[band] > e[band - 1]));
-        c.fast = psd + c.fgain;
-        c.slow = psd + c.sgain;
-        while (band < 7) {
-            if (band < last) {
-                if (e[band + 1] == e[band] - 2) lowcomp = 384;
-                else if (lowcomp && e[band + 1] > e[band]) lowcomp -= 64;
-            }
-            psd = 128 * e[band];
-            ba_leak(c, psd);
-            mask = (c.fast + lowcomp < c.slow) ? c.fast + lowcomp : c.slow;
-            mask = ba_mask(c, mask, psd, band);
-            bap[band] = ba_width(L.width, mask + 4 * e[band]);
-            band++;
-        }
-        if (end == 7) return;
-        do {
-            if (e[band + 1] == e[band] - 2) lowcomp = 320;
-            else if (lowcomp && e[band + 1] > e[band]) lowcomp -= 64;
-            psd = 128 * e[band];
-            ba_leak(c, psd);
-            mask = (c.fast + lowcomp < c.slow) ? c.fast + lowcomp : c.slow;
-            mask = ba_mask(c, mask, psd, band);
-            bap[band] = ba_width(L.width, mask + 4 * e[band]);
-            band++;
-        } while (band < 20);
-        while (lowcomp > 128) {
-            lowcomp -= 128;
-            psd = 128 * e[band];
-            ba_leak(c, psd);
-            mask = (c.fast + lowcomp < c.slow) ? c.fast + lowcomp : c.slow;
-            mask = ba_mask(c, mask, psd, band);
-            bap[band] = ba_width(L.width, mask + 4 * e[band]);
-            band++;
-        }
-        bin = band;
-    }
-    do {
-        const int first = bin;
-        const int stop = L.band_end[band - 20] < end ? L.band_end[band - 20] : end;
-        psd = 128 * e[bin++];
-        while (bin < stop) {
-            const int next = 128 * e[bin++], d = next - psd;
-            const int q = d >> 9;
-            if (q <= -2) psd = next;
-            else if (q == -1) { int a = (-d) >> 1; psd = next + L.la_neg[a > 255 ? 255 : a]; }
-            else if (q == 0) psd += L.la_neg[d >> 1];
-        }
-        ba_leak(c, psd);
-        mask = ba_mask(c, c.fast < c.slow ? c.fast : c.slow, psd, band);
-        band++;
-        for (bin = first; bin < stop; bin++) bap[bin] = ba_width(L.width, mask + 4 * e[bin]);
-    } while (bin < end);
-}
-
-// The same allocation for one channel with the whole wavefront (one lane per band, then per bin):
-//  * band PSDs: each of the <= 50 bands integrated by its own lane (<= 24 dependent log-adds)
+// Everything behind the band PSDs.  psd: band b's in lane b; live: the band has a bin in [start, end).
 //  * lowcomp (bands 0..21 of a channel that starts at bin 0) is a reset-or-decrement automaton:
 //    value = max(0, R(last reset) - 64 * decrements since); bands 20/21 take 128 off while > 128
 //  * the fast / slow leaks are prefix minima of psd + gain - band * decay seeded at the last band
 //    of the first loop (bit_allocate.c:150-166), or at the coupling leak values
 template <class LDS>
-__device__ void bit_allocate_wave(const LDS &L, int16_t *bmask, const BaCtx &c, int bndstart, int start, int end, const uint8_t *e,
-                                  int8_t *bap, int lane)
+__device__ __forceinline__ void ba_from_psd(const LDS &L, int16_t *bmask, const BaCtx &c, int bndstart, int start, int end, const uint8_t *e,
+                                            int8_t *bap, int psd, bool live, int lane)
 {
     constexpr int INF = 0x3fffffff, NEG = -0x3fffffff;
     const int b = lane;
-    // S1: band PSD
-    int lo = b < 21 ? b : (int)L.band_end[b < 50 ? b - 21 : 0];
-    int hi = b < 20 ? b + 1 : (int)L.band_end[b < 50 ? b - 20 : 0];
-    lo = lo > start ? lo : start;
-    hi = hi < end ? hi : end;
-    const int w = b < 50 ? hi - lo : 0;
-    const bool live = w > 0;
-    lo = live ? lo : start;
-    int psd = 128 * e[lo];
-    const int wmax = (int)wave_last((uint32_t)wave_incl_scan_max(w));
-    for (int j = 1; j < wmax; j++) {
-        const int next = 128 * e[j < w ? lo + j : lo];
-        const int d = next - psd, q = d >> 9;
-        int idx = q == -1 ? (-d) >> 1 : d >> 1;
-        idx = idx < 0 ? 0 : idx > 255 ? 255 : idx;
-        const int la = L.la_neg[idx];
-        const int nv = q <= -2 ? next : q == -1 ? next + la : q == 0 ? psd + la : psd;
-        psd = j < w ? nv : psd;
-    }
     // S2: lowcomp and the extent of the first loop
     int lc = 0, bA = 0;
     if (start == 0) {
@@ -525,9 +448,7 @@ __device__ void bit_allocate_wave(const LDS &L, int16_t *bmask, const BaCtx &c, 
     // S4: mask
     int mask = (start == 0 && b < bA) ? psd + c.fgain + lc : (fast + lc < slow ? fast + lc : slow);
     if (live) bmask[b] = (int16_t)ba_mask(c, mask, psd, b);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     // S5: bins
     const int shift = bndstart - (int)L.band_of_bin[start];
 #pragma unroll
@@ -535,6 +456,41 @@ __device__ void bit_allocate_wave(const LDS &L, int16_t *bmask, const BaCtx &c, 
         const int bin = 64 * k + lane;
         if (bin >= start && bin < end) bap[bin] = ba_width(L.width, (int)bmask[L.band_of_bin[bin] + shift] + 4 * e[bin]);
     }
+}
+
+// band `lane`'s bins of a channel that covers [start, end): its first bin (`start` for a band without one) and their number
+template <class LDS>
+__device__ __forceinline__ int ba_band_bins(const LDS &L, int start, int end, int lane, int &lo)
+{
+    const int b = lane;
+    lo = b < 21 ? b : (int)L.band_end[b < 50 ? b - 21 : 0];
+    int hi = b < 20 ? b + 1 : (int)L.band_end[b < 50 ? b - 20 : 0];
+    lo = lo > start ? lo : start;
+    hi = hi < end ? hi : end;
+    const int w = b < 50 ? hi - lo : 0;
+    lo = w > 0 ? lo : start;
+    return w;
+}
+
+// One row: each of the <= 50 bands integrated by its own lane (<= 24 dependent log-adds), then ba_from_psd
+template <class LDS>
+__device__ void bit_allocate_wave(const LDS &L, int16_t *bmask, const BaCtx &c, int bndstart, int start, int end, const uint8_t *e,
+                                  int8_t *bap, int lane)
+{
+    int lo;
+    const int w = ba_band_bins(L, start, end, lane, lo);
+    int psd = 128 * e[lo];
+    const int wmax = (int)wave_last((uint32_t)wave_incl_scan_max(w));
+    for (int j = 1; j < wmax; j++) {
+        const int next = 128 * e[j < w ? lo + j : lo];
+        const int d = next - psd, q = d >> 9;
+        int idx = q == -1 ? (-d) >> 1 : d >> 1;
+        idx = idx < 0 ? 0 : idx > 255 ? 255 : idx;
+        const int la = L.la_neg[idx];
+        const int nv = q <= -2 ? next : q == -1 ? next + la : q == 0 ? psd + la : psd;
+        psd = j < w ? nv : psd;
+    }
+    ba_from_psd(L, bmask, c, bndstart, start, end, e, bap, psd, w > 0, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -605,63 +561,16 @@ __device__ __forceinline__ int ba_wide_psd(const LDS &L, int lo0, int hi0, const
     return psd - 2048;
 }
 
-// everything after the band PSDs for one row; `wide` = ba_wide_psd's result, this row's in the lanes of half `half`
+// One row of the two: `wide` = ba_wide_psd's result, this row's in the lanes of half `half`; bands below 28 are one bin wide
 template <class LDS>
 __device__ void bit_allocate_finish(const LDS &L, int16_t *bmask, const BaCtx &c, int bndstart, int start, int end, const uint8_t *e,
                                     int8_t *bap, int wide, int half, int lane)
 {
-    constexpr int INF = 0x3fffffff, NEG = -0x3fffffff;
     const int b = lane;
-    int lo = b < 21 ? b : (int)L.band_end[b < 50 ? b - 21 : 0];
-    int hi = b < 20 ? b + 1 : (int)L.band_end[b < 50 ? b - 20 : 0];
-    lo = lo > start ? lo : start;
-    hi = hi < end ? hi : end;
-    const int w = b < 50 ? hi - lo : 0;
-    const bool live = w > 0;
-    lo = live ? lo : start;
+    int lo;
+    const int w = ba_band_bins(L, start, end, lane, lo);
     const int pw = __shfl(wide, (b >= 28 ? b - 28 : 0) + 32 * half, 64);
-    const int psd = b >= 28 ? pw : 128 * e[lo];
-    // S2: lowcomp and the extent of the first loop
-    int lc = 0, bA = 0;
-    if (start == 0) {
-        const int eb = e[b < 253 ? b : 0], eb1 = e[b < 252 ? b + 1 : 0], ebm = e[b > 0 && b < 254 ? b - 1 : 0];
-        const bool upd = b < 20 && (b >= 7 || b < end - 1);
-        const bool reset = upd && eb1 == eb - 2;
-        const int dec = upd && !reset && eb1 > eb ? 1 : 0;
-        const int D = (int)wave_incl_scan_u32((uint32_t)dec);
-        const int rix = wave_incl_scan_max(reset ? b : NEG);
-        const int Dr = __shfl(D, rix < 0 ? 0 : rix, 64);
-        if (rix >= 0) { lc = (rix < 7 ? 384 : 320) - 64 * (D - Dr); lc = lc < 0 ? 0 : lc; }
-        const int l19 = __builtin_amdgcn_readlane(lc, 19);
-        lc = b == 20 ? (l19 > 128 ? l19 - 128 : 0) : b == 21 ? (l19 > 256 ? l19 - 256 : 0) : b >= 22 ? 0 : lc;
-        const unsigned long long stopm = __ballot(b >= 3 && b < 7 && !(eb > ebm));
-        bA = stopm ? __builtin_ctzll(stopm) : 7;
-    }
-    // S3: leaks
-    const int seed = start == 0 ? bA - 1 : bndstart;
-    const bool in = live && b >= seed;
-    int fast = in ? psd + c.fgain - b * c.fdecay : INF, slow = in ? psd + c.sgain - b * c.sdecay : INF;
-    wave_incl_scan_min2(fast, slow);                    // (two scans interleaved, wave_ops.h)
-    fast += b * c.fdecay;
-    slow += b * c.sdecay;
-    if (start != 0) {
-        const int ff = c.fast + (b - bndstart + 1) * c.fdecay, sl = c.slow + (b - bndstart + 1) * c.sdecay;
-        fast = ff < fast ? ff : fast;
-        slow = sl < slow ? sl : slow;
-    }
-    // S4: mask
-    int mask = (start == 0 && b < bA) ? psd + c.fgain + lc : (fast + lc < slow ? fast + lc : slow);
-    if (live) bmask[b] = (int16_t)ba_mask(c, mask, psd, b);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // S5: bins
-    const int shift = bndstart - (int)L.band_of_bin[start];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int bin = 64 * k + lane;
-        if (bin >= start && bin < end) bap[bin] = ba_width(L.width, (int)bmask[L.band_of_bin[bin] + shift] + 4 * e[bin]);
-    }
+    ba_from_psd(L, bmask, c, bndstart, start, end, e, bap, b >= 28 ? pw : 128 * e[lo], w > 0, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -672,14 +581,6 @@ __device__ __forceinline__ int16_t dither_at(const uint16_t *lfsr_seq, uint32_t 
     uint32_t i = idx0 + (uint32_t)k + 1;
     i %= 65535u;
     const int16_t ns = (int16_t)lfsr_seq[i];
-    return (int16_t)((3 * ns) >> 2);
-}
-__device__ __forceinline__ int16_t dither_value(const DecodeParams &P, uint32_t idx0, int k)
-{
-    // k-th draw (k = 0 first) = state after k+1 steps
-    uint32_t i = idx0 + (uint32_t)k + 1;
-    i %= 65535u;
-    const int16_t ns = (int16_t)P.lfsr_seq[i];
     return (int16_t)((3 * ns) >> 2);
 }
 
@@ -885,9 +786,7 @@ __device__ __forceinline__ void mant_block(const MantBlk &B, ERow erow_of, BRow 
         sb.r11 += T.n11;
         sb.draw += T.draws;
         if (COUNT) continue;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         if (slot < 6) {
             float out[4];
             int cd = R.cd;
@@ -968,9 +867,7 @@ __device__ __forceinline__ void mant_block(const MantBlk &B, ERow erow_of, BRow 
         }
     }
     if (!COUNT && remat_late) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         volatile float *p0 = cblk + (size_t)B.in_lfe * 256, *p1 = p0 + 256;
         for (int bin = 13 + lane; bin < remat_end; bin += 64) {
             const int band = bin < 25 ? 0 : bin < 37 ? 1 : bin < 61 ? 2 : 3;
@@ -984,26 +881,7 @@ __device__ __forceinline__ void mant_block(const MantBlk &B, ERow erow_of, BRow 
 }
 
 // ---------------------------------------------------------------------------
-// The split front end: decode_kernel<4 / 5> parses (side information, exponents, bit allocation) and leaves, per audio
-// block, this descriptor plus the exponent / bap rows that changed; mant_kernel (one wavefront per block) unpacks and
-// dequantises from them.  What a block needs of the blocks before it is all here: where its mantissas start, how many
-// dither draws came before, which rows are current.
-
-struct alignas(16) BlkDesc {
-    uint32_t bitpos;            // first mantissa bit of the block
-    uint32_t draw_off;          // dither draws of the frame before this block
-    uint32_t flags;             // bit 0: the block failed (zero planes); 8-12 chincpl; 16-20 dither flags; 24-27 rematflg
-    uint32_t cplbndstrc;
-    uint16_t endmant[5], cplstrt, cplend;
-    uint16_t own_bytes;         // the frame's own size where it is below frame_bytes, else 0 (every block of a frame, failed ones too)
-    uint8_t rv_exp[8], rv_bap[8];   // block of THIS frame whose row holds the slot's current exponents / bap
-    float gain[5], lfe_gain;        // parse.c:810-811 (dynamic range folded in); LFE: 0 when it is not an output
-    uint32_t src_snr;           // 16 csnroffst + fsnroffst (channel 0) the frame was coded with, as of this block
-    uint32_t pad1;
-};
-static_assert(sizeof(BlkDesc) == 80 && offsetof(BlkDesc, src_snr) == 72 && offsetof(BlkDesc, own_bytes) == 30, "BlkDesc layout");
-
-constexpr int ROWSET = 7 * 512;         // bytes of one (frame, block) row set: 7 slots x (256 exponents + 256 row bytes)
+// The parse half of the split front end (decode_kernel<4 / 5>; the descriptor it leaves per audio block: BlkDesc, mant2.h)
 
 // totals of one slot's row over [start, end): a = plain bits | 3-level members << 13 | 5-level members << 22,
 // b = 11-level members | zero-bit bins << 9.  Wave-uniform.

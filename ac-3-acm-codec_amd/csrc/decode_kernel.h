@@ -21,7 +21,7 @@ namespace ac3mi {
 // MODE 4 (one wavefront per stream) / MODE 5 + lfsr_prefix_kernel (one per frame): the parse half of the split front
 // end - side information, exponents, bit allocation; the mantissas of a block are only COUNTED, from per-row totals, and
 // mant_kernel (one wavefront per audio block, a workgroup per frame) unpacks them from the block descriptors and rows
-// this kernel leaves in the workspace (BlkDesc, decode_common.h).
+// this kernel leaves in the workspace (BlkDesc, mant2.h).
 #ifndef DEC_LBP
 #define DEC_LBP 5
 #endif
@@ -80,9 +80,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
         for (int i = lane; i < (2 * ROWS + 6 * 52 + 90 * 4) / 4; i += 64) z[i] = 0u;
     }
 
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     int ba_lo0, ba_hi0;                 // the lane's wide band (ba_wide_psd)
     ba_lane_band(L, lane, ba_lo0, ba_hi0);
 
@@ -147,9 +145,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
 
         Rd rd{FB, 0, 0, 0};
         // ---- a52_syncinfo (the header rule: sync_rule.h through frame_own_bytes) + a52_frame (parse.c:131-205) ----
@@ -168,9 +164,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                 if (own < P.frame_bytes) {                         // (wave-uniform) the slot's bytes behind a shorter frame are not the frame's
                     trim_staged_frame(frw, own, (P.frame_bytes + 3) >> 2, lane, 64);
                     short_bytes = own;
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_sync();
                 }
             }
         }
@@ -382,9 +376,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                     }
                     if (err) break;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_sync();
 
                 // ---- bit allocation: parse.c:774-798 ----
                 if (redo) {
@@ -417,29 +409,15 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                                 const int slot = h ? sB : sA, start = h ? stB : stA, end = h ? enB : enA;
                                 const int mybai = st.cbai(slot);
                                 const int mydeltbae = slot == 5 ? 2 : st.deltbae(slot == 6 ? 5 : slot);
-                                BaCtx c;
-                                const int bai = st.bai();
-                                c.halfrate = st.halfrate();
-                                c.fdecay = (63 + 20 * ((bai >> 7) & 3)) >> c.halfrate;
-                                c.fgain = 128 + 128 * (mybai & 7);
-                                c.sdecay = (15 + 2 * (bai >> 9)) >> c.halfrate;
-                                c.sgain = k_slowgain[(bai >> 5) & 3];
-                                c.dbknee = k_dbpb[(bai >> 3) & 3];
-                                c.hth = L.hth;
-                                c.deltba = (mydeltbae == 2) ? nullptr : L.deltba[slot == 6 ? 5 : slot];
-                                const int fl = k_floors[bai & 7];
-                                c.snroffset = 960 - 64 * st.csnroffst() - 4 * (mybai >> 3) + fl;
-                                c.floor = fl >> 5;
-                                c.fast = slot == 6 ? st.cplfleak() << 8 : 0;
-                                c.slow = slot == 6 ? st.cplsleak() << 8 : 0;
+                                const BaCtx c = ba_ctx(st.bai(), mybai, st.csnroffst(), st.halfrate(), L.hth,
+                                                       mydeltbae == 2 ? nullptr : L.deltba[slot == 6 ? 5 : slot],
+                                                       slot == 6 ? st.cplfleak() << 8 : 0, slot == 6 ? st.cplsleak() << 8 : 0);
                                 bit_allocate_finish(L, L.bmask, c, slot == 6 ? st.cplstrtbnd() : 0, start, end, L.exp + row_off(slot), L.bap + row_off(slot), wide, h, lane);
                             }
                         }
 #undef AC3MI_SLOT_END
                     }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_sync();
                 }
                 if (rd.get(1)) {                                            // skip field
                     const int n = rd.get(9);
@@ -551,21 +529,23 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                         cc[lane] = (&L.cplco[0][0])[lane];
                         if (lane < 26) cc[64 + lane] = (&L.cplco[0][0])[64 + lane];
                     }
-                    // the descriptor, straight from the lanes (BlkDesc's layout)
+                    // the descriptor, straight from the lanes, one lane per field: lanes 0-3 the first four dwords, 0-7 the eight
+                    // halfwords from endmant on and the row indices, 0-6 the seven dwords from gain on (BlkDesc, mant2.h,
+                    // asserts that the members lie so)
                     {
                         uint8_t *dp = reinterpret_cast<uint8_t *>(P.desc + (fidx * 6 + blk));
-                        const uint32_t fl = ((uint32_t)st.chincpl << 8) | ((uint32_t)dithmask << 16) | ((uint32_t)st.rematflg() << 24);
+                        const uint32_t fl = ((uint32_t)st.chincpl << BLK_CHINCPL) | ((uint32_t)dithmask << BLK_DITH) | ((uint32_t)st.rematflg() << BLK_REMAT);
                         const uint32_t w0 = lane == 0 ? rd.pos() : lane == 1 ? frame_draws : lane == 2 ? fl : st.cplbndstrc;
                         if (lane < 4) reinterpret_cast<uint32_t *>(dp)[lane] = w0;
                         const int em = lane == 5 ? st.cplstrtmant : lane == 7 ? short_bytes : (int)((uint32_t)(st.ends >> (8 * (lane & 7))) & 0xffu);
-                        if (lane < 8) reinterpret_cast<uint16_t *>(dp + 16)[lane] = (uint16_t)em;
-                        if (lane < 8) { dp[32 + lane] = (uint8_t)rv_exp; dp[40 + lane] = (uint8_t)rv_bap; }
+                        if (lane < 8) reinterpret_cast<uint16_t *>(dp + offsetof(BlkDesc, endmant))[lane] = (uint16_t)em;
+                        if (lane < 8) { dp[offsetof(BlkDesc, rv_exp) + lane] = (uint8_t)rv_exp; dp[offsetof(BlkDesc, rv_bap) + lane] = (uint8_t)rv_bap; }
                         const float gl = lane == 0 ? gain[0] : lane == 1 ? gain[1] : lane == 2 ? gain[2] : lane == 3 ? gain[3] : lane == 4 ? gain[4]
                                        : (st.output & AC3MI_LFE) ? st.dynrng : 0.f;
-                        // spare word: the frame's own SNR offsets, 16 csnroffst + fsnroffst of channel 0 - a transcode's encoder starts
+                        // src_snr: the frame's own SNR offsets, 16 csnroffst + fsnroffst of channel 0 - a transcode's encoder starts
                         // costing its search there (a hint: which offsets are costed never changes a result, encode.hip)
                         const uint32_t w12 = lane < 6 ? __float_as_uint(gl) : (uint32_t)(16 * st.csnroffst() + (st.cbai(0) >> 3));
-                        if (lane < 7) reinterpret_cast<uint32_t *>(dp + 48)[lane] = w12;
+                        if (lane < 7) reinterpret_cast<uint32_t *>(dp + offsetof(BlkDesc, gain))[lane] = w12;
                     }
                     bd_ok = true;
                 }
@@ -578,7 +558,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
             if (err) { status |= 1u << blk; frame_dead = true; }
             if constexpr (PARSE) {
                 if ((err || !bd_ok) && lane == 0) {
-                    reinterpret_cast<uint32_t *>(P.desc + (fidx * 6 + blk))[2] = 1u;      // flags: the block failed
+                    P.desc[fidx * 6 + blk].flags = BLK_FAILED;
                     // (no descriptor was stored: the word a transcode's encoder reads as its search hint must not be a leftover
                     // of an earlier call - 0 = no hint, see enc_search_kernel)
                     P.desc[fidx * 6 + blk].src_snr = 0u;

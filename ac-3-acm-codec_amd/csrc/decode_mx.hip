@@ -76,14 +76,10 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
     const int tid = threadIdx.x, lane = tid & 63;
     const int blk = __builtin_amdgcn_readfirstlane(tid >> 6);
     MX_T0();
-    unsigned fidx;                                              // consecutive frames on one XCD, as mant_kernel
-    {
-        const unsigned n = gridDim.x, q = n >> 3, r = n & 7u, x = blockIdx.x & 7u, i = blockIdx.x >> 3;
-        fidx = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
+    const unsigned fidx = xcd_remap(blockIdx.x, gridDim.x);     // consecutive frames on one XCD, as mant_kernel
     const size_t unit = (size_t)fidx * 6 + blk;
     const uint4 *dq = reinterpret_cast<const uint4 *>(P.desc + unit);
-    const uint4 w0v = dq[0], w1v = dq[1], w2v = dq[2], w3v = dq[3], w4v = dq[4];
+    const BlkWords D{{dq[0], dq[1], dq[2], dq[3], dq[4]}};
     const uint32_t fposv = P.frame_pos[fidx];
     const int nw = (P.frame_bytes + 3) >> 2;
     // Set-up.  Every load is issued before the first wait on any of them (a copy loop, or a load and its LDS store inside one
@@ -101,23 +97,16 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
     const float2 twv = *twsrc;
     uint8_t *const region = L.wave[blk];
     float *const planes = reinterpret_cast<float *>(region);
-    const uint32_t flags = rfl(w0v.z);
-    const bool failed = (flags & 1u) != 0u;
     MantBlk B;
     B.nf = nfchans; B.lfeon = FX ? 1 : P.lfeon; B.acmod = FX ? 7 : P.acmod; B.in_lfe = FX ? 1 : P.lfeon ? 1 : 0;
-    B.chincpl = (int)((flags >> 8) & 31u); B.dithmask = (int)((flags >> 16) & 31u); B.rematflg = (int)((flags >> 24) & 15u);
+    const bool failed = D.head(B);
     // (a failed block's row indices read as 0: its request below then goes to the frame's own first row set and is never looked
     // at.  Behind a branch on `failed` the request would not cross the barrier - the waits for the words requested before it
     // have to assume the fewest loads in flight behind them - and it is the one load that should)
-    const uint64_t rve = failed ? 0ull : (uint64_t)rfl(w2v.x) | ((uint64_t)rfl(w2v.y) << 32);
-    const uint64_t rvb = failed ? 0ull : (uint64_t)rfl(w2v.z) | ((uint64_t)rfl(w2v.w) << 32);
-    const uint8_t *rowbase = P.rows + (size_t)fidx * 6 * ROWSET;
-    auto fetch = [&](int slot) -> uint2 {
-        const uint8_t *er = rowbase + (size_t)((rve >> (8 * slot)) & 7u) * ROWSET + slot * 512;
-        const uint8_t *br = rowbase + (size_t)((rvb >> (8 * slot)) & 7u) * ROWSET + slot * 512 + 256;
-        if (slot == 5) return lane < 7 ? make_uint2(br[lane], er[lane]) : make_uint2(1u, 0u);
-        return make_uint2(reinterpret_cast<const uint32_t *>(br)[lane], reinterpret_cast<const uint32_t *>(er)[lane]);
-    };
+    const uint64_t rve = failed ? 0ull : D.rv_exp();
+    const uint64_t rvb = failed ? 0ull : D.rv_bap();
+    const uint8_t *const rowbase = P.rows + (size_t)fidx * 6 * ROWSET;
+    const RowFetch fetch{rowbase, rve, rvb, lane};
     __builtin_assume(B.nf >= 1);                                // (every acmod has a channel: the first segment is slot 0's, and its request below sits behind no branch)
     const int slot0 = seg_slot(0, B.nf, B.chincpl, B.chincpl ? __builtin_ctz(B.chincpl) : 99);
     const uint2 first = fetch(slot0);
@@ -125,7 +114,7 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
         stage_frame_store<384>(frw, fw, P.frame_bytes, tid);
         // the slot's bytes behind a frame shorter than frame_bytes are not the frame's.  The parse kernel leaves such a frame's own
         // size in every block's descriptor (0: full size - every frame of a batch of one frame size); each thread clears what it staged
-        if (const int own = (int)(rfl(w1v.w) >> 16)) trim_staged_frame(frw, own, nw, tid, 384);
+        if (const int own = D.own_bytes()) trim_staged_frame(frw, own, nw, tid, 384);
         if (tid < M2_NDESC) L.dsc[tid] = mant_desc2((uint32_t)tid);
         L.qtab[tid] = q0;
         if (tid < 760 - 384) L.qtab[384 + tid] = q1;
@@ -140,28 +129,20 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
         for (int c = 0; c < n_in; c++)
             *reinterpret_cast<float4 *>(planes + c * MX_PLANE + 4 * lane) = make_float4(0.f, 0.f, 0.f, 0.f);
     } else {
-        {
-            const uint32_t a = rfl(w1v.x), b = rfl(w1v.y), c = rfl(w1v.z), d = rfl(w1v.w);
-            B.cplstrtmant = (int)(c >> 16); B.cplendmant = (int)(d & 0xffffu);
-            B.ends = (uint64_t)((a & 0xffu) | ((a >> 8) & 0xff00u) | ((b & 0xffu) << 16) | ((b << 8) & 0xff000000u)) | ((uint64_t)(c & 0xffu) << 32);
-        }
-        // the gains, lane k = slot k's (lane 5: the LFE's): one v_readlane per segment in mant_block2
-        B.gainv = lane == 0 ? __uint_as_float(w3v.x) : lane == 1 ? __uint_as_float(w3v.y) : lane == 2 ? __uint_as_float(w3v.z)
-                : lane == 3 ? __uint_as_float(w3v.w) : lane == 4 ? __uint_as_float(w4v.x) : __uint_as_float(w4v.y);
+        D.ranges(B);
+        B.gainv = D.gainv(lane);
         if (B.chincpl && lane < 18) {                               // sub-band -> band (parse.c:448-456)
-            const uint32_t below = rfl(w0v.w) & ((1u << lane) - 1u);
+            const uint32_t below = D.cplbndstrc() & ((1u << lane) - 1u);
             L.cplbnd[blk][lane] = (uint8_t)(lane - __popc(below));
         }
         const uint32_t fpos = rfl(fposv);
         const bool lfsr_live = fpos != 0xffffffffu;
-        const uint32_t i0 = lfsr_live ? (fpos + rfl(w0v.y)) % 65535u : 0u;
+        const uint32_t i0 = lfsr_live ? (fpos + D.draw_off()) % 65535u : 0u;
         const float *cc = P.cplco + unit * 90;
         mant_block2<MX_PLANE, true>(B, fetch, first, [&](int c, int bnd) { return cc[c * 18 + bnd]; }, L.cplbnd[blk], L.dsc, region + MX_RING, frw,
-                              (uint32_t)nw + 2u, L.qtab, reinterpret_cast<const int16_t *>(P.lfsr_seq) + 1 + i0, lfsr_live, planes, rfl(w0v.x), lane);
+                              (uint32_t)nw + 2u, L.qtab, reinterpret_cast<const int16_t *>(P.lfsr_seq) + 1 + i0, lfsr_live, planes, D.bitpos(), lane);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
 
     MX_LAP(1);
     // ---- transform: 8-lane group g takes plane g (left-over groups shadow plane 0 and store nothing) ----
@@ -208,9 +189,7 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
                 xb[n] = __builtin_fmaf(1.f, pb[-16 * n], 0.f);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         float2 *ex = reinterpret_cast<float2 *>(region) + o * EX_GROUP;
         const float2 *tw = &L.tw[sw ? 1 : 0][l8 * 16];
         cf r[16];
@@ -287,9 +266,7 @@ __global__ __launch_bounds__(384, MANTX_LB) void mantx_kernel(const MantxParams 
         }
     }
     if (S16) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         const int upb = 32 * n_in;                                // 16-byte units of the block
         int16_t *dst = Q.pcm16 + unit * 256 * n_in;
 #pragma unroll

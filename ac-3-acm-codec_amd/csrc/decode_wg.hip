@@ -106,12 +106,6 @@ __device__ __forceinline__ void wg_barrier()
 {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // An opaque copy of a lane-dependent value: address arithmetic derived from it stays where it is used instead of being
 // hoisted out of the (long) block loop and spilled.
 __device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
@@ -518,20 +512,8 @@ __device__ __forceinline__ void slot_t1(WgLDS &L, const BlkInfo &B, const FrameB
     } else if (end > start) {
         const int bai = ldsu(B.bai), mybai = ldsu(B.cbai[slot]);
         const int mydeltbae = slot == 5 ? 2 : ldsu(B.deltbae[slot == 6 ? 5 : slot]);
-        BaCtx c;
-        c.halfrate = halfrate;
-        c.fdecay = (63 + 20 * ((bai >> 7) & 3)) >> halfrate;
-        c.fgain = 128 + 128 * (mybai & 7);
-        c.sdecay = (15 + 2 * (bai >> 9)) >> halfrate;
-        c.sgain = k_slowgain[(bai >> 5) & 3];
-        c.dbknee = k_dbpb[(bai >> 3) & 3];
-        c.hth = L.hth;
-        c.deltba = (mydeltbae == 2) ? nullptr : L.deltba[slot == 6 ? 5 : slot];
-        const int fl = k_floors[bai & 7];
-        c.snroffset = 960 - 64 * ldsu(B.csnroffst) - 4 * (mybai >> 3) + fl;
-        c.floor = fl >> 5;
-        c.fast = slot == 6 ? ldsu(B.cplfleak) << 8 : 0;
-        c.slow = slot == 6 ? ldsu(B.cplsleak) << 8 : 0;
+        const BaCtx c = ba_ctx(bai, mybai, ldsu(B.csnroffst), halfrate, L.hth, mydeltbae == 2 ? nullptr : L.deltba[slot == 6 ? 5 : slot],
+                               slot == 6 ? ldsu(B.cplfleak) << 8 : 0, slot == 6 ? ldsu(B.cplsleak) << 8 : 0);
         bit_allocate_wave(L, L.bmask[wave], c, slot == 6 ? ldsu(B.cplstrtbnd) : 0, start, end, erow, brow, lane);
     }
     wave_sync();

@@ -336,9 +336,7 @@ __device__ __forceinline__ uint32_t mant_pack_block(const MantBlock &B, const ui
         const int E = k == 0 ? E0 : k == 1 ? E1 : E2;
         if (lane < 6) B.glist[k * GL_STRIDE + E + (lane & 1)] = 0;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
 
     MANT_LAP(9);
     // ---- stage 2 ----
@@ -395,9 +393,7 @@ __device__ __forceinline__ uint32_t mant_pack_block(const MantBlock &B, const ui
         pos += wave_last(bin_);
     }
     MANT_LAP(10);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     return pos;
 }
 

@@ -33,13 +33,6 @@
 
 namespace ac3mi {
 
-#define WAVE_SYNC()                                          \
-    do {                                                     \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                     \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-    } while (0)
-
 __device__ __forceinline__ int ilog2u(unsigned v) { return v ? 31 - __builtin_clz(v) : 0; }   // av_log2, :1539-1567
 
 __device__ __forceinline__ int wave_sum(int v) { return (int)wave_sum_u32((uint32_t)v); }
@@ -205,9 +198,9 @@ struct PackSink : SynWriter<PackSink<Row>> {
         const int gs = syn_grpsize(strat), first = row == SYN_CPL ? cs : 1;
         const uint8_t *e = erow;
         const uint32_t dw = row_of(row);
-        WAVE_SYNC();                                                // the previous row's groups have read the row
+        wave_sync();                                                // the previous row's groups have read the row
         *reinterpret_cast<uint32_t *>(&erow[4 * lane]) = dw;
-        WAVE_SYNC();
+        wave_sync();
         this->put(4, (uint32_t)__builtin_amdgcn_readfirstlane((int)e[first - 1]) >> (row == SYN_CPL ? 1 : 0));
         this->flush();
         for (int g = lane; g < ng; g += 64) {
@@ -331,11 +324,11 @@ __device__ uint32_t xs_choose(const uint8_t (*E)[256], uint8_t *scratch, uint32_
             int c15, c25 = 0, c45 = 0;
             if constexpr (CPLROW) {
                 *reinterpret_cast<uint32_t *>(&scratch[4 * lane]) = acc;
-                WAVE_SYNC();
+                wave_sync();
                 c15 = cpl_exp_sum(scratch, cs, ce, 1, lane);
                 c25 = cpl_exp_sum(scratch, cs, ce, 2, lane);
                 c45 = cpl_exp_sum(scratch, cs, ce, 3, lane);
-                WAVE_SYNC();
+                wave_sync();
             } else {
                 c15 = encode_exp_sum_t<4>(acc, n, lane);
                 if (!d15) {
@@ -513,7 +506,7 @@ __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, in
         }
         if (touched) *reinterpret_cast<uint32_t *>(&L.E[b][4 * lane]) = raw[b];
     }
-    WAVE_SYNC();
+    wave_sync();
 
     // ---- encode_exp on run starts (:1739-1746); the blocks of a run are sent the start's exponents ----
     int exp_bits = 0;
@@ -521,7 +514,7 @@ __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, in
         const int b = __builtin_ctz(m);
         exp_bits += encode_exp_wave(L.E[b], n, L.strat[b], lane);
     }
-    WAVE_SYNC();
+    wave_sync();
     {
         uint32_t cur = 0;
         for (int b = 0; b < 6; b++) {
@@ -581,7 +574,7 @@ __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, in
             }
             if (len > 0) mrow[((((uint32_t)(len - 1)) * 0xaaabu) >> 17) >> lw] = (int16_t)v;
         }
-        WAVE_SYNC();
+        wave_sync();
         // fixed allocation codes (:861-879)
         const int sdecaycod = 2, fdecaycod = 1, fgaincod = 4;
         constexpr int sgaincod = 1, dbkneecod = 2;
@@ -591,7 +584,7 @@ __device__ void exp_stage(const ExpParams &P, ExpLDS &L, size_t fidx, int ch, in
         for (uint32_t m = starts; m; m &= m - 1)
             mask_row_wave(L.t, L.mask[__builtin_ctz(m)], bndend, is_lfe, sdecay, fdecay, sgain, dbknee, fgain, P.halfrate, lane);
     }
-    WAVE_SYNC();
+    wave_sync();
 
     // ---- results: the pack kernel wants the masks minus the floor (floorcod 4: 0x1f0); a block inside a run has its start's
     //      curve.  Two rows of 25 dwords per step ----
@@ -636,16 +629,6 @@ struct MdctParams {
     ExpParams x;                // the exponent stage that follows the transform
     uint8_t *remat;             // enc_mdct_kernel<*, true>: [S][F][6] rematrixing decisions for the search and the packers
 };
-
-struct c16 { int16_t re, im; };
-
-__device__ __forceinline__ void bfly(c16 &p, c16 &q, int bx, int by, int ax, int ay)
-{
-    p.re = (int16_t)((bx + ax) >> 1);
-    p.im = (int16_t)((by + ay) >> 1);
-    q.re = (int16_t)((bx - ax) >> 1);
-    q.im = (int16_t)((by - ay) >> 1);
-}
 
 #ifndef ENC_MDCT_LB
 #define ENC_MDCT_LB 7        // 71 VGPRs, no scratch: 1.97 ms against 2.00 at 5 or 6 (75 VGPRs) and 2.07 at 8 (64 VGPRs, 24 bytes of scratch)
@@ -704,12 +687,8 @@ void enc_mdct_kernel(const MdctParams P)
     // samples for itself (PMC: 114 KB fetched per frame against 18 KB of PCM).  The bijective remap of cdna_hip_programming.md
     // (T1) makes consecutive units share an XCD: blocks with equal blockIdx % 8 take one contiguous range of units.  With
     // REMAT a unit is a workgroup = a stereo frame (the same bijection over gridDim.x = frames), its waves the channels.
-    int unit;                                       // (s*F + f)*nch + ch; REMAT: s*F + f
-    {
-        const unsigned n = gridDim.x, q = n >> 3, r = n & 7u, x = blockIdx.x & 7u, i = blockIdx.x >> 3;
-        unit = (int)((x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i);
-        unit = __builtin_amdgcn_readfirstlane(unit);        // (wave-uniform by construction: row and state addresses on the scalar unit)
-    }
+    // (s*F + f)*nch + ch; REMAT: s*F + f.  Wave-uniform by construction: row and state addresses on the scalar unit
+    const int unit = __builtin_amdgcn_readfirstlane((int)xcd_remap(blockIdx.x, gridDim.x));
     static_assert(!(LFEROW && (BSW || REMAT)), "the LFE row alone takes the plain kernel");
     static_assert(!(FX && (BSW || REMAT || BW || XS || LFEROW)), "the fixed 5.1 shape is the plain kernel's");
     const int nch = FX ? 6 : P.nch, frames = FX ? 1 : P.frames, nbc = FX ? 223 : P.x.nbc;
@@ -777,7 +756,7 @@ void enc_mdct_kernel(const MdctParams P)
         if constexpr (BSW) {
 #pragma unroll
             for (int k = 0; k < 4; k++) { zs[jpos[k]] = oldv[k]; zs[256 + jpos[k]] = newv[k]; }
-            WAVE_SYNC();
+            wave_sync();
             const int n0 = 8 * lane;
             int zm2 = lane ? zs[n0 - 2] : 0, zm1 = lane ? zs[n0 - 1] : 0, m = 0;
 #pragma unroll
@@ -798,7 +777,7 @@ void enc_mdct_kernel(const MdctParams P)
             sw = !lfe_ch && p11 > 400 &&
                  (p11 > 10 * p10 || 3 * p21 > 40 * p20 || 3 * p22 > 40 * p21 ||
                   g[4] > 20 * g[3] || g[5] > 20 * g[4] || g[6] > 20 * g[5] || g[7] > 20 * g[6]);
-            WAVE_SYNC();                                            // (every lane has read z before the row reuses the LDS)
+            wave_sync();                                            // (every lane has read z before the row reuses the LDS)
         }
         // ---- 512 input samples: 256 old + 256 new (:1673-1683), windowed (:1686-1693) - in registers ----
         int win_[8];
@@ -835,7 +814,7 @@ void enc_mdct_kernel(const MdctParams P)
             // 256 rotated samples - transform 1: rot = in[0..255]; transform 2: rot = -in[384..511] || in[256..383]
 #pragma unroll
             for (int k = 0; k < 4; k++) { zs[jpos[k]] = (int16_t)O[k]; zs[256 + jpos[k]] = (int16_t)N[k]; }
-            WAVE_SYNC();
+            wave_sync();
             int rr[2], ri[2], spc[2], sps[2];
 #pragma unroll
             for (int k = 0; k < 2; k++) { spc[k] = -P.tab->xcos2[Ls + 32 * k]; sps[k] = P.tab->xsin2[Ls + 32 * k]; }
@@ -850,7 +829,7 @@ void enc_mdct_kernel(const MdctParams P)
                 ri[k] = (int16_t)((__mul24(re, sps[k]) + __mul24(spc[k], im)) >> 15);
             }
             pr = rr[0]; pi = ri[0]; qr = rr[1]; qi = ri[1];
-            WAVE_SYNC();                                            // (z is read everywhere before the post-rotation writes the row)
+            wave_sync();                                            // (z is read everywhere before the post-rotation writes the row)
         } else {
             const int re0 = ((int)(int16_t)(-N[2]) - N[1]) >> 1, im0 = (-(O[2] - O[1])) >> 1;
             const int re1 = (O[0] - O[3]) >> 1, im1 = (-(N[0] - (int)(int16_t)(-N[3]))) >> 1;
@@ -950,7 +929,7 @@ void enc_mdct_kernel(const MdctParams P)
                 out[255 - 2 * (lane + 64)] = (__mul24(qr, sx1) - __mul24(qi, c1)) >> 15;
             }
         }
-        WAVE_SYNC();
+        wave_sync();
         // ---- exponents (:1707-1722) ----
         const size_t row = (((size_t)s * frames + f) * 6 + blk) * nch + ch;
         int4 cv = *reinterpret_cast<const int4 *>(&out[4 * lane]);
@@ -1048,7 +1027,7 @@ void enc_mdct_kernel(const MdctParams P)
         (void)rprev;
 #pragma unroll
         for (int k = 0; k < 4; k++) newv[k] = nxtv[k];
-        WAVE_SYNC();
+        wave_sync();
     }
     exp_stage<false, XS ? 1 : 0, FX>(P.x, XL, (size_t)sf, ch, lane);
 }
@@ -1189,7 +1168,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
     if (lane < 6 * nch) L.sh[lane / nch][lane % nch] = rm ? P.w.pshift[fidx * (6 * RN) + lane] : P.shift[fidx * 6 * nch + lane];
     bool decline = false;
     if (P.bsw) decline = __ballot(lane < 6 * nch && lane % nch < nfbw && P.bsw[fidx * 6 * nch + lane] != 0) != 0;
-    WAVE_SYNC();
+    wave_sync();
     int fmin = 127;
     for (int b = 0; b < 6; b++)
         for (int ch = 0; ch < nfbw; ch++) fmin = L.sh[b][ch] < fmin ? L.sh[b][ch] : fmin;
@@ -1235,7 +1214,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
         *reinterpret_cast<uint32_t *>(&X.E[b][4 * lane]) = epack;
         if (lane == 0) P.w.shift[fidx * 8 + b] = (int8_t)shb;
     }
-    WAVE_SYNC();
+    wave_sync();
 
     // ---- the frame decision: no band where 4 E(sum) < sum of the channels' E, E(sum) = 2^(2 g) E(coupling row) ----
     {
@@ -1265,7 +1244,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
             }
         }
     }
-    WAVE_SYNC();
+    wave_sync();
     uint32_t word = 1;
     for (int ch = 0; ch < nfbw; ch++) {
         int best = 0;
@@ -1331,13 +1310,13 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
             }
             if (touched) *reinterpret_cast<uint32_t *>(&X.E[b][4 * lane]) = raw[b];
         }
-        WAVE_SYNC();
+        wave_sync();
         int bits = 0;
         for (uint32_t m = starts; m; m &= m - 1) {
             const int b = __builtin_ctz(m);
             bits += cpl_encode_exp(X.E[b], cs, ce, st[b], lane);
         }
-        WAVE_SYNC();
+        wave_sync();
         constexpr int sdecaycod = 2, fdecaycod = 1, fgaincod = 4, sgaincod = 1, dbkneecod = 2;
         const int sdecay = enc_sdecay(sdecaycod) >> P.x.halfrate, fdecay = enc_fdecay(fdecaycod) >> P.x.halfrate;
         for (uint32_t m = starts; m; m &= m - 1) {
@@ -1345,7 +1324,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
             cpl_mask_wave(X.t, X.E[b], X.mask[b], cs, ce, sdecay, fdecay, enc_sgain(sgaincod), enc_dbknee(dbkneecod),
                           enc_fgain(fgaincod), P.x.halfrate, lane);
         }
-        WAVE_SYNC();
+        wave_sync();
         int src = 0;
         for (int b = 0; b < 6; b++) {
             src = ((starts >> b) & 1u) ? b : src;
@@ -1354,7 +1333,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
         }
         if (lane < 6) P.w.strat[fidx * 8 + lane] = (uint8_t)(lane == 0 ? st[0] : lane == 1 ? st[1] : lane == 2 ? st[2] : lane == 3 ? st[3] : lane == 4 ? st[4] : st[5]);
         if (lane == 0) P.w.ebits[fidx] = bits;
-        WAVE_SYNC();
+        wave_sync();
     }
 
     if (rm) {
@@ -1365,7 +1344,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
         int prev = 0;
         for (int b = 0; b < 6; b++) {
             if (lane < 16) (&L.rq[0][0])[lane] = 0;
-            WAVE_SYNC();
+            wave_sync();
             const int vl = L.sh[b][0], vr = L.sh[b][1], vm = vl < vr ? vl : vr;
             const int4 lv = *reinterpret_cast<const int4 *>(md + (b * RN) * 256 + 4 * lane);
             const int4 rv = *reinterpret_cast<const int4 *>(md + (b * RN + 1) * 256 + 4 * lane);
@@ -1384,7 +1363,7 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
                     atomicAdd(&L.rq[3][bd], (unsigned long long)(d * d));
                 }
             }
-            WAVE_SYNC();
+            wave_sync();
             int flags = 0;
             if (!P.bsw || P.bsw[(fidx * 6 + b) * RN] == P.bsw[(fidx * 6 + b) * RN + 1])
                 for (int bd = 0; bd < nrem; bd++) {
@@ -1425,12 +1404,12 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
             if (lane == 0) P.remat[fidx * 6 + b] = (uint8_t)(flags | (b == 0 || flags != prev ? 0x10 : 0));
             prev = flags;
         }
-        WAVE_SYNC();
+        wave_sync();
         exp_stage<false, XS ? 2 : 0>(P.x, X, fidx, 0, lane);
-        WAVE_SYNC();
+        wave_sync();
 #pragma unroll
         for (int b = 0; b < 6; b++) *reinterpret_cast<uint32_t *>(&X.E[b][4 * lane]) = *reinterpret_cast<const uint32_t *>(&L.E1[b][4 * lane]);
-        WAVE_SYNC();
+        wave_sync();
         exp_stage<false, XS ? 2 : 0>(P.x, X, fidx, 1, lane);
         return;
     }
@@ -1451,9 +1430,9 @@ __global__ __launch_bounds__(64) void enc_cpl_kernel(const CplParams P)
             }
             *reinterpret_cast<uint32_t *>(&X.E[b][4 * lane]) = epack;
         }
-        WAVE_SYNC();
+        wave_sync();
         exp_stage<!XS, XS ? 2 : 0>(P.x, X, fidx, ch, lane);
-        WAVE_SYNC();
+        wave_sync();
     }
 }
 
@@ -1651,7 +1630,7 @@ __global__ __launch_bounds__(64, FX ? 7 : ENC_SEARCH_LB) void enc_search_kernel(
             }
             if (lane < 6 * nch) { const int b = lane / nch, ch = lane - b * nch; L.strat[b][ch] = P.strat[fidx * 6 * nch + lane]; }
             frame_bits = wave_sum(lane < nch ? P.ebits[fidx * nch + lane] : 0);
-            WAVE_SYNC();
+            wave_sync();
             // rows (blk * 6 + ch) that send new exponents, i.e. start a run, as a bit set; and the same as bit 8*ch + b
             {
                 const int b6 = lane / 6, c6 = lane - 6 * b6;
@@ -1719,7 +1698,7 @@ __global__ __launch_bounds__(64, FX ? 7 : ENC_SEARCH_LB) void enc_search_kernel(
                     L.rowdesc[n0 + __builtin_popcount(cst & ((1u << lane) - 1u))] = (uint32_t)(lane * 256) | (1u << 15) | (cover << 16) | ((uint32_t)(36 + lane) << 24);
                 }
                 ncplrows = __builtin_popcount(cst & 0x3fu);
-                WAVE_SYNC();
+                wave_sync();
             }
         };
         // PART 1 replays the search from tabulated verdicts and needs the frame's data only for a verdict that is missing
@@ -2373,7 +2352,7 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         snroffset = (((csnr - 15) << 4) + fsnr) << 2;
         if (w1 & 0x100) snroffset = (((w1 >> 9) - 15) << 4) << 2;       // a frame whose search failed: the last attempt's allocation under the stale header offsets
     }
-    WAVE_SYNC();
+    wave_sync();
     PK_LAP(6);
 
     // ---- header (:1113-1147) ----
@@ -2492,14 +2471,14 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
     uint32_t crc1 = region_crc(L, fr, 2 * fs58, 2 * fs58, P.c1, P.pw1_t, 4, lane);
     crc1 = gf_mul_tab(crc1, P.crc_inv_t);
     const uint32_t crc2 = region_crc(L, fr, 2 * fs - 2, (fs - fs58) * 2 - 2, P.c2, P.pw2_t, 0, lane);
-    WAVE_SYNC();
+    wave_sync();
     if (lane == 0) {
         fr[0] = (fr[0] & 0xffff0000u) | (crc1 & 0xffff);                      // bytes 2,3
         const int p = 2 * fs - 2;                                                 // even -> inside one dword
         const int shft = 16 - 8 * (p & 3);
         fr[p >> 2] = (fr[p >> 2] & ~(0xffffu << shft)) | ((crc2 & 0xffff) << shft);
     }
-    WAVE_SYNC();
+    wave_sync();
     uint8_t *dst = P.frames + fidx * P.frame_stride;
     for (int i = lane; i < (2 * fs + 3) / 4; i += 64) {
         uint32_t v = __builtin_bswap32(fr[i]);
@@ -2557,11 +2536,7 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
     const int b = __builtin_amdgcn_readfirstlane(tid >> 6);
     PackbWave &W = L.w[b];
     // consecutive frames on one XCD (cdna_hip_programming.md T1): the six wavefronts' rows sit side by side in memory
-    size_t fidx;
-    {
-        const unsigned n = gridDim.x, q = n >> 3, r = n & 7u, x = blockIdx.x & 7u, i = blockIdx.x >> 3;
-        fidx = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
+    const size_t fidx = xcd_remap(blockIdx.x, gridDim.x);
     const int nch = P.nch, nfbw = P.nfbw, nbc = P.nbc, fs = P.frame_words;
 
     for (int i = tid; i < 256; i += 384) {

@@ -19,6 +19,104 @@ constexpr int M2_LDS_WAVE = M2_RING + 256;      // + one sink dword per lane for
 constexpr int M2_NDESC = 97;
 constexpr int LFSR_EXT = 16384;                 // entries of lfsr_seq past the period (a block draws < 5 * 1280 values)
 
+// ---------------------------------------------------------------------------
+// The split front end: decode_kernel<4 / 5> parses (side information, exponents, bit allocation) and leaves, per audio
+// block, this descriptor plus the exponent / bap rows that changed; mant_kernel and mantx_kernel (one wavefront per block)
+// unpack and dequantise from them.  What a block needs of the blocks before it is all here: where its mantissas start, how
+// many dither draws came before, which rows are current.  The reader (BlkWords: the descriptor as five 16-byte words in
+// registers) takes every offset and shift from the struct; the writer's are asserted below it.
+
+struct alignas(16) BlkDesc {
+    uint32_t bitpos;            // first mantissa bit of the block
+    uint32_t draw_off;          // dither draws of the frame before this block
+    uint32_t flags;             // BLK_FAILED, BLK_CHINCPL, BLK_DITH, BLK_REMAT
+    uint32_t cplbndstrc;
+    uint16_t endmant[5], cplstrt, cplend;
+    uint16_t own_bytes;         // the frame's own size where it is below frame_bytes, else 0 (every block of a frame, failed ones too)
+    uint8_t rv_exp[8], rv_bap[8];   // block of THIS frame whose row holds the slot's current exponents / bap
+    float gain[5], lfe_gain;        // parse.c:810-811 (dynamic range folded in); LFE: 0 when it is not an output
+    uint32_t src_snr;           // 16 csnroffst + fsnroffst (channel 0) the frame was coded with, as of this block
+    uint32_t pad1;
+};
+constexpr uint32_t BLK_FAILED = 1u;                             // flags: the block failed (zero planes)
+constexpr int BLK_CHINCPL = 8, BLK_DITH = 16, BLK_REMAT = 24;   // flags: first bit of chincpl (5 bits), the dither flags (5), rematflg (4)
+static_assert(sizeof(BlkDesc) == BLKDESC_BYTES && offsetof(BlkDesc, src_snr) == BLKDESC_SRC_SNR, "what the host sizes and reads (ac3mi_internal.h)");
+
+constexpr int ROWSET = 7 * 512;         // bytes of one (frame, block) row set: 7 slots x (256 exponents + 256 row bytes)
+
+// the parse kernel stores it from the lanes, one lane per field (decode_kernel.h): what lane k's member is
+static_assert(offsetof(BlkDesc, bitpos) == 0 && offsetof(BlkDesc, draw_off) == 4 && offsetof(BlkDesc, flags) == 8 && offsetof(BlkDesc, cplbndstrc) == 12,
+              "lanes 0-3: the first four dwords");
+static_assert(offsetof(BlkDesc, cplstrt) == offsetof(BlkDesc, endmant) + 2 * 5 && offsetof(BlkDesc, cplend) == offsetof(BlkDesc, endmant) + 2 * 6 &&
+              offsetof(BlkDesc, own_bytes) == offsetof(BlkDesc, endmant) + 2 * 7, "lanes 0-7: eight halfwords from endmant on; 6 = the coupling slot");
+static_assert(offsetof(BlkDesc, lfe_gain) == offsetof(BlkDesc, gain) + 4 * 5 && offsetof(BlkDesc, src_snr) == offsetof(BlkDesc, gain) + 4 * 6,
+              "lanes 0-6: seven dwords from gain on");
+
+// A block's descriptor as a wavefront of the mantissa kernels holds it: five 16-byte loads of one address (the kernel's own,
+// issued where its set-up wants them); only register arithmetic here.  u32<OFF>: the dword at byte OFF, per lane; s32<OFF>,
+// s16<OFF>: the dword / halfword there as a wave-uniform scalar.
+struct BlkWords {
+    uint4 q[sizeof(BlkDesc) / 16];
+    template <size_t OFF> __device__ __forceinline__ uint32_t u32() const
+    {
+        static_assert(OFF % 4 == 0 && OFF < sizeof(BlkDesc), "a dword of the descriptor");
+        constexpr int j = (OFF / 4) & 3;
+        const uint4 &v = q[OFF / 16];
+        return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w;
+    }
+    template <size_t OFF> __device__ __forceinline__ uint32_t s32() const { return rfl(u32<OFF>()); }
+    template <size_t OFF> __device__ __forceinline__ uint32_t s16() const
+    {
+        static_assert(OFF % 2 == 0, "a halfword of the descriptor");
+        return (s32<OFF & ~(size_t)3>() >> (8 * (OFF & 3))) & 0xffffu;
+    }
+    // the flags word: MantBlk's chincpl, dithmask and rematflg; returns whether the block failed
+    __device__ __forceinline__ bool head(MantBlk &B) const
+    {
+        const uint32_t flags = s32<offsetof(BlkDesc, flags)>();
+        B.chincpl = (int)((flags >> BLK_CHINCPL) & 31u); B.dithmask = (int)((flags >> BLK_DITH) & 31u); B.rematflg = (int)((flags >> BLK_REMAT) & 15u);
+        return (flags & BLK_FAILED) != 0u;
+    }
+    // MantBlk's coupling range and packed ends (byte k: endmant[k])
+    __device__ __forceinline__ void ranges(MantBlk &B) const
+    {
+        constexpr size_t E = offsetof(BlkDesc, endmant);
+        B.cplstrtmant = (int)s16<offsetof(BlkDesc, cplstrt)>(); B.cplendmant = (int)s16<offsetof(BlkDesc, cplend)>();
+        B.ends = (uint64_t)((s16<E>() & 0xffu) | ((s16<E + 2>() & 0xffu) << 8) | ((s16<E + 4>() & 0xffu) << 16) | ((s16<E + 6>() & 0xffu) << 24)) |
+                 ((uint64_t)(s16<E + 8>() & 0xffu) << 32);
+    }
+    // MantBlk's gainv: lane k = slot k's gain (lane 5 and up: the LFE's) - one v_readlane per segment in mant_block2
+    __device__ __forceinline__ float gainv(int lane) const
+    {
+        constexpr size_t G = offsetof(BlkDesc, gain);
+        return __uint_as_float(lane == 0 ? u32<G>() : lane == 1 ? u32<G + 4>() : lane == 2 ? u32<G + 8>() : lane == 3 ? u32<G + 12>()
+                             : lane == 4 ? u32<G + 16>() : u32<offsetof(BlkDesc, lfe_gain)>());
+    }
+    __device__ __forceinline__ int own_bytes() const { return (int)s16<offsetof(BlkDesc, own_bytes)>(); }
+    __device__ __forceinline__ uint32_t cplbndstrc() const { return s32<offsetof(BlkDesc, cplbndstrc)>(); }
+    __device__ __forceinline__ uint32_t bitpos() const { return s32<offsetof(BlkDesc, bitpos)>(); }
+    __device__ __forceinline__ uint32_t draw_off() const { return s32<offsetof(BlkDesc, draw_off)>(); }
+    // the row indices, byte k: slot k's
+    __device__ __forceinline__ uint64_t rv_exp() const { return (uint64_t)s32<offsetof(BlkDesc, rv_exp)>() | ((uint64_t)s32<offsetof(BlkDesc, rv_exp) + 4>() << 32); }
+    __device__ __forceinline__ uint64_t rv_bap() const { return (uint64_t)s32<offsetof(BlkDesc, rv_bap)>() | ((uint64_t)s32<offsetof(BlkDesc, rv_bap) + 4>() << 32); }
+};
+
+// The lane's row bytes and exponents of a slot's segment (mant_block2's fetch) from the frame's row sets: rve / rvb = the
+// descriptor's row indices (BlkWords::rv_exp / rv_bap).  It refers to the kernel's own values, as the closures it replaces
+// did: with copies mantx_kernel came out 1 to 5 instructions longer (profiles/decoder_shared_resources.md)
+struct RowFetch {
+    const uint8_t *const &rowbase;      // the frame's six row sets
+    const uint64_t &rve, &rvb;
+    const int &lane;
+    __device__ __forceinline__ uint2 operator()(int slot) const
+    {
+        const uint8_t *er = rowbase + (size_t)((rve >> (8 * slot)) & 7u) * ROWSET + slot * 512;
+        const uint8_t *br = rowbase + (size_t)((rvb >> (8 * slot)) & 7u) * ROWSET + slot * 512 + 256;
+        if (slot == 5) return lane < 7 ? make_uint2(br[lane], er[lane]) : make_uint2(1u, 0u);
+        return make_uint2(reinterpret_cast<const uint32_t *>(br)[lane], reinterpret_cast<const uint32_t *>(er)[lane]);
+    }
+};
+
 //  x: rank increment: 1 << 20 / 10 / 0 for a member of a 3- / 5- / 11-level code, 0 else
 //  y: plain bits | opener bits << 8 | members per code << 16 | rank field shift << 24
 //  z: 2048 / members rounded up (683, 1024; 0: ungrouped) | dequantiser table base << 16
@@ -187,9 +285,7 @@ __device__ __forceinline__ void mant_block2(const MantBlk &B, Fetch fetch, uint2
             // LFE: bins 0..6, one per lane; never coupled, never dithered, not rematrixed
             Bins2<1> R;
             seg2_first<1>(lane < 7 ? cur.x & 0xffu : 1u, dsc, ring, frw, frw_last, 0, S, R, lane);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             float q;
             seg2_values<1>(R, ring, qtab, &q);
             const float lfe_gain = PK ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, B.gainv), 5)) : B.lfe_gain;
@@ -227,9 +323,7 @@ __device__ __forceinline__ void mant_block2(const MantBlk &B, Fetch fetch, uint2
         }
         Bins2<4> R;
         seg2_first<4>(bytes4, dsc, ring, frw, frw_last, draws, S, R, lane);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         if (slot < 5) {
             float out[4], qv[4];
             seg2_values<4>(R, ring, qtab, qv);
@@ -304,9 +398,7 @@ __device__ __forceinline__ void mant_block2(const MantBlk &B, Fetch fetch, uint2
         }
     }
     if (remat_late) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         volatile float *p0 = cblk + (size_t)B.in_lfe * PS, *p1 = p0 + PS;
         for (int bin = 13 + lane; bin < remat_end; bin += 64) {
             const int band = bin < 25 ? 0 : bin < 37 ? 1 : bin < 61 ? 2 : 3;

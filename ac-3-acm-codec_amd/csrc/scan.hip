@@ -33,6 +33,7 @@ extern "C" int ac3mi_frame_scan(const uint8_t *buf, size_t len, int mode, int ma
 
 #ifdef __HIPCC__
 #include "ac3mi_internal.h"
+#include "wave_ops.h"
 
 namespace ac3mi {
 
@@ -120,9 +121,7 @@ __global__ __launch_bounds__(64 * SCAN_WAVES) void frame_scan_kernel(const ScanP
                     const uint32_t i = (uint32_t)lane + 64u * j;
                     if (i < nv) stage[wave][i] = v[j];
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_sync();
                 // ---- per-lane chunk sums; bytes in front of a region count as 0 ----
                 const int cls = fs > 1920u ? 3 : fs > 960u ? 2 : fs > 480u ? 1 : 0;
                 const int c1 = P.c1[cls], c2 = P.c2[cls];

@@ -33,16 +33,23 @@ __device__ __forceinline__ uint32_t wave_last(uint32_t v) { return (uint32_t)__b
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) { return wave_last(wave_incl_scan_u32(v)); }
 
-// bitwise OR of all lanes, wave-uniform
-__device__ __forceinline__ uint32_t wave_or_u32(uint32_t v)
+// What the lanes of a wavefront wrote to LDS or memory before this point, every lane of it reads behind it: release fence,
+// wavefront barrier, acquire fence.  (A release and a barrier WITHOUT the acquire - a wavefront that only hands its stores on -
+// is another fence and stays spelled out where it is used.)
+__device__ __forceinline__ void wave_sync()
 {
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-    return wave_last(v);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Consecutive work items on one XCD (its L2 then serves what neighbours share once): workgroup `block` of `grid`, which the
+// hardware deals to the eight XCDs in turn, takes the item that a contiguous eight-way split of the grid gives its XCD -
+// the bijective remap of cdna_hip_programming.md T1 (the first grid % 8 XCDs hold one item more).
+__device__ __forceinline__ unsigned xcd_remap(unsigned block, unsigned grid)
+{
+    const unsigned q = grid >> 3, r = grid & 7u, x = block & 7u, i = block >> 3;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
 }
 
 // a * b on the low 24 bits of both, as v_mul_u32_u24 and nothing else: where only the low bits of `__umul24(x & 0xffff, w)`

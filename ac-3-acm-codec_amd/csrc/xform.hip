@@ -319,9 +319,7 @@ __global__ __launch_bounds__(256, WPS) void xform_kernel(const XformParams P)
             dl[j].y = ft.t1[j];
         }
         if (S16 && emit) {                          // wave-uniform: a wavefront's groups share the segment
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             const int upb = 32 * P.n_out;           // 16-byte units per stream-block
 #pragma unroll
             for (int it = 0; it < 4; it++) {

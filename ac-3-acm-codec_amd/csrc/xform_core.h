@@ -33,6 +33,7 @@
 // per group per instruction.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "wave_ops.h"
 
 namespace ac3mi {
 
@@ -135,9 +136,7 @@ __device__ __forceinline__ void transpose_8x16_put(float2 *ex, int l8, const cf 
     float4 *row = reinterpret_cast<float4 *>(ex + l8 * EX_ROW);
 #pragma unroll
     for (int j = 0; j < 8; j++) row[j] = make_float4(v[2 * j].re, v[2 * j].im, v[2 * j + 1].re, v[2 * j + 1].im);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
 }
 __device__ __forceinline__ void transpose_8x16_get(const float2 *ex, int l8, cf (&r)[16])
 {
@@ -150,11 +149,6 @@ __device__ __forceinline__ void transpose_8x16_get(const float2 *ex, int l8, cf 
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-}
-__device__ __forceinline__ void transpose_8x16(float2 *ex, int l8, const cf (&v)[16], cf (&r)[16])
-{
-    transpose_8x16_put(ex, l8, v);
-    transpose_8x16_get(ex, l8, r);
 }
 
 // e^{-j pi k/16}, k = 0..7 and e^{-j pi k/8}, k = 0..3
