@@ -14,5 +14,6 @@ from .engine import Engine, XformDesc, DecodeDesc, EncodeDesc, syncinfo, bsi_rea
 from .engine import loudness_state_bytes, loudness_roles, loudness_tables, loudness_read  # noqa: F401
 from .engine import loudness_range_state_bytes, loudness_range_read  # noqa: F401
 from .engine import truepeak_state_bytes, truepeak_tables, truepeak_ceiling, truepeak_read, truepeak_host  # noqa: F401
+from .engine import limit_state_bytes, limit_release_step, limit_read, limit_host  # noqa: F401
 from . import flags  # noqa: F401
 from . import sharding  # noqa: F401

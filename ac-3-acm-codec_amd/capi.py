@@ -125,6 +125,22 @@ def truepeak_result_dtype():
     return dt
 
 
+class LimitResultC(ctypes.Structure):
+    """ac3mi_limit_result"""
+    _fields_ = [("samples", ctypes.c_uint64), ("reduced", ctypes.c_uint64), ("max_detect", ctypes.c_uint32),
+                ("min_gain_q24", ctypes.c_uint32), ("in_dbtp", ctypes.c_float), ("reduction_db", ctypes.c_float),
+                ("flags", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 7)]
+
+
+def limit_result_dtype():
+    """ac3mi_limit_result as a numpy structured dtype (40 bytes; a uint8 tensor [..., 40] views as it)"""
+    import numpy as np
+    dt = np.dtype([("samples", "<u8"), ("reduced", "<u8"), ("max_detect", "<u4"), ("min_gain_q24", "<u4"), ("in_dbtp", "<f4"),
+                   ("reduction_db", "<f4"), ("flags", "u1"), ("reserved", "u1", (7,))])
+    assert dt.itemsize == ctypes.sizeof(LimitResultC) == 40
+    return dt
+
+
 def _struct_dtype(cls, size):
     import numpy as np
     t = {ctypes.c_uint8: "u1", ctypes.c_uint16: "<u2", ctypes.c_uint32: "<u4"}
@@ -230,6 +246,14 @@ def load_library():
     lib.ac3mi_truepeak_read_batch.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_uint32, c_void_p]
     lib.ac3mi_truepeak_read.argtypes = [c_void_p, ctypes.c_uint32, ctypes.POINTER(TruePeakResultC)]
     lib.ac3mi_truepeak_host.argtypes = [c_int, c_void_p, c_void_p, c_int, c_void_p]
+    lib.ac3mi_limit_state_bytes.restype = c_size_t
+    lib.ac3mi_limit_state_bytes.argtypes = []
+    lib.ac3mi_limit_release_step.restype = ctypes.c_uint32
+    lib.ac3mi_limit_release_step.argtypes = [c_int, ctypes.c_double]
+    lib.ac3mi_limit_batch.argtypes = [c_void_p, c_int, c_void_p, ctypes.c_uint32, ctypes.c_uint32, c_void_p, c_void_p, c_int, c_int, c_void_p]
+    lib.ac3mi_limit_read_batch.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
+    lib.ac3mi_limit_read.argtypes = [c_void_p, ctypes.POINTER(LimitResultC)]
+    lib.ac3mi_limit_host.argtypes = [c_int, c_void_p, ctypes.c_uint32, ctypes.c_uint32, c_void_p, c_void_p, c_int, c_void_p]
     lib.ac3mi_set_encode_drc.argtypes = [c_void_p, c_int, c_void_p]
     lib.ac3mi_set_encode_dynrng_frames.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.ac3mi_set_encode_drc_source.argtypes = [c_void_p, c_int]

@@ -308,6 +308,21 @@ struct TruePeakLaunch {
 hipError_t launch_truepeak(const TruePeakLaunch &L, hipStream_t stream);
 hipError_t launch_truepeak_read(const void *state, int n_streams, uint32_t ceiling_q28, ac3mi_truepeak_result *results, hipStream_t stream);
 
+// limit.hip: the true-peak limiter (ac3mi_limit_*; the rule is include/ac3mi.h's, its steps limit_rule.h's).  No table and no
+// workspace in device memory
+struct LimitLaunch {
+    const int16_t *pcm;             // [S][F][1536][channels]
+    int16_t *out;                   // the same shape; pcm itself, or no overlap at all
+    int channels;
+    uint8_t role[6];
+    uint32_t ceiling_q28, release_step_q24;
+    int n_streams, frames_per_stream;
+    void *state;                    // [S] LimitState
+};
+bool limit_args_ok(const LimitLaunch &L);   // everything ac3mi_limit_batch refuses, the context apart
+hipError_t launch_limit(const LimitLaunch &L, hipStream_t stream);
+hipError_t launch_limit_read(const void *state, int n_streams, ac3mi_limit_result *results, hipStream_t stream);
+
 struct EncodeLaunch {
     EncConfig cfg;
     const int16_t *pcm;         // [S][F][1536][nch]

@@ -1452,6 +1452,44 @@ int ac3mi_truepeak_read_batch(ac3mi_ctx *ctx, const void *d_state, int n_streams
     return AC3MI_OK;
 }
 
+// (ac3mi_limit_state_bytes, _release_step, _read and _host, the host side, live in limit.hip beside the rule)
+int ac3mi_limit_batch(ac3mi_ctx *ctx, int channels, const uint8_t *role, uint32_t ceiling_q28, uint32_t release_step_q24,
+                      const int16_t *d_pcm, int16_t *d_out, int n_streams, int frames_per_stream, void *d_state)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    LimitLaunch L;
+    L.pcm = d_pcm;
+    L.out = d_out;
+    L.channels = channels;
+    for (int c = 0; c < 6; c++) L.role[c] = role && c < channels ? role[c] : 0;
+    L.ceiling_q28 = ceiling_q28;
+    L.release_step_q24 = release_step_q24;
+    L.n_streams = n_streams;
+    L.frames_per_stream = frames_per_stream;
+    L.state = d_state;
+    if (!role || !limit_args_ok(L)) {
+        ctx->err = "ac3mi_limit_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    if (n_streams == 0) return AC3MI_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, launch_limit(L, ctx->stream));
+    return AC3MI_OK;
+}
+
+int ac3mi_limit_read_batch(ac3mi_ctx *ctx, const void *d_state, int n_streams, ac3mi_limit_result *d_results)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (!d_state || !d_results || n_streams < 0 || ((uintptr_t)d_state & 7) || ((uintptr_t)d_results & 7)) {
+        ctx->err = "ac3mi_limit_read_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    if (n_streams == 0) return AC3MI_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, launch_limit_read(d_state, n_streams, d_results, ctx->stream));
+    return AC3MI_OK;
+}
+
 int ac3mi_decode_planes(const ac3mi_decode_desc *desc, int *n_out, int *out_flags)
 {
     if (!desc || desc->acmod < 0 || desc->acmod > 7) return AC3MI_ERR_ARG;

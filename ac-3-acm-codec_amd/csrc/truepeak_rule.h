@@ -64,7 +64,7 @@ static_assert(32768 * tp_abs_sum(1) == 542998528 && 32768 * tp_abs_sum(1) < (int
 
 // y[4 n + p] = sum over k of H[p][k] x[n - k], p = 0..3, from the 12 samples x[n - 11] .. x[n] in time order (x12[11] is x[n]).
 // The host twin runs this; truepeak_kernel forms the same int32 sums from pairs of samples with packed 16-bit dot products
-// (tp_phases_packed, truepeak.hip) - integer sums that cannot wrap, so the same bits in any order of adding.
+// (tp_phases_packed, truepeak_packed.h) - integer sums that cannot wrap, so the same bits in any order of adding.
 template <class X>
 __host__ __device__ inline void tp_phases(const X *x12, int32_t y[TP_PHASES])
 {

@@ -198,6 +198,49 @@ def truepeak_host(roles, pcm, state=None):
     return buf.raw
 
 
+def limit_state_bytes():
+    """ac3mi_limit_state_bytes: bytes of one stream's limiter state (all zeros: a new stream)"""
+    return int(capi.load_library().ac3mi_limit_state_bytes())
+
+
+def limit_release_step(sample_rate, full_recovery_ms):
+    """ac3mi_limit_release_step: the Q24 gain step per sample that recovers full scale in full_recovery_ms, in [1, 2^20]"""
+    return int(capi.load_library().ac3mi_limit_release_step(int(sample_rate), float(full_recovery_ms)))
+
+
+def limit_read(state):
+    """ac3mi_limit_read, the host read-out: one state's bytes (ac3mi_limit_state_bytes of them) -> a numpy record of
+    capi.limit_result_dtype()"""
+    import numpy as np
+    lib = capi.load_library()
+    data = bytes(bytearray(state))
+    if len(data) != lib.ac3mi_limit_state_bytes():
+        raise ValueError("a state is %d bytes" % lib.ac3mi_limit_state_bytes())
+    res = capi.LimitResultC()
+    if lib.ac3mi_limit_read(data, ctypes.byref(res)) != 0:
+        raise capi.AC3MIError("ac3mi_limit_read: bad argument")
+    return np.frombuffer(bytes(res), capi.limit_result_dtype())[0]
+
+
+def limit_host(roles, ceiling_q28, release_step_q24, pcm, state=None):
+    """ac3mi_limit_host, the host limiter (no GPU): pcm int16 [n][channels] of ONE stream, n a multiple of 1536, on the
+    state's bytes (None: a new stream) -> (out int16 [n][channels], the new state's bytes).  roles: 0 = not detected, else
+    detected, one per channel; every channel is delayed by 77 samples and gets the gain."""
+    import numpy as np
+    lib = capi.load_library()
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+    if pcm.ndim != 2 or pcm.shape[0] % 1536 or len(roles) != pcm.shape[1]:
+        raise ValueError("pcm is [frames * 1536][channels], one role per channel")
+    nb = lib.ac3mi_limit_state_bytes()
+    buf = ctypes.create_string_buffer(bytes(bytearray(state)) if state is not None else bytes(nb), nb)
+    role = (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6])
+    out = np.empty_like(pcm)
+    if lib.ac3mi_limit_host(int(pcm.shape[1]), role, int(ceiling_q28), int(release_step_q24), pcm.ctypes.data, out.ctypes.data,
+                            pcm.shape[0] // 1536, buf) != 0:
+        raise capi.AC3MIError("ac3mi_limit_host: bad argument")
+    return out, buf.raw
+
+
 def encode_metadata_word(**fields):
     """ac3mi_encode_metadata_word: the fields of Engine.set_encode_metadata (those not given: the defaults) -> the packed
     word; raises on a field out of range."""
@@ -708,6 +751,47 @@ class Engine:
         self._drain_torch(wait_torch)
         self._check(self.lib.ac3mi_truepeak_read_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(state.data_ptr()), int(S),
                                                        ctypes.c_uint32(int(ceiling_q28)), ctypes.c_void_p(out.data_ptr())))
+        self._keep.append((state, out))
+        return out
+
+    def limit_batch(self, roles, ceiling_q28, release_step_q24, pcm, state=None, out=None, wait_torch=True):
+        """ac3mi_limit_batch: limits pcm [S][F][1536][channels] s16 on the device to ceiling_q28 (truepeak_ceiling(dBTP)) with
+        release step release_step_q24 (limit_release_step) -> (out, state).  out: the same shape (default: allocated here;
+        `pcm` itself: in place); state u8 [S][limit_state_bytes()] (zeros: new streams; default: allocated here).  roles: 0 =
+        not detected, anything else = detected; every channel is delayed by 77 samples and gets the stream's gain."""
+        import torch
+        assert pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.is_cuda and pcm.dim() == 4 and pcm.shape[2] == 1536
+        S, F, _, nch = pcm.shape
+        nb = int(self.lib.ac3mi_limit_state_bytes())
+        if state is None:
+            state = torch.zeros((S, nb), dtype=torch.uint8, device=pcm.device)
+        if out is None:
+            out = torch.empty_like(pcm)
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == S * nb
+        assert out.dtype == torch.int16 and out.is_contiguous() and out.is_cuda and out.numel() == pcm.numel()
+        if len(roles) != nch:
+            raise ValueError("one role per channel")
+        role = (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6])
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_limit_batch(ctypes.c_void_p(self.ctx), int(nch), role, ctypes.c_uint32(int(ceiling_q28)),
+                                               ctypes.c_uint32(int(release_step_q24)), ctypes.c_void_p(pcm.data_ptr()),
+                                               ctypes.c_void_p(out.data_ptr()), int(S), int(F), ctypes.c_void_p(state.data_ptr())))
+        self._keep.append((pcm, out, state))
+        return out, state
+
+    def limit_read_batch(self, state, out=None, wait_torch=True):
+        """ac3mi_limit_read_batch: state u8 [S][limit_state_bytes()] -> results u8 [S][40];
+        `.cpu().numpy().view(capi.limit_result_dtype())[..., 0]` names the fields."""
+        import torch
+        nb = int(self.lib.ac3mi_limit_state_bytes())
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.is_cuda and state.numel() % nb == 0
+        S = state.numel() // nb
+        if out is None:
+            out = torch.zeros((S, 40), dtype=torch.uint8, device=state.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == S * 40
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_limit_read_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(state.data_ptr()), int(S),
+                                                    ctypes.c_void_p(out.data_ptr())))
         self._keep.append((state, out))
         return out
 

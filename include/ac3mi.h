@@ -548,6 +548,76 @@ int ac3mi_truepeak_read(const void *h_state, uint32_t ceiling_q28, ac3mi_truepea
  * sample on a state in host memory (any alignment).  The same errors. */
 int ac3mi_truepeak_host(int channels, const uint8_t *role, const int16_t *h_pcm, int frames, void *h_state);
 
+/* A true-peak limiter on the device (new): the stage that acts on AC3MI_TRUEPEAK_OVER.  A look-ahead limiter over the same s16
+ * PCM, between ac3mi_decode_s16_batch and ac3mi_encode_batch, with its state carried per stream from call to call like the
+ * meters'.  The whole rule, exact integer arithmetic throughout (the detector is the meter's interpolator):
+ *   constants  ONE = 2^24 (gains are Q24); W = 80, the hold window; B = 64, the smoothing window; D = 77 = AC3MI_LIMIT_DELAY,
+ *              the delay in samples.
+ *   parameters C = ceiling_q28 in [1, 2^28], in the meter's unit (ac3mi_truepeak_ceiling(-1.0) is a valid value);
+ *              R = release_step_q24 in [1, 2^20], the gain recovered per sample (ac3mi_limit_release_step).
+ *   input      d_pcm [n_streams][frames_per_stream][1536][channels] s16 interleaved and role[] as ac3mi_truepeak_batch takes
+ *              them: role[c] != 0 = slot c is detected.  Every slot is delayed and gets the gain, role-0 slots included (an
+ *              LFE stays aligned and balanced); there is one gain per stream, the slots are linked.
+ *   signal     per stream n counts sample instants from the stream's first sample over all calls; x_c[n] = 0 for n < 0; y is
+ *              the meter's y[4 n + p] = sum over k of H[p][k] x[n - k].
+ *                d[n] = max over detected slots c of max(|y_c[4 n + p]|, p = 0..3; |x_c[n - 5]| * 8192; |x_c[n - 6]| * 8192)
+ *                       (u32, < 2^30; the phases at instant n are the signal at the times n - 5.875 + p / 4)
+ *                q[n] = ONE if d[n] <= C, else floor(C * 2^24 / d[n])        (exact; the numerator has up to 52 bits)
+ *                m[n] = min(q[j], n - 79 <= j <= n),  q[j] = ONE for j < 0
+ *                r[n] = min(m[n], r[n - 1] + R),  r[-1] = ONE
+ *                g[n] = (sum of r[k], n - 63 <= k <= n) >> 6,  r[k] = ONE for k < 0
+ *                z_c[n] = (x_c[n - 77] * g[n] + 2^23) >> 24                  (arithmetic shift: floor; every slot c)
+ *   what follows   g[n] <= q[j] for n - 79 <= j <= n - 63, the instants around the sample being output; g <= ONE, so z never
+ *              leaves an s16 and nothing is clamped; |z_c[n]| <= (C + 4096) >> 13 for every detected slot, a hard bound on the
+ *              output's sample peak; where g is constant over 12 consecutive outputs the output's true peak there is
+ *              <= C + 8286 (half an output step times the interpolator's largest absolute phase sum, 16571).
+ *   scope      the gain only reduces: no make-up or pre-gain (dialnorm is the loudness remedy).  The first 77 output samples
+ *              of a stream are zeros and its last 77 input samples stay in the state: a caller who wants them feeds one more
+ *              frame of zeros.  There is no flush call.
+ *   state      samples and reduced (instants with g < ONE), u64; max d and ONE - min g; ONE - q of the last 80 instants,
+ *              ONE - r of the last 64, the last 80 input samples of every slot.
+ *   read-out   samples, reduced, max_detect, min_gain_q24 = min g;  in_dbtp = 20 log10(max_detect / 2^28), -200 when it is 0,
+ *              reduction_db = 20 log10(min_gain_q24 / 2^24), 0 when nothing was reduced (-200 for a gain of 0), floats,
+ *              informative;  AC3MI_LIMIT_EMPTY when samples == 0, AC3MI_LIMIT_ACTIVE when reduced > 0.
+ * The output and the state are the same bits for every way of cutting a stream into calls, for either alignment of the
+ * buffers, in place or not, and on the host twins, which run the same rule code sample by sample. */
+#define AC3MI_LIMIT_DELAY 77
+typedef struct {
+    uint64_t samples;               /* sample instants processed */
+    uint64_t reduced;               /* ... with g[n] < ONE */
+    uint32_t max_detect;            /* max d[n], 2^-28 of full scale: the input's true peak as the limiter saw it */
+    uint32_t min_gain_q24;          /* min g[n] */
+    float in_dbtp, reduction_db;    /* informative; -200 / 0 when empty */
+    uint8_t flags;                  /* AC3MI_LIMIT_EMPTY, AC3MI_LIMIT_ACTIVE */
+    uint8_t reserved[7];            /* 0 */
+} ac3mi_limit_result;               /* 40 bytes */
+#define AC3MI_LIMIT_EMPTY 1         /* nothing was processed */
+#define AC3MI_LIMIT_ACTIVE 2        /* the gain was below ONE somewhere */
+
+/* Bytes of one stream's state.  Opaque, in the caller's device memory, d_state[n_streams] records of this size (8-byte
+ * aligned); all zeros is a new stream, and every ac3mi_limit_batch reads and rewrites it. */
+size_t ac3mi_limit_state_bytes(void);
+/* ceil(2^24 / (sample_rate * full_recovery_ms / 1000)) clamped to [1, 2^20]: the step that recovers full scale in the given
+ * time.  Not a number: 1.  Once, on the host. */
+uint32_t ac3mi_limit_release_step(int sample_rate, double full_recovery_ms);
+/* Limits frames_per_stream more frames of every stream, one wavefront per stream, asynchronous on the context's stream; no
+ * workspace and no table in device memory.  d_out [n_streams][frames_per_stream][1536][channels] may be exactly d_pcm (in
+ * place) or must not overlap it at all; both 2-byte aligned (16-byte aligned bases are moved with 16-byte loads and stores,
+ * same bits).  AC3MI_ERR_ARG, with state and output untouched: channels outside 1..6, a NULL or misaligned pointer, a partial
+ * overlap, frames_per_stream < 1, n_streams < 0, a ceiling outside [1, 2^28], a step outside [1, 2^20].  n_streams 0:
+ * AC3MI_OK, nothing is launched. */
+int ac3mi_limit_batch(ac3mi_ctx *ctx, int channels, const uint8_t *role, uint32_t ceiling_q28, uint32_t release_step_q24,
+                      const int16_t *d_pcm, int16_t *d_out, int n_streams, int frames_per_stream, void *d_state);
+/* The read-out of n_streams states into d_results[n_streams] (8-byte aligned), one stream per lane; the states are not
+ * changed. */
+int ac3mi_limit_read_batch(ac3mi_ctx *ctx, const void *d_state, int n_streams, ac3mi_limit_result *d_results);
+/* Host twin of the read-out, no GPU and no context: the same rule code on one state copied to host memory (any alignment). */
+int ac3mi_limit_read(const void *h_state, ac3mi_limit_result *out);
+/* Host twin of the limiter, no GPU and no context: `frames` more frames of ONE stream, h_pcm and h_out
+ * [frames][1536][channels], sample by sample on a state in host memory (any alignment).  The same errors. */
+int ac3mi_limit_host(int channels, const uint8_t *role, uint32_t ceiling_q28, uint32_t release_step_q24,
+                     const int16_t *h_pcm, int16_t *h_out, int frames, void *h_state);
+
 /* How ac3mi_encode_batch / ac3mi_transcode_batch pack a frame once its SNR offsets are found (new; same bytes either way -
  * the searches always run first, one wavefront per stream, frames in order):
  *   1  one wavefront per frame packs it;
