@@ -6,7 +6,8 @@
 // A sink has put(n, v), flush() and exponents(row, strat, ng): the emitters call the last where a row's absolute exponent
 // and its ng 7-bit groups go, and what it does is the sink's (encode.hip: PackSink::exponents; SynCounter: 4 + 7 ng).
 // enc_packf_kernel and enc_packb_kernel write through these lists; enc_packb_kernel places its blocks by their closed forms
-// (syn_header_bits, syn_block_bits).
+// (syn_header_bits, syn_block_bits); enc_packf_kernel<FIXED51> without tools places the images of the 5.1 frame
+// (syn_block_images_51, syn_header_image_51), a restatement of the lists that tests/syn_images_c holds to them.
 // Plain C++: compiles without HIP (tests/enc_syntax_c walks every shape on the host under the sanitisers).
 #pragma once
 #include <stdint.h>
@@ -212,6 +213,84 @@ SYN_FN int syn_block_bits(const SynShape &s, int b, uint32_t dynrng0, uint32_t d
         bits += 4 + 7 * syn_exp_groups(is_lfe ? 7 : s.nbc, stg) + (is_lfe ? 0 : 8);      // (fbw: chbwcod 6 + gainrng 2)
     }
     return bits;
+}
+
+// ---- the fixed 5.1 frame once more, as images ----
+// A RESTATEMENT for enc_packf_kernel<FIXED51> without tools (acmod 7 + LFE, five full-bandwidth channels, the reference's BSI;
+// no coupling, rematrixing, dynrng or compr words): the lists above stay the one authority, and tests/syn_images_c holds
+// these to them bit for bit.  Everything between two exponent rows is a constant or a function of the block's six
+// strategies, so the block's fields come as two images the lanes OR into the frame and one bit offset per row, instead of
+// a field at a time through the accumulator:
+//   pre   blksw .. the last chbwcod, MSB-first (bit 31 of pre[0] = the block's first bit), pre_bits <= 54
+//   suf   baie .. skiple, suf_bits = 63 in block 0 (the allocation codes and offsets), else 4 zeros; at bit suf_at
+//   absexp_at[ch] / gainrng_at[ch]: where a row that sends exponents has its absolute exponent (its groups follow at + 4 + 7 g)
+//   and its gainrng (0: the row sends none; the LFE has no gainrng); all offsets from the block's first bit
+//   bits  = syn_block_bits
+// Values wider than their fields (csnr, fsnr) spill as in the accumulator: onto the fields before them.
+struct SynImages51 {
+    uint32_t pre[2], suf[2];
+    int pre_bits, suf_bits, suf_at, bits;
+    int absexp_at[6], gainrng_at[6];
+};
+// blksw: channel 0's flag in bit 4 .. channel 4's in bit 0; strat_of(ch), ch 5 = the LFE; nbc, chbwcod: SynShape's
+template <class Strat>
+SYN_FN void syn_block_images_51(SynImages51 &im, int b, uint32_t blksw, Strat strat_of, int nbc, uint32_t chbwcod, uint32_t csnr, uint32_t fsnr)
+{
+    uint64_t acc = ((uint64_t)blksw << 5) | 31u;                // blksw, dithflag
+    acc = b == 0 ? (acc << 3) | 2u : acc << 2;                  // dynrnge 0; cplstre (+ cplinu 0 in block 0)
+    int n = b == 0 ? 13 : 12;
+    for (int ch = 0; ch < 5; ch++) acc = (acc << 2) | strat_of(ch);
+    acc = (acc << 1) | strat_of(5);
+    n += 11;
+    for (int ch = 0; ch < 5; ch++)
+        if (strat_of(ch) != 0) { acc = (acc << 6) | chbwcod; n += 6; }
+    im.pre_bits = n;
+    acc <<= 64 - n;                                             // (23 <= n <= 54)
+    im.pre[0] = (uint32_t)(acc >> 32);
+    im.pre[1] = (uint32_t)acc;
+    int at = n;
+    for (int ch = 0; ch < 6; ch++) {
+        const int stg = (int)strat_of(ch);
+        im.absexp_at[ch] = im.gainrng_at[ch] = 0;
+        if (stg == 0) continue;
+        im.absexp_at[ch] = at;
+        at += 4 + 7 * syn_exp_groups(ch == 5 ? 7 : nbc, stg);
+        if (ch < 5) { im.gainrng_at[ch] = at; at += 2; }
+    }
+    im.suf_at = at;
+    // baie, the five codes, snroffste, csnroffst, six fsnroffst / fgaincod pairs, deltbaie, skiple
+    uint64_t s = (1u << 11) | (sdecaycod << 9) | (fdecaycod << 7) | (sgaincod << 5) | (dbkneecod << 3) | floorcod;
+    s = (((s << 1) | 1u) << 6) | csnr;
+    for (int ch = 0; ch < 6; ch++) s = (((s << 4) | fsnr) << 3) | fgaincod;
+    s <<= 3;                                                    // (the two zeros; 63 bits, left-aligned)
+    im.suf[0] = b == 0 ? (uint32_t)(s >> 32) : 0u;
+    im.suf[1] = b == 0 ? (uint32_t)s : 0u;
+    im.suf_bits = b == 0 ? 63 : 4;
+    im.bits = at + im.suf_bits;
+}
+// dword j (0, 1, 2) of what a two-dword image w0 : w1 puts into the frame's MSB-first dwords from dword at >> 5 on, its first
+// bit at bit `at`: a funnel shift (v_alignbit_b32) per dword, one lane each
+SYN_FN uint32_t syn_image_dword(uint32_t w0, uint32_t w1, int j, uint32_t at)
+{
+    const uint32_t a = j == 1 ? w0 : j == 2 ? w1 : 0u, c = j == 0 ? w0 : j == 1 ? w1 : 0u, s = at & 31u;
+    return s ? (a << (32u - s)) | (c >> s) : c;
+}
+// The header of the same frames (syn_header with BSI_DEFAULT, acmod 7, LFE, no compr word: 69 bits), crc1 as zeros
+constexpr int SYN_HEADER_BITS_51 = 69;
+SYN_FN void syn_header_image_51(uint32_t (&w)[3], uint32_t fscod, uint32_t frmsizecod, uint32_t bsid, uint32_t m)
+{
+    w[0] = 0x0b770000u;
+    // fscod 2, frmsizecod 6, bsid 5, bsmod 3, acmod 3 (7), cmixlev 2, surmixlev 2, lfeon 1, dialnorm 5, compre 0, langcode 0 | audprodie 0: 32
+    uint32_t v = (fscod << 6) | frmsizecod;
+    v = (v << 5) | bsid;
+    v = (v << 3) | ((m >> 5) & 7u);
+    v = (v << 3) | 7u;
+    v = (v << 2) | ((m >> 8) & 3u);
+    v = (v << 2) | ((m >> 10) & 3u);
+    v = (v << 1) | 1u;
+    v = (v << 5) | (m & 31u);
+    w[1] = v << 3;
+    w[2] = ((((m >> 14) & 1u) << 1) | ((m >> 15) & 1u)) << 30;                 // copyrightb, origbs; timecod1e, timecod2e, addbsie 0
 }
 
 // ---- what the SNR-offset search charges a frame besides its channels' exponents and mantissas (:880-916) ----

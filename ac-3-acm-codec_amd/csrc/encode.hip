@@ -17,7 +17,8 @@
 //  enc_packb_kernel    the same with a workgroup of six wavefronts per frame, one per audio block (small batches)
 //  The frame's side-information syntax - the field lists both packers write through, the field accumulator, enc_packb_kernel's
 //  closed-form counts and the search's price for the same fields - is enc_syntax.h's; here are the sink that puts the fields
-//  into the LDS frame (PackSink) and the values each kernel feeds the lists.
+//  into the LDS frame (PackSink) and the values each kernel feeds the lists.  enc_packf_kernel<FIXED51> without tools places
+//  enc_syntax.h's images of the same fields by lanes instead (or_image, exp_row_at).
 //
 // Integer arithmetic only (no -ffast-math dependence); the Q15 tables come from the host (capi.hip)
 // with the reference's expressions.
@@ -212,6 +213,34 @@ struct PackSink : SynWriter<PackSink<Row>> {
         this->pos += 7 * ng;
     }
 };
+
+// The same for a frame whose side information comes as images (enc_syntax.h: SynImages51).
+// A two-dword image w[0] : w[1] into the frame from bit `at`: lanes 0..2 OR a dword each (syn_image_dword).  Dwords that would
+// start within the last two of the buffer are dropped, as put_bits drops a field there: 256 bytes behind the frame's last byte.
+__device__ __forceinline__ void or_image(uint32_t *fr, int frw, const uint32_t *w, uint32_t at, int lane)
+{
+    if (lane < 3) {
+        const uint32_t d = syn_image_dword(w[0], w[1], lane, at), i = (at >> 5) + (uint32_t)lane;
+        if (d && i + 1 < (uint32_t)frw) atomicOr(&fr[i], d);
+    }
+}
+// A row's exponents from bit `at`: PackSink::exponents of a channel row without the accumulator - the lane of group 0 writes
+// the absolute exponent in front of it, as one field of 11 bits.
+__device__ __forceinline__ void exp_row_at(uint32_t *fr, int frw, uint8_t *erow, uint32_t dw, uint32_t at, int strat, int ng, int lane)
+{
+    const int gs = syn_grpsize(strat);
+    const uint8_t *e = erow;
+    wave_sync();                                                    // the previous row's groups have read the row
+    *reinterpret_cast<uint32_t *>(&erow[4 * lane]) = dw;
+    wave_sync();
+    for (int g = lane; g < ng; g += 64) {
+        const int k0 = 1 + 3 * g * gs;
+        const int prev = g ? e[k0 - gs] : e[0];
+        const int d0 = e[k0] - prev + 2, d1 = e[k0 + gs] - e[k0] + 2, d2 = e[k0 + 2 * gs] - e[k0 + gs] + 2;
+        const uint32_t code = (uint32_t)((d0 * 5 + d1) * 5 + d2);
+        put_bits(fr, frw, g ? at + 4 + 7 * g : at, g ? 7 : 11, g ? code : ((uint32_t)e[0] << 7) | code);
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // exp_stage's routines, wavefront-wide.
@@ -2271,9 +2300,18 @@ __global__ __launch_bounds__(64, FX ? 7 : ENC_SEARCH_LB) void enc_search_kernel(
 // ---------------------------------------------------------------------------------------------
 // enc_packf_kernel: a frame whose SNR offsets are known (P.snr, from enc_search_kernel<1>) is packed by ONE wavefront -
 // the packer of large batches.  Header, side information and exponent groups as wave-uniform fields through a 64-bit
-// scalar accumulator, the mantissas block by block on enc_mant.h, both CRCs, the frame out.
-template <bool CPL>
-struct alignas(16) PackfLDS {
+// scalar accumulator - or, for the 5.1 frame without tools, from images by lanes (IMG below) - the mantissas block by block
+// on enc_mant.h, both CRCs, the frame out.
+// The six blocks' side information as images (enc_syntax.h: SynImages51), left here once per frame by lanes 0..5 (lane = block):
+// 152 bytes (160 with the alignment), with which a 384 kbps frame's workgroup takes 9 744 bytes of LDS - still 16 per CU.
+struct PackfImages {
+    alignas(16) uint16_t at[6][8];      // per block: absexp_at of rows 0..5, suf_at, bits
+    uint32_t pre[6][2];
+    uint32_t suf0[2];                   // block 0's suffix (the other blocks': four zero bits, nothing to write)
+};
+struct PackfNoImages {};
+template <bool CPL, bool IMG = false>
+struct alignas(16) PackfLDS : std::conditional_t<IMG, PackfImages, PackfNoImages> {
     int16_t mask[CPL ? 7 : 6][50];  // this block's masking curves as band terms (mant_band_terms), one row per channel (+ coupling)
     uint4 packlut[64];                  // mant_pack_entry per bap table address
     alignas(16) uint16_t glist[GL_ENTRIES];
@@ -2283,8 +2321,8 @@ struct alignas(16) PackfLDS {
 };
 
 #ifndef ENC_PACK2_LB
-#define ENC_PACK2_LB 4           // <true>: 125 VGPRs, no scratch (<true, false, true>: 11 VGPRs spilled, the coupled ones none).  5 per SIMD cannot
-                                 // be reached any more: with the 1-KiB quantiser table a 384 kbps frame's workgroup takes ~9.6 KB of LDS, 16 per CU
+#define ENC_PACK2_LB 4           // <true>: 124 VGPRs, no scratch (<true, false, true>: 10 VGPRs spilled, the coupled ones none).  5 per SIMD cannot
+                                 // be reached any more: with the 1-KiB quantiser table a 384 kbps frame's workgroup takes ~9.7 KB of LDS, 16 per CU
                                  // (round 4, before the table: 1.78 ms per 65 536 frames at 4 against 1.84 at 5)
 #endif
 // FIXED51: the 5.1 configuration (five full-bandwidth channels + LFE, acmod 7) as compile-time constants - the shape large batches
@@ -2303,7 +2341,9 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
     static_assert(!DW || MD, "the array words are written where the profiles' are");
     static_assert(!(FIXED51 && CPL), "coupled frames take the generic packer");
     static_assert(!(DUAL && (FIXED51 || CPL)), "dual mono is neither 5.1 nor coupled");
-    __shared__ PackfLDS<CPL> L;
+    // IMG: the 5.1 frame without tools - its side information from images (syn_block_images_51), placed by lanes
+    constexpr bool IMG = FIXED51 && !CPL && !MD && !DUAL && !DW;
+    __shared__ PackfLDS<CPL, IMG> L;
     extern __shared__ uint4 pk_dyn[];
     uint32_t *fr = reinterpret_cast<uint32_t *>(pk_dyn);
     const int lane = threadIdx.x;
@@ -2352,14 +2392,38 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
         snroffset = (((csnr - 15) << 4) + fsnr) << 2;
         if (w1 & 0x100) snroffset = (((w1 >> 9) - 15) << 4) << 2;       // a frame whose search failed: the last attempt's allocation under the stale header offsets
     }
+    if constexpr (IMG) {
+        // lane b: block b's images and row offsets, from the strategies' two bit planes (lane 6 b + ch: bit 6 b + ch)
+        const uint64_t s_lo = __ballot(strat_l & 1), s_hi = __ballot(strat_l & 2);
+        if (lane < 6) {
+            const uint32_t lo = (uint32_t)(s_lo >> (6 * lane)) & 63u, hi = (uint32_t)(s_hi >> (6 * lane)) & 63u;
+            uint32_t bswm = 0;
+            if (P.bsw) {
+#pragma unroll
+                for (int ch = 0; ch < 5; ch++) bswm = (bswm << 1) | P.bsw[(fidx * 6 + lane) * 6 + ch];
+            }
+            SynImages51 im;
+            syn_block_images_51(im, lane, bswm, [&](int ch) { return ((lo >> ch) & 1u) | (((hi >> ch) & 1u) << 1); }, nbc, (uint32_t)P.chbwcod,
+                                (uint32_t)csnr, (uint32_t)fsnr);
+            *reinterpret_cast<uint4 *>(L.at[lane]) = make_uint4((uint32_t)(im.absexp_at[0] | im.absexp_at[1] << 16), (uint32_t)(im.absexp_at[2] | im.absexp_at[3] << 16),
+                                                                (uint32_t)(im.absexp_at[4] | im.absexp_at[5] << 16), (uint32_t)(im.suf_at | im.bits << 16));
+            *reinterpret_cast<uint2 *>(L.pre[lane]) = make_uint2(im.pre[0], im.pre[1]);
+            if (lane == 0) *reinterpret_cast<uint2 *>(L.suf0) = make_uint2(im.suf[0], im.suf[1]);
+        }
+    }
     wave_sync();
     PK_LAP(6);
 
     // ---- header (:1113-1147) ----
     // Side information is wave-uniform: the field lists of enc_syntax.h through its 64-bit accumulator (PackSink), which stays
-    // in scalar registers.
+    // in scalar registers - but for the 5.1 frame without tools (IMG), whose header is one image stored by three lanes.
     uint32_t pos;                       // first bit not yet in the frame
-    {
+    if constexpr (IMG) {
+        uint32_t hw[3];
+        syn_header_image_51(hw, (uint32_t)P.fscod, (uint32_t)P.frmsizecod, (uint32_t)P.bsid, BSI_DEFAULT);
+        if (lane < 3) fr[lane] = lane == 0 ? hw[0] : lane == 1 ? hw[1] : hw[2];
+        pos = SYN_HEADER_BITS_51;
+    } else {
         PackSink k(fr, P.frw, lane, L.erow, [](int) { return 0u; }, cs, 0u);
         syn_header(k, P.fscod, P.frmsizecod, P.bsid, acmod, lfe, DUAL, MD ? pack_bsi(P, fidx) : BSI_DEFAULT,
                    DW ? compr_word(P, fidx, 0) : 0u, DW && DUAL ? compr_word(P, fidx, 1) : 0u);
@@ -2394,14 +2458,31 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
                 if (lane + 64 * j < nch * 25) reinterpret_cast<uint32_t *>(&L.mask[0][0])[lane + 64 * j] = mant_band_terms(mv[j], snroffset);
         }
         auto strat_of = [&](int ch) { return (uint32_t)__builtin_amdgcn_readlane(strat_l, 6 * b + ch); };
-        const uint8_t *bs = P.bsw ? P.bsw + (fidx * 6 + b) * nch : nullptr;
-        PackSink k(fr, P.frw, lane, L.erow, [&](int row) { return pick_row(ew, row, cew); }, cs, pos);
-        syn_block(k, shape, SynCpl{cplw, P.cpl_begf, cendf, (uint32_t)cstg}, b,
-                  [&](int ch) -> uint32_t { return bs ? bs[ch] : 0u; },
-                  [&](int p) { return pack_dynrng<MD, DW>(P, fidx, b, p); },
-                  acmod == 2 && P.remat ? (uint32_t)P.remat[fidx * 6 + b] : b == 0 ? 0x10u : 0u, strat_of,
-                  [&](int ch, int bd) -> uint32_t { return P.cpl.co[fidx * 80 + ch * 16 + bd]; }, (uint32_t)csnr, (uint32_t)fsnr);
-        pos = k.pos;
+        if constexpr (IMG) {
+            // the block's fields from its images: three lanes OR the prefix in at `pos` (block 0: three more the suffix at
+            // suf_at), and every row's group lanes write at the row's offset - no field goes through an accumulator, and
+            // nothing between two rows waits for lane 0.  (gainrng is 0: its two bits are the frame's zeros.)
+            const uint4 atw = *reinterpret_cast<const uint4 *>(L.at[b]);
+            or_image(fr, P.frw, L.pre[b], pos, lane);
+#pragma unroll
+            for (int ch = 0; ch < 6; ch++) {
+                const int stg = (int)strat_of(ch);
+                if (stg == 0) continue;
+                const uint32_t pair = ch < 2 ? atw.x : ch < 4 ? atw.y : atw.z;
+                exp_row_at(fr, P.frw, L.erow, ew[ch], pos + ((ch & 1) ? pair >> 16 : pair & 0xffffu), stg, syn_exp_groups(ch == 5 ? 7 : nbc, stg), lane);
+            }
+            if (b == 0) or_image(fr, P.frw, L.suf0, pos + (atw.w & 0xffffu), lane);
+            pos += (uint32_t)__builtin_amdgcn_readfirstlane((int)(atw.w >> 16));
+        } else {
+            const uint8_t *bs = P.bsw ? P.bsw + (fidx * 6 + b) * nch : nullptr;
+            PackSink k(fr, P.frw, lane, L.erow, [&](int row) { return pick_row(ew, row, cew); }, cs, pos);
+            syn_block(k, shape, SynCpl{cplw, P.cpl_begf, cendf, (uint32_t)cstg}, b,
+                      [&](int ch) -> uint32_t { return bs ? bs[ch] : 0u; },
+                      [&](int p) { return pack_dynrng<MD, DW>(P, fidx, b, p); },
+                      acmod == 2 && P.remat ? (uint32_t)P.remat[fidx * 6 + b] : b == 0 ? 0x10u : 0u, strat_of,
+                      [&](int ch, int bd) -> uint32_t { return P.cpl.co[fidx * 80 + ch * 16 + bd]; }, (uint32_t)csnr, (uint32_t)fsnr);
+            pos = k.pos;
+        }
         PK_LAP(1);
 
         // ---- mantissas (:1341-1501): enc_mant.h ----
