@@ -15,5 +15,6 @@ from .engine import loudness_state_bytes, loudness_roles, loudness_tables, loudn
 from .engine import loudness_range_state_bytes, loudness_range_read  # noqa: F401
 from .engine import truepeak_state_bytes, truepeak_tables, truepeak_ceiling, truepeak_read, truepeak_host  # noqa: F401
 from .engine import limit_state_bytes, limit_release_step, limit_read, limit_host  # noqa: F401
+from .engine import ResampleDesc, resample_ratio, resample_tables, resample_state_bytes, resample_plan, resample_host  # noqa: F401
 from . import flags  # noqa: F401
 from . import sharding  # noqa: F401

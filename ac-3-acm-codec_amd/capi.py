@@ -72,6 +72,11 @@ class LoudnessDescC(ctypes.Structure):
     _fields_ = [("sample_rate", ctypes.c_int), ("channels", ctypes.c_int), ("role", ctypes.c_uint8 * 6)]
 
 
+class ResampleDescC(ctypes.Structure):
+    """ac3mi_resample_desc"""
+    _fields_ = [("in_rate", ctypes.c_int), ("out_rate", ctypes.c_int), ("channels", ctypes.c_int)]
+
+
 class LoudnessResultC(ctypes.Structure):
     """ac3mi_loudness_result"""
     _fields_ = [("mean_energy", ctypes.c_double), ("max_block_energy", ctypes.c_double), ("lkfs", ctypes.c_float),
@@ -254,6 +259,13 @@ def load_library():
     lib.ac3mi_limit_read_batch.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
     lib.ac3mi_limit_read.argtypes = [c_void_p, ctypes.POINTER(LimitResultC)]
     lib.ac3mi_limit_host.argtypes = [c_int, c_void_p, ctypes.c_uint32, ctypes.c_uint32, c_void_p, c_void_p, c_int, c_void_p]
+    lib.ac3mi_resample_ratio.argtypes = [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+    lib.ac3mi_resample_tables.argtypes = [c_int, c_int, c_void_p]
+    lib.ac3mi_resample_state_bytes.restype = c_size_t
+    lib.ac3mi_resample_state_bytes.argtypes = []
+    lib.ac3mi_resample_plan.argtypes = [c_int, c_int, ctypes.c_uint64, ctypes.c_uint64, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+    lib.ac3mi_resample_batch.argtypes = [c_void_p, ctypes.POINTER(ResampleDescC), c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]
+    lib.ac3mi_resample_host.argtypes = [ctypes.POINTER(ResampleDescC), c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.POINTER(ctypes.c_uint32)]
     lib.ac3mi_set_encode_drc.argtypes = [c_void_p, c_int, c_void_p]
     lib.ac3mi_set_encode_dynrng_frames.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.ac3mi_set_encode_drc_source.argtypes = [c_void_p, c_int]

@@ -323,6 +323,22 @@ bool limit_args_ok(const LimitLaunch &L);   // everything ac3mi_limit_batch refu
 hipError_t launch_limit(const LimitLaunch &L, hipStream_t stream);
 hipError_t launch_limit_read(const void *state, int n_streams, ac3mi_limit_result *results, hipStream_t stream);
 
+// resample.hip: the sample-rate converter (ac3mi_resample_*; the rule is include/ac3mi.h's, its steps resample_rule.h's).  tab: the
+// pair's table on the device as resample_packed_table writes it on the host, [L][taps / 2] pairs of dwords
+struct ResampleLaunch {
+    int in_rate, out_rate, channels;
+    const int16_t *pcm;             // [S][in_frames][1536][channels]
+    int16_t *out;                   // [S][out_frames][1536][channels]; may be null when out_frames is 0
+    int n_streams, in_frames, out_frames;
+    void *state;                    // [S] ResampleState
+    uint32_t *status;               // [S]
+    const uint32_t *tab;
+};
+bool resample_args_ok(const ResampleLaunch &L);     // everything ac3mi_resample_batch refuses, the context and the table apart
+// the pair's table in the kernel's form, L * taps dwords (null: only the count); 0: the pair's split does not pass its bound check
+size_t resample_packed_table(int in_rate, int out_rate, uint32_t *h_tab);
+hipError_t launch_resample(const ResampleLaunch &L, hipStream_t stream);
+
 struct EncodeLaunch {
     EncConfig cfg;
     const int16_t *pcm;         // [S][F][1536][nch]
@@ -456,6 +472,7 @@ struct ac3mi_ctx {
     int fixed_shape = 1;    // ac3mi_set_fixed_shape
     int32_t *debug_search_curve = nullptr;  // ac3mi_debug_search_curve
     ac3mi::LaunchLog launch_log;            // ac3mi_debug_launch_log (host memory; words null: no tap)
+    uint32_t *resample_tab[6] = {};  // ac3mi_resample_batch: a pair's table on the device, put there by the pair's first call, freed in ac3mi_destroy
     double *loud_tab = nullptr;     // ac3mi_loudness_*: bin edges and dialnorm thresholds on the device, put there by the first call (no workspace: it is a table)
     std::string err;
 };

@@ -4,6 +4,7 @@
 #include "a52_levels.h"
 #include "spec_tables.h"
 #include "sync_rule.h"
+#include "resample_rule.h"
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -511,6 +512,7 @@ void ac3mi_destroy(ac3mi_ctx *ctx)
     for (DevBuf *b : ac3mi_ctx::workspaces(ctx)) (void)hipFree(b->p);
     (void)hipFree(ctx->tab.enc);
     (void)hipFree(ctx->loud_tab);
+    for (uint32_t *t : ctx->resample_tab) (void)hipFree(t);
     (void)hipEventDestroy(ctx->ev0);
     (void)hipEventDestroy(ctx->ev1);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -1487,6 +1489,54 @@ int ac3mi_limit_read_batch(ac3mi_ctx *ctx, const void *d_state, int n_streams, a
     if (n_streams == 0) return AC3MI_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, launch_limit_read(d_state, n_streams, d_results, ctx->stream));
+    return AC3MI_OK;
+}
+
+// (ac3mi_resample_ratio, _tables, _state_bytes, _plan and _host, the host side, live in resample.hip beside the rule)
+static int resample_tab_ready(ac3mi_ctx *ctx, int in_rate, int out_rate, const uint32_t **tab)
+{
+    const int pair = rs_pair(in_rate, out_rate);
+    if (!ctx->resample_tab[pair]) {
+        std::vector<uint32_t> h(resample_packed_table(in_rate, out_rate, nullptr));
+        if (resample_packed_table(in_rate, out_rate, h.data()) == 0) {
+            ctx->err = "ac3mi_resample_batch: the pair's table does not pass its bound check";
+            return AC3MI_ERR_UNSUPPORTED;
+        }
+        uint32_t *d = nullptr;
+        if (hipMalloc((void **)&d, h.size() * 4) != hipSuccess) { ctx->err = "ac3mi_resample_batch: out of memory"; return AC3MI_ERR_HIP; }
+        hipError_t e = hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);       // h leaves scope
+        if (e != hipSuccess) { (void)hipFree(d); ctx->err = std::string("ac3mi_resample_batch: ") + hipGetErrorString(e); return AC3MI_ERR_HIP; }
+        ctx->resample_tab[pair] = d;
+    }
+    *tab = ctx->resample_tab[pair];
+    return AC3MI_OK;
+}
+
+int ac3mi_resample_batch(ac3mi_ctx *ctx, const ac3mi_resample_desc *desc, const int16_t *d_pcm, int n_streams, int in_frames,
+                         int16_t *d_out, int out_frames, void *d_state, uint32_t *d_status)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    ResampleLaunch L;
+    L.in_rate = desc ? desc->in_rate : 0;
+    L.out_rate = desc ? desc->out_rate : 0;
+    L.channels = desc ? desc->channels : 0;
+    L.pcm = d_pcm;
+    L.out = d_out;
+    L.n_streams = n_streams;
+    L.in_frames = in_frames;
+    L.out_frames = out_frames;
+    L.state = d_state;
+    L.status = d_status;
+    L.tab = nullptr;
+    if (!resample_args_ok(L)) {
+        ctx->err = "ac3mi_resample_batch: bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    if (n_streams == 0) return AC3MI_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = resample_tab_ready(ctx, L.in_rate, L.out_rate, &L.tab)) return rc;
+    HIPCHK(ctx, launch_resample(L, ctx->stream));
     return AC3MI_OK;
 }
 

@@ -241,6 +241,63 @@ def limit_host(roles, ceiling_q28, release_step_q24, pcm, state=None):
     return out, buf.raw
 
 
+ResampleDesc = capi.ResampleDescC
+
+
+def resample_ratio(in_rate, out_rate):
+    """ac3mi_resample_ratio: (L, M, taps per phase) of one of the six pairs of {32000, 44100, 48000}"""
+    L, M, T = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    if capi.load_library().ac3mi_resample_ratio(int(in_rate), int(out_rate), ctypes.byref(L), ctypes.byref(M), ctypes.byref(T)) != 0:
+        raise capi.AC3MIError("ac3mi_resample_ratio: bad argument")
+    return L.value, M.value, T.value
+
+
+def resample_tables(in_rate, out_rate):
+    """ac3mi_resample_tables: the pair's Q23 table, int32 [L][taps]"""
+    import numpy as np
+    L, _, T = resample_ratio(in_rate, out_rate)
+    coef = np.zeros((L, T), np.int32)
+    rc = capi.load_library().ac3mi_resample_tables(int(in_rate), int(out_rate), coef.ctypes.data)
+    if rc != 0:
+        raise capi.AC3MIError("ac3mi_resample_tables: %d" % rc)
+    return coef
+
+
+def resample_state_bytes():
+    """ac3mi_resample_state_bytes: bytes of one stream's converter state (all zeros: a new stream)"""
+    return int(capi.load_library().ac3mi_resample_state_bytes())
+
+
+def resample_plan(in_rate, out_rate, samples_in, frames_out, in_frames):
+    """ac3mi_resample_plan: (out_frames, pending_after) of a call that pushes in_frames frames to a stream of that age"""
+    of, left = ctypes.c_int(), ctypes.c_int()
+    if capi.load_library().ac3mi_resample_plan(int(in_rate), int(out_rate), int(samples_in), int(frames_out), int(in_frames),
+                                               ctypes.byref(of), ctypes.byref(left)) != 0:
+        raise capi.AC3MIError("ac3mi_resample_plan: bad argument")
+    return of.value, left.value
+
+
+def resample_host(desc, pcm, out_frames, state=None):
+    """ac3mi_resample_host, the host converter (no GPU): pcm int16 [n][channels] of ONE stream, n a multiple of 1536, on the
+    state's bytes (None: a new stream) -> (out int16 [out_frames * 1536][channels], the state's bytes, status).  desc: a
+    ResampleDesc or (in_rate, out_rate)."""
+    import numpy as np
+    lib = capi.load_library()
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+    if pcm.ndim != 2 or pcm.shape[0] % 1536:
+        raise ValueError("pcm is [frames * 1536][channels]")
+    if not isinstance(desc, capi.ResampleDescC):
+        desc = capi.ResampleDescC(int(desc[0]), int(desc[1]), int(pcm.shape[1]))
+    nb = lib.ac3mi_resample_state_bytes()
+    buf = ctypes.create_string_buffer(bytes(bytearray(state)) if state is not None else bytes(nb), nb)
+    out = np.full((int(out_frames) * 1536, pcm.shape[1]), 0x5a5a, np.int16)
+    status = ctypes.c_uint32(0xffffffff)
+    if lib.ac3mi_resample_host(ctypes.byref(desc), pcm.ctypes.data, pcm.shape[0] // 1536, out.ctypes.data if out.size else None,
+                               int(out_frames), buf, ctypes.byref(status)) != 0:
+        raise capi.AC3MIError("ac3mi_resample_host: bad argument")
+    return out, buf.raw, int(status.value)
+
+
 def encode_metadata_word(**fields):
     """ac3mi_encode_metadata_word: the fields of Engine.set_encode_metadata (those not given: the defaults) -> the packed
     word; raises on a field out of range."""
@@ -778,6 +835,35 @@ class Engine:
                                                ctypes.c_void_p(out.data_ptr()), int(S), int(F), ctypes.c_void_p(state.data_ptr())))
         self._keep.append((pcm, out, state))
         return out, state
+
+    def resample_batch(self, desc, pcm, out_frames, state=None, out=None, status=None, wait_torch=True):
+        """ac3mi_resample_batch: converts pcm [S][F][1536][channels] s16 on the device from desc.in_rate to desc.out_rate ->
+        (out [S][out_frames][1536][channels], state, status).  out_frames is what resample_plan gives for the streams' age;
+        state u8 [S][resample_state_bytes()] (zeros: new streams; default: allocated here); status u32 [S]: 0, or why a
+        stream was left untouched with zeros for output.  desc: a ResampleDesc or (in_rate, out_rate)."""
+        import torch
+        assert pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.is_cuda and pcm.dim() == 4 and pcm.shape[2] == 1536
+        S, F, _, nch = pcm.shape
+        if not isinstance(desc, capi.ResampleDescC):
+            desc = capi.ResampleDescC(int(desc[0]), int(desc[1]), int(nch))
+        if desc.channels != nch:
+            raise ValueError("desc.channels is pcm's last dimension")
+        nb = int(self.lib.ac3mi_resample_state_bytes())
+        if state is None:
+            state = torch.zeros((S, nb), dtype=torch.uint8, device=pcm.device)
+        if out is None:
+            out = torch.empty((S, int(out_frames), 1536, nch), dtype=torch.int16, device=pcm.device)
+        if status is None:
+            status = torch.zeros((S,), dtype=torch.int32, device=pcm.device)
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == S * nb
+        assert out.dtype == torch.int16 and out.is_contiguous() and out.is_cuda and out.numel() == S * int(out_frames) * 1536 * nch
+        assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() == S
+        self._drain_torch(wait_torch)
+        self._check(self.lib.ac3mi_resample_batch(ctypes.c_void_p(self.ctx), ctypes.byref(desc), ctypes.c_void_p(pcm.data_ptr()), int(S),
+                                                  int(F), ctypes.c_void_p(out.data_ptr()) if out.numel() else None, int(out_frames),
+                                                  ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(status.data_ptr())))
+        self._keep.append((pcm, out, state, status))
+        return out, state, status
 
     def limit_read_batch(self, state, out=None, wait_torch=True):
         """ac3mi_limit_read_batch: state u8 [S][limit_state_bytes()] -> results u8 [S][40];

@@ -618,6 +618,88 @@ int ac3mi_limit_read(const void *h_state, ac3mi_limit_result *out);
 int ac3mi_limit_host(int channels, const uint8_t *role, uint32_t ceiling_q28, uint32_t release_step_q24,
                      const int16_t *h_pcm, int16_t *h_out, int frames, void *h_state);
 
+/* A sample-rate converter on the device (new): the stage that takes the same s16 PCM between the three AC-3 rates, between
+ * ac3mi_decode_s16_batch and ac3mi_encode_batch, with its state carried per stream from call to call like the limiter's.  A
+ * rational-ratio polyphase FIR.  The whole rule; every bit is decided by integers, floats appear only in the table's design:
+ *   pairs      the six ordered pairs of {32000, 44100, 48000}.  g = gcd(in_rate, out_rate), L = out_rate / g, M = in_rate / g;
+ *              T, the taps per phase in input samples, is 64 when L > M, else 64 M / L rounded up to a multiple of 8:
+ *                44.1->48  160/147  64     48->44.1  147/160  72     32->48  3/2  64
+ *                48->32    2/3      96     32->44.1  441/320  64     44.1->32  320/441  96
+ *   table      C[L][T], int32, Q23, designed once per pair on the host in double, in exactly this order of operations:
+ *                r = min(1.0, (double)L / M);  beta = 9.2;  for p = 0..L-1, k = 0..T-1:
+ *                t = (k + (double)p / L) - T / 2
+ *                a = r * t;   sinc = (a == 0) ? 1 : sin(pi * a) / (pi * a)
+ *                q = (2 * t) / T;   u = 1 - q * q;   w = I0(beta * sqrt(max(u, 0))) / I0(beta)
+ *                  I0(x): s = term = 1; for j = 1, 2, ..: v = x / 2 / j; term *= v * v; s += term; stop when term < 1e-21 * s
+ *                h = (r * sinc) * w
+ *                C[p][k] = floor(8388608 * h + 0.5)
+ *              then per phase p, 8388608 - sum over k of C[p][k] is added to the first largest C[p][k]: every phase has unit gain
+ *              at DC, exactly.  A Kaiser-windowed sinc that cuts at the lower of the two Nyquist frequencies (pass band flat
+ *              within 0.001 dB to 0.907 of it, -90 dB from 1.093 of it); its delay is T / 2 input samples.
+ *   signal     per slot c; n counts the stream's input instants over all calls, x_c[n] = 0 for n < 0; m counts output instants:
+ *                i = floor(m * M / L),  p = (m * M) mod L                       (64-bit integers)
+ *                acc = sum over k = 0..T-1 of C[p][k] * x_c[i - k]              (|acc| < 2^41)
+ *                y_c[m] = clamp((acc + 2^22) >> 23, -32768, 32767)              (arithmetic shift: floor; a windowed sinc overshoots)
+ *              After n input instants exactly ceil(n * L / M) output instants exist: those with i(m) <= n - 1.
+ *   32 bits    with hi = (C + 256) >> 9 and lo = C - 512 * hi, acc = 512 * sum(hi * x) + sum(lo * x).  The table's builder checks
+ *              that every hi fits an int16 and that neither sum of |hi| nor of |lo| over a phase exceeds 65535, so that both
+ *              sums fit an int32 for every input (on the six tables: at most 45658 and 14220), and refuses the pair with
+ *              AC3MI_ERR_UNSUPPORTED otherwise.
+ *   elastic    input and output of a call are whole 1536-instant frames; the output instants that do not fill a frame yet stay
+ *   buffer     in the state as `pending`, 0..1535 of them.  A call pushes in_frames frames and takes out_frames per stream; with
+ *              n = samples_in and f = frames_out before it:
+ *                total = ceil((n + 1536 * in_frames) * L / M) - 1536 * f        (pending before + new)
+ *                the call is valid for the stream iff out_frames == total / 1536 (integer division)
+ *                pending after = total - 1536 * out_frames;  samples_in += 1536 * in_frames;  frames_out += out_frames
+ *              out_frames depends on the stream's age alone (ac3mi_resample_plan; one-frame calls at 44.1->48 take 1 frame
+ *              eleven times, then 2; 147 frames in give exactly 160 out with nothing pending).  A stream for which the call is
+ *              not valid gets d_status AC3MI_RESAMPLE_FRAMES, a stream whose state was started with another pair or channel
+ *              count AC3MI_RESAMPLE_STATE: its state stays byte for byte and its out_frames output frames are zeros; the rest
+ *              of the batch proceeds.
+ *   scope      every slot is converted with the same table, an LFE included: no roles.  No dither: the output is the rounded
+ *              sum.  The first T / 2 * L / M output instants of a stream are the filter's rise, and its last T / 2 input
+ *              instants and the pending tail stay in the state: a caller who wants them feeds frames of zeros.  There is no
+ *              flush call.  Half and quarter rates (bsid 9 / 10) and equal rates are AC3MI_ERR_ARG.
+ *   state      samples_in and frames_out, u64; a byte that names the pair and the channel count (0 = new); the last 96 input
+ *              samples of each of 6 slots (the longest filter reads 95); 1536 x 6 pending samples, interleaved by the call's
+ *              channel count, zero from the pending count on.  Only the call's `channels` share is read or written.
+ * The output and the state are the same bits for every way of cutting a stream into calls, for either alignment of the
+ * buffers, and on the host twin, which runs the same rule code instant by instant. */
+typedef struct { int in_rate; int out_rate; int channels; } ac3mi_resample_desc;
+#define AC3MI_RESAMPLE_FRAMES 1     /* d_status: out_frames is not this stream's whole-frame count; stream untouched, output zeros */
+#define AC3MI_RESAMPLE_STATE 2      /* d_status: the state belongs to another pair / channel count; same treatment */
+
+/* L, M and the taps per phase of a pair (any of the three may be NULL).  AC3MI_ERR_ARG for anything but the six pairs.  Host,
+ * no context. */
+int ac3mi_resample_ratio(int in_rate, int out_rate, int *L, int *M, int *taps);
+/* The pair's table C[L][taps], row-major, as the converter uses it.  Host, no context. */
+int ac3mi_resample_tables(int in_rate, int out_rate, int32_t *coef);
+/* Bytes of one stream's state.  Opaque, in the caller's device memory, d_state[n_streams] records of this size (8-byte
+ * aligned); all zeros is a new stream. */
+size_t ac3mi_resample_state_bytes(void);
+/* The elastic buffer's arithmetic for a stream that has pushed samples_in instants and taken frames_out frames: the out_frames
+ * a call with in_frames must ask for, and what is pending behind it (either may be NULL).  AC3MI_ERR_ARG: not one of the six
+ * pairs, in_frames outside 1..2^20, or counters that no sequence of valid calls leaves.  Host, no context. */
+int ac3mi_resample_plan(int in_rate, int out_rate, uint64_t samples_in, uint64_t frames_out, int in_frames, int *out_frames,
+                        int *pending_after);
+/* Converts in_frames more frames of every stream, one workgroup per stream, asynchronous on the context's stream.
+ * d_pcm [n_streams][in_frames][1536][channels], d_out [n_streams][out_frames][1536][channels], both 2-byte aligned (what lies
+ * between 16-byte boundaries is moved with 16-byte accesses; every alignment gives the same bits); d_out may be NULL when
+ * out_frames is 0.  d_status[n_streams] (4-byte aligned) is written for every
+ * stream, 0 when it is fine.  Nothing outside the two arrays, the states and d_status is touched.  AC3MI_ERR_ARG, with states
+ * and output untouched: a NULL desc, a rate outside the three, equal rates, channels outside 1..6, in_frames outside 1..2^20,
+ * out_frames outside 0..2^20, n_streams < 0, a NULL or misaligned pointer, any overlap of d_pcm and d_out.  n_streams 0:
+ * AC3MI_OK, nothing is launched.  A pair's first call on a context builds the pair's table and copies it to device memory
+ * (an allocation and a synchronous copy: not inside a graph capture; make one call per pair before capturing); ac3mi_destroy
+ * frees it. */
+int ac3mi_resample_batch(ac3mi_ctx *ctx, const ac3mi_resample_desc *desc, const int16_t *d_pcm, int n_streams, int in_frames,
+                         int16_t *d_out, int out_frames, void *d_state, uint32_t *d_status);
+/* Host twin of the converter, no GPU and no context: ONE stream, h_pcm [in_frames][1536][channels] and h_out
+ * [out_frames][1536][channels], output instant by output instant on a state in host memory (any alignment); *status as
+ * d_status.  The same errors. */
+int ac3mi_resample_host(const ac3mi_resample_desc *desc, const int16_t *h_pcm, int in_frames, int16_t *h_out, int out_frames,
+                        void *h_state, uint32_t *status);
+
 /* How ac3mi_encode_batch / ac3mi_transcode_batch pack a frame once its SNR offsets are found (new; same bytes either way -
  * the searches always run first, one wavefront per stream, frames in order):
  *   1  one wavefront per frame packs it;
