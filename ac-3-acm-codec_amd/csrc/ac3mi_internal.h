@@ -289,6 +289,7 @@ struct LoudnessLaunch {
     const double *tab;
     void *range_state = nullptr;    // [S] RangeState: the range meter beside it (ac3mi_loudness_range_batch); nullptr: the plain meter
 };
+bool loudness_args_ok(const LoudnessLaunch &L);     // everything ac3mi_loudness_batch and _range_batch refuse, the context and the table apart
 hipError_t launch_loudness(const LoudnessLaunch &L, hipStream_t stream);
 hipError_t launch_loudness_read(const void *state, int n_streams, const double *tab, ac3mi_loudness_result *results, hipStream_t stream);
 hipError_t launch_loudness_range_read(const void *range_state, int n_streams, const double *tab, ac3mi_loudness_range_result *results,
@@ -305,6 +306,7 @@ struct TruePeakLaunch {
     int n_streams, frames_per_stream;
     void *state;                    // [S] TruePeakState
 };
+bool truepeak_args_ok(const TruePeakLaunch &L);     // everything ac3mi_truepeak_batch refuses, the context apart
 hipError_t launch_truepeak(const TruePeakLaunch &L, hipStream_t stream);
 hipError_t launch_truepeak_read(const void *state, int n_streams, uint32_t ceiling_q28, ac3mi_truepeak_result *results, hipStream_t stream);
 

@@ -5,6 +5,7 @@
 #include "spec_tables.h"
 #include "sync_rule.h"
 #include "resample_rule.h"
+#include "pcm_lanes.h"
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -418,6 +419,34 @@ __global__ __launch_bounds__(256) void mixed_probe_kernel(uint32_t *out, int ite
     if ((a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ s0 ^ s1 ^ s2 ^ s3) == 0x12345678u) out[0] = a0;
 }
 }  // namespace ac3mi
+
+// A table in device memory, put there by the first call of a context that needs it (*slot; freed in ac3mi_destroy)
+template <class T>
+static int upload_table_once(ac3mi_ctx *ctx, const char *who, const T *h, size_t bytes, T **slot)
+{
+    if (*slot) return AC3MI_OK;
+    T *d = nullptr;
+    if (hipMalloc((void **)&d, bytes) != hipSuccess) { ctx->err = std::string(who) + ": out of memory"; return AC3MI_ERR_HIP; }
+    hipError_t e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);       // h leaves scope
+    if (e != hipSuccess) { (void)hipFree(d); ctx->err = std::string(who) + ": " + hipGetErrorString(e); return AC3MI_ERR_HIP; }
+    *slot = d;
+    return AC3MI_OK;
+}
+
+// The device read-out of a PCM tool: [n_streams] states -> [n_streams] records; launch() does what lies behind the checks
+template <class F>
+static int read_batch(ac3mi_ctx *ctx, const char *who, const void *d_state, int n_streams, const void *d_results, const F &launch)
+{
+    if (!ctx) return AC3MI_ERR_ARG;
+    if (!d_state || !d_results || n_streams < 0 || ((uintptr_t)d_state & 7) || ((uintptr_t)d_results & 7)) {
+        ctx->err = std::string(who) + ": bad argument";
+        return AC3MI_ERR_ARG;
+    }
+    if (n_streams == 0) return AC3MI_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return launch();
+}
 
 extern "C" {
 
@@ -1324,13 +1353,7 @@ static int loud_tab_ready(ac3mi_ctx *ctx, const char *who)
     if (ctx->loud_tab) return AC3MI_OK;
     double h[LOUD_TAB_DOUBLES];
     loud_fill_tab(h);
-    double *d = nullptr;
-    if (hipMalloc((void **)&d, sizeof h) != hipSuccess) { ctx->err = std::string(who) + ": out of memory"; return AC3MI_ERR_HIP; }
-    hipError_t e = hipMemcpyAsync(d, h, sizeof h, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);       // h leaves scope
-    if (e != hipSuccess) { (void)hipFree(d); ctx->err = std::string(who) + ": " + hipGetErrorString(e); return AC3MI_ERR_HIP; }
-    ctx->loud_tab = d;
-    return AC3MI_OK;
+    return upload_table_once(ctx, who, h, sizeof h, &ctx->loud_tab);
 }
 
 // the plain meter (d_range_state nullptr, with_range false) and the one that meters the range beside it
@@ -1338,27 +1361,24 @@ static int loudness_batch(ac3mi_ctx *ctx, const char *who, const ac3mi_loudness_
                           int frames_per_stream, void *d_state, void *d_range_state, bool with_range)
 {
     if (!ctx) return AC3MI_ERR_ARG;
-    bool ok = desc && d_pcm && d_state && n_streams >= 0 && frames_per_stream >= 1 && !((uintptr_t)d_pcm & 1) && !((uintptr_t)d_state & 7);
-    ok = ok && (!with_range || (d_range_state && !((uintptr_t)d_range_state & 7)));
-    ok = ok && (desc->sample_rate == 48000 || desc->sample_rate == 44100 || desc->sample_rate == 32000) && desc->channels >= 1 && desc->channels <= 6;
-    for (int c = 0; ok && c < desc->channels; c++) ok = desc->role[c] <= 2;
-    if (!ok) {
+    LoudnessLaunch L;
+    L.pcm = d_pcm;
+    L.sample_rate = desc ? desc->sample_rate : 0;
+    L.channels = desc ? desc->channels : 0;
+    pcm_copy_roles(L.role, desc ? desc->role : nullptr, L.channels);
+    L.n_streams = n_streams;
+    L.frames_per_stream = frames_per_stream;
+    L.state = d_state;
+    L.tab = nullptr;
+    L.range_state = with_range ? d_range_state : nullptr;
+    if ((with_range && !d_range_state) || !loudness_args_ok(L)) {
         ctx->err = std::string(who) + ": bad argument";
         return AC3MI_ERR_ARG;
     }
     if (n_streams == 0) return AC3MI_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (int rc = loud_tab_ready(ctx, who)) return rc;
-    LoudnessLaunch L;
-    L.pcm = d_pcm;
-    L.sample_rate = desc->sample_rate;
-    L.channels = desc->channels;
-    for (int c = 0; c < 6; c++) L.role[c] = c < desc->channels ? desc->role[c] : 0;
-    L.n_streams = n_streams;
-    L.frames_per_stream = frames_per_stream;
-    L.state = d_state;
     L.tab = ctx->loud_tab;
-    L.range_state = with_range ? d_range_state : nullptr;
     HIPCHK(ctx, launch_loudness(L, ctx->stream));
     return AC3MI_OK;
 }
@@ -1377,30 +1397,20 @@ int ac3mi_loudness_range_batch(ac3mi_ctx *ctx, const ac3mi_loudness_desc *desc, 
 
 int ac3mi_loudness_range_read_batch(ac3mi_ctx *ctx, const void *d_range_state, int n_streams, ac3mi_loudness_range_result *d_results)
 {
-    if (!ctx) return AC3MI_ERR_ARG;
-    if (!d_range_state || !d_results || n_streams < 0 || ((uintptr_t)d_range_state & 7) || ((uintptr_t)d_results & 7)) {
-        ctx->err = "ac3mi_loudness_range_read_batch: bad argument";
-        return AC3MI_ERR_ARG;
-    }
-    if (n_streams == 0) return AC3MI_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (int rc = loud_tab_ready(ctx, "ac3mi_loudness_range_read_batch")) return rc;
-    HIPCHK(ctx, launch_loudness_range_read(d_range_state, n_streams, ctx->loud_tab, d_results, ctx->stream));
-    return AC3MI_OK;
+    return read_batch(ctx, "ac3mi_loudness_range_read_batch", d_range_state, n_streams, d_results, [&]() -> int {
+        if (int rc = loud_tab_ready(ctx, "ac3mi_loudness_range_read_batch")) return rc;
+        HIPCHK(ctx, launch_loudness_range_read(d_range_state, n_streams, ctx->loud_tab, d_results, ctx->stream));
+        return AC3MI_OK;
+    });
 }
 
 int ac3mi_loudness_read_batch(ac3mi_ctx *ctx, const void *d_state, int n_streams, ac3mi_loudness_result *d_results)
 {
-    if (!ctx) return AC3MI_ERR_ARG;
-    if (!d_state || !d_results || n_streams < 0 || ((uintptr_t)d_state & 7) || ((uintptr_t)d_results & 7)) {
-        ctx->err = "ac3mi_loudness_read_batch: bad argument";
-        return AC3MI_ERR_ARG;
-    }
-    if (n_streams == 0) return AC3MI_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (int rc = loud_tab_ready(ctx, "ac3mi_loudness_read_batch")) return rc;
-    HIPCHK(ctx, launch_loudness_read(d_state, n_streams, ctx->loud_tab, d_results, ctx->stream));
-    return AC3MI_OK;
+    return read_batch(ctx, "ac3mi_loudness_read_batch", d_state, n_streams, d_results, [&]() -> int {
+        if (int rc = loud_tab_ready(ctx, "ac3mi_loudness_read_batch")) return rc;
+        HIPCHK(ctx, launch_loudness_read(d_state, n_streams, ctx->loud_tab, d_results, ctx->stream));
+        return AC3MI_OK;
+    });
 }
 
 int ac3mi_loudness_words_batch(ac3mi_ctx *ctx, const ac3mi_loudness_result *d_results, int n_streams, int frames_per_stream,
@@ -1423,35 +1433,29 @@ int ac3mi_truepeak_batch(ac3mi_ctx *ctx, int channels, const uint8_t *role, cons
                          int frames_per_stream, void *d_state)
 {
     if (!ctx) return AC3MI_ERR_ARG;
-    if (channels < 1 || channels > 6 || !role || !d_pcm || !d_state || n_streams < 0 || frames_per_stream < 1 || ((uintptr_t)d_pcm & 1) ||
-        ((uintptr_t)d_state & 7)) {
+    TruePeakLaunch L;
+    L.pcm = d_pcm;
+    L.channels = channels;
+    pcm_copy_roles(L.role, role, channels);
+    L.n_streams = n_streams;
+    L.frames_per_stream = frames_per_stream;
+    L.state = d_state;
+    if (!role || !truepeak_args_ok(L)) {
         ctx->err = "ac3mi_truepeak_batch: bad argument";
         return AC3MI_ERR_ARG;
     }
     if (n_streams == 0) return AC3MI_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    TruePeakLaunch L;
-    L.pcm = d_pcm;
-    L.channels = channels;
-    for (int c = 0; c < 6; c++) L.role[c] = c < channels ? role[c] : 0;
-    L.n_streams = n_streams;
-    L.frames_per_stream = frames_per_stream;
-    L.state = d_state;
     HIPCHK(ctx, launch_truepeak(L, ctx->stream));
     return AC3MI_OK;
 }
 
 int ac3mi_truepeak_read_batch(ac3mi_ctx *ctx, const void *d_state, int n_streams, uint32_t ceiling_q28, ac3mi_truepeak_result *d_results)
 {
-    if (!ctx) return AC3MI_ERR_ARG;
-    if (!d_state || !d_results || n_streams < 0 || ((uintptr_t)d_state & 7) || ((uintptr_t)d_results & 7)) {
-        ctx->err = "ac3mi_truepeak_read_batch: bad argument";
-        return AC3MI_ERR_ARG;
-    }
-    if (n_streams == 0) return AC3MI_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, launch_truepeak_read(d_state, n_streams, ceiling_q28, d_results, ctx->stream));
-    return AC3MI_OK;
+    return read_batch(ctx, "ac3mi_truepeak_read_batch", d_state, n_streams, d_results, [&]() -> int {
+        HIPCHK(ctx, launch_truepeak_read(d_state, n_streams, ceiling_q28, d_results, ctx->stream));
+        return AC3MI_OK;
+    });
 }
 
 // (ac3mi_limit_state_bytes, _release_step, _read and _host, the host side, live in limit.hip beside the rule)
@@ -1463,7 +1467,7 @@ int ac3mi_limit_batch(ac3mi_ctx *ctx, int channels, const uint8_t *role, uint32_
     L.pcm = d_pcm;
     L.out = d_out;
     L.channels = channels;
-    for (int c = 0; c < 6; c++) L.role[c] = role && c < channels ? role[c] : 0;
+    pcm_copy_roles(L.role, role, channels);
     L.ceiling_q28 = ceiling_q28;
     L.release_step_q24 = release_step_q24;
     L.n_streams = n_streams;
@@ -1481,35 +1485,25 @@ int ac3mi_limit_batch(ac3mi_ctx *ctx, int channels, const uint8_t *role, uint32_
 
 int ac3mi_limit_read_batch(ac3mi_ctx *ctx, const void *d_state, int n_streams, ac3mi_limit_result *d_results)
 {
-    if (!ctx) return AC3MI_ERR_ARG;
-    if (!d_state || !d_results || n_streams < 0 || ((uintptr_t)d_state & 7) || ((uintptr_t)d_results & 7)) {
-        ctx->err = "ac3mi_limit_read_batch: bad argument";
-        return AC3MI_ERR_ARG;
-    }
-    if (n_streams == 0) return AC3MI_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, launch_limit_read(d_state, n_streams, d_results, ctx->stream));
-    return AC3MI_OK;
+    return read_batch(ctx, "ac3mi_limit_read_batch", d_state, n_streams, d_results, [&]() -> int {
+        HIPCHK(ctx, launch_limit_read(d_state, n_streams, d_results, ctx->stream));
+        return AC3MI_OK;
+    });
 }
 
 // (ac3mi_resample_ratio, _tables, _state_bytes, _plan and _host, the host side, live in resample.hip beside the rule)
 static int resample_tab_ready(ac3mi_ctx *ctx, int in_rate, int out_rate, const uint32_t **tab)
 {
-    const int pair = rs_pair(in_rate, out_rate);
-    if (!ctx->resample_tab[pair]) {
+    uint32_t **slot = &ctx->resample_tab[rs_pair(in_rate, out_rate)];
+    if (!*slot) {
         std::vector<uint32_t> h(resample_packed_table(in_rate, out_rate, nullptr));
         if (resample_packed_table(in_rate, out_rate, h.data()) == 0) {
             ctx->err = "ac3mi_resample_batch: the pair's table does not pass its bound check";
             return AC3MI_ERR_UNSUPPORTED;
         }
-        uint32_t *d = nullptr;
-        if (hipMalloc((void **)&d, h.size() * 4) != hipSuccess) { ctx->err = "ac3mi_resample_batch: out of memory"; return AC3MI_ERR_HIP; }
-        hipError_t e = hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);       // h leaves scope
-        if (e != hipSuccess) { (void)hipFree(d); ctx->err = std::string("ac3mi_resample_batch: ") + hipGetErrorString(e); return AC3MI_ERR_HIP; }
-        ctx->resample_tab[pair] = d;
+        if (int rc = upload_table_once(ctx, "ac3mi_resample_batch", h.data(), h.size() * 4, slot)) return rc;
     }
-    *tab = ctx->resample_tab[pair];
+    *tab = *slot;
     return AC3MI_OK;
 }
 

@@ -2,11 +2,10 @@
 // steps and the state's layout are limit_rule.h's, the interpolator truepeak_rule.h's).
 //
 // limit_kernel: one wavefront per stream, four per workgroup, the stream's frames in order; integers throughout.  A frame is 64
-// segments of 24 sample instants, one per lane, as in truepeak_kernel:
-//   load        lane l's 24 instants: 16-byte loads when both bases are 16-byte aligned, else 16-bit loads (same bits)
-//   detect      per detected slot the 11 instants before the segment come from the left neighbour's registers (lane 0: from
-//               the carried dwords), the four phases by packed 16-bit dot products (truepeak_packed.h); d[n] also takes the
-//               two samples beside the phases, which are the halves of one of the pairs
+// segments of 24 sample instants, one per lane (pcm_lanes.h), as in truepeak_kernel:
+//   load        pcm_load_segment, the 16-byte form when both bases are 16-byte aligned
+//   detect      per detected slot tp_pairs and the four phases by packed 16-bit dot products (truepeak_packed.h); d[n] also
+//               takes the two samples beside the phases, which are the halves of one of the pairs
 //   q           d goes to the wavefront's q line in LDS (1536 entries behind the 79 carried ones); one loop that is not
 //               unrolled replaces each by lim_quot - a single copy of the 64-bit division, which runs only where d > C
 //   m           a lane-local pass over its 24 + 79 entries: the 57 that all its windows share, then suffix and prefix minima
@@ -14,8 +13,8 @@
 //               value - position * R (an int32 given R <= 2^20, limit_rule.h), the left neighbour's exit is the lane's entry
 //   g           r goes to the r line (1536 behind the 63 carried); a sliding sum over 64 + 23 entries
 //   apply       the delayed samples x[n - 77] are lanes l - 4 and l - 3's registers, one lane shift per dword (lanes 0..3:
-//               the dwords lanes 60..63 left in LDS the frame before); lim_apply; the lane stores the 24 instants it loaded,
-//               so an in-place call never reads what it has overwritten
+//               the dwords lanes 60..63 left in LDS the frame before); lim_apply; pcm_store_segment: the lane stores the 24
+//               instants it loaded, so an in-place call never reads what it has overwritten
 // Both lines are padded by one entry in 24 (entry j at j + j / 24): lane l's entries start at 25 l, and a pass in which every
 // lane reads its k-th entry meets no bank twice.  Nothing waits on another wavefront; every loop is bounded by the frame count
 // or a constant; no atomics; plain vector stores.
@@ -92,26 +91,13 @@ struct LimitParams {
     uint8_t role[8];
 };
 
-// One detected slot of one frame in one lane: d[i] takes the slot's share (lim_detect's value, from packed pairs).  own = the
-// lane's 24 instants as dwords [24][NCH]; carry = the 12 instants before the frame as dwords [12][NCH] in LDS
+// One detected slot of one frame in one lane: d[i] takes the slot's share (lim_detect's value, from packed pairs).  own, carry:
+// tp_pairs', the carried dwords in LDS
 template <int NCH, int C>
 __device__ __forceinline__ void lim_slot(const uint32_t *own, const uint32_t *carry, int lane, uint32_t *d)
 {
-    constexpr int HW = 6 * NCH;
-    uint32_t h[TP_HIST];                // the dwords with instants -11 .. -1 of this slot
-#pragma unroll
-    for (int j = 0; j < TP_HIST; j++) {
-        const int k = ((j + 1) * NCH + C) >> 1;
-        const uint32_t left = __shfl_up(own[HW + k], 1u);
-        h[j] = lane == 0 ? carry[k] : left;
-    }
-    uint32_t q[TP_HIST + TP_SEG - 1];   // the pairs of instants (-11, -10) .. (22, 23)
-#pragma unroll
-    for (int j = 0; j < TP_HIST + TP_SEG - 1; j++) {
-        const int a = (j + 1) * NCH + C, b = a + NCH;
-        const uint32_t wa = j < TP_HIST ? h[j] : own[(a >> 1) - HW], wb = j + 1 < TP_HIST ? h[j + 1] : own[(b >> 1) - HW];
-        q[j] = tp_pack(wa, a & 1, wb, b & 1);
-    }
+    uint32_t q[TP_HIST + TP_SEG - 1];
+    tp_pairs<NCH, C>(own, carry, lane, q);
 #pragma unroll
     for (int i = 0; i < TP_SEG; i++) {
         int32_t y[TP_PHASES];
@@ -122,15 +108,6 @@ __device__ __forceinline__ void lim_slot(const uint32_t *own, const uint32_t *ca
 #pragma unroll
         for (int p = 0; p < TP_PHASES; p++) a = tp_abs(y[p]) > a ? tp_abs(y[p]) : a;
         d[i] = a > d[i] ? a : d[i];
-    }
-}
-
-template <int NCH, int C>
-__device__ __forceinline__ void lim_slots(const uint8_t *role, const uint32_t *own, const uint32_t *carry, int lane, uint32_t *d)
-{
-    if constexpr (C < NCH) {
-        if (role[C] != 0) lim_slot<NCH, C>(own, carry, lane, d);
-        lim_slots<NCH, C + 1>(role, own, carry, lane, d);
     }
 }
 
@@ -149,7 +126,7 @@ __global__ __launch_bounds__(64 * LIM_WAVES, LIM_MIN_WAVES) void limit_kernel(co
     constexpr int HW = 6 * NCH, NW = 12 * NCH;      // dwords of 12 instants, of a lane's 24
     __shared__ uint32_t s_q[LIM_WAVES][LIM_Q_WORDS], s_r[LIM_WAVES][LIM_R_WORDS], s_kept[LIM_WAVES][4 * NW];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned s = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * LIM_WAVES + wv));
+    const unsigned s = pcm_wave_stream(LIM_WAVES);
     if (s >= P.n_streams) return;
     uint32_t *lq = s_q[wv], *lr = s_r[wv], *kept = s_kept[wv];
     LimitState *st = P.state + s;
@@ -177,25 +154,16 @@ __global__ __launch_bounds__(64 * LIM_WAVES, LIM_MIN_WAVES) void limit_kernel(co
     const size_t at = (size_t)s * (size_t)P.frames * (1536 * NCH) + lane * (TP_SEG * NCH);
     for (int f = 0; f < P.frames; f++) {
         const int16_t *fp = P.pcm + at + (size_t)f * (1536 * NCH);
-        if constexpr (VEC) {
-            const uint4 *v = reinterpret_cast<const uint4 *>(fp);
-#pragma unroll
-            for (int k = 0; k < 3 * NCH; k++) {
-                const uint4 t = v[k];
-                w[4 * k] = t.x; w[4 * k + 1] = t.y; w[4 * k + 2] = t.z; w[4 * k + 3] = t.w;
-            }
-        } else {
-            const uint16_t *h = reinterpret_cast<const uint16_t *>(fp);
-#pragma unroll
-            for (int k = 0; k < NW; k++) w[k] = (uint32_t)h[2 * k] | ((uint32_t)h[2 * k + 1] << 16);
-        }
+        pcm_load_segment<NCH, VEC>(fp, w);
 
         // d, then q in place in the line
         {
             uint32_t d[TP_SEG];
 #pragma unroll
             for (int i = 0; i < TP_SEG; i++) d[i] = 0;
-            lim_slots<NCH, 0>(P.role, w, kept + 3 * NW + HW, lane, d);
+            pcm_for_each_slot<NCH>(P.role, [&](auto c) __attribute__((always_inline)) {
+                lim_slot<NCH, decltype(c)::value>(w, kept + 3 * NW + HW, lane, d);
+            });
 #pragma unroll
             for (int i = 0; i < TP_SEG; i++) {
                 lq[B + lim_pos(LIM_Q_CARRY + i)] = d[i];
@@ -293,19 +261,7 @@ __global__ __launch_bounds__(64 * LIM_WAVES, LIM_MIN_WAVES) void limit_kernel(co
             }
             z[k] = half[0] | (half[1] << 16);
         }
-        int16_t *op = P.out + at + (size_t)f * (1536 * NCH);
-        if constexpr (VEC) {
-            uint4 *v = reinterpret_cast<uint4 *>(op);
-#pragma unroll
-            for (int k = 0; k < 3 * NCH; k++) v[k] = make_uint4(z[4 * k], z[4 * k + 1], z[4 * k + 2], z[4 * k + 3]);
-        } else {
-            uint16_t *h = reinterpret_cast<uint16_t *>(op);
-#pragma unroll
-            for (int k = 0; k < NW; k++) {
-                h[2 * k] = (uint16_t)z[k];
-                h[2 * k + 1] = (uint16_t)(z[k] >> 16);
-            }
-        }
+        pcm_store_segment<NCH, VEC>(P.out + at + (size_t)f * (1536 * NCH), z);
 
         // hand over: the lines' last 79 and 63 entries become the carried ones, lanes 60..63 leave their dwords
         const uint32_t q0 = lq[lim_pos(1536 + lane)], q1 = lane < LIM_Q_CARRY - 64 ? lq[lim_pos(1536 + 64 + lane)] : 0u;
@@ -330,7 +286,7 @@ __global__ __launch_bounds__(64 * LIM_WAVES, LIM_MIN_WAVES) void limit_kernel(co
             const int j = TP_SEG * (lane - 60) + i - (96 - LIM_HIST);
             if (j >= 0) {
 #pragma unroll
-                for (int c = 0; c < NCH; c++) st->hist[c][j] = (int16_t)tp_sample<NCH>(w, i, c);
+                for (int c = 0; c < NCH; c++) st->hist[c][j] = (int16_t)pcm_sample<NCH>(w, i, c);
             }
         }
     }
@@ -357,18 +313,9 @@ __global__ __launch_bounds__(256) void limit_read_kernel(const LimitState *state
     lim_result(state + s, results + s);
 }
 
-template <int NCH>
-static void lim_launch_nch(const LimitParams &P, bool vec, hipStream_t stream)
-{
-    const dim3 grid((P.n_streams + LIM_WAVES - 1) / LIM_WAVES), block(64 * LIM_WAVES);
-    if (vec) hipLaunchKernelGGL((limit_kernel<NCH, true>), grid, block, 0, stream, P);
-    else hipLaunchKernelGGL((limit_kernel<NCH, false>), grid, block, 0, stream, P);
-}
-
 hipError_t launch_limit(const LimitLaunch &L, hipStream_t stream)
 {
     if (!limit_args_ok(L)) return hipErrorInvalidValue;
-    if (L.n_streams == 0) return hipSuccess;
     LimitParams P;
     P.pcm = L.pcm;
     P.out = L.out;
@@ -377,25 +324,19 @@ hipError_t launch_limit(const LimitLaunch &L, hipStream_t stream)
     P.frames = L.frames_per_stream;
     P.ceiling = L.ceiling_q28;
     P.step = L.release_step_q24;
-    for (int c = 0; c < 8; c++) P.role[c] = c < L.channels ? L.role[c] : 0;
-    const bool vec = (((uintptr_t)L.pcm | (uintptr_t)L.out) & 15) == 0;     // every frame and every lane's segment then is
-    switch (L.channels) {
-    case 1: lim_launch_nch<1>(P, vec, stream); break;
-    case 2: lim_launch_nch<2>(P, vec, stream); break;
-    case 3: lim_launch_nch<3>(P, vec, stream); break;
-    case 4: lim_launch_nch<4>(P, vec, stream); break;
-    case 5: lim_launch_nch<5>(P, vec, stream); break;
-    default: lim_launch_nch<6>(P, vec, stream); break;
-    }
-    return hipGetLastError();
+    pcm_copy_roles(P.role, L.role, L.channels);
+    const bool vec = (((uintptr_t)L.pcm | (uintptr_t)L.out) & 15) == 0;
+    hipError_t e = hipSuccess;
+    pcm_dispatch_channels(L.channels, [&](auto nch) {
+        constexpr int NCH = decltype(nch)::value;
+        e = pcm_launch_streams(vec ? limit_kernel<NCH, true> : limit_kernel<NCH, false>, L.n_streams, LIM_WAVES, 64 * LIM_WAVES, stream, P);
+    });
+    return e;
 }
 
 hipError_t launch_limit_read(const void *state, int n_streams, ac3mi_limit_result *results, hipStream_t stream)
 {
-    if (n_streams <= 0) return hipSuccess;
-    hipLaunchKernelGGL(limit_read_kernel, dim3(((unsigned)n_streams + 255) / 256), dim3(256), 0, stream, (const LimitState *)state,
-                       (unsigned)n_streams, results);
-    return hipGetLastError();
+    return pcm_launch_streams(limit_read_kernel, n_streams, 256, 256, stream, (const LimitState *)state, (unsigned)n_streams, results);
 }
 
 }  // namespace ac3mi

@@ -3,9 +3,9 @@
 //
 // loudness_kernel: one wavefront per stream, four per workgroup, the stream's frames in order; float64 throughout (a float32
 // recursion moves block energies by 1e-4 relative: the high-pass poles sit at radius 0.995).  A frame is 64 segments of 24
-// sample instants, one per lane, and the two biquads are one linear system v' = A v + B x, y = C v + D x on four states:
-//   load        lane l's 24 instants are 48 channels contiguous bytes: 16-byte loads when the base is 16-byte aligned, else
-//               16-bit loads into the same registers (same bits either way)
+// sample instants, one per lane (pcm_lanes.h), and the two biquads are one linear system v' = A v + B x, y = C v + D x on four
+// states:
+//   load        pcm_load_segment
 //   zero state  per measured slot the lane runs the cascade over its 24 samples from v = 0: 24 outputs and an end state
 //   scan        the true end states follow from e[l] = A^24 e[l - 1] + (zero-state end of l): lane 0 adds A^24 (carried
 //               state), then six steps e[l] += A^(24 2^k) e[l - 2^k] with the constant matrices from the kernel arguments
@@ -64,6 +64,8 @@ extern "C" int ac3mi_loudness_range_read(const void *h_range_state, ac3mi_loudne
 
 #ifdef __HIPCC__
 #include "ac3mi_internal.h"
+#include "pcm_lanes.h"
+#include "wave_ops.h"
 
 // the roles of the slots the s16 converters write for these output flags (s16_channel_map, dropin.hip: slot -> plane; plane 0
 // is the LFE when the flags carry it, the surround planes are the last one of 2F1R / 3F1R and the last two of 2F2R / 3F2R)
@@ -81,6 +83,17 @@ extern "C" int ac3mi_loudness_roles(int a52_flags, uint8_t role[6])
 }
 
 namespace ac3mi {
+
+static_assert(LOUD_SEG == PCM_SEG, "a lane's segment is the frame's");
+
+// (a range state that is asked for and missing is the entry's to refuse: here nullptr means the plain meter)
+bool loudness_args_ok(const LoudnessLaunch &L)
+{
+    bool ok = loud_coefs(L.sample_rate) && L.channels >= 1 && L.channels <= 6 && L.n_streams >= 0 && L.frames_per_stream >= 1 && L.pcm &&
+              !((uintptr_t)L.pcm & 1) && L.state && !((uintptr_t)L.state & 7) && !((uintptr_t)L.range_state & 7);
+    for (int c = 0; ok && c < L.channels; c++) ok = L.role[c] <= 2;
+    return ok;
+}
 
 void loud_fill_tab(double *h_tab)
 {
@@ -116,18 +129,11 @@ __device__ __forceinline__ double loud_readlane(double v, int l)
     return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
-__device__ __forceinline__ double loud_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 template <int NCH, bool VEC, bool RANGE>
 __global__ __launch_bounds__(64 * LOUD_WAVES, LOUD_MIN_WAVES) void loudness_kernel(const LoudParams P)
 {
     const int lane = threadIdx.x & 63;
-    const unsigned s = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * LOUD_WAVES + (threadIdx.x >> 6)));
+    const unsigned s = pcm_wave_stream(LOUD_WAVES);
     if (s >= P.n_streams) return;
     LoudState *st = P.state + s;
     double q[NCH][4];                   // the carried filter states, the same in every lane
@@ -142,18 +148,7 @@ __global__ __launch_bounds__(64 * LOUD_WAVES, LOUD_MIN_WAVES) void loudness_kern
     for (int f = 0; f < P.frames; f++) {
         const int16_t *fp = sp + (size_t)f * (1536 * NCH);
         uint32_t w[12 * NCH];           // the lane's 24 NCH samples, two to a dword
-        if constexpr (VEC) {
-            const uint4 *v = reinterpret_cast<const uint4 *>(fp);
-#pragma unroll
-            for (int k = 0; k < 3 * NCH; k++) {
-                const uint4 t = v[k];
-                w[4 * k] = t.x; w[4 * k + 1] = t.y; w[4 * k + 2] = t.z; w[4 * k + 3] = t.w;
-            }
-        } else {
-            const uint16_t *h = reinterpret_cast<const uint16_t *>(fp);
-#pragma unroll
-            for (int k = 0; k < 12 * NCH; k++) w[k] = (uint32_t)h[2 * k] | ((uint32_t)h[2 * k + 1] << 16);
-        }
+        pcm_load_segment<NCH, VEC>(fp, w);
         // the hop closes behind sample nb - 1 of this frame if nb <= 1536 (a state that is not one: no boundary, nothing worse)
         const uint32_t nb = P.hop - pos;
         const int n0 = lane * LOUD_SEG;
@@ -164,8 +159,7 @@ __global__ __launch_bounds__(64 * LOUD_WAVES, LOUD_MIN_WAVES) void loudness_kern
             double y[LOUD_SEG], s1 = 0.0, s2 = 0.0, t1 = 0.0, t2 = 0.0;
 #pragma unroll
             for (int i = 0; i < LOUD_SEG; i++) {
-                const int idx = i * NCH + c;
-                const double x = (double)(int)(int16_t)(w[idx >> 1] >> (16 * (idx & 1)));
+                const double x = (double)pcm_sample<NCH>(w, i, c);
                 const double y1 = __builtin_fma(P.b0, x, s1);
                 s1 = __builtin_fma(-P.a1, y1, __builtin_fma(P.b1, x, s2));
                 s2 = __builtin_fma(-P.a2, y1, P.b2 * x);
@@ -221,8 +215,8 @@ __global__ __launch_bounds__(64 * LOUD_WAVES, LOUD_MIN_WAVES) void loudness_kern
             e_before = __builtin_fma(P.w[c], cb, e_before);
             e_after = __builtin_fma(P.w[c], ca, e_after);
         }
-        e_before = loud_wave_sum(e_before);
-        e_after = loud_wave_sum(e_after);
+        e_before = wave_all_sum_f64(e_before);
+        e_after = wave_all_sum_f64(e_after);
         hop_sum += e_before;
         if (nb <= 1536u) {              // (the same in every lane)
             const double hn = hop_sum;
@@ -273,20 +267,18 @@ __global__ __launch_bounds__(64 * LOUD_WAVES) void loudness_read_kernel(const Lo
                                                                        ac3mi_loudness_result *results)
 {
     const int lane = threadIdx.x & 63;
-    const unsigned s = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * LOUD_WAVES + (threadIdx.x >> 6)));
+    const unsigned s = pcm_wave_stream(LOUD_WAVES);
     if (s >= n_streams) return;
     const LoudState *st = state + s;
     double sum;
     uint32_t n;
     loud_total_part(st, lane, 64, &sum, &n);
-    sum = loud_wave_sum(sum);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o);
+    sum = wave_all_sum_f64(sum);
+    n = wave_sum_u32(n);
     const double gamma = loud_gamma(sum, n);
     loud_gated_part(st, tab, gamma, lane, 64, &sum, &n);
-    sum = loud_wave_sum(sum);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o);
+    sum = wave_all_sum_f64(sum);
+    n = wave_sum_u32(n);
     if (lane == 0) loud_result(st, tab + LOUD_BINS + 1, sum, n, results + s);
 }
 
@@ -294,7 +286,7 @@ __global__ __launch_bounds__(64 * LOUD_WAVES) void loudness_range_read_kernel(co
                                                                              ac3mi_loudness_range_result *results)
 {
     const int lane = threadIdx.x & 63;
-    const unsigned s = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * LOUD_WAVES + (threadIdx.x >> 6)));
+    const unsigned s = pcm_wave_stream(LOUD_WAVES);
     if (s >= n_streams) return;
     const RangeState *rs = state + s;
     const double gamma = range_gamma(rs->sum_abs, rs->blocks_abs);
@@ -337,24 +329,10 @@ __global__ __launch_bounds__(256) void loudness_words_kernel(const ac3mi_loudnes
     words[i] = (r->flags & AC3MI_LOUDNESS_EMPTY) ? base_word : ((base_word & ~31u) | (uint32_t)(r->dialnorm & 31u));
 }
 
-template <int NCH>
-static void loud_launch_nch(const LoudParams &P, bool vec, hipStream_t stream)
-{
-    const dim3 grid((P.n_streams + LOUD_WAVES - 1) / LOUD_WAVES), block(64 * LOUD_WAVES);
-    if (P.range) {
-        if (vec) hipLaunchKernelGGL((loudness_kernel<NCH, true, true>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((loudness_kernel<NCH, false, true>), grid, block, 0, stream, P);
-    } else {
-        if (vec) hipLaunchKernelGGL((loudness_kernel<NCH, true, false>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((loudness_kernel<NCH, false, false>), grid, block, 0, stream, P);
-    }
-}
-
 hipError_t launch_loudness(const LoudnessLaunch &L, hipStream_t stream)
 {
+    if (!loudness_args_ok(L) || !L.tab) return hipErrorInvalidValue;
     const double *coef = loud_coefs(L.sample_rate);
-    if (!coef || L.channels < 1 || L.channels > 6 || L.frames_per_stream < 1 || !L.pcm || !L.state || !L.tab) return hipErrorInvalidValue;
-    if (L.n_streams <= 0) return hipSuccess;
     LoudParams P;
     P.pcm = L.pcm;
     P.state = (LoudState *)L.state;
@@ -363,37 +341,32 @@ hipError_t launch_loudness(const LoudnessLaunch &L, hipStream_t stream)
     P.n_streams = (unsigned)L.n_streams;
     P.frames = L.frames_per_stream;
     P.hop = (uint32_t)(L.sample_rate / 10);
-    for (int c = 0; c < 8; c++) P.role[c] = c < L.channels ? L.role[c] : 0;
+    pcm_copy_roles(P.role, L.role, L.channels);
     for (int c = 0; c < 6; c++) P.w[c] = P.role[c] == 2 ? 1.41 : P.role[c] == 1 ? 1.0 : 0.0;
     P.b0 = coef[0] / 32768.0; P.b1 = coef[1] / 32768.0; P.b2 = coef[2] / 32768.0; P.a1 = coef[3]; P.a2 = coef[4]; P.c1 = coef[8]; P.c2 = coef[9];
     P.block_samples = 4.0 * (double)P.hop;
     loud_build_segment(coef, P.M, P.Z);
-    const bool vec = ((uintptr_t)L.pcm & 15) == 0;     // every frame and every lane's segment then is: 3072 and 48 channels bytes apart
-    switch (L.channels) {
-    case 1: loud_launch_nch<1>(P, vec, stream); break;
-    case 2: loud_launch_nch<2>(P, vec, stream); break;
-    case 3: loud_launch_nch<3>(P, vec, stream); break;
-    case 4: loud_launch_nch<4>(P, vec, stream); break;
-    case 5: loud_launch_nch<5>(P, vec, stream); break;
-    default: loud_launch_nch<6>(P, vec, stream); break;
-    }
-    return hipGetLastError();
+    const bool vec = ((uintptr_t)L.pcm & 15) == 0;
+    hipError_t e = hipSuccess;
+    pcm_dispatch_channels(L.channels, [&](auto nch) {
+        constexpr int NCH = decltype(nch)::value;
+        const auto kernel = P.range ? (vec ? loudness_kernel<NCH, true, true> : loudness_kernel<NCH, false, true>)
+                                    : (vec ? loudness_kernel<NCH, true, false> : loudness_kernel<NCH, false, false>);
+        e = pcm_launch_streams(kernel, L.n_streams, LOUD_WAVES, 64 * LOUD_WAVES, stream, P);
+    });
+    return e;
 }
 
 hipError_t launch_loudness_read(const void *state, int n_streams, const double *tab, ac3mi_loudness_result *results, hipStream_t stream)
 {
-    if (n_streams <= 0) return hipSuccess;
-    hipLaunchKernelGGL(loudness_read_kernel, dim3(((unsigned)n_streams + LOUD_WAVES - 1) / LOUD_WAVES), dim3(64 * LOUD_WAVES), 0, stream,
-                       (const LoudState *)state, (unsigned)n_streams, tab, results);
-    return hipGetLastError();
+    return pcm_launch_streams(loudness_read_kernel, n_streams, LOUD_WAVES, 64 * LOUD_WAVES, stream, (const LoudState *)state, (unsigned)n_streams,
+                              tab, results);
 }
 
 hipError_t launch_loudness_range_read(const void *range_state, int n_streams, const double *tab, ac3mi_loudness_range_result *results, hipStream_t stream)
 {
-    if (n_streams <= 0) return hipSuccess;
-    hipLaunchKernelGGL(loudness_range_read_kernel, dim3(((unsigned)n_streams + LOUD_WAVES - 1) / LOUD_WAVES), dim3(64 * LOUD_WAVES), 0, stream,
-                       (const RangeState *)range_state, (unsigned)n_streams, tab, results);
-    return hipGetLastError();
+    return pcm_launch_streams(loudness_range_read_kernel, n_streams, LOUD_WAVES, 64 * LOUD_WAVES, stream, (const RangeState *)range_state,
+                              (unsigned)n_streams, tab, results);
 }
 
 hipError_t launch_loudness_words(const ac3mi_loudness_result *results, int n_streams, int frames_per_stream, uint32_t base_word,

@@ -120,6 +120,7 @@ extern "C" int ac3mi_resample_host(const ac3mi_resample_desc *desc, const int16_
 
 #ifdef __HIPCC__
 #include "ac3mi_internal.h"
+#include "pcm_lanes.h"
 
 namespace ac3mi {
 
@@ -381,14 +382,7 @@ hipError_t launch_resample(const ResampleLaunch &L, hipStream_t stream)
     P.step = P.active / P.L * P.M;
     P.tag = rs_tag(rs_pair(L.in_rate, L.out_rate), L.channels);
     const dim3 grid((unsigned)L.n_streams), block(rs_threads(P.L));
-    switch (L.channels) {
-    case 1: rs_launch_nch<1>(P, t, grid, block, stream); break;
-    case 2: rs_launch_nch<2>(P, t, grid, block, stream); break;
-    case 3: rs_launch_nch<3>(P, t, grid, block, stream); break;
-    case 4: rs_launch_nch<4>(P, t, grid, block, stream); break;
-    case 5: rs_launch_nch<5>(P, t, grid, block, stream); break;
-    default: rs_launch_nch<6>(P, t, grid, block, stream); break;
-    }
+    pcm_dispatch_channels(L.channels, [&](auto nch) { rs_launch_nch<decltype(nch)::value>(P, t, grid, block, stream); });
     return hipGetLastError();
 }
 

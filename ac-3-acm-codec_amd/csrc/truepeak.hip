@@ -2,16 +2,14 @@
 // (ac3mi_truepeak_*; the rule is include/ac3mi.h's, its steps and the state's layout are truepeak_rule.h's).
 //
 // truepeak_kernel: one wavefront per stream, four per workgroup, the stream's frames in order; int32 throughout.  A frame is
-// 64 segments of 24 sample instants, one per lane:
-//   load        lane l's 24 instants are 48 channels contiguous bytes: 16-byte loads when the base is 16-byte aligned, else
-//               16-bit loads into the same registers (same bits either way)
-//   history     per measured slot the 11 instants before a lane's segment come from the left neighbour's registers, one lane
-//               shift per dword; lane 0 takes them from the 12 instants carried from the frame before (whole dwords for
-//               every channel count, wave-uniform: lane 63's last 6 channels dwords, or at a call's first frame rebuilt
-//               from the state's 11 samples per slot).  No sample is read twice from memory
-//   phases      the lane packs the slot's 35 samples into the 34 pairs of neighbours (v_perm_b32) and forms the 4 x 24
-//               phases with six packed 16-bit dot products each (v_dot2_i32_i16: tp_phases' sums, the same int32), keeping
-//               the largest |y| with its first index in the frame, the largest |x| and the full-scale count
+// 64 segments of 24 sample instants, one per lane (pcm_lanes.h):
+//   load        pcm_load_segment
+//   history     tp_pairs (truepeak_packed.h), per measured slot; the 12 instants it takes as carried are whole dwords for every
+//               channel count, wave-uniform: lane 63's last 6 channels dwords, or at a call's first frame rebuilt from the
+//               state's 11 samples per slot
+//   phases      from the slot's 34 pairs the 4 x 24 phases with six packed 16-bit dot products each (v_dot2_i32_i16:
+//               tp_phases' sums, the same int32), keeping the largest |y| with its first index in the frame, the largest |x|
+//               and the full-scale count
 //   combine     behind the last frame a butterfly with the rule's ordering (tp_before) gives every lane the call's maxima and
 //               sums; lane 0 merges them into the state - strictly greater replaces - with plain stores
 // The PCM is read once; nothing waits on another wavefront; every loop is bounded by the frame count or a constant; no LDS,
@@ -19,6 +17,14 @@
 //
 // truepeak_read_kernel: one stream per lane (tp_result, the code ac3mi_truepeak_read runs).
 #include "truepeak_rule.h"
+
+namespace ac3mi {
+// what the host meter and the device meter refuse alike of one call's shape (the roles apart: a pointer in both entries)
+static inline bool truepeak_call_ok(int channels, const void *pcm, int frames, const void *state)
+{
+    return channels >= 1 && channels <= 6 && pcm && !((uintptr_t)pcm & 1) && frames >= 1 && state;
+}
+}  // namespace ac3mi
 
 extern "C" size_t ac3mi_truepeak_state_bytes(void) { return sizeof(ac3mi::TruePeakState); }
 
@@ -40,7 +46,7 @@ extern "C" int ac3mi_truepeak_read(const void *h_state, uint32_t ceiling_q28, ac
 
 extern "C" int ac3mi_truepeak_host(int channels, const uint8_t *role, const int16_t *h_pcm, int frames, void *h_state)
 {
-    if (channels < 1 || channels > 6 || !role || !h_pcm || ((uintptr_t)h_pcm & 1) || frames < 1 || !h_state) return AC3MI_ERR_ARG;
+    if (!role || !ac3mi::truepeak_call_ok(channels, h_pcm, frames, h_state)) return AC3MI_ERR_ARG;
     ac3mi::truepeak_meter_host(channels, role, h_pcm, frames, h_state);
     return AC3MI_OK;
 }
@@ -50,6 +56,11 @@ extern "C" int ac3mi_truepeak_host(int channels, const uint8_t *role, const int1
 #include "truepeak_packed.h"
 
 namespace ac3mi {
+
+bool truepeak_args_ok(const TruePeakLaunch &L)
+{
+    return truepeak_call_ok(L.channels, L.pcm, L.frames_per_stream, L.state) && L.n_streams >= 0 && !((uintptr_t)L.state & 7);
+}
 
 constexpr int TP_WAVES = 4;
 // wavefronts per SIMD the meter kernel is compiled for.  The six-channel variant holds a frame's 72 dwords, 30 registers of
@@ -71,27 +82,12 @@ struct TpLane {
     uint32_t peak, full;                // the largest |x|; the full-scale samples (24 a frame: a u32 holds more frames than device memory)
 };
 
-// One slot of one frame in one lane.  own = the lane's 24 instants as dwords [24][NCH]; carry = the 12 instants before the
-// frame, as dwords [12][NCH], the same in every lane.  The 11 instants before the segment come from the left neighbour's
-// registers, one lane shift each (the dword that holds the sample; lane 0: the carried one)
+// One slot of one frame in one lane (own, carry: tp_pairs')
 template <int NCH, int C>
 __device__ __forceinline__ void tp_slot(const uint32_t *own, const uint32_t *carry, uint32_t lane, uint32_t f, TpLane &L)
 {
-    constexpr int HW = 6 * NCH;
-    uint32_t h[TP_HIST];                // the dwords with instants -11 .. -1 of this slot
-#pragma unroll
-    for (int j = 0; j < TP_HIST; j++) {
-        const int k = ((j + 1) * NCH + C) >> 1;
-        const uint32_t left = __shfl_up(own[HW + k], 1u);
-        h[j] = lane == 0 ? carry[k] : left;
-    }
-    uint32_t q[TP_HIST + TP_SEG - 1];   // the pairs of instants (-11, -10) .. (22, 23)
-#pragma unroll
-    for (int j = 0; j < TP_HIST + TP_SEG - 1; j++) {
-        const int a = (j + 1) * NCH + C, b = a + NCH;       // (in dwords that start 12 instants before the segment)
-        const uint32_t wa = j < TP_HIST ? h[j] : own[(a >> 1) - HW], wb = j + 1 < TP_HIST ? h[j + 1] : own[(b >> 1) - HW];
-        q[j] = tp_pack(wa, a & 1, wb, b & 1);
-    }
+    uint32_t q[TP_HIST + TP_SEG - 1];
+    tp_pairs<NCH, C>(own, carry, (int)lane, q);
     // |y| < 2^30 (truepeak_rule.h), so key = |y| << 2 | (3 - p) orders an instant's four phases by the rule - the larger value,
     // then the earlier phase - in one maximum; across instants only a strictly greater |y| replaces: key > (kept | 3)
     uint32_t key = 0, inst = 0, pk = 0, fs = 0;
@@ -108,12 +104,12 @@ __device__ __forceinline__ void tp_slot(const uint32_t *own, const uint32_t *car
         const bool later = k4 > (key | 3u);
         inst = later ? (uint32_t)i : inst;
         key = later ? k4 : key;
-        const uint32_t ax = tp_abs(tp_sample<NCH>(own, i, C));
+        const uint32_t ax = tp_abs(pcm_sample<NCH>(own, i, C));
         pk = ax > pk ? ax : pk;
     }
     if (pk >= 32767u) {
 #pragma unroll
-        for (int i = 0; i < TP_SEG; i++) fs += tp_full_scale(tp_sample<NCH>(own, i, C)) ? 1u : 0u;
+        for (int i = 0; i < TP_SEG; i++) fs += tp_full_scale(pcm_sample<NCH>(own, i, C)) ? 1u : 0u;
     }
     const uint32_t m = key >> 2, at = 4 * inst + (3u - (key & 3u));
     const bool take = m > L.best;       // frames in order: only a strictly greater value replaces the lane's
@@ -124,22 +120,12 @@ __device__ __forceinline__ void tp_slot(const uint32_t *own, const uint32_t *car
     L.full += fs;
 }
 
-// ... every measured slot (written as a recursion: the slot is a compile-time constant, so the dwords stay in registers)
-template <int NCH, int C>
-__device__ __forceinline__ void tp_slots(const uint8_t *role, const uint32_t *own, const uint32_t *carry, uint32_t lane, uint32_t f, TpLane *acc)
-{
-    if constexpr (C < NCH) {
-        if (role[C] != 0) tp_slot<NCH, C>(own, carry, lane, f, acc[C]);
-        tp_slots<NCH, C + 1>(role, own, carry, lane, f, acc);
-    }
-}
-
 template <int NCH, bool VEC>
 __global__ __launch_bounds__(64 * TP_WAVES, TP_MIN_WAVES) void truepeak_kernel(const TruePeakParams P)
 {
     constexpr int HW = 6 * NCH;         // dwords of 12 instants
     const int lane = threadIdx.x & 63;
-    const unsigned s = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * TP_WAVES + (threadIdx.x >> 6)));
+    const unsigned s = pcm_wave_stream(TP_WAVES);
     if (s >= P.n_streams) return;
     TruePeakState *st = P.state + s;
     // the 12 instants before the frame, as dwords [12][NCH] (the same in every lane); instant 0 of them is never read
@@ -162,19 +148,10 @@ __global__ __launch_bounds__(64 * TP_WAVES, TP_MIN_WAVES) void truepeak_kernel(c
     for (int f = 0; f < P.frames; f++) {
         const int16_t *fp = sp + (size_t)f * (1536 * NCH);
         uint32_t w[12 * NCH];           // the lane's 24 NCH samples, two to a dword
-        if constexpr (VEC) {
-            const uint4 *v = reinterpret_cast<const uint4 *>(fp);
-#pragma unroll
-            for (int k = 0; k < 3 * NCH; k++) {
-                const uint4 t = v[k];
-                w[4 * k] = t.x; w[4 * k + 1] = t.y; w[4 * k + 2] = t.z; w[4 * k + 3] = t.w;
-            }
-        } else {
-            const uint16_t *h = reinterpret_cast<const uint16_t *>(fp);
-#pragma unroll
-            for (int k = 0; k < 12 * NCH; k++) w[k] = (uint32_t)h[2 * k] | ((uint32_t)h[2 * k + 1] << 16);
-        }
-        tp_slots<NCH, 0>(P.role, w, carry, (uint32_t)lane, (uint32_t)f, acc);
+        pcm_load_segment<NCH, VEC>(fp, w);
+        pcm_for_each_slot<NCH>(P.role, [&](auto c) __attribute__((always_inline)) {
+            tp_slot<NCH, decltype(c)::value>(w, carry, (uint32_t)lane, (uint32_t)f, acc[decltype(c)::value]);
+        });
 #pragma unroll
         for (int k = 0; k < HW; k++) carry[k] = (uint32_t)__builtin_amdgcn_readlane((int)w[HW + k], 63);
     }
@@ -204,7 +181,7 @@ __global__ __launch_bounds__(64 * TP_WAVES, TP_MIN_WAVES) void truepeak_kernel(c
             if (pk > st->sample_peak[c]) st->sample_peak[c] = pk;
             st->full_scale[c] = tp_add_sat(st->full_scale[c], n);
 #pragma unroll
-            for (int j = 0; j < TP_HIST; j++) st->hist[c][j] = (int16_t)tp_sample<NCH>(carry, j + 1, c);
+            for (int j = 0; j < TP_HIST; j++) st->hist[c][j] = (int16_t)pcm_sample<NCH>(carry, j + 1, c);
         }
         measured |= (uint8_t)(1u << c);
     }
@@ -222,42 +199,28 @@ __global__ __launch_bounds__(256) void truepeak_read_kernel(const TruePeakState 
     tp_result(state + s, ceiling_q28, results + s);
 }
 
-template <int NCH>
-static void tp_launch_nch(const TruePeakParams &P, bool vec, hipStream_t stream)
-{
-    const dim3 grid((P.n_streams + TP_WAVES - 1) / TP_WAVES), block(64 * TP_WAVES);
-    if (vec) hipLaunchKernelGGL((truepeak_kernel<NCH, true>), grid, block, 0, stream, P);
-    else hipLaunchKernelGGL((truepeak_kernel<NCH, false>), grid, block, 0, stream, P);
-}
-
 hipError_t launch_truepeak(const TruePeakLaunch &L, hipStream_t stream)
 {
-    if (L.channels < 1 || L.channels > 6 || L.frames_per_stream < 1 || !L.pcm || !L.state) return hipErrorInvalidValue;
-    if (L.n_streams <= 0) return hipSuccess;
+    if (!truepeak_args_ok(L)) return hipErrorInvalidValue;
     TruePeakParams P;
     P.pcm = L.pcm;
     P.state = (TruePeakState *)L.state;
     P.n_streams = (unsigned)L.n_streams;
     P.frames = L.frames_per_stream;
-    for (int c = 0; c < 8; c++) P.role[c] = c < L.channels ? L.role[c] : 0;
-    const bool vec = ((uintptr_t)L.pcm & 15) == 0;      // every frame and every lane's segment then is: 3072 and 48 channels bytes apart
-    switch (L.channels) {
-    case 1: tp_launch_nch<1>(P, vec, stream); break;
-    case 2: tp_launch_nch<2>(P, vec, stream); break;
-    case 3: tp_launch_nch<3>(P, vec, stream); break;
-    case 4: tp_launch_nch<4>(P, vec, stream); break;
-    case 5: tp_launch_nch<5>(P, vec, stream); break;
-    default: tp_launch_nch<6>(P, vec, stream); break;
-    }
-    return hipGetLastError();
+    pcm_copy_roles(P.role, L.role, L.channels);
+    const bool vec = ((uintptr_t)L.pcm & 15) == 0;
+    hipError_t e = hipSuccess;
+    pcm_dispatch_channels(L.channels, [&](auto nch) {
+        constexpr int NCH = decltype(nch)::value;
+        e = pcm_launch_streams(vec ? truepeak_kernel<NCH, true> : truepeak_kernel<NCH, false>, L.n_streams, TP_WAVES, 64 * TP_WAVES, stream, P);
+    });
+    return e;
 }
 
 hipError_t launch_truepeak_read(const void *state, int n_streams, uint32_t ceiling_q28, ac3mi_truepeak_result *results, hipStream_t stream)
 {
-    if (n_streams <= 0) return hipSuccess;
-    hipLaunchKernelGGL(truepeak_read_kernel, dim3(((unsigned)n_streams + 255) / 256), dim3(256), 0, stream, (const TruePeakState *)state,
-                       (unsigned)n_streams, ceiling_q28, results);
-    return hipGetLastError();
+    return pcm_launch_streams(truepeak_read_kernel, n_streams, 256, 256, stream, (const TruePeakState *)state, (unsigned)n_streams, ceiling_q28,
+                              results);
 }
 
 }  // namespace ac3mi

@@ -1,25 +1,43 @@
 // truepeak_packed.h — the device form of truepeak_rule.h's interpolator that truepeak_kernel (truepeak.hip) and limit_kernel
-// (limit.hip) share: samples two to a dword, pairs of neighbours by v_perm_b32, an instant's four phases as six packed 16-bit
-// dot products each.  Integer sums that cannot wrap (truepeak_rule.h), so tp_phases' bits in any order of adding.
+// (limit.hip) share, on pcm_lanes.h's frame: samples two to a dword, a slot's history from the left neighbour, pairs of
+// neighbours by v_perm_b32, an instant's four phases as six packed 16-bit dot products each.  Integer sums that cannot wrap
+// (truepeak_rule.h), so tp_phases' bits in any order of adding.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "pcm_lanes.h"
 #include "truepeak_rule.h"
 
 namespace ac3mi {
 
-// sample (instant i, slot c) of dwords that hold [instant][NCH] int16 from instant 0 on
-template <int NCH>
-__device__ __forceinline__ int32_t tp_sample(const uint32_t *w, int i, int c)
-{
-    const int idx = i * NCH + c;
-    return (int32_t)(int16_t)(w[idx >> 1] >> (16 * (idx & 1)));
-}
+static_assert(TP_SEG == PCM_SEG, "a lane's segment is the frame's");
 
 // two int16 (dword a's half ha below dword b's half hb) as one dword: one v_perm_b32
 __device__ __forceinline__ uint32_t tp_pack(uint32_t a, int ha, uint32_t b, int hb)
 {
     const uint32_t sel = (uint32_t)(2 * ha) | ((uint32_t)(2 * ha + 1) << 8) | ((uint32_t)(4 + 2 * hb) << 16) | ((uint32_t)(5 + 2 * hb) << 24);
     return __builtin_amdgcn_perm(b, a, sel);
+}
+
+// The interpolator's input for slot C of one frame in one lane: q = the pairs of instants (-11, -10) .. (22, 23) of the lane's
+// segment.  own = the lane's 24 instants as dwords [24][NCH]; carry = the 12 instants before the frame as dwords [12][NCH],
+// the same in every lane.  The 11 instants before the segment come from the left neighbour's registers, one lane shift each
+// (the dword that holds the sample; lane 0: the carried one)
+template <int NCH, int C>
+__device__ __forceinline__ void tp_pairs(const uint32_t *own, const uint32_t *carry, int lane, uint32_t q[TP_HIST + TP_SEG - 1])
+{
+    constexpr int HW = 6 * NCH;
+    uint32_t h[TP_HIST];                // the dwords with instants -11 .. -1 of this slot
+#pragma unroll
+    for (int j = 0; j < TP_HIST; j++) {
+        const int k = ((j + 1) * NCH + C) >> 1;
+        const uint32_t left = __shfl_up(own[HW + k], 1u);
+        h[j] = lane == 0 ? carry[k] : left;
+    }
+#pragma unroll
+    for (int j = 0; j < TP_HIST + TP_SEG - 1; j++) {
+        const int a = (j + 1) * NCH + C, b = a + NCH;       // (in dwords that start 12 instants before the segment)
+        const uint32_t wa = j < TP_HIST ? h[j] : own[(a >> 1) - HW], wb = j + 1 < TP_HIST ? h[j + 1] : own[(b >> 1) - HW];
+        q[j] = tp_pack(wa, a & 1, wb, b & 1);
+    }
 }
 
 // (H[p][2 m + 1], H[p][2 m]) as the two halves of a dword: what meets the pair (x[n - 2 m - 1], x[n - 2 m])

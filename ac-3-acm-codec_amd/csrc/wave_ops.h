@@ -33,6 +33,15 @@ __device__ __forceinline__ uint32_t wave_last(uint32_t v) { return (uint32_t)__b
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) { return wave_last(wave_incl_scan_u32(v)); }
 
+// The sum of all lanes' values in every lane, by a butterfly that adds in this order and no other - the partner 32 lanes away
+// first, the neighbour last: the loudness meter's bits depend on it
+__device__ __forceinline__ double wave_all_sum_f64(double v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
 // What the lanes of a wavefront wrote to LDS or memory before this point, every lane of it reads behind it: release fence,
 // wavefront barrier, acquire fence.  (A release and a barrier WITHOUT the acquire - a wavefront that only hands its stores on -
 // is another fence and stays spelled out where it is used.)

@@ -91,6 +91,37 @@ def frame_scan(buf, mode=0, max_frames=None):
     return np.frombuffer(bytes(refs), capi.frame_ref_dtype())[:int(out["n_frames"])].copy(), out
 
 
+def _read_host(entry_name, state_bytes_name, ResultC, dtype, state, *extra, what="state"):
+    """A PCM tool's host read-out: one state's bytes, then `extra`, -> a numpy record of dtype"""
+    import numpy as np
+    lib = capi.load_library()
+    data = bytes(bytearray(state))
+    nb = getattr(lib, state_bytes_name)()
+    if len(data) != nb:
+        raise ValueError("a %s is %d bytes" % (what, nb))
+    res = ResultC()
+    if getattr(lib, entry_name)(data, *extra, ctypes.byref(res)) != 0:
+        raise capi.AC3MIError(entry_name + ": bad argument")
+    return np.frombuffer(bytes(res), dtype)[0]
+
+
+def _roles_array(roles, nch):
+    """one role per channel -> the uint8 [6] the C entries take"""
+    if len(roles) != nch:
+        raise ValueError("one role per channel")
+    return (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6])
+
+
+def _host_stream(pcm, state, state_bytes, roles=None):
+    """A PCM tool's host twin works on ONE stream: pcm -> int16 [frames * 1536][channels], contiguous; the state's bytes (None:
+    a new stream) -> a buffer of state_bytes that the call updates"""
+    import numpy as np
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+    if pcm.ndim != 2 or pcm.shape[0] % 1536 or (roles is not None and len(roles) != pcm.shape[1]):
+        raise ValueError("pcm is [frames * 1536][channels]" + (", one role per channel" if roles is not None else ""))
+    return pcm, ctypes.create_string_buffer(bytes(bytearray(state)) if state is not None else bytes(state_bytes), state_bytes)
+
+
 def loudness_state_bytes():
     """ac3mi_loudness_state_bytes: bytes of one stream's meter state (all zeros: a new stream)"""
     return int(capi.load_library().ac3mi_loudness_state_bytes())
@@ -119,15 +150,7 @@ def loudness_tables(sample_rate):
 def loudness_read(state):
     """ac3mi_loudness_read, the host read-out: one state's bytes (ac3mi_loudness_state_bytes of them) -> a numpy record of
     capi.loudness_result_dtype()"""
-    import numpy as np
-    lib = capi.load_library()
-    data = bytes(bytearray(state))
-    if len(data) != lib.ac3mi_loudness_state_bytes():
-        raise ValueError("a state is %d bytes" % lib.ac3mi_loudness_state_bytes())
-    res = capi.LoudnessResultC()
-    if lib.ac3mi_loudness_read(data, ctypes.byref(res)) != 0:
-        raise capi.AC3MIError("ac3mi_loudness_read: bad argument")
-    return np.frombuffer(bytes(res), capi.loudness_result_dtype())[0]
+    return _read_host("ac3mi_loudness_read", "ac3mi_loudness_state_bytes", capi.LoudnessResultC, capi.loudness_result_dtype(), state)
 
 
 def loudness_range_state_bytes():
@@ -138,15 +161,8 @@ def loudness_range_state_bytes():
 def loudness_range_read(state):
     """ac3mi_loudness_range_read, the host read-out: one range state's bytes (ac3mi_loudness_range_state_bytes of them) -> a
     numpy record of capi.loudness_range_result_dtype()"""
-    import numpy as np
-    lib = capi.load_library()
-    data = bytes(bytearray(state))
-    if len(data) != lib.ac3mi_loudness_range_state_bytes():
-        raise ValueError("a range state is %d bytes" % lib.ac3mi_loudness_range_state_bytes())
-    res = capi.LoudnessRangeResultC()
-    if lib.ac3mi_loudness_range_read(data, ctypes.byref(res)) != 0:
-        raise capi.AC3MIError("ac3mi_loudness_range_read: bad argument")
-    return np.frombuffer(bytes(res), capi.loudness_range_result_dtype())[0]
+    return _read_host("ac3mi_loudness_range_read", "ac3mi_loudness_range_state_bytes", capi.LoudnessRangeResultC,
+                      capi.loudness_range_result_dtype(), state, what="range state")
 
 
 def truepeak_state_bytes():
@@ -171,29 +187,16 @@ def truepeak_ceiling(dbtp):
 def truepeak_read(state, ceiling_q28=0):
     """ac3mi_truepeak_read, the host read-out: one state's bytes (ac3mi_truepeak_state_bytes of them) -> a numpy record of
     capi.truepeak_result_dtype()"""
-    import numpy as np
-    lib = capi.load_library()
-    data = bytes(bytearray(state))
-    if len(data) != lib.ac3mi_truepeak_state_bytes():
-        raise ValueError("a state is %d bytes" % lib.ac3mi_truepeak_state_bytes())
-    res = capi.TruePeakResultC()
-    if lib.ac3mi_truepeak_read(data, int(ceiling_q28), ctypes.byref(res)) != 0:
-        raise capi.AC3MIError("ac3mi_truepeak_read: bad argument")
-    return np.frombuffer(bytes(res), capi.truepeak_result_dtype())[0]
+    return _read_host("ac3mi_truepeak_read", "ac3mi_truepeak_state_bytes", capi.TruePeakResultC, capi.truepeak_result_dtype(), state,
+                      int(ceiling_q28))
 
 
 def truepeak_host(roles, pcm, state=None):
     """ac3mi_truepeak_host, the host meter (no GPU): pcm int16 [n][channels] of ONE stream, n a multiple of 1536, on the
     state's bytes (None: a new stream) -> the new state's bytes.  roles: 0 = not measured, else measured, one per channel."""
-    import numpy as np
     lib = capi.load_library()
-    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-    if pcm.ndim != 2 or pcm.shape[0] % 1536 or len(roles) != pcm.shape[1]:
-        raise ValueError("pcm is [frames * 1536][channels], one role per channel")
-    nb = lib.ac3mi_truepeak_state_bytes()
-    buf = ctypes.create_string_buffer(bytes(bytearray(state)) if state is not None else bytes(nb), nb)
-    role = (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6])
-    if lib.ac3mi_truepeak_host(int(pcm.shape[1]), role, pcm.ctypes.data, pcm.shape[0] // 1536, buf) != 0:
+    pcm, buf = _host_stream(pcm, state, lib.ac3mi_truepeak_state_bytes(), roles)
+    if lib.ac3mi_truepeak_host(int(pcm.shape[1]), _roles_array(roles, pcm.shape[1]), pcm.ctypes.data, pcm.shape[0] // 1536, buf) != 0:
         raise capi.AC3MIError("ac3mi_truepeak_host: bad argument")
     return buf.raw
 
@@ -211,15 +214,7 @@ def limit_release_step(sample_rate, full_recovery_ms):
 def limit_read(state):
     """ac3mi_limit_read, the host read-out: one state's bytes (ac3mi_limit_state_bytes of them) -> a numpy record of
     capi.limit_result_dtype()"""
-    import numpy as np
-    lib = capi.load_library()
-    data = bytes(bytearray(state))
-    if len(data) != lib.ac3mi_limit_state_bytes():
-        raise ValueError("a state is %d bytes" % lib.ac3mi_limit_state_bytes())
-    res = capi.LimitResultC()
-    if lib.ac3mi_limit_read(data, ctypes.byref(res)) != 0:
-        raise capi.AC3MIError("ac3mi_limit_read: bad argument")
-    return np.frombuffer(bytes(res), capi.limit_result_dtype())[0]
+    return _read_host("ac3mi_limit_read", "ac3mi_limit_state_bytes", capi.LimitResultC, capi.limit_result_dtype(), state)
 
 
 def limit_host(roles, ceiling_q28, release_step_q24, pcm, state=None):
@@ -228,15 +223,10 @@ def limit_host(roles, ceiling_q28, release_step_q24, pcm, state=None):
     detected, one per channel; every channel is delayed by 77 samples and gets the gain."""
     import numpy as np
     lib = capi.load_library()
-    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-    if pcm.ndim != 2 or pcm.shape[0] % 1536 or len(roles) != pcm.shape[1]:
-        raise ValueError("pcm is [frames * 1536][channels], one role per channel")
-    nb = lib.ac3mi_limit_state_bytes()
-    buf = ctypes.create_string_buffer(bytes(bytearray(state)) if state is not None else bytes(nb), nb)
-    role = (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6])
+    pcm, buf = _host_stream(pcm, state, lib.ac3mi_limit_state_bytes(), roles)
     out = np.empty_like(pcm)
-    if lib.ac3mi_limit_host(int(pcm.shape[1]), role, int(ceiling_q28), int(release_step_q24), pcm.ctypes.data, out.ctypes.data,
-                            pcm.shape[0] // 1536, buf) != 0:
+    if lib.ac3mi_limit_host(int(pcm.shape[1]), _roles_array(roles, pcm.shape[1]), int(ceiling_q28), int(release_step_q24), pcm.ctypes.data,
+                            out.ctypes.data, pcm.shape[0] // 1536, buf) != 0:
         raise capi.AC3MIError("ac3mi_limit_host: bad argument")
     return out, buf.raw
 
@@ -283,13 +273,9 @@ def resample_host(desc, pcm, out_frames, state=None):
     ResampleDesc or (in_rate, out_rate)."""
     import numpy as np
     lib = capi.load_library()
-    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-    if pcm.ndim != 2 or pcm.shape[0] % 1536:
-        raise ValueError("pcm is [frames * 1536][channels]")
+    pcm, buf = _host_stream(pcm, state, lib.ac3mi_resample_state_bytes())
     if not isinstance(desc, capi.ResampleDescC):
         desc = capi.ResampleDescC(int(desc[0]), int(desc[1]), int(pcm.shape[1]))
-    nb = lib.ac3mi_resample_state_bytes()
-    buf = ctypes.create_string_buffer(bytes(bytearray(state)) if state is not None else bytes(nb), nb)
     out = np.full((int(out_frames) * 1536, pcm.shape[1]), 0x5a5a, np.int16)
     status = ctypes.c_uint32(0xffffffff)
     if lib.ac3mi_resample_host(ctypes.byref(desc), pcm.ctypes.data, pcm.shape[0] // 1536, out.ctypes.data if out.size else None,
@@ -683,133 +669,102 @@ class Engine:
         self._keep.append((streams, refs, info, out))
         return out
 
+    def _pcm_call(self, pcm, state_bytes_entry, state):
+        """What every PCM tool takes: pcm [S][F][1536][channels] s16 on the device and state u8 [S][state bytes] (None: zeros,
+        allocated here) -> (S, F, channels, state)"""
+        import torch
+        assert pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.is_cuda and pcm.dim() == 4 and pcm.shape[2] == 1536
+        S, F, _, nch = pcm.shape
+        nb = int(getattr(self.lib, state_bytes_entry)())
+        if state is None:
+            state = torch.zeros((S, nb), dtype=torch.uint8, device=pcm.device)
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == S * nb
+        return S, F, nch, state
+
+    def _launch(self, wait_torch, entry, keep, *args):
+        """entry(ctx, *args) behind torch's queued work; `keep` stays referenced until the next sync"""
+        self._drain_torch(wait_torch)
+        self._check(getattr(self.lib, entry)(ctypes.c_void_p(self.ctx), *args))
+        self._keep.append(keep)
+
+    def _read_batch(self, entry, state_bytes, ResultC, state, out, wait_torch, *extra):
+        """A PCM tool's device read-out: state u8 [S][state bytes], then `extra`, -> results u8 [S][sizeof(ResultC)]"""
+        import torch
+        nb, nr = int(getattr(self.lib, state_bytes)()), ctypes.sizeof(ResultC)
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.is_cuda and state.numel() % nb == 0
+        S = state.numel() // nb
+        if out is None:
+            out = torch.zeros((S, nr), dtype=torch.uint8, device=state.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == S * nr
+        self._launch(wait_torch, entry, (state, out), ctypes.c_void_p(state.data_ptr()), int(S), *extra, ctypes.c_void_p(out.data_ptr()))
+        return out
+
     def loudness_batch(self, sample_rate, roles, pcm, state=None, wait_torch=True):
         """ac3mi_loudness_batch: meters pcm [S][F][1536][channels] s16 on the device (any 2-byte aligned view that is
         contiguous) into state u8 [S][loudness_state_bytes()] (zeros: new streams; default: allocated here) -> state.  roles:
         one of 0 / 1 / 2 per channel (loudness_roles)."""
-        import torch
-        assert pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.is_cuda and pcm.dim() == 4 and pcm.shape[2] == 1536
-        S, F, _, nch = pcm.shape
-        nb = int(self.lib.ac3mi_loudness_state_bytes())
-        if state is None:
-            state = torch.zeros((S, nb), dtype=torch.uint8, device=pcm.device)
-        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == S * nb
-        desc = capi.LoudnessDescC(int(sample_rate), int(nch), (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6]))
-        if len(roles) != nch:
-            raise ValueError("one role per channel")
-        self._drain_torch(wait_torch)
-        self._check(self.lib.ac3mi_loudness_batch(ctypes.c_void_p(self.ctx), ctypes.byref(desc), ctypes.c_void_p(pcm.data_ptr()), int(S), int(F),
-                                                  ctypes.c_void_p(state.data_ptr())))
-        self._keep.append((pcm, state))
+        S, F, nch, state = self._pcm_call(pcm, "ac3mi_loudness_state_bytes", state)
+        desc = capi.LoudnessDescC(int(sample_rate), int(nch), _roles_array(roles, nch))
+        self._launch(wait_torch, "ac3mi_loudness_batch", (pcm, state), ctypes.byref(desc), ctypes.c_void_p(pcm.data_ptr()), int(S), int(F),
+                     ctypes.c_void_p(state.data_ptr()))
         return state
 
     def loudness_read_batch(self, state, out=None, wait_torch=True):
         """ac3mi_loudness_read_batch: state u8 [S][loudness_state_bytes()] -> results u8 [S][40];
         `.cpu().numpy().view(capi.loudness_result_dtype())[..., 0]` names the fields."""
-        import torch
-        nb = int(self.lib.ac3mi_loudness_state_bytes())
-        assert state.dtype == torch.uint8 and state.is_contiguous() and state.is_cuda and state.numel() % nb == 0
-        S = state.numel() // nb
-        if out is None:
-            out = torch.zeros((S, 40), dtype=torch.uint8, device=state.device)
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == S * 40
-        self._drain_torch(wait_torch)
-        self._check(self.lib.ac3mi_loudness_read_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(state.data_ptr()), int(S),
-                                                       ctypes.c_void_p(out.data_ptr())))
-        self._keep.append((state, out))
-        return out
+        return self._read_batch("ac3mi_loudness_read_batch", "ac3mi_loudness_state_bytes", capi.LoudnessResultC, state, out, wait_torch)
 
     def loudness_range_batch(self, sample_rate, roles, pcm, state=None, range_state=None, wait_torch=True):
         """ac3mi_loudness_range_batch: loudness_batch and the EBU Tech 3342 range meter in one pass over pcm -> (state,
         range_state); range_state u8 [S][loudness_range_state_bytes()] belongs to the state it was started with (zeros: new
         streams; default: allocated here, both together)."""
         import torch
-        assert pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.is_cuda and pcm.dim() == 4 and pcm.shape[2] == 1536
-        S, F, _, nch = pcm.shape
-        nb, nr = int(self.lib.ac3mi_loudness_state_bytes()), int(self.lib.ac3mi_loudness_range_state_bytes())
         if (state is None) != (range_state is None):
             raise ValueError("a range state belongs to the loudness state it was started with: pass both or neither")
-        if state is None:
-            state = torch.zeros((S, nb), dtype=torch.uint8, device=pcm.device)
+        S, F, nch, state = self._pcm_call(pcm, "ac3mi_loudness_state_bytes", state)
+        nr = int(self.lib.ac3mi_loudness_range_state_bytes())
+        if range_state is None:
             range_state = torch.zeros((S, nr), dtype=torch.uint8, device=pcm.device)
-        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == S * nb
         assert range_state.dtype == torch.uint8 and range_state.is_contiguous() and range_state.is_cuda and range_state.numel() == S * nr
-        desc = capi.LoudnessDescC(int(sample_rate), int(nch), (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6]))
-        if len(roles) != nch:
-            raise ValueError("one role per channel")
-        self._drain_torch(wait_torch)
-        self._check(self.lib.ac3mi_loudness_range_batch(ctypes.c_void_p(self.ctx), ctypes.byref(desc), ctypes.c_void_p(pcm.data_ptr()), int(S),
-                                                        int(F), ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(range_state.data_ptr())))
-        self._keep.append((pcm, state, range_state))
+        desc = capi.LoudnessDescC(int(sample_rate), int(nch), _roles_array(roles, nch))
+        self._launch(wait_torch, "ac3mi_loudness_range_batch", (pcm, state, range_state), ctypes.byref(desc), ctypes.c_void_p(pcm.data_ptr()),
+                     int(S), int(F), ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(range_state.data_ptr()))
         return state, range_state
 
     def loudness_range_read_batch(self, range_state, out=None, wait_torch=True):
         """ac3mi_loudness_range_read_batch: range_state u8 [S][loudness_range_state_bytes()] -> results u8 [S][48];
         `.cpu().numpy().view(capi.loudness_range_result_dtype())[..., 0]` names the fields."""
-        import torch
-        nr = int(self.lib.ac3mi_loudness_range_state_bytes())
-        assert range_state.dtype == torch.uint8 and range_state.is_contiguous() and range_state.is_cuda and range_state.numel() % nr == 0
-        S = range_state.numel() // nr
-        if out is None:
-            out = torch.zeros((S, 48), dtype=torch.uint8, device=range_state.device)
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == S * 48
-        self._drain_torch(wait_torch)
-        self._check(self.lib.ac3mi_loudness_range_read_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(range_state.data_ptr()), int(S),
-                                                             ctypes.c_void_p(out.data_ptr())))
-        self._keep.append((range_state, out))
-        return out
+        return self._read_batch("ac3mi_loudness_range_read_batch", "ac3mi_loudness_range_state_bytes", capi.LoudnessRangeResultC, range_state,
+                                out, wait_torch)
 
     def loudness_words_batch(self, results, frames_per_stream, base_word, out=None, wait_torch=True):
         """ac3mi_loudness_words_batch: results u8 [S][40] (loudness_read_batch) -> words int32 [S][frames_per_stream], base_word
         with each stream's dialnorm (base_word's own where a stream is flagged empty), for set_encode_metadata_frames."""
         import torch
-        assert results.dtype == torch.uint8 and results.is_contiguous() and results.is_cuda and results.numel() % 40 == 0
-        S = results.numel() // 40
+        nr = ctypes.sizeof(capi.LoudnessResultC)
+        assert results.dtype == torch.uint8 and results.is_contiguous() and results.is_cuda and results.numel() % nr == 0
+        S = results.numel() // nr
         if out is None:
             out = torch.zeros((S, int(frames_per_stream)), dtype=torch.int32, device=results.device)
         assert out.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and out.is_contiguous() and out.numel() == S * int(frames_per_stream)
-        self._drain_torch(wait_torch)
-        self._check(self.lib.ac3mi_loudness_words_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(results.data_ptr()), int(S),
-                                                        int(frames_per_stream), ctypes.c_uint32(int(base_word) & 0xffffffff),
-                                                        ctypes.c_void_p(out.data_ptr())))
-        self._keep.append((results, out))
+        self._launch(wait_torch, "ac3mi_loudness_words_batch", (results, out), ctypes.c_void_p(results.data_ptr()), int(S),
+                     int(frames_per_stream), ctypes.c_uint32(int(base_word) & 0xffffffff), ctypes.c_void_p(out.data_ptr()))
         return out
 
     def truepeak_batch(self, roles, pcm, state=None, wait_torch=True):
         """ac3mi_truepeak_batch: meters pcm [S][F][1536][channels] s16 on the device (any 2-byte aligned view that is
         contiguous) into state u8 [S][truepeak_state_bytes()] (zeros: new streams; default: allocated here) -> state.  roles:
         0 = not measured, anything else = measured, one per channel (loudness_roles' list can be passed as it is)."""
-        import torch
-        assert pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.is_cuda and pcm.dim() == 4 and pcm.shape[2] == 1536
-        S, F, _, nch = pcm.shape
-        nb = int(self.lib.ac3mi_truepeak_state_bytes())
-        if state is None:
-            state = torch.zeros((S, nb), dtype=torch.uint8, device=pcm.device)
-        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == S * nb
-        if len(roles) != nch:
-            raise ValueError("one role per channel")
-        role = (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6])
-        self._drain_torch(wait_torch)
-        self._check(self.lib.ac3mi_truepeak_batch(ctypes.c_void_p(self.ctx), int(nch), role, ctypes.c_void_p(pcm.data_ptr()), int(S), int(F),
-                                                  ctypes.c_void_p(state.data_ptr())))
-        self._keep.append((pcm, state))
+        S, F, nch, state = self._pcm_call(pcm, "ac3mi_truepeak_state_bytes", state)
+        self._launch(wait_torch, "ac3mi_truepeak_batch", (pcm, state), int(nch), _roles_array(roles, nch), ctypes.c_void_p(pcm.data_ptr()),
+                     int(S), int(F), ctypes.c_void_p(state.data_ptr()))
         return state
 
     def truepeak_read_batch(self, state, ceiling_q28=0, out=None, wait_torch=True):
         """ac3mi_truepeak_read_batch: state u8 [S][truepeak_state_bytes()] -> results u8 [S][96];
         `.cpu().numpy().view(capi.truepeak_result_dtype())[..., 0]` names the fields.  ceiling_q28: truepeak_ceiling(dBTP), 0 = none."""
-        import torch
-        nb = int(self.lib.ac3mi_truepeak_state_bytes())
-        assert state.dtype == torch.uint8 and state.is_contiguous() and state.is_cuda and state.numel() % nb == 0
-        S = state.numel() // nb
-        if out is None:
-            out = torch.zeros((S, 96), dtype=torch.uint8, device=state.device)
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == S * 96
-        self._drain_torch(wait_torch)
-        self._check(self.lib.ac3mi_truepeak_read_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(state.data_ptr()), int(S),
-                                                       ctypes.c_uint32(int(ceiling_q28)), ctypes.c_void_p(out.data_ptr())))
-        self._keep.append((state, out))
-        return out
+        return self._read_batch("ac3mi_truepeak_read_batch", "ac3mi_truepeak_state_bytes", capi.TruePeakResultC, state, out, wait_torch,
+                                ctypes.c_uint32(int(ceiling_q28)))
 
     def limit_batch(self, roles, ceiling_q28, release_step_q24, pcm, state=None, out=None, wait_torch=True):
         """ac3mi_limit_batch: limits pcm [S][F][1536][channels] s16 on the device to ceiling_q28 (truepeak_ceiling(dBTP)) with
@@ -817,24 +772,19 @@ class Engine:
         `pcm` itself: in place); state u8 [S][limit_state_bytes()] (zeros: new streams; default: allocated here).  roles: 0 =
         not detected, anything else = detected; every channel is delayed by 77 samples and gets the stream's gain."""
         import torch
-        assert pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.is_cuda and pcm.dim() == 4 and pcm.shape[2] == 1536
-        S, F, _, nch = pcm.shape
-        nb = int(self.lib.ac3mi_limit_state_bytes())
-        if state is None:
-            state = torch.zeros((S, nb), dtype=torch.uint8, device=pcm.device)
+        S, F, nch, state = self._pcm_call(pcm, "ac3mi_limit_state_bytes", state)
         if out is None:
             out = torch.empty_like(pcm)
-        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == S * nb
         assert out.dtype == torch.int16 and out.is_contiguous() and out.is_cuda and out.numel() == pcm.numel()
-        if len(roles) != nch:
-            raise ValueError("one role per channel")
-        role = (ctypes.c_uint8 * 6)(*(list(roles) + [0] * 6)[:6])
-        self._drain_torch(wait_torch)
-        self._check(self.lib.ac3mi_limit_batch(ctypes.c_void_p(self.ctx), int(nch), role, ctypes.c_uint32(int(ceiling_q28)),
-                                               ctypes.c_uint32(int(release_step_q24)), ctypes.c_void_p(pcm.data_ptr()),
-                                               ctypes.c_void_p(out.data_ptr()), int(S), int(F), ctypes.c_void_p(state.data_ptr())))
-        self._keep.append((pcm, out, state))
+        self._launch(wait_torch, "ac3mi_limit_batch", (pcm, out, state), int(nch), _roles_array(roles, nch), ctypes.c_uint32(int(ceiling_q28)),
+                     ctypes.c_uint32(int(release_step_q24)), ctypes.c_void_p(pcm.data_ptr()), ctypes.c_void_p(out.data_ptr()), int(S), int(F),
+                     ctypes.c_void_p(state.data_ptr()))
         return out, state
+
+    def limit_read_batch(self, state, out=None, wait_torch=True):
+        """ac3mi_limit_read_batch: state u8 [S][limit_state_bytes()] -> results u8 [S][40];
+        `.cpu().numpy().view(capi.limit_result_dtype())[..., 0]` names the fields."""
+        return self._read_batch("ac3mi_limit_read_batch", "ac3mi_limit_state_bytes", capi.LimitResultC, state, out, wait_torch)
 
     def resample_batch(self, desc, pcm, out_frames, state=None, out=None, status=None, wait_torch=True):
         """ac3mi_resample_batch: converts pcm [S][F][1536][channels] s16 on the device from desc.in_rate to desc.out_rate ->
@@ -842,44 +792,21 @@ class Engine:
         state u8 [S][resample_state_bytes()] (zeros: new streams; default: allocated here); status u32 [S]: 0, or why a
         stream was left untouched with zeros for output.  desc: a ResampleDesc or (in_rate, out_rate)."""
         import torch
-        assert pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.is_cuda and pcm.dim() == 4 and pcm.shape[2] == 1536
-        S, F, _, nch = pcm.shape
+        S, F, nch, state = self._pcm_call(pcm, "ac3mi_resample_state_bytes", state)
         if not isinstance(desc, capi.ResampleDescC):
             desc = capi.ResampleDescC(int(desc[0]), int(desc[1]), int(nch))
         if desc.channels != nch:
             raise ValueError("desc.channels is pcm's last dimension")
-        nb = int(self.lib.ac3mi_resample_state_bytes())
-        if state is None:
-            state = torch.zeros((S, nb), dtype=torch.uint8, device=pcm.device)
         if out is None:
             out = torch.empty((S, int(out_frames), 1536, nch), dtype=torch.int16, device=pcm.device)
         if status is None:
             status = torch.zeros((S,), dtype=torch.int32, device=pcm.device)
-        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == S * nb
         assert out.dtype == torch.int16 and out.is_contiguous() and out.is_cuda and out.numel() == S * int(out_frames) * 1536 * nch
         assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() == S
-        self._drain_torch(wait_torch)
-        self._check(self.lib.ac3mi_resample_batch(ctypes.c_void_p(self.ctx), ctypes.byref(desc), ctypes.c_void_p(pcm.data_ptr()), int(S),
-                                                  int(F), ctypes.c_void_p(out.data_ptr()) if out.numel() else None, int(out_frames),
-                                                  ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(status.data_ptr())))
-        self._keep.append((pcm, out, state, status))
+        self._launch(wait_torch, "ac3mi_resample_batch", (pcm, out, state, status), ctypes.byref(desc), ctypes.c_void_p(pcm.data_ptr()), int(S),
+                     int(F), ctypes.c_void_p(out.data_ptr()) if out.numel() else None, int(out_frames), ctypes.c_void_p(state.data_ptr()),
+                     ctypes.c_void_p(status.data_ptr()))
         return out, state, status
-
-    def limit_read_batch(self, state, out=None, wait_torch=True):
-        """ac3mi_limit_read_batch: state u8 [S][limit_state_bytes()] -> results u8 [S][40];
-        `.cpu().numpy().view(capi.limit_result_dtype())[..., 0]` names the fields."""
-        import torch
-        nb = int(self.lib.ac3mi_limit_state_bytes())
-        assert state.dtype == torch.uint8 and state.is_contiguous() and state.is_cuda and state.numel() % nb == 0
-        S = state.numel() // nb
-        if out is None:
-            out = torch.zeros((S, 40), dtype=torch.uint8, device=state.device)
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == S * 40
-        self._drain_torch(wait_torch)
-        self._check(self.lib.ac3mi_limit_read_batch(ctypes.c_void_p(self.ctx), ctypes.c_void_p(state.data_ptr()), int(S),
-                                                    ctypes.c_void_p(out.data_ptr())))
-        self._keep.append((state, out))
-        return out
 
     def set_encode_drc(self, profile, state=None):
         """Dynamic range control (ac3mi_set_encode_drc): profile 0 = no dynrng words, 1..5 = film standard / film light /

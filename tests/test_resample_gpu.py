@@ -113,12 +113,18 @@ def test_channel_counts(engine, channels):
 
 
 def test_alignment(engine):
-    """d_pcm and d_out one sample behind a 16-byte boundary: the same bits as aligned"""
+    """d_pcm and d_out one sample behind a 16-byte boundary: the same bits as aligned; and with 3 and 5 channels (5 streams x
+    2 frames), where an instant's slots straddle the 16-byte boundaries differently"""
     import torch
     pcm = np.stack([R.contents(44100, 3, 6, seed=300 + s)[2][1] for s in range(3)])
     out0, state0, _, _ = _check(engine, UP, pcm, cuts=(1, 2))
     out1, state1, _, _ = _check(engine, UP, pcm, cuts=(1, 2), offset=1)
     assert out0.tobytes() == out1.tobytes() and torch.equal(state0, state1)
+    for channels in (3, 5):
+        pcm = np.stack([R.contents(44100, 2, channels, seed=310 + s)[2][1] for s in range(5)])
+        out0, state0, _, _ = _check(engine, UP, pcm, channels)
+        out1, state1, _, _ = _check(engine, UP, pcm, channels, offset=1)
+        assert out0.tobytes() == out1.tobytes() and torch.equal(state0, state1), channels
 
 
 def test_extremes(engine):
