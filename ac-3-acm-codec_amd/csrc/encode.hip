@@ -29,6 +29,7 @@
 #include "enc_syntax.h"
 #include "enc_exp.h"
 #include "snr_window.h"
+#include "mdct_rule.h"
 
 #include <type_traits>
 
@@ -754,8 +755,11 @@ void enc_mdct_kernel(const MdctParams P)
 #pragma unroll
     for (int k = 0; k < 5; k++) {
         const int nloops = 4 << k, nblocks = 16 >> k, m = lane & (nloops - 1);
-        twc[k] = P.tab->cos[m * nblocks];
-        tws[k] = -P.tab->sin[m * nblocks];
+        // (a group's first butterfly, m == 0, takes no multiply in the reference: the twiddle that multiplies to the same - mdct_rule.h)
+        const int tc = P.tab->cos[m * nblocks], ts = -P.tab->sin[m * nblocks];       // (loaded by every lane: selects, no exec regions)
+        static_assert(MDCT_TW_ONE_IM == 0, "sin[0] is 0 already");
+        twc[k] = m == 0 ? MDCT_TW_ONE_RE : tc;
+        tws[k] = ts;
     }
     // the short pair: lane = 32 tsh + ls holds points Ls = bitrev5(ls) and Ls + 32 of transform tsh before the passes, ls and
     // ls + 32 after them (rotation factors read per switched block, from L1: held across the loop they spill)
@@ -825,10 +829,7 @@ void enc_mdct_kernel(const MdctParams P)
         }
         // ---- block floating point (:1697-1700): v from the position of the largest magnitude's top bit (the reference ORs the
         //      magnitudes, :1570-1596; the maximum has the same top bit) ----
-        int acc = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) acc = max(acc, max(win_[k], -win_[k]));
-        acc = wave_max_nonneg(acc);
+        const int acc = wave_max_nonneg(mdct_mag8(win_));
         int v = 14 - ilog2u((unsigned)acc);
         if (v < 0) v = 0;
         int shift = v - 9;
@@ -903,19 +904,7 @@ void enc_mdct_kernel(const MdctParams P)
                 pr = __builtin_amdgcn_update_dpp(pr, qr0, from_below, 0xf, up_banks, false);
                 pi = __builtin_amdgcn_update_dpp(pi, qi0, from_below, 0xf, up_banks, false);
             } else {
-                const bool up = (lane & d) != 0;
-                const int sr = up ? pr : qr, si = up ? pi : qi;
-                int rr, ri;
-                if constexpr (d == 1) {
-                    rr = __builtin_amdgcn_update_dpp(0, sr, 0xb1, 0xf, 0xf, false);         // quad_perm [1,0,3,2]
-                    ri = __builtin_amdgcn_update_dpp(0, si, 0xb1, 0xf, 0xf, false);
-                } else {
-                    static_assert(d == 2, "");
-                    rr = __builtin_amdgcn_update_dpp(0, sr, 0x4e, 0xf, 0xf, false);         // quad_perm [2,3,0,1]
-                    ri = __builtin_amdgcn_update_dpp(0, si, 0x4e, 0xf, 0xf, false);
-                }
-                pr = up ? rr : pr; pi = up ? ri : pi;
-                qr = up ? qr : rr; qi = up ? qi : ri;
+                quad_trade2<d>(pr, pi, qr, qi);                              // one select through the quad permute per component
             }
         };
         bfly_r(qr, qi);                                                     // pass 0
@@ -923,12 +912,10 @@ void enc_mdct_kernel(const MdctParams P)
         if (lane & 1) bfly_r(qi, -qr); else bfly_r(qr, qi);                 // pass 1: twiddles 1 and -j
         trade(std::integral_constant<int, 2>{});
         auto pass = [&](int k) {                                            // passes 2..6
-            const int nloops = 4 << k;
             const int c = twc[k], sx = tws[k];
             const int tr = (__mul24(c, qr) - __mul24(sx, qi)) >> 15;
             const int ti = (__mul24(c, qi) + __mul24(qr, sx)) >> 15;
-            const bool plain = (lane & (nloops - 1)) == 0;
-            bfly_r(plain ? qr : tr, plain ? qi : ti);
+            bfly_r(tr, ti);
         };
         pass(0); trade(std::integral_constant<int, 4>{});
         pass(1); trade(std::integral_constant<int, 8>{});
@@ -1031,18 +1018,12 @@ void enc_mdct_kernel(const MdctParams P)
             if (lane == 0 && wave == 0) P.remat[(size_t)sf * 6 + blk] = (uint8_t)(flags | (blk == 0 || flags != rprev ? 0x10 : 0));
             rprev = flags;
         }
-        uint32_t epack = 0;
+        // (mdct_rule.h: no branch; the low bytes of the four exponents gathered by three byte permutes)
+        int e4[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int a = cc[k] < 0 ? -cc[k] : cc[k];
-            int e;
-            if (a == 0) e = 24;
-            else {
-                e = 23 - ilog2u((unsigned)a) + shift;
-                if (e >= 24) { e = 24; cc[k] = 0; }
-            }
-            epack |= (uint32_t)(e & 0xff) << (8 * k);
-        }
+        for (int k = 0; k < 4; k++) e4[k] = mdct_raw_exp(cc[k], shift);
+        const uint32_t epack = __builtin_amdgcn_perm(__builtin_amdgcn_perm((uint32_t)e4[3], (uint32_t)e4[2], 0x0c0c0400u),
+                                                     __builtin_amdgcn_perm((uint32_t)e4[1], (uint32_t)e4[0], 0x0c0c0400u), 0x05040100u);
         // (the packers read a row's coded bins only: nbc of a full-bandwidth channel, 7 of the LFE - a quarter of the store traffic.
         //  Every reader of a row masks what lies beyond: the search and the packers give bins >= nbc exponent 255 (bap 0, no bits),
         //  enc_cpl_kernel reads [cplstrtmant, cplendmant) and, for a coupled channel's exponents, bins below cplstrtmant only)

@@ -113,6 +113,39 @@ __device__ __forceinline__ void wave_incl_scan_max2(int &a, int &b)
     asm volatile(AC3MI_DPP6x2("v_max_i32_dpp") : "+v"(a), "+v"(b));
 }
 
+// A butterfly network's trade inside the quads, D = 1 or 2 lanes apart: a lane with (lane & D) == 0 keeps p and takes its
+// partner's p for q, the partner keeps q and takes this lane's q for p - for two components at once.  v_cndmask_b32_dpp reads
+// its first source through the quad permutation and selects with VCC, so each result is one instruction: VCC = the lower
+// lanes gives p' = lower ? p : partner's q, its complement q' = upper ? q : partner's p.  hipcc does not form this from
+// __builtin_amdgcn_update_dpp + select (two selects, two zero moves, two DPP moves and four selects per trade); the block
+// carries its own wait states, as the scans above do.  Every lane of the wavefront must be active.
+template <int D>
+__device__ __forceinline__ void quad_trade2(int &pr, int &pi, int &qr, int &qi)
+{
+    static_assert(D == 1 || D == 2, "inside a quad");
+    constexpr uint64_t lower = D == 1 ? 0x5555555555555555ull : 0x3333333333333333ull;
+    int npr, npi, nqr, nqi;
+    if constexpr (D == 1)
+        asm volatile("s_mov_b64 vcc, %8\n\ts_nop 1\n\t"
+                     "v_cndmask_b32_dpp %0, %6, %4, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %1, %7, %5, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                     "s_not_b64 vcc, vcc\n\t"
+                     "v_cndmask_b32_dpp %2, %4, %6, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %3, %5, %7, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                     "s_nop 1"
+                     : "=&v"(npr), "=&v"(npi), "=&v"(nqr), "=&v"(nqi) : "v"(pr), "v"(pi), "v"(qr), "v"(qi), "s"(lower) : "vcc", "scc");
+    else
+        asm volatile("s_mov_b64 vcc, %8\n\ts_nop 1\n\t"
+                     "v_cndmask_b32_dpp %0, %6, %4, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %1, %7, %5, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                     "s_not_b64 vcc, vcc\n\t"
+                     "v_cndmask_b32_dpp %2, %4, %6, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %3, %5, %7, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                     "s_nop 1"
+                     : "=&v"(npr), "=&v"(npi), "=&v"(nqr), "=&v"(nqi) : "v"(pr), "v"(pi), "v"(qr), "v"(qi), "s"(lower) : "vcc", "scc");
+    pr = npr; pi = npi; qr = nqr; qi = nqi;
+}
+
 // maximum of all lanes' non-negative values, wave-uniform
 __device__ __forceinline__ int wave_max_nonneg(int v) { return __builtin_amdgcn_readlane(wave_incl_scan_max(v), 63); }
 
