@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <array>
 #include <string>
+#include <utility>
+#include <vector>
 #include "../../include/ac3mi.h"
 #include "launch_rule.h"
 
@@ -388,6 +390,7 @@ struct EncodeLaunch {
     const uint8_t *dyn_codes = nullptr;
     const uint16_t *compr_words = nullptr;
     const LaunchLog *log = nullptr;     // ac3mi_debug_launch_log: launch_stage appends what it launches (launch_rule.h); null: no tap
+    const uint16_t *crc_rows = nullptr; // the packers' CRC table of cfg.frame_words on the device, [64][16] (crc_lanes.h: crcl_fill_rows); required
 };
 // carves CPL_FRAME_BYTES * nfr bytes at `base` into the arrays of CplWs (base 16-byte aligned)
 CplWs cpl_slices(void *base, size_t nfr);
@@ -475,6 +478,8 @@ struct ac3mi_ctx {
     int32_t *debug_search_curve = nullptr;  // ac3mi_debug_search_curve
     ac3mi::LaunchLog launch_log;            // ac3mi_debug_launch_log (host memory; words null: no tap)
     uint32_t *resample_tab[6] = {};  // ac3mi_resample_batch: a pair's table on the device, put there by the pair's first call, freed in ac3mi_destroy
+    // the packers' CRC tables (crc_lanes.h), frame_words -> 2 KB on the device: put there when the context first meets the frame size, freed in ac3mi_destroy
+    std::vector<std::pair<int, uint16_t *>> crc_rows;
     double *loud_tab = nullptr;     // ac3mi_loudness_*: bin edges and dialnorm thresholds on the device, put there by the first call (no workspace: it is a table)
     std::string err;
 };

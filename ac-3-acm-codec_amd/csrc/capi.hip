@@ -6,6 +6,7 @@
 #include "sync_rule.h"
 #include "resample_rule.h"
 #include "pcm_lanes.h"
+#include "crc_lanes.h"
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -542,6 +543,7 @@ void ac3mi_destroy(ac3mi_ctx *ctx)
     (void)hipFree(ctx->tab.enc);
     (void)hipFree(ctx->loud_tab);
     for (uint32_t *t : ctx->resample_tab) (void)hipFree(t);
+    for (const auto &e : ctx->crc_rows) (void)hipFree(e.second);
     (void)hipEventDestroy(ctx->ev0);
     (void)hipEventDestroy(ctx->ev1);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -1111,6 +1113,21 @@ static EncWs enc_ws_layout(size_t rows)
 // the transcode's s16 PCM between the transform and the encoder (ws_tc)
 static size_t s16_ws_bytes(size_t nfr, int n_out) { return nfr * 1536 * n_out * 2 + 512; }
 
+// The packers' CRC table of a frame size (crc_lanes.h): built and uploaded when the context first meets the size, kept by
+// frame_words - a later call of that size finds it and adds no host work, no copy and no synchronisation
+static int crc_rows_ready(ac3mi_ctx *ctx, int frame_words, const uint16_t **rows)
+{
+    for (const auto &e : ctx->crc_rows)
+        if (e.first == frame_words) { *rows = e.second; return AC3MI_OK; }
+    uint16_t h[CRCL_LANES][CRCL_ROW];
+    crcl_fill_rows(frame_words, h);
+    uint16_t *d = nullptr;
+    if (int rc = upload_table_once(ctx, "ac3mi_encode_batch", &h[0][0], sizeof h, &d)) return rc;
+    ctx->crc_rows.emplace_back(frame_words, d);
+    *rows = d;
+    return AC3MI_OK;
+}
+
 // The encoder's part of a call of nfr frames (E.cfg set): grows the encoder's and the tools' workspaces, and fills E's
 // workspace arrays (the taps replace theirs), the tool settings and what else comes from the context.
 static int encode_setup(ac3mi_ctx *ctx, EncodeLaunch &E, const ac3mi_encode_desc *desc, size_t nfr, const ac3mi_encode_taps *taps)
@@ -1119,6 +1136,7 @@ static int encode_setup(ac3mi_ctx *ctx, EncodeLaunch &E, const ac3mi_encode_desc
     const size_t rows = nfr * 6 * E.cfg.nch;
     const EncWs W = enc_ws_layout(rows);
     TRY(ws_grow(ctx, ctx->ws_enc, W.need));
+    TRY(crc_rows_ready(ctx, E.cfg.frame_words, &E.crc_rows));
     if (t.block_switch) {
         TRY(ws_grow(ctx, ctx->ws_bsw, rows));
         E.ws_bsw = ctx->ws_bsw.at<uint8_t>();

@@ -6,8 +6,8 @@
 // One wavefront per frame, four frames per workgroup, every frame of the call in one launch before the decoder's front
 // end.  The header test and the frame's size (sync_rule.h's) run on wave-uniform values (the frame's first two dwords, a scalar read of their
 // own); then the frame is read once into LDS (16-byte loads where base and stride allow, else dwords).  Each lane then sums
-// a chunk of C bytes of a region through the 256-entry table (LDS), and six steps combine the 64 chunk sums: crc = left * x^(8 C 2^k) + crc in GF(2)[x] / poly, the scheme of
-// the encoder's region_crc (encode.hip).  Chunks are aligned to the region's END and the front is padded with zero bytes -
+// a chunk of C bytes of a region through the 256-entry table (LDS), and six steps combine the 64 chunk sums: crc = left * x^(8 C 2^k) + crc in GF(2)[x] / poly, the scheme
+// the encoder's packers had before the lane rule of crc_lanes.h.  Chunks are aligned to the region's END and the front is padded with zero bytes -
 // a zero prefix does not change a sum that starts at 0 - so one C and one set of power tables per region and call, sized
 // by the batch's largest frame, serve every frame size in the batch (44.1 kHz streams alternate between two).
 // The verdict is one byte per frame, stored by lane 0 (a vector store): bit 0 crc1's region fails, bit 1 crc2's, bit 6

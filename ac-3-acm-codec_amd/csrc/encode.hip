@@ -29,6 +29,7 @@
 #include "enc_syntax.h"
 #include "enc_exp.h"
 #include "snr_window.h"
+#include "crc_lanes.h"
 #include "mdct_rule.h"
 
 #include <type_traits>
@@ -65,11 +66,9 @@ struct PackParams {
     int nch, nfbw, lfe, acmod, fscod, halfrate, bsid, frmsizecod, frame_words;
     int nbc;                    // coefficients per full-bandwidth channel (223)
     int chbwcod;
-    // CRC constants as multiplication tables: entry i = constant * x^i mod poly, so that a product with a per-lane value is 16
-    // select-and-xor steps with no scalar chain (gf_mul_tab)
-    uint16_t crc_inv_t[16];     // x^-(16*fs58-16) mod poly (:1627)
-    uint16_t pw1_t[6][16], pw2_t[6][16];    // x^(8*C*2^k) mod poly for the two CRC regions
-    int c1, c2;                 // CRC chunk bytes per lane
+    // both CRC words by the lane rule (crc_lanes.h): the frame size's table in device memory, a row per lane, and its split
+    const uint16_t *crc_rows;   // [64][16]: entry j of lane i's row = the lane's constant * x^j mod poly
+    int crc_c, crc_n1;          // chunk bytes per lane; lanes of region 1
     int frw;                    // dwords of the frame buffer in (dynamic) LDS: the frame + 256 bytes of headroom, multiple of 4
     int marker;                 // the reference's "member already merged" value, 128 (:1375-1413); AC3MI_ENC_MARKER: test aid
     const uint32_t *hint;       // optional, [frame * hint_stride]: 16 csnroffst + fsnroffst the frame's SOURCE was coded with (transcode)
@@ -1490,35 +1489,21 @@ struct SnrSearch {
     }
 };
 
-// CRC-16 of `len` bytes ending at byte `end` (exclusive) of the MSB-first frame, per-lane chunks of C
-// bytes aligned to the end of the region, combined in GF(2)[x]/poly.  Bytes < zero_below count as 0.
-// a * t[0] in GF(2)[x]/poly for a table t[i] = t[0] * x^i mod poly (wave-uniform, from the kernel arguments)
-__device__ __forceinline__ uint32_t gf_mul_tab(uint32_t a, const uint16_t *t)
-{
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) c ^= (uint32_t)__builtin_amdgcn_sbfe((int)a, i, 1) & (uint32_t)t[i];
-    return c;
-}
-
+// Both CRC words of the staged frame (MSB-first dwords in LDS) by the lane rule of crc_lanes.h, on one whole wavefront:
+// crc1 in the low half, crc2 in the high half, wave-uniform.  The lane's row is requested first and travels during the byte
+// loop; nothing of it is live before this point.
 template <class LDS>
-__device__ uint32_t region_crc(const LDS &L, const uint32_t *fr, int end, int len, int C, const uint16_t (*pw)[16], int zero_below, int lane)
+__device__ __forceinline__ uint32_t frame_crcs(const LDS &L, const uint32_t *fr, const PackParams &P, int fs, int lane)
 {
-    const int start = end - 64 * C;                 // may be negative: leading zero padding
-    int p = start + lane * C;
-    uint32_t crc = 0;
-    for (int i = 0; i < C; i++, p++) {
-        uint32_t byte = 0;
-        if (p >= end - len && p >= zero_below) byte = (fr[p >> 2] >> (24 - 8 * (p & 3))) & 0xff;
-        crc = (L.crc_tab[byte ^ (crc >> 8)] ^ (crc << 8)) & 0xffff;
-    }
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        const int d = 1 << k;
-        const uint32_t left = __shfl_up(crc, d, 64);
-        if (((lane + 1) & (2 * d - 1)) == 0) crc = gf_mul_tab(left, pw[k]) ^ crc;
-    }
-    return __shfl(crc, 63, 64);
+    const uint4 *row = reinterpret_cast<const uint4 *>(P.crc_rows) + 2 * lane;
+    const uint4 r0 = row[0], r1 = row[1];
+    const CrcSplit sp{P.crc_c, P.crc_n1};
+    const CrcLane ln = crcl_lane(sp, fs, lane);
+    const uint32_t sum = crcl_chunk_sum(fr, L.crc_tab, ln.begin, sp.C, ln.lo);
+    const uint32_t r[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+    const uint32_t scan = wave_incl_scan_xor_u32(crcl_mul_row(sum, r));
+    const uint32_t crc1 = (uint32_t)__builtin_amdgcn_readlane((int)scan, sp.n1 - 1);
+    return crc1 | ((wave_last(scan) ^ crc1) << 16);
 }
 
 // PART 0: one wavefront per stream does everything, frames in order.
@@ -2527,18 +2512,15 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
     }
 
     // ---- frame end (:1599-1638): bytes past 2*fs are dropped, CRCs stored over whatever is there ----
-    const int fs58 = (fs >> 1) + (fs >> 3);
     // (the reference only zero-pads when the data is short; data bits beyond byte 2*fs-2 stay and are then overwritten by
     // crc2 - its own overshoot quirk)
-    uint32_t crc1 = region_crc(L, fr, 2 * fs58, 2 * fs58, P.c1, P.pw1_t, 4, lane);
-    crc1 = gf_mul_tab(crc1, P.crc_inv_t);
-    const uint32_t crc2 = region_crc(L, fr, 2 * fs - 2, (fs - fs58) * 2 - 2, P.c2, P.pw2_t, 0, lane);
+    const uint32_t crcs = frame_crcs(L, fr, P, fs, lane);
     wave_sync();
     if (lane == 0) {
-        fr[0] = (fr[0] & 0xffff0000u) | (crc1 & 0xffff);                      // bytes 2,3
+        fr[0] = (fr[0] & 0xffff0000u) | (crcs & 0xffff);                      // bytes 2,3
         const int p = 2 * fs - 2;                                                 // even -> inside one dword
         const int shft = 16 - 8 * (p & 3);
-        fr[p >> 2] = (fr[p >> 2] & ~(0xffffu << shft)) | ((crc2 & 0xffff) << shft);
+        fr[p >> 2] = (fr[p >> 2] & ~(0xffffu << shft)) | ((crcs >> 16) << shft);
     }
     wave_sync();
     uint8_t *dst = P.frames + fidx * P.frame_stride;
@@ -2557,7 +2539,7 @@ __global__ __launch_bounds__(64, ENC_PACK2_LB) void enc_packf_kernel(const PackP
 // wavefronts, one per AUDIO BLOCK.  Nothing but its first bit ties a block to the blocks before it, and that follows from
 // bit COUNTS: every wavefront first counts its block (side information from the strategies, mantissas from one table look-up
 // per coefficient), the counts meet in LDS, then all six pack at once into the frame they share (fields reach it by LDS
-// atomics, so neighbours may write into one dword); both CRCs run side by side on two wavefronts; 384 lanes store the frame.
+// atomics, so neighbours may write into one dword); both CRCs on one wavefront (crc_lanes.h); 384 lanes store the frame.
 // The reference's merged-code marker quirk (a grouped code whose value equals 128 is not written, :1466-1480) shortens a
 // block, i.e. moves every later block: any wavefront that meets one reports it, and the workgroup packs the frame once more
 // with those fields at width 0 - as enc_pack_kernel does per block.
@@ -2574,7 +2556,6 @@ struct alignas(16) PackbLDS {
     uint8_t band_of_bin[256];
     uint32_t blk_bits[6];           // bits of each block: nominal (from the bap codes) ...
     uint32_t blk_bits2[6];          // ... and as packed (a grouped code equal to the merged-marker takes none)
-    uint32_t crc[2];
     int any_coll;
 };
 
@@ -2717,22 +2698,15 @@ __global__ __launch_bounds__(384, ENC_PACKB_LB) void enc_packb_kernel(const Pack
         __syncthreads();
     }
 
-    // ---- frame end (:1599-1638): the two CRC regions on two wavefronts, then the frame goes out ----
-    const int fs58 = (fs >> 1) + (fs >> 3);
+    // ---- frame end (:1599-1638): both CRC regions on one wavefront, then the frame goes out ----
     if (b == 0) {
-        uint32_t crc1 = region_crc(L, fr, 2 * fs58, 2 * fs58, P.c1, P.pw1_t, 4, lane);
-        crc1 = gf_mul_tab(crc1, P.crc_inv_t);
-        if (lane == 0) L.crc[0] = crc1;
-    } else if (b == 1) {
-        const uint32_t crc2 = region_crc(L, fr, 2 * fs - 2, (fs - fs58) * 2 - 2, P.c2, P.pw2_t, 0, lane);
-        if (lane == 0) L.crc[1] = crc2;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        fr[0] = (fr[0] & 0xffff0000u) | (L.crc[0] & 0xffff);                      // bytes 2,3
-        const int p = 2 * fs - 2;                                                     // even -> inside one dword
-        const int shft = 16 - 8 * (p & 3);
-        fr[p >> 2] = (fr[p >> 2] & ~(0xffffu << shft)) | ((L.crc[1] & 0xffff) << shft);
+        const uint32_t crcs = frame_crcs(L, fr, P, fs, lane);
+        if (lane == 0) {
+            fr[0] = (fr[0] & 0xffff0000u) | (crcs & 0xffff);                      // bytes 2,3
+            const int p = 2 * fs - 2;                                                 // even -> inside one dword
+            const int shft = 16 - 8 * (p & 3);
+            fr[p >> 2] = (fr[p >> 2] & ~(0xffffu << shft)) | ((crcs >> 16) << shft);
+        }
     }
     __syncthreads();
     uint8_t *dst = P.frames + fidx * P.frame_stride;
@@ -2752,30 +2726,6 @@ extern "C" __attribute__((visibility("default"))) int ac3mi_debug_pack_cycles(un
     return 0;
 }
 #endif
-
-// ---------------------------------------------------------------------------------------------
-
-static uint32_t h_gf_mul(uint32_t a, uint32_t b)
-{
-    uint32_t c = 0;
-    while (a) {
-        if (a & 1) c ^= b;
-        a >>= 1;
-        b <<= 1;
-        if (b & 0x10000u) b ^= 0x18005u;
-    }
-    return c;
-}
-static uint32_t h_gf_pow(uint32_t a, uint32_t n)
-{
-    uint32_t r = 1;
-    while (n) {
-        if (n & 1) r = h_gf_mul(r, a);
-        a = h_gf_mul(a, a);
-        n >>= 1;
-    }
-    return r;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Dynamic range control (ac3mi_set_encode_drc; the rule is include/ac3mi.h's).  Two kernels before the search:
@@ -3083,18 +3033,12 @@ hipError_t launch_encode(const DeviceTables &tab, const EncodeLaunch &E, hipStre
     P.frame_words = c.frame_words;
     P.nbc = R.nbc;
     P.chbwcod = E.chbwcod;
-    const int fs = c.frame_words, fs58 = (fs >> 1) + (fs >> 3);
-    auto times_x = [](uint16_t *t, uint32_t v) {                    // t[i] = v * x^i mod poly
-        for (int i = 0; i < 16; i++) { t[i] = (uint16_t)v; v = h_gf_mul(v, 2); }
-    };
-    times_x(P.crc_inv_t, h_gf_pow(0x18005 >> 1, 16 * fs58 - 16));
-    const int len1 = 2 * fs58, len2 = (fs - fs58) * 2 - 2;
-    P.c1 = (len1 + 63) / 64;
-    P.c2 = (len2 + 63) / 64;
-    for (int k = 0; k < 6; k++) {
-        times_x(P.pw1_t[k], h_gf_pow(2, 8u * P.c1 * (1u << k)));
-        times_x(P.pw2_t[k], h_gf_pow(2, 8u * P.c2 * (1u << k)));
-    }
+    const int fs = c.frame_words;
+    if (!E.crc_rows) return hipErrorInvalidValue;
+    const CrcSplit split = crcl_split(fs);
+    P.crc_rows = E.crc_rows;
+    P.crc_c = split.C;
+    P.crc_n1 = split.n1;
     P.snr = E.ws_snr;
     P.memo = R.memo ? E.ws_memo : nullptr;
     P.hint = E.search_hint;
