@@ -4,8 +4,18 @@
 // (L52/downmix.c:162-330).  Operand types (int / float / double) and evaluation
 // order follow the reference so that the resulting floats are bit-identical; the
 // translation units that include this header are built with -ffp-contract=off.
+// Plain C++: compiles without HIP (dec_syntax.h and, through it, the sanitiser program of tests/dec_syntax_c include it).
 #pragma once
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#else
+#ifndef __host__
+#define __host__
+#endif
+#ifndef __device__
+#define __device__
+#endif
+#endif
 
 namespace ac3mi {
 

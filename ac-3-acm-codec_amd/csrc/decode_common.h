@@ -1,10 +1,11 @@
 // decode_common.h — device-side pieces shared by the two AC-3 front ends (decode.hip: one wavefront per stream or
 // per frame; decode_wg.hip: one workgroup per stream, one wavefront per channel, transform fused in): frame staging, the
-// header decision (sync_rule.h's rule) and the BSI skip, bit reader, exponent decode (L52/parse.c:218-270), parametric bit allocation (L52/bit_allocate.c:124-265), dither access.
+// header decision (sync_rule.h's rule), bit reader, the scalar-register state the field lists of dec_syntax.h (the one statement of
+// the side-information syntax) fill, exponent decode (L52/parse.c:218-270), parametric bit allocation (L52/bit_allocate.c:124-265), dither access.
 #pragma once
 #include <type_traits>
 #include "ac3mi_internal.h"
-#include "a52_levels.h"
+#include "dec_syntax.h"
 #include "sync_rule.h"
 #include "wave_ops.h"
 
@@ -19,11 +20,6 @@ constexpr int GRING = 128;                // see DecLDS::gcode
 constexpr int ROWS = 6 * ROW + LFE_ROW;
 __device__ __forceinline__ int row_off(int slot) { return slot < 5 ? slot * ROW : slot == 6 ? 5 * ROW : 6 * ROW; }
 
-__device__ const uint8_t k_nfchans[11] = {2, 1, 2, 3, 3, 4, 4, 5, 1, 1, 2};
-__device__ const float k_clev[4] = {(float)AC3MI_G_3DB, (float)AC3MI_G_45DB, (float)AC3MI_G_6DB, (float)AC3MI_G_45DB};
-__device__ const float k_slev[4] = {(float)AC3MI_G_3DB, (float)AC3MI_G_6DB, 0.f, (float)AC3MI_G_6DB};
-__device__ const uint8_t k_cpl_bnd0[16] = {31, 35, 37, 39, 41, 42, 43, 44, 45, 45, 46, 46, 47, 47, 48, 48};
-__device__ const int k_remat_edge[5] = {13, 25, 37, 61, 253};
 __device__ const int k_slowgain[4] = {0x540, 0x4d8, 0x478, 0x410};
 __device__ const int k_dbpb[4] = {0xc00, 0x500, 0x300, 0x100};
 __device__ const int k_floors[8] = {0x910, 0x950, 0x990, 0x9d0, 0xa10, 0xa90, 0xb10, 0x1400};
@@ -180,28 +176,13 @@ struct Rd {                                   // wave-uniform serial reader
     __device__ __forceinline__ void skip(uint32_t n) { seek(pos() + n); }
 };
 
-// The BSI behind lfeon, which the decoder reads past (a52_frame, parse.c:131-205): dialnorm, compr, langcod, audprodi (twice for 1+1),
-// copyrightb + origbs, the two timecodes, addbsi.  R: a reader with get(n) - Rd above, the workgroup kernel's VRd
-template <class R>
-__device__ __forceinline__ void skip_bsi_tail(R &rd, bool dual_mono)
-{
-    int twice = dual_mono;
-    do {
-        rd.get(5);
-        if (rd.get(1)) rd.get(8);
-        if (rd.get(1)) rd.get(8);
-        if (rd.get(1)) rd.get(7);
-    } while (twice--);
-    rd.get(2);
-    if (rd.get(1)) rd.get(14);
-    if (rd.get(1)) rd.get(14);
-    if (rd.get(1)) {
-        int len = rd.get(6);
-        do rd.get(8); while (len--);
-    }
-}
-
 __device__ __forceinline__ float sf_of(int e) { return __int_as_float((127 - 15 - e) << 23); }   // 2^-(15+e)
+// a coupling coordinate from its fields (parse.c:625-636)
+__device__ __forceinline__ float cplco_value(int ex, int ma, int master)
+{
+    ma = (ex == 15) ? (ma << 14) : ((ma | 0x10) << 13);
+    return (float)ma * sf_of(ex + master);
+}
 
 // liba52 drops the surround channels of such a frame from transform and mix instead of mixing them at level 0
 // (L52/downmix.c:494-583: the slev == 0 cases of MONO, STEREO and 3F outputs)
@@ -211,20 +192,31 @@ __device__ __forceinline__ int surround_level_is_zero(int acmod, int output, flo
     return ((acmod & 4) && slev == 0.f && (out == 1 || out == 2 || out == 3)) ? 1 : 0;
 }
 
-// stream-persistent decoder fields (wave-uniform)
+// stream-persistent decoder fields (wave-uniform), with the values a stream starts from: dynrnge 1, no deltba, the LFE ending at bin 7
 struct St {
-    int acmod, lfeon, nf;
-    float clev, slev, level, bias_unused, dynrng;
-    int output;
-    int chincpl, cplstrtmant;
-    uint32_t cplbndstrc;
+    int acmod = 0;
+#define AC3MI_ST_PLAIN(type, name) \
+    type name##_ = 0; \
+    __device__ __forceinline__ type name() const { return name##_; } \
+    __device__ __forceinline__ void set_##name(type v) { name##_ = v; }
+    AC3MI_ST_PLAIN(int, lfeon)
+    AC3MI_ST_PLAIN(int, nf)
+    AC3MI_ST_PLAIN(float, clev)
+    AC3MI_ST_PLAIN(float, slev)
+    AC3MI_ST_PLAIN(float, level)
+    AC3MI_ST_PLAIN(float, dynrng)
+    AC3MI_ST_PLAIN(int, output)
+    AC3MI_ST_PLAIN(int, chincpl)
+    AC3MI_ST_PLAIN(int, cplstrtmant)
+    AC3MI_ST_PLAIN(uint32_t, cplbndstrc)
+#undef AC3MI_ST_PLAIN
     // Everything else packed (round 4: the parse kernel spills scalar registers by the hundred; these fields were 38 of them,
     // and a slot picked at run time is now a shift instead of a chain of selects)
-    uint64_t ends;          // byte k: end of slot k's mantissas - 0..4 the full-bandwidth channels' endmant, 5: 7 (LFE), 6: cplendmant
-    uint64_t cbai8;         // byte k: slot k's fsnroffst << 3 | fgaincod (0..4 fbw, 5 lfe, 6 cpl)
-    uint32_t deltbae2;      // 2 bits per slot: 0..4 fbw, 5 = cpl
-    uint32_t cplw;          // phsflginu 0 | ncplbnd 1-5 | cplstrtbnd 6-11 | cplfleak 12-15 | cplsleak 16-19 | rematflg 20-23
-    uint32_t cfg;           // fscod 0-1 | halfrate 2-3 | dynrnge 4 | bai 5-15 | csnroffst 16-21
+    uint64_t ends = 7ull << 40;     // byte k: end of slot k's mantissas - 0..4 the full-bandwidth channels' endmant, 5: 7 (LFE), 6: cplendmant
+    uint64_t cbai8 = 0;     // byte k: slot k's fsnroffst << 3 | fgaincod (0..4 fbw, 5 lfe, 6 cpl)
+    uint32_t deltbae2 = 0xaaau;     // 2 bits per slot: 0..4 fbw, 5 = cpl
+    uint32_t cplw = 0;      // phsflginu 0 | ncplbnd 1-5 | cplstrtbnd 6-11 | cplfleak 12-15 | cplsleak 16-19 | rematflg 20-23
+    uint32_t cfg = 1u << 4; // fscod 0-1 | halfrate 2-3 | dynrnge 4 | bai 5-15 | csnroffst 16-21
     __device__ __forceinline__ int endm(int k) const { return (int)((uint32_t)(ends >> (8 * k)) & 0xffu); }
     __device__ __forceinline__ void set_endm(int k, int v) { ends = (ends & ~(0xffull << (8 * k))) | ((uint64_t)(uint32_t)v << (8 * k)); }
     __device__ __forceinline__ int cbai(int k) const { return (int)((uint32_t)(cbai8 >> (8 * k)) & 0xffu); }
@@ -232,6 +224,7 @@ struct St {
     __device__ __forceinline__ int deltbae(int k) const { return (int)((deltbae2 >> (2 * k)) & 3u); }
     __device__ __forceinline__ void set_deltbae(int k, int v) { deltbae2 = (deltbae2 & ~(3u << (2 * k))) | ((uint32_t)v << (2 * k)); }
     __device__ __forceinline__ int cplendmant() const { return endm(6); }
+    __device__ __forceinline__ void reset_deltbae() { deltbae2 = 0xaaau; }
 #define AC3MI_ST_FIELD(name, word, pos, bits) \
     __device__ __forceinline__ int name() const { return (int)((word >> (pos)) & ((1u << (bits)) - 1u)); } \
     __device__ __forceinline__ void set_##name(int v) { word = (word & ~(((1u << (bits)) - 1u) << (pos))) | ((uint32_t)v << (pos)); }

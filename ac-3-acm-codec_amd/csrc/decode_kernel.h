@@ -1,6 +1,8 @@
 // decode_kernel.h — decode_kernel<MODE, FX, SRC>, the front end of decode.hip (see there), as a header: decode.hip instantiates
 // it, and decode_src.hip instantiates the one variant that must not share a translation unit with its twin.
 // Which heads it refuses and a frame's own size: frame_own_bytes (decode_common.h) on sync_rule.h, as the workgroup kernel.
+// The side information it reads: the field lists of dec_syntax.h, as the workgroup kernel; its own are the reader (Rd), the state
+// (St) and the sink (DkSink), and everything computed from what was read.
 #pragma once
 #include "decode_common.h"
 #include "mant2.h"
@@ -34,12 +36,49 @@ __device__ unsigned long long g_dec_cycles[8];
 #define DK_T0() dk_t = __builtin_readcyclecounter()
 #define DK_LAP(id) do { const unsigned long long t_ = __builtin_readcyclecounter(); dk_acc[id] += t_ - dk_t; dk_t = t_; } while (0)
 #define DK_END() do { if (lane == 0) for (int i_ = 0; i_ < 6; i_++) atomicAdd(&g_dec_cycles[i_], dk_acc[i_]); } while (0)
+#define DK_SINK , dk_t, dk_acc
 #else
 #define DK_DECL() do { } while (0)
 #define DK_T0() do { } while (0)
 #define DK_LAP(id) do { } while (0)
 #define DK_END() do { } while (0)
+#define DK_SINK
 #endif
+
+// decode_kernel's sink of the field lists (dec_syntax.h): coupling coordinates and deltba rows into the wavefront's LDS, the
+// exponent groups read where they stand, dynamic-range words through the call's taps; SRC: the block's raw words collect in raw
+template <bool SRC>
+struct DkSink {
+    DecLDS &L;
+    const DecodeParams &P;
+    const FrameBits FB;
+    size_t blk_index;                   // fidx * 6 + blk
+    int lane;
+    uint32_t raw;
+#ifdef DEC_STAMPS
+    unsigned long long &dk_t, *dk_acc;
+#endif
+    __device__ __forceinline__ float dynrng(int code, int word, bool apply)
+    {
+        if constexpr (SRC) raw |= src_dyn_field(code, word);
+        return apply ? dynrng_range(P, code, blk_index * 2 + word, lane) : 0.f;
+    }
+    __device__ __forceinline__ void cplco(int ch, int bnd, int ex, int ma, int master)
+    {
+        const float co = cplco_value(ex, ma, master);
+        if (lane == 0) L.cplco[ch][bnd] = co;
+    }
+    __device__ __forceinline__ void cplco_flip(int bnd) { if (lane == 0) L.cplco[1][bnd] = -L.cplco[1][bnd]; }
+    __device__ __forceinline__ int exponents(int slot, int es, int ngrp, int e0, int start, uint32_t pos)
+    {
+        uint8_t *row = L.exp + row_off(slot);
+        if (slot != 6 && lane == 0) row[0] = (uint8_t)e0;
+        return read_exponents(FB, pos, es, ngrp, e0, row + (slot == 6 ? start : 1), lane);
+    }
+    __device__ __forceinline__ void deltba_clear(int slot) { if (lane < 50) L.deltba[slot][lane] = 0; }
+    __device__ __forceinline__ void deltba_seg(int slot, int band, int len, int d) { if (lane < len) L.deltba[slot][band + lane] = (int8_t)d; }
+    __device__ __forceinline__ void lap(int point) { if (point == 2) DK_LAP(1); }
+};
 
 // (crc_verdicts() reads DecodeParams::crc from the kernel-argument segment: P must stay this kernel's first argument)
 // FX (MODE 4; launch_decode's fixed-shape rule): one-frame 5.1 streams - a single frame (no frame loop, nothing carried from
@@ -85,17 +124,6 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
     ba_lane_band(L, lane, ba_lo0, ba_hi0);
 
     St st;
-    st.acmod = st.lfeon = 0;
-    st.nf = 0;
-    st.cfg = 1u << 4;                   // dynrnge 1, the rest 0
-    st.cplw = 0;
-    st.clev = st.slev = st.level = st.dynrng = 0.f;
-    st.output = 0;
-    st.chincpl = st.cplstrtmant = 0;
-    st.cplbndstrc = 0;
-    st.ends = 7ull << 40;
-    st.cbai8 = 0;
-    st.deltbae2 = 0xaaau;
     const int sslot = P.slot ? P.slot[s] : s;
     DK_DECL();
     st.lfsr = (MODE == 0 || MODE == 4) ? (uint32_t)P.lfsr_state[sslot] : 1u;
@@ -148,7 +176,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
         wave_sync();
 
         Rd rd{FB, 0, 0, 0};
-        // ---- a52_syncinfo (the header rule: sync_rule.h through frame_own_bytes) + a52_frame (parse.c:131-205) ----
+        // ---- a52_syncinfo (the header rule: sync_rule.h through frame_own_bytes) + a52_frame (dsyn_frame, dec_syntax.h) ----
         bool hdr_ok = true;
         if (const uint8_t *crcp = crc_verdicts())           // ac3mi_set_decode_crc 2: the CRC kernel's verdict (wave-uniform) refuses the frame
             if (crcp[fidx] & 0x40u) hdr_ok = false;
@@ -169,218 +197,51 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
             }
         }
         if (hdr_ok) {
-            int acmod = FX ? 7 : st.acmod;
             rd.seek(6 * 8 + 3);
-            if (acmod == 2 && rd.get(2) == 2) acmod = 10;                 // dsurmod -> DOLBY
-            st.clev = st.slev = 0.f;
-            if ((acmod & 1) && acmod != 1) st.clev = k_clev[rd.get(2)];
-            if (acmod & 4) st.slev = k_slev[rd.get(2)];
-            st.lfeon = rd.get(1);
-            if (st.lfeon != (FX ? 1 : P.lfeon)) hdr_ok = false;
-            float level = P.level;
-            st.output = a52_downmix_init_hd(acmod, P.req_flags, &level, st.clev, st.slev);
-            if (st.output < 0) hdr_ok = false;
+            const DsynRequest q{FX ? 1 : P.lfeon, P.req_flags, P.level, P.dynrng_on ? 1 : 0};
+            const int output = dsyn_frame(rd, st, FX ? 7 : st.acmod, q);
+            hdr_ok = output >= 0;
             if (hdr_ok) {
-                if ((FX || st.lfeon) && (P.req_flags & AC3MI_LFE)) st.output |= AC3MI_LFE;
-                st.dynrng = st.level = level * 2;
-                st.set_dynrnge(P.dynrng_on ? 1 : 0);
-                st.deltbae2 = 0xaaau;
-                skip_bsi_tail(rd, !acmod);
-                st.nf = FX ? 5 : k_nfchans[st.acmod];
                 if (hth_fscod != st.fscod()) {
                     if (lane < 50) L.hth[lane] = P.tab->hth[st.fscod()][lane];
                     hth_fscod = st.fscod();
                 }
-                status |= (uint32_t)st.output << 16;
+                status |= (uint32_t)output << 16;
             }
         }
         if (!hdr_ok) status |= 0x100u | 0x3fu;
 
         bool frame_dead = !hdr_ok;
         // (the blocks of a frame that passed the header test: its acmod and lfeon are the call's)
-        const int acm = FX ? 7 : st.acmod, lfeon = FX ? 1 : st.lfeon;
+        const int acm = FX ? 7 : st.acmod, lfeon = FX ? 1 : st.lfeon();
         DK_LAP(0);
         for (int blk = 0; blk < 6; blk++) {
             float *cblk = cout + (size_t)blk * n_in * 256;
             const int in_lfe = FX ? 1 : P.lfeon ? 1 : 0;
             int err = frame_dead ? 1 : 0;
-            int blkswm = 0, dithmask = 0;
+            DsynBlock sd{};                         // blksw / dithflag masks, strategies, the slots to allocate anew
             bool bd_ok = false;
             float gain[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-            const int nf = FX ? 5 : st.nf;
+            const int nf = FX ? 5 : st.nf();
 
             if (!err) do {
-                // ---- side information: parse.c:572-701 ----
-                // blksw[ch], dithflag[ch]: nf flags each, channel 0 first = in the field's top bit
-                blkswm = (int)(__builtin_bitreverse32(rd.get(nf)) >> (32 - nf));
-                dithmask = (int)(__builtin_bitreverse32(rd.get(nf)) >> (32 - nf));
-                int twice = !acm, word = 0;
-                [[maybe_unused]] uint32_t raw = 0;
-                do {
-                    if (rd.get(1)) {
-                        const int code = rd.sget(8);
-                        if constexpr (SRC) raw |= src_dyn_field(code, word);
-                        if (st.dynrnge()) st.dynrng = st.level * dynrng_range(P, code, (fidx * 6 + blk) * 2 + word, lane);
-                    }
-                    word++;
-                } while (twice--);
-                if constexpr (SRC) if (lane == 0) P.src_dyn[fidx * 6 + blk] = raw;
-
-                if (rd.get(1)) {                                            // cplstre
-                    st.chincpl = 0;
-                    if (rd.get(1)) {                                        // cplinu
-                        st.chincpl = (int)(__builtin_bitreverse32(rd.get(nf)) >> (32 - nf));
-                        if (acm < 2) { err = 1; break; }
-                        if (acm == 2) st.set_phsflginu(rd.get(1));
-                        const int begf = rd.get(4), endf = rd.get(4);
-                        if (endf + 3 - begf < 0) { err = 1; break; }
-                        const int nsub = endf + 3 - begf;
-                        int ncplbnd = nsub;
-                        st.set_cplstrtbnd(k_cpl_bnd0[begf]);
-                        st.cplstrtmant = begf * 12 + 37;
-                        st.set_endm(6, endf * 12 + 73);
-                        st.cplbndstrc = 0;
-                        for (int i = 0; i < nsub - 1; i++)
-                            if (rd.get(1)) { st.cplbndstrc |= 1u << i; ncplbnd--; }
-                        st.set_ncplbnd(ncplbnd);
-                    }
-                } else if (blk == 0) reuse0 = true;
-                if (st.chincpl) {                                           // coupling coordinates
-                    int any = 0;
-                    for (int i = 0; i < nf; i++)
-                        if ((st.chincpl >> i) & 1) {
-                            if (rd.get(1)) {
-                                const int master = 3 * rd.get(2);
-                                any = 1;
-                                for (int j = 0, nb = st.ncplbnd(); j < nb; j++) {
-                                    const int ex = rd.get(4);
-                                    int ma = rd.get(4);
-                                    ma = (ex == 15) ? (ma << 14) : ((ma | 0x10) << 13);
-                                    const float co = (float)ma * sf_of(ex + master);
-                                    if (lane == 0) L.cplco[i][j] = co;
-                                }
-                            } else if (blk == 0) reuse0 = true;
-                        }
-                    if (acm == 2 && st.phsflginu() && any)
-                        for (int j = 0, nb = st.ncplbnd(); j < nb; j++)
-                            if (rd.get(1) && lane == 0) L.cplco[1][j] = -L.cplco[1][j];
-                }
-                if (acm == 2) {
-                    if (rd.get(1)) {                                        // rematstr
-                        const int end = st.chincpl ? st.cplstrtmant : 253;
-                        int i = 0;
-                        int rematflg = 0;
-                        do rematflg |= rd.get(1) << i; while (k_remat_edge[1 + i++] < end);
-                        st.set_rematflg(rematflg);
-                    } else if (blk == 0) reuse0 = true;
-                }
-                int cplexpstr = 0, lfeexpstr = 0, chexp = 0;   // chexp: 2 bits per channel
-                if (st.chincpl) cplexpstr = rd.get(2);
-                {                                               // chexpstr[ch]: nf two-bit codes, channel 0 first
-                    const uint32_t r = __builtin_bitreverse32(rd.get(2 * nf)) >> (32 - 2 * nf);       // channel order right, each code's bits swapped
-                    chexp = (int)(((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u));
-                }
-                if (lfeon) lfeexpstr = rd.get(1);
-                if (blk == 0) {
-                    if (st.chincpl && !cplexpstr) reuse0 = true;
-                    if (lfeon && !lfeexpstr) reuse0 = true;
-                    for (int i = 0; i < nf; i++) if (!((chexp >> (2 * i)) & 3)) reuse0 = true;
-                }
-#pragma unroll
-                for (int i = 0; i < 5; i++)
-                    if (i < nf && !err && ((chexp >> (2 * i)) & 3)) {
-                        if ((st.chincpl >> i) & 1) st.set_endm(i, st.cplstrtmant);
-                        else {
-                            const int bw = rd.get(6);
-                            if (bw > 60) err = 1;
-                            else st.set_endm(i, bw * 3 + 73);
-                        }
-                    }
+                // ---- side information and exponents: the field lists of dec_syntax.h ----
+                DkSink<SRC> k{L, P, FB, fidx * 6 + blk, lane, 0u DK_SINK};
+                err = dsyn_block_a(rd, st, k, sd, blk, acm, nf, lfeon);
+                if constexpr (SRC) if (lane == 0) P.src_dyn[fidx * 6 + blk] = k.raw;
+                if (sd.reuse0) reuse0 = true;
                 if (err) break;
-
-                DK_LAP(1);
-                // ---- exponents: parse.c:703-736 ----
-                int redo = 0;
-                if (cplexpstr) {
-                    const int ngrp = (st.cplendmant() - st.cplstrtmant) / (3 << (cplexpstr - 1));
-                    const int e0 = rd.get(4) << 1;
-                    redo = 64;
-                    if (read_exponents(FB, rd.pos(), cplexpstr, ngrp, e0, L.exp + row_off(6) + st.cplstrtmant, lane)) { err = 1; break; }
-                    rd.skip(7 * ngrp);
-                }
-#pragma unroll
-                for (int i = 0; i < 5; i++) {
-                    const int es = (chexp >> (2 * i)) & 3;
-                    if (i < nf && !err && es) {
-                        const int gs = 3 << (es - 1), ngrp = (st.endm(i) + gs - 4) / gs;
-                        redo |= 1 << i;
-                        const int e0 = rd.get(4);
-                        if (lane == 0) L.exp[row_off(i)] = (uint8_t)e0;
-                        if (read_exponents(FB, rd.pos(), es, ngrp, e0, L.exp + row_off(i) + 1, lane)) err = 1;
-                        rd.skip(7 * ngrp);
-                        rd.get(2);                                          // gainrng
-                    }
-                }
-                if (err) break;
-                if (lfeexpstr) {
-                    redo |= 32;
-                    const int e0 = rd.get(4);
-                    if (lane == 0) L.exp[row_off(5)] = (uint8_t)e0;
-                    if (read_exponents(FB, rd.pos(), lfeexpstr, 2, e0, L.exp + row_off(5) + 1, lane)) { err = 1; break; }
-                    rd.skip(14);
-                }
-
                 DK_LAP(2);
-                dirty_exp |= redo;                                          // (bits: 0..4 fbw, 5 lfe, 6 coupling channel)
-                // ---- bit-allocation parameters: parse.c:738-772 ----
-                if (rd.get(1)) { redo = 127; st.set_bai(rd.get(11)); }
-                else if (blk == 0) reuse0 = true;
-                if (rd.get(1)) {
-                    redo = 127;
-                    st.set_csnroffst(rd.get(6));
-                    if (st.chincpl) st.set_cbai(6, rd.get(7));
-#pragma unroll
-                    for (int i = 0; i < 5; i++) if (i < nf) st.set_cbai(i, rd.get(7));
-                    if (lfeon) st.set_cbai(5, rd.get(7));
-                } else if (blk == 0) reuse0 = true;
-                if (st.chincpl) {
-                    if (rd.get(1)) {
-                        redo |= 64;
-                        st.set_cplfleak(9 - rd.get(3));
-                        st.set_cplsleak(9 - rd.get(3));
-                    } else if (blk == 0) reuse0 = true;
-                }
-                if (rd.get(1)) {                                            // deltbaie
-                    redo = 127;
-                    if (st.chincpl) st.set_deltbae(5, rd.get(2));
-#pragma unroll
-                    for (int i = 0; i < 5; i++) if (i < nf) st.set_deltbae(i, rd.get(2));
-#pragma unroll
-                    for (int pass = 0; pass < 6; pass++) {
-                        const int slot = pass == 0 ? 5 : pass - 1;          // cpl first, then fbw (parse.c:763-771)
-                        if (err || pass > nf) continue;
-                        if (slot == 5 && !st.chincpl) continue;
-                        if (st.deltbae(slot) != 1) continue;
-                        // parse_deltba: parse.c:272-294
-                        if (lane < 50) L.deltba[slot][lane] = 0;
-                        int nseg = rd.get(3), band = 0;
-                        do {
-                            band += rd.get(5);
-                            int len = rd.get(4), d = rd.get(3);
-                            d -= (d >= 4) ? 3 : 4;
-                            if (!len) continue;
-                            if (band + len >= 50) { err = 1; break; }
-                            if (lane < len) L.deltba[slot][band + lane] = (int8_t)d;
-                            band += len;
-                        } while (nseg--);
-                    }
-                    if (err) break;
-                }
+                dirty_exp |= sd.redo;                                       // (bits: 0..4 fbw, 5 lfe, 6 coupling channel)
+                err = dsyn_block_b(rd, st, k, sd, blk, nf, lfeon);
+                if (sd.reuse0) reuse0 = true;
+                if (err) break;
+                const int redo = sd.redo;
                 wave_sync();
 
                 // ---- bit allocation: parse.c:774-798 ----
                 if (redo) {
-                    bool allzero = !st.csnroffst() && !(st.chincpl && (st.cbai(6) >> 3)) && !(lfeon && (st.cbai(5) >> 3));
+                    bool allzero = !st.csnroffst() && !(st.chincpl() && (st.cbai(6) >> 3)) && !(lfeon && (st.cbai(5) >> 3));
 #pragma unroll
                     for (int i = 0; i < 5; i++)
                         if (i < nf && (st.cbai(i) >> 3)) allzero = false;
@@ -392,17 +253,17 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                         // the channel slots that need a new allocation, two per sweep of the band PSDs (wave-uniform; written
                         // out rather than as lambdas over `st`: a closure that holds its address keeps the whole state in scratch)
 #define AC3MI_SLOT_END(slot) st.endm(slot)
-                        int todo = redo & (((1 << nf) - 1) | (lfeon ? 32 : 0) | (st.chincpl ? 64 : 0));
+                        int todo = redo & (((1 << nf) - 1) | (lfeon ? 32 : 0) | (st.chincpl() ? 64 : 0));
 #pragma unroll
                         for (int i = 0; i < 5; i++) if (st.endm(i) <= 0) todo &= ~(1 << i);
-                        if (st.cplendmant() <= st.cplstrtmant) todo &= ~64;
+                        if (st.cplendmant() <= st.cplstrtmant()) todo &= ~64;
                         while (todo) {
                             const int sA = __builtin_ctz(todo);
                             todo &= todo - 1;
                             const bool two = todo != 0;
                             const int sB = two ? __builtin_ctz(todo) : sA;
                             if (two) todo &= todo - 1;
-                            const int stA = sA == 6 ? st.cplstrtmant : 0, stB = sB == 6 ? st.cplstrtmant : 0;
+                            const int stA = sA == 6 ? st.cplstrtmant() : 0, stB = sB == 6 ? st.cplstrtmant() : 0;
                             const int enA = AC3MI_SLOT_END(sA), enB = AC3MI_SLOT_END(sB);
                             const int wide = ba_wide_psd(L, ba_lo0, ba_hi0, L.exp + row_off(sA), stA, enA, L.exp + row_off(sB), stB, enB, two, lane);
                             for (int h = 0; h < (two ? 2 : 1); h++) {          // (one call site: the routine is inlined once)
@@ -419,11 +280,9 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                     }
                     wave_sync();
                 }
-                if (rd.get(1)) {                                            // skip field
-                    const int n = rd.get(9);
-                    rd.skip(8 * n);
-                }
+                dsyn_skip_field(rd);
             } while (0);
+            const int blkswm = sd.blkswm, dithmask = sd.dithmask;
 
             // optional stage taps
             if (!FX && P.tap_exp) {
@@ -440,11 +299,11 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
             if (!err) {
                 DK_LAP(3);
                 // ---- gains: parse.c:810-811 ----
-                a52_downmix_coeff_hd(gain, acm, st.output, st.dynrng, st.clev, st.slev);
+                a52_downmix_coeff_hd(gain, acm, st.output(), st.dynrng(), st.clev(), st.slev());
 
                 // ---- mantissas: the segments of the block in bitstream order (mant_block, decode_common.h) ----
-                if (!PARSE && st.chincpl && lane < 18) {                    // sub-band -> band (parse.c:448-456)
-                    const uint32_t below = st.cplbndstrc & ((1u << lane) - 1u);
+                if (!PARSE && st.chincpl() && lane < 18) {                    // sub-band -> band (parse.c:448-456)
+                    const uint32_t below = st.cplbndstrc() & ((1u << lane) - 1u);
                     L.cplbnd[lane] = (uint8_t)(lane - __popc(below));
                 }
                 SegBase sb;
@@ -453,11 +312,11 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                 if constexpr (!PARSE) {
                     MantBlk B;
                     B.nf = nf; B.lfeon = lfeon; B.acmod = acm; B.in_lfe = in_lfe;
-                    B.chincpl = st.chincpl; B.dithmask = dithmask; B.rematflg = st.rematflg();
-                    B.cplstrtmant = st.cplstrtmant; B.cplendmant = st.cplendmant();
+                    B.chincpl = st.chincpl(); B.dithmask = dithmask; B.rematflg = st.rematflg();
+                    B.cplstrtmant = st.cplstrtmant(); B.cplendmant = st.cplendmant();
 #pragma unroll
                     for (int i = 0; i < 5; i++) { B.endmant[i] = st.endm(i); B.gain[i] = gain[i]; }
-                    B.lfe_gain = (st.output & AC3MI_LFE) ? st.dynrng : 0.f;
+                    B.lfe_gain = (st.output() & AC3MI_LFE) ? st.dynrng() : 0.f;
                     const uint32_t lfsr_i0 = P.lfsr_idx[st.lfsr];
                     const bool lfsr_live = st.lfsr != 0;
                     mant_block<false>(B, [&](int slot) { return (const uint8_t *)L.exp + row_off(slot); },
@@ -471,14 +330,14 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                     // the dither draws of the block; rows that changed go to the workspace; the descriptor names them.
                     // Lane k takes segment k (the scalar unit is this kernel's bottleneck: a loop over the segments on
                     // wave-uniform values costs 600 scalar instructions per block, this form about 80 vector ones).
-                    const int cplfirst = st.chincpl ? __builtin_ctz(st.chincpl) : 99;
-                    const int nseg = nf + (st.chincpl ? 1 : 0) + (lfeon ? 1 : 0);
-                    const int ncpl_dith = __popc(st.chincpl & dithmask);
+                    const int cplfirst = st.chincpl() ? __builtin_ctz(st.chincpl()) : 99;
+                    const int nseg = nf + (st.chincpl() ? 1 : 0) + (lfeon ? 1 : 0);
+                    const int ncpl_dith = __popc(st.chincpl() & dithmask);
                     const int k = lane;
-                    const int slot_l = st.chincpl ? (k <= cplfirst ? k : k == cplfirst + 1 ? 6 : k - 1 < nf ? k - 1 : 5) : (k < nf ? k : 5);
+                    const int slot_l = st.chincpl() ? (k <= cplfirst ? k : k == cplfirst + 1 ? 6 : k - 1 < nf ? k - 1 : 5) : (k < nf ? k : 5);
                     const bool seg_l = k < nseg;
-                    const int end_l = (int)((uint32_t)(st.ends >> (8 * slot_l)) & 0xffu);
-                    const int start_l = slot_l == 6 ? st.cplstrtmant : 0;
+                    const int end_l = st.endm(slot_l);
+                    const int start_l = slot_l == 6 ? st.cplstrtmant() : 0;
                     const int mult_l = slot_l < 5 ? (dithmask >> slot_l) & 1 : slot_l == 6 ? ncpl_dith : 0;
                     const uint32_t key_l = 0x80000000u | (uint32_t)start_l | ((uint32_t)end_l << 10);
                     uint32_t ca = L.tot[slot_l][0], cb = L.tot[slot_l][1];
@@ -506,7 +365,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                     }
                     {
                         uint8_t *rowset = P.rows + (fidx * 6 + blk) * (size_t)ROWSET;
-                        const int used = ((1 << nf) - 1) | (lfeon ? 32 : 0) | (st.chincpl ? 64 : 0);
+                        const int used = ((1 << nf) - 1) | (lfeon ? 32 : 0) | (st.chincpl() ? 64 : 0);
                         const int we = dirty_exp & used, wb = dirty_bap & used;
                         for (int m = we; m; m &= m - 1) {
                             const int s0 = __builtin_ctz(m);
@@ -524,7 +383,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                         rv_exp = ((we >> lane) & 1) ? (uint32_t)blk : rv_exp;
                         rv_bap = ((wb >> lane) & 1) ? (uint32_t)blk : rv_bap;
                     }
-                    if (st.chincpl) {
+                    if (st.chincpl()) {
                         float *cc = P.cplco + (fidx * 6 + blk) * 90;
                         cc[lane] = (&L.cplco[0][0])[lane];
                         if (lane < 26) cc[64 + lane] = (&L.cplco[0][0])[64 + lane];
@@ -534,14 +393,14 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
                     // asserts that the members lie so)
                     {
                         uint8_t *dp = reinterpret_cast<uint8_t *>(P.desc + (fidx * 6 + blk));
-                        const uint32_t fl = ((uint32_t)st.chincpl << BLK_CHINCPL) | ((uint32_t)dithmask << BLK_DITH) | ((uint32_t)st.rematflg() << BLK_REMAT);
-                        const uint32_t w0 = lane == 0 ? rd.pos() : lane == 1 ? frame_draws : lane == 2 ? fl : st.cplbndstrc;
+                        const uint32_t fl = ((uint32_t)st.chincpl() << BLK_CHINCPL) | ((uint32_t)dithmask << BLK_DITH) | ((uint32_t)st.rematflg() << BLK_REMAT);
+                        const uint32_t w0 = lane == 0 ? rd.pos() : lane == 1 ? frame_draws : lane == 2 ? fl : st.cplbndstrc();
                         if (lane < 4) reinterpret_cast<uint32_t *>(dp)[lane] = w0;
-                        const int em = lane == 5 ? st.cplstrtmant : lane == 7 ? short_bytes : (int)((uint32_t)(st.ends >> (8 * (lane & 7))) & 0xffu);
+                        const int em = lane == 5 ? st.cplstrtmant() : lane == 7 ? short_bytes : st.endm(lane & 7);
                         if (lane < 8) reinterpret_cast<uint16_t *>(dp + offsetof(BlkDesc, endmant))[lane] = (uint16_t)em;
                         if (lane < 8) { dp[offsetof(BlkDesc, rv_exp) + lane] = (uint8_t)rv_exp; dp[offsetof(BlkDesc, rv_bap) + lane] = (uint8_t)rv_bap; }
                         const float gl = lane == 0 ? gain[0] : lane == 1 ? gain[1] : lane == 2 ? gain[2] : lane == 3 ? gain[3] : lane == 4 ? gain[4]
-                                       : (st.output & AC3MI_LFE) ? st.dynrng : 0.f;
+                                       : (st.output() & AC3MI_LFE) ? st.dynrng() : 0.f;
                         // src_snr: the frame's own SNR offsets, 16 csnroffst + fsnroffst of channel 0 - a transcode's encoder starts
                         // costing its search there (a hint: which offsets are costed never changes a result, encode.hip)
                         const uint32_t w12 = lane < 6 ? __float_as_uint(gl) : (uint32_t)(16 * st.csnroffst() + (st.cbai(0) >> 3));
@@ -585,7 +444,7 @@ __global__ __launch_bounds__(64, MODE >= 4 ? DEC_LBP : DEC_LB0) void decode_kern
             if (!(status & 0x100u) || (cv & 0x40u)) status |= (cv & 3u) << 10;
         }
         if (lane == 0) P.status[fidx] = status | (reuse0 ? 0x200u : 0u);
-        if (lane == 0 && P.zs) P.zs[fidx] = (uint8_t)((status & 0x100u) ? 0 : surround_level_is_zero(acm, st.output, st.slev));
+        if (lane == 0 && P.zs) P.zs[fidx] = (uint8_t)((status & 0x100u) ? 0 : surround_level_is_zero(acm, st.output(), st.slev()));
         if (MODE == 5 && lane == 0) P.frame_draws[fidx] = frame_draws;
         if (MODE == 4) {
             if (lane == 0) P.frame_pos[fidx] = pos_live ? lfsr_pos : 0xffffffffu;

@@ -30,7 +30,8 @@
 //
 // Built with -ffp-contract=off: dequantised coefficients are bit-identical to liba52's; the transform arithmetic is
 // xform_core.h's with its fused multiply-adds written out: the same bits as xform.hip produces from the same planes.
-// Staging, the header decision (sync_rule.h's rule) and the BSI skip are decode_common.h's, shared with decode.hip's kernels.
+// Staging and the header decision (sync_rule.h's rule) are decode_common.h's and the side-information syntax is dec_syntax.h's
+// field lists, both shared with decode.hip's kernels; the parser supplies its reader (VRd), state (PView) and sink (WgSink).
 #include "decode_common.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -132,12 +133,14 @@ struct WgParams {
 struct VRd {
     const uint32_t *w;
     uint32_t last;          // as FrameBits::last (words up to last + 1 exist)
-    uint32_t pos, base;
+    uint32_t at, base;      // the next bit; the window's first word
     uint32_t vwin;
     int lane;
+    __device__ __forceinline__ uint32_t pos() const { return at; }
+    __device__ __forceinline__ void skip(uint32_t n) { at += n; }
     __device__ __forceinline__ void load()
     {
-        base = pos >> 5;
+        base = at >> 5;
         uint32_t i = base + (uint32_t)lane;
         i = i < last + 1u ? i : last + 1u;
         vwin = w[i];
@@ -145,12 +148,12 @@ struct VRd {
     __device__ __forceinline__ uint32_t get(int n)
     {
         if (n == 0) return 0;
-        uint32_t wi = (pos >> 5) - base;
+        uint32_t wi = (at >> 5) - base;
         if (wi >= 63u) { load(); wi = 0; }
         const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)vwin, (int)wi);
         const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)vwin, (int)wi + 1);
-        const uint32_t v = (uint32_t)(((((uint64_t)hi << 32) | lo) << (pos & 31u)) >> (64 - n));
-        pos += (uint32_t)n;
+        const uint32_t v = (uint32_t)(((((uint64_t)hi << 32) | lo) << (at & 31u)) >> (64 - n));
+        at += (uint32_t)n;
         return v;
     }
     __device__ __forceinline__ int32_t sget(int n)
@@ -179,7 +182,7 @@ struct ParserState {
     int endmant[5];
     int bai, csnroffst, cbai[7], deltbae[6], cplfleak, cplsleak;
     uint32_t pos;               // the bit reader's position
-    int cplexpstr, lfeexpstr, chexp, redo;      // from the first to the second half of a block's side information
+    int redo;                   // from the first to the second half of a block's side information
     uint32_t status, reuse0;
     uint32_t crcv;              // the frame's CRC verdict byte (ac3mi_set_decode_crc), 0 when the frames are not checked
     int frame_dead;
@@ -190,213 +193,120 @@ struct ParserState {
 
 #define PSET(field, value) do { const auto pset_v_ = (value); if (lane == 0) (field) = pset_v_; } while (0)
 
-// ---- side information, first half: L52/parse.c:572-736 without the exponent payloads (their positions are recorded) ----
+// The state the field lists of dec_syntax.h fill, over ParserState: St's accessor names, read with ldsu and written with PSET
+struct PView {
+    ParserState &S;
+    int lane;
+#define PV_FIELD(type, name, read) \
+    __device__ __forceinline__ type name() const { return read; } \
+    __device__ __forceinline__ void set_##name(type v) { PSET(S.name, v); }
+#define PV_INT(name) PV_FIELD(int, name, ldsu(S.name))
+#define PV_SLOTS(name, member) \
+    __device__ __forceinline__ int name(int k) const { return ldsu(S.member[k]); } \
+    __device__ __forceinline__ void set_##name(int k, int v) { PSET(S.member[k], v); }
+    PV_INT(lfeon) PV_INT(nf) PV_INT(output) PV_INT(dynrnge) PV_INT(chincpl) PV_INT(phsflginu) PV_INT(cplstrtmant) PV_INT(ncplbnd)
+    PV_INT(cplstrtbnd) PV_INT(rematflg) PV_INT(bai) PV_INT(csnroffst) PV_INT(cplfleak) PV_INT(cplsleak)
+    PV_FIELD(float, clev, ldsf(S.clev)) PV_FIELD(float, slev, ldsf(S.slev)) PV_FIELD(float, level, ldsf(S.level)) PV_FIELD(float, dynrng, ldsf(S.dynrng))
+    PV_FIELD(uint32_t, cplbndstrc, (uint32_t)ldsu((const int &)S.cplbndstrc))
+    PV_SLOTS(cbai, cbai) PV_SLOTS(deltbae, deltbae)
+#undef PV_SLOTS
+#undef PV_INT
+#undef PV_FIELD
+    // slot 6: the coupling channel's end
+    __device__ __forceinline__ int endm(int k) const { return ldsu(k == 6 ? S.cplendmant : S.endmant[k]); }
+    __device__ __forceinline__ void set_endm(int k, int v) { PSET(k == 6 ? S.cplendmant : S.endmant[k], v); }
+    __device__ __forceinline__ void reset_deltbae() { if (lane < 6) S.deltbae[lane] = 2; }
+};
+
 #ifdef WG_STAMPS
 #define PSTAMP(i) do { if (dbg && lane == 0) dbg[i] = __builtin_readcyclecounter(); } while (0)
 #else
 #define PSTAMP(i) do { } while (0)
 #endif
+
+// The parser's sink of the field lists: coupling coordinates into the block's BlkInfo, exponent fields recorded, not read (the
+// channel waves decode them side by side), deltba rows into the workgroup's; SRC: the block's raw dynamic-range words in raw
+template <bool SRC>
+struct WgSink {
+    BlkInfo &B;
+    int8_t (*deltba)[52];
+    const DecodeParams &P;
+    size_t blk_index;                   // fidx * 6 + blk
+    int lane;
+    unsigned long long *dbg;
+    uint32_t raw;
+    __device__ __forceinline__ float dynrng(int code, int word, bool apply)
+    {
+        if constexpr (SRC) raw |= src_dyn_field(code, word);
+        return apply ? dynrng_range(P, code, blk_index * 2 + word, lane) : 0.f;
+    }
+    __device__ __forceinline__ void cplco(int ch, int bnd, int ex, int ma, int master)
+    {
+        const float co = cplco_value(ex, ma, master);
+        if (lane == 0) B.cplco[ch][bnd] = co;
+    }
+    __device__ __forceinline__ void cplco_flip(int bnd) { if (lane == 0) B.cplco[1][bnd] = -B.cplco[1][bnd]; }
+    __device__ __forceinline__ int exponents(int slot, int, int ngrp, int e0, int, uint32_t pos)
+    {
+        if (lane == 0) { B.absexp[slot] = e0; B.exp_pos[slot] = (int)pos; B.ngrp[slot] = ngrp; }
+        return 0;
+    }
+    __device__ __forceinline__ void deltba_clear(int slot) { if (lane < 50) deltba[slot][lane] = 0; }
+    __device__ __forceinline__ void deltba_seg(int slot, int band, int len, int d) { if (lane < len) deltba[slot][band + lane] = (int8_t)d; }
+    __device__ __forceinline__ void lap(int point) { PSTAMP(2 + point); }
+};
+
+// ---- side information, first half (dsyn_block_a): the exponent payloads are skipped, their positions recorded ----
 template <bool SRC = false>
 __device__ __forceinline__ void parse_block_a(const FrameBits FB, ParserState &S, BlkInfo &B, const BlkInfo &prev, int blk, int lane, const DecodeParams &P, size_t fidx,
                               unsigned long long *dbg = nullptr)
 {
     PSTAMP(0);
     VRd rd = make_reader(FB, (uint32_t)ldsu((const int &)S.pos), lane);
-    const int nf = ldsu(S.nf), acmod = ldsu(S.acmod), lfeon = ldsu(S.lfeon);
-    int err = 0, blkswm = 0, dithmask = 0, reuse0 = 0;
-    int cplexpstr = 0, lfeexpstr = 0, chexp = 0, redo = 0;
+    PView st{S, lane};
+    WgSink<SRC> k{B, nullptr, P, fidx * 6 + blk, lane, dbg, 0u};
+    DsynBlock sd;
     // coupling coordinates persist from block to block (and frame to frame)
     for (int i = lane; i < 90; i += 64) (&B.cplco[0][0])[i] = (&prev.cplco[0][0])[i];
     PSTAMP(1);
-    do {
-        for (int i = 0; i < nf; i++) blkswm |= rd.get(1) << i;
-        for (int i = 0; i < nf; i++) dithmask |= rd.get(1) << i;
-        int twice = !acmod, word = 0;
-        [[maybe_unused]] uint32_t raw = 0;
-        do {
-            if (rd.get(1)) {
-                const int code = rd.sget(8);
-                if constexpr (SRC) raw |= src_dyn_field(code, word);
-                if (ldsu(S.dynrnge)) PSET(S.dynrng, ldsf(S.level) * dynrng_range(P, code, (fidx * 6 + blk) * 2 + word, lane));
-            }
-            word++;
-        } while (twice--);
-        if constexpr (SRC) if (lane == 0) P.src_dyn[fidx * 6 + blk] = raw;
-
-        PSTAMP(2);
-        int chincpl = ldsu(S.chincpl);
-        if (rd.get(1)) {                                            // cplstre
-            chincpl = 0;
-            if (rd.get(1)) {                                        // cplinu
-                for (int i = 0; i < nf; i++) chincpl |= rd.get(1) << i;
-                PSET(S.chincpl, chincpl);
-                if (acmod < 2) { err = 1; break; }
-                if (acmod == 2) PSET(S.phsflginu, (int)rd.get(1));
-                const int begf = rd.get(4), endf = rd.get(4);
-                if (endf + 3 - begf < 0) { err = 1; break; }
-                const int nsub = endf + 3 - begf;
-                int ncplbnd = nsub;
-                uint32_t strc = 0;
-                for (int i = 0; i < nsub - 1; i++)
-                    if (rd.get(1)) { strc |= 1u << i; ncplbnd--; }
-                PSET(S.ncplbnd, ncplbnd);
-                PSET(S.cplstrtbnd, (int)k_cpl_bnd0[begf]);
-                PSET(S.cplstrtmant, begf * 12 + 37);
-                PSET(S.cplendmant, endf * 12 + 73);
-                PSET(S.cplbndstrc, strc);
-            } else PSET(S.chincpl, 0);
-        } else if (blk == 0) reuse0 = 1;
-        if (chincpl) {                                              // coupling coordinates
-            const int ncplbnd = ldsu(S.ncplbnd);
-            int any = 0;
-            for (int i = 0; i < nf; i++)
-                if ((chincpl >> i) & 1) {
-                    if (rd.get(1)) {
-                        const int master = 3 * rd.get(2);
-                        any = 1;
-                        for (int j = 0; j < ncplbnd; j++) {
-                            const int ex = rd.get(4);
-                            int ma = rd.get(4);
-                            ma = (ex == 15) ? (ma << 14) : ((ma | 0x10) << 13);
-                            const float co = (float)ma * sf_of(ex + master);
-                            if (lane == 0) B.cplco[i][j] = co;
-                        }
-                    } else if (blk == 0) reuse0 = 1;
-                }
-            if (acmod == 2 && ldsu(S.phsflginu) && any)
-                for (int j = 0; j < ncplbnd; j++)
-                    if (rd.get(1) && lane == 0) B.cplco[1][j] = -B.cplco[1][j];
-        }
-        if (acmod == 2) {
-            if (rd.get(1)) {                                        // rematstr
-                const int end = chincpl ? ldsu(S.cplstrtmant) : 253;
-                int i = 0, flg = 0;
-                do flg |= rd.get(1) << i; while (k_remat_edge[1 + i++] < end);
-                PSET(S.rematflg, flg);
-            } else if (blk == 0) reuse0 = 1;
-        }
-        PSTAMP(3);
-        if (chincpl) cplexpstr = rd.get(2);
-        for (int i = 0; i < nf; i++) chexp |= rd.get(2) << (2 * i);
-        if (lfeon) lfeexpstr = rd.get(1);
-        if (blk == 0) {
-            if (chincpl && !cplexpstr) reuse0 = 1;
-            if (lfeon && !lfeexpstr) reuse0 = 1;
-            for (int i = 0; i < nf; i++) if (!((chexp >> (2 * i)) & 3)) reuse0 = 1;
-        }
-        const int cplstrtmant = ldsu(S.cplstrtmant), cplendmant = ldsu(S.cplendmant);
-        for (int i = 0; i < nf; i++)
-            if (!err && ((chexp >> (2 * i)) & 3)) {
-                if ((chincpl >> i) & 1) PSET(S.endmant[i], cplstrtmant);
-                else {
-                    const int bw = rd.get(6);
-                    if (bw > 60) err = 1;
-                    else PSET(S.endmant[i], bw * 3 + 73);
-                }
-            }
-        PSTAMP(4);
-        if (err) break;
-        // exponent fields: recorded, not read (the channel waves decode them side by side)
-        if (cplexpstr) {
-            const int ngrp = (cplendmant - cplstrtmant) / (3 << (cplexpstr - 1));
-            const int e0 = rd.get(4) << 1;
-            redo = 64;
-            if (lane == 0) { B.absexp[6] = e0; B.exp_pos[6] = (int)rd.pos; B.ngrp[6] = ngrp; }
-            rd.pos += 7 * ngrp;
-        }
-        for (int i = 0; i < nf; i++) {
-            const int es = (chexp >> (2 * i)) & 3;
-            if (es) {
-                const int gs = 3 << (es - 1), ngrp = (ldsu(S.endmant[i]) + gs - 4) / gs;
-                redo |= 1 << i;
-                const int e0 = rd.get(4);
-                if (lane == 0) { B.absexp[i] = e0; B.exp_pos[i] = (int)rd.pos; B.ngrp[i] = ngrp; }
-                rd.pos += 7 * ngrp;
-                rd.get(2);                                          // gainrng
-            }
-        }
-        if (lfeexpstr) {
-            redo |= 32;
-            const int e0 = rd.get(4);
-            if (lane == 0) { B.absexp[5] = e0; B.exp_pos[5] = (int)rd.pos; B.ngrp[5] = 2; }
-            rd.pos += 14;
-        }
-    } while (0);
+    const int err = dsyn_block_a(rd, st, k, sd, blk, ldsu(S.acmod), st.nf(), st.lfeon());
+    if constexpr (SRC) if (lane == 0) P.src_dyn[fidx * 6 + blk] = k.raw;
     PSTAMP(5);
     if (lane == 0) {
         B.err = err;
-        B.blkswm = blkswm;
-        B.dithmask = dithmask;
-        for (int i = 0; i < 5; i++) B.expstr[i] = (chexp >> (2 * i)) & 3;
-        B.expstr[5] = lfeexpstr;
-        B.expstr[6] = cplexpstr;
-        S.pos = rd.pos;
-        S.cplexpstr = cplexpstr;
-        S.lfeexpstr = lfeexpstr;
-        S.chexp = chexp;
-        S.redo = redo;
-        if (reuse0) S.reuse0 = 1;
+        B.blkswm = sd.blkswm;
+        B.dithmask = sd.dithmask;
+        for (int i = 0; i < 5; i++) B.expstr[i] = (sd.chexp >> (2 * i)) & 3;
+        B.expstr[5] = sd.lfeexpstr;
+        B.expstr[6] = sd.cplexpstr;
+        S.pos = rd.pos();
+        S.redo = sd.redo;
+        if (sd.reuse0) S.reuse0 = 1;
     }
     // sub-band -> band of the coupling channel (parse.c:448-456): one lane per sub-band
     if (lane < 18) {
-        const uint32_t below = (uint32_t)ldsu((const int &)S.cplbndstrc) & ((1u << lane) - 1u);
+        const uint32_t below = st.cplbndstrc() & ((1u << lane) - 1u);
         B.cplbnd[lane] = (uint8_t)(lane - __popc(below));
     }
     PSTAMP(6);
 }
 
-// ---- second half: bit-allocation parameters, delta bit allocation, skip field (parse.c:738-772, 800-804) ----
-__device__ __forceinline__ void parse_block_b(const FrameBits FB, ParserState &S, BlkInfo &B, int8_t (*deltba)[52], int blk, int lane)
+// ---- second half (dsyn_block_b, dsyn_skip_field), and what the channel waves and the transformer need of the block ----
+__device__ __forceinline__ void parse_block_b(const FrameBits FB, ParserState &S, BlkInfo &B, int8_t (*deltba)[52], int blk, int lane, const DecodeParams &P)
 {
     VRd rd = make_reader(FB, (uint32_t)ldsu((const int &)S.pos), lane);
-    const int nf = ldsu(S.nf), lfeon = ldsu(S.lfeon), chincpl = ldsu(S.chincpl), acmod = ldsu(S.acmod);
-    int err = ldsu(B.err), redo = ldsu(S.redo), reuse0 = 0;
-    if (!err) do {
-        if (rd.get(1)) { redo = 127; PSET(S.bai, (int)rd.get(11)); }
-        else if (blk == 0) reuse0 = 1;
-        if (rd.get(1)) {
-            redo = 127;
-            PSET(S.csnroffst, (int)rd.get(6));
-            if (chincpl) PSET(S.cbai[6], (int)rd.get(7));
-            for (int i = 0; i < nf; i++) PSET(S.cbai[i], (int)rd.get(7));
-            if (lfeon) PSET(S.cbai[5], (int)rd.get(7));
-        } else if (blk == 0) reuse0 = 1;
-        if (chincpl) {
-            if (rd.get(1)) {
-                redo |= 64;
-                PSET(S.cplfleak, 9 - (int)rd.get(3));
-                PSET(S.cplsleak, 9 - (int)rd.get(3));
-            } else if (blk == 0) reuse0 = 1;
-        }
-        if (rd.get(1)) {                                            // deltbaie
-            redo = 127;
-            if (chincpl) PSET(S.deltbae[5], (int)rd.get(2));
-            for (int i = 0; i < nf; i++) PSET(S.deltbae[i], (int)rd.get(2));
-            for (int pass = 0; pass <= nf && !err; pass++) {
-                const int slot = pass == 0 ? 5 : pass - 1;          // cpl first, then fbw (parse.c:763-771)
-                if (slot == 5 && !chincpl) continue;
-                if (ldsu(S.deltbae[slot]) != 1) continue;
-                if (lane < 50) deltba[slot][lane] = 0;              // parse_deltba: parse.c:272-294
-                int nseg = rd.get(3), band = 0;
-                do {
-                    band += rd.get(5);
-                    int len = rd.get(4), d = rd.get(3);
-                    d -= (d >= 4) ? 3 : 4;
-                    if (!len) continue;
-                    if (band + len >= 50) { err = 1; break; }
-                    if (lane < len) deltba[slot][band + lane] = (int8_t)d;
-                    band += len;
-                } while (nseg--);
-            }
-            if (err) break;
-        }
-        if (rd.get(1)) {                                            // skip field
-            const int n = rd.get(9);
-            rd.pos += 8 * n;
-        }
-    } while (0);
+    PView st{S, lane};
+    const int nf = st.nf(), lfeon = st.lfeon(), chincpl = st.chincpl(), acmod = ldsu(S.acmod);
+    int err = ldsu(B.err);
+    DsynBlock sd{};
+    sd.redo = ldsu(S.redo);
+    if (!err) {
+        WgSink<false> k{B, deltba, P, 0, lane, nullptr, 0u};
+        err = dsyn_block_b(rd, st, k, sd, blk, nf, lfeon);
+        if (!err) dsyn_skip_field(rd);
+    }
     wave_sync();
-    // publish what the channel waves and the transformer need (one field per lane where it is a plain copy)
+    // (one field per lane where it is a plain copy)
     const int csnroffst = ldsu(S.csnroffst);
     bool allzero = !csnroffst && !(chincpl && (ldsu(S.cbai[6]) >> 3)) && !(lfeon && (ldsu(S.cbai[5]) >> 3));
     for (int i = 0; i < nf; i++)
@@ -412,7 +322,7 @@ __device__ __forceinline__ void parse_block_b(const FrameBits FB, ParserState &S
         const int e0 = S.endmant[0], e1 = S.endmant[1], rematflg = acmod == 2 ? S.rematflg : 0;
         B.err = err;
         B.halfrate = S.halfrate;
-        B.mant_pos = (int)rd.pos;
+        B.mant_pos = (int)rd.pos();
         B.chincpl = chincpl;
         B.cplstrtmant = S.cplstrtmant;
         B.cplendmant = S.cplendmant;
@@ -421,19 +331,19 @@ __device__ __forceinline__ void parse_block_b(const FrameBits FB, ParserState &S
         B.remat_end = e0 < e1 ? e0 : e1;
         B.need_fix = (chincpl || rematflg) ? 1 : 0;
         B.gain[0] = gain[0]; B.gain[1] = gain[1]; B.gain[2] = gain[2]; B.gain[3] = gain[3]; B.gain[4] = gain[4];
-        B.redo = redo;
+        B.redo = sd.redo;
         B.allzero = allzero ? 1 : 0;
         B.bai = S.bai;
         B.csnroffst = csnroffst;
         B.cplfleak = S.cplfleak;
         B.cplsleak = S.cplsleak;
         B.lfe_gain = (output & AC3MI_LFE) ? dynrng : 0.f;
-        S.pos = rd.pos;
-        if (reuse0) S.reuse0 = 1;
+        S.pos = rd.pos();
+        if (sd.reuse0) S.reuse0 = 1;
     }
 }
 
-// ---- a52_syncinfo (frame_own_bytes) + a52_frame (parse.c:131-205): frame header and BSI; returns false for a frame the
+// ---- a52_syncinfo (frame_own_bytes) + a52_frame (dsyn_frame): frame header and BSI; returns false for a frame the
 // batch cannot hold (no sync word, other channel configuration, too long, an output liba52 would refuse) ----
 __device__ __forceinline__ bool parse_frame_header(const FrameBits FB, uint32_t *frw, ParserState &S, uint16_t *hth, const DecodeParams &P, int lane)
 {
@@ -450,37 +360,18 @@ __device__ __forceinline__ bool parse_frame_header(const FrameBits FB, uint32_t 
         wave_sync();
     }
     VRd rd = make_reader(FB, 6 * 8 + 3, lane);
-    int acmod = acmod0;
-    if (acmod == 2 && rd.get(2) == 2) acmod = 10;                 // dsurmod -> DOLBY
-    float clev = 0.f, slev = 0.f;
-    if ((acmod & 1) && acmod != 1) clev = k_clev[rd.get(2)];
-    if (acmod & 4) slev = k_slev[rd.get(2)];
-    PSET(S.clev, clev);
-    PSET(S.slev, slev);
-    const int lfeon = rd.get(1);
-    PSET(S.lfeon, lfeon);
-    if (lfeon != P.lfeon) return false;
-    float level = P.level;
-    int output = a52_downmix_init_hd(acmod, P.req_flags, &level, clev, slev);
+    PView st{S, lane};
+    const DsynRequest q{P.lfeon, P.req_flags, P.level, P.dynrng_on};
+    const int output = dsyn_frame(rd, st, acmod0, q);
     if (output < 0) return false;
-    if (lfeon && (P.req_flags & AC3MI_LFE)) output |= AC3MI_LFE;
-    PSET(S.output, output);
-    PSET(S.level, level * 2);
-    PSET(S.dynrng, level * 2);
-    PSET(S.dynrnge, P.dynrng_on);
-    if (lane < 6) S.deltbae[lane] = 2;
-    skip_bsi_tail(rd, !acmod);
-    PSET(S.nf, (int)k_nfchans[acmod0]);
     if (ldsu(S.hth_fscod) != fscod) {
         if (lane < 50) hth[lane] = P.tab->hth[fscod][lane];
         PSET(S.hth_fscod, fscod);
     }
-    PSET(S.pos, rd.pos);
+    PSET(S.pos, rd.pos());
     PSET(S.status, (uint32_t)output << 16);
     return true;
 }
-
-
 
 // ---- T1 of one slot: exponents, bit allocation, census --------------------------------------------------------------
 __device__ __forceinline__ void slot_t1(WgLDS &L, const BlkInfo &B, const FrameBits FB, int slot, int wave, int lane)
@@ -801,7 +692,7 @@ __global__ __launch_bounds__(512, WG_LB) void decode_wg_kernel(const WgParams W)
                 if (ok) {
                     parse_block_a<SRC>(FB, S, B0, L.bi[1], 0, lane, P, fidx);
                     wave_sync();
-                    parse_block_b(FB, S, B0, L.deltba, 0, lane);
+                    parse_block_b(FB, S, B0, L.deltba, 0, lane, P);
                 } else PSET(B0.err, 1);
                 wave_sync();
                 if (lane == 0) {
@@ -982,7 +873,7 @@ __global__ __launch_bounds__(512, WG_LB) void decode_wg_kernel(const WgParams W)
                 } else if (wave == W_PARSE) {
                     if (blk < 5) {
                         const int dead = ldsu(S.frame_dead);
-                        if (!dead) parse_block_b(FB, S, Bn, L.deltba, blk + 1, lane);
+                        if (!dead) parse_block_b(FB, S, Bn, L.deltba, blk + 1, lane, P);
                         wave_sync();
                         if (lane == 0) {
                             Bn.lfsr_i0 = S.lfsr_idx;

@@ -44,7 +44,7 @@ __host__ __device__ inline bool sync_header_ok_le(uint32_t w0, uint32_t w1)
 }
 
 // full-bandwidth channels of an acmod (A/52 table 5.8) and of liba52's three output configurations behind them (8 and 9:
-// one programme of dual mono, 10: Dolby surround stereo); the kernels read k_nfchans (decode_common.h)
+// one programme of dual mono, 10: Dolby surround stereo); the decoder's field lists have their own table (dec_syntax.h)
 __host__ __device__ inline int sync_nfchans(int cfg)
 {
     constexpr uint8_t n[11] = {2, 1, 2, 3, 3, 4, 4, 5, 1, 1, 2};

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B timing aid: ms per pass of ac3mi_decode_s16_batch over 65 536 bench-like one-frame streams for the decode modes
-given on the command line (default 3 1), with the library AC3MI_LIB points at.   python profiles/decode_ab.py [S] [modes...]"""
+given on the command line (default 3 1), with the library AC3MI_LIB points at; AC3MI_FIXED_SHAPE=0: the fixed-shape kernels off.   python profiles/decode_ab.py [S] [modes...]"""
 import importlib
 import os
 import sys
@@ -33,6 +33,8 @@ lfsr = torch.ones((S,), dtype=torch.int16, device=dev)
 out = torch.empty((S, 1, 6, 256, 6), dtype=torch.int16, device=dev)
 status = torch.zeros((S, 1), dtype=torch.int32, device=dev)
 torch.cuda.synchronize()
+if os.environ.get("AC3MI_FIXED_SHAPE") == "0":            # the generic kernels (A/B runs of decode_kernel<4>, <5>, <0>)
+    eng.set_fixed_shape(0)
 for mode in modes:
     eng.set_decode_mode(mode)
     for _ in range(2):

@@ -42,6 +42,33 @@ def pkg():
     return importlib.import_module("ac-3-acm-codec_amd")
 
 
+CSRC = os.path.join(ROOT, "ac-3-acm-codec_amd", "csrc")
+SANITISE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"]
+_LANG = {"c++": ["g++", "-std=c++17"], "c": ["gcc", "-std=c99"], "hip": ["g++", "-std=c++17", "-x", "c++"]}
+
+
+def build_sanitised(sources, exe, lang=None, includes=()):
+    """The one recipe of the stand-alone sanitiser programs: `sources` built by the host compiler with SANITISE, -Wall -Werror,
+    into the program `exe`, which the caller runs on its own (never loaded into Python).  One source is compiled and linked
+    in one call; several are compiled to objects beside `exe` and linked by g++.  lang: "c++", "c" or "hip" for every source,
+    by default each one's by its suffix (.cpp, .c; .hip: a kernel file's host-only translation, compiled as C++).  includes:
+    -I directories of the .c and .cpp sources (a .hip source finds its headers beside itself)."""
+    def compile_(src):
+        kind = lang or {".cpp": "c++", ".c": "c", ".hip": "hip"}[os.path.splitext(src)[1]]
+        inc = [] if kind == "hip" else [a for d in includes for a in ("-I", d)]
+        return _LANG[kind] + SANITISE + ["-Wall", "-Werror"] + inc
+    if len(sources) == 1:
+        cmds = [compile_(sources[0]) + [sources[0], "-o", exe]]
+    else:
+        objs = [os.path.join(os.path.dirname(exe), os.path.splitext(os.path.basename(s))[0] + ".o") for s in sources]
+        assert len(set(objs)) == len(objs)
+        cmds = [compile_(s) + ["-c", s, "-o", o] for s, o in zip(sources, objs)] + [["g++"] + SANITISE + objs + ["-o", exe]]
+    for cmd in cmds:
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+    return exe
+
+
 def P(a, t):
     return a.ctypes.data_as(t)
 

@@ -16,11 +16,8 @@ from tests import crc_model as M
 @pytest.fixture(scope="module")
 def program_output(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("crc_lanes")
-    csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
     exe = str(tmp / "crc_lanes")
-    r = subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1", "-Wall", "-Werror",
-                        "-I", csrc, os.path.join(H.ROOT, "tests", "crc_lanes_c", "main.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.build_sanitised([os.path.join(H.ROOT, "tests", "crc_lanes_c", "main.cpp")], exe, includes=[H.CSRC])
     r = subprocess.run([exe, "20261"], capture_output=True, text=True)
     assert r.returncode == 0 and r.stderr == "", r.stderr[-2000:]
     return r.stdout.splitlines()

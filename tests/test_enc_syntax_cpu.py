@@ -23,11 +23,8 @@ def _ints(s):
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("enc_syntax")
-    csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
     exe = str(tmp / "enc_syntax")
-    r = subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1", "-Wall", "-Werror",
-                        "-I", csrc, os.path.join(H.ROOT, "tests", "enc_syntax_c", "main.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.build_sanitised([os.path.join(H.ROOT, "tests", "enc_syntax_c", "main.cpp")], exe, includes=[H.CSRC])
     return exe
 
 

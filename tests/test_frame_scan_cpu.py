@@ -156,16 +156,7 @@ def test_argument_refusals():
 def test_host_scan_under_the_sanitisers(tmp_path):
     """tests/frame_scan_c/scan_main.c with a host-only translation of csrc/scan.hip, both built with
     -fsanitize=address,undefined and run on the CPU: the model's lists, and not a word from either sanitiser"""
-    csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
-    inc = os.path.join(H.ROOT, "include")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"]
-    exe = str(tmp_path / "scan_main")
-    for cmd in (["g++", "-std=c++17", "-x", "c++"] + san + ["-Wall", "-Werror", "-c", os.path.join(csrc, "scan.hip"), "-o", str(tmp_path / "scan.o")],
-                ["gcc", "-std=c99"] + san + ["-Wall", "-Werror", "-I", inc, "-c", os.path.join(H.ROOT, "tests", "frame_scan_c", "scan_main.c"),
-                                             "-o", str(tmp_path / "main.o")],
-                ["g++"] + san + [str(tmp_path / "main.o"), str(tmp_path / "scan.o"), "-o", exe]):
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+    exe = H.build_sanitised([os.path.join(H.ROOT, "tests", "frame_scan_c", "scan_main.c"), os.path.join(H.CSRC, "scan.hip")], str(tmp_path / "scan_main"), includes=[os.path.join(H.ROOT, "include")])
     dirty, _ = M.dirty_stream()
     fr = M.frame(1, 21, 0)
     for i, data in enumerate((dirty, dirty[1:], fr[:0], fr[:7], fr[:8], fr[:-1], fr, np.concatenate([M.garbage(50, 1), fr[:8]]))):

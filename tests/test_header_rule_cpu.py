@@ -27,11 +27,8 @@ def program(tmp_path_factory):
     """tests/header_rule_c/main.cpp built as tests/frame_scan_c is -> (sizes, sizes_le, fscod, halfrate, each [4][256][256]
     indexed [sync word][byte 4][byte 5]; lfeon position per acmod)"""
     tmp = tmp_path_factory.mktemp("header_rule")
-    csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
     exe = str(tmp / "header_rule")
-    r = subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1", "-Wall", "-Werror",
-                        "-I", csrc, os.path.join(H.ROOT, "tests", "header_rule_c", "main.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.build_sanitised([os.path.join(H.ROOT, "tests", "header_rule_c", "main.cpp")], exe, includes=[H.CSRC])
     r = subprocess.run([exe, "20250"], capture_output=True, text=True)
     assert r.returncode == 0 and r.stderr == "", r.stderr
     v = np.array(r.stdout.split(), np.int64)

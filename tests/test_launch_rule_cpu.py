@@ -20,10 +20,7 @@ HERE = os.path.join(H.ROOT, "tests", "launch_rule_c")
 def program(tmp_path_factory):
     """main.cpp built as tests/header_rule_c is -> run(mode): the lines it prints"""
     exe = str(tmp_path_factory.mktemp("launch_rule") / "launch_rule")
-    csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
-    r = subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1", "-Wall", "-Werror",
-                        "-I", csrc, os.path.join(HERE, "main.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.build_sanitised([os.path.join(HERE, "main.cpp")], exe, includes=[H.CSRC])
 
     def run(mode):
         r = subprocess.run([exe, mode], capture_output=True, text=True)

@@ -199,16 +199,7 @@ def test_host_twins_under_the_sanitisers(tmp_path):
     """tests/limit_c/limit_main.c with a host-only translation of csrc/limit.hip (limit_rule.h's limiter and read-out), both
     built with -fsanitize=address,undefined and run on the CPU: the model's outputs and states, out of place in two calls and
     in place in one, and not a word from either sanitiser"""
-    csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
-    inc = os.path.join(H.ROOT, "include")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"]
-    exe = str(tmp_path / "limit_main")
-    for cmd in (["g++", "-std=c++17", "-x", "c++"] + san + ["-Wall", "-Werror", "-c", os.path.join(csrc, "limit.hip"), "-o", str(tmp_path / "limit.o")],
-                ["gcc", "-std=c99"] + san + ["-Wall", "-Werror", "-I", inc, "-c", os.path.join(H.ROOT, "tests", "limit_c", "limit_main.c"),
-                                             "-o", str(tmp_path / "main.o")],
-                ["g++"] + san + [str(tmp_path / "main.o"), str(tmp_path / "limit.o"), "-o", exe]):
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+    exe = H.build_sanitised([os.path.join(H.ROOT, "tests", "limit_c", "limit_main.c"), os.path.join(H.CSRC, "limit.hip")], str(tmp_path / "limit_main"), includes=[os.path.join(H.ROOT, "include")])
     cases = _host_cases()[::3] + _host_cases()[-3:]
     for i, (name, roles, pcm) in enumerate(cases):
         C, R = ((C1, 3496), (C6, 1), (1, 1 << 20), (1 << 28, 70000))[i % 4]

@@ -200,16 +200,7 @@ def test_host_read_out_against_the_model():
 def test_host_read_out_under_the_sanitisers(tmp_path):
     """tests/loudness_c/loudness_main.c with a host-only translation of csrc/loudness.hip (loudness_rule.h's read-out), both
     built with -fsanitize=address,undefined and run on the CPU: the model's results, and not a word from either sanitiser"""
-    csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
-    inc = os.path.join(H.ROOT, "include")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"]
-    exe = str(tmp_path / "loudness_main")
-    for cmd in (["g++", "-std=c++17", "-x", "c++"] + san + ["-Wall", "-Werror", "-c", os.path.join(csrc, "loudness.hip"), "-o", str(tmp_path / "loudness.o")],
-                ["gcc", "-std=c99"] + san + ["-Wall", "-Werror", "-I", inc, "-c", os.path.join(H.ROOT, "tests", "loudness_c", "loudness_main.c"),
-                                             "-o", str(tmp_path / "main.o")],
-                ["g++"] + san + [str(tmp_path / "main.o"), str(tmp_path / "loudness.o"), "-o", exe]):
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+    exe = H.build_sanitised([os.path.join(H.ROOT, "tests", "loudness_c", "loudness_main.c"), os.path.join(H.CSRC, "loudness.hip")], str(tmp_path / "loudness_main"), includes=[os.path.join(H.ROOT, "include")])
     for i, (name, m) in enumerate(_states()):
         path = tmp_path / ("state%d.bin" % i)
         path.write_bytes(m.record().tobytes())

@@ -192,16 +192,7 @@ def test_host_read_out_under_the_sanitisers(tmp_path):
     """tests/loudness_range_c/range_main.c with a host-only translation of csrc/loudness.hip, both built with
     -fsanitize=address,undefined and run on the CPU over every state above, the all-0xff garbage among them, from stdin: the
     model's results, and not a word from either sanitiser"""
-    csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
-    inc = os.path.join(H.ROOT, "include")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"]
-    exe = str(tmp_path / "range_main")
-    for cmd in (["g++", "-std=c++17", "-x", "c++"] + san + ["-Wall", "-Werror", "-c", os.path.join(csrc, "loudness.hip"), "-o", str(tmp_path / "loudness.o")],
-                ["gcc", "-std=c99"] + san + ["-Wall", "-Werror", "-I", inc, "-c", os.path.join(H.ROOT, "tests", "loudness_range_c", "range_main.c"),
-                                             "-o", str(tmp_path / "main.o")],
-                ["g++"] + san + [str(tmp_path / "main.o"), str(tmp_path / "loudness.o"), "-o", exe]):
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+    exe = H.build_sanitised([os.path.join(H.ROOT, "tests", "loudness_range_c", "range_main.c"), os.path.join(H.CSRC, "loudness.hip")], str(tmp_path / "range_main"), includes=[os.path.join(H.ROOT, "include")])
     states = _states()
     r = subprocess.run([exe], input=b"".join(rec.tobytes() for _, rec in states), capture_output=True)
     assert r.returncode == 0 and r.stderr == b"", (r.stdout, r.stderr)

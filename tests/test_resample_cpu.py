@@ -244,16 +244,7 @@ def test_host_twin_under_the_sanitisers(tmp_path):
     """tests/resample_c/resample_main.c with a host-only translation of csrc/resample.hip (resample_rule.h's table builder, plan
     and converter), both built with -fsanitize=address,undefined and run on the CPU as a program of its own: the model's
     outputs and states, in two calls and in one, a refused call, and not a word from either sanitiser"""
-    csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
-    inc = os.path.join(H.ROOT, "include")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"]
-    exe = str(tmp_path / "resample_main")
-    for cmd in (["g++", "-std=c++17", "-x", "c++"] + san + ["-Wall", "-Werror", "-c", os.path.join(csrc, "resample.hip"), "-o", str(tmp_path / "resample.o")],
-                ["gcc", "-std=c99"] + san + ["-Wall", "-Werror", "-I", inc, "-c", os.path.join(H.ROOT, "tests", "resample_c", "resample_main.c"),
-                                             "-o", str(tmp_path / "main.o")],
-                ["g++"] + san + [str(tmp_path / "main.o"), str(tmp_path / "resample.o"), "-o", exe]):
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+    exe = H.build_sanitised([os.path.join(H.ROOT, "tests", "resample_c", "resample_main.c"), os.path.join(H.CSRC, "resample.hip")], str(tmp_path / "resample_main"), includes=[os.path.join(H.ROOT, "include")])
     for i, pair in enumerate(R.PAIRS):
         ch = (6, 2, 1, 3, 5, 4)[i]
         frames = (3, 2, 1, 3, 2, 1)[i]

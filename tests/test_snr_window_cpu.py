@@ -19,11 +19,8 @@ FRAMES = 40
 @pytest.fixture(scope="module")
 def program_output(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("snr_window")
-    csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
     exe = str(tmp / "snr_window")
-    r = subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1", "-Wall", "-Werror",
-                        "-I", csrc, os.path.join(H.ROOT, "tests", "snr_window_c", "main.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.build_sanitised([os.path.join(H.ROOT, "tests", "snr_window_c", "main.cpp")], exe, includes=[H.CSRC])
     r = subprocess.run([exe, "20251", str(FRAMES)], capture_output=True, text=True)
     assert r.returncode == 0 and r.stderr == "", r.stderr[-2000:]
     return r.stdout.splitlines()

@@ -19,11 +19,8 @@ FRAMES = 5 * 3 * 4 ** 5 + 2 ** 5 + 6 * 3 * 2
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("syn_images")
-    csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
     exe = str(tmp / "syn_images")
-    r = subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1", "-Wall", "-Werror",
-                        "-I", csrc, os.path.join(H.ROOT, "tests", "syn_images_c", "main.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.build_sanitised([os.path.join(H.ROOT, "tests", "syn_images_c", "main.cpp")], exe, includes=[H.CSRC])
     return exe
 
 

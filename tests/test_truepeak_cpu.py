@@ -210,16 +210,7 @@ def test_host_twins_under_the_sanitisers(tmp_path):
     """tests/truepeak_c/truepeak_main.c with a host-only translation of csrc/truepeak.hip (truepeak_rule.h's meter and
     read-out), both built with -fsanitize=address,undefined and run on the CPU: the model's states and results, and not a word
     from either sanitiser"""
-    csrc = os.path.join(H.ROOT, "ac-3-acm-codec_amd", "csrc")
-    inc = os.path.join(H.ROOT, "include")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"]
-    exe = str(tmp_path / "truepeak_main")
-    for cmd in (["g++", "-std=c++17", "-x", "c++"] + san + ["-Wall", "-Werror", "-c", os.path.join(csrc, "truepeak.hip"), "-o", str(tmp_path / "truepeak.o")],
-                ["gcc", "-std=c99"] + san + ["-Wall", "-Werror", "-I", inc, "-c", os.path.join(H.ROOT, "tests", "truepeak_c", "truepeak_main.c"),
-                                             "-o", str(tmp_path / "main.o")],
-                ["g++"] + san + [str(tmp_path / "main.o"), str(tmp_path / "truepeak.o"), "-o", exe]):
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+    exe = H.build_sanitised([os.path.join(H.ROOT, "tests", "truepeak_c", "truepeak_main.c"), os.path.join(H.CSRC, "truepeak.hip")], str(tmp_path / "truepeak_main"), includes=[os.path.join(H.ROOT, "include")])
     for i, (name, roles, pcm) in enumerate(_cases()):
         path = tmp_path / ("pcm%d.bin" % i)
         path.write_bytes(pcm.astype("<i2").tobytes())
